@@ -14,6 +14,8 @@ Default run (no --workload) = the HEADLINE of BASELINE.json's metric ("dog LMS +
     dog and honeybee-MST++, PCIe-inclusive frames/s for the whole job (strong scaling: compare across --gpus).
 --workload NAME times that one workload instead (all species, spectral config 5, ...); the UV species run a step's frames on up to
 four streams, one recorded plan each (AVX_BENCH_UV_LANES), mantis through avx_mantis_u8_batch's lanes.
+--dump-outputs DIR writes what the timed workload's last step computed (Workload.outputs) as DIR/<name>.npy; the inputs are seeded
+synthetic frames (and, for MST++, seeded weights), so two builds run with the same arguments can be compared output for output.
 
 --gpus N: one process per GPU.  Launched by torchrun (WORLD_SIZE set) this process IS a rank; launched bare with N > 1 it
 becomes a launcher: it touches no GPU (no torch / HIP import), starts N rank processes of this file with RANK / LOCAL_RANK /
@@ -77,6 +79,8 @@ MSTPP_FLOP_PER_PX = 703.4e3  # 2 x 351.7 kMAC/px (23.05 GMAC at 256
 #   scale, half a conversion; gamma / beta live in the first GEMM's weights since round 3: 5 before)
 VALU_MIN_LANE_INSTR_PER_PX = 2808 * 4 + 1404 + 312 * 3.5
 VALU_PEAK_LANE_INSTR_PER_S = 1024 * 16 * 2.4e9  # 1,024 SIMDs x 16 lanes per clock (a wave64 instruction holds its SIMD for 4 cycles) x 2.4 GHz
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: bytes of all .npy payloads together (under 64 MB)
+DUMP_SEED = 0  # --dump-outputs: the flat indices kept when the outputs are larger than that
 
 
 def log(*a):
@@ -121,7 +125,35 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for each CPU baseline sample")
     ap.add_argument("--stream-frames", type=int, default=256, help="frames of the config-4 4K stream (whole job)")
     ap.add_argument("--dry-run", action="store_true", help="ranks rendezvous over gloo and report, no GPU work (launcher test on a CPU box)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy in float32 (rank 0; outputs over "
+                         f"{DUMP_MAX_BYTES >> 20} MiB in all: the same seeded sample of flat indices per array, see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def dump_outputs(outputs, out_dir, max_bytes=DUMP_MAX_BYTES, seed=DUMP_SEED):
+    """Write {name: array} as out_dir/<name>.npy, float32 (float64 stays float64).  When the arrays hold more than `max_bytes` at that
+    width, each array keeps the same fraction of its elements, flattened: the sorted distinct indices of a draw from default_rng(seed)
+    over its flat indices, so runs with the same arguments write the same positions.  No GPU work; returns
+    {name: [shape, elements written]}."""
+    import numpy as np
+
+    width = {k: 8 if a.dtype == np.float64 else 4 for k, a in outputs.items()}
+    total = sum(a.size * width[k] for k, a in outputs.items())
+    frac = min(1.0, max_bytes / total) if total else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for k, a in outputs.items():
+        a = np.ascontiguousarray(a)
+        if frac < 1.0:
+            a = a.reshape(-1)[np.unique(np.random.default_rng(seed).integers(0, a.size, int(a.size * frac)))]
+        a = a.astype(np.float64 if width[k] == 8 else np.float32)
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        written[k] = [list(outputs[k].shape), int(a.size)]
+    return written
 
 
 # ------------------------------------------------------------------------------------------ launcher (no GPU calls) ----
@@ -346,6 +378,25 @@ class Workload:
         self.elapsed_local = time.perf_counter() - t0
         elapsed = env.max_over_ranks(self.elapsed_local)
         return elapsed, ev_ms
+
+    def outputs(self):
+        """What the timed path computed in its last step, as its caller receives it: {name: host array}.  Frames are uint8 HxWx3, one per
+        frame of the step; the UV species' plans hold one frame per lane (every lane runs the same input), the spectral path one set of K
+        float32 planes per slot."""
+        np, ctx, B, H, W = self.np, self.ctx, self.B, self.H, self.W
+        ctx.device_sync()
+        if self.mst is not None:
+            import torch
+
+            torch.cuda.synchronize()
+            return {"out": self.t_out.cpu().numpy()}
+        if self.spectral:
+            return {"planes": ctx.download(self.d_planes, (min(B, 4), self.Kp, H, W), np.float32)}
+        if self.uvsp and self.species != "mantis":
+            return {nm: np.stack([ctx.download(getattr(be, "d_" + nm), (H, W, 3), np.uint8) for be in self.sop.plans]) for nm in ("base", "out")}
+        if self.species == "mantis":
+            return {"base": ctx.download(self.d_base, self.batch.shape, np.uint8), "out": ctx.download(self.d_out, self.batch.shape, np.uint8)}
+        return {"out": ctx.download(self.d_out, self.batch.shape, np.uint8)}
 
     def steps_for(self, seconds, probe=3):
         """How many steps fill `seconds` of timed region (one short untimed probe)."""
@@ -694,6 +745,8 @@ def worker(args):
     steps, warmup = args.steps, args.warmup
     elapsed, ev_ms = wl.time(steps, warmup, args.ramp_ms)
     elapsed_local = wl.elapsed_local
+    if args.dump_outputs and env.rank == 0:  # before parity(), which runs the MST++ route once more into the same output
+        log(f"bench.py: outputs of the last timed step -> {args.dump_outputs}: {dump_outputs(wl.outputs(), args.dump_outputs)}")
     rep = wl.report(steps, warmup, elapsed, ev_ms)
     result = {
         "metric": "megapixels/sec per-frame pipeline",

@@ -565,6 +565,15 @@ def von_kries_gray_world(U, B, G, eps: float = EPS_DEFAULT):
     return U / max(U.mean(), eps), B / max(B.mean(), eps), G / max(G.mean(), eps)
 
 
+def _lobe_exp(x):
+    """The float32 exp of the wavelength lobes (torch.exp, as the reference calls it).  Its last bit is the host's: torch-CPU hands it
+    to MKL's vector math, whose code path depends on the CPU (another one on non-Intel processors), so a bit-exact comparison with
+    golden vectors recorded elsewhere swaps in the values recorded with them (tests/conftest.py::golden_lobe_exp)."""
+    import torch
+
+    return torch.exp(x)
+
+
 def classic_rgb_to_hsi_lobes(frame: np.ndarray, wavelengths: np.ndarray) -> np.ndarray:
     """ml/classic_rgb_to_hsi/classic_rgb_to_hsi.py:47-82 (the branch a GPU box runs, F5).
 
@@ -580,15 +589,15 @@ def classic_rgb_to_hsi_lobes(frame: np.ndarray, wavelengths: np.ndarray) -> np.n
     wl = torch.as_tensor(wavelengths.astype(np.float32)).view(-1, 1, 1)
     cR, cG, cB = 610.0, 545.0, 460.0
     sR, sG, sB = 60.0, 60.0, 55.0
-    gR = torch.exp(-0.5 * ((wl - cR) / sR) ** 2)
-    gG = torch.exp(-0.5 * ((wl - cG) / sG) ** 2)
-    gB = torch.exp(-0.5 * ((wl - cB) / sB) ** 2)
+    gR = _lobe_exp(-0.5 * ((wl - cR) / sR) ** 2)
+    gG = _lobe_exp(-0.5 * ((wl - cG) / sG) ** 2)
+    gB = _lobe_exp(-0.5 * ((wl - cB) / sB) ** 2)
     spec = gR * R.unsqueeze(0) + gG * G.unsqueeze(0) + gB * Bc.unsqueeze(0)
     w1 = wl.squeeze()
     denom = (
-        torch.exp(-0.5 * ((w1 - cR) / sR) ** 2)
-        + torch.exp(-0.5 * ((w1 - cG) / sG) ** 2)
-        + torch.exp(-0.5 * ((w1 - cB) ** 2) / (sB**2))
+        _lobe_exp(-0.5 * ((w1 - cR) / sR) ** 2)
+        + _lobe_exp(-0.5 * ((w1 - cG) / sG) ** 2)
+        + _lobe_exp(-0.5 * ((w1 - cB) ** 2) / (sB**2))
     ).mean()
     spec = spec / (denom + 1e-8)
     spec = spec.clamp_min(0.0).permute(1, 2, 0).contiguous()

@@ -333,3 +333,20 @@ def test_image_renderer_surface(tmp_path):
     r.close()
     with pytest.raises(NotImplementedError):
         ImageRenderer(show_window=True).render(a)
+
+
+def test_bench_dump_outputs_is_the_timed_path(tmp_path, oracle):
+    """bench.py --dump-outputs: the result line counts exactly --steps timed steps and reports ms_per_step, and the dump is the timed
+    step's output (dog, one 1080p frame: bit-exact against the oracle on the same seeded frame)."""
+    from animal_vision_amd.synthetic import noise_frame
+
+    d = str(tmp_path / "dump")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "dog_1080p", "--batch", "1", "--steps", "4", "--warmup", "1",
+                          "--ramp-ms", "0", "--no-cpu-baseline", "--no-e2e", "--dump-outputs", d], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert r["steps"] == 4 and r["ms_per_step"] > 0 and r["parity_checked"] is True
+    got = np.load(os.path.join(d, "out.npy"))
+    assert got.dtype == np.float32 and got.shape == (1, 1080, 1920, 3)
+    _, want = oracle.dichromat_visualize(oracle.DICHROMATS["dog"], noise_frame(0, 1080, 1920))
+    assert np.array_equal(got[0], want.astype(np.float32))

@@ -119,3 +119,30 @@ def test_bench_ranks_fail_loudly_without_a_gpu():
     assert out.returncode != 0
     assert not [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert "rank exit codes" in out.stderr
+
+
+def test_bench_dump_outputs_is_seeded_and_capped(tmp_path):
+    """bench.py --dump-outputs without a GPU: outputs that fit are written whole in float32; larger ones become the same seeded sample of
+    flat indices on every run, under the byte cap; float64 stays float64."""
+    import bench
+
+    rng = np.random.default_rng(7)
+    small = {"out": rng.integers(0, 256, (2, 6, 5, 3), dtype=np.uint8), "planes": rng.random((3, 4, 4)).astype(np.float64)}
+    bench.dump_outputs(small, str(tmp_path / "a"))
+    got = np.load(tmp_path / "a" / "out.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small["out"])
+    assert np.load(tmp_path / "a" / "planes.npy").dtype == np.float64
+    big = {"base": rng.integers(0, 256, (4, 100, 90, 3), dtype=np.uint8), "out": rng.integers(0, 256, (4, 100, 90, 3), dtype=np.uint8)}
+    cap = 40_000
+    for d in ("b", "c"):
+        info = bench.dump_outputs(big, str(tmp_path / d), max_bytes=cap)
+        assert sum(n for _, n in info.values()) * 4 <= cap and info["out"][0] == [4, 100, 90, 3]
+    for k in big:
+        b, c = np.load(tmp_path / "b" / f"{k}.npy"), np.load(tmp_path / "c" / f"{k}.npy")
+        assert b.dtype == np.float32 and b.ndim == 1 and b.size > 4000 and np.array_equal(b, c)
+        assert set(np.unique(b)) <= set(np.unique(big[k]).astype(np.float32))
+
+
+def test_bench_rejects_zero_steps():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert out.returncode != 0 and "--steps" in out.stderr

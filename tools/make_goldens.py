@@ -294,6 +294,30 @@ def g_lobes():
     save("lobes", **out)
 
 
+def g_lobe_exp():
+    """The float32 exp of every wavelength-lobe exponent of the grids above (oracle/cpu_ref.py::_lobe_exp), as torch-CPU computes it
+    on this host: its last bit depends on the host's vector math library, so the oracle is pinned bit for bit with these values
+    wherever the tests run.  x / exp: float32, the values the calls returned, x unique by bit pattern."""
+    seen = {}
+    orig = O._lobe_exp
+
+    def rec(x):
+        y = orig(x)
+        for a, b in zip(x.reshape(-1).numpy().view(np.uint32).tolist(), y.reshape(-1).numpy().view(np.uint32).tolist()):
+            assert seen.setdefault(a, b) == b, "exp of one argument differs between calls"
+        return y
+
+    O._lobe_exp = rec
+    try:
+        for lam in (np.linspace(400.0, 700.0, 31, dtype=np.float32), np.linspace(300.0, 700.0, 81, dtype=np.float32),
+                    np.linspace(320.0, 700.0, 129)):
+            O.classic_rgb_to_hsi_lobes(np.zeros((1, 1, 3), np.float32), lam)
+    finally:
+        O._lobe_exp = orig
+    x = np.array(sorted(seen), np.uint32)
+    save("lobe_exp", x=x.view(np.float32), exp=np.array([seen[k] for k in x.tolist()], np.uint32).view(np.float32))
+
+
 def g_honeybee():
     """a12-a21 end to end: the reference HoneyBee class, every mapping mode."""
     _ref_classic()
@@ -590,7 +614,7 @@ def g_uv_species():
 
 
 GENERATORS = {"srgb_tables": g_srgb_tables, "matrices": g_matrices, "dichromat": g_dichromat, "bloom_rod": g_bloom_rod, "uv": g_uv,
-              "lobes": g_lobes, "honeybee": g_honeybee, "mstpp": g_mstpp, "mstpp_large": g_mstpp_large, "mstpp_4k": g_mstpp_4k, "geometry": g_geometry, "mantis": g_mantis, "uv_species": g_uv_species}
+              "lobes": g_lobes, "lobe_exp": g_lobe_exp, "honeybee": g_honeybee, "mstpp": g_mstpp, "mstpp_large": g_mstpp_large, "mstpp_4k": g_mstpp_4k, "geometry": g_geometry, "mantis": g_mantis, "uv_species": g_uv_species}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()

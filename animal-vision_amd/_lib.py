@@ -138,6 +138,21 @@ class BandStackDesc(ctypes.Structure):
     ]
 
 
+class GalleryTile(ctypes.Structure):
+    """avx_gallery_tile (include/avx.h)."""
+
+    _fields_ = [
+        ("src", ctypes.c_void_p),
+        ("dtype", ctypes.c_int32),
+        ("H", ctypes.c_int32),
+        ("W", ctypes.c_int32),
+        ("h", ctypes.c_int32),
+        ("w", ctypes.c_int32),
+        ("seg_offset", ctypes.c_int32),
+        ("seg_count", ctypes.c_int32),
+    ]
+
+
 class EwInsn(ctypes.Structure):
     _fields_ = [("op", ctypes.c_uint8), ("dst", ctypes.c_uint8), ("a", ctypes.c_uint8), ("b", ctypes.c_uint8), ("imm", ctypes.c_uint32)]
 
@@ -248,6 +263,7 @@ _SIGS = {
     "avx_binocular_warp_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "avx_split_compose_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "avx_draw_label_u8": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_int), _fp, _i, ctypes.c_float, ctypes.c_float, _i, _vp]),
+    "avx_gallery_compose_u8": (_i, [_vp, ctypes.POINTER(GalleryTile), _i, _fp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "dichromat_common.h"
+#include "resize_common.h"
 #include "stack_up.h"
 
 using namespace avxk;
@@ -20,9 +21,7 @@ namespace {
 
 constexpr int kGT = 256;
 
-struct AxisLin { int* ofs; float* f; int dmax; };
-struct AxisCub { int* idx; float* a; };                 // [d][4]
-struct AxisArea { int* start; int* cnt; float* alpha; int maxcnt; };  // alpha [d][maxcnt]
+struct AxisCub { int* idx; float* a; };                 // [d][4]   (AxisLin, AxisArea: resize_common.h)
 
 // One thread per DESTINATION PIXEL (all C channels: the weights and the four source addresses are shared; 16-byte loads / stores when C is a multiple of 4 and the
 // pointers allow).  Round 2's form was one thread per output element with three 64-bit divisions each (i % C, (i / C) % Wd, i / (C Wd): ~300 vector instructions
@@ -63,16 +62,7 @@ __global__ __launch_bounds__(kGT) void k_resize_linear_u8(const uint8_t* __restr
     for (size_t i = (size_t)blockIdx.x * kGT + threadIdx.x; i < total; i += (size_t)gridDim.x * kGT) {
         const int c = (int)(i % C);
         const int x = (int)((i / C) % Wd), y = (int)(i / ((size_t)C * Wd));
-        const int sx = ax.ofs[x], sy0 = ay.ofs[y], sy1 = sy0 + 1 < H ? sy0 + 1 : sy0;
-        const int a0 = __float2int_rn((1.f - ax.f[x]) * 2048.f), a1 = __float2int_rn(ax.f[x] * 2048.f);  // saturate_cast<short>: |v| <= 2048
-        const int b0 = __float2int_rn((1.f - ay.f[y]) * 2048.f), b1 = __float2int_rn(ay.f[y] * 2048.f);
-        const uint8_t* S0 = src + ((size_t)sy0 * W + sx) * C + c;
-        const uint8_t* S1 = src + ((size_t)sy1 * W + sx) * C + c;
-        int r0, r1;
-        if (x < ax.dmax) { r0 = S0[0] * a0 + S0[C] * a1; r1 = S1[0] * a0 + S1[C] * a1; }
-        else { r0 = S0[0] * 2048; r1 = S1[0] * 2048; }
-        int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-        dst[i] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+        AVX_LINEAR_U8(dst[i], src, H, W, C, c, x, y, ax, ay);  // resize_common.h
     }
 }
 
@@ -113,12 +103,7 @@ __global__ __launch_bounds__(kGT) void k_panorama_cubic_x(const float* __restric
     }
 }
 
-// cv::saturate_cast<uchar>(float): cvRound (round half to even), clamped
-__device__ __forceinline__ void put_area(float* d, float v) { *d = v; }
-__device__ __forceinline__ void put_area(uint8_t* d, float v) { const float r = rintf(v); *d = (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r)); }
-
-// T = float or uint8_t (cv::resize INTER_AREA of a uint8 image: resizeAreaFast_<uchar, int> sums integers -- exact in float32
-// below 2^24 -- and stores saturate_cast<uchar>(sum * scale); its 2x2 special case rounds (sum + 2) >> 2 instead)
+// cv::resize INTER_AREA (resize_common.h holds the arithmetic: AVX_AREA_FAST, area_sum)
 template <typename T>
 __global__ __launch_bounds__(kGT) void k_resize_area_fast_f32(const T* __restrict__ src, int H, int W, int C, T* __restrict__ dst, int Hd, int Wd,
                                                               int isx, int isy) {
@@ -128,14 +113,7 @@ __global__ __launch_bounds__(kGT) void k_resize_area_fast_f32(const T* __restric
     for (size_t i = (size_t)blockIdx.x * kGT + threadIdx.x; i < total; i += (size_t)gridDim.x * kGT) {
         const int c = (int)(i % C);
         const int x = (int)((i / C) % Wd), y = (int)(i / ((size_t)C * Wd));
-        const T* S = src + ((size_t)(y * isy) * W + (size_t)x * isx) * C + c;
-        auto at = [&](int k) { const int sy = k / isx, sx = k - sy * isx; return (float)S[((size_t)sy * W + sx) * C]; };
-        float sum = 0;
-        int k = 0;
-        for (; k <= area - 4; k += 4) sum += at(k) + at(k + 1) + at(k + 2) + at(k + 3);  // resizeAreaFast_: groups of four
-        for (; k < area; ++k) sum += at(k);
-        if (sizeof(T) == 1 && isx == 2 && isy == 2) put_area(dst + i, (float)(((int)sum + 2) >> 2));  // ResizeAreaFastVec, 8-bit 2x2
-        else put_area(dst + i, sum * scale);
+        AVX_AREA_FAST(T, dst + i, src, W, C, c, x, y, isx, isy, area, scale);  // resize_common.h
     }
 }
 
@@ -146,17 +124,7 @@ __global__ __launch_bounds__(kGT) void k_resize_area_f32(const T* __restrict__ s
     for (size_t i = (size_t)blockIdx.x * kGT + threadIdx.x; i < total; i += (size_t)gridDim.x * kGT) {
         const int c = (int)(i % C);
         const int x = (int)((i / C) % Wd), y = (int)(i / ((size_t)C * Wd));
-        const int x0 = ax.start[x], nx = ax.cnt[x], y0 = ay.start[y], ny = ay.cnt[y];
-        const float* al = ax.alpha + (size_t)x * ax.maxcnt;
-        const float* be = ay.alpha + (size_t)y * ay.maxcnt;
-        float sum = 0.f;
-        for (int j = 0; j < ny; ++j) {
-            const T* S = src + ((size_t)(y0 + j) * W + x0) * C + c;
-            float buf = 0.f;
-            for (int k = 0; k < nx; ++k) buf += (float)S[(size_t)k * C] * al[k];  // ResizeArea_Invoker: buf[dx] += S*alpha
-            sum = j == 0 ? be[j] * buf : sum + be[j] * buf;               // first row of a dy starts the sum
-        }
-        put_area(dst + i, sum);
+        put_area(dst + i, area_sum(src, W, C, c, x, y, ax, ay));
     }
 }
 
@@ -281,21 +249,7 @@ __global__ __launch_bounds__(kGT) void k_sobel3(const float* __restrict__ src, i
     }
 }
 
-// ---- host-side coefficient tables (same construction as OpenCV's resizeGeneric_ / computeResizeAreaTab) ----
-struct HostLin { std::vector<int> ofs; std::vector<float> f; int dmax; };
-HostLin host_lin(int ssize, int dsize) {
-    HostLin t; t.ofs.resize(dsize); t.f.resize(dsize); t.dmax = dsize;
-    const double scale = 1.0 / ((double)dsize / ssize);
-    for (int d = 0; d < dsize; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)std::floor(f);
-        f -= s;
-        if (s < 0) { f = 0; s = 0; }
-        if (s + 1 >= ssize) { if (t.dmax > d) t.dmax = d; if (s >= ssize - 1) { f = 0; s = ssize - 1; } }
-        t.ofs[d] = s; t.f[d] = f;
-    }
-    return t;
-}
+// ---- host-side coefficient tables (same construction as OpenCV's resizeGeneric_; host_lin / host_area: resize_common.h) ----
 void host_cubic(int ssize, int dsize, std::vector<int>& idx, std::vector<float>& a) {
     idx.resize((size_t)dsize * 4); a.resize((size_t)dsize * 4);
     const double scale = 1.0 / ((double)dsize / ssize);
@@ -312,29 +266,6 @@ void host_cubic(int ssize, int dsize, std::vector<int>& idx, std::vector<float>&
         for (int k = 0; k < 4; ++k) { int i = s - 1 + k; idx[(size_t)d * 4 + k] = i < 0 ? 0 : (i >= ssize ? ssize - 1 : i); }
     }
 }
-void host_area(int ssize, int dsize, std::vector<int>& start, std::vector<int>& cnt, std::vector<float>& alpha, int& maxcnt) {
-    const double scale = (double)ssize / dsize;
-    std::vector<std::vector<std::pair<int, float>>> ent(dsize);
-    maxcnt = 1;
-    for (int dx = 0; dx < dsize; ++dx) {
-        const double fsx1 = dx * scale, fsx2 = fsx1 + scale;
-        const double cell = std::fmin(scale, ssize - fsx1);
-        int sx1 = (int)std::ceil(fsx1), sx2 = (int)std::floor(fsx2);
-        sx2 = sx2 < ssize - 1 ? sx2 : ssize - 1;
-        sx1 = sx1 < sx2 ? sx1 : sx2;
-        if (sx1 - fsx1 > 1e-3) ent[dx].push_back({sx1 - 1, (float)((sx1 - fsx1) / cell)});
-        for (int sx = sx1; sx < sx2; ++sx) ent[dx].push_back({sx, (float)(1.0 / cell)});
-        if (fsx2 - sx2 > 1e-3) ent[dx].push_back({sx2, (float)(std::fmin(std::fmin(fsx2 - sx2, 1.), cell) / cell)});
-        if ((int)ent[dx].size() > maxcnt) maxcnt = (int)ent[dx].size();
-    }
-    start.assign(dsize, 0); cnt.assign(dsize, 0); alpha.assign((size_t)dsize * maxcnt, 0.f);
-    for (int dx = 0; dx < dsize; ++dx) {
-        cnt[dx] = (int)ent[dx].size();
-        start[dx] = cnt[dx] ? ent[dx][0].first : 0;
-        for (int k = 0; k < cnt[dx]; ++k) alpha[(size_t)dx * maxcnt + k] = ent[dx][k].second;  // entries are consecutive source indices
-    }
-}
-
 int grid_for(avx_ctx* ctx, size_t items) {
     const size_t want = (items + kGT - 1) / kGT, cap = (size_t)ctx->num_cus * 16;
     return (int)(want < cap ? (want ? want : 1) : cap);

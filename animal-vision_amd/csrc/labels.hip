@@ -9,6 +9,7 @@
 // segment, 0, 1), round caps and joins -- not OpenCV's fixed-point LINE_AA scan converter: label pixels are PARITY UNPINNED
 // against OpenCV (it is not installed anywhere in the pipeline); they are bit-identical to oracle/cpu_ref.draw_label.
 #include "avx_internal.h"
+#include "label_common.h"
 
 namespace {
 
@@ -24,38 +25,16 @@ struct LabelArgs {
     float half_outline, half_text;  // thickness / 2 of the black outline pass and of the white pass
 };
 
-__device__ __forceinline__ float cover(float d, float half_t) {
-    const float c = half_t + 0.5f - d;
-    return c < 0.f ? 0.f : (c > 1.f ? 1.f : c);
-}
-
 __global__ __launch_bounds__(kLT) void k_draw_label(LabelArgs a) {
     const int rw = a.rx1 - a.rx0 + 1, rh = a.ry1 - a.ry0 + 1;
     for (int i = blockIdx.x * kLT + threadIdx.x; i < rw * rh; i += gridDim.x * kLT) {
         const int x = a.rx0 + i % rw, y = a.ry0 + i / rw;
-        float d2 = 3.0e38f;
-        const float px = (float)x, py = (float)y;
-        for (int s = 0; s < a.nseg; ++s) {
-            const float* g = a.seg + 6 * s;
-            const float qx = px - g[0], qy = py - g[1];
-            float t = (qx * g[2] + qy * g[3]) * g[4];
-            t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-            const float ex = qx - t * g[2], ey = qy - t * g[3];
-            const float e2 = ex * ex + ey * ey;
-            d2 = e2 < d2 ? e2 : d2;
-        }
-        const float d = __fsqrt_rn(d2);
+        const float d = label_dist(a.seg, a.nseg, (float)x, (float)y);  // label_common.h
         const float co = cover(d, a.half_outline), ct = cover(d, a.half_text);
         const bool inbox = x >= a.bx0 && x <= a.bx1 && y >= a.by0 && y <= a.by1;
         uint8_t* p = a.img + ((size_t)y * a.W + x) * 3;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float v = (float)p[c];
-            if (inbox) v = rintf(v * 0.4f);       // addWeighted(overlay, 0.6, img, 0.4): the overlay is black inside the box
-            v = rintf(v - v * co);                // black outline: v + (0 - v) * coverage
-            v = rintf(v + (255.f - v) * ct);      // white text
-            p[c] = (uint8_t)(v < 0.f ? 0.f : (v > 255.f ? 255.f : v));
-        }
+        for (int c = 0; c < 3; ++c) p[c] = label_blend(p[c], inbox, co, ct);
     }
 }
 

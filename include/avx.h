@@ -210,6 +210,26 @@ int avx_split_compose_u8(avx_ctx* ctx, const uint8_t* original_hwc, const uint8_
 int avx_draw_label_u8(avx_ctx* ctx, uint8_t* img_hwc, int H, int W, const int box_xyxy[4], const float* segments_host, int n_segments,
                       float outline_thickness, float text_thickness, int slot, void* stream);
 
+/* One tile of a labelled contact sheet (avx_gallery_compose_u8). */
+typedef struct avx_gallery_tile {
+    const void* src;           /* device, C-contiguous H x W x 3                                               */
+    int32_t dtype;             /* 0 float32 (clipped to [0, 1], then * 255 + 0.5, truncated), 2 uint8           */
+    int32_t H, W;              /* source size                                                                   */
+    int32_t h, w;              /* resized size: (H, W) = no resize; else INTER_AREA (INTER_LINEAR when enlarging) */
+    int32_t seg_offset, seg_count;  /* this tile's label: rows of the concatenated segment table               */
+} avx_gallery_tile;
+
+/* gallery_grid.build_labeled_grid (gallery_grid.py:8-106) after the host has laid it out, in ONE launch that writes every
+ * byte of the Hc x Wc x 3 uint8 canvas once.  Tile i sits in cell (i / cols, i % cols) of (max h + strip_h + pad) x
+ * (max w + pad) pixels, at (pad + row * cell_h, pad + col * cell_w); it is its source resized to h x w with avx_resize_hwc's
+ * arithmetic (cv2.resize INTER_AREA), a black strip of strip_h rows below it, and its label drawn on that (h + strip_h) x w
+ * image exactly as avx_draw_label_u8 draws it with the box (0, h, w - 1, h + strip_h - 1), outline 3 and text 1
+ * (_label_strip: the text is clipped to the tile).  The segments ({ax, ay, dx, dy, 1 / len^2, 0} rows, avx_draw_label_u8's
+ * format) are in the coordinates of that tile-plus-strip image, the label origin applied.  Every other byte is bg.  The
+ * canvas must not overlap a source. */
+int avx_gallery_compose_u8(avx_ctx* ctx, const avx_gallery_tile* tiles_host, int n_tiles, const float* segments_host, int n_segments,
+                           int strip_h, int pad, int cols, const int bg_rgb[3], uint8_t* canvas_hwc, int Hc, int Wc, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

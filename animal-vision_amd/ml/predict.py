@@ -6,6 +6,7 @@ contracts over every pixel of the frame, so the reference's OOM tile fallback (:
 needed nor equivalent."""
 from __future__ import annotations
 
+import weakref
 from typing import Optional, Tuple
 
 import numpy as np
@@ -45,6 +46,16 @@ def crop_pads(x: np.ndarray, pads) -> np.ndarray:
     return x[t : H - b if b else H, l : W - r if r else W, :]
 
 
+def check_bands(op) -> None:
+    """The cube MST++ hands over has the model's 31 bands (400-700 nm, padded to a 32-wide group): a HoneybeeOp built for another band
+    grid (HoneyBee(hsi_band_centers_nm=...)) would weight the wrong bands once padded to 32."""
+    from .mst_plus_plus import DIM
+
+    bands = op.weights.shape[1]
+    if bands != DIM:
+        raise ValueError(f"MST++ -> honeybee hand-off: the operator integrates {bands} bands, the network's cube has {DIM}")
+
+
 class MSTPlusPlusPredictor:
     """RGB frame -> 31-band cube on the GPU.  weights: None (seeded random init: no checkpoint ships with the
     reference and there is no network), a path to a local .pth, or a state_dict."""
@@ -67,7 +78,7 @@ class MSTPlusPlusPredictor:
             model.load_reference_state_dict(torch.load(weights, map_location="cpu", weights_only=True), strict=False)
         else:
             model.load_reference_state_dict(weights)
-        self._padded_ops = {}
+        self._padded_ops = weakref.WeakKeyDictionary()  # HoneybeeOp -> its clone padded to 32 bands; by identity, dropped with the op (an id() key outlives it)
         self.model = model.to(self.device).eval()
         if self.half:
             self.model = self.model.half()
@@ -106,14 +117,14 @@ class MSTPlusPlusPredictor:
 
     def honeybee_device(self, frame_dev, op32, d_out, stream_handle):
         """uint8 (H, W, 3) device frame -> honeybee frame in d_out (a DeviceBuffer of H*W*3 bytes), everything enqueued on torch's current stream
-        (= stream_handle).  Where the fused kernels apply, the 31-band cube is never written: conv_out's epilogue integrates it into the three catch
-        planes (+ their statistics) that the honeybee tail starts from; else the cube is handed over by data_ptr.  op32: the HoneybeeOp padded to
+        (= stream_handle).  Where the fused kernels apply and op32.takes_catches(), the 31-band cube is never written: conv_out's epilogue integrates it
+        into the three catch planes (+ their statistics) that the honeybee tail starts from; else the cube is handed over by data_ptr.  op32: the HoneybeeOp padded to
         32 bands (op.padded_clone(32)).  Returns the tensors that must stay alive until the stream has run (the caller records / keeps them)."""
         torch = self.torch
         H, W, _ = frame_dev.shape
         t, b, l, r = pad_amounts(H, W, self.stride)
         fuse = (self.half and frame_dev.dtype == torch.uint8 and self.stride % 8 == 0 and max(t, b) < H and max(l, r) < W and H > 1 and W > 1
-                and self.model.can_fuse_spectral() and op32.weights.shape == (3, 32))
+                and self.model.can_fuse_spectral() and op32.weights.shape == (3, 32) and op32.takes_catches())
         if fuse:
             planes, partials, n = self.model.forward_from_u8(frame_dev, (t, b, l, r), spectral=op32.weights)
             op32.run_device(None, d_out, 1, H, W, catches=(planes.data_ptr(), partials.data_ptr(), n), stream=stream_handle)
@@ -141,6 +152,7 @@ class MSTPlusPlusPredictor:
     def honeybee(self, image: np.ndarray, op) -> np.ndarray:
         """uint8 frame -> MST++ cube -> HoneybeeOp (csrc/uv.hip), the cube handed over on the device:
         the (H,W,32) channels-last tensor's data_ptr goes straight into avx_honeybee_u8 on torch's current stream."""
+        check_bands(op)
         torch = self.torch
         if self.device.type != "cuda":
             raise RuntimeError("MST++ -> libavx hand-off needs the GPU (no CPU path)")
@@ -151,9 +163,9 @@ class MSTPlusPlusPredictor:
         out = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
         ctx = op._ctx()
         stream = torch.cuda.current_stream().cuda_stream
-        op32 = self._padded_ops.get(id(op))
+        op32 = self._padded_ops.get(op)
         if op32 is None:
-            op32 = self._padded_ops.setdefault(id(op), op.padded_clone(32))  # the cube is channels-last, 31 bands in a 32-wide group
+            op32 = self._padded_ops.setdefault(op, op.padded_clone(32))  # the cube is channels-last, 31 bands in a 32-wide group
         keep = self.honeybee_device(frame, op32, DeviceBuffer(ctx, out.data_ptr(), out.numel(), owned=False), stream)
         res = out.cpu().numpy()  # synchronises: `keep` may go
         del keep
@@ -167,6 +179,7 @@ class MstHoneybeeStreamOp:
     stream for the duration of the call, and the cube goes from the network to csrc/uv.hip by data_ptr (no copy, no sync)."""
 
     def __init__(self, predictor: "MSTPlusPlusPredictor", bee_op, H: int, W: int, depth: int = 3):
+        check_bands(bee_op)
         torch = predictor.torch
         if predictor.device.type != "cuda":
             raise RuntimeError("MST++ -> libavx hand-off needs the GPU (no CPU path)")

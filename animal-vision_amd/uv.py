@@ -245,6 +245,12 @@ class HoneybeeOp:
             self.ctx = get_context()
         return self.ctx
 
+    def takes_catches(self) -> bool:
+        """Whether run_device(catches=...) (source 2: catch planes formed upstream, e.g. in MST++ conv_out's epilogue) applies to this
+        configuration: the tile schedule's mappings (not falsecolor_uv_mixed) and blur sizes (0, 1 or 3).  The same rule as
+        csrc/uv.hip:1778 (avx_honeybee_u8's source-2 check); every other configuration needs the cube (run_device(hsi_ptr=...))."""
+        return self.desc.mapping != _lib.AVX_MAP["falsecolor_uv_mixed"] and self.desc.blur_ksize in (0, 1, 3)
+
     def padded_clone(self, bands: int) -> "HoneybeeOp":
         """The same pipeline for a cube stored with `bands` >= B channels per pixel, the extra ones being padding
         (weights zero): what MSTPlusPlus.forward_nhwc emits (31 bands in a 32-wide, 64-byte-aligned group)."""

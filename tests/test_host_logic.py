@@ -157,6 +157,40 @@ def test_honeybee_constructor_surface():
         bee.visualize(np.zeros((4, 4), np.uint8))
 
 
+def test_honeybee_op_takes_catches_exactly_where_the_source_2_schedule_does():
+    """HoneybeeOp.takes_catches() (whether the MST++ route may hand the tail catch planes, avx_honeybee_u8 source 2) against the rule
+    avx_honeybee_u8 enforces: not falsecolor_uv_mixed (mapping 4), blur ksize 0, 1 or 3 -- i.e. sigma <= 1/3.  Built without a GPU."""
+    from animal_vision_amd.animals import HoneyBee
+
+    src = open(os.path.join(ROOT, "animal-vision_amd", "csrc", "uv.hip")).read()
+    assert re.search(r"d->source != 2 \|\| \(n_frames == 1 && d->mapping != 4 && !debug_planes && "
+                     r"\(d->blur_ksize == 0 \|\| d->blur_ksize == 1 \|\| d->blur_ksize == 3\)", src), "the C rule changed: update takes_catches()"
+    sigmas = (0.0, 0.1, 0.2, 1.0 / 3.0, 0.34, 0.5, 1.5)
+    ksizes = (0, 3, 3, 3, 5, 5, 11)
+    for mapping in av._lib.AVX_MAP:
+        for sigma, k in zip(sigmas, ksizes):
+            op = HoneyBee(mapping_mode=mapping, blur_sigma_px=sigma, custom_matrix=np.eye(3, dtype=np.float32))._operator()
+            assert op.desc.blur_ksize == k and op.desc.mapping == av._lib.AVX_MAP[mapping], (mapping, sigma)
+            assert op.takes_catches() == (mapping != "falsecolor_uv_mixed" and sigma <= 1.0 / 3.0), (mapping, sigma)
+            assert op.padded_clone(32).takes_catches() == op.takes_catches()
+
+
+def test_mst_honeybee_hand_off_refuses_another_band_count():
+    """The MST++ cube has 31 bands: an operator on another band grid is refused before anything runs (ValueError), a 31-band one passes."""
+    from animal_vision_amd.animals import HoneyBee
+    from animal_vision_amd.ml import MSTPlusPlusPredictor
+    from animal_vision_amd.ml.predict import check_bands
+
+    check_bands(HoneyBee()._operator())
+    op16 = HoneyBee(hsi_band_centers_nm=np.linspace(400.0, 700.0, 16, dtype=np.float32))._operator()
+    with pytest.raises(ValueError):
+        check_bands(op16)
+    with pytest.raises(ValueError):
+        check_bands(op16.padded_clone(32))
+    with pytest.raises(ValueError):
+        MSTPlusPlusPredictor(None, seed=0, device="cpu").honeybee(np.zeros((16, 16, 3), np.uint8), op16)
+
+
 def test_gelu_tables_of_the_matrix_pipe_kernels_hold_their_stated_error():
     """csrc/mst_common.h: the coefficient tables of the clamped odd polynomial (gelu_poly2: degree 7 / 6 / 5, x clamped to +-A) and of its
     prescaled form (gelu_pre_multi: x / 4 enters, t = clamp01(x'^2), Phi = clamp01(x' R^(t) + 1/2), x' Phi = gelu(x) / 4 leaves), evaluated here

@@ -264,6 +264,9 @@ _SIGS = {
     "avx_split_compose_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "avx_draw_label_u8": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_int), _fp, _i, ctypes.c_float, ctypes.c_float, _i, _vp]),
     "avx_gallery_compose_u8": (_i, [_vp, ctypes.POINTER(GalleryTile), _i, _fp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp]),
+    "avx_i420_to_rgb_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "avx_rgb_to_i420_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "avx_yuv_coefficients": (_i, [_i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

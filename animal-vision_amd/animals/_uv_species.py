@@ -80,6 +80,11 @@ class SpeciesStreamOp:
         be = self.plans[k]
         return be.d_in, be.d_out
 
+    def slot_baseline(self, k: int):
+        """Slot k's baseline frame (uint8 HxWx3 on the device): what visualize() returns first, the panorama-warped input
+        (FramePipeline(split_baseline=True) composes the split frame against it)."""
+        return self.plans[k].d_base
+
     def run_device(self, d_in, d_out, n_frames: int, H: int, W: int, stream=None):
         assert n_frames == 1 and (H, W) == (self.H, self.W)
         self._by_in[d_in.ptr].run_device(stream)

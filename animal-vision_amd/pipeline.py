@@ -101,6 +101,9 @@ class _Slot:
     d_out: object
     index: int = -1
     busy: bool = False
+    d_yuv_in: object = None   # io_format="i420": the frame's payload on the device, in and out
+    d_yuv_out: object = None
+    d_left: object = None     # the left half of the split frame: d_in, or the op's baseline (split_baseline)
 
 
 class FramePipeline:
@@ -108,13 +111,29 @@ class FramePipeline:
     uint8 frames with `depth` frames in flight."""
 
     def __init__(self, op, H: int, W: int, *, ctx=None, depth: int = 3, split_compare: bool = False, draw_seam: bool = True,
-                 labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed")):
+                 labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed"), io_format: str = "rgb",
+                 matrix: str = "bt601", yuv_range: str = "limited", split_baseline: bool = False):
         """split_compare: emit make_split_frame(original, transformed) composed on the device (renderers/video.py:198-245:
-        halves, seam, and the two corner labels -- `labels` = (left, right), None = none) instead of the transformed frame."""
-        from .runtime import get_context
+        halves, seam, and the two corner labels -- `labels` = (left, right), None = none) instead of the transformed frame.
 
+        io_format: "rgb" -- frames in and out are HxWx3 uint8; "i420" -- they are flat I420 payloads (the Y4M layout, 1.5 B/px:
+        half the bytes of the host and PCIe copies), converted on the slot stream into the op's d_in and back out of its
+        d_out (yuv.py, with `matrix` and `yuv_range`); the op, the split composition and the labels run on RGB as before.
+
+        split_baseline: the split frame's left half is the op's own baseline -- `op.slot_baseline(k)`, the frame a species'
+        visualize() returns first (a UV species' panorama-warped input, SpeciesStreamOp) -- instead of the input frame."""
+        from .runtime import get_context
+        from .yuv import _codes, i420_size
+
+        if io_format not in ("rgb", "i420"):
+            raise ValueError(f"io_format must be 'rgb' or 'i420' (got {io_format!r})")
+        _codes(matrix, yuv_range)
+        self.io_format, self.matrix, self.yuv_range = io_format, matrix, yuv_range
         self.op, self.H, self.W, self.depth = op, H, W, depth
         self.split_compare, self.draw_seam = bool(split_compare), bool(draw_seam)
+        baseline = getattr(op, "slot_baseline", None) if split_baseline else None
+        if split_baseline and baseline is None:
+            raise ValueError(f"split_baseline: {type(op).__name__} has no slot_baseline(k)")
         self.labels = tuple(labels) if labels else (None, None)
         self.ctx = ctx or getattr(op, "ctx", None) or get_context()
         if getattr(op, "ctx", None) is None:
@@ -124,9 +143,14 @@ class FramePipeline:
         lend = getattr(op, "slot_buffers", None)
         self._lent = lend is not None
         self.slots = []
+        self._io_shape = (H, W, 3) if io_format == "rgb" else (i420_size(H, W),)
         for k in range(depth):
             d_in, d_out = lend(k) if lend else (self.ctx.malloc(nbytes), self.ctx.malloc(nbytes))
-            self.slots.append(_Slot(self.ctx.stream_create(), self.ctx.pinned((H, W, 3), np.uint8), self.ctx.pinned((H, W, 3), np.uint8), d_in, d_out))
+            s = _Slot(self.ctx.stream_create(), self.ctx.pinned(self._io_shape, np.uint8), self.ctx.pinned(self._io_shape, np.uint8), d_in, d_out)
+            s.d_left = baseline(k) if baseline is not None else d_in
+            if io_format == "i420":
+                s.d_yuv_in, s.d_yuv_out = self.ctx.malloc(i420_size(H, W)), self.ctx.malloc(i420_size(H, W))
+            self.slots.append(s)
 
     def close(self):
         for s in self.slots:
@@ -139,6 +163,8 @@ class FramePipeline:
             s.h_in.free(); s.h_out.free()
             if not self._lent:
                 s.d_in.free(); s.d_out.free()
+            if s.d_yuv_in is not None:
+                s.d_yuv_in.free(); s.d_yuv_out.free()
         self.slots = []
 
     def _retire(self, s: _Slot, emit: Callable[[int, np.ndarray], None]):
@@ -152,29 +178,40 @@ class FramePipeline:
             s.busy = False
 
     def run(self, frames: Iterator[Tuple[int, np.ndarray]], emit: Callable[[int, np.ndarray], None]) -> StreamStats:
-        """frames: (global index, HxWx3 uint8) pairs owned by this rank; emit(index, out) in submission order."""
+        """frames: (global index, HxWx3 uint8 -- or, io_format="i420", a flat I420 payload) pairs owned by this rank;
+        emit(index, out) in submission order, `out` in the same format."""
         from ._lib import lib
+        from .yuv import i420_to_rgb_device, rgb_to_i420_device
 
         ctx, n, t0 = self.ctx, 0, time.perf_counter()
         self._copy_s = 0.0
-        nbytes = self.H * self.W * 3
+        i420 = self.io_format == "i420"
+        nbytes = int(np.prod(self._io_shape))
         for k, (index, frame) in enumerate(frames):
             s = self.slots[k % self.depth]
             self._retire(s, emit)
-            if frame.shape != (self.H, self.W, 3) or frame.dtype != np.uint8:
-                raise ValueError(f"frame {index}: expected uint8 {(self.H, self.W, 3)}, got {frame.dtype} {frame.shape}")
+            if frame.shape != self._io_shape or frame.dtype != np.uint8:
+                raise ValueError(f"frame {index}: expected uint8 {self._io_shape}, got {frame.dtype} {frame.shape}")
             tc = time.perf_counter()
             _pcopy(s.h_in.array, frame)
             self._copy_s += time.perf_counter() - tc
-            ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_in.ptr, s.h_in.ptr, nbytes, s.stream))
+            if i420:
+                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_yuv_in.ptr, s.h_in.ptr, nbytes, s.stream))
+                i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, 1, self.H, self.W, matrix=self.matrix, range=self.yuv_range, stream=s.stream)
+            else:
+                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_in.ptr, s.h_in.ptr, nbytes, s.stream))
             self.op.run_device(s.d_in, s.d_out, 1, self.H, self.W, stream=s.stream)
             if self.split_compare:
-                ctx._check(lib.avx_split_compose_u8(ctx._h, s.d_in.ptr, s.d_out.ptr, s.d_out.ptr, self.H, self.W, int(self.draw_seam), s.stream))
+                ctx._check(lib.avx_split_compose_u8(ctx._h, s.d_left.ptr, s.d_out.ptr, s.d_out.ptr, self.H, self.W, int(self.draw_seam), s.stream))
                 if self.labels[0] is not None or self.labels[1] is not None:
                     from .renderers.labels import draw_split_labels_device
 
                     draw_split_labels_device(ctx, s.d_out, self.H, self.W, self.labels[0], self.labels[1], s.stream)
-            ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_out.ptr, nbytes, s.stream))
+            if i420:
+                rgb_to_i420_device(ctx, s.d_out, s.d_yuv_out, 1, self.H, self.W, matrix=self.matrix, range=self.yuv_range, stream=s.stream)
+                ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_yuv_out.ptr, nbytes, s.stream))
+            else:
+                ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_out.ptr, nbytes, s.stream))
             s.index, s.busy = index, True
             n += 1
         for j in range(self.depth):  # drain in submission order
@@ -183,22 +220,32 @@ class FramePipeline:
 
 
 def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int = 3, split_compare: bool = False, dist=None,
-              labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed")) -> StreamStats:
+              labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed"), split_baseline: bool = False) -> StreamStats:
     """main.py:53-72 on the device: read -> visualize -> (split-compose + labels) -> render, this rank's shard only.
 
     A renderer that shards itself (renderers.VideoRenderer(rank=, world=): strided source, index-addressed sink) hands over
     only this rank's frames and its `last_index` names each one's place in the stream; any other get_image()/render() pair
     is read in full and filtered here (frame i belongs to rank i mod world).  Outputs go to the sink under their GLOBAL frame
     index; after the ranks' closing collective (the statistics reduction) rank 0 reassembles a sharded .npy sink into the one
-    ordered stream ("host re-orders outputs by frame index before render()")."""
+    ordered stream ("host re-orders outputs by frame index before render()").
+
+    A renderer whose frames can stay I420 end to end (`yuv_hw` not None: renderers.VideoRenderer from a .y4m to a .y4m) hands
+    over get_yuv() payloads, and the pipeline runs with io_format="i420" in the renderer's `matrix` and `yuv_range`.
+    split_baseline: see FramePipeline."""
     self_sharding = getattr(renderer, "world", 1) == world and getattr(renderer, "rank", 0) == rank and hasattr(renderer, "last_index") and world > 1
-    first = renderer.get_image()
+    yuv_hw = getattr(renderer, "yuv_hw", None) if callable(getattr(renderer, "get_yuv", None)) else None
+    get = renderer.get_yuv if yuv_hw is not None else renderer.get_image
+    first = get()
     if first is None:
         stats = StreamStats()
         pipe = None
+    elif yuv_hw is not None:
+        H, W = yuv_hw
+        pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, io_format="i420",
+                             matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline)
     else:
         H, W, _ = first.shape
-        pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels)
+        pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, split_baseline=split_baseline)
 
     def frames():
         i, f = 0, first
@@ -208,7 +255,7 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
             elif owner_of(i, world) == rank:
                 yield i, f
             i += 1
-            f = renderer.get_image()
+            f = get()
 
     def emit(i, out):
         if self_sharding:

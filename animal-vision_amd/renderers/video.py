@@ -5,8 +5,14 @@ None at end of stream, :82-96).
 Codec I/O is out of scope (the reference leans on cv2.VideoCapture / VideoWriter 'mp4v', :68,:113; neither
 cv2 nor ffmpeg exists here), so paths name what this box can read and write:
   read_path : "synthetic:<W>x<H>:<n>[:noise|structured]"  |  a .npy file (N,H,W,3 uint8)  |  a directory of images
-  write_path: a directory (one PNG per frame, via Pillow)  |  a .npy file  |  None
+              |  a .y4m file or "-" (stdin / a FIFO: YUV4MPEG2, 8-bit 4:2:0, what `ffmpeg -f yuv4mpegpipe` writes)
+  write_path: a directory (one PNG per frame, via Pillow)  |  a .npy file  |  a .y4m file or "-" (stdout)  |  None
 No preview window (no GUI); `window_name` is accepted and ignored.
+
+Y4M (renderers/y4m.py): get_image() still returns RGB uint8 HxWx3, converted from the I420 payload on the device (yuv.py);
+get_yuv() hands over the payload itself, and render() takes RGB frames (converted on the device) or payloads.  `matrix` and
+`range` name the conversion; range None = the source's XCOLORRANGE tag, else limited.  The sink echoes the
+source's header (size, rate, aspect, colour range, unknown tags) when the source is a .y4m.
 
 Sharded streams (two keywords the reference does not have, both defaulted): with `world` > 1 this renderer
 serves and stores only the frames of rank `rank` (global frame i belongs to rank i mod world) -- every source here is
@@ -55,11 +61,18 @@ def split_compose(original: np.ndarray, modified: np.ndarray, draw_seam: bool = 
     return out
 
 
+def is_y4m(path: Optional[str]) -> bool:
+    """A path the Y4M reader / writer serves: "-" (stdin / stdout) or a name ending in .y4m."""
+    return bool(path) and (path == "-" or path.lower().endswith(".y4m"))
+
+
 class VideoRenderer(Renderer):
     def __init__(self, *, read_path: Optional[str] = None, write_path: Optional[str] = None, fps: Optional[int] = None,
-                 window_name: str = "Video Analysis", rank: int = 0, world: int = 1):
+                 window_name: str = "Video Analysis", rank: int = 0, world: int = 1, matrix: str = "bt601", range: Optional[str] = None):
         if not (0 <= rank < world):
             raise ValueError(f"rank {rank} outside world {world}")
+        if write_path == "-" and world > 1:
+            raise ValueError("stdout is one ordered stream: it can only be written with world = 1")
         self.read_path, self.write_path = read_path, write_path
         self.fps = fps or 30
         self.window_name = window_name
@@ -73,12 +86,20 @@ class VideoRenderer(Renderer):
         self._sink = None            # memory-mapped .npy shard (streamed)
         self._sink_rows = 0
         self.frames_written = 0
+        self.matrix, self._range = matrix, range
+        self._y4m = None             # renderers.y4m.Y4MReader
+        self._y4m_out = None         # renderers.y4m.Y4MWriter (created by the first render)
 
     # ---- source ----------------------------------------------------------------------------------------
     def open(self) -> None:
         p = self.read_path
         if p:
-            if p.startswith("synthetic:"):
+            if is_y4m(p):
+                from .y4m import Y4MReader
+
+                self._y4m = Y4MReader(p, rank=self.rank, world=self.world)
+                self.total_frames = self._y4m.total_frames
+            elif p.startswith("synthetic:"):
                 parts = p.split(":")
                 w, h = (int(v) for v in parts[1].lower().split("x"))
                 kind = parts[3] if len(parts) > 3 else "noise"
@@ -92,10 +113,46 @@ class VideoRenderer(Renderer):
                 self.total_frames = len(self._files)
             else:
                 raise RuntimeError(f"Failed to open video for reading: {p} (no codec on this box: synthetic:, .npy or an image directory)")
-        if self.write_path and not self.write_path.endswith(".npy"):
+        if self.write_path and not self.write_path.endswith(".npy") and not is_y4m(self.write_path):
             os.makedirs(self.write_path, exist_ok=True)
 
+    @property
+    def yuv_range(self) -> str:
+        """The YUV range of the conversions: the constructor's, else the .y4m source's XCOLORRANGE tag, else limited."""
+        if self._range is not None:
+            return self._range
+        return "full" if self._y4m is not None and self._y4m.header.full_range else "limited"
+
+    @property
+    def y4m_header(self):
+        """The .y4m source's header (renderers.y4m.Y4MHeader), None for other sources."""
+        return None if self._y4m is None else self._y4m.header
+
+    @property
+    def yuv_hw(self) -> Optional[tuple]:
+        """(H, W) when frames can stay I420 end to end -- a .y4m source and a .y4m sink (or none) -- else None.
+        pipeline.run_video then streams get_yuv() payloads (FramePipeline io_format="i420")."""
+        if self._y4m is None or (self.write_path and not is_y4m(self.write_path)):
+            return None
+        return self._y4m.header.height, self._y4m.header.width
+
+    def get_yuv(self) -> Optional[np.ndarray]:
+        """The next frame of a .y4m source as its flat uint8 I420 payload, None at end of stream."""
+        if self._y4m is None:
+            raise RuntimeError("get_yuv() needs a .y4m (or '-') source")
+        f = self._y4m.read()
+        if f is not None:
+            self.last_index = self._y4m.last_index
+        return f
+
     def get_image(self) -> Optional[np.ndarray]:
+        if self._y4m is not None:
+            f = self.get_yuv()
+            if f is None:
+                return None
+            from ..yuv import i420_to_rgb
+
+            return i420_to_rgb(f, self._y4m.header.height, self._y4m.header.width, matrix=self.matrix, range=self.yuv_range)
         if self._src is not None:
             f = self._src.get_image()
             if f is not None:
@@ -116,18 +173,21 @@ class VideoRenderer(Renderer):
 
     # ---- sink ------------------------------------------------------------------------------------------
     def _shard_path(self, rank: int) -> str:
-        return self.write_path if self.world == 1 else f"{self.write_path[:-4]}.rank{rank}of{self.world}.npy"
+        return self.write_path if self.world == 1 else f"{self.write_path[:-4]}.rank{rank}of{self.world}{self.write_path[-4:]}"
 
     def _own_count(self) -> Optional[int]:
         return None if self.total_frames is None else len(range(self.rank, self.total_frames, self.world))
 
     def render(self, frame: np.ndarray, *, index: Optional[int] = None) -> None:
         """renderers/video.py:118-142 (write the frame).  `index` = the frame's GLOBAL stream index; by default frames are
-        taken to arrive in this rank's stream order (rank, rank + world, ...)."""
+        taken to arrive in this rank's stream order (rank, rank + world, ...).  A .y4m sink also takes flat I420 payloads of the
+        source's size, and writes its frames in this rank's stream order (one shard per rank when world > 1)."""
         if index is None:
             index = self.rank + self.frames_written * self.world
         if self.write_path:
-            if self.write_path.endswith(".npy"):
+            if is_y4m(self.write_path):
+                self._render_y4m(frame, index)
+            elif self.write_path.endswith(".npy"):
                 row = (index - self.rank) // self.world
                 if (index - self.rank) % self.world or row < 0:
                     raise ValueError(f"frame {index} does not belong to rank {self.rank} of {self.world}")
@@ -139,6 +199,40 @@ class VideoRenderer(Renderer):
 
                 Image.fromarray(frame).save(os.path.join(self.write_path, f"frame_{index:06d}.png"))
         self.frames_written += 1
+
+    def _render_y4m(self, frame: np.ndarray, index: int) -> None:
+        if index != self.rank + self.frames_written * self.world:
+            raise ValueError(f"frame {index}: a .y4m sink is written in stream order; rank {self.rank} of {self.world} expects frame "
+                             f"{self.rank + self.frames_written * self.world}")
+        frame = np.asarray(frame)
+        if frame.ndim == 3:
+            if frame.dtype != np.uint8 or frame.shape[2] != 3:
+                raise ValueError(f"a .y4m sink takes RGB uint8 HxWx3 frames or I420 payloads, got {frame.dtype} {frame.shape}")
+            H, W = frame.shape[:2]
+            from ..yuv import rgb_to_i420
+
+            payload = rgb_to_i420(frame, matrix=self.matrix, range=self.yuv_range)
+        elif frame.ndim == 1 and frame.dtype == np.uint8:
+            if self._y4m_out is None and self._y4m is None:
+                raise ValueError("an I420 payload names no frame size: render an RGB frame first, or read from a .y4m")
+            hdr = self._y4m_out.header if self._y4m_out is not None else self._y4m.header
+            H, W, payload = hdr.height, hdr.width, frame
+        else:
+            raise ValueError(f"a .y4m sink takes RGB uint8 HxWx3 frames or flat uint8 I420 payloads, got {frame.dtype} {frame.shape}")
+        if self._y4m_out is None:
+            self._open_y4m_sink(H, W)
+        self._y4m_out.write(payload)
+
+    def _open_y4m_sink(self, H: int, W: int) -> None:
+        """Create the .y4m sink (this rank's shard when world > 1) and write its header."""
+        from .y4m import Y4MWriter, default_header
+
+        if self._y4m is not None:  # echo the source's header: rate, aspect, unknown tags; the range this sink encodes with
+            hdr = self._y4m.header.with_size(W, H)
+            hdr = hdr.replaced("XCOLORRANGE=", "FULL" if self.yuv_range == "full" else ("LIMITED" if hdr.tag("XCOLORRANGE=") else None))
+        else:
+            hdr = default_header(W, H, fps=self.fps, full_range=self.yuv_range == "full")
+        self._y4m_out = Y4MWriter(self._shard_path(self.rank), hdr)
 
     def _grow_sink(self, frame: np.ndarray, row: int) -> None:
         """Create the shard on first use (sized from the source's frame count when it is known); a stream of unknown length
@@ -158,6 +252,8 @@ class VideoRenderer(Renderer):
     def flush(self) -> None:
         """Everything rendered so far is on disk as a well-formed .npy (a mapping sized for more frames than arrived is
         trimmed to what was written); rendering may continue afterwards."""
+        if self._y4m_out is not None:
+            self._y4m_out.flush()
         if self._sink is None:
             return
         self._sink.flush()
@@ -176,10 +272,21 @@ class VideoRenderer(Renderer):
         self.flush()
         self._sink = None
         self._src = self._frames = None
+        if self._y4m_out is None and self._y4m is not None and is_y4m(self.write_path):
+            # no frame was rendered: the sink is still a valid (empty) stream, its header at the source's size
+            self._open_y4m_sink(self._y4m.header.height, self._y4m.header.width)
+        if self._y4m_out is not None:
+            self._y4m_out.close()
+            self._y4m_out = None
+        if self._y4m is not None:
+            self._y4m.close()
+            self._y4m = None
 
     def merge_shards(self) -> Optional[str]:
         """Rank 0, after every rank has flushed/closed its shard (run_video calls it behind the closing collective): interleave
-        <write_path>.rank<r>of<world>.npy into the one ordered stream <write_path>, frame i from shard i mod world."""
+        <write_path>.rank<r>of<world>.npy (.y4m) into the one ordered stream <write_path>, frame i from shard i mod world."""
+        if self.write_path and is_y4m(self.write_path) and self.world > 1:
+            return self._merge_y4m_shards()
         if not (self.write_path and self.write_path.endswith(".npy")) or self.world == 1:
             return self.write_path
         shards = [np.load(self._shard_path(r), mmap_mode="r") if os.path.exists(self._shard_path(r)) else None for r in range(self.world)]
@@ -200,6 +307,31 @@ class VideoRenderer(Renderer):
         for r in range(self.world):
             if os.path.exists(self._shard_path(r)):
                 os.remove(self._shard_path(r))
+        return self.write_path
+
+    def _merge_y4m_shards(self) -> Optional[str]:
+        from .y4m import Y4MReader, Y4MWriter
+
+        paths = [self._shard_path(r) for r in range(self.world)]
+        shards = [Y4MReader(p) if os.path.exists(p) else None for p in paths]
+        have = [s for s in shards if s is not None]
+        if not have:
+            return None
+        n = sum(s.total_frames for s in have)
+        counts = [0 if s is None else s.total_frames for s in shards]
+        if counts != [len(range(r, n, self.world)) for r in range(self.world)]:
+            raise ValueError(f"shards of {counts} frames are not a round-robin partition of one stream")
+        out = Y4MWriter(self.write_path, have[0].header)
+        try:
+            for i in range(n):  # frame by frame: bounded memory
+                out.write(shards[i % self.world].read())
+        finally:
+            out.close()
+            for s in have:
+                s.close()
+        for p in paths:
+            if os.path.exists(p):
+                os.remove(p)
         return self.write_path
 
     # ---- split compare ---------------------------------------------------------------------------------

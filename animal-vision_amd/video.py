@@ -1,0 +1,128 @@
+"""The reference's `video` command (main.py:53-72): every frame of a video through one species, written as a video --
+non-interactive, and with Y4M in and out, so real footage can come and go through ffmpeg:
+
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m animal_vision_amd.video - out.y4m --species Dog --split-compare
+
+INPUT and OUTPUT are a .y4m file, "-" (stdin / stdout, Y4M), or the other forms renderers.VideoRenderer takes (synthetic:,
+.npy, an image directory).  Species are the display names of gallery.py's registry.  Routing:
+  * the dichromats but Cat (DichromatOp), HoneyBee (HoneybeeOp) and the plane-program UV species with a fixed plan
+    (SpeciesStreamOp) stream through pipeline.run_video: `--depth` frames in flight, split-compose and labels on the device
+    (against each species' own baseline, as visualize() returns it: the plane-program species' is their panorama-warped
+    input), and, from a .y4m to a .y4m, I420 across the host and PCIe (FramePipeline io_format="i420");
+  * every other species (Cat, whose baseline is the zoomed frame; MantisShrimp; RatUV, whose plan depends on the frame) runs
+    visualize() per frame, and the split frame is composed from visualize's own (baseline, out) pair, as the reference does."""
+from __future__ import annotations
+
+import argparse
+import sys
+import time
+from typing import Optional, Sequence
+
+import numpy as np
+
+from .gallery import _CLASS_NAMES, ensure_rgb_uint8, species_class
+
+SPECIES_NAMES = list(_CLASS_NAMES)  # all 36 display names
+
+
+def route(animal) -> str:
+    """How the command runs `animal`: "dichromat" / "honeybee" / "plane" stream through run_video, "frame" runs visualize() per frame."""
+    from .animals import Cat, HoneyBee
+    from .animals._dichromats import _Dichromat
+    from .animals._uv_species import UVSpecies
+    from .animals.rat_uv import RatUV
+
+    if isinstance(animal, _Dichromat) and not isinstance(animal, Cat):
+        return "dichromat"
+    if isinstance(animal, HoneyBee) and animal.hsi_model is None and not animal.hsi_downsample:
+        return "honeybee"
+    if isinstance(animal, UVSpecies) and not isinstance(animal, RatUV):
+        return "plane"
+    return "frame"
+
+
+def stream_op(animal, H: int, W: int, depth: int):
+    """The op run_video streams for `animal`, or None when the species goes through the per-frame loop."""
+    kind = route(animal)
+    if kind in ("dichromat", "honeybee"):
+        return animal._operator()
+    if kind == "plane":
+        from .animals._uv_species import SpeciesStreamOp
+
+        return SpeciesStreamOp(animal, H, W, depth=depth)
+    return None
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="video", description="Run one species on every frame of a video (Y4M in and out, or the other "
+                                                          "VideoRenderer forms).")
+    ap.add_argument("input", help=".y4m file, '-' (stdin, Y4M), synthetic:<W>x<H>:<n>[:kind], .npy or an image directory")
+    ap.add_argument("output", help=".y4m file, '-' (stdout, Y4M), .npy or a directory of PNG frames")
+    ap.add_argument("--species", required=True, choices=SPECIES_NAMES, metavar="NAME", help="display name, e.g. Dog, HoneyBee, 'Mantis Shrimp'")
+    ap.add_argument("--split-compare", action="store_true", help="left half original, right half transformed (the reference's output)")
+    ap.add_argument("--no-labels", action="store_true", help="no corner labels on the split frame")
+    ap.add_argument("--depth", type=int, default=3, help="frames in flight on the device (streamed species)")
+    ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"])
+    ap.add_argument("--range", default=None, choices=["limited", "full"], help="YUV range (default: the input's XCOLORRANGE, else limited)")
+    return ap
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    args = build_parser().parse_args(argv)
+    if args.depth < 1:
+        raise SystemExit("video: --depth must be at least 1")
+    from .animals._uv_species import SpeciesStreamOp
+    from .pipeline import run_video
+    from .renderers import VideoRenderer, split_compose
+
+    vr = VideoRenderer(read_path=args.input, write_path=args.output, window_name="AnimalCam", matrix=args.matrix, range=args.range)
+    vr.open()
+    animal = species_class(args.species)()
+    labels = None if args.no_labels else ("Original", "Transformed")
+    t0 = time.perf_counter()
+    try:
+        hw = None if vr.y4m_header is None else (vr.y4m_header.height, vr.y4m_header.width)
+        if hw is None:  # synthetic:, .npy or an image directory: peek at the size the stream op is built for, then start over
+            first = vr.get_image()
+            hw = None if first is None else first.shape[:2]
+            vr.close()
+            vr = VideoRenderer(read_path=args.input, write_path=args.output, window_name="AnimalCam", matrix=args.matrix, range=args.range)
+            vr.open()
+        op = None if hw is None else stream_op(animal, hw[0], hw[1], args.depth)
+        if op is not None:
+            try:
+                # the split frame's left half is visualize()'s baseline: the input for the dichromats and HoneyBee, the
+                # panorama-warped input for the plane-program species (their plans' baseline frames)
+                stats = run_video(op, vr, depth=args.depth, split_compare=args.split_compare, labels=labels,
+                                  split_baseline=isinstance(op, SpeciesStreamOp))
+            finally:
+                if isinstance(op, SpeciesStreamOp):
+                    op.close()
+            frames = stats.frames
+        else:
+            frames = 0
+            while True:
+                frame = vr.get_image()
+                if frame is None:
+                    break
+                res = animal.visualize(frame)
+                if res is None:
+                    continue
+                base, out = res
+                if out is None:
+                    continue
+                base, out = ensure_rgb_uint8(np.asarray(base)), ensure_rgb_uint8(np.asarray(out))
+                if args.split_compare:
+                    vr.render(split_compose(base, out, left_label=labels[0] if labels else None, right_label=labels[1] if labels else None))
+                else:
+                    vr.render(out)
+                frames += 1
+    finally:
+        vr.close()
+    dt = time.perf_counter() - t0
+    print(f"video: {args.species}: {frames} frames in {dt:.2f} s ({frames / dt if dt > 0 else 0.0:.1f} fps)", file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

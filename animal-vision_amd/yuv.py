@@ -1,0 +1,109 @@
+"""YUV 4:2:0 (I420, the Y4M payload) <-> RGB uint8 on the device (csrc/yuv.hip), in the style of geometry.py.
+
+The arithmetic (int32 fixed point, 16 fractional bits, BT.601 / BT.709, limited / full range) is defined in DESIGN §4.8; the
+coefficient tables are built by the C entry points from the (matrix, range) names below.  A payload is one frame's Y plane
+(H x W), then U and V (ceil(H/2) x ceil(W/2) each), frames back to back."""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from ._lib import lib
+from .runtime import Context, DeviceBuffer, get_context
+
+MATRICES = {"bt601": 0, "bt709": 1}  # AVX_YUV_BT601, AVX_YUV_BT709
+RANGES = {"limited": 0, "full": 1}   # the full_range argument
+
+
+def i420_size(H: int, W: int) -> int:
+    """Bytes of one I420 frame of H x W pixels."""
+    return H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)
+
+
+def _codes(matrix: str, range: str):
+    if matrix not in MATRICES:
+        raise ValueError(f"matrix must be one of {sorted(MATRICES)} (got {matrix!r})")
+    if range not in RANGES:
+        raise ValueError(f"range must be one of {sorted(RANGES)} (got {range!r})")
+    return MATRICES[matrix], RANGES[range]
+
+
+def coefficients(matrix: str = "bt601", range: str = "limited"):
+    """The fixed-point tables the kernels run with, as the C side builds them: (cy, crv, cgu, cgv, cbu, yo) for the decode and
+    ((Y row), (U row), (V row)), yo for the encode, each row an (r, g, b) triple of 16.16 coefficients."""
+    import ctypes
+
+    m, r = _codes(matrix, range)
+    dec, enc = (ctypes.c_int * 6)(), (ctypes.c_int * 10)()
+    if lib.avx_yuv_coefficients(m, r, dec, enc) != 0:
+        raise ValueError(f"avx_yuv_coefficients({matrix!r}, {range!r}) failed")
+    e = list(enc)
+    return tuple(dec), ((tuple(e[0:3]), tuple(e[3:6]), tuple(e[6:9])), e[9])
+
+
+def _check_sizes(n_frames: int, H: int, W: int, d_rgb: DeviceBuffer, d_yuv: DeviceBuffer) -> None:
+    """The kernels write n_frames whole frames: an undersized buffer is an error here, before the launch."""
+    if n_frames < 1 or H < 1 or W < 1:
+        raise ValueError(f"bad shape: {n_frames} frames of {H} x {W}")
+    if d_rgb.nbytes < n_frames * H * W * 3 or d_yuv.nbytes < n_frames * i420_size(H, W):
+        raise ValueError(f"{n_frames} frames of {H} x {W} need {n_frames * H * W * 3} RGB and {n_frames * i420_size(H, W)} I420 bytes; "
+                         f"the buffers hold {d_rgb.nbytes} and {d_yuv.nbytes}")
+
+
+def i420_to_rgb_device(ctx: Context, d_yuv: DeviceBuffer, d_rgb: DeviceBuffer, n_frames: int, H: int, W: int, *, matrix: str = "bt601",
+                       range: str = "limited", stream=None) -> None:
+    m, r = _codes(matrix, range)
+    _check_sizes(n_frames, H, W, d_rgb, d_yuv)
+    ctx._check(lib.avx_i420_to_rgb_u8(ctx._h, d_yuv.ptr, d_rgb.ptr, int(n_frames), int(H), int(W), m, r, ctx._s(stream)))
+
+
+def rgb_to_i420_device(ctx: Context, d_rgb: DeviceBuffer, d_yuv: DeviceBuffer, n_frames: int, H: int, W: int, *, matrix: str = "bt601",
+                       range: str = "limited", stream=None) -> None:
+    m, r = _codes(matrix, range)
+    _check_sizes(n_frames, H, W, d_rgb, d_yuv)
+    ctx._check(lib.avx_rgb_to_i420_u8(ctx._h, d_rgb.ptr, d_yuv.ptr, int(n_frames), int(H), int(W), m, r, ctx._s(stream)))
+
+
+def i420_to_rgb(buf: np.ndarray, H: int, W: int, *, matrix: str = "bt601", range: str = "limited", ctx: Optional[Context] = None) -> np.ndarray:
+    """I420 payload(s) -> RGB uint8.  `buf`: uint8 of one frame (any shape holding i420_size(H, W) bytes, e.g. flat) -> (H, W, 3),
+    or with a leading frame axis (N, i420_size) -> (N, H, W, 3)."""
+    _codes(matrix, range)
+    a = np.ascontiguousarray(buf)
+    if a.dtype != np.uint8:
+        raise TypeError(f"I420 payloads are uint8 (got {a.dtype})")
+    fsz = i420_size(H, W)
+    batched = a.ndim == 2 and a.shape[1] == fsz
+    if not batched and a.size != fsz:
+        raise ValueError(f"expected {fsz} bytes per {H}x{W} frame (or an (N, {fsz}) batch), got shape {a.shape}")
+    n = a.shape[0] if batched else 1
+    ctx = ctx or get_context()
+    d_in = ctx.upload(a)
+    d_out = ctx.malloc(n * H * W * 3)
+    try:
+        i420_to_rgb_device(ctx, d_in, d_out, n, H, W, matrix=matrix, range=range)
+        out = ctx.download(d_out, (n, H, W, 3), np.uint8)
+    finally:
+        d_in.free()
+        d_out.free()
+    return out if batched else out[0]
+
+
+def rgb_to_i420(rgb: np.ndarray, *, matrix: str = "bt601", range: str = "limited", ctx: Optional[Context] = None) -> np.ndarray:
+    """RGB uint8 (H, W, 3) -> flat I420 payload (i420_size(H, W),), or (N, H, W, 3) -> (N, i420_size(H, W))."""
+    _codes(matrix, range)
+    a = np.ascontiguousarray(rgb)
+    if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.shape[-1] != 3:
+        raise ValueError(f"expected uint8 (H, W, 3) or (N, H, W, 3), got {a.dtype} {a.shape}")
+    batched = a.ndim == 4
+    n, H, W = (a.shape[0] if batched else 1), a.shape[-3], a.shape[-2]
+    ctx = ctx or get_context()
+    d_in = ctx.upload(a)
+    d_out = ctx.malloc(n * i420_size(H, W))
+    try:
+        rgb_to_i420_device(ctx, d_in, d_out, n, H, W, matrix=matrix, range=range)
+        out = ctx.download(d_out, (n, i420_size(H, W)), np.uint8)
+    finally:
+        d_in.free()
+        d_out.free()
+    return out if batched else out[0]

@@ -230,6 +230,19 @@ typedef struct avx_gallery_tile {
 int avx_gallery_compose_u8(avx_ctx* ctx, const avx_gallery_tile* tiles_host, int n_tiles, const float* segments_host, int n_segments,
                            int strip_h, int pad, int cols, const int bg_rgb[3], uint8_t* canvas_hwc, int Hc, int Wc, void* stream);
 
+/* YUV 4:2:0 <-> RGB (Y4M video I/O).  `yuv` is the Y4M payload of n_frames frames back to back: a Y plane of H x W, then U,
+ * then V, each ceil(H/2) x ceil(W/2), no padding; `rgb_hwc` is n_frames x H x W x 3.  int32 fixed point with 16 fractional
+ * bits: decode clamp((sum c_i x_i + 2^15) >> 16, 0, 255) with x = (Y - yo, U - 128, V - 128) and chroma replicated
+ * over its 2x2 block; encode Y per pixel, U / V from the 2x2 block sums (an odd last column / row replicated) with
+ * 128 + ((sum c_i S_i + 2^17) >> 18).  matrix: AVX_YUV_BT601 (default of OpenCV and swscale) or AVX_YUV_BT709; full_range 0 =
+ * limited (Y 16..235, chroma scale 224/255), 1 = full.  Chroma siting is ignored.  The buffers must not overlap. */
+enum { AVX_YUV_BT601 = 0, AVX_YUV_BT709 = 1 };
+int avx_i420_to_rgb_u8(avx_ctx* ctx, const uint8_t* yuv, uint8_t* rgb_hwc, int n_frames, int H, int W, int matrix, int full_range, void* stream);
+int avx_rgb_to_i420_u8(avx_ctx* ctx, const uint8_t* rgb_hwc, uint8_t* yuv, int n_frames, int H, int W, int matrix, int full_range, void* stream);
+/* The coefficient tables those two kernels run with (host only, no ctx, no device): dec_out = {cy, crv, cgu, cgv, cbu, yo}
+ * (R = cy y + crv v, G = cy y + cgu u + cgv v, B = cy y + cbu u), enc_out = {Y row r g b, U row r g b, V row r g b, yo}. */
+int avx_yuv_coefficients(int matrix, int full_range, int dec_out[6], int enc_out[10]);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

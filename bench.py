@@ -3,19 +3,26 @@
 
 A "step" is one pass of the hot path over one batch of synthetic frames that are already resident in HBM.
 
-Default run (no --workload) = the HEADLINE of BASELINE.json's metric ("dog LMS + honeybee MST++ UV, 1080p & 4K"):
-  * the JSON line's value / roofline / config are the honeybee UV path with the MST++ HSI stage at 4K (`honeybee_mst_4k`,
-    dtype f16 = the reference's autocast, predict_torch.py:109), timed over exactly --steps steps after --warmup; a step is two
-    independent frames on two streams forked from / joined into the timed one (AVX_BENCH_MST_LANES=1: one after the other);
-  * `workloads` carries the driver-run numbers of the metric's other legs and of BASELINE config 2 -- dog_1080p, dog_4k,
-    honeybee_mst_1080p, cat_1080p -- each timed the same way over >= 1 s, each with its own roofline and parity_checked;
-  * `c4_stream` is BASELINE config 4: a fixed 256-frame 4K synthetic stream through the frame loop (pipeline.run_video:
-    pinned staging, H2D || kernels || D2H, frames round-robin over the ranks, each rank touching only its own frames),
-    dog and honeybee-MST++, PCIe-inclusive frames/s for the whole job (strong scaling: compare across --gpus).
+Default run (no --workload) = the HEADLINE of BASELINE.json's metric ("dog LMS + honeybee MST++ UV, 1080p & 4K"): the JSON line's
+value / roofline / config are the honeybee UV path with the MST++ HSI stage at 4K (`honeybee_mst_4k`, dtype f16 = the reference's
+autocast, predict_torch.py:109), timed over exactly --steps steps after --warmup; a step is four independent frames on two streams
+forked from / joined into the timed one (AVX_BENCH_MST_LANES=1: one after the other).
 --workload NAME times that one workload instead (all species, spectral config 5, ...); the UV species run a step's frames on up to
 four streams, one recorded plan each (AVX_BENCH_UV_LANES), mantis through avx_mantis_u8_batch's lanes.
 --dump-outputs DIR writes what the timed workload's last step computed (Workload.outputs) as DIR/<name>.npy; the inputs are seeded
 synthetic frames (and, for MST++, seeded weights), so two builds run with the same arguments can be compared output for output.
+
+A plain run does only that: set up, warm up, time the steps, dump the outputs if asked, print the line.  Its roofline is arithmetic
+on the timed steps (plus the committed PMC traffic of profiles/pmc_traffic.json).  --full adds everything that takes runs of its own:
+  * `parity_checked` / `parity_stats`: one batch of the timed path against the oracle (rank 0, N = 1);
+  * `cpu_baseline` (--no-cpu-baseline drops it), `e2e_pcie` of a single dichromat / honeybee workload (--no-e2e drops it) and
+    `roofline.dominant_kernel` of the MST++ route, timed on its own;
+  * headline only: `workloads` carries the driver-run numbers of the metric's other legs and of BASELINE config 2 -- dog_1080p,
+    dog_4k, honeybee_mst_1080p, cat_1080p, ... -- each timed the same way over >= 1 s, each with its own roofline and parity_checked
+    (--no-legs drops them);
+  * headline only: `c4_stream` is BASELINE config 4: a fixed 256-frame 4K synthetic stream through the frame loop (pipeline.run_video:
+    pinned staging, H2D || kernels || D2H, frames round-robin over the ranks, each rank touching only its own frames), dog and
+    honeybee-MST++, PCIe-inclusive frames/s for the whole job (strong scaling: compare across --gpus; --no-e2e drops it).
 
 --gpus N: one process per GPU.  Launched by torchrun (WORLD_SIZE set) this process IS a rank; launched bare with N > 1 it
 becomes a launcher: it touches no GPU (no torch / HIP import), starts N rank processes of this file with RANK / LOCAL_RANK /
@@ -26,8 +33,8 @@ stream is sharded round-robin (frame i -> rank i mod N), no data-path collective
 `roofline`: HBM-bound workloads = algorithmic bytes per launch / the launch's duration from HIP events on the
 kernel's own stream; the MST++ route (98 launches per frame) reports SURVEY 8(d)'s quantity -- 703.4 kFLOP per pixel x pixels per step / step
 time against the dense float16 matrix peak (`bound: "mfma"`) -- with the byte view at the current fusion level (`hbm_at_fusion_level`, `traffic` =
-PMC-measured bytes), the vector unit's view (`valu`: the resource that binds) and the dominant kernel timed on its own (`dominant_kernel`) beside it.  `cpu_baseline` = the
-oracle (or, for the network, this repo's CPU float32 port of it) timed on this box's host cores on a bounded sample (rank 0)."""
+PMC-measured bytes), the vector unit's view (`valu`: the resource that binds) and, with --full, the dominant kernel timed on its own (`dominant_kernel`) beside it.
+`cpu_baseline` (--full) = the oracle (or, for the network, this repo's CPU float32 port of it) timed on this box's host cores on a bounded sample (rank 0)."""
 import argparse
 import json
 import os
@@ -117,13 +124,16 @@ def parse_args(argv=None):
     ap.add_argument("--ramp-ms", type=float, default=300.0, help="untimed run of the hot path before the warm-up steps (GPU clock ramp)")
     ap.add_argument("--workload", default="headline", choices=["headline"] + sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="frames per step (0 = workload default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive legs (profiling runs)")
-    ap.add_argument("--no-legs", action="store_true", help="headline only: skip the `workloads` legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: parity against the oracle, CPU baselines, PCIe-inclusive legs, the dominant "
+                         "kernel alone, and for the headline the `workloads` legs and the config-4 stream")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the PCIe-inclusive legs (profiling runs)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full, headline only: skip the `workloads` legs (profiling runs)")
     ap.add_argument("--frames", choices=["auto", "noise", "structured"], default="auto",
                     help="synthetic content: uniform noise (dichromat default: worst case for the decode-table lookups) or gradients + bars + noise")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for each CPU baseline sample")
-    ap.add_argument("--stream-frames", type=int, default=256, help="frames of the config-4 4K stream (whole job)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: budget for each CPU baseline sample")
+    ap.add_argument("--stream-frames", type=int, default=256, help="with --full: frames of the config-4 4K stream (whole job)")
     ap.add_argument("--dry-run", action="store_true", help="ranks rendezvous over gloo and report, no GPU work (launcher test on a CPU box)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy in float32 (rank 0; outputs over "
@@ -461,7 +471,8 @@ class Workload:
     def dtype(self):
         return "f16" if (self.spectral or self.mst is not None) else "f32" if (self.uvsp or self.bee) else "f64" if self.species == "cat" else "f32"
 
-    def report(self, steps, warmup, elapsed, ev_ms):
+    def report(self, steps, warmup, elapsed, ev_ms, dominant=False):
+        """The workload's part of the line from the timed steps alone; dominant: also time the MST++ route's dominant kernel on its own."""
         B, H, W, world = self.B, self.H, self.W, self.env.world
         value = world * B * H * W / 1e6 * steps / elapsed
         launch_s = ev_ms / 1e3 / steps
@@ -496,7 +507,7 @@ class Workload:
                              "frac": round(vi / VALU_PEAK_LANE_INSTR_PER_S, 4), "min_lane_instr_per_px": VALU_MIN_LANE_INSTR_PER_PX,
                              "note": "minimal vector work of the network per pixel (2,808 GELUs x 4 + conversions + LayerNorm; the 16,848 depthwise MACs run on the matrix pipe) "
                                      "x pixels / step time against 1,024 SIMDs x 16 lanes x 2.4 GHz; measured: see `valu_measured` (PMC SQ_INSTS_VALU, profiles/)"}}
-            dom = self.dominant_kernel()
+            dom = self.dominant_kernel() if dominant else None
             if dom:
                 roof["dominant_kernel"] = dom
         else:
@@ -747,7 +758,7 @@ def worker(args):
     elapsed_local = wl.elapsed_local
     if args.dump_outputs and env.rank == 0:  # before parity(), which runs the MST++ route once more into the same output
         log(f"bench.py: outputs of the last timed step -> {args.dump_outputs}: {dump_outputs(wl.outputs(), args.dump_outputs)}")
-    rep = wl.report(steps, warmup, elapsed, ev_ms)
+    rep = wl.report(steps, warmup, elapsed, ev_ms, dominant=args.full)
     result = {
         "metric": "megapixels/sec per-frame pipeline",
         "value": rep["value"], "unit": "MP/s", "n_gpus": env.world, "steps": steps, "warmup": warmup, "ramp_ms": args.ramp_ms,
@@ -768,7 +779,7 @@ def worker(args):
         result["ranks_seen"] = int(seen.item())
         result["ms_per_step_ranks"] = {"min": round(float(lo.item()), 4), "max": round(float(hi.item()), 4)}
     lead = env.rank == 0 and env.world == 1
-    if lead:
+    if args.full and lead:
         ok, stats = wl.parity()
         result["parity_checked"] = ok
         if stats:
@@ -779,13 +790,13 @@ def worker(args):
             result["e2e_pcie"] = wl.e2e_pcie()
     wl.close()
     del wl
-    if not single and not args.no_legs:
+    if args.full and not single and not args.no_legs:
         legs = {}
         for leg in HEADLINE_LEGS:
             w2 = Workload(leg, env)
             k = int(env.max_over_ranks(float(w2.steps_for(1.2))))  # the same K on every rank
             el, ev = w2.time(k, 3, args.ramp_ms)
-            r = w2.report(k, 3, el, ev)
+            r = w2.report(k, 3, el, ev, dominant=True)
             if lead:
                 ok, stats = w2.parity()
                 r["parity_checked"] = ok
@@ -799,7 +810,7 @@ def worker(args):
             w2.close()
             del w2
         result["workloads"] = legs
-    if not single and not args.no_e2e:
+    if args.full and not single and not args.no_e2e:
         result["c4_stream"] = c4_stream(env, args.stream_frames)
     if env.rank == 0:
         print(json.dumps(result), flush=True)

@@ -336,13 +336,13 @@ def test_image_renderer_surface(tmp_path):
 
 
 def test_bench_dump_outputs_is_the_timed_path(tmp_path, oracle):
-    """bench.py --dump-outputs: the result line counts exactly --steps timed steps and reports ms_per_step, and the dump is the timed
+    """bench.py --full --dump-outputs: the result line counts exactly --steps timed steps and reports ms_per_step, and the dump is the timed
     step's output (dog, one 1080p frame: bit-exact against the oracle on the same seeded frame)."""
     from animal_vision_amd.synthetic import noise_frame
 
     d = str(tmp_path / "dump")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "dog_1080p", "--batch", "1", "--steps", "4", "--warmup", "1",
-                          "--ramp-ms", "0", "--no-cpu-baseline", "--no-e2e", "--dump-outputs", d], capture_output=True, text=True, timeout=600)
+                          "--ramp-ms", "0", "--full", "--no-cpu-baseline", "--no-e2e", "--dump-outputs", d], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert r["steps"] == 4 and r["ms_per_step"] > 0 and r["parity_checked"] is True
@@ -350,3 +350,17 @@ def test_bench_dump_outputs_is_the_timed_path(tmp_path, oracle):
     assert got.dtype == np.float32 and got.shape == (1, 1080, 1920, 3)
     _, want = oracle.dichromat_visualize(oracle.DICHROMATS["dog"], noise_frame(0, 1080, 1920))
     assert np.array_equal(got[0], want.astype(np.float32))
+
+
+def test_bench_plain_run_times_only(tmp_path):
+    """A plain bench.py run (no --full) prints the headline fields and nothing that needs runs of its own: no parity, CPU baseline or
+    PCIe-inclusive leg.  Its dump is the timed step's output, as with --full."""
+    d = str(tmp_path / "dump")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "dog_1080p", "--batch", "1", "--steps", "3", "--warmup", "1",
+                          "--ramp-ms", "0", "--dump-outputs", d], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert r["metric"] == "megapixels/sec per-frame pipeline" and r["unit"] == "MP/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert not {"parity_checked", "parity_stats", "cpu_baseline", "e2e_pcie", "workloads", "c4_stream"} & set(r)
+    assert np.load(os.path.join(d, "out.npy")).shape == (1, 1080, 1920, 3)

@@ -146,3 +146,14 @@ def test_bench_dump_outputs_is_seeded_and_capped(tmp_path):
 def test_bench_rejects_zero_steps():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "0"], capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and "--steps" in out.stderr
+
+
+def test_bench_full_is_opt_in():
+    """A plain run times the steps and prints the line; parity, CPU baselines, legs and streams wait for --full.  The --no-* switches
+    still parse: they narrow a --full run."""
+    import bench
+
+    plain = bench.parse_args(["--steps", "5", "--warmup", "2"])
+    assert plain.full is False and (plain.steps, plain.warmup) == (5, 2)
+    full = bench.parse_args(["--full", "--no-cpu-baseline", "--no-e2e", "--no-legs"])
+    assert full.full is True and full.no_cpu_baseline and full.no_e2e and full.no_legs

@@ -8,7 +8,7 @@ for r in $(seq $R); do
   for v in "$@" cur; do
     if [ $v = cur ]; then cp /tmp/libavx_cur.so $L/libavx.so; else cp $L/libavx_$v.so $L/libavx.so; fi
     for wl in $WLS; do
-      timeout -k 10 200 python bench.py --workload $wl --no-cpu-baseline --no-e2e --no-legs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$v $wl', d['value'], d['ms_per_step'], d['parity_checked'])"
+      timeout -k 10 200 python bench.py --full --workload $wl --no-cpu-baseline --no-e2e --no-legs 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$v $wl', d['value'], d['ms_per_step'], d['parity_checked'])"
     done
   done
 done

@@ -47,8 +47,8 @@ for f in glob.glob("gpurun_out/pmc_mst/p*/**/*counter_collection.csv", recursive
     # the last kernel of a frame: k_map_encode (plane schedule of the honeybee tail) or k_bee_tile<.., .., 1, ..> (its map + encode stage)
     marks = [i for i, r in enumerate(rows) if "k_map_encode" in r["Kernel_Name"] or re.search(r"k_bee_tile<\d, \d, 1, ", r["Kernel_Name"])]
     if len(marks) >= 2:
-        # a steady frame: the window after the warm-up frame's mark (the LAST window also holds bench.py's own 20 extra launches of the
-        # dominant kernel and the parity check's forward pass)
+        # a steady frame: the window after the warm-up frame's mark (under bench.py --full the LAST window also holds its own 20 extra
+        # launches of the dominant kernel and the parity check's forward pass)
         lo, hi = (marks[1], marks[2]) if len(marks) >= 3 else (marks[-2], marks[-1])
         win = rows[lo + 1: hi + 1]
         tot[rows[0]["Counter_Name"]] = sum(float(r["Counter_Value"]) for r in win)

@@ -3,6 +3,7 @@
 // the shared building blocks (decode table, cubic panorama warp, area/linear resize, plane blur, Sobel,
 // radix-select percentile, threshold encode).  Float contract: within 1e-4 relative of the reference; the
 // categorical `argmax` of :202 can differ where two band maps tie to within rounding.
+#include <cfloat>
 #include <cmath>
 #include <type_traits>
 #include <vector>
@@ -288,13 +289,23 @@ __global__ __launch_bounds__(kMT) void k_prep_render(const float* __restrict__ l
 // :226-242 the polarisation gain of one pixel from its Sobel pair.  cos(2 theta) and sin(2 theta) of theta = atan2(gy, gx) are taken algebraically,
 // (gx^2 - gy^2) / (gx^2 + gy^2) and 2 gx gy / (gx^2 + gy^2) (1, 0 for a zero gradient, where atan2 gives 0): the same functions of the gradient's direction to ~2 ulp
 // without atan2f + cosf + sinf (~100 of this stage's ~250 instructions per pixel; round 3).  cos2g / sin2g arrive as float32((1 - mix) * global).
+// Below FLT_MIN, r2 is subnormal or has underflowed to 0 while the gradient is not 0: 1 / r2 would overflow (inf, then inf * 0 = NaN), so the
+// direction is taken from the components scaled by max(|gx|, |gy|) instead (r2 of those lies in [1, 2]).  Normal-range r2 is untouched.
 __device__ __forceinline__ float pol_gain_of(float gxv, float gyv, float cos2g, float sin2g, float mix, float lin_s, float lin_gamma, float circ_s) {
     const float r2 = gxv * gxv + gyv * gyv;
     float c2 = 1.0f, s2 = 0.0f;
-    if (r2 > 0.f) {
+    if (r2 >= FLT_MIN) {
         const float inv = 1.0f / r2;
         c2 = (gxv * gxv - gyv * gyv) * inv;
         s2 = (2.0f * gxv * gyv) * inv;
+    } else {
+        const float m = fmaxf(fabsf(gxv), fabsf(gyv));
+        if (m > 0.f) {
+            const float ux = gxv / m, uy = gyv / m;
+            const float inv = 1.0f / (ux * ux + uy * uy);
+            c2 = (ux * ux - uy * uy) * inv;
+            s2 = (2.0f * ux * uy) * inv;
+        }
     }
     const float cm = cos2g + mix * c2, sm = sin2g + mix * s2;
     const float al = powf(clip01f(0.5f * (cm + 1.0f)), lin_gamma);

@@ -45,6 +45,18 @@ class DichromatDesc(ctypes.Structure):
     ]
 
 
+class DichromatLaunchInfo(ctypes.Structure):
+    """avx_dichromat_launch_info (include/avx.h): kernel family and launch geometry of the last avx_dichromat_u8 call."""
+
+    _fields_ = [("struct_size", ctypes.c_uint32)] + [
+        (n, ctypes.c_int32)
+        for n in ("family", "R", "f64", "NG", "spec", "sw", "nstrips", "ch", "nchunks", "xcd_remap", "narrow", "tuned_now", "grid", "per_cu")
+    ]
+
+
+AVX_LAUNCH_FAMILIES = ("none", "reference", "tiled", "march", "streak")  # AVX_LAUNCH_* (include/avx.h)
+
+
 class HoneybeeDesc(ctypes.Structure):
     """avx_honeybee_desc (include/avx.h)."""
 
@@ -241,6 +253,7 @@ _SIGS = {
     "avx_timer_start": (_i, [_vp, _vp]),
     "avx_timer_stop": (_i, [_vp, _vp, ctypes.POINTER(ctypes.c_float)]),
     "avx_dichromat_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(DichromatDesc), _vp]),
+    "avx_dichromat_last_launch": (_i, [_vp, ctypes.POINTER(DichromatLaunchInfo)]),
     "avx_get_table": (_i, [_i, _vp, _sz]),
     "avx_percentile": (_i, [_vp, _vp, _sz, ctypes.c_double, ctypes.POINTER(ctypes.c_double), _vp]),
     "avx_spectral_integrate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),

@@ -68,8 +68,11 @@ struct avx_ctx {
     // Measured launch geometry of the marching kernels (dichromat_march.hip): rows-per-workgroup split that was
     // fastest for (kernel configuration, batch, frame size), found by timing the candidates on the first call.
     struct tuned { uint64_t key; int nchunks; };
-    tuned march_tuned[64] = {};
+    static constexpr int kMarchTuned = 128;  // 3 entries per measured shape (workgroup width + the row split of either width)
+    tuned march_tuned[kMarchTuned] = {};
     int n_march_tuned = 0;
+    int n_march_seeded = 0;          // the first entries are the seeded table: never evicted; the rest are oldest first
+    avx_dichromat_launch_info last_launch = {};  // avx_dichromat_last_launch: what the last avx_dichromat_u8 call ran (host words only)
     // Frame lanes (uv.hip): the UV tail of a frame is ~10 dependent launches of 7-25 us each, none of which fills the GPU at
     // 1080p; independent frames of a batch are therefore enqueued round-robin on these internal streams (forked from and
     // joined back into the caller's stream with events), each with its own workspace, so their kernels overlap.

@@ -179,6 +179,10 @@ int launch_simple(avx_ctx* ctx, DichromatArgs& a, const avx_dichromat_desc* d, h
     AVX_HIP(ctx, hipFuncSetAttribute((const void*)kmain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     AVX_HIP(ctx, hipFuncSetAttribute((const void*)kdark, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     AVX_HIP(ctx, hipMemsetAsync(a.flags, 0, sizeof(uint32_t) * a.n_frames, s));
+    ctx->last_launch.family = AVX_LAUNCH_REFERENCE;
+    ctx->last_launch.R = a.r;
+    ctx->last_launch.f64 = sizeof(T) == 8;
+    ctx->last_launch.grid = grid;
     hipLaunchKernelGGL(kmain, dim3(grid), dim3(kThreads), lds, s, a, taps);
     AVX_HIP(ctx, hipGetLastError());
     // Fix-up for frames whose every byte is <= 1 (get_normalized_image does not divide those by 255):
@@ -567,6 +571,11 @@ int launch_tiled(avx_ctx* ctx, DichromatArgs& a, const avx_dichromat_desc* d, co
     AVX_HIP(ctx, hipFuncSetAttribute((const void*)kmain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     AVX_HIP(ctx, hipFuncSetAttribute((const void*)kdark, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     AVX_HIP(ctx, hipMemsetAsync(a.flags, 0, sizeof(uint32_t) * a.n_frames, s));
+    ctx->last_launch.family = AVX_LAUNCH_TILED;
+    ctx->last_launch.R = R;
+    ctx->last_launch.f64 = sizeof(T) == 8;
+    ctx->last_launch.grid = grid;
+    ctx->last_launch.per_cu = per_cu;
     hipLaunchKernelGGL(kmain, dim3(grid), dim3(NT), lds, s, a, taps, qc);
     AVX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(kdark, dim3(grid), dim3(NT), lds, s, a, taps, qc);
@@ -588,6 +597,7 @@ extern "C" int avx_dichromat_u8(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* ou
                 "avx_dichromat_u8: unknown color_mode %d", d->color_mode);
     AVX_REQUIRE(ctx, d->post_mode >= AVX_POST_NONE && d->post_mode <= AVX_POST_STREAK,
                 "avx_dichromat_u8: unknown post_mode %d", d->post_mode);
+    ctx->last_launch = avx_dichromat_launch_info{};  // filled by whichever launcher runs (avx_dichromat_last_launch)
     if (n_frames == 0) return AVX_OK;
     AVX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = avx_pick_stream(ctx, stream);
@@ -682,4 +692,13 @@ extern "C" int avx_dichromat_u8(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* ou
         return launch_tiled<double, AVX_COLOR_CAT_MERGE, 4, 64, 48, 512, NF>(ctx, a, d, qc, s);
     }
     return launch_simple<double, AVX_COLOR_CAT_MERGE>(ctx, a, d, s);
+}
+
+extern "C" int avx_dichromat_last_launch(avx_ctx* ctx, avx_dichromat_launch_info* out) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, out != nullptr && out->struct_size == sizeof(avx_dichromat_launch_info),
+                "avx_dichromat_last_launch: out is NULL or struct_size mismatch (ABI %d)", AVX_ABI_VERSION);
+    *out = ctx->last_launch;
+    out->struct_size = sizeof(avx_dichromat_launch_info);
+    return AVX_OK;
 }

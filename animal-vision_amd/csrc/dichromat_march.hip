@@ -647,6 +647,31 @@ __global__ __launch_bounds__(3 * NG + (SPEC ? 64 : 0), MINW) void dichromat_marc
 
 constexpr int kNarrowStrips = 1 << 16;  // flag bit in a remembered launch geometry: use the narrowed strips
 
+// The (radius, type, batch, frame size) a remembered key belongs to, whichever of the two key kinds it is (chunk_key /
+// width_key below): bit 62 marks a width key.
+uint64_t tuned_shape(uint64_t key) {
+    const bool wk = (key >> 62) & 1;
+    const uint64_t f64 = wk ? (key >> 61) & 1 : key >> 63, R = wk ? (key >> 52) & 0xf : (key >> 56) & 0xf;
+    return (f64 << 48) | (R << 44) | (key & ((1ull << 44) - 1));
+}
+
+// Remember a measured geometry.  The table is small and a long-lived context may see any number of shapes: when it is full
+// the OLDEST measured shape makes room -- all its entries together (its width key and its chunk keys), so that a shape is
+// either known or measured again in full -- and the seeded entries stay.  (Before, a result that did not fit was dropped,
+// and every later call at such a shape ran the whole timing pass again.)
+void avx_march_remember(avx_ctx* ctx, uint64_t key, int value) {
+    for (int i = 0; i < ctx->n_march_tuned; ++i)
+        if (ctx->march_tuned[i].key == key) { ctx->march_tuned[i].nchunks = value; return; }
+    if (ctx->n_march_tuned >= avx_ctx::kMarchTuned && ctx->n_march_seeded < ctx->n_march_tuned) {
+        const uint64_t victim = tuned_shape(ctx->march_tuned[ctx->n_march_seeded].key);
+        int n = ctx->n_march_seeded;
+        for (int i = ctx->n_march_seeded; i < ctx->n_march_tuned; ++i)
+            if (tuned_shape(ctx->march_tuned[i].key) != victim) ctx->march_tuned[n++] = ctx->march_tuned[i];
+        ctx->n_march_tuned = n;
+    }
+    if (ctx->n_march_tuned < avx_ctx::kMarchTuned) ctx->march_tuned[ctx->n_march_tuned++] = {key, value};
+}
+
 template <typename T, int COLOR, int R, int SY, int XPT, int NG, int MINW, int NFIX, bool SPEC = false>
 int launch_march(avx_ctx* ctx, DichromatArgs& a, const avx_dichromat_desc* d, const QuantCoarse& qc, hipStream_t s) {
     using C = MarchCfg<T, R, SY, XPT, NG, SPEC>;
@@ -675,7 +700,9 @@ int launch_march(avx_ctx* ctx, DichromatArgs& a, const avx_dichromat_desc* d, co
         if (sw_narrow < 32 || sw_narrow >= C::SW) sw_narrow = 0;
     }
     long cols = 0;
+    int cap_used = 0;
     auto set_strips = [&](int sw_cap) {
+        cap_used = sw_cap;
         g.nstrips = (a.W + sw_cap - 1) / sw_cap;
         g.sw = ((a.W + g.nstrips - 1) / g.nstrips + C::XPT - 1) / C::XPT * C::XPT;
         // prefer 16-px multiples (16-byte output vectors) when they fit under the cap, even if the last strip comes out narrower
@@ -718,6 +745,7 @@ int launch_march(avx_ctx* ctx, DichromatArgs& a, const avx_dichromat_desc* d, co
         if (!found && (size_t)a.n_frames * a.H * a.W >= (size_t)256 * 1024) {  // tiny launches: not worth timing
             const long cand[] = {nchunks, 1, 2, 3, 4, 6, 8, 12, 16, 24};
             float best_ms = 3.4e38f;
+            ctx->last_launch.tuned_now = 1;
             hipEvent_t e0, e1;
             AVX_HIP(ctx, hipEventCreate(&e0));
             AVX_HIP(ctx, hipEventCreate(&e1));
@@ -763,7 +791,7 @@ int launch_march(avx_ctx* ctx, DichromatArgs& a, const avx_dichromat_desc* d, co
             }
             (void)hipEventDestroy(e0);
             (void)hipEventDestroy(e1);
-            if (found && ctx->n_march_tuned < 64) ctx->march_tuned[ctx->n_march_tuned++] = {tkey, found};
+            if (found) avx_march_remember(ctx, tkey, found);
             if (getenv("AVX_TUNE_LOG")) fprintf(stderr, "[avx tune] chunks: f64=%d R=%d NG=%d frames=%d H=%d W=%d -> %d%s (%.3f ms)\n", (int)(sizeof(T) == 8), R, NG, a.n_frames, a.H, a.W, found & (kNarrowStrips - 1), (found & kNarrowStrips) ? " narrow strips" : "", best_ms);
         }
         if (found) nchunks = found & (kNarrowStrips - 1);
@@ -793,6 +821,22 @@ int launch_march(avx_ctx* ctx, DichromatArgs& a, const avx_dichromat_desc* d, co
         }
     }
     AVX_HIP(ctx, hipMemsetAsync(a.flags, 0, sizeof(uint32_t) * a.n_frames, s));
+    {   // avx_dichromat_last_launch (tuned_now is left as the timing passes of this call set it)
+        avx_dichromat_launch_info& li = ctx->last_launch;
+        li.family = AVX_LAUNCH_MARCH;
+        li.R = R;
+        li.f64 = sizeof(T) == 8;
+        li.NG = NG;
+        li.spec = SPEC ? 1 : 0;
+        li.sw = g.sw;
+        li.nstrips = g.nstrips;
+        li.ch = g.ch;
+        li.nchunks = g.nchunks;
+        li.xcd_remap = g.xcd_remap;
+        li.narrow = cap_used < C::SW_CAP ? 1 : 0;
+        li.grid = (int)total;
+        li.per_cu = per_cu;
+    }
     hipLaunchKernelGGL(kmain, dim3((unsigned)total), dim3(kMarchThreads), lds, s, a, taps, qc, g);
     AVX_HIP(ctx, hipGetLastError());
     // Fix-up for frames whose every byte is <= 1 (get_normalized_image does not divide those by 255);
@@ -825,10 +869,11 @@ void avx_march_seed_tuned(avx_ctx* ctx) {
     };
     if (getenv("AVX_MARCH_NOSEED")) return;  // measure everything on first use (re-deriving the table below)
     for (const auto& e : kSeed) {
-        if (ctx->n_march_tuned + 2 > 64) break;
+        if (ctx->n_march_tuned + 2 > avx_ctx::kMarchTuned) break;
         ctx->march_tuned[ctx->n_march_tuned++] = {width_key(e.f64, e.R, e.frames, e.H, e.W), e.NG};
         ctx->march_tuned[ctx->n_march_tuned++] = {chunk_key(e.f64, e.R, e.NG, e.frames, e.H, e.W), e.chunks};
     }
+    ctx->n_march_seeded = ctx->n_march_tuned;
 }
 
 static int march_dispatch(avx_ctx* ctx, DichromatArgs& a, const avx_dichromat_desc* d, bool f64_cat, bool ng64, hipStream_t s) {
@@ -877,6 +922,7 @@ int avx_launch_dichromat_march(avx_ctx* ctx, DichromatArgs& a, const avx_dichrom
     hipEvent_t e0, e1;
     AVX_HIP(ctx, hipEventCreate(&e0));
     AVX_HIP(ctx, hipEventCreate(&e1));
+    ctx->last_launch.tuned_now = 1;
     float ms[2] = {3.4e38f, 3.4e38f};
     int rc = AVX_OK;
     for (int v = 0; v < 2 && rc == AVX_OK; ++v) {
@@ -893,7 +939,7 @@ int avx_launch_dichromat_march(avx_ctx* ctx, DichromatArgs& a, const avx_dichrom
     (void)hipEventDestroy(e1);
     if (rc) return rc;
     const bool pick64 = ms[0] <= ms[1];
-    if (ctx->n_march_tuned < 64) ctx->march_tuned[ctx->n_march_tuned++] = {key, pick64 ? 64 : 128};
+    avx_march_remember(ctx, key, pick64 ? 64 : 128);
     if (getenv("AVX_TUNE_LOG")) fprintf(stderr, "[avx tune] width: f64=%d R=%d frames=%d H=%d W=%d -> NG=%d (%.3f vs %.3f ms)\n", (int)f64_cat, a.r, a.n_frames, a.H, a.W, pick64 ? 64 : 128, ms[0], ms[1]);
     return march_dispatch(ctx, a, d, f64_cat, pick64, s);
 }

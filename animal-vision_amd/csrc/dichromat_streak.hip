@@ -294,6 +294,9 @@ int avx_launch_dichromat_streak(avx_ctx* ctx, avx_ws* ws, DichromatArgs& a, cons
     const int grid = (int)(rows < cap ? rows : cap);
     if (getenv("AVX_TUNE_LOG")) fprintf(stderr, "[avx streak] lds=%zu occupancy=%d workgroups/CU grid=%d\n", lds, per_cu, grid);
     AVX_HIP(ctx, hipMemsetAsync(a.flags, 0, sizeof(uint32_t) * a.n_frames, s));
+    ctx->last_launch.family = AVX_LAUNCH_STREAK;
+    ctx->last_launch.grid = grid;
+    ctx->last_launch.per_cu = per_cu;
     hipLaunchKernelGGL(kmain, dim3(grid), dim3(kST), lds, s, a, st, qc);
     AVX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(kdark, dim3(grid), dim3(kST), lds, s, a, st, qc);

@@ -185,6 +185,18 @@ class DichromatOp:
             self.desc.streak_rows_host = self._streak.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
         ctx._check(lib.avx_dichromat_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, ctypes.byref(self.desc), ctx._s(stream)))
 
+    def last_launch(self) -> dict:
+        """Which kernel and launch geometry the last dichromat call on this op's context ran (avx_dichromat_last_launch; host
+        state only).  `family` is one of "reference", "tiled", "march", "streak" ("none": no launch yet); the other keys are
+        the integer fields of avx_dichromat_launch_info."""
+        ctx = self._ctx()
+        info = _lib.DichromatLaunchInfo()
+        info.struct_size = ctypes.sizeof(info)
+        ctx._check(lib.avx_dichromat_last_launch(ctx._h, ctypes.byref(info)))
+        out = {n: int(getattr(info, n)) for n, _ in info._fields_[2:]}
+        out["family"] = _lib.AVX_LAUNCH_FAMILIES[info.family]
+        return out
+
     def __call__(self, image: np.ndarray) -> np.ndarray:
         """uint8 HxWx3 (or NxHxWx3) host frame(s) -> same shape uint8, via upload/kernel/download."""
         if image.dtype != np.uint8:

@@ -15,7 +15,8 @@
  *     a torch.cuda.Stream.cuda_stream value is accepted as is; every launch is asynchronous on it, with ONE exception:
  *     the first avx_dichromat_u8 call for a (kernel configuration, batch, frame size) that is not in the seeded table
  *     times its candidate launch geometries on the caller's frames (~40 ms, blocking; the results are the same for every
- *     candidate) and remembers the winner in the ctx -- AVX_MARCH_CHUNKS / AVX_MARCH_NG pin a geometry and skip it;
+ *     candidate) and remembers the winner in the ctx (the ~38 most recently measured shapes next to the seeded ones; an
+ *     older shape is measured again when it returns) -- AVX_MARCH_CHUNKS / AVX_MARCH_NG pin a geometry and skip it;
  *   - frame/plane pointers are DEVICE pointers unless the parameter name ends in `_host`;
  *     the caller owns them; ctx owns only its scratch and its constant tables;
  *   - images are C-contiguous HWC (H x W x 3), batches are N such frames back to back.
@@ -110,6 +111,29 @@ typedef struct avx_dichromat_desc {
 
 int avx_dichromat_u8(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_hwc, int n_frames, int H, int W,
                      const avx_dichromat_desc* desc, void* stream);
+
+/* Which kernel and launch geometry the LAST avx_dichromat_u8 call on this ctx used (host state only, no device work; filled
+ * by every call that got as far as choosing a kernel).  Read-only: for tests and tools that pin a geometry (AVX_MARCH_NG,
+ * AVX_MARCH_CHUNKS, AVX_MARCH_SWCAP) and need to see that the pin took effect.  Fields that do not apply to a family are 0. */
+enum { AVX_LAUNCH_NONE = 0, AVX_LAUNCH_REFERENCE = 1, AVX_LAUNCH_TILED = 2, AVX_LAUNCH_MARCH = 3, AVX_LAUNCH_STREAK = 4 };
+
+typedef struct avx_dichromat_launch_info {
+    uint32_t struct_size;  /* sizeof(avx_dichromat_launch_info), set by the caller                                  */
+    int32_t family;        /* AVX_LAUNCH_*                                                                           */
+    int32_t R;             /* blur radius (ksize / 2); 0 for the row-gain, streak and no-post stages                 */
+    int32_t f64;           /* 1: float64 arithmetic (AVX_COLOR_CAT_MERGE), 0: float32                                */
+    int32_t NG;            /* marching: column groups per workgroup (64: 192 compute threads, 128: 384)              */
+    int32_t spec;          /* marching: 1 = wave-specialised form (one producer wave more)                           */
+    int32_t sw, nstrips;   /* marching: nominal strip width in pixels, strips per frame row                          */
+    int32_t ch, nchunks;   /* marching: rows per chunk, row chunks per (frame, strip)                                */
+    int32_t xcd_remap;     /* marching: 1 = workgroups b and b + 8 are neighbours                                    */
+    int32_t narrow;        /* marching: 1 = the narrowed strips (tuner's choice or AVX_MARCH_SWCAP below the full width) */
+    int32_t tuned_now;     /* marching: 1 = this call ran a timing pass (workgroup width and / or row chunks)        */
+    int32_t grid;          /* workgroups launched (every family)                                                     */
+    int32_t per_cu;        /* streak, tiled, marching: resident workgroups per CU the grid / fallback was sized with */
+} avx_dichromat_launch_info;
+
+int avx_dichromat_last_launch(avx_ctx* ctx, avx_dichromat_launch_info* out);
 
 /* ---- UV / spectral path: uv_helpers.py, uv_mappers.py, ml/classic_rgb_to_hsi, animals/honeybee.py ----
  *

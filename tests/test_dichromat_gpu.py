@@ -3,6 +3,7 @@ uint8 in, uint8 out: BIT-EXACT everywhere."""
 import numpy as np
 import pytest
 
+import _march_geometry as G
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -191,3 +192,64 @@ def test_cat_float_frames(av, oracle, warp):
         assert out.dtype == frame.dtype == want.dtype and out.shape == frame.shape and base.dtype == frame.dtype
         np.testing.assert_allclose(out, want, rtol=0, atol=1e-4)
         np.testing.assert_allclose(base, want_base, rtol=0, atol=1e-4 * max(1.0, float(frame.max())))
+
+
+# ---- all 20 species at video sizes, auto route (which kernel ran is read back, not assumed) -------------------------------
+
+STREAK = ["sheep", "pig", "cow", "goat", "horse", "rabbit", "panda", "deer", "kangaroo"]
+
+
+def _family(name, aligned):
+    """The kernel family the auto route takes: the streak kernel for the streak species, the reference kernel for the row
+    gain (rat), the marching kernel for a Gaussian species when the batch is a whole number of dwords, else the 2-D tiled one."""
+    return "streak" if name in STREAK else ("reference" if name == "rat" else ("march" if aligned else "tiled"))
+
+
+def _video_case(av, oracle, name, seed, H, W, variant=0):
+    frame = G.frame(seed, H, W)
+    want = G.oracle_bytes(oracle, name, oracle.DICHROMATS[name], (seed, H, W), frame)
+    sp = _species(av, name)
+    op = sp._operator()
+    op.desc.variant = variant
+    base, got = sp.visualize(frame)
+    li = op.last_launch()
+    G.assert_same_bytes(got, want, f"{name} {H}x{W} variant {variant}", li)
+    return li
+
+
+@pytest.mark.parametrize("name", GAUSS)
+@pytest.mark.parametrize("shape", [(1080, 1920), (1079, 1917)])
+def test_every_species_at_video_size(av, oracle, name, shape):
+    """1080p, and 1079 x 1917 whose byte count is odd: the marching kernel declines it and the Gaussian species take the
+    2-D tiled kernel (ragged tiles on both edges); the streak kernel takes its byte-granular form."""
+    H, W = shape
+    aligned = (H * W * 3) % 4 == 0
+    li = _video_case(av, oracle, name, G.SEED_1080P if aligned else 41, H, W)
+    assert li["family"] == _family(name, aligned), li
+
+
+@pytest.mark.parametrize("name", ["dog", "cat", "squirrel", "sheep", "rat", "pig"])
+def test_one_species_per_kernel_family_at_4k(av, oracle, name):
+    li = _video_case(av, oracle, name, G.SEED_4K, 2160, 3840)
+    assert li["family"] == _family(name, True), li
+
+
+@pytest.mark.parametrize("variant,family", [(1, "reference"), (2, "tiled")])
+@pytest.mark.parametrize("name", ["squirrel", "cat", "lion", "wolf", "bear", "raccoon", "dog"])  # R = 3, 4, 5, 6, 7, 8, 14
+def test_reference_and_tiled_kernels_at_1080p(av, oracle, name, variant, family):
+    li = _video_case(av, oracle, name, G.SEED_1080P, 1080, 1920, variant)
+    assert li["family"] == family, li
+
+
+@pytest.mark.parametrize("name", ["sheep", "rabbit"])  # streak; streak + chroma compression
+def test_streak_kernel_edges_at_video_scale(av, oracle, name):
+    """Tall-narrow and short-wide frames (narrower than the 13-tap row kernel, one column, one row), and more than twice as
+    many rows as the persistent grid has workgroups (every workgroup loops at least twice, the last round is ragged)."""
+    for H, W in [(2160, 13), (2160, 1), (1, 3840)]:
+        li = _video_case(av, oracle, name, 42, H, W)
+        assert li["family"] == "streak" and 1 <= li["grid"] <= H, li
+    grid = _video_case(av, oracle, name, 42, 2160, 1920)["grid"]  # one resident set: CUs x workgroups per CU at this row length
+    assert 0 < grid <= 2160
+    H = 2 * grid + 5
+    li = _video_case(av, oracle, name, 42, H, 1920)
+    assert li["family"] == "streak" and li["grid"] == grid and H > 2 * li["grid"] and li["per_cu"] >= 1, li

@@ -7,7 +7,7 @@
 //                       reaches memory: a workgroup owns a 16 x 16 pixel tile and keeps the hidden map of its 18 x 18 halo
 //                       region in LDS (the 1-pixel halo is recomputed: 27 % more first-GEMM + GELU work, no HBM traffic).
 //
-// Schedule (512 threads = 8 waves, one workgroup per CU, persistent over tiles; v_mfma_f32_32x32x16_f16):
+// Schedule (512 threads = 8 waves, one workgroup per CU, persistent over tiles in the XCD-aware order of mst_tile_order.h; v_mfma_f32_32x32x16_f16):
 //   phase 0  LayerNorm of the 324 halo pixels (lane pair = one pixel, float32 statistics over the 31 real channels of each
 //            32-wide group), normalised rows to LDS as float16.  The raw rows were fetched into registers BEFORE the
 //            previous tile's phase 2, so their HBM latency is off the critical path.
@@ -28,9 +28,11 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "avx_internal.h"
 #include "mst_common.h"
+#include "mst_tile_order.h"
 
 namespace {
 
@@ -55,29 +57,13 @@ constexpr int kFfnNGRP = (HS * (kFfnTH + 2) + 31) / 32;
 __device__ __forceinline__ float16_t mfma16(half8_t a, half8_t b, float16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
 struct Tile { int x0, y0; long b; };
-// Tiles blockIdx.x, + gridDim.x, ... of a (frames x ty x tx) grid WITHOUT a division per tile: the coordinates advance by the step's own
-// (dx, dy, db) with carries -- scalar adds and compares.  tile_of(t) = (t % tx, (t / tx) % ty, t / (tx ty)) as 64-bit divisions cost ~150
-// vector instructions per tile and wave (there is no scalar divide): a fifth of the attention tail's instruction stream.
-struct TileWalk {
-    int xi, yi, dx, dy, tx, ty;
-    long b, db;
-    __device__ __forceinline__ void init(long t0, long step, int tx_, int ty_) {
-        tx = tx_; ty = ty_;
-        auto uni = [](long v) { return (long)(unsigned)__builtin_amdgcn_readfirstlane((int)v) | (long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32; };  // the divisions run on the vector unit
-        xi = (int)uni(t0 % tx); yi = (int)uni((t0 / tx) % ty); b = uni(t0 / ((long)tx * ty));
-        dx = (int)uni(step % tx); dy = (int)uni((step / tx) % ty); db = uni(step / ((long)tx * ty));
-    }
-    __device__ __forceinline__ void advance() {
-        xi += dx;
-        const int cx = xi >= tx ? 1 : 0;
-        xi -= cx ? tx : 0;
-        yi += dy + cx;
-        const int cy = yi >= ty ? 1 : 0;
-        yi -= cy ? ty : 0;
-        b += db + cy;
-    }
-    __device__ __forceinline__ Tile tile(int side) const { return Tile{xi * side, yi * side, b}; }
-};
+// TileWalk (mst_tile_order.h): the tiles of a (frames x ty x tx) grid this workgroup visits, raster or XCD-aware order, WITHOUT a division per tile.
+__device__ __forceinline__ Tile tile_at(const TileWalk& wk, int side_x, int side_y) { return Tile{wk.xi * side_x, wk.yi * side_y, (long)wk.b}; }
+// AVX_MST_TILE_ORDER=raster (read per call, like the AVX_MST_NO_* switches): the round-2 order, so that one process can compare both.  The results do not depend on it.
+int mst_tile_order() {
+    const char* e = getenv("AVX_MST_TILE_ORDER");
+    return e && !strcmp(e, "raster") ? AVX_TILE_ORDER_RASTER : AVX_TILE_ORDER_XCD;
+}
 
 // DWM (round 3): the depthwise 3x3 conv runs on the MATRIX pipe.  A depthwise conv contracts over taps only, so as a matrix product its weight
 // operand is diagonal in the channels; the waste is bounded by letting the 16 rows of a v_mfma_f32_16x16x32_f16 result be 8 channels (one
@@ -98,7 +84,7 @@ template <int C, int HPASS, int MINW, bool DWM, bool STAMP = false, int NW = 8>
 __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* __restrict__ x /*[B][H][W][C]*/, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           float eps, const uint4* __restrict__ w1pack /*[4C/32][C/16][64]*/, const __half* __restrict__ taps /*[9][4C]*/,
                                                           const uint4* __restrict__ w2pack /*[C/32][4C/16][64]*/, __half* __restrict__ out /*[B][H][W][C], != x*/, int B,
-                                                          int H, int W, const uint4* __restrict__ dwpack /*[4C/8][3][64], DWM only*/, unsigned long long* __restrict__ stamps /*STAMP: [blocks][8 waves][8 segments] cycles*/) {
+                                                          int H, int W, const uint4* __restrict__ dwpack /*[4C/8][3][64], DWM only*/, unsigned long long* __restrict__ stamps /*STAMP: [blocks][8 waves][8 segments] cycles*/, int order /*AVX_TILE_ORDER_*/) {
     // tile = TS (16) columns x FTH rows (16; 14 is the measured-and-rejected alternative, see kFfnTH)
     constexpr int FTH = kFfnTH, HSY = FTH + 2, NHALO = HS * HSY, NGRP = (NHALO + 31) / 32;
     constexpr int HID = 4 * C, NPASS = HID / HPASS, KS1 = C / 16, KS2 = HPASS / 16, NT = C / 32, YPITCH = C * 2 + 16, LNV = C / 16;
@@ -131,8 +117,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
         for (int i = tid; i < 9 * HID; i += NTHR) tapl[i] = taps[i];
     for (int i = tid; i < C; i += NTHR) { gl[i] = gamma[i]; gl[C + i] = beta[i]; }
     const int tx = (W + TS - 1) / TS, ty = (H + FTH - 1) / FTH;
-    const long total = (long)B * ty * tx;
-    auto tile_of = [&](long t) { return Tile{(int)(t % tx) * TS, (int)((t / tx) % ty) * FTH, t / ((long)tx * ty)}; };  // (TileWalk measured 2 % slower in THIS kernel: the divisions run on the scalar unit beside a saturated vector unit)
     const float cnt = (float)(NT * 31);
 
     // ---- phase 0, split: fetch the raw rows of this wave's halo pixel groups (wave w: groups w and w + 8) ----
@@ -278,14 +262,15 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
         p1_dst[j] = (g < NGRP && q < NHALO) ? (qc / HS) * RPITCH + (qc % HS) * HPITCH + 32 * h : -1;
         p1_dy[j] = qc / HS - 1; p1_dx[j] = qc % HS - 1;
     }
-    long tile = blockIdx.x;
-    if (tile >= total) return;
-    Tile t = tile_of(tile);
+    TileWalk ahead;  // after its first step: the NEXT tile (this one's coordinates are in t).  (Round 3's pair of 64-bit walks measured 2 % slower than a division per tile in THIS kernel; this one walk of 32-bit state measures level with it: profiles/r04/ab_tile_order.txt)
+    ahead.init(blockIdx.x, gridDim.x, B, ty, tx, order);
+    if (!ahead.live) return;
+    Tile t = tile_at(ahead, TS, FTH);
+    ahead.advance();
     fetch(t);
     __syncthreads();  // tables are in LDS
     layernorm();
     for (;;) {
-        const long next = tile + gridDim.x;
         const bool halo_inside = t.y0 >= 1 && t.y0 + HSY - 1 <= H && t.x0 >= 1 && t.x0 + HS - 1 <= W;  // scalar
         float16_t D[NTW];
 #pragma unroll
@@ -348,7 +333,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
             stamp(1);
             __syncthreads();  // ht complete
             stamp(2);
-            if (PREFETCH && pass == NPASS - 1 && next < total) fetch(tile_of(next));  // next tile's raw rows: in flight during phase 2
+            if (PREFETCH && pass == NPASS - 1 && ahead.live) fetch(tile_at(ahead, TS, FTH));  // next tile's raw rows: in flight during phase 2
             if constexpr (NPASS > 1 && !W2LDS) load_w2(pass);
             if constexpr (DWM) {
                 // ---- phase 2a: depthwise 3x3 on the matrix pipe + GELU, in place in the hidden tile (see the kernel's head comment) ----
@@ -481,9 +466,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
             }
         }
         stamp(6);
-        if (next >= total) break;
-        tile = next;
-        t = tile_of(tile);
+        if (!ahead.live) break;
+        t = tile_at(ahead, TS, FTH);
+        ahead.advance();
         if (!PREFETCH) fetch(t);
         layernorm();  // yt is free: every wave is past the last pass's first barrier, after which nobody reads it
     }
@@ -527,7 +512,6 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_attn_tail(const __half* __res
     for (int i = tid; i < 9 * C; i += kFT) { t2l[i] = taps2[i]; t1l[i] = taps1[i]; }
     for (int i = tid; i < C; i += kFT) bl[i] = bias ? bias[i] : 0.f;
     const int tx = (W + TS - 1) / TS, ty = (H + TS - 1) / TS;
-    const long total = (long)B * ty * tx;
     // phase B role: a wave keeps ONE channel octet (its first-conv taps are wave-uniform LDS reads: broadcasts) and walks pixels of the 18 x 18 map
     const int oct = wave % NO, part = wave / NO, nparts = 8 / NO, per = (MS * MS + nparts - 1) / nparts;
     half8_t mf[NT * NS];
@@ -583,13 +567,11 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_attn_tail(const __half* __res
         const int qc = ok ? q : 0, my = qc / MS, mx = qc % MS;
         b_src[i] = ok ? my * VRP + mx * PP + 16 * oct : -1;  // in vt: the window's first tap; in mt: the pixel itself
     }
-    long tile = blockIdx.x;
-    if (tile >= total) return;
-    TileWalk walk, ahead;  // this tile, the next one
-    walk.init(tile, gridDim.x, tx, ty);
-    ahead = walk;
+    TileWalk ahead;  // after its first step: the NEXT tile (this one's coordinates are in t)
+    ahead.init(blockIdx.x, gridDim.x, B, ty, tx, AVX_TILE_ORDER_RASTER);
+    if (!ahead.live) return;
+    Tile t = tile_at(ahead, TS, TS);
     ahead.advance();
-    Tile t = walk.tile(TS);
     fetch(t);
     for (;;) {
         fill();
@@ -662,8 +644,7 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_attn_tail(const __half* __res
             *reinterpret_cast<uint4*>(mt + b_src[i]) = ov;
         }
         __syncthreads();  // mt complete
-        const long next = tile + gridDim.x;
-        if (next < total) fetch(ahead.tile(TS));  // in flight during phase C
+        if (ahead.live) fetch(tile_at(ahead, TS, TS));  // in flight during phase C
         // ---- phase C: dw2(mid) + v @ M + bias + x for this wave's 32 pixels (rows 2 wave, 2 wave + 1) ----
         {
             const int r = 2 * wave + (p >> 4), c = p & 15;
@@ -723,11 +704,9 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_attn_tail(const __half* __res
                 }
             }
         }
-        if (next >= total) break;
-        tile = next;
-        walk = ahead;
+        if (!ahead.live) break;
+        t = tile_at(ahead, TS, TS);
         ahead.advance();
-        t = walk.tile(TS);
         __syncthreads();  // everyone is done reading vt / mt
     }
 }
@@ -763,7 +742,7 @@ int launch_attn_tail(avx_ctx* ctx, const void* v, const void* x, const void* mpa
 //   * depthwise convs do not mix channels, so after v is complete a wave needs NOBODY ELSE: wave w owns octet w % NOCT (and, where two waves
 //     share an octet, half of the tile's rows: the one mid row pair both halves need is computed by both), runs conv1 -> GELU -> mid (its own
 //     bytes of the LDS map) -> conv2 + projection for its units back to back and stores its 8 bytes per lane and pixel straight to memory with
-//     the residual (requested before the first unit) added: two barriers per tile (v complete; v free), no output staging;
+//     the residual added (C = 32 / 64: from the LDS stash phase A fills, see STASH; C = 128: requested before the first unit): two barriers per tile (v complete; v free), no output staging;
 //   * v is formed from x as it arrives: a lane's prefetched half row of its halo pixel IS its B operand (W_v packed in that K order,
 //     pack_fragments16(halfrow=True)); the x tile never sits in LDS.
 // NW: waves per workgroup (8; 16 for the 62-channel blocks, whose LDS footprint admits one workgroup per CU: two waves per octet as at C = 32, four waves per SIMD)
@@ -771,7 +750,7 @@ template <int C, int TR, int MINW, bool STAMP = false, int NW = 8>
 __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half* __restrict__ x /*[B][H][W][C]*/, const uint4* __restrict__ wvpack /*[C/32][C/16][64], half-row K order*/,
                                                                 const uint4* __restrict__ mpack /*[C/8][C/16][64]*/, const uint4* __restrict__ dw1 /*[C/8][3][64]*/,
                                                                 const uint4* __restrict__ dw2 /*[C/8][3][64]*/, const float* __restrict__ bias /*[C] or NULL*/,
-                                                                __half* __restrict__ out, int B, int H, int W, unsigned long long* __restrict__ stamps /*STAMP: [blocks][8][8]*/) {
+                                                                __half* __restrict__ out, int B, int H, int W, unsigned long long* __restrict__ stamps /*STAMP: [blocks][8][8]*/, int order /*AVX_TILE_ORDER_*/) {
     constexpr int TW = 14, VW = 18, VR = TR + 4, MR = TR + 2, NOCT = C / 8, NK = C / 16, NT = C / 32, NS = C / 16, LNV = C / 16;
     constexpr int PP = C * 2 + 16, RP = (VW * PP + 255) / 256 * 256, MP = 16 * PP;  // pixel pitch; row pitch of v (18 px) and of mid (16 px): multiples of 256 bytes
     constexpr int NTHR = 64 * NW, NG = (VR * VW + 31) / 32, NGW = (NG + NW - 1) / NW;                     // 32-pixel groups of the halo region; per wave
@@ -783,6 +762,12 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
     unsigned char* vt = smem;                                            // [VR][RP]: v on the halo region (zeros outside the image)
     unsigned char* mt = vt + (size_t)VR * RP;                            // [MR][MP]: mid = gelu(dw1(v)), 16 columns; an octet's bytes belong to its wave(s)
     uint4* wvl = reinterpret_cast<uint4*>(mt + (size_t)MR * MP);         // [NT * NS][64]: W_v's fragments (also absorbs the reads of the two unused columns past the last mid row)
+    // STASH (round 4): the residual + x comes from the chip.  The lanes of phase A whose halo pixel lies inside the output tile also put their raw half row of x here, and
+    // the 8 bytes per lane and unit that the stores add are LDS reads: no second request for x (it used to be issued right behind the next tile's prefetch, and waiting for
+    // it -- loads return in order -- meant waiting for that prefetch too).  Pixel pitch PP as in the v map: the 16-byte writes of consecutive pixels and the 8-byte reads of
+    // 16 pixels x 2 halves each cover the banks once.  C = 128 has no room for it (137 KB + 29 KB) and keeps the global read.
+    constexpr bool STASH = C <= 64 && NW == 8;  // (the 16-wave form of the C = 64 A/B is at 128 registers: the extra reads spill there)
+    unsigned char* xs = reinterpret_cast<unsigned char*>(wvl + NT * NS * 64);  // [TR][TW] pixels x PP (+ 2 pixels: lanes 14, 15 of the last row read past it)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 31, h = lane >> 5, n16 = lane & 15, q = lane >> 4;
     // STAMP (AVX_TAIL_STAMPS=1): cycles per segment and wave -- 0 v from x (incl. waiting for the prefetch), 1 barrier, 2 conv1 + GELU, 3 conv2 + projection + stores, 4 barrier
     unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
@@ -795,7 +780,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
     };
     if constexpr (STAMP) tlast = __builtin_readcyclecounter();
     const int tx = (W + TW - 1) / TW, ty = (H + TR - 1) / TR;
-    const long total = (long)B * ty * tx;
     for (int i = tid; i < NT * NS * 64; i += NTHR) wvl[i] = wvpack[i];
     const int o = wave % NOCT, rpo = (wave / NOCT) * NOUT;  // this wave's (first) octet and first row pair
     half8_t a1[3], a2[3], am[NK];
@@ -864,14 +848,11 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
             }
         }
     };
-    long tile = blockIdx.x;
-    if (tile >= total) return;
-    TileWalk walk, ahead;
-    walk.init(tile, gridDim.x, tx, ty);
-    ahead = walk;
+    TileWalk ahead;  // after its first step: the NEXT tile (this one's coordinates are in t)
+    ahead.init(blockIdx.x, gridDim.x, B, ty, tx, order);
+    if (!ahead.live) return;
+    Tile t = tile_at(ahead, TW, TR);
     ahead.advance();
-    auto tile_at = [&](const TileWalk& wk) { return Tile{wk.xi * TW, wk.yi * TR, wk.b}; };
-    Tile t = tile_at(walk);
     fetch(t);
     __syncthreads();  // W_v's fragments are in LDS
     for (;;) {
@@ -894,25 +875,33 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
                     reinterpret_cast<uint4*>(vt + v_dst[gi] + 64 * nt)[1] = __builtin_bit_cast(uint4, w1);
                 }
             }
+            if constexpr (STASH) {
+                const unsigned sr = (unsigned)(p_row[gi] - 2), sc = (unsigned)(p_col[gi] - 2);
+                if (v_dst[gi] >= 0 && sr < (unsigned)TR && sc < (unsigned)TW) {
+                    unsigned char* dst = xs + (sr * TW + sc) * PP + h * C;
+#pragma unroll
+                    for (int v = 0; v < LNV; ++v) *reinterpret_cast<uint4*>(dst + 16 * v) = pre[gi][v];
+                }
+            }
         }
         stamp(0);
         __syncthreads();  // v complete
         stamp(1);
-        const long next = tile + gridDim.x;
-        if (next < total) fetch(tile_at(ahead));  // the next tile's halo rows: in flight while this wave works through its units
+        if (ahead.live) fetch(tile_at(ahead, TW, TR));  // the next tile's halo rows: in flight while this wave works through its units
 #pragma unroll
         for (int kk = 0; kk < OPW; ++kk) {
         const int oc = o + NW * kk, ob = 16 * NW * kk;  // this pass's octet; its byte offset from the lane-constant addresses (which carry octet o)
         if constexpr (OPW > 1) load_frags(oc);
-        // the residual's pieces of x for this wave's output units (8 bytes per lane and unit): requested now, added at the stores
-        uint2 xr[NOUT];
-        size_t e_off[NOUT];
+        // the residual's pieces of x for this wave's output units (8 bytes per lane and unit): without the stash requested now, added at the stores
+        uint2 xr[STASH ? 1 : NOUT];
+        // where unit u's 8 bytes go: e0 + u * estep elements, when the pixel lies in the frame (one 64-bit lane offset for all units: registers are what this kernel is short of)
+        const int yo0 = t.y0 + 2 * rpo + (q >> 1), xo = t.x0 + n16;
+        const bool livex = n16 < TW && xo < W;
+        const size_t e0 = ((t.b * H + (yo0 < H ? yo0 : 0)) * (size_t)W + (livex ? xo : 0)) * C + 8 * oc + 4 * (q & 1), estep = (size_t)2 * W * C;
+        auto live = [&](int u) { return livex && yo0 + 2 * u < H; };
+        if constexpr (!STASH) {  // STASH: read from LDS one unit ahead of its store, below
 #pragma unroll
-        for (int u = 0; u < NOUT; ++u) {
-            const int yo = t.y0 + 2 * (rpo + u) + (q >> 1), xo = t.x0 + n16;
-            const bool live = n16 < TW && yo < H && xo < W;
-            e_off[u] = live ? ((t.b * H + yo) * (size_t)W + xo) * C + 8 * oc + 4 * (q & 1) : ~(size_t)0;
-            xr[u] = live ? *reinterpret_cast<const uint2*>(x + e_off[u]) : uint2{0, 0};
+            for (int u = 0; u < NOUT; ++u) xr[u] = live(u) ? *reinterpret_cast<const uint2*>(x + e0 + u * estep) : uint2{0, 0};
         }
         // ---- conv1 + GELU -> mid, this wave's octet, mid row pairs rpo ... rpo + NOUT (zero outside the image: the second conv's padding applies to THIS map) ----
         {
@@ -954,37 +943,66 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
         // ---- conv2(mid) + v @ M + bias + x for this wave's output units, stored from registers ----
         {
             uint4 bq[3], bg[NK];
+            uint2 xn = uint2{0, 0};  // STASH: unit u's piece of x, read with its operands
+            const unsigned char* rbX = xs + (size_t)((q >> 1) * TW + n16) * PP + 16 * o + 8 * (q & 1);  // + 2 rp TW PP; lanes 14, 15 read what they do not use
             auto rd = [&](int u) {
 #pragma unroll
                 for (int i = 0; i < 3; ++i) bq[i] = *reinterpret_cast<const uint4*>(rbC + (size_t)(2 * (rpo + u)) * MP + i * PP + ob);
 #pragma unroll
                 for (int t2 = 0; t2 < NK; ++t2) bg[t2] = *reinterpret_cast<const uint4*>(rbG + (size_t)(2 * (rpo + u)) * RP + 32 * t2);
+                if constexpr (STASH) xn = *reinterpret_cast<const uint2*>(rbX + (size_t)(2 * (rpo + u)) * TW * PP);
             };
-            rd(0);
-#pragma unroll
-            for (int u = 0; u < NOUT; ++u) {
-                float4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 3; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[i], __builtin_bit_cast(half8_t, bq[i]), acc, 0, 0, 0);
-#pragma unroll
-                for (int t2 = 0; t2 < NK; ++t2) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(am[t2], __builtin_bit_cast(half8_t, bg[t2]), acc, 0, 0, 0);
-                if (u + 1 < NOUT) rd(u + 1);
-                if (e_off[u] != ~(size_t)0) {  // ((pos_emb + projection) + bias) + x: the float16 residual taken as it is (v_fma_mix_f32: x * 1.0 + sum)
+            auto finish = [&](int u, float4_t acc, uint2 xu) {
+                if (live(u)) {  // ((pos_emb + projection) + bias) + x: the float16 residual taken as it is (v_fma_mix_f32: x * 1.0 + sum)
                     constexpr unsigned kOnes = 0x3c003c00u;
                     float s0 = acc[0] + bs[0], s1 = acc[1] + bs[1], s2 = acc[2] + bs[2], s3 = acc[3] + bs[3];
-                    fma_mix_lo(s0, xr[u].x, kOnes); fma_mix_hi(s1, xr[u].x, kOnes);
-                    fma_mix_lo(s2, xr[u].y, kOnes); fma_mix_hi(s3, xr[u].y, kOnes);
-                    *reinterpret_cast<uint2*>(out + e_off[u]) = uint2{pack_f16(s0, s1), pack_f16(s2, s3)};
+                    fma_mix_lo(s0, xu.x, kOnes); fma_mix_hi(s1, xu.x, kOnes);
+                    fma_mix_lo(s2, xu.y, kOnes); fma_mix_hi(s3, xu.y, kOnes);
+                    *reinterpret_cast<uint2*>(out + e0 + u * estep) = uint2{pack_f16(s0, s1), pack_f16(s2, s3)};
+                }
+            };
+            rd(0);
+#ifndef AVX_TAIL_PIPE2
+#define AVX_TAIL_PIPE2 1
+#endif
+            if constexpr (STASH && (AVX_TAIL_PIPE2 == 2 || (AVX_TAIL_PIPE2 == 1 && C == 64))) {  // C = 32: not a register to spare (the lagging accumulator spills 4); -DAVX_TAIL_PIPE2=0 / 2: nowhere / everywhere, for an A/B
+                // two units in flight (as the first conv's loop above): unit u's 3 + NK MFMAs | the reads of unit u + 1 | sums and store of unit u - 1
+                float4_t prev = {0.f, 0.f, 0.f, 0.f};
+                uint2 xp = uint2{0, 0};
+#pragma unroll
+                for (int u = 0; u < NOUT; ++u) {
+                    const uint2 xu = xn;
+                    float4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[i], __builtin_bit_cast(half8_t, bq[i]), acc, 0, 0, 0);
+#pragma unroll
+                    for (int t2 = 0; t2 < NK; ++t2) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(am[t2], __builtin_bit_cast(half8_t, bg[t2]), acc, 0, 0, 0);
+                    if (u + 1 < NOUT) rd(u + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (u > 0) finish(u - 1, prev, xp);
+                    __builtin_amdgcn_sched_barrier(0);
+                    prev = acc; xp = xu;
+                }
+                finish(NOUT - 1, prev, xp);
+            } else {
+#pragma unroll
+                for (int u = 0; u < NOUT; ++u) {
+                    const uint2 xu = STASH ? xn : xr[STASH ? 0 : u];
+                    float4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[i], __builtin_bit_cast(half8_t, bq[i]), acc, 0, 0, 0);
+#pragma unroll
+                    for (int t2 = 0; t2 < NK; ++t2) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(am[t2], __builtin_bit_cast(half8_t, bg[t2]), acc, 0, 0, 0);
+                    if (u + 1 < NOUT) rd(u + 1);
+                    finish(u, acc, xu);
                 }
             }
         }
         }  // octets of this wave
         stamp(3);
-        if (next >= total) break;
-        tile = next;
-        walk = ahead;
+        if (!ahead.live) break;
+        t = tile_at(ahead, TW, TR);
         ahead.advance();
-        t = tile_at(walk);
         __syncthreads();  // every wave is done reading v: the next tile's may be written
         stamp(4);
     }
@@ -999,9 +1017,10 @@ template <int C, int TR, int MINW, int NW = 8>
 int launch_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack, const void* mpack, const void* dw1, const void* dw2, const float* bias, void* out, int B, int H, int W,
                         hipStream_t s) {
     constexpr int PP = C * 2 + 16, RP = (18 * PP + 255) / 256 * 256;
-    const size_t lds = (size_t)(TR + 4) * RP + (size_t)(TR + 2) * 16 * PP + (size_t)(C / 32) * (C / 16) * 1024;
+    const size_t lds = (size_t)(TR + 4) * RP + (size_t)(TR + 2) * 16 * PP + (size_t)(C / 32) * (C / 16) * 1024 + ((C <= 64 && NW == 8) ? (size_t)(TR * 14 + 2) * PP : 0) /*the residual's stash*/;
     const long total = (long)B * ((H + TR - 1) / TR) * ((W + 13) / 14);
     const long cap = (long)ctx->num_cus * (NW == 16 ? 1 : MINW / 2);
+    AVX_REQUIRE(ctx, total <= 0x7fffffffl, "avx_mst_attn_tail_mx: 2^31 tiles or more");
     const unsigned blocks = (unsigned)(total < cap ? total : cap);
     if (getenv("AVX_TAIL_STAMPS")) {  // diagnostic: per-segment cycles of every wave, summed and printed
         auto ks = k_mst_attn_tail_mx<C, TR, MINW, true, NW>;
@@ -1009,7 +1028,7 @@ int launch_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack, const v
         const size_t n = (size_t)blocks * NW * 8;
         AVX_HIP(ctx, hipMalloc((void**)&d_st, n * sizeof(unsigned long long)));
         AVX_HIP(ctx, hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(ks, dim3(blocks), dim3(64 * NW), lds, s, (const __half*)x, (const uint4*)wvpack, (const uint4*)mpack, (const uint4*)dw1, (const uint4*)dw2, bias, (__half*)out, B, H, W, d_st);
+        hipLaunchKernelGGL(ks, dim3(blocks), dim3(64 * NW), lds, s, (const __half*)x, (const uint4*)wvpack, (const uint4*)mpack, (const uint4*)dw1, (const uint4*)dw2, bias, (__half*)out, B, H, W, d_st, mst_tile_order());
         AVX_HIP(ctx, hipStreamSynchronize(s));
         unsigned long long* h_st = (unsigned long long*)malloc(n * sizeof(unsigned long long));
         AVX_HIP(ctx, hipMemcpy(h_st, d_st, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -1026,7 +1045,7 @@ int launch_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack, const v
     auto k = k_mst_attn_tail_mx<C, TR, MINW, false, NW>;
     AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * NW), lds, s, (const __half*)x, (const uint4*)wvpack, (const uint4*)mpack, (const uint4*)dw1,
-                       (const uint4*)dw2, bias, (__half*)out, B, H, W, (unsigned long long*)nullptr);
+                       (const uint4*)dw2, bias, (__half*)out, B, H, W, (unsigned long long*)nullptr, mst_tile_order());
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
 }
@@ -1053,7 +1072,7 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_conv3x3_lds(const __half* __r
                                                                const uint4* __restrict__ wqk /*[2][2][64]: pack_qkv16's q and k tiles*/, float* __restrict__ partial /*[blocks][34][32]*/,
                                                                const float* __restrict__ specw = nullptr /*SPEC: [32 bands][4]: the three catches' weights, band-major*/,
                                                                float* __restrict__ planes = nullptr /*SPEC: [3][Hc * Wc]*/, SpecStat3* __restrict__ spart = nullptr /*SPEC: [blocks][3]*/,
-                                                               int crop_t = 0, int crop_l = 0, int Hc = 0, int Wc = 0) {
+                                                               int crop_t = 0, int crop_l = 0, int Hc = 0, int Wc = 0, int order = AVX_TILE_ORDER_RASTER /*GRAM / SPEC: raster only (their per-workgroup partial sums pin the summation order)*/) {
     constexpr int C = 32, PP = C * 2 + 16, RP = (HS * PP + 255) / 256 * 256, NFILL = (HS * HS * 4 + kFT - 1) / kFT;
     __shared__ __align__(16) unsigned char xt[HS * RP];
     __shared__ uint4 wl[18 * 64];  // the 18 A fragments (9 taps x 2 K-steps): in registers they cost 72 VGPRs and a wave of occupancy
@@ -1070,7 +1089,6 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_conv3x3_lds(const __half* __r
     float smn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, smx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
     double ssum[3] = {0.0, 0.0, 0.0};
     const int tx = (W + TS - 1) / TS, ty = (H + TS - 1) / TS;
-    const long total = (long)B * ty * tx;
     uint4 pre[NFILL];
     unsigned f_rel[NFILL];  // this thread's halo elements as byte offsets from the halo origin (y0 - 1, x0 - 1)
 #pragma unroll
@@ -1100,13 +1118,11 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_conv3x3_lds(const __half* __r
             pre[k] = r;
         }
     };
-    long tile = blockIdx.x;
-    if (tile >= total) return;
-    TileWalk walk, ahead;  // this tile, the next one
-    walk.init(tile, gridDim.x, tx, ty);
-    ahead = walk;
+    TileWalk ahead;  // after its first step: the NEXT tile (this one's coordinates are in t)
+    ahead.init(blockIdx.x, gridDim.x, B, ty, tx, (GRAM || SPEC) ? (int)AVX_TILE_ORDER_RASTER : order);
+    if (!ahead.live) return;
+    Tile t = tile_at(ahead, TS, TS);
     ahead.advance();
-    Tile t = walk.tile(TS);
     fetch(t);
     for (;;) {
 #pragma unroll
@@ -1115,8 +1131,7 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_conv3x3_lds(const __half* __r
             if (it < HS * HS * 4) *reinterpret_cast<uint4*>(xt + (size_t)(q / HS) * RP + (size_t)(q % HS) * PP + 16 * part) = pre[k];
         }
         __syncthreads();
-        const long next = tile + gridDim.x;
-        if (next < total) fetch(ahead.tile(TS));
+        if (ahead.live) fetch(tile_at(ahead, TS, TS));
         {
             const int r = 2 * wave + (p >> 4), c = p & 15;
             const int yo = t.y0 + r, xo = t.x0 + c;
@@ -1190,11 +1205,9 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_conv3x3_lds(const __half* __r
                                __builtin_bit_cast(half8_t, uint4{aq[4 * b2], aq[4 * b2 + 1], aq[4 * b2 + 2], aq[4 * b2 + 3]}), G);
             }
         }
-        if (next >= total) break;
-        tile = next;
-        walk = ahead;
+        if (!ahead.live) break;
+        t = tile_at(ahead, TS, TS);
         ahead.advance();
-        t = walk.tile(TS);
         __syncthreads();  // everyone is done reading xt
     }
     if constexpr (SPEC) {  // this workgroup's statistics of the three planes (every workgroup writes its slot: k_finalize_stats reads them all)
@@ -1287,7 +1300,7 @@ __device__ __forceinline__ void lds_dma16(const void* base /*the same in every l
 #pragma clang diagnostic pop
 template <int C>
 __global__ __launch_bounds__(kFT, 2) void k_mst_down4x4_dma(const __half* __restrict__ x /*[B][H][W][C]*/, const uint4* __restrict__ wpack /*[16][2C/32][C/16][64]*/,
-                                                            __half* __restrict__ out /*[B][H/2][W/2][2C]*/, const void* __restrict__ zero, int B, int H, int W) {
+                                                            __half* __restrict__ out /*[B][H/2][W/2][2C]*/, const void* __restrict__ zero, int B, int H, int W, int order /*AVX_TILE_ORDER_*/) {
     using G = DownGeo<C>;
     constexpr int CO = 2 * C, NT = CO / 32, KS = C / 16;
     __shared__ __align__(1024) unsigned char lds[G::NBUF * G::BUF + G::PART];
@@ -1301,9 +1314,8 @@ __global__ __launch_bounds__(kFT, 2) void k_mst_down4x4_dma(const __half* __rest
     }
     const int Ho = H / 2, Wo = W / 2;
     const int tx = (Wo + G::OW - 1) / G::OW, ty = (Ho + G::OH - 1) / G::OH;
-    const unsigned total = (unsigned)B * ty * tx;
     struct T2 { int ox0, oy0, b; };
-    auto tile_at = [&](const TileWalk& w) { return T2{w.xi * G::OW, w.yi * G::OH, (int)w.b}; };  // coordinates advance with the walk: no division per tile
+    auto tile_at = [&](const TileWalk& w) { return T2{w.xi * G::OW, w.yi * G::OH, w.b}; };  // coordinates advance with the walk: no division per tile
     // this lane's slots of a tile: tile-relative pixel and byte offset, fixed for the launch
     int rel[G::PER_WAVE], rc[G::PER_WAVE];
 #pragma unroll
@@ -1314,8 +1326,8 @@ __global__ __launch_bounds__(kFT, 2) void k_mst_down4x4_dma(const __half* __rest
         rc[k] = inside ? row << 8 | col : -1;
     }
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds);
-    auto fill = [&](unsigned u, const TileWalk& w, int slot) {
-        const bool exists = u < total;  // past the end: the walk's coordinates mean nothing and every lane reads zeros
+    auto fill = [&](const TileWalk& w, int slot) {
+        const bool exists = w.live;  // past the end: the walk's coordinates mean nothing and every lane reads zeros
         const T2 t = tile_at(w);
         const int y0 = 2 * t.oy0 - 1, x0 = 2 * t.ox0 - 1;
         const char* origin = reinterpret_cast<const char*>(x) + (((long)t.b * H + y0) * W + x0) * (long)(C * 2);
@@ -1332,13 +1344,12 @@ __global__ __launch_bounds__(kFT, 2) void k_mst_down4x4_dma(const __half* __rest
             }
         }
     };
-    unsigned tile = blockIdx.x;
-    if (tile >= total) return;
     TileWalk walk, look;  // this tile; the one NBUF - 1 steps ahead, whose loads are issued next
-    walk.init(tile, gridDim.x, tx, ty);
+    walk.init(blockIdx.x, gridDim.x, B, ty, tx, order);
+    if (!walk.live) return;
     look = walk;
 #pragma unroll
-    for (int a = 0; a < G::NBUF - 1; ++a) { fill(tile + a * gridDim.x, look, a); look.advance(); }
+    for (int a = 0; a < G::NBUF - 1; ++a) { fill(look, a); look.advance(); }
     // operand addressing: pixel (row 2 g + (p >> 4), col p & 15) of the group; tap (ky, kx) reads tile pixel (2 row + ky, 2 col + kx)
     const int c2 = 2 * (p & 15);
     int colofs[4];
@@ -1355,7 +1366,7 @@ __global__ __launch_bounds__(kFT, 2) void k_mst_down4x4_dma(const __half* __rest
         {
             int nslot = slot + G::NBUF - 1;
             nslot -= nslot >= G::NBUF ? G::NBUF : 0;
-            fill(tile + (G::NBUF - 1) * gridDim.x, look, nslot);
+            fill(look, nslot);
             look.advance();
         }
         const T2 t = tile_at(walk);
@@ -1419,9 +1430,8 @@ __global__ __launch_bounds__(kFT, 2) void k_mst_down4x4_dma(const __half* __rest
             }
         }
         plain_stores = whole ? (plain_stores < G::NBUF - 1 ? plain_stores + 1 : plain_stores) : 0;
-        if (tile + gridDim.x >= total) break;
-        tile += gridDim.x;
         walk.advance();
+        if (!walk.live) break;
         slot = slot + 1 == G::NBUF ? 0 : slot + 1;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the look-ahead loads of tiles past the end still target this workgroup's LDS
@@ -1545,6 +1555,25 @@ static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, con
 // and W2 * s; avx_mst_attn_tail_mx takes pos_emb's first depthwise weights / s and the second * s.  s = 4 (1 when built with -DAVX_GELU_PRE=0).
 extern "C" float avx_mst_gelu_prescale(void) { return kGeluPrescale; }
 
+// The tile order of the persistent tile kernels (mst_tile_order.h), run on the host with the kernels' own walk: visit[wg * steps_cap + k] = raster index
+// ((frame * ty + row) * tx + column) of the tile workgroup wg of nwg takes at its k-th step, -1 past its last one.
+extern "C" int avx_mst_tile_order(int frames, int ty, int tx, int nwg, int raster, long long* visit, int steps_cap, int* steps_out) {
+    if (frames <= 0 || ty <= 0 || tx <= 0 || nwg <= 0 || (visit && steps_cap <= 0) || (long long)frames * ty * tx > 0x7fffffffll) return AVX_ERR_INVALID;
+    int most = 0;
+    for (int wg = 0; wg < nwg; ++wg) {
+        TileWalk wk;
+        wk.init((unsigned)wg, (unsigned)nwg, frames, ty, tx, raster ? AVX_TILE_ORDER_RASTER : AVX_TILE_ORDER_XCD);
+        int k = 0;
+        for (; wk.live; wk.advance(), ++k)
+            if (visit && k < steps_cap) visit[(size_t)wg * steps_cap + k] = ((long long)wk.b * ty + wk.yi) * tx + wk.xi;
+        if (visit)
+            for (int r = k; r < steps_cap; ++r) visit[(size_t)wg * steps_cap + r] = -1;
+        most = k > most ? k : most;
+    }
+    if (steps_out) *steps_out = most;
+    return AVX_OK;
+}
+
 extern "C" int avx_mst_ffn_fused(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* taps_9xhid,
                                  const void* w2pack, void* out, int B, int H, int W, int C, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
@@ -1576,13 +1605,15 @@ static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, con
     const long cap = (long)ctx->num_cus * (small ? 2 : 1);
     const bool nw16 = C == 64 && dwpack && !(getenv("AVX_MST_FFN_NW") && atoi(getenv("AVX_MST_FFN_NW")) == 8);  // AVX_MST_FFN_NW=8: A/B, the round-2 split
     const size_t lds = (size_t)kFfnNGRP * 32 * (C * 2 + 16) + (size_t)(kFfnTH + 2) * rpitch + (dwpack ? 0 : (size_t)9 * 4 * C * 2) + sizeof(float) * 2 * C + (nw16 ? (size_t)(C / 32) * (hpass / 16) * 1024 : 0);
+    AVX_REQUIRE(ctx, total <= 0x7fffffffl, "avx_mst_ffn_fused: 2^31 tiles or more");
     const dim3 grid((unsigned)(total < cap ? total : cap));
+    const int order = mst_tile_order();
 #define AVX_FFN1(CV, HP, MW, DW, NWV)                                                                                                            \
     {                                                                                                                                            \
         auto k = k_mst_ffn_fused<CV, HP, MW, DW, false, NWV>;                                                                                    \
         AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
         hipLaunchKernelGGL(k, grid, dim3(64 * NWV), lds, s, (const __half*)x, gamma, beta, eps, (const uint4*)w1pack, (const __half*)taps_9xhid, \
-                           (const uint4*)w2pack, (__half*)out, B, H, W, (const uint4*)dwpack, (unsigned long long*)nullptr);                     \
+                           (const uint4*)w2pack, (__half*)out, B, H, W, (const uint4*)dwpack, (unsigned long long*)nullptr, order);              \
     }
 #define AVX_FFN(CV, HP, MW) { if (dwpack) AVX_FFN1(CV, HP, MW, true, 8) else AVX_FFN1(CV, HP, MW, false, 8) }
     if (dwpack && getenv("AVX_FFN_STAMPS") && ((C == 32 && small) || C == 64 || C == 128)) {  // diagnostic: per-segment cycles of every wave, summed and printed
@@ -1595,7 +1626,7 @@ static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, con
         auto k = k_mst_ffn_fused<CV, HP, MW, true, true, NWV>;                                                                                   \
         AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
         hipLaunchKernelGGL(k, grid, dim3(64 * NWV), lds, s, (const __half*)x, gamma, beta, eps, (const uint4*)w1pack, (const __half*)taps_9xhid, \
-                           (const uint4*)w2pack, (__half*)out, B, H, W, (const uint4*)dwpack, d_st);                                             \
+                           (const uint4*)w2pack, (__half*)out, B, H, W, (const uint4*)dwpack, d_st, order);                                      \
     }
         if (C == 32) AVX_FFN_ST(32, 64, 4, 8) else if (nw16) AVX_FFN_ST(64, 128, 1, 16) else if (C == 64) AVX_FFN_ST(64, 128, 2, 8) else AVX_FFN_ST(128, 64, 2, 8)
 #undef AVX_FFN_ST
@@ -1680,8 +1711,9 @@ extern "C" int avx_mst_conv3x3_lds(avx_ctx* ctx, const void* x, const void* wpac
     hipStream_t s = avx_pick_stream(ctx, stream);
     const long total = (long)B * ((H + TS - 1) / TS) * ((W + TS - 1) / TS);
     const long cap = (long)ctx->num_cus * 3;
+    AVX_REQUIRE(ctx, total <= 0x7fffffffl, "avx_mst_conv3x3_lds: 2^31 tiles or more");
     hipLaunchKernelGGL((k_mst_conv3x3_lds<6, false>), dim3((unsigned)(total < cap ? total : cap)), dim3(kFT), 0, s, (const __half*)x, (const uint4*)wpack16, (const __half*)add,
-                       (__half*)out, B, H, W, (const uint4*)nullptr, (float*)nullptr);
+                       (__half*)out, B, H, W, (const uint4*)nullptr, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (SpecStat3*)nullptr, 0, 0, 0, 0, mst_tile_order());
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
 }
@@ -1776,11 +1808,11 @@ extern "C" int avx_mst_down4x4(avx_ctx* ctx, const void* x, const void* wpack16,
     if (C == 32) {
         using G = DownGeo<32>;
         const long total = (long)B * ((H / 2 + G::OH - 1) / G::OH) * ((W / 2 + G::OW - 1) / G::OW);
-        hipLaunchKernelGGL(k_mst_down4x4_dma<32>, dim3((unsigned)(total < cap ? total : cap)), dim3(kFT), 0, s, (const __half*)x, (const uint4*)wpack16, (__half*)out, (const void*)ctx->d_zero, B, H, W);
+        hipLaunchKernelGGL(k_mst_down4x4_dma<32>, dim3((unsigned)(total < cap ? total : cap)), dim3(kFT), 0, s, (const __half*)x, (const uint4*)wpack16, (__half*)out, (const void*)ctx->d_zero, B, H, W, mst_tile_order());
     } else {
         using G = DownGeo<64>;
         const long total = (long)B * ((H / 2 + G::OH - 1) / G::OH) * ((W / 2 + G::OW - 1) / G::OW);
-        hipLaunchKernelGGL(k_mst_down4x4_dma<64>, dim3((unsigned)(total < cap ? total : cap)), dim3(kFT), 0, s, (const __half*)x, (const uint4*)wpack16, (__half*)out, (const void*)ctx->d_zero, B, H, W);
+        hipLaunchKernelGGL(k_mst_down4x4_dma<64>, dim3((unsigned)(total < cap ? total : cap)), dim3(kFT), 0, s, (const __half*)x, (const uint4*)wpack16, (__half*)out, (const void*)ctx->d_zero, B, H, W, mst_tile_order());
     }
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;

@@ -496,6 +496,14 @@ int avx_mst_ffn_fused_mx(avx_ctx* ctx, const void* x, const float* gamma, const 
  * avx_mst_attn_tail_mx takes pos_emb's first depthwise weights / s in dw1pack and the second * s in dw2pack. */
 float avx_mst_gelu_prescale(void);
 
+/* The order in which the persistent tile kernels of csrc/mst_fused.hip (attention tail, FeedForward, the plain 3x3 conv, the encoder's downsampling) hand the tiles
+ * of a (frames x ty x tx) grid to their nwg workgroups, run on the host with the kernels' own walk (csrc/mst_tile_order.h): visit[wg * steps_cap + k] receives the
+ * raster index ((frame * ty + row) * tx + column) of the tile workgroup wg takes at its k-th step, -1 past its last one; *steps_out the largest number of steps of any
+ * workgroup (visit may be NULL to ask for it first).  raster = 0: the XCD-aware order -- the workgroups with the same index % 8 share one contiguous stretch of
+ * the band-major order (bands of tile columns, each walked frame by frame and row by row), so neighbouring tiles meet in one L2; raster != 0: tiles wg, wg + nwg,
+ * ... of the raster, which the environment variable AVX_MST_TILE_ORDER=raster (read per call) selects in the kernels.  Results do not depend on the order. */
+int avx_mst_tile_order(int frames, int ty, int tx, int nwg, int raster, long long* visit, int steps_cap, int* steps_out);
+
 /* out = [add +] a @ W [+ a2 @ W2] for (rows x C) float16 tensors and C x C weights in fragment order (out may alias
  * add; a2 / W2 and add may be NULL): MS_MSA's `proj(attn @ v)` collapsed to one matrix per frame (:132-135)
  * accumulated onto pos_emb(v) + x, and the decoder's 1x1 fusion conv over [up | skip] (:257) without the concatenation. */

@@ -192,6 +192,7 @@ class EwProgram(ctypes.Structure):
 
 
 AVX_EW_MAX_INSN, AVX_EW_MAX_PLANES, AVX_EW_MAX_REGS, AVX_EW_MAX_ACC = 384, 24, 32, 16
+AVX_EW_MAX_FRAMES = 16  # frames of one batched launch (avx_ew_run_batch and the *_batch stage calls)
 _EW_OPS = ("CONST SCALAR LOAD STORE ADD SUB MUL DIV MIN MAX POW ATAN2 NEG ABS SQRT EXP LOG SIN COS FLOOR CEIL CLIP01 TANH "
            "LT LE GT GE EQ AND OR NOT SELECT ACCMIN ACCMAX ACCSUM").split()
 EW = {name: i + 1 for i, name in enumerate(_EW_OPS)}  # enum in include/avx.h starts at AVX_EW_CONST = 1
@@ -259,16 +260,20 @@ _SIGS = {
     "avx_spectral_integrate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "avx_plane_stats": (_i, [_vp, _vp, _i, _sz, _i, ctypes.c_float, _vp, _vp]),
     "avx_planes_gaussian_blur": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "avx_planes_gaussian_blur_batch": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "avx_streak_planes_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "avx_rgb_to_hsi_lobes": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_float, _vp, _vp]),
     "avx_honeybee_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(HoneybeeDesc), _vp, _vp]),
     "avx_uv_front_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "avx_uv_front_u8_batch": (_i, [_vp, _vp, _i, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     "avx_panorama_warp_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "avx_band_stack": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(BandStackDesc), _vp, _vp]),
+    "avx_band_stack_batch": (_i, [_vp, _vp, _i, _sz, _i, _i, ctypes.POINTER(BandStackDesc), _vp, _sz, _vp]),
     "avx_percentile_dev": (_i, [_vp, _vp, _sz, ctypes.c_double, _vp, _vp]),
     "avx_percentiles_dev": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(ctypes.c_void_p), _vp]),
     "avx_ew_run": (_i, [_vp, ctypes.POINTER(EwProgram), _vp]),
+    "avx_ew_run_batch": (_i, [_vp, ctypes.POINTER(EwProgram), _i, ctypes.POINTER(ctypes.c_size_t), _sz, _vp]),
     "avx_ew_spec_stats": (_i, [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "avx_mantis_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, ctypes.POINTER(MantisDesc), _vp]),
     "avx_mantis_u8_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(MantisDesc), _vp]),

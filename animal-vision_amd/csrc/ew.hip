@@ -62,6 +62,7 @@ __global__ __launch_bounds__(kET) void k_ew(const EwArgs a) {
         EW_WR(reg, vv);
     }
     const uint32_t n = (uint32_t)a.n, W = (uint32_t)a.W;  // the host checks H*W < 2^31
+    const unsigned f = blockIdx.y;                         // frame of the batch: own planes, scalar table, partials and ticket words
     for (uint32_t base = blockIdx.x * (kET * PX); base < n; base += gridDim.x * (kET * PX)) {
         uint32_t ii[PX], px[PX], py[PX];
         bool valid[PX];
@@ -93,9 +94,9 @@ __global__ __launch_bounds__(kET) void k_ew(const EwArgs a) {
             float r[PX];
             switch (in.op & AVX_EW_OPCODE_MASK) {
                 case AVX_EW_CONST: { const float c = __uint_as_float(in.imm); _Pragma("unroll") EW_FOR r[k] = c; } break;
-                case AVX_EW_SCALAR: { const float c = (float)a.scalars[in.imm]; _Pragma("unroll") EW_FOR r[k] = c; } break;
+                case AVX_EW_SCALAR: { const float c = (float)a.scalars[(size_t)f * a.scalars_fs + in.imm]; _Pragma("unroll") EW_FOR r[k] = c; } break;
                 case AVX_EW_LOAD: {
-                    const avx_ew_plane p = a.planes[in.imm];
+                    const avx_ew_plane p = ew_plane_of(a, in.imm, f);
                     if (p.kind == AVX_EW_PLANE_F32) { _Pragma("unroll") EW_FOR r[k] = ((const float*)p.ptr)[(size_t)ii[k] * p.stride]; }
                     else if (p.kind == AVX_EW_PLANE_U8) { _Pragma("unroll") EW_FOR r[k] = (float)((const uint8_t*)p.ptr)[(size_t)ii[k] * p.stride]; }
                     else if (p.kind == AVX_EW_PLANE_U8_LUT) { _Pragma("unroll") EW_FOR r[k] = a.lut[((const uint8_t*)p.ptr)[(size_t)ii[k] * p.stride]]; }
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kET) void k_ew(const EwArgs a) {
                     break;
                 }
                 case AVX_EW_STORE: {
-                    const avx_ew_plane p = a.planes[in.imm];
+                    const avx_ew_plane p = ew_plane_of(a, in.imm, f);
                     if (p.kind == AVX_EW_PLANE_F32) {
 #pragma unroll
                         EW_FOR if (valid[k]) ((float*)p.ptr)[(size_t)ii[k] * p.stride] = xs[k];
@@ -185,12 +186,12 @@ __global__ __launch_bounds__(kET) void k_ew(const EwArgs a) {
         if (tid == 0) {
             float t = red[0];
             for (int w = 1; w < kET / 64; ++w) t = acc_merge(kind, t, red[w]);
-            __hip_atomic_store(&a.partial[(size_t)blockIdx.x * a.n_acc + k], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&a.partial[(size_t)f * a.partial_fs + (size_t)blockIdx.x * a.n_acc + k], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     if (tid == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        is_last = avxk::ticket_is_last(a.ticket, blockIdx.x, gridDim.x);
+        is_last = avxk::ticket_is_last(a.ticket + f * kEwTicketStride, blockIdx.x, gridDim.x);
     }
     __syncthreads();
     if (!is_last) return;
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(kET) void k_ew(const EwArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int i = i0 + 64 * j;
-                vals[j] = i < (int)gridDim.x ? __hip_atomic_load(&a.partial[(size_t)i * a.n_acc + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : init;
+                vals[j] = i < (int)gridDim.x ? __hip_atomic_load(&a.partial[(size_t)f * a.partial_fs + (size_t)i * a.n_acc + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : init;
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -216,11 +217,11 @@ __global__ __launch_bounds__(kET) void k_ew(const EwArgs a) {
         if (mm) {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) vm = acc_merge(kind, vm, __shfl_xor(vm, o));
-            if (lane == 0) a.scalars_out[a.acc_slot[k]] = (double)vm;
+            if (lane == 0) a.scalars_out[(size_t)f * a.scalars_fs + a.acc_slot[k]] = (double)vm;
         } else {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) vs += __shfl_xor(vs, o);
-            if (lane == 0) a.scalars_out[a.acc_slot[k]] = kind == AVX_EW_ACC_MEAN ? (double)((float)vs / (float)a.n) : (double)(float)vs;
+            if (lane == 0) a.scalars_out[(size_t)f * a.scalars_fs + a.acc_slot[k]] = kind == AVX_EW_ACC_MEAN ? (double)((float)vs / (float)a.n) : (double)(float)vs;
         }
     }
 
@@ -236,8 +237,13 @@ extern "C" int avx_ew_spec_stats(unsigned long long* hits, unsigned long long* m
     return avxew::kEwSpecCount;
 }
 
-extern "C" int avx_ew_run(avx_ctx* ctx, const avx_ew_program* p, void* stream) {
+extern "C" int avx_ew_run(avx_ctx* ctx, const avx_ew_program* p, void* stream) { return avx_ew_run_batch(ctx, p, 1, nullptr, 0, stream); }
+
+// One launch for n_frames frames: the frame is blockIdx.y.  The x-grid and the pixels per thread are the single-frame call's, so a frame's
+// partial sums are formed and folded in the same order as there: its reductions are bit-identical to avx_ew_run on that frame.
+extern "C" int avx_ew_run_batch(avx_ctx* ctx, const avx_ew_program* p, int n_frames, const size_t* plane_fs_host, size_t scalars_fs, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, n_frames >= 1 && n_frames <= AVX_EW_MAX_FRAMES, "avx_ew_run_batch: n_frames %d outside 1..%d", n_frames, AVX_EW_MAX_FRAMES);
     AVX_REQUIRE(ctx, p && p->struct_size == sizeof(avx_ew_program), "avx_ew_run: program is NULL or struct_size mismatch");
     AVX_REQUIRE(ctx, p->n_insn >= 1 && p->n_insn <= AVX_EW_MAX_INSN && p->insn_host, "avx_ew_run: instruction count out of range");
     AVX_REQUIRE(ctx, p->n_planes >= 0 && p->n_planes <= AVX_EW_MAX_PLANES && (p->n_planes == 0 || p->planes_host), "avx_ew_run: plane count out of range");
@@ -253,9 +259,15 @@ extern "C" int avx_ew_run(avx_ctx* ctx, const avx_ew_program* p, void* stream) {
     a.uses_encode = 0; a.uses_xy = 0;
     AVX_REQUIRE(ctx, (size_t)p->H * p->W < ((size_t)1 << 31), "avx_ew_run: frame too large");
     int max_reg = 0;
+    AVX_REQUIRE(ctx, n_frames == 1 || p->n_planes == 0 || plane_fs_host, "avx_ew_run_batch: a batch needs the planes' frame strides");
+    AVX_REQUIRE(ctx, n_frames == 1 || !p->scalars_dev || scalars_fs == 0 || scalars_fs >= (size_t)p->n_scalars, "avx_ew_run_batch: scalar tables of the frames overlap");
+    AVX_REQUIRE(ctx, n_frames == 1 || p->n_acc == 0 || scalars_fs >= (size_t)p->n_scalars, "avx_ew_run_batch: reductions of a batch need one scalar table per frame");
+    for (int i = 0; i < AVX_EW_MAX_PLANES; ++i) a.plane_fs[i] = 0;
+    a.scalars_fs = n_frames > 1 ? scalars_fs : 0;
     for (int i = 0; i < p->n_planes; ++i) {
         a.planes[i] = p->planes_host[i];
         AVX_REQUIRE(ctx, a.planes[i].ptr && a.planes[i].stride >= 1 && a.planes[i].kind >= 0 && a.planes[i].kind <= AVX_EW_PLANE_U8_ENC, "avx_ew_run: bad plane entry");
+        if (n_frames > 1) a.plane_fs[i] = plane_fs_host[i];
     }
     for (int i = 0; i < p->n_insn; ++i) {
         const avx_ew_insn in = p->insn_host[i];
@@ -270,6 +282,9 @@ extern "C" int avx_ew_run(avx_ctx* ctx, const avx_ew_program* p, void* stream) {
             if (kind == AVX_EW_PLANE_COL || kind == AVX_EW_PLANE_ROW) a.uses_xy = 1;
             if (opc == AVX_EW_STORE) {
                 AVX_REQUIRE(ctx, kind == AVX_EW_PLANE_F32 || kind == AVX_EW_PLANE_U8_ENC, "avx_ew_run: store to a read-only plane kind");
+                // frame f + 1 of a stored plane begins behind the last element frame f writes: otherwise the frames overwrite each other
+                AVX_REQUIRE(ctx, n_frames == 1 || a.plane_fs[in.imm] >= ((a.n - 1) * (size_t)a.planes[in.imm].stride + 1) * (kind == AVX_EW_PLANE_F32 ? sizeof(float) : 1),
+                            "avx_ew_run_batch: frame stride of stored plane %d is shorter than the plane (0: the frames would share it)", (int)in.imm);
                 if (kind == AVX_EW_PLANE_U8_ENC) a.uses_encode = 1;
             } else {
                 AVX_REQUIRE(ctx, kind != AVX_EW_PLANE_U8_ENC, "avx_ew_run: load from an encode-only plane");
@@ -312,13 +327,17 @@ extern "C" int avx_ew_run(avx_ctx* ctx, const avx_ew_program* p, void* stream) {
     const int px = (max_reg < 16 && a.n >= (size_t)1 << 20 && !getenv("AVX_EW_PX4")) ? 8 : 4;  // big frames, small programs: 8 pixels per thread
     const size_t want = (a.n + (size_t)kET * px - 1) / ((size_t)kET * px), cap = (size_t)ctx->num_cus * (p->n_acc ? 4 : 8);
     const int grid = (int)(want < cap ? want : cap);
-    if (p->n_acc && ws->d_ew == nullptr) {  // per-block partials + the ticket (zero at rest)
-        const size_t full = (size_t)ctx->num_cus * 8 * AVX_EW_MAX_ACC * sizeof(float) + 256;
+    // per frame of a batch: the ticket words (zero at rest) and the per-block partials.  Allocated once for AVX_EW_MAX_FRAMES frames, so a
+    // later, longer batch never reallocates under a launch that is still in flight on this stream.
+    const size_t partial_fs = (size_t)ctx->num_cus * 8 * AVX_EW_MAX_ACC;
+    if (p->n_acc && ws->d_ew == nullptr) {
+        const size_t full = (size_t)AVX_EW_MAX_FRAMES * (kEwTicketStride * sizeof(uint32_t) + partial_fs * sizeof(float));
         AVX_HIP(ctx, hipMalloc(&ws->d_ew, full));
         AVX_HIP(ctx, hipMemsetAsync(ws->d_ew, 0, full, s));
         ws->ew_cap = full;
     }
-    a.scalars = p->scalars_dev; a.partial = (float*)ws->d_ew + 64; a.ticket = (uint32_t*)ws->d_ew; a.scalars_out = p->scalars_dev;
+    a.scalars = p->scalars_dev; a.ticket = (uint32_t*)ws->d_ew; a.partial = (float*)ws->d_ew + AVX_EW_MAX_FRAMES * kEwTicketStride; a.scalars_out = p->scalars_dev;
+    a.partial_fs = partial_fs;
     a.lut = ctx->d_decode_lut; a.thr = ctx->d_enc_thr_f32; a.coarse = ctx->d_coarse_f32; a.lo_key = ctx->coarse_lo_key[0];
     // A program whose structure was recorded when ew_gen.hip was generated runs as its own straight-line kernel (same arithmetic,
     // registers and loads scheduled by the compiler instead of an instruction at a time); anything else is interpreted.
@@ -342,7 +361,7 @@ extern "C" int avx_ew_run(avx_ctx* ctx, const avx_ew_program* p, void* stream) {
             const EwSpecEntry& e = kEwSpec[mid];
             if (e.h1 == h1 && e.h2 == h2) {
                 ++g_spec_hits;
-                hipLaunchKernelGGL(px == 8 ? e.k8 : e.k4, dim3(grid), dim3(kET), 0, s, a);
+                hipLaunchKernelGGL(px == 8 ? e.k8 : e.k4, dim3(grid, n_frames), dim3(kET), 0, s, a);
                 AVX_HIP(ctx, hipGetLastError());
                 return AVX_OK;
             }
@@ -350,9 +369,9 @@ extern "C" int avx_ew_run(avx_ctx* ctx, const avx_ew_program* p, void* stream) {
         }
         ++g_spec_misses;
     }
-    if (max_reg < 16 && px == 8) hipLaunchKernelGGL((k_ew<16, 8>), dim3(grid), dim3(kET), 0, s, a);
-    else if (max_reg < 16) hipLaunchKernelGGL((k_ew<16, 4>), dim3(grid), dim3(kET), 0, s, a);
-    else hipLaunchKernelGGL((k_ew<32, 4>), dim3(grid), dim3(kET), 0, s, a);
+    if (max_reg < 16 && px == 8) hipLaunchKernelGGL((k_ew<16, 8>), dim3(grid, n_frames), dim3(kET), 0, s, a);
+    else if (max_reg < 16) hipLaunchKernelGGL((k_ew<16, 4>), dim3(grid, n_frames), dim3(kET), 0, s, a);
+    else hipLaunchKernelGGL((k_ew<32, 4>), dim3(grid, n_frames), dim3(kET), 0, s, a);
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
 }

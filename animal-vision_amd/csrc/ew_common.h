@@ -22,7 +22,21 @@ struct EwArgs {
     const float* lut; const float* thr; const uint8_t* coarse; uint32_t lo_key;
     int uses_encode, uses_xy;
     uint32_t* ticket; double* scalars_out; uint8_t acc_out_kind[AVX_EW_MAX_ACC]; int acc_slot[AVX_EW_MAX_ACC];
+    // frames of a batch (blockIdx.y): byte distance from frame f to f + 1 of every plane (0: shared by the frames), of the scalar
+    // table (in doubles) and of the per-block partials (in floats); the ticket words of frame f are at ticket + f * kEwTicketStride
+    size_t plane_fs[AVX_EW_MAX_PLANES];
+    size_t scalars_fs, partial_fs;
 };
+static_assert(sizeof(EwArgs) <= 4096, "EwArgs travels as kernel arguments");
+
+constexpr int kEwTicketStride = 64;  // words per frame: ticket_is_last's 1 + 32 counters, padded
+
+// plane j as frame f of the batch sees it
+__device__ __forceinline__ avx_ew_plane ew_plane_of(const EwArgs& a, int j, unsigned f) {
+    avx_ew_plane p = a.planes[j];
+    p.ptr = (char*)p.ptr + (size_t)f * a.plane_fs[j];
+    return p;
+}
 
 __device__ __forceinline__ float acc_init(int kind) { return kind == AVX_EW_ACC_MIN ? INFINITY : (kind == AVX_EW_ACC_MAX ? -INFINITY : 0.f); }
 __device__ __forceinline__ float acc_merge(int kind, float a, float b) { return kind == AVX_EW_ACC_MIN ? fminf(a, b) : (kind == AVX_EW_ACC_MAX ? fmaxf(a, b) : a + b); }
@@ -31,7 +45,8 @@ __device__ __forceinline__ float acc_merge(int kind, float a, float b) { return 
 // workgroup (ticket) folds the per-block partials into the scalar table.  Same merge order as the interpreter, so a program gives
 // the same scalars through either kernel.
 template <int NACC, int PX>
-__device__ __forceinline__ void ew_reduce_tail(const EwArgs& a, const float (&acc)[NACC][PX]) {
+__device__ __forceinline__ void ew_reduce_tail(const EwArgs& a, const float (&acc)[NACC][PX], const unsigned f) {
+    // f: the frame.  Each frame of a batch reduces on its own: own partials, own ticket words, own scalar table
     __shared__ float red[kET / 64];
     __shared__ int is_last;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -49,12 +64,12 @@ __device__ __forceinline__ void ew_reduce_tail(const EwArgs& a, const float (&ac
         if (tid == 0) {
             float t = red[0];
             for (int w = 1; w < kET / 64; ++w) t = acc_merge(kind, t, red[w]);
-            __hip_atomic_store(&a.partial[(size_t)blockIdx.x * a.n_acc + k], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&a.partial[(size_t)f * a.partial_fs + (size_t)blockIdx.x * a.n_acc + k], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     if (tid == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        is_last = avxk::ticket_is_last(a.ticket, blockIdx.x, gridDim.x);
+        is_last = avxk::ticket_is_last(a.ticket + f * kEwTicketStride, blockIdx.x, gridDim.x);
     }
     __syncthreads();
     if (!is_last) return;
@@ -69,7 +84,7 @@ __device__ __forceinline__ void ew_reduce_tail(const EwArgs& a, const float (&ac
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int i = i0 + 64 * j;
-                vals[j] = i < (int)gridDim.x ? __hip_atomic_load(&a.partial[(size_t)i * a.n_acc + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : init;
+                vals[j] = i < (int)gridDim.x ? __hip_atomic_load(&a.partial[(size_t)f * a.partial_fs + (size_t)i * a.n_acc + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : init;
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -80,11 +95,11 @@ __device__ __forceinline__ void ew_reduce_tail(const EwArgs& a, const float (&ac
         if (mm) {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) vm = acc_merge(kind, vm, __shfl_xor(vm, o));
-            if (lane == 0) a.scalars_out[a.acc_slot[k]] = (double)vm;
+            if (lane == 0) a.scalars_out[(size_t)f * a.scalars_fs + a.acc_slot[k]] = (double)vm;
         } else {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) vs += __shfl_xor(vs, o);
-            if (lane == 0) a.scalars_out[a.acc_slot[k]] = kind == AVX_EW_ACC_MEAN ? (double)((float)vs / (float)a.n) : (double)(float)vs;
+            if (lane == 0) a.scalars_out[(size_t)f * a.scalars_fs + a.acc_slot[k]] = kind == AVX_EW_ACC_MEAN ? (double)((float)vs / (float)a.n) : (double)(float)vs;
         }
     }
 }

@@ -63,7 +63,11 @@ __global__ __launch_bounds__(kMT) void k_encode_hwc(const float* __restrict__ in
 // per 1080p frame; same tables, same arithmetic, byte-identical outputs.
 __global__ __launch_bounds__(kMT) void k_uv_front_u8(const uint8_t* __restrict__ in, int H, int W, const int* __restrict__ idx, const float* __restrict__ ca,
                                                      const float* __restrict__ lut_g, const float* __restrict__ thr_g, const uint8_t* __restrict__ coarse_g,
-                                                     uint32_t lo_key, float* __restrict__ lin_out, uint8_t* __restrict__ base_out) {
+                                                     uint32_t lo_key, float* __restrict__ lin_out, uint8_t* __restrict__ base_out,
+                                                     size_t in_fs, size_t lin_fs, size_t base_fs) {  // frame strides (elements) of a batch: frame = blockIdx.y
+    in += (size_t)blockIdx.y * in_fs;
+    lin_out += (size_t)blockIdx.y * lin_fs;
+    if (base_out) base_out += (size_t)blockIdx.y * base_fs;
     __shared__ float lut[256];
     __shared__ float thr[256];
     __shared__ uint8_t coarse[kCoarseTableBytes];
@@ -98,13 +102,16 @@ __global__ __launch_bounds__(kMT) void k_uv_front_u8(const uint8_t* __restrict__
 // windows: stack[p][k] = sum_j M[k][j] * s2l(lin[p][j])   (HxWxK, the reference's S layout before safe_norm).
 // A pixel with a negative channel (cubic overshoot of the panorama warp) takes the band-by-band route, where
 // the per-wavelength clamp_min(0) of classic_rgb_to_hsi.py:81 is applied before the band-pass sum.
-struct StackArgs { const float* lin; size_t n; const float* M; int K; int B; const float* gains; float denom; const float* wts; float* out; };
+struct StackArgs { const float* lin; size_t n; const float* M; int K; int B; const float* gains; float denom; const float* wts; float* out;
+                   size_t lin_fs, out_fs; };  // frame strides (floats) of a batch: frame = blockIdx.y
 // Round 3: the band-by-band pixels of a workgroup's 256 are COLLECTED (LDS list) and then worked off densely, one (pixel, window) pair per thread: with the route
 // taken inline a wave paid the B-step serial loop for all 64 lanes as soon as one of its pixels had a negative channel -- on structured frames nearly every wave
 // (hummingbird's 270 x 480 small frame: 53 us; 5 % of the pixels take the route).  The tables (B x 3 gains, K x B window weights) are staged in LDS once per
 // workgroup.  A window's sum still runs over b in order with the same operations, so the values are the inline form's.
 constexpr int kStackBMax = 160;  // wavelengths the LDS tables hold (the reference's grids: 31, 81, 129); longer grids read global memory
 __global__ __launch_bounds__(kMT) void k_rgbf_to_stack(StackArgs a) {
+    a.lin += (size_t)blockIdx.y * a.lin_fs;
+    a.out += (size_t)blockIdx.y * a.out_fs;
     __shared__ float M[KMAX * 3];
     __shared__ float gl[kStackBMax * 3];
     __shared__ float wl[kStackBMax * KMAX];  // [b][KMAX]
@@ -627,7 +634,9 @@ int grid_for(avx_ctx* ctx, size_t items) {
 
 // ---- shared front end and band stack of the UV species (also exported on their own, include/avx.h) ------------
 // to_float01 + srgb_to_linear -> panorama_warp -> baseline encode.  tmp: 3*H*W floats (used when the warp is on).
-static int uv_front(avx_ctx* ctx, const uint8_t* in_hwc, int H, int W, int newW, float* tmp, float* lin_out, uint8_t* base_out, hipStream_t s) {
+// n_frames frames at the given strides (elements): one launch on the one-pass route, a loop over the frames on the split route.
+static int uv_front(avx_ctx* ctx, const uint8_t* in_hwc, int H, int W, int newW, float* tmp, float* lin_out, uint8_t* base_out, hipStream_t s,
+                    int n_frames = 1, size_t in_fs = 0, size_t lin_fs = 0, size_t base_fs = 0) {
     const size_t n = (size_t)H * W;
     int rc;
     if (!getenv("AVX_UV_FRONT_SPLIT") && n < ((size_t)1 << 31)) {  // one pass (k_uv_front_u8, 32-bit pixel indices); AVX_UV_FRONT_SPLIT=1: decode, warp and encode as separate launches
@@ -638,9 +647,14 @@ static int uv_front(avx_ctx* ctx, const uint8_t* in_hwc, int H, int W, int newW,
             if (!ws) return AVX_ERR_NOMEM;
             if ((rc = avx_geom_cubic_x_tables(ctx, ws, s, W, newW, (newW - W) / 2, &idx, &ca))) return rc;
         }
-        hipLaunchKernelGGL(k_uv_front_u8, dim3(grid_for(ctx, n)), dim3(kMT), 0, s, in_hwc, H, W, idx, ca, ctx->d_decode_lut, ctx->d_enc_thr_f32, ctx->d_coarse_f32,
-                           ctx->coarse_lo_key[0], lin_out, base_out);
+        hipLaunchKernelGGL(k_uv_front_u8, dim3(grid_for(ctx, n), n_frames), dim3(kMT), 0, s, in_hwc, H, W, idx, ca, ctx->d_decode_lut, ctx->d_enc_thr_f32, ctx->d_coarse_f32,
+                           ctx->coarse_lo_key[0], lin_out, base_out, in_fs, lin_fs, base_fs);
         AVX_HIP(ctx, hipGetLastError());
+        return AVX_OK;
+    }
+    if (n_frames > 1) {
+        for (int f = 0; f < n_frames; ++f)
+            if ((rc = uv_front(ctx, in_hwc + f * in_fs, H, W, newW, tmp, lin_out + f * lin_fs, base_out ? base_out + f * base_fs : nullptr, s))) return rc;
         return AVX_OK;
     }
     if (newW > W) {
@@ -658,7 +672,8 @@ static int uv_front(avx_ctx* ctx, const uint8_t* in_hwc, int H, int W, int newW,
 // classic_rgb_to_hsi(_scaled) x K band windows -> HxWxK stack (raw integrate_band values).
 // tab: (K*3 + B*3 + K*B) floats of device scratch; small / sstack: 3*hs*ws and hs*ws*K floats (reduced-size route).
 static int band_stack(avx_ctx* ctx, const float* lin_hwc, int H, int W, int K, const float* M_host, int B, const float* gains_host, float denom,
-                      const float* wts_host, int hs, int wsm, float* tab, float* small, float* sstack, float* stack, hipStream_t s) {
+                      const float* wts_host, int hs, int wsm, float* tab, float* small, float* sstack, float* stack, hipStream_t s,
+                      int n_frames = 1, size_t lin_fs = 0, size_t stack_fs = 0) {
     // The three small tables are constants of a species: cached on the device under a hash of their contents (one
     // blocking upload the first time, no per-frame copies afterwards); `tab` is unused when the cache holds them.
     (void)tab;
@@ -687,20 +702,30 @@ static int band_stack(avx_ctx* ctx, const float* lin_hwc, int H, int W, int K, c
     float* dgains = dM + K * 3; float* dwts = dgains + 3 * B;
     const size_t n = (size_t)H * W, nsmall = (size_t)hs * wsm;
     int rc;
-    if (hs != H || wsm != W) {
-        if ((rc = avx_resize_hwc(ctx, lin_hwc, 0, H, W, 3, small, hs, wsm, 3, s))) return rc;
-        hipLaunchKernelGGL(k_rgbf_to_stack, dim3(grid_for(ctx, nsmall)), dim3(kMT), 0, s, StackArgs{small, nsmall, dM, K, B, dgains, denom, dwts, sstack});
-        if ((rc = avx_resize_hwc(ctx, sstack, 0, hs, wsm, K, stack, H, W, 1, s))) return rc;
+    if (hs != H || wsm != W) {  // reduced size: the frames of a batch one after the other through the same scratch (the stream orders them)
+        for (int f = 0; f < n_frames; ++f) {
+            if ((rc = avx_resize_hwc(ctx, lin_hwc + f * lin_fs, 0, H, W, 3, small, hs, wsm, 3, s))) return rc;
+            hipLaunchKernelGGL(k_rgbf_to_stack, dim3(grid_for(ctx, nsmall)), dim3(kMT), 0, s, StackArgs{small, nsmall, dM, K, B, dgains, denom, dwts, sstack});
+            if ((rc = avx_resize_hwc(ctx, sstack, 0, hs, wsm, K, stack + f * stack_fs, H, W, 1, s))) return rc;
+        }
     } else {
-        hipLaunchKernelGGL(k_rgbf_to_stack, dim3(grid_for(ctx, n)), dim3(kMT), 0, s, StackArgs{lin_hwc, n, dM, K, B, dgains, denom, dwts, stack});
+        hipLaunchKernelGGL(k_rgbf_to_stack, dim3(grid_for(ctx, n), n_frames), dim3(kMT), 0, s, StackArgs{lin_hwc, n, dM, K, B, dgains, denom, dwts, stack, lin_fs, stack_fs});
     }
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
 }
 
 extern "C" int avx_uv_front_u8(avx_ctx* ctx, const uint8_t* in_hwc, int H, int W, int pano_new_w, float* lin_hwc_out, uint8_t* baseline_hwc_out, void* stream) {
+    return avx_uv_front_u8_batch(ctx, in_hwc, 1, 0, H, W, pano_new_w, lin_hwc_out, 0, baseline_hwc_out, 0, stream);
+}
+
+extern "C" int avx_uv_front_u8_batch(avx_ctx* ctx, const uint8_t* in_hwc, int n_frames, size_t in_frame_stride, int H, int W, int pano_new_w, float* lin_hwc_out,
+                                     size_t lin_frame_stride, uint8_t* baseline_hwc_out, size_t baseline_frame_stride, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
     AVX_REQUIRE(ctx, in_hwc && lin_hwc_out && H > 0 && W > 0, "avx_uv_front_u8: bad arguments");
+    AVX_REQUIRE(ctx, n_frames >= 1 && n_frames <= AVX_EW_MAX_FRAMES, "avx_uv_front_u8_batch: n_frames %d outside 1..%d", n_frames, AVX_EW_MAX_FRAMES);
+    AVX_REQUIRE(ctx, n_frames == 1 || (in_frame_stride >= 3 * (size_t)H * W && lin_frame_stride >= 3 * (size_t)H * W && (!baseline_hwc_out || baseline_frame_stride >= 3 * (size_t)H * W)),
+                "avx_uv_front_u8_batch: frame strides shorter than a frame");
     AVX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = avx_pick_stream(ctx, stream);
     avx_ws* ws = avx_workspace(ctx, s);
@@ -712,7 +737,7 @@ extern "C" int avx_uv_front_u8(avx_ctx* ctx, const uint8_t* in_hwc, int H, int W
         if (rc) return rc;
         tmp = (float*)ws->d_scratch;
     }
-    return uv_front(ctx, in_hwc, H, W, newW, tmp, lin_hwc_out, baseline_hwc_out, s);
+    return uv_front(ctx, in_hwc, H, W, newW, tmp, lin_hwc_out, baseline_hwc_out, s, n_frames, in_frame_stride, lin_frame_stride, baseline_frame_stride);
 }
 
 extern "C" int avx_panorama_warp_f32(avx_ctx* ctx, const float* src_hwc, int H, int W, int new_w, float* dst_hwc, void* stream) {
@@ -723,8 +748,16 @@ extern "C" int avx_panorama_warp_f32(avx_ctx* ctx, const float* src_hwc, int H, 
 }
 
 extern "C" int avx_band_stack(avx_ctx* ctx, const float* lin_hwc, int H, int W, const avx_band_stack_desc* d, float* stack_hwk_out, void* stream) {
+    return avx_band_stack_batch(ctx, lin_hwc, 1, 0, H, W, d, stack_hwk_out, 0, stream);
+}
+
+extern "C" int avx_band_stack_batch(avx_ctx* ctx, const float* lin_hwc, int n_frames, size_t lin_frame_stride, int H, int W, const avx_band_stack_desc* d,
+                                    float* stack_hwk_out, size_t stack_frame_stride, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
     AVX_REQUIRE(ctx, d && d->struct_size == sizeof(avx_band_stack_desc), "avx_band_stack: desc is NULL or struct_size mismatch");
+    AVX_REQUIRE(ctx, n_frames >= 1 && n_frames <= AVX_EW_MAX_FRAMES, "avx_band_stack_batch: n_frames %d outside 1..%d", n_frames, AVX_EW_MAX_FRAMES);
+    AVX_REQUIRE(ctx, n_frames == 1 || (H > 0 && W > 0 && lin_frame_stride >= 3 * (size_t)H * W && d->n_bands >= 1 && stack_frame_stride >= (size_t)d->n_bands * H * W),
+                "avx_band_stack_batch: frame strides shorter than a frame");
     AVX_REQUIRE(ctx, lin_hwc && stack_hwk_out && H > 0 && W > 0, "avx_band_stack: bad arguments");
     AVX_REQUIRE(ctx, d->n_bands >= 1 && d->n_bands <= KMAX && d->band_matrix_host && d->n_wavelengths >= 1 && d->lobe_gains_host && d->band_weights_host && d->lobe_denom > 0.f,
                 "avx_band_stack: bad band tables");
@@ -742,7 +775,7 @@ extern "C" int avx_band_stack(avx_ctx* ctx, const float* lin_hwc, int H, int W, 
     if (rc) return rc;
     float* base = (float*)ws->d_scratch;
     return band_stack(ctx, lin_hwc, H, W, K, d->band_matrix_host, B, d->lobe_gains_host, d->lobe_denom, d->band_weights_host, hs, wsm, base + o_tab, base + o_small,
-                      base + o_sstack, stack_hwk_out, s);
+                      base + o_sstack, stack_hwk_out, s, n_frames, lin_frame_stride, stack_frame_stride);
 }
 
 extern "C" int avx_percentiles_dev(avx_ctx* ctx, int count, const float* const* data_dev, const size_t* n, const double* q, double* const* out_dev, void* stream) {

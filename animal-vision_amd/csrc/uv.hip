@@ -291,6 +291,7 @@ __global__ void k_finalize_stats(const Stat3* partials, int nblocks, int K, size
 struct BlurArgs {
     const float* in; float* out; int K, H, W, r; const float4* stats; int scale_mode;
     float taps[AVX_MAX_KSIZE];
+    size_t in_fs, out_fs;  // frame strides (floats) of a batch: frame = blockIdx.y
 };
 
 __device__ __forceinline__ float rescale(float v, int mode, float4 st) {
@@ -312,8 +313,8 @@ __global__ __launch_bounds__(kT) void k_plane_blur(BlurArgs a) {
         const int k = tile / (tiles_x * tiles_y), t2 = tile - k * tiles_x * tiles_y;
         const int ty = t2 / tiles_x, tx = t2 - ty * tiles_x;
         const int x0 = tx * TW, y0 = ty * TH;
-        const float* src = a.in + (size_t)k * n;
-        float* dst = a.out + (size_t)k * n;
+        const float* src = a.in + (size_t)blockIdx.y * a.in_fs + (size_t)k * n;
+        float* dst = a.out + (size_t)blockIdx.y * a.out_fs + (size_t)k * n;
         const float4 st = a.scale_mode ? a.stats[k] : make_float4(0.f, 0.f, 0.f, 1.f);
         for (int i = threadIdx.x; i < AH * AW; i += kT) {
             const int ly = i / AW, lx = i - ly * AW;
@@ -373,8 +374,8 @@ __global__ __launch_bounds__(kT) void k_plane_blur_t(BlurArgs a) {
         const int k = tile / (tiles_x * tiles_y), t2 = tile - k * tiles_x * tiles_y;
         const int ty = t2 / tiles_x, tx = t2 - ty * tiles_x;
         const int x0 = tx * TW, y0 = ty * TH;
-        const float* src = a.in + (size_t)k * n;
-        float* dst = a.out + (size_t)k * n;
+        const float* src = a.in + (size_t)blockIdx.y * a.in_fs + (size_t)k * n;
+        float* dst = a.out + (size_t)blockIdx.y * a.out_fs + (size_t)k * n;
         const float4 st = a.scale_mode ? a.stats[k] : make_float4(0.f, 0.f, 0.f, 1.f);
         const bool interior = x0 - R >= 0 && x0 + TW + R <= a.W && y0 - R >= 0 && y0 + TH + R <= a.H;  // uniform
         constexpr int AW = TW + 2 * R, NLD = (AH * AW + kT - 1) / kT;
@@ -442,14 +443,14 @@ __global__ __launch_bounds__(kT) void k_plane_blur_t(BlurArgs a) {
 }
 
 // one place that launches a plane blur: the compile-time-radius kernel where an instantiation exists, else the generic one
-static int launch_plane_blur(avx_ctx* ctx, const BlurArgs& a, hipStream_t s) {
+static int launch_plane_blur(avx_ctx* ctx, const BlurArgs& a, hipStream_t s, int n_frames = 1) {
     const long tiles = (long)((a.W + 63) / 64) * ((a.H + 31) / 32) * a.K;
     const int g = (int)(tiles < (long)ctx->num_cus * 8 ? tiles : (long)ctx->num_cus * 8);  // measured: 8 per CU beats 4 by 3-4 %
 #define AVX_BLUR_T(RR)                                                                                                       \
     case RR: {                                                                                                               \
         const size_t lds = sizeof(float) * ((size_t)(32 + 2 * RR) * ((64 + 2 * RR + 3) & ~3) + (size_t)(32 + 2 * RR) * 64);    \
         AVX_HIP(ctx, hipFuncSetAttribute((const void*)k_plane_blur_t<RR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(k_plane_blur_t<RR>, dim3(g), dim3(kT), lds, s, a);                                                 \
+        hipLaunchKernelGGL(k_plane_blur_t<RR>, dim3(g, n_frames), dim3(kT), lds, s, a);                                                 \
         break;                                                                                                               \
     }
     switch (a.r) {
@@ -458,7 +459,7 @@ static int launch_plane_blur(avx_ctx* ctx, const BlurArgs& a, hipStream_t s) {
             const int AW = 64 + 2 * a.r, AH = 32 + 2 * a.r;
             const size_t lds = sizeof(float) * ((size_t)AH * AW + (size_t)AH * 64);
             AVX_HIP(ctx, hipFuncSetAttribute((const void*)k_plane_blur, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_plane_blur, dim3(g), dim3(kT), lds, s, a);
+            hipLaunchKernelGGL(k_plane_blur, dim3(g, n_frames), dim3(kT), lds, s, a);
         }
     }
 #undef AVX_BLUR_T
@@ -1712,7 +1713,16 @@ int avx_spectral_integrate(avx_ctx* ctx, const void* hsi, int layout, int dtype,
 
 int avx_planes_gaussian_blur(avx_ctx* ctx, const float* in, float* out, int K, int H, int W, int ksize, const double* taps_host,
                              int scale_mode, void* stream) {
+    return avx_planes_gaussian_blur_batch(ctx, in, 0, out, 0, 1, K, H, W, ksize, taps_host, scale_mode, stream);
+}
+
+int avx_planes_gaussian_blur_batch(avx_ctx* ctx, const float* in, size_t in_frame_stride, float* out, size_t out_frame_stride, int n_frames, int K, int H, int W,
+                                   int ksize, const double* taps_host, int scale_mode, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, n_frames >= 1 && n_frames <= AVX_EW_MAX_FRAMES, "avx_planes_gaussian_blur_batch: n_frames %d outside 1..%d", n_frames, AVX_EW_MAX_FRAMES);
+    AVX_REQUIRE(ctx, n_frames == 1 || (K > 0 && H > 0 && W > 0 && in_frame_stride >= (size_t)K * H * W && out_frame_stride >= (size_t)K * H * W),
+                "avx_planes_gaussian_blur_batch: frame strides shorter than a frame");
+    AVX_REQUIRE(ctx, n_frames == 1 || scale_mode == 0, "avx_planes_gaussian_blur_batch: the statistics of scale_mode %d are one frame's", scale_mode);
     AVX_REQUIRE(ctx, in && out && in != out, "avx_planes_gaussian_blur: NULL or aliased planes");
     AVX_REQUIRE(ctx, K > 0 && K <= 16 && H > 0 && W > 0, "avx_planes_gaussian_blur: bad shape");
     AVX_REQUIRE(ctx, ksize >= 1 && ksize <= AVX_MAX_KSIZE && (ksize & 1), "avx_planes_gaussian_blur: ksize %d must be odd, 1..%d", ksize, AVX_MAX_KSIZE);
@@ -1726,7 +1736,8 @@ int avx_planes_gaussian_blur(avx_ctx* ctx, const float* in, float* out, int K, i
     BlurArgs a{};
     a.in = in; a.out = out; a.K = K; a.H = H; a.W = W; a.r = ksize / 2; a.stats = u.stats; a.scale_mode = scale_mode;
     for (int i = 0; i < ksize; ++i) a.taps[i] = ksize == 1 ? 1.0f : (float)taps_host[i];
-    return launch_plane_blur(ctx, a, s);
+    a.in_fs = in_frame_stride; a.out_fs = out_frame_stride;
+    return launch_plane_blur(ctx, a, s, n_frames);
 }
 
 int avx_plane_stats(avx_ctx* ctx, const float* planes, int K, size_t n, int adapt, float eps, float* stats_host, void* stream) {

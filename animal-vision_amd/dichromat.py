@@ -168,6 +168,8 @@ class DichromatOp:
             self.ctx = get_context()
         return self.ctx
 
+    max_batch = 16  # frames one run_device call takes from a pipeline slot (pipeline.FramePipeline(batch=))
+
     def run_device(self, d_in: DeviceBuffer, d_out: DeviceBuffer, n_frames: int, H: int, W: int, stream=None):
         """N uint8 HWC frames resident in HBM -> N uint8 HWC frames; asynchronous on `stream`."""
         ctx = self._ctx()

@@ -101,18 +101,19 @@ class _Slot:
     d_out: object
     index: int = -1
     busy: bool = False
+    indices: List[int] = field(default_factory=list)  # global indices of the frames the slot carries (<= batch)
     d_yuv_in: object = None   # io_format="i420": the frame's payload on the device, in and out
     d_yuv_out: object = None
     d_left: object = None     # the left half of the split frame: d_in, or the op's baseline (split_baseline)
 
 
 class FramePipeline:
-    """Runs `op.run_device(d_in, d_out, 1, H, W, stream=...)` (DichromatOp / HoneybeeOp) over a stream of
-    uint8 frames with `depth` frames in flight."""
+    """Runs `op.run_device(d_in, d_out, n, H, W, stream=...)` (DichromatOp / HoneybeeOp / SpeciesStreamOp) over a stream of
+    uint8 frames with `depth` slots in flight, each carrying up to `batch` frames (n = batch, or what is left at the end)."""
 
     def __init__(self, op, H: int, W: int, *, ctx=None, depth: int = 3, split_compare: bool = False, draw_seam: bool = True,
                  labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed"), io_format: str = "rgb",
-                 matrix: str = "bt601", yuv_range: str = "limited", split_baseline: bool = False):
+                 matrix: str = "bt601", yuv_range: str = "limited", split_baseline: bool = False, batch: int = 1):
         """split_compare: emit make_split_frame(original, transformed) composed on the device (renderers/video.py:198-245:
         halves, seam, and the two corner labels -- `labels` = (left, right), None = none) instead of the transformed frame.
 
@@ -121,7 +122,12 @@ class FramePipeline:
         d_out (yuv.py, with `matrix` and `yuv_range`); the op, the split composition and the labels run on RGB as before.
 
         split_baseline: the split frame's left half is the op's own baseline -- `op.slot_baseline(k)`, the frame a species'
-        visualize() returns first (a UV species' panorama-warped input, SpeciesStreamOp) -- instead of the input frame."""
+        visualize() returns first (a UV species' panorama-warped input, SpeciesStreamOp) -- instead of the input frame.
+
+        batch: frames per slot.  A slot's pinned staging and device buffers hold `batch` contiguous frames: one H2D copy, one
+        op.run_device(..., n, ...), the split composition and labels per frame, the I420 conversions over the n frames, one D2H
+        copy.  Frames are still emitted one by one in submission order; the last slot of a stream may carry fewer frames.  The
+        op states how many frames one call takes in `max_batch` (absent: 1); an op that cannot take `batch` is refused here."""
         from .runtime import get_context
         from .yuv import _codes, i420_size
 
@@ -130,6 +136,12 @@ class FramePipeline:
         _codes(matrix, yuv_range)
         self.io_format, self.matrix, self.yuv_range = io_format, matrix, yuv_range
         self.op, self.H, self.W, self.depth = op, H, W, depth
+        self.batch = int(batch)
+        if self.batch < 1:
+            raise ValueError(f"batch must be at least 1 (got {batch})")
+        cap = getattr(op, "max_batch", 1)
+        if self.batch > 1 and self.batch > cap:
+            raise ValueError(f"batch={self.batch}: {type(op).__name__} takes at most {cap} frame(s) per call")
         self.split_compare, self.draw_seam = bool(split_compare), bool(draw_seam)
         baseline = getattr(op, "slot_baseline", None) if split_baseline else None
         if split_baseline and baseline is None:
@@ -138,18 +150,21 @@ class FramePipeline:
         self.ctx = ctx or getattr(op, "ctx", None) or get_context()
         if getattr(op, "ctx", None) is None:
             op.ctx = self.ctx
-        nbytes = H * W * 3
+        nbytes = H * W * 3 * self.batch
         # ops that own their device frames (recorded species plans, animals/_uv_species.py::SpeciesStreamOp) lend them per slot
         lend = getattr(op, "slot_buffers", None)
         self._lent = lend is not None
         self.slots = []
         self._io_shape = (H, W, 3) if io_format == "rgb" else (i420_size(H, W),)
+        stage = (self.batch,) + self._io_shape
         for k in range(depth):
             d_in, d_out = lend(k) if lend else (self.ctx.malloc(nbytes), self.ctx.malloc(nbytes))
-            s = _Slot(self.ctx.stream_create(), self.ctx.pinned(self._io_shape, np.uint8), self.ctx.pinned(self._io_shape, np.uint8), d_in, d_out)
+            if d_in.nbytes < nbytes or d_out.nbytes < nbytes:
+                raise ValueError(f"batch={self.batch}: {type(op).__name__}'s slot buffers hold fewer than {self.batch} frames")
+            s = _Slot(self.ctx.stream_create(), self.ctx.pinned(stage, np.uint8), self.ctx.pinned(stage, np.uint8), d_in, d_out)
             s.d_left = baseline(k) if baseline is not None else d_in
             if io_format == "i420":
-                s.d_yuv_in, s.d_yuv_out = self.ctx.malloc(i420_size(H, W)), self.ctx.malloc(i420_size(H, W))
+                s.d_yuv_in, s.d_yuv_out = self.ctx.malloc(self.batch * i420_size(H, W)), self.ctx.malloc(self.batch * i420_size(H, W))
             self.slots.append(s)
 
     def close(self):
@@ -170,12 +185,13 @@ class FramePipeline:
     def _retire(self, s: _Slot, emit: Callable[[int, np.ndarray], None]):
         if s.busy:
             self.ctx.sync(s.stream)
-            t0 = time.perf_counter()
-            out = np.empty_like(s.h_out.array)
-            _pcopy(out, s.h_out.array)
-            self._copy_s += time.perf_counter() - t0
-            emit(s.index, out)
-            s.busy = False
+            for j, index in enumerate(s.indices):
+                t0 = time.perf_counter()
+                out = np.empty(self._io_shape, np.uint8)
+                _pcopy(out, s.h_out.array[j])
+                self._copy_s += time.perf_counter() - t0
+                emit(index, out)
+            s.busy, s.indices = False, []
 
     def run(self, frames: Iterator[Tuple[int, np.ndarray]], emit: Callable[[int, np.ndarray], None]) -> StreamStats:
         """frames: (global index, HxWx3 uint8 -- or, io_format="i420", a flat I420 payload) pairs owned by this rank;
@@ -185,42 +201,62 @@ class FramePipeline:
 
         ctx, n, t0 = self.ctx, 0, time.perf_counter()
         self._copy_s = 0.0
+        for s in self.slots:  # a run that ended in an error may have left a half-filled slot behind
+            s.busy, s.indices = False, []
         i420 = self.io_format == "i420"
-        nbytes = int(np.prod(self._io_shape))
-        for k, (index, frame) in enumerate(frames):
-            s = self.slots[k % self.depth]
-            self._retire(s, emit)
+        fbytes = int(np.prod(self._io_shape))
+        rgb_bytes = self.H * self.W * 3
+
+        def submit(s: _Slot):
+            """Everything one slot's frames need, in order on the slot's stream."""
+            m = len(s.indices)
+            if i420:
+                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_yuv_in.ptr, s.h_in.ptr, m * fbytes, s.stream))
+                i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, m, self.H, self.W, matrix=self.matrix, range=self.yuv_range, stream=s.stream)
+            else:
+                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_in.ptr, s.h_in.ptr, m * fbytes, s.stream))
+            self.op.run_device(s.d_in, s.d_out, m, self.H, self.W, stream=s.stream)
+            if self.split_compare:
+                for f in range(m):
+                    o = f * rgb_bytes
+                    ctx._check(lib.avx_split_compose_u8(ctx._h, s.d_left.ptr + o, s.d_out.ptr + o, s.d_out.ptr + o, self.H, self.W, int(self.draw_seam), s.stream))
+                    if self.labels[0] is not None or self.labels[1] is not None:
+                        from .renderers.labels import draw_split_labels_device
+
+                        draw_split_labels_device(ctx, s.d_out.ptr + o, self.H, self.W, self.labels[0], self.labels[1], s.stream)
+            if i420:
+                rgb_to_i420_device(ctx, s.d_out, s.d_yuv_out, m, self.H, self.W, matrix=self.matrix, range=self.yuv_range, stream=s.stream)
+                ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_yuv_out.ptr, m * fbytes, s.stream))
+            else:
+                ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_out.ptr, m * fbytes, s.stream))
+            s.index, s.busy = s.indices[0], True
+
+        k, s = 0, None  # slots submitted so far; the slot being filled
+        for index, frame in frames:
+            if s is None:
+                s = self.slots[k % self.depth]
+                self._retire(s, emit)
             if frame.shape != self._io_shape or frame.dtype != np.uint8:
                 raise ValueError(f"frame {index}: expected uint8 {self._io_shape}, got {frame.dtype} {frame.shape}")
             tc = time.perf_counter()
-            _pcopy(s.h_in.array, frame)
+            _pcopy(s.h_in.array[len(s.indices)], frame)
             self._copy_s += time.perf_counter() - tc
-            if i420:
-                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_yuv_in.ptr, s.h_in.ptr, nbytes, s.stream))
-                i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, 1, self.H, self.W, matrix=self.matrix, range=self.yuv_range, stream=s.stream)
-            else:
-                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_in.ptr, s.h_in.ptr, nbytes, s.stream))
-            self.op.run_device(s.d_in, s.d_out, 1, self.H, self.W, stream=s.stream)
-            if self.split_compare:
-                ctx._check(lib.avx_split_compose_u8(ctx._h, s.d_left.ptr, s.d_out.ptr, s.d_out.ptr, self.H, self.W, int(self.draw_seam), s.stream))
-                if self.labels[0] is not None or self.labels[1] is not None:
-                    from .renderers.labels import draw_split_labels_device
-
-                    draw_split_labels_device(ctx, s.d_out, self.H, self.W, self.labels[0], self.labels[1], s.stream)
-            if i420:
-                rgb_to_i420_device(ctx, s.d_out, s.d_yuv_out, 1, self.H, self.W, matrix=self.matrix, range=self.yuv_range, stream=s.stream)
-                ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_yuv_out.ptr, nbytes, s.stream))
-            else:
-                ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_out.ptr, nbytes, s.stream))
-            s.index, s.busy = index, True
+            s.indices.append(index)
             n += 1
+            if len(s.indices) == self.batch:
+                submit(s)
+                k, s = k + 1, None
+        if s is not None and s.indices:  # the stream's last, partial batch
+            submit(s)
+            k += 1
         for j in range(self.depth):  # drain in submission order
-            self._retire(self.slots[(n + j) % self.depth], emit)
+            self._retire(self.slots[(k + j) % self.depth], emit)
         return StreamStats(n, n * self.H * self.W, time.perf_counter() - t0, 1, self._copy_s)
 
 
 def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int = 3, split_compare: bool = False, dist=None,
-              labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed"), split_baseline: bool = False) -> StreamStats:
+              labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed"), split_baseline: bool = False,
+              batch: int = 1) -> StreamStats:
     """main.py:53-72 on the device: read -> visualize -> (split-compose + labels) -> render, this rank's shard only.
 
     A renderer that shards itself (renderers.VideoRenderer(rank=, world=): strided source, index-addressed sink) hands over
@@ -231,7 +267,7 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
 
     A renderer whose frames can stay I420 end to end (`yuv_hw` not None: renderers.VideoRenderer from a .y4m to a .y4m) hands
     over get_yuv() payloads, and the pipeline runs with io_format="i420" in the renderer's `matrix` and `yuv_range`.
-    split_baseline: see FramePipeline."""
+    split_baseline, batch (frames per slot and per op call): see FramePipeline."""
     self_sharding = getattr(renderer, "world", 1) == world and getattr(renderer, "rank", 0) == rank and hasattr(renderer, "last_index") and world > 1
     yuv_hw = getattr(renderer, "yuv_hw", None) if callable(getattr(renderer, "get_yuv", None)) else None
     get = renderer.get_yuv if yuv_hw is not None else renderer.get_image
@@ -242,10 +278,10 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
     elif yuv_hw is not None:
         H, W = yuv_hw
         pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, io_format="i420",
-                             matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline)
+                             matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline, batch=batch)
     else:
         H, W, _ = first.shape
-        pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, split_baseline=split_baseline)
+        pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, split_baseline=split_baseline, batch=batch)
 
     def frames():
         i, f = 0, first

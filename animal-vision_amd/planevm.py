@@ -36,13 +36,17 @@ _BINARY = {"add": "ADD", "sub": "SUB", "mul": "MUL", "div": "DIV", "min": "MIN",
 
 
 class PlaneRef:
-    """One addressable plane: element i of the frame at ptr[i * stride] (float32) / per-column / per-row vector."""
+    """One addressable plane: element i of the frame at ptr[i * stride] (float32) / per-column / per-row vector.
 
-    __slots__ = ("buf", "offset", "stride", "kind", "uid")
+    `offset` is the plane's place inside ONE frame's layout of its buffer; `fstride` is the buffer's per-frame size in bytes: a
+    backend with frames=N keeps N copies of the layout back to back, frame f of the plane is at ptr + f * fstride (0: shared by
+    the frames).  The backend fills it in (`DeviceBackend.frame_stride`) when the plane first enters a recorded call."""
+
+    __slots__ = ("buf", "offset", "stride", "kind", "uid", "fstride")
     _next = 0
 
     def __init__(self, buf: DeviceBuffer, offset: int = 0, stride: int = 1, kind: str = "f32"):
-        self.buf, self.offset, self.stride, self.kind = buf, int(offset), int(stride), kind
+        self.buf, self.offset, self.stride, self.kind, self.fstride = buf, int(offset), int(stride), kind, None
         PlaneRef._next += 1
         self.uid = PlaneRef._next
 
@@ -255,6 +259,7 @@ class _Compiled:
         self.n_insn = len(insn)
         self.insn = (EwInsn * len(insn))(*[EwInsn(*t) for t in insn])
         self.planes = (EwPlane * max(1, len(planes)))(*[EwPlane(p.ptr, p.stride, EW_PLANE[p.kind]) for p in planes])
+        self.fstrides = (ctypes.c_size_t * max(1, len(planes)))(*[be.frame_stride(p) for p in planes])  # avx_ew_run_batch
         self._keep = planes
         flat = []
         for o in accs:
@@ -271,39 +276,69 @@ class _Compiled:
 
 
 class DeviceBackend:
-    """Records the device call sequence of one species for one frame size; `run()` replays it per frame."""
+    """Records the device call sequence of one species for one frame size; `run()` replays it per frame.
+
+    frames=N (uint8 video frames): the plan owns everything N times over and every recorded call is the batched call -- the
+    frame is a grid dimension of the kernels, so N frames cost one launch wherever one frame costs one.  d_in /
+    d_base / d_out are N contiguous HWC frames, every buffer of `_alloc` / `new_planes` is N copies of its one-frame layout, the
+    scalar table is N x N_SCALARS doubles; host-built vectors (col, row, taps, band tables) are shared.  `run_device(stream,
+    n_frames=m)` replays the first m <= N frames.  frames=1 records and runs exactly the single-frame calls."""
 
     N_SCALARS = 256
     name = "device"
 
-    def __init__(self, H: int, W: int, ctx: Optional[Context] = None, float_frames: bool = False):
+    def __init__(self, H: int, W: int, ctx: Optional[Context] = None, float_frames: bool = False, frames: int = 1):
         """float_frames: the frames are float32 HxWx3 (sRGB in [0,1] or [0,255]); outputs are float32 too."""
         self.ctx = ctx or get_context()
         self.float_frames = bool(float_frames)
+        self.frames = int(frames)
+        if not 1 <= self.frames <= _lib.AVX_EW_MAX_FRAMES:
+            raise ValueError(f"frames={frames}: a plan holds 1..{_lib.AVX_EW_MAX_FRAMES} frames")
+        if self.float_frames and self.frames > 1:
+            raise NotImplementedError("batched plans (frames > 1) are for uint8 video frames; float frames run one frame per plan")
         self.H, self.W, self.n = int(H), int(W), int(H) * int(W)
         self.plan: List = []          # callables(stream)
         self.pending: List = []       # outputs of the elementwise program being assembled
         self._pend_planes: set = set()
         self._pend_slots: set = set()
-        self.scalars = self.ctx.malloc(8 * self.N_SCALARS)
+        self.scalars = self.ctx.malloc(8 * self.N_SCALARS * self.frames)
         self._slot = 0
         self._bufs: List[DeviceBuffer] = [self.scalars]
+        self._fs: Dict[int, int] = {}  # id(buffer) -> bytes of ONE frame's layout in it (absent: shared by the frames)
         self._keep: List = []         # ctypes structs / host arrays referenced by the recorded calls
         item = 4 if self.float_frames else 1
-        self.d_in = self.ctx.malloc(3 * self.n * item)
-        self.d_base = self.ctx.malloc(3 * self.n * item)
-        self.d_out = self.ctx.malloc(3 * self.n * item)
-        self._bufs += [self.d_in, self.d_base, self.d_out]
+        self.d_in = self._alloc(3 * self.n * item)
+        self.d_base = self._alloc(3 * self.n * item)
+        self.d_out = self._alloc(3 * self.n * item)
         self.n_programs = 0
         self.n_insn = 0
         self._memo: Dict = {}         # id(Val) / tuple of ids -> materialised loads (keeps the Vals alive)
         self.stages: List[str] = []   # human-readable trace of the recorded plan (tools/dbg_plan.py)
 
     # -- memory ------------------------------------------------------------------------------------
-    def _alloc(self, nbytes: int) -> DeviceBuffer:
-        b = self.ctx.malloc(nbytes)
+    def _alloc(self, nbytes: int, shared: bool = False) -> DeviceBuffer:
+        """`nbytes` per frame (x frames, back to back); shared=True: one copy every frame reads (host-built vectors)."""
+        b = self.ctx.malloc(nbytes if shared else nbytes * self.frames)
         self._bufs.append(b)
+        if not shared:
+            self._fs[id(b)] = int(nbytes)
         return b
+
+    def frame_stride(self, ref: PlaneRef) -> int:
+        """Bytes from frame f to frame f + 1 of the plane (0: shared)."""
+        if ref.fstride is None:
+            ref.fstride = self._fs.get(id(ref.buf), 0)
+        return ref.fstride
+
+    def _frames_loop(self, fn):
+        """A stage without a batched entry point: one call per live frame, on the same stream.  fn(stream, frame)."""
+        if self.frames == 1:
+            return lambda s, m=1: fn(s, 0)
+
+        def loop(s, m=1):
+            for f in range(m):
+                fn(s, f)
+        return loop
 
     def new_planes(self, k: int = 1) -> List[PlaneRef]:
         b = self._alloc(4 * self.n * k)
@@ -334,7 +369,7 @@ class DeviceBackend:
     def _vector(self, vec: np.ndarray, kind: str) -> Val:
         v = np.ascontiguousarray(vec, dtype=np.float32)
         assert v.shape == ((self.W,) if kind == "col" else (self.H,))
-        b = self._alloc(v.nbytes)
+        b = self._alloc(v.nbytes, shared=True)
         self.ctx.upload(v, b)
         return self.load(PlaneRef(b, 0, 1, kind))
 
@@ -383,8 +418,11 @@ class DeviceBackend:
         self._keep.append(comp)
         self.n_programs += 1
         self.n_insn += comp.n_insn
-        ctx = self.ctx
-        self.plan.append(lambda s, c=comp: ctx._check(lib.avx_ew_run(ctx._h, ctypes.byref(c.program), s)))
+        ctx, ns = self.ctx, self.N_SCALARS
+        if self.frames == 1:
+            self.plan.append(lambda s, m=1, c=comp: ctx._check(lib.avx_ew_run(ctx._h, ctypes.byref(c.program), s)))
+        else:
+            self.plan.append(lambda s, m=1, c=comp: ctx._check(lib.avx_ew_run_batch(ctx._h, ctypes.byref(c.program), m, c.fstrides, ns, s)))
         self.stages.append(f"ew[{comp.n_insn} insn, {comp.n_regs} regs, {comp.program.n_planes} planes, {comp.program.n_acc} acc]")
         self.pending, self._pend_planes, self._pend_slots = [], set(), set()
 
@@ -459,48 +497,84 @@ class DeviceBackend:
     def percentile(self, v, q: float) -> Val:
         """np.percentile over one value or over a list of values taken together (e.g. an HxWx3 array)."""
         vals = list(v) if isinstance(v, (list, tuple)) else [v]
-        ptr, _ = self._contiguous(vals)
+        ptr, _, fs = self._contiguous(vals)
         count = self.n * len(vals)
         slot = self.new_slot()
         ctx, out = self.ctx, self.scalars.ptr + 8 * slot
-        self._call(lambda s: ctx._check(lib.avx_percentile_dev(ctx._h, ptr, count, float(q), out, s)))
+        if self.frames == 1:
+            self._call(lambda s, m=1: ctx._check(lib.avx_percentile_dev(ctx._h, ptr, count, float(q), out, s)))
+        else:
+            self._call(self._percentile_jobs([ptr], [fs], [count], float(q), [slot]))
         return self.scalar(slot)
+
+    def _percentile_jobs(self, ptrs, fss, counts, q: float, slots):
+        """The batched percentile stage: frames x planes independent jobs for avx_percentiles_dev (<= 16 per call, four per set
+        of radix passes), frame-major, so the first m frames are a prefix of the job list."""
+        jobs = [(p + f * fs, c, self.scalars.ptr + 8 * (f * self.N_SCALARS + sl)) for f in range(self.frames) for p, fs, c, sl in zip(ptrs, fss, counts, slots)]
+        per, ctx, cache = len(ptrs), self.ctx, {}
+
+        def chunks(m):
+            hit = cache.get(m)
+            if hit is None:
+                hit = []
+                live = jobs[:m * per]
+                for i in range(0, len(live), 16):
+                    part = live[i:i + 16]
+                    k = len(part)
+                    hit.append((k, (ctypes.c_void_p * k)(*[j[0] for j in part]), (ctypes.c_size_t * k)(*[j[1] for j in part]),
+                                (ctypes.c_double * k)(*([q] * k)), (ctypes.c_void_p * k)(*[j[2] for j in part])))
+                cache[m] = hit
+            return hit
+
+        def run(s, m=1):
+            for k, a_ptr, a_n, a_q, a_out in chunks(m):
+                ctx._check(lib.avx_percentiles_dev(ctx._h, k, a_ptr, a_n, a_q, a_out, s))
+        return run
 
     def percentiles(self, vals: Sequence, q: float) -> List[Val]:
         """np.percentile(v, q) for several independent planes: resolved together (one set of radix passes per four)."""
-        ptrs = [self._contiguous([v])[0] for v in vals]
+        cont = [self._contiguous([v]) for v in vals]
+        ptrs = [c[0] for c in cont]
         slots = [self.new_slot() for _ in vals]
         k = len(vals)
+        if self.frames > 1:
+            self._call(self._percentile_jobs(ptrs, [c[2] for c in cont], [self.n] * k, float(q), slots))
+            return [self.scalar(s_) for s_ in slots]
         a_ptr = (ctypes.c_void_p * k)(*ptrs)
         a_n = (ctypes.c_size_t * k)(*([self.n] * k))
         a_q = (ctypes.c_double * k)(*([float(q)] * k))
         a_out = (ctypes.c_void_p * k)(*[self.scalars.ptr + 8 * s_ for s_ in slots])
         self._keep += [a_ptr, a_n, a_q, a_out]
         ctx = self.ctx
-        self._call(lambda s: ctx._check(lib.avx_percentiles_dev(ctx._h, k, a_ptr, a_n, a_q, a_out, s)))
+        self._call(lambda s, m=1: ctx._check(lib.avx_percentiles_dev(ctx._h, k, a_ptr, a_n, a_q, a_out, s)))
         return [self.scalar(s_) for s_ in slots]
 
-    def _contiguous(self, vals: Sequence) -> Tuple[int, List[Val]]:
-        """Device pointer of K consecutive float32 planes holding `vals` (materialising if they are not already so)."""
+    def _contiguous(self, vals: Sequence) -> Tuple[int, List[Val], int]:
+        """Device pointer of K consecutive float32 planes holding `vals` (materialising if they are not already so), and the
+        byte distance from one frame's K planes to the next frame's (the planes may sit inside a larger buffer)."""
         vals = [self._v(v) for v in vals]
         refs = [v.imm for v in vals if v.op == "load"]
         if len(refs) == len(vals) and all(r.kind == "f32" and r.stride == 1 and r.buf is refs[0].buf and r.offset == refs[0].offset + 4 * self.n * i
                                            for i, r in enumerate(refs)):
-            return refs[0].ptr, vals
+            return refs[0].ptr, vals, self.frame_stride(refs[0])
         ms, _ = self.mat_many(vals)
-        return ms[0].imm.ptr, ms
+        return ms[0].imm.ptr, ms, self.frame_stride(ms[0].imm)
 
     def blur_taps(self, vals: Sequence, ksize: int, taps: np.ndarray) -> List[Val]:
         """cv2.GaussianBlur with an explicit kernel on K planes (shared Gaussian contract, BORDER_REFLECT_101)."""
         if ksize > _lib.AVX_MAX_KSIZE:
             raise ValueError(f"blur ksize {ksize} > {_lib.AVX_MAX_KSIZE}")
-        src, _ = self._contiguous(vals)
+        src, _, sfs = self._contiguous(vals)
         K = len(vals)
         out = self.new_planes(K)
         self._keep.append(taps)
         ctx, H, W, dst = self.ctx, self.H, self.W, out[0].ptr
         tp = taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        self._call(lambda s: ctx._check(lib.avx_planes_gaussian_blur(ctx._h, src, dst, K, H, W, int(ksize), tp, 0, s)))
+        if self.frames == 1:
+            self._call(lambda s, m=1: ctx._check(lib.avx_planes_gaussian_blur(ctx._h, src, dst, K, H, W, int(ksize), tp, 0, s)))
+        else:
+            dfs = self.frame_stride(out[0])
+            self._call(lambda s, m=1: ctx._check(lib.avx_planes_gaussian_blur_batch(ctx._h, src, sfs // 4, dst, dfs // 4, m, K, H, W, int(ksize), tp, 0, s)))
         return [self.load(r) for r in out]
 
     def streak(self, vals: Sequence, params) -> List[Val]:
@@ -509,13 +583,15 @@ class DeviceBackend:
         from .dichromat import STREAK_STRIDE, streak_row_tables
 
         assert len(vals) == 3
-        src, _ = self._contiguous(vals)
+        if self.frames > 1:
+            raise NotImplementedError("streak: the float dichromat route has no batched form (frames > 1)")
+        src, _, _ = self._contiguous(vals)
         out = self.new_planes(3)
         rows = np.ascontiguousarray(streak_row_tables(self.H, *params), dtype=np.float32)
         self._keep.append(rows)
         ctx, H, W, dst = self.ctx, self.H, self.W, out[0].ptr
         rp = rows.ctypes.data_as(ctypes.c_void_p)
-        self._call(lambda s: ctx._check(lib.avx_streak_planes_f32(ctx._h, src, dst, H, W, rp, STREAK_STRIDE, s)))
+        self._call(lambda s, m=1: ctx._check(lib.avx_streak_planes_f32(ctx._h, src, dst, H, W, rp, STREAK_STRIDE, s)))
         return [self.load(r) for r in out]
 
     def blur(self, vals: Sequence, sigma: float) -> List[Val]:
@@ -527,21 +603,22 @@ class DeviceBackend:
 
     def sobel(self, v) -> Tuple[Val, Val]:
         """cv2.Sobel(ksize=3, REFLECT101) -> (gx, gy)."""
-        src, _ = self._contiguous([v])
+        src, _, sfs = self._contiguous([v])
         gx, gy = self.new_planes(2)
-        ctx, H, W = self.ctx, self.H, self.W
-        self._call(lambda s: ctx._check(lib.avx_sobel3_plane(ctx._h, src, H, W, gx.ptr, gy.ptr, s)))
+        ctx, H, W, gfs = self.ctx, self.H, self.W, self.frame_stride(gx)
+        self._call(self._frames_loop(lambda s, f: ctx._check(lib.avx_sobel3_plane(ctx._h, src + f * sfs, H, W, gx.ptr + f * gfs, gy.ptr + f * gfs, s))))
         return self.load(gx), self.load(gy)
 
     def remap(self, vals: Sequence, map_x, map_y, border_value: float = 0.0) -> List[Val]:
         """cv2.remap(stack(vals), map_x, map_y, INTER_LINEAR, BORDER_CONSTANT) with per-pixel float32 maps."""
         K = len(vals)
-        src, _ = self._contiguous(vals)
-        mx, _ = self._contiguous([map_x])
-        my, _ = self._contiguous([map_y])
+        src, _, sfs = self._contiguous(vals)
+        mx, _, xfs = self._contiguous([map_x])
+        my, _, yfs = self._contiguous([map_y])
         out = self.new_planes(K)
-        ctx, H, W, dst = self.ctx, self.H, self.W, out[0].ptr
-        self._call(lambda s: ctx._check(lib.avx_remap_linear_planes(ctx._h, src, K, H, W, mx, my, dst, float(border_value), s)))
+        ctx, H, W, dst, dfs = self.ctx, self.H, self.W, out[0].ptr, self.frame_stride(out[0])
+        self._call(self._frames_loop(lambda s, f: ctx._check(lib.avx_remap_linear_planes(ctx._h, src + f * sfs, K, H, W, mx + f * xfs, my + f * yfs, dst + f * dfs,
+                                                                                           float(border_value), s))))
         return [self.load(r) for r in out]
 
     def down_up(self, vals: Sequence, h: int, w: int, interp_down: int, interp_up: int) -> List[Val]:
@@ -554,8 +631,9 @@ class DeviceBackend:
         small = self._alloc(4 * h * w * K)
         out = self._alloc(4 * self.n * K)
         ctx, H, W = self.ctx, self.H, self.W
-        self._call(lambda s: ctx._check(lib.avx_resize_hwc(ctx._h, hwc.ptr, 0, H, W, K, small.ptr, int(h), int(w), int(interp_down), s)))
-        self._call(lambda s: ctx._check(lib.avx_resize_hwc(ctx._h, small.ptr, 0, int(h), int(w), K, out.ptr, H, W, int(interp_up), s)))
+        hfs, sfs, ofs = self._fs[id(hwc)], self._fs[id(small)], self._fs[id(out)]
+        self._call(self._frames_loop(lambda s, f: ctx._check(lib.avx_resize_hwc(ctx._h, hwc.ptr + f * hfs, 0, H, W, K, small.ptr + f * sfs, int(h), int(w), int(interp_down), s))))
+        self._call(self._frames_loop(lambda s, f: ctx._check(lib.avx_resize_hwc(ctx._h, small.ptr + f * sfs, 0, int(h), int(w), K, out.ptr + f * ofs, H, W, int(interp_up), s))))
         return [self.load(PlaneRef(out, 4 * c, K)) for c in range(K)]
 
     # -- species skeleton ------------------------------------------------------------------------------
@@ -576,7 +654,11 @@ class DeviceBackend:
         self.lin_hwc = lin
         ctx, d_in, d_base = self.ctx, self.d_in, self.d_base
         if not self.float_frames:
-            self._call(lambda s: ctx._check(lib.avx_uv_front_u8(ctx._h, d_in.ptr, H, W, new_w, lin.ptr, d_base.ptr, s)))
+            if self.frames == 1:
+                self._call(lambda s, m=1: ctx._check(lib.avx_uv_front_u8(ctx._h, d_in.ptr, H, W, new_w, lin.ptr, d_base.ptr, s)))
+            else:
+                ifs, lfs, bfs = self._fs[id(d_in)], self._fs[id(lin)] // 4, self._fs[id(d_base)]  # elements: d_in / d_base are uint8, lin float32
+                self._call(lambda s, m=1: ctx._check(lib.avx_uv_front_u8_batch(ctx._h, d_in.ptr, m, ifs, H, W, new_w, lin.ptr, lfs, d_base.ptr, bfs, s)))
             return [self.load(PlaneRef(lin, 4 * c, 3)) for c in range(3)]
         # float frames (uv_helpers.py:15-23,33-37): /255 and clip only when the frame's maximum exceeds 1.001
         y = [self.load(PlaneRef(d_in, 4 * c, 3)) for c in range(3)]
@@ -587,7 +669,7 @@ class DeviceBackend:
             v = self.where(mx > 1.001, self.clip01(y[c] / 255.0), y[c])
             self.store(self.where(v <= 0.04045, v / 12.92, ((v + a) / (1 + a)) ** 2.4), PlaneRef(pre, 4 * c, 3))
         if new_w > W:
-            self._call(lambda s: ctx._check(lib.avx_panorama_warp_f32(ctx._h, pre.ptr, H, W, new_w, lin.ptr, s)), "panorama")
+            self._call(lambda s, m=1: ctx._check(lib.avx_panorama_warp_f32(ctx._h, pre.ptr, H, W, new_w, lin.ptr, s)), "panorama")
         rgb = [self.load(PlaneRef(lin, 4 * c, 3)) for c in range(3)]
         for c in range(3):  # baseline = linear_to_srgb(clip(baseline_lin, 0, 1)).astype(dtype)
             self.store(self._linear_to_srgb(self.clip01(rgb[c])), PlaneRef(d_base, 4 * c, 3))
@@ -616,7 +698,11 @@ class DeviceBackend:
         self._keep += [wts, gains, M, d]
         stack = self._alloc(4 * self.n * K)
         ctx, lin = self.ctx, self.lin_hwc
-        self._call(lambda s: ctx._check(lib.avx_band_stack(ctx._h, lin.ptr, H, W, ctypes.byref(d), stack.ptr, s)), "band_stack")
+        if self.frames == 1:
+            self._call(lambda s, m=1: ctx._check(lib.avx_band_stack(ctx._h, lin.ptr, H, W, ctypes.byref(d), stack.ptr, s)), "band_stack")
+        else:
+            lfs, kfs = self._fs[id(lin)] // 4, self._fs[id(stack)] // 4
+            self._call(lambda s, m=1: ctx._check(lib.avx_band_stack_batch(ctx._h, lin.ptr, m, lfs, H, W, ctypes.byref(d), stack.ptr, kfs, s)), "band_stack")
         self.last_stack = stack
         return [self.load(PlaneRef(stack, 4 * k, K)) for k in range(K)]
 
@@ -634,6 +720,9 @@ class DeviceBackend:
         ctx = self.ctx
         dt = np.float32 if self.float_frames else np.uint8
         assert image.shape == (self.H, self.W, 3) and (image.dtype == np.uint8) == (not self.float_frames)
+        if self.frames > 1:
+            base, out = self.run_batch(image[None], stream)
+            return base[0], out[0]
         ctx.upload(np.ascontiguousarray(image, dtype=dt), self.d_in, stream)  # float64 frames: x.astype(float32), the reference's first step
         s = ctx._s(stream)
         for fn in self.plan:
@@ -644,11 +733,25 @@ class DeviceBackend:
             base, out = base.astype(image.dtype), out.astype(image.dtype)
         return base, out
 
-    def run_device(self, stream=None):
-        """Replay on frames already in d_in (device-resident loop: bench, pipeline)."""
+    def run_batch(self, images: np.ndarray, stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        """m <= frames uint8 frames (m x H x W x 3) through the plan in one launch chain -> (baselines, outs), m x H x W x 3."""
+        ctx, m = self.ctx, images.shape[0]
+        assert images.shape[1:] == (self.H, self.W, 3) and images.dtype == np.uint8 and not self.float_frames and 1 <= m <= self.frames
+        ctx.upload(np.ascontiguousarray(images), self.d_in, stream)
+        self.run_device(stream, m)
+        base = ctx.download(self.d_base, images.shape, np.uint8, stream=stream, sync=False)
+        out = ctx.download(self.d_out, images.shape, np.uint8, stream=stream)
+        return base, out
+
+    def run_device(self, stream=None, n_frames: Optional[int] = None):
+        """Replay on frames already in d_in (device-resident loop: bench, pipeline); n_frames: the live frames of a batched plan
+        (default: all it holds)."""
+        m = self.frames if n_frames is None else int(n_frames)
+        if not 1 <= m <= self.frames:
+            raise ValueError(f"n_frames={n_frames}: this plan holds {self.frames} frame(s)")
         s = self.ctx._s(stream)
         for fn in self.plan:
-            fn(s)
+            fn(s, m)
 
 
 class DeviceProbes:

@@ -268,6 +268,8 @@ class HoneybeeOp:
         op.desc = d
         return op
 
+    max_batch = 16  # frames one run_device call takes from a pipeline slot (pipeline.FramePipeline(batch=))
+
     def run_device(self, d_in: Optional[DeviceBuffer], d_out: DeviceBuffer, n_frames: int, H: int, W: int, *, hsi_ptr: int = 0,
                    hsi_layout: int = 1, hsi_dtype: int = 0, debug: Optional[DeviceBuffer] = None, stream=None, catches=None):
         """uint8 frames (or an HSI cube at hsi_ptr, e.g. the MST++ output tensor; or catches = (planes_ptr, partials_ptr, n_partials): the three

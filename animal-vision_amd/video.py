@@ -10,7 +10,11 @@ INPUT and OUTPUT are a .y4m file, "-" (stdin / stdout, Y4M), or the other forms 
     (against each species' own baseline, as visualize() returns it: the plane-program species' is their panorama-warped
     input), and, from a .y4m to a .y4m, I420 across the host and PCIe (FramePipeline io_format="i420");
   * every other species (Cat, whose baseline is the zoomed frame; MantisShrimp; RatUV, whose plan depends on the frame) runs
-    visualize() per frame, and the split frame is composed from visualize's own (baseline, out) pair, as the reference does."""
+    visualize() per frame, and the split frame is composed from visualize's own (baseline, out) pair, as the reference does.
+
+`--batch N` (1..16) puts N frames into every pipeline slot: the plane-program species then run their launch chain once per N
+frames (planevm.DeviceBackend(frames=N): the frame is a grid dimension of the kernels), the dichromats and HoneyBee hand their
+kernels n_frames = N.  The species of the per-frame loop have no batched form: for them `--batch` above 1 is an error."""
 from __future__ import annotations
 
 import argparse
@@ -41,16 +45,32 @@ def route(animal) -> str:
     return "frame"
 
 
-def stream_op(animal, H: int, W: int, depth: int):
-    """The op run_video streams for `animal`, or None when the species goes through the per-frame loop."""
+def stream_op(animal, H: int, W: int, depth: int, batch: int = 1):
+    """The op run_video streams for `animal`, or None when the species goes through the per-frame loop.  batch: frames per
+    pipeline slot -- the plane-program species record their plans for that many frames; the dichromat and honeybee ops take
+    n_frames per call as they are; a species of the per-frame loop cannot batch (ValueError)."""
     kind = route(animal)
     if kind in ("dichromat", "honeybee"):
         return animal._operator()
     if kind == "plane":
         from .animals._uv_species import SpeciesStreamOp
 
-        return SpeciesStreamOp(animal, H, W, depth=depth)
+        return SpeciesStreamOp(animal, H, W, depth=depth, batch=batch)
+    if batch > 1:
+        raise ValueError(f"{type(animal).__name__} runs visualize() per frame: it has no batched form (--batch {batch})")
     return None
+
+
+def _batch_arg(text: str) -> int:
+    from ._lib import AVX_EW_MAX_FRAMES
+
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--batch takes an integer (got {text!r})")
+    if not 1 <= v <= AVX_EW_MAX_FRAMES:
+        raise argparse.ArgumentTypeError(f"--batch must be 1..{AVX_EW_MAX_FRAMES} (got {v})")
+    return v
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -62,6 +82,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--split-compare", action="store_true", help="left half original, right half transformed (the reference's output)")
     ap.add_argument("--no-labels", action="store_true", help="no corner labels on the split frame")
     ap.add_argument("--depth", type=int, default=3, help="frames in flight on the device (streamed species)")
+    ap.add_argument("--batch", type=_batch_arg, default=1, metavar="N", help="frames per slot and per launch chain, 1..16 (streamed species only)")
     ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"])
     ap.add_argument("--range", default=None, choices=["limited", "full"], help="YUV range (default: the input's XCOLORRANGE, else limited)")
     return ap
@@ -78,6 +99,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     vr = VideoRenderer(read_path=args.input, write_path=args.output, window_name="AnimalCam", matrix=args.matrix, range=args.range)
     vr.open()
     animal = species_class(args.species)()
+    if args.batch > 1 and route(animal) == "frame":  # before any frame is read
+        vr.close()
+        raise SystemExit(f"video: --batch {args.batch}: {args.species} runs visualize() per frame and has no batched form")
     labels = None if args.no_labels else ("Original", "Transformed")
     t0 = time.perf_counter()
     try:
@@ -88,13 +112,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             vr.close()
             vr = VideoRenderer(read_path=args.input, write_path=args.output, window_name="AnimalCam", matrix=args.matrix, range=args.range)
             vr.open()
-        op = None if hw is None else stream_op(animal, hw[0], hw[1], args.depth)
+        op = None if hw is None else stream_op(animal, hw[0], hw[1], args.depth, args.batch)
         if op is not None:
             try:
                 # the split frame's left half is visualize()'s baseline: the input for the dichromats and HoneyBee, the
                 # panorama-warped input for the plane-program species (their plans' baseline frames)
                 stats = run_video(op, vr, depth=args.depth, split_compare=args.split_compare, labels=labels,
-                                  split_baseline=isinstance(op, SpeciesStreamOp))
+                                  split_baseline=isinstance(op, SpeciesStreamOp), batch=args.batch)
             finally:
                 if isinstance(op, SpeciesStreamOp):
                     op.close()

@@ -160,6 +160,11 @@ int avx_plane_stats(avx_ctx* ctx, const float* planes, int K, size_t n, int adap
  * 3 safe_norm.  ksize == 1: rescale only.  taps_host: ksize normalised taps in double. */
 int avx_planes_gaussian_blur(avx_ctx* ctx, const float* in, float* out, int K, int H, int W, int ksize,
                              const double* taps_host, int scale_mode, void* stream);
+/* The same for n_frames (<= AVX_EW_MAX_FRAMES) frames of K planes in one launch: frame f at in + f * in_frame_stride /
+ * out + f * out_frame_stride (in floats, >= K*H*W).  scale_mode must be 0 when n_frames > 1 (the statistics are one frame's). */
+int avx_planes_gaussian_blur_batch(avx_ctx* ctx, const float* in, size_t in_frame_stride, float* out, size_t out_frame_stride,
+                                   int n_frames, int K, int H, int W, int ksize, const double* taps_host, int scale_mode,
+                                   void* stream);
 
 /* apply_anisotropic_acuity_blur_with_streak (animals/animal_utils.py:147-172, as coded: quirk Q3) on three float32
  * planes of linear light (3 x H x W in, 3 x H x W out): the float-frame form of the streak species; uint8 frames take
@@ -338,6 +343,14 @@ typedef struct avx_band_stack_desc {
 } avx_band_stack_desc;
 int avx_band_stack(avx_ctx* ctx, const float* lin_hwc, int H, int W, const avx_band_stack_desc* desc,
                    float* stack_hwk_out, void* stream);
+/* Batched forms: n_frames (<= AVX_EW_MAX_FRAMES) independent frames, frame f of every device pointer at pointer + f * its frame
+ * stride (in ELEMENTS of that pointer; >= one frame).  The frame is a grid dimension: one launch where the single-frame call is one
+ * launch (avx_band_stack's reduced-size route loops over the frames inside the call).  The tables are looked up once per call. */
+int avx_uv_front_u8_batch(avx_ctx* ctx, const uint8_t* in_hwc, int n_frames, size_t in_frame_stride, int H, int W, int pano_new_w,
+                          float* lin_hwc_out, size_t lin_frame_stride, uint8_t* baseline_hwc_out, size_t baseline_frame_stride,
+                          void* stream);
+int avx_band_stack_batch(avx_ctx* ctx, const float* lin_hwc, int n_frames, size_t lin_frame_stride, int H, int W,
+                         const avx_band_stack_desc* desc, float* stack_hwk_out, size_t stack_frame_stride, void* stream);
 /* avx_percentile with the result left on the device (one double, the float32 value NumPy would return). */
 int avx_percentile_dev(avx_ctx* ctx, const float* data_dev, size_t n, double q, double* out_dev, void* stream);
 /* `count` (<= 16) independent percentiles; up to four are resolved by the same three radix passes (the arrays of
@@ -384,6 +397,14 @@ typedef struct avx_ew_program {
     double* scalars_dev; int32_t n_scalars;              /* the device-side scalar table                             */
 } avx_ew_program;
 int avx_ew_run(avx_ctx* ctx, const avx_ew_program* program, void* stream);
+/* The same program over n_frames (<= AVX_EW_MAX_FRAMES) independent frames in ONE launch (the frame is a grid dimension).
+ * plane_frame_stride_bytes_host: one entry per plane of the program, the byte distance from frame f to frame f + 1 of that plane; 0 for a
+ * plane every frame shares (AVX_EW_PLANE_COL / _ROW vectors, constant maps; never a plane the program stores to).  Frame f reads
+ * AVX_EW_SCALAR from scalars_dev + f * scalars_frame_stride (in doubles, >= n_scalars when the program has reductions) and leaves its
+ * reductions there.  Each frame's reductions are bit-identical to avx_ew_run on that frame.  n_frames == 1 ignores the strides. */
+enum { AVX_EW_MAX_FRAMES = 16 };
+int avx_ew_run_batch(avx_ctx* ctx, const avx_ew_program* program, int n_frames, const size_t* plane_frame_stride_bytes_host,
+                     size_t scalars_frame_stride, void* stream);
 /* Programs whose structure was recorded when csrc/ew_gen.hip was generated (tools/gen_ew_kernels.py) run as their own straight-line
  * kernels; others are interpreted.  Returns the number of generated kernels; *hits / *misses count avx_ew_run calls of either kind. */
 int avx_ew_spec_stats(unsigned long long* hits, unsigned long long* misses);

@@ -78,6 +78,8 @@ def emit(idx, ins, kinds, acc):
     w(f"__global__ __launch_bounds__(kET) void k_ews_{idx}(const EwArgs a) {{")
     w("    const int tid = threadIdx.x;")
     w("    (void)tid;")
+    w("    const unsigned f = blockIdx.y;  // frame of the batch (0 in a single-frame launch)")
+    w("    (void)f;")
     if uses_enc:
         w("    __shared__ float thr[256];")
         w("    __shared__ uint8_t coarse[kCoarseTableBytes];")
@@ -95,9 +97,9 @@ def emit(idx, ins, kinds, acc):
         if o == CONST or (op & (IMM_A | IMM_B)):
             w(f"    const float i{pc} = __uint_as_float(a.insn[{pc}].imm);")
         elif o == SCALAR:
-            w(f"    const float i{pc} = (float)a.scalars[a.insn[{pc}].imm];")
+            w(f"    const float i{pc} = (float)a.scalars[(size_t)f * a.scalars_fs + a.insn[{pc}].imm];")
     for j in range(len(kinds)):
-        w(f"    const avx_ew_plane p{j} = a.planes[{j}];")
+        w(f"    const avx_ew_plane p{j} = ew_plane_of(a, {j}, f);")
     w("    const uint32_t n = (uint32_t)a.n, W = (uint32_t)a.W;")
     w("    (void)W;")
     w("    for (uint32_t base = blockIdx.x * (kET * PX); base < n; base += gridDim.x * (kET * PX)) {")
@@ -154,13 +156,13 @@ def emit(idx, ins, kinds, acc):
         reg[d] = v
     w("    }")
     if acc:
-        w(f"    ew_reduce_tail<{len(acc)}, PX>(a, acc);")
+        w(f"    ew_reduce_tail<{len(acc)}, PX>(a, acc, f);")
     w("}")
     return "\n".join(L)
 
 
 def main():
-    lines = sorted({l.strip() for l in open(SRC) if l.strip()})
+    lines = sorted({l.strip() for l in open(SRC) if l.strip() and not l.startswith("#")})  # "#": a comment line
     progs = []
     for l in lines:
         ins, kinds, acc = parse(l)

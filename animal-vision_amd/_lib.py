@@ -14,6 +14,9 @@ AVX_ERR_INVALID, AVX_ERR_NO_DEVICE, AVX_ERR_HIP, AVX_ERR_UNSUPPORTED, AVX_ERR_NO
 AVX_COLOR_MATRIX, AVX_COLOR_CAT_MERGE = 0, 1
 AVX_POST_NONE, AVX_POST_GAUSS, AVX_POST_ROWGAIN, AVX_POST_STREAK = 0, 1, 2, 3
 AVX_MAX_KSIZE = 33
+# enum avx_pix_fmt (include/avx.h), by ffmpeg's -pix_fmt names
+AVX_PIX_FMTS = {"yuv420p": 0, "nv12": 1, "yuv422p": 2, "yuv444p": 3, "gray": 4, "yuv420p10le": 5, "yuv422p10le": 6, "yuv444p10le": 7,
+                "p010le": 8}
 
 
 class AvxError(RuntimeError):
@@ -285,6 +288,10 @@ _SIGS = {
     "avx_i420_to_rgb_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "avx_rgb_to_i420_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "avx_yuv_coefficients": (_i, [_i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "avx_yuv_coefficients_d": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "avx_yuv_frame_size": (_sz, [_i, _i, _i]),
+    "avx_yuv_to_rgb_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "avx_rgb_to_yuv_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

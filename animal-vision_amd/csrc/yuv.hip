@@ -187,16 +187,18 @@ void kr_kb(int matrix, double& kr, double& kb) {
     else { kr = 0.299; kb = 0.114; }
 }
 
-void scales(int full_range, double& ys, double& cs, int& yo) {
-    if (full_range) { ys = 1.0; cs = 1.0; yo = 0; }
-    else { ys = 219.0 / 255.0; cs = 224.0 / 255.0; yo = 16; }
+// depth d of the samples (8 or 10): s = 2^(d-8); at d = 8 these are the §4.8 values to the bit
+void scales(int full_range, int depth, double& ys, double& cs, int& yo) {
+    const double s = (double)(1 << (depth - 8)), top = (double)((1 << depth) - 1);
+    if (full_range) { ys = top / 255.0; cs = top / 255.0; yo = 0; }
+    else { ys = 219.0 * s / 255.0; cs = 224.0 * s / 255.0; yo = 16 << (depth - 8); }
 }
 
-DecCoef dec_coef(int matrix, int full_range) {
+DecCoef dec_coef(int matrix, int full_range, int depth = 8) {
     double kr, kb, ys, cs;
     int yo;
     kr_kb(matrix, kr, kb);
-    scales(full_range, ys, cs, yo);
+    scales(full_range, depth, ys, cs, yo);
     const double kg = 1.0 - kr - kb;
     DecCoef c;
     c.cy = q16(1.0 / ys);
@@ -208,11 +210,11 @@ DecCoef dec_coef(int matrix, int full_range) {
     return c;
 }
 
-EncCoef enc_coef(int matrix, int full_range) {
+EncCoef enc_coef(int matrix, int full_range, int depth = 8) {
     double kr, kb, ys, cs;
     int yo;
     kr_kb(matrix, kr, kb);
-    scales(full_range, ys, cs, yo);
+    scales(full_range, depth, ys, cs, yo);
     EncCoef c;
     // in each row the G coefficient is derived, so Y sums to round(ys 2^16) and U, V sum to 0 (greys encode to 128 exactly)
     c.yr = q16(ys * kr); c.yb = q16(ys * kb); c.yg = q16(ys) - c.yr - c.yb;
@@ -282,13 +284,19 @@ extern "C" int avx_rgb_to_i420_u8(avx_ctx* ctx, const uint8_t* rgb_hwc, uint8_t*
     return AVX_OK;
 }
 
-extern "C" int avx_yuv_coefficients(int matrix, int full_range, int dec_out[6], int enc_out[10]) {
-    if ((matrix != AVX_YUV_BT601 && matrix != AVX_YUV_BT709) || (full_range != 0 && full_range != 1) || !dec_out || !enc_out) return AVX_ERR_INVALID;
-    const DecCoef d = dec_coef(matrix, full_range);
-    const EncCoef e = enc_coef(matrix, full_range);
+extern "C" int avx_yuv_coefficients_d(int matrix, int full_range, int depth, int dec_out[6], int enc_out[10]) {
+    if ((matrix != AVX_YUV_BT601 && matrix != AVX_YUV_BT709) || (full_range != 0 && full_range != 1) || (depth != 8 && depth != 10) || !dec_out ||
+        !enc_out)
+        return AVX_ERR_INVALID;
+    const DecCoef d = dec_coef(matrix, full_range, depth);
+    const EncCoef e = enc_coef(matrix, full_range, depth);
     const int dv[6] = {d.cy, d.crv, d.cgu, d.cgv, d.cbu, d.yo};
     const int ev[10] = {e.yr, e.yg, e.yb, e.ur, e.ug, e.ub, e.vr, e.vg, e.vb, e.yo};
     memcpy(dec_out, dv, sizeof dv);
     memcpy(enc_out, ev, sizeof ev);
     return AVX_OK;
+}
+
+extern "C" int avx_yuv_coefficients(int matrix, int full_range, int dec_out[6], int enc_out[10]) {
+    return avx_yuv_coefficients_d(matrix, full_range, 8, dec_out, enc_out);
 }

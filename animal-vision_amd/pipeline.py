@@ -102,7 +102,7 @@ class _Slot:
     index: int = -1
     busy: bool = False
     indices: List[int] = field(default_factory=list)  # global indices of the frames the slot carries (<= batch)
-    d_yuv_in: object = None   # io_format="i420": the frame's payload on the device, in and out
+    d_yuv_in: object = None   # io_format="i420" / "yuv": the frame's payload on the device, in and out
     d_yuv_out: object = None
     d_left: object = None     # the left half of the split frame: d_in, or the op's baseline (split_baseline)
 
@@ -113,13 +113,16 @@ class FramePipeline:
 
     def __init__(self, op, H: int, W: int, *, ctx=None, depth: int = 3, split_compare: bool = False, draw_seam: bool = True,
                  labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed"), io_format: str = "rgb",
-                 matrix: str = "bt601", yuv_range: str = "limited", split_baseline: bool = False, batch: int = 1):
+                 matrix: str = "bt601", yuv_range: str = "limited", split_baseline: bool = False, batch: int = 1,
+                 pix_fmt: Optional[str] = None):
         """split_compare: emit make_split_frame(original, transformed) composed on the device (renderers/video.py:198-245:
         halves, seam, and the two corner labels -- `labels` = (left, right), None = none) instead of the transformed frame.
 
         io_format: "rgb" -- frames in and out are HxWx3 uint8; "i420" -- they are flat I420 payloads (the Y4M layout, 1.5 B/px:
         half the bytes of the host and PCIe copies), converted on the slot stream into the op's d_in and back out of its
-        d_out (yuv.py, with `matrix` and `yuv_range`); the op, the split composition and the labels run on RGB as before.
+        d_out (yuv.py, with `matrix` and `yuv_range`); the op, the split composition and the labels run on RGB as before;
+        "yuv" -- as "i420", with flat payloads in the raw pixel format `pix_fmt` (one of yuv.PIX_FMTS: nv12, p010le, ...; DESIGN
+        §4.9) and the conversions of csrc/yuv_raw.hip.  Format names go in `pix_fmt`, not in io_format.
 
         split_baseline: the split frame's left half is the op's own baseline -- `op.slot_baseline(k)`, the frame a species'
         visualize() returns first (a UV species' panorama-warped input, SpeciesStreamOp) -- instead of the input frame.
@@ -129,12 +132,16 @@ class FramePipeline:
         copy.  Frames are still emitted one by one in submission order; the last slot of a stream may carry fewer frames.  The
         op states how many frames one call takes in `max_batch` (absent: 1); an op that cannot take `batch` is refused here."""
         from .runtime import get_context
-        from .yuv import _codes, i420_size
+        from .yuv import PIX_FMTS, _codes, frame_size, i420_size
 
-        if io_format not in ("rgb", "i420"):
-            raise ValueError(f"io_format must be 'rgb' or 'i420' (got {io_format!r})")
+        if io_format not in ("rgb", "i420", "yuv"):
+            raise ValueError(f"io_format must be 'rgb', 'i420' or 'yuv' (got {io_format!r})")
+        if io_format == "yuv" and pix_fmt not in PIX_FMTS:
+            raise ValueError(f"io_format='yuv' needs pix_fmt, one of {', '.join(PIX_FMTS)} (got {pix_fmt!r})")
+        if io_format != "yuv" and pix_fmt is not None:
+            raise ValueError(f"pix_fmt goes with io_format='yuv' (got io_format={io_format!r})")
         _codes(matrix, yuv_range)
-        self.io_format, self.matrix, self.yuv_range = io_format, matrix, yuv_range
+        self.io_format, self.matrix, self.yuv_range, self.pix_fmt = io_format, matrix, yuv_range, pix_fmt
         self.op, self.H, self.W, self.depth = op, H, W, depth
         self.batch = int(batch)
         if self.batch < 1:
@@ -155,7 +162,7 @@ class FramePipeline:
         lend = getattr(op, "slot_buffers", None)
         self._lent = lend is not None
         self.slots = []
-        self._io_shape = (H, W, 3) if io_format == "rgb" else (i420_size(H, W),)
+        self._io_shape = (H, W, 3) if io_format == "rgb" else ((i420_size(H, W),) if io_format == "i420" else (frame_size(pix_fmt, H, W),))
         stage = (self.batch,) + self._io_shape
         for k in range(depth):
             d_in, d_out = lend(k) if lend else (self.ctx.malloc(nbytes), self.ctx.malloc(nbytes))
@@ -163,8 +170,8 @@ class FramePipeline:
                 raise ValueError(f"batch={self.batch}: {type(op).__name__}'s slot buffers hold fewer than {self.batch} frames")
             s = _Slot(self.ctx.stream_create(), self.ctx.pinned(stage, np.uint8), self.ctx.pinned(stage, np.uint8), d_in, d_out)
             s.d_left = baseline(k) if baseline is not None else d_in
-            if io_format == "i420":
-                s.d_yuv_in, s.d_yuv_out = self.ctx.malloc(self.batch * i420_size(H, W)), self.ctx.malloc(self.batch * i420_size(H, W))
+            if io_format != "rgb":
+                s.d_yuv_in, s.d_yuv_out = self.ctx.malloc(self.batch * self._io_shape[0]), self.ctx.malloc(self.batch * self._io_shape[0])
             self.slots.append(s)
 
     def close(self):
@@ -194,16 +201,29 @@ class FramePipeline:
             s.busy, s.indices = False, []
 
     def run(self, frames: Iterator[Tuple[int, np.ndarray]], emit: Callable[[int, np.ndarray], None]) -> StreamStats:
-        """frames: (global index, HxWx3 uint8 -- or, io_format="i420", a flat I420 payload) pairs owned by this rank;
+        """frames: (global index, HxWx3 uint8 -- or, io_format="i420" / "yuv", a flat payload) pairs owned by this rank;
         emit(index, out) in submission order, `out` in the same format."""
         from ._lib import lib
-        from .yuv import i420_to_rgb_device, rgb_to_i420_device
+        from .yuv import i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_to_rgb_device
 
         ctx, n, t0 = self.ctx, 0, time.perf_counter()
         self._copy_s = 0.0
         for s in self.slots:  # a run that ended in an error may have left a half-filled slot behind
             s.busy, s.indices = False, []
-        i420 = self.io_format == "i420"
+        i420 = self.io_format != "rgb"  # payloads cross the host and PCIe; RGB exists on the device only
+        kw = dict(matrix=self.matrix, range=self.yuv_range)
+        if self.io_format == "yuv":
+            def to_rgb(s, m):
+                yuv_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
+
+            def from_rgb(s, m):
+                rgb_to_yuv_device(ctx, self.pix_fmt, s.d_out, s.d_yuv_out, m, self.H, self.W, stream=s.stream, **kw)
+        else:
+            def to_rgb(s, m):
+                i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
+
+            def from_rgb(s, m):
+                rgb_to_i420_device(ctx, s.d_out, s.d_yuv_out, m, self.H, self.W, stream=s.stream, **kw)
         fbytes = int(np.prod(self._io_shape))
         rgb_bytes = self.H * self.W * 3
 
@@ -212,7 +232,7 @@ class FramePipeline:
             m = len(s.indices)
             if i420:
                 ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_yuv_in.ptr, s.h_in.ptr, m * fbytes, s.stream))
-                i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, m, self.H, self.W, matrix=self.matrix, range=self.yuv_range, stream=s.stream)
+                to_rgb(s, m)
             else:
                 ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_in.ptr, s.h_in.ptr, m * fbytes, s.stream))
             self.op.run_device(s.d_in, s.d_out, m, self.H, self.W, stream=s.stream)
@@ -225,7 +245,7 @@ class FramePipeline:
 
                         draw_split_labels_device(ctx, s.d_out.ptr + o, self.H, self.W, self.labels[0], self.labels[1], s.stream)
             if i420:
-                rgb_to_i420_device(ctx, s.d_out, s.d_yuv_out, m, self.H, self.W, matrix=self.matrix, range=self.yuv_range, stream=s.stream)
+                from_rgb(s, m)
                 ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_yuv_out.ptr, m * fbytes, s.stream))
             else:
                 ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_out.ptr, m * fbytes, s.stream))
@@ -267,7 +287,8 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
 
     A renderer whose frames can stay I420 end to end (`yuv_hw` not None: renderers.VideoRenderer from a .y4m to a .y4m) hands
     over get_yuv() payloads, and the pipeline runs with io_format="i420" in the renderer's `matrix` and `yuv_range`.
-    split_baseline, batch (frames per slot and per op call): see FramePipeline."""
+    When that renderer names a raw pixel format (`yuv_pix_fmt`: raw video in and out in one format), the pipeline runs with
+    io_format="yuv" in that format.  split_baseline, batch (frames per slot and per op call): see FramePipeline."""
     self_sharding = getattr(renderer, "world", 1) == world and getattr(renderer, "rank", 0) == rank and hasattr(renderer, "last_index") and world > 1
     yuv_hw = getattr(renderer, "yuv_hw", None) if callable(getattr(renderer, "get_yuv", None)) else None
     get = renderer.get_yuv if yuv_hw is not None else renderer.get_image
@@ -277,8 +298,9 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
         pipe = None
     elif yuv_hw is not None:
         H, W = yuv_hw
-        pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, io_format="i420",
-                             matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline, batch=batch)
+        fmt = getattr(renderer, "yuv_pix_fmt", None)
+        pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, io_format="yuv" if fmt else "i420",
+                             pix_fmt=fmt, matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline, batch=batch)
     else:
         H, W, _ = first.shape
         pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, split_baseline=split_baseline, batch=batch)

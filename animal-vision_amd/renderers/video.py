@@ -14,6 +14,11 @@ get_yuv() hands over the payload itself, and render() takes RGB frames (converte
 `range` name the conversion; range None = the source's XCOLORRANGE tag, else limited.  The sink echoes the
 source's header (size, rate, aspect, colour range, unknown tags) when the source is a .y4m.
 
+Raw video (renderers/rawvideo.py): `pix_fmt` and `size=(W, H)` read `read_path` (a file, "-" or a FIFO) as headerless
+frames in one of yuv.PIX_FMTS (nv12, p010le, yuv422p, ...); `write_pix_fmt` writes `write_path` the same way, and defaults to
+`pix_fmt` when the sink is "-" or ends in .yuv.  get_image() and get_yuv() keep their contracts; a raw source into a .y4m sink
+goes through RGB.
+
 Sharded streams (two keywords the reference does not have, both defaulted): with `world` > 1 this renderer
 serves and stores only the frames of rank `rank` (global frame i belongs to rank i mod world) -- every source here is
 index-addressable, so the other ranks' frames are never generated, read or decoded.  Outputs carry the GLOBAL frame
@@ -61,6 +66,11 @@ def split_compose(original: np.ndarray, modified: np.ndarray, draw_seam: bool = 
     return out
 
 
+def is_raw_sink(path: Optional[str]) -> bool:
+    """A path that is written as raw video when the source's pix_fmt is known and no write_pix_fmt is given: "-" or *.yuv."""
+    return bool(path) and (path == "-" or path.lower().endswith(".yuv"))
+
+
 def is_y4m(path: Optional[str]) -> bool:
     """A path the Y4M reader / writer serves: "-" (stdin / stdout) or a name ending in .y4m."""
     return bool(path) and (path == "-" or path.lower().endswith(".y4m"))
@@ -68,9 +78,26 @@ def is_y4m(path: Optional[str]) -> bool:
 
 class VideoRenderer(Renderer):
     def __init__(self, *, read_path: Optional[str] = None, write_path: Optional[str] = None, fps: Optional[int] = None,
-                 window_name: str = "Video Analysis", rank: int = 0, world: int = 1, matrix: str = "bt601", range: Optional[str] = None):
+                 window_name: str = "Video Analysis", rank: int = 0, world: int = 1, matrix: str = "bt601", range: Optional[str] = None,
+                 pix_fmt: Optional[str] = None, size: Optional[tuple] = None, write_pix_fmt: Optional[str] = None):
         if not (0 <= rank < world):
             raise ValueError(f"rank {rank} outside world {world}")
+        if (pix_fmt is None) != (size is None):
+            raise ValueError("a raw video source is named by both pix_fmt and size=(W, H)")
+        if write_pix_fmt is None and pix_fmt is not None and is_raw_sink(write_path):
+            write_pix_fmt = pix_fmt
+        from ..yuv import PIX_FMTS
+
+        for f in (pix_fmt, write_pix_fmt):
+            if f is not None and f not in PIX_FMTS:
+                raise ValueError(f"pix_fmt must be one of {', '.join(PIX_FMTS)} (got {f!r})")
+        if write_pix_fmt is not None and not write_path:
+            raise ValueError("write_pix_fmt needs a write_path")
+        self.pix_fmt, self.write_pix_fmt = pix_fmt, write_pix_fmt
+        self.size = None if size is None else (int(size[0]), int(size[1]))
+        self._raw = None             # renderers.rawvideo.RawVideoReader
+        self._raw_out = None         # renderers.rawvideo.RawVideoWriter (created by the first render)
+        self._merge_size = self.size  # (W, H) of the raw sink's frames, for merge_shards()
         if write_path == "-" and world > 1:
             raise ValueError("stdout is one ordered stream: it can only be written with world = 1")
         self.read_path, self.write_path = read_path, write_path
@@ -94,7 +121,12 @@ class VideoRenderer(Renderer):
     def open(self) -> None:
         p = self.read_path
         if p:
-            if is_y4m(p):
+            if self.pix_fmt is not None:
+                from .rawvideo import RawVideoReader
+
+                self._raw = RawVideoReader(p, self.pix_fmt, self.size[0], self.size[1], rank=self.rank, world=self.world)
+                self.total_frames = self._raw.total_frames
+            elif is_y4m(p):
                 from .y4m import Y4MReader
 
                 self._y4m = Y4MReader(p, rank=self.rank, world=self.world)
@@ -113,7 +145,7 @@ class VideoRenderer(Renderer):
                 self.total_frames = len(self._files)
             else:
                 raise RuntimeError(f"Failed to open video for reading: {p} (no codec on this box: synthetic:, .npy or an image directory)")
-        if self.write_path and not self.write_path.endswith(".npy") and not is_y4m(self.write_path):
+        if self.write_path and not self.write_path.endswith(".npy") and not is_y4m(self.write_path) and self.write_pix_fmt is None:
             os.makedirs(self.write_path, exist_ok=True)
 
     @property
@@ -132,20 +164,41 @@ class VideoRenderer(Renderer):
     def yuv_hw(self) -> Optional[tuple]:
         """(H, W) when frames can stay I420 end to end -- a .y4m source and a .y4m sink (or none) -- else None.
         pipeline.run_video then streams get_yuv() payloads (FramePipeline io_format="i420")."""
-        if self._y4m is None or (self.write_path and not is_y4m(self.write_path)):
+        if self._raw is not None:
+            if self.write_path and self.write_pix_fmt != self.pix_fmt:
+                return None
+            return self._raw.height, self._raw.width
+        if self._y4m is None or self.write_pix_fmt is not None or (self.write_path and not is_y4m(self.write_path)):
             return None
         return self._y4m.header.height, self._y4m.header.width
 
+    @property
+    def yuv_pix_fmt(self) -> Optional[str]:
+        """The raw pixel format of the payloads get_yuv() hands over when `yuv_hw` is set; None = I420 (.y4m)."""
+        return self.pix_fmt if self._raw is not None else None
+
     def get_yuv(self) -> Optional[np.ndarray]:
-        """The next frame of a .y4m source as its flat uint8 I420 payload, None at end of stream."""
+        """The next frame of a .y4m or raw source as its flat uint8 payload, None at end of stream."""
+        if self._raw is not None:
+            f = self._raw.read()
+            if f is not None:
+                self.last_index = self._raw.last_index
+            return f
         if self._y4m is None:
-            raise RuntimeError("get_yuv() needs a .y4m (or '-') source")
+            raise RuntimeError("get_yuv() needs a .y4m (or '-') or raw video source")
         f = self._y4m.read()
         if f is not None:
             self.last_index = self._y4m.last_index
         return f
 
     def get_image(self) -> Optional[np.ndarray]:
+        if self._raw is not None:
+            f = self.get_yuv()
+            if f is None:
+                return None
+            from ..yuv import yuv_to_rgb
+
+            return yuv_to_rgb(f, self._raw.height, self._raw.width, pix_fmt=self.pix_fmt, matrix=self.matrix, range=self.yuv_range)
         if self._y4m is not None:
             f = self.get_yuv()
             if f is None:
@@ -185,7 +238,9 @@ class VideoRenderer(Renderer):
         if index is None:
             index = self.rank + self.frames_written * self.world
         if self.write_path:
-            if is_y4m(self.write_path):
+            if self.write_pix_fmt is not None:
+                self._render_raw(frame, index)
+            elif is_y4m(self.write_path):
                 self._render_y4m(frame, index)
             elif self.write_path.endswith(".npy"):
                 row = (index - self.rank) // self.world
@@ -223,6 +278,34 @@ class VideoRenderer(Renderer):
             self._open_y4m_sink(H, W)
         self._y4m_out.write(payload)
 
+    def _render_raw(self, frame: np.ndarray, index: int) -> None:
+        """A raw sink takes RGB uint8 HxWx3 frames (encoded on the device) or flat payloads in write_pix_fmt, in stream order."""
+        if index != self.rank + self.frames_written * self.world:
+            raise ValueError(f"frame {index}: a raw video sink is written in stream order; rank {self.rank} of {self.world} expects frame "
+                             f"{self.rank + self.frames_written * self.world}")
+        frame = np.asarray(frame)
+        if frame.ndim == 3 and frame.dtype == np.uint8 and frame.shape[2] == 3:
+            H, W = frame.shape[:2]
+            from ..yuv import rgb_to_yuv
+
+            payload = rgb_to_yuv(frame, pix_fmt=self.write_pix_fmt, matrix=self.matrix, range=self.yuv_range)
+        elif frame.ndim == 1 and frame.dtype == np.uint8:
+            if self._raw_out is None and (self._raw is None or self.pix_fmt != self.write_pix_fmt):
+                raise ValueError(f"a {self.write_pix_fmt} payload names no frame size: render an RGB frame first, or read raw video in that format")
+            H, W = (self._raw_out.height, self._raw_out.width) if self._raw_out is not None else (self._raw.height, self._raw.width)
+            payload = frame
+        else:
+            raise ValueError(f"a raw video sink takes RGB uint8 HxWx3 frames or flat uint8 {self.write_pix_fmt} payloads, got {frame.dtype} {frame.shape}")
+        if self._raw_out is None:
+            self._open_raw_sink(H, W)
+        self._raw_out.write(payload)
+
+    def _open_raw_sink(self, H: int, W: int) -> None:
+        from .rawvideo import RawVideoWriter
+
+        self._raw_out = RawVideoWriter(self._shard_path(self.rank), self.write_pix_fmt, W, H)
+        self._merge_size = (W, H)
+
     def _open_y4m_sink(self, H: int, W: int) -> None:
         """Create the .y4m sink (this rank's shard when world > 1) and write its header."""
         from .y4m import Y4MWriter, default_header
@@ -254,6 +337,8 @@ class VideoRenderer(Renderer):
         trimmed to what was written); rendering may continue afterwards."""
         if self._y4m_out is not None:
             self._y4m_out.flush()
+        if self._raw_out is not None:
+            self._raw_out.flush()
         if self._sink is None:
             return
         self._sink.flush()
@@ -272,7 +357,7 @@ class VideoRenderer(Renderer):
         self.flush()
         self._sink = None
         self._src = self._frames = None
-        if self._y4m_out is None and self._y4m is not None and is_y4m(self.write_path):
+        if self._y4m_out is None and self._y4m is not None and is_y4m(self.write_path) and self.write_pix_fmt is None:
             # no frame was rendered: the sink is still a valid (empty) stream, its header at the source's size
             self._open_y4m_sink(self._y4m.header.height, self._y4m.header.width)
         if self._y4m_out is not None:
@@ -281,10 +366,20 @@ class VideoRenderer(Renderer):
         if self._y4m is not None:
             self._y4m.close()
             self._y4m = None
+        if self._raw_out is None and self._raw is not None and self.write_pix_fmt is not None:
+            self._open_raw_sink(self._raw.height, self._raw.width)  # no frame was rendered: an empty file, not a missing one
+        if self._raw_out is not None:
+            self._raw_out.close()
+            self._raw_out = None
+        if self._raw is not None:
+            self._raw.close()
+            self._raw = None
 
     def merge_shards(self) -> Optional[str]:
         """Rank 0, after every rank has flushed/closed its shard (run_video calls it behind the closing collective): interleave
         <write_path>.rank<r>of<world>.npy (.y4m) into the one ordered stream <write_path>, frame i from shard i mod world."""
+        if self.write_path and self.write_pix_fmt is not None:
+            return self._merge_raw_shards() if self.world > 1 else self.write_path
         if self.write_path and is_y4m(self.write_path) and self.world > 1:
             return self._merge_y4m_shards()
         if not (self.write_path and self.write_path.endswith(".npy")) or self.world == 1:
@@ -307,6 +402,36 @@ class VideoRenderer(Renderer):
         for r in range(self.world):
             if os.path.exists(self._shard_path(r)):
                 os.remove(self._shard_path(r))
+        return self.write_path
+
+    def _merge_raw_shards(self) -> Optional[str]:
+        """Raw shards carry no header: every one holds whole frames of one size, which the first non-empty shard's writer knew.
+        The frame size comes from this renderer's source size, else from `size`."""
+        paths = [self._shard_path(r) for r in range(self.world)]
+        if self._merge_size is None:
+            raise ValueError("merging raw video shards needs the frame size: render a frame first, or pass size=(W, H)")
+        W, H = self._merge_size
+        from .rawvideo import RawVideoReader, RawVideoWriter
+
+        shards = [RawVideoReader(p, self.write_pix_fmt, W, H) if os.path.exists(p) else None for p in paths]
+        have = [s for s in shards if s is not None]
+        if not have:
+            return None
+        n = sum(s.total_frames for s in have)
+        counts = [0 if s is None else s.total_frames for s in shards]
+        if counts != [len(range(r, n, self.world)) for r in range(self.world)]:
+            raise ValueError(f"shards of {counts} frames are not a round-robin partition of one stream")
+        out = RawVideoWriter(self.write_path, self.write_pix_fmt, W, H)
+        try:
+            for i in range(n):  # frame by frame: bounded memory
+                out.write(shards[i % self.world].read())
+        finally:
+            out.close()
+            for s in have:
+                s.close()
+        for p in paths:
+            if os.path.exists(p):
+                os.remove(p)
         return self.write_path
 
     def _merge_y4m_shards(self) -> Optional[str]:

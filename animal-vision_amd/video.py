@@ -3,6 +3,13 @@ non-interactive, and with Y4M in and out, so real footage can come and go throug
 
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m animal_vision_amd.video - out.y4m --species Dog --split-compare
 
+Raw (headerless) video, what `ffmpeg -f rawvideo` and hardware decoders write, is named by `--pix-fmt` and `--size`:
+
+    ffmpeg -i in.mkv -f rawvideo -pix_fmt p010le - | python -m animal_vision_amd.video - out.yuv --species Dog --pix-fmt p010le --size 3840x2160
+
+`--out-pix-fmt` names the output's format; it defaults to the input's when OUTPUT is "-" or ends in .yuv.  Raw in and raw out in one
+format keep the payload (1.5 B/px for nv12, 3 B/px for p010le) across the host and PCIe (FramePipeline io_format="yuv").
+
 INPUT and OUTPUT are a .y4m file, "-" (stdin / stdout, Y4M), or the other forms renderers.VideoRenderer takes (synthetic:,
 .npy, an image directory).  Species are the display names of gallery.py's registry.  Routing:
   * the dichromats but Cat (DichromatOp), HoneyBee (HoneybeeOp) and the plane-program UV species with a fixed plan
@@ -24,6 +31,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from ._lib import AVX_PIX_FMTS
 from .gallery import _CLASS_NAMES, ensure_rgb_uint8, species_class
 
 SPECIES_NAMES = list(_CLASS_NAMES)  # all 36 display names
@@ -73,11 +81,23 @@ def _batch_arg(text: str) -> int:
     return v
 
 
+def _size_arg(text: str):
+    try:
+        w, h = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--size takes WxH, e.g. 3840x2160 (got {text!r})")
+    if w < 1 or h < 1:
+        raise argparse.ArgumentTypeError(f"--size must be positive (got {text!r})")
+    return w, h
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="video", description="Run one species on every frame of a video (Y4M in and out, or the other "
                                                           "VideoRenderer forms).")
-    ap.add_argument("input", help=".y4m file, '-' (stdin, Y4M), synthetic:<W>x<H>:<n>[:kind], .npy or an image directory")
-    ap.add_argument("output", help=".y4m file, '-' (stdout, Y4M), .npy or a directory of PNG frames")
+    ap.add_argument("input", help=".y4m file, '-' (stdin: Y4M, or raw video with --pix-fmt), a raw video file (--pix-fmt), "
+                                  "synthetic:<W>x<H>:<n>[:kind], .npy or an image directory")
+    ap.add_argument("output", help=".y4m file, '-' (stdout: Y4M, or raw video with --pix-fmt / --out-pix-fmt), a raw video file, .npy or a "
+                                   "directory of PNG frames")
     ap.add_argument("--species", required=True, choices=SPECIES_NAMES, metavar="NAME", help="display name, e.g. Dog, HoneyBee, 'Mantis Shrimp'")
     ap.add_argument("--split-compare", action="store_true", help="left half original, right half transformed (the reference's output)")
     ap.add_argument("--no-labels", action="store_true", help="no corner labels on the split frame")
@@ -85,18 +105,35 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch", type=_batch_arg, default=1, metavar="N", help="frames per slot and per launch chain, 1..16 (streamed species only)")
     ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"])
     ap.add_argument("--range", default=None, choices=["limited", "full"], help="YUV range (default: the input's XCOLORRANGE, else limited)")
+    ap.add_argument("--pix-fmt", default=None, choices=list(AVX_PIX_FMTS), metavar="NAME",
+                    help="read INPUT as raw video in this format (ffmpeg's -pix_fmt names: " + ", ".join(AVX_PIX_FMTS) + "); needs --size")
+    ap.add_argument("--size", default=None, type=_size_arg, metavar="WxH", help="frame size of the raw input")
+    ap.add_argument("--out-pix-fmt", default=None, choices=list(AVX_PIX_FMTS), metavar="NAME",
+                    help="write OUTPUT as raw video in this format (default: --pix-fmt when OUTPUT is '-' or ends in .yuv)")
     return ap
 
 
+def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if (args.pix_fmt is None) != (args.size is None):
+        ap.error("--pix-fmt and --size go together: raw video carries neither its format nor its size")
+    return args
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.depth < 1:
         raise SystemExit("video: --depth must be at least 1")
     from .animals._uv_species import SpeciesStreamOp
     from .pipeline import run_video
     from .renderers import VideoRenderer, split_compose
 
-    vr = VideoRenderer(read_path=args.input, write_path=args.output, window_name="AnimalCam", matrix=args.matrix, range=args.range)
+    def renderer():
+        return VideoRenderer(read_path=args.input, write_path=args.output, window_name="AnimalCam", matrix=args.matrix, range=args.range,
+                             pix_fmt=args.pix_fmt, size=args.size, write_pix_fmt=args.out_pix_fmt)
+
+    vr = renderer()
     vr.open()
     animal = species_class(args.species)()
     if args.batch > 1 and route(animal) == "frame":  # before any frame is read
@@ -106,11 +143,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     t0 = time.perf_counter()
     try:
         hw = None if vr.y4m_header is None else (vr.y4m_header.height, vr.y4m_header.width)
+        if args.size is not None:
+            hw = (args.size[1], args.size[0])
         if hw is None:  # synthetic:, .npy or an image directory: peek at the size the stream op is built for, then start over
             first = vr.get_image()
             hw = None if first is None else first.shape[:2]
             vr.close()
-            vr = VideoRenderer(read_path=args.input, write_path=args.output, window_name="AnimalCam", matrix=args.matrix, range=args.range)
+            vr = renderer()
             vr.open()
         op = None if hw is None else stream_op(animal, hw[0], hw[1], args.depth, args.batch)
         if op is not None:

@@ -1,4 +1,5 @@
-"""YUV 4:2:0 (I420, the Y4M payload) <-> RGB uint8 on the device (csrc/yuv.hip), in the style of geometry.py.
+"""YUV <-> RGB uint8 on the device, in the style of geometry.py: the I420 pair of the Y4M path (csrc/yuv.hip) and the raw video
+pixel formats -- nv12, p010le, 4:2:2, 4:4:4, gray, 10-bit planar -- of csrc/yuv_raw.hip (PIX_FMTS).
 
 The arithmetic (int32 fixed point, 16 fractional bits, BT.601 / BT.709, limited / full range) is defined in DESIGN §4.8; the
 coefficient tables are built by the C entry points from the (matrix, range) names below.  A payload is one frame's Y plane
@@ -9,11 +10,12 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import lib
+from ._lib import AVX_PIX_FMTS, lib
 from .runtime import Context, DeviceBuffer, get_context
 
 MATRICES = {"bt601": 0, "bt709": 1}  # AVX_YUV_BT601, AVX_YUV_BT709
 RANGES = {"limited": 0, "full": 1}   # the full_range argument
+PIX_FMTS = tuple(AVX_PIX_FMTS)       # ffmpeg's -pix_fmt names of the raw formats (include/avx.h: enum avx_pix_fmt)
 
 
 def i420_size(H: int, W: int) -> int:
@@ -29,15 +31,16 @@ def _codes(matrix: str, range: str):
     return MATRICES[matrix], RANGES[range]
 
 
-def coefficients(matrix: str = "bt601", range: str = "limited"):
+def coefficients(matrix: str = "bt601", range: str = "limited", depth: int = 8):
     """The fixed-point tables the kernels run with, as the C side builds them: (cy, crv, cgu, cgv, cbu, yo) for the decode and
-    ((Y row), (U row), (V row)), yo for the encode, each row an (r, g, b) triple of 16.16 coefficients."""
+    ((Y row), (U row), (V row)), yo for the encode, each row an (r, g, b) triple of 16.16 coefficients.  depth: bits per
+    sample, 8 or 10."""
     import ctypes
 
     m, r = _codes(matrix, range)
     dec, enc = (ctypes.c_int * 6)(), (ctypes.c_int * 10)()
-    if lib.avx_yuv_coefficients(m, r, dec, enc) != 0:
-        raise ValueError(f"avx_yuv_coefficients({matrix!r}, {range!r}) failed")
+    if lib.avx_yuv_coefficients_d(m, r, int(depth), dec, enc) != 0:
+        raise ValueError(f"avx_yuv_coefficients_d({matrix!r}, {range!r}, depth={depth!r}) failed")
     e = list(enc)
     return tuple(dec), ((tuple(e[0:3]), tuple(e[3:6]), tuple(e[6:9])), e[9])
 
@@ -103,6 +106,91 @@ def rgb_to_i420(rgb: np.ndarray, *, matrix: str = "bt601", range: str = "limited
     try:
         rgb_to_i420_device(ctx, d_in, d_out, n, H, W, matrix=matrix, range=range)
         out = ctx.download(d_out, (n, i420_size(H, W)), np.uint8)
+    finally:
+        d_in.free()
+        d_out.free()
+    return out if batched else out[0]
+
+
+# ---------------------------------------------------------------- raw pixel formats (csrc/yuv_raw.hip) ---------------------------
+def _fmt_code(pix_fmt: str) -> int:
+    if pix_fmt not in AVX_PIX_FMTS:
+        raise ValueError(f"pix_fmt must be one of {', '.join(PIX_FMTS)} (got {pix_fmt!r})")
+    return AVX_PIX_FMTS[pix_fmt]
+
+
+def frame_size(pix_fmt: str, H: int, W: int) -> int:
+    """Bytes of one H x W frame in `pix_fmt`."""
+    n = int(lib.avx_yuv_frame_size(_fmt_code(pix_fmt), int(H), int(W)))
+    if n == 0:
+        raise ValueError(f"bad frame size {H} x {W}")
+    return n
+
+
+def _check_raw_sizes(pix_fmt: str, n_frames: int, H: int, W: int, d_rgb: DeviceBuffer, d_yuv: DeviceBuffer) -> None:
+    if n_frames < 1 or H < 1 or W < 1:
+        raise ValueError(f"bad shape: {n_frames} frames of {H} x {W}")
+    fsz = frame_size(pix_fmt, H, W)
+    if d_rgb.nbytes < n_frames * H * W * 3 or d_yuv.nbytes < n_frames * fsz:
+        raise ValueError(f"{n_frames} frames of {H} x {W} need {n_frames * H * W * 3} RGB and {n_frames * fsz} {pix_fmt} bytes; "
+                         f"the buffers hold {d_rgb.nbytes} and {d_yuv.nbytes}")
+
+
+def yuv_to_rgb_device(ctx: Context, pix_fmt: str, d_yuv: DeviceBuffer, d_rgb: DeviceBuffer, n_frames: int, H: int, W: int, *,
+                      matrix: str = "bt601", range: str = "limited", stream=None) -> None:
+    m, r = _codes(matrix, range)
+    _check_raw_sizes(pix_fmt, n_frames, H, W, d_rgb, d_yuv)
+    ctx._check(lib.avx_yuv_to_rgb_u8(ctx._h, _fmt_code(pix_fmt), d_yuv.ptr, d_rgb.ptr, int(n_frames), int(H), int(W), m, r, ctx._s(stream)))
+
+
+def rgb_to_yuv_device(ctx: Context, pix_fmt: str, d_rgb: DeviceBuffer, d_yuv: DeviceBuffer, n_frames: int, H: int, W: int, *,
+                      matrix: str = "bt601", range: str = "limited", stream=None) -> None:
+    m, r = _codes(matrix, range)
+    _check_raw_sizes(pix_fmt, n_frames, H, W, d_rgb, d_yuv)
+    ctx._check(lib.avx_rgb_to_yuv_u8(ctx._h, _fmt_code(pix_fmt), d_rgb.ptr, d_yuv.ptr, int(n_frames), int(H), int(W), m, r, ctx._s(stream)))
+
+
+def yuv_to_rgb(buf: np.ndarray, H: int, W: int, *, pix_fmt: str, matrix: str = "bt601", range: str = "limited",
+               ctx: Optional[Context] = None) -> np.ndarray:
+    """Raw payload(s) in `pix_fmt` -> RGB uint8.  `buf`: uint8 of one frame (frame_size(pix_fmt, H, W) bytes, 16-bit samples as
+    little-endian byte pairs) -> (H, W, 3), or with a leading frame axis (N, frame_size) -> (N, H, W, 3)."""
+    _codes(matrix, range)
+    fsz = frame_size(pix_fmt, H, W)
+    a = np.ascontiguousarray(buf)
+    if a.dtype != np.uint8:
+        raise TypeError(f"raw video payloads are uint8 (got {a.dtype})")
+    batched = a.ndim == 2 and a.shape[1] == fsz
+    if not batched and a.size != fsz:
+        raise ValueError(f"expected {fsz} bytes per {H}x{W} {pix_fmt} frame (or an (N, {fsz}) batch), got shape {a.shape}")
+    n = a.shape[0] if batched else 1
+    ctx = ctx or get_context()
+    d_in = ctx.upload(a)
+    d_out = ctx.malloc(n * H * W * 3)
+    try:
+        yuv_to_rgb_device(ctx, pix_fmt, d_in, d_out, n, H, W, matrix=matrix, range=range)
+        out = ctx.download(d_out, (n, H, W, 3), np.uint8)
+    finally:
+        d_in.free()
+        d_out.free()
+    return out if batched else out[0]
+
+
+def rgb_to_yuv(rgb: np.ndarray, *, pix_fmt: str, matrix: str = "bt601", range: str = "limited", ctx: Optional[Context] = None) -> np.ndarray:
+    """RGB uint8 (H, W, 3) -> flat uint8 payload in `pix_fmt` (frame_size bytes), or (N, H, W, 3) -> (N, frame_size)."""
+    _codes(matrix, range)
+    _fmt_code(pix_fmt)
+    a = np.ascontiguousarray(rgb)
+    if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.shape[-1] != 3:
+        raise ValueError(f"expected uint8 (H, W, 3) or (N, H, W, 3), got {a.dtype} {a.shape}")
+    batched = a.ndim == 4
+    n, H, W = (a.shape[0] if batched else 1), a.shape[-3], a.shape[-2]
+    fsz = frame_size(pix_fmt, H, W)
+    ctx = ctx or get_context()
+    d_in = ctx.upload(a)
+    d_out = ctx.malloc(n * fsz)
+    try:
+        rgb_to_yuv_device(ctx, pix_fmt, d_in, d_out, n, H, W, matrix=matrix, range=range)
+        out = ctx.download(d_out, (n, fsz), np.uint8)
     finally:
         d_in.free()
         d_out.free()

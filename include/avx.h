@@ -272,6 +272,29 @@ int avx_rgb_to_i420_u8(avx_ctx* ctx, const uint8_t* rgb_hwc, uint8_t* yuv, int n
  * (R = cy y + crv v, G = cy y + cgu u + cgv v, B = cy y + cbu u), enc_out = {Y row r g b, U row r g b, V row r g b, yo}. */
 int avx_yuv_coefficients(int matrix, int full_range, int dec_out[6], int enc_out[10]);
 
+/* Raw video pixel formats (csrc/yuv_raw.hip), named as ffmpeg's -pix_fmt names them.  One frame of H x W, with
+ * cw = ceil(W/2) and ch = ceil(H/2), no padding, frames back to back:
+ *   YUV420P  Y, U (ch x cw), V (ch x cw), 8-bit: the I420 payload above      NV12    Y, then ch rows of cw (U, V) byte pairs
+ *   YUV422P  Y, U (H x cw), V (H x cw)        YUV444P  Y, U, V (H x W each)  GRAY    Y only (decodes with neutral chroma)
+ *   YUV4xxP10LE  as the 8-bit planar forms, every sample a little-endian uint16 holding 0..1023
+ *   P010LE   as NV12, every sample a little-endian uint16 with the 10-bit value in its high bits (value << 6); the low 6 bits
+ *            are ignored on read and written as zero
+ * A payload is always addressed as bytes.  The arithmetic is that of the I420 pair at sample depth d = 8 or 10: yo = 16 s,
+ * ys = 219 s / 255, cs = 224 s / 255 with s = 2^(d-8) (limited) or yo = 0, ys = cs = (2^d - 1) / 255 (full), the chroma centre
+ * 2^(d-1), outputs clamped to 0 .. 2^d - 1, chroma from the sum over its block of n = 1, 2 or 4 pixels with
+ * c + ((sum + 2^(15 + log2 n)) >> (16 + log2 n)).  At d = 8 the tables are those of avx_yuv_coefficients, so YUV420P equals the
+ * I420 pair byte for byte.  The buffers must not overlap; payloads of 16-bit samples must be 2-byte aligned. */
+enum avx_pix_fmt {
+    AVX_PIX_YUV420P = 0, AVX_PIX_NV12 = 1, AVX_PIX_YUV422P = 2, AVX_PIX_YUV444P = 3, AVX_PIX_GRAY = 4,
+    AVX_PIX_YUV420P10LE = 5, AVX_PIX_YUV422P10LE = 6, AVX_PIX_YUV444P10LE = 7, AVX_PIX_P010LE = 8, AVX_PIX_FMT_COUNT = 9
+};
+/* Bytes of one frame (host only); 0 for a bad format or size. */
+size_t avx_yuv_frame_size(int fmt, int H, int W);
+int avx_yuv_to_rgb_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t* rgb_hwc, int n_frames, int H, int W, int matrix, int full_range, void* stream);
+int avx_rgb_to_yuv_u8(avx_ctx* ctx, int fmt, const uint8_t* rgb_hwc, uint8_t* yuv, int n_frames, int H, int W, int matrix, int full_range, void* stream);
+/* avx_yuv_coefficients at sample depth 8 or 10 (host only). */
+int avx_yuv_coefficients_d(int matrix, int full_range, int depth, int dec_out[6], int enc_out[10]);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

@@ -1,14 +1,16 @@
-"""I420 vs RGB host I/O of the 4K dog stream, and the YUV kernels' time per 4K frame (DESIGN §4.8).  Not part of bench.py.
+"""I420 vs RGB host I/O of the 4K dog stream, and the YUV kernels' time per 4K frame (DESIGN §4.8, §4.9).  Not part of bench.py.
 
-  python tools/yuv_stream_bench.py stream  [--frames 256] [--distinct 32] [--reps 3]
+  python tools/yuv_stream_bench.py stream  [--frames 256] [--distinct 32] [--reps 3] [--pix-fmt NAME ...]
       The dog stream at 3840x2160 with split-compare through FramePipeline (depth 3), fed from frames held in memory (`distinct`
       frames cycled, converted beforehand, so no disk or decode bounds it): io_format="rgb" and "i420" alternately, `reps`
-      times each after one warm-up run each.  One JSON line per run: frames/s and host_copy_s.
-  python tools/yuv_stream_bench.py kernels [--iters 20]
-      8-frame 4K batches through avx_i420_to_rgb_u8 and avx_rgb_to_i420_u8, for `rocprofv3 --kernel-trace --stats` to time.
+      times each after one warm-up run each.  One JSON line per run: frames/s and host_copy_s.  With --pix-fmt the runs are
+      io_format="i420" (the baseline) and io_format="yuv" in every named raw format instead.
+  python tools/yuv_stream_bench.py kernels [--iters 20] [--pix-fmt NAME ...]
+      8-frame 4K batches through avx_i420_to_rgb_u8 and avx_rgb_to_i420_u8, for `rocprofv3 --kernel-trace --stats` to time; with
+      --pix-fmt, also through avx_yuv_to_rgb_u8 and avx_rgb_to_yuv_u8 in every named format, in the same process.
   python tools/yuv_stream_bench.py report STATS_CSV
       The kernels' mean time per 4K frame from rocprofv3's kernel_stats.csv, and its share of 6.29 TB/s (the measured HBM copy
-      rate, MI355X) for the 4.5 B/px each direction moves."""
+      rate, MI355X) for the bytes each direction moves: the format's B/px plus 3 B/px of RGB."""
 import argparse
 import csv
 import json
@@ -32,12 +34,19 @@ def stream(args):
     from animal_vision_amd.synthetic import structured_frame
     from animal_vision_amd.yuv import rgb_to_i420
 
+    from animal_vision_amd.yuv import rgb_to_yuv
+
     rgb = [structured_frame(k, H, W) for k in range(args.distinct)]
-    yuv = [rgb_to_i420(f) for f in rgb]
-    src = {"rgb": rgb, "i420": yuv}
+    src = {"i420": [rgb_to_i420(f) for f in rgb]}
+    if args.pix_fmt:
+        for p in args.pix_fmt:
+            src[p] = [rgb_to_yuv(f, pix_fmt=p) for f in rgb]
+    else:
+        src = {"rgb": rgb, **src}
 
     def run(fmt, n):
-        pipe = FramePipeline(DichromatOp(Dog.SPEC), H, W, depth=3, split_compare=True, io_format=fmt)
+        raw = fmt not in ("rgb", "i420")
+        pipe = FramePipeline(DichromatOp(Dog.SPEC), H, W, depth=3, split_compare=True, io_format="yuv" if raw else fmt, pix_fmt=fmt if raw else None)
         try:
             frames = src[fmt]
             st = pipe.run(((i, frames[i % len(frames)]) for i in range(n)), lambda i, o: None)
@@ -45,10 +54,10 @@ def stream(args):
             pipe.close()
         return st
 
-    for fmt in ("rgb", "i420"):
+    for fmt in src:
         run(fmt, 16)
     for rep in range(args.reps):
-        for fmt in ("rgb", "i420"):
+        for fmt in src:
             st = run(fmt, args.frames)
             print(json.dumps({"io_format": fmt, "rep": rep, "frames": st.frames, "seconds": round(st.seconds, 4),
                               "fps": round(st.frames / st.seconds, 1), "host_copy_s": round(st.host_copy_seconds, 4)}), flush=True)
@@ -56,7 +65,7 @@ def stream(args):
 
 def kernels(args):
     from animal_vision_amd.runtime import get_context
-    from animal_vision_amd.yuv import i420_size, i420_to_rgb_device, rgb_to_i420_device
+    from animal_vision_amd.yuv import frame_size, i420_size, i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_to_rgb_device
 
     ctx = get_context()
     n = 8
@@ -66,23 +75,48 @@ def kernels(args):
     for _ in range(args.iters):
         rgb_to_i420_device(ctx, d_rgb, d_yuv, n, H, W)
         i420_to_rgb_device(ctx, d_yuv, d_rgb2, n, H, W)
+    for p in args.pix_fmt or []:
+        d_raw = ctx.malloc(n * frame_size(p, H, W))
+        for _ in range(args.iters):
+            rgb_to_yuv_device(ctx, p, d_rgb, d_raw, n, H, W)
+            yuv_to_rgb_device(ctx, p, d_raw, d_rgb2, n, H, W)
+        ctx.sync()
+        d_raw.free()
     ctx.sync()
-    print(json.dumps({"kernels": "done", "iters": args.iters, "batch": n}))
+    print(json.dumps({"kernels": "done", "iters": args.iters, "batch": n, "pix_fmt": args.pix_fmt or []}))
     for d in (d_rgb, d_yuv, d_rgb2):
         d.free()
 
 
+# the template arguments of csrc/yuv_raw.hip's Fmt<T, SX, SY, IL, SH, LUMA>, as they appear in a demangled kernel name
+_RAW_FMT = {("unsigned char", 1, 1, False, 0, False): "yuv420p", ("unsigned char", 1, 1, True, 0, False): "nv12",
+            ("unsigned char", 1, 0, False, 0, False): "yuv422p", ("unsigned char", 0, 0, False, 0, False): "yuv444p",
+            ("unsigned char", 0, 0, False, 0, True): "gray", ("unsigned short", 1, 1, False, 0, False): "yuv420p10le",
+            ("unsigned short", 1, 0, False, 0, False): "yuv422p10le", ("unsigned short", 0, 0, False, 0, False): "yuv444p10le",
+            ("unsigned short", 1, 1, True, 6, False): "p010le"}
+
+
+def _raw_fmt_of(name):
+    m = re.search(r"Fmt<(unsigned char|unsigned short), (\d+), (\d+), (true|false), (\d+), (true|false)>", name)
+    if not m:
+        return None
+    return _RAW_FMT.get((m.group(1), int(m.group(2)), int(m.group(3)), m.group(4) == "true", int(m.group(5)), m.group(6) == "true"))
+
+
 def report(args):
-    bytes_per_frame = 4.5 * H * W  # 1.5 B/px of I420 + 3 B/px of RGB, in one direction
+    from animal_vision_amd.yuv import frame_size
+
     with open(args.csv) as f:
         for row in csv.DictReader(f):
             name = row.get("Name") or row.get("KernelName") or ""
-            if "i420" not in name:
+            fmt = "yuv420p" if "i420" in name else _raw_fmt_of(name)
+            if fmt is None:
                 continue
+            bytes_per_frame = frame_size(fmt, H, W) + 3.0 * H * W  # the payload + 3 B/px of RGB, in one direction
             avg_ns = float(row.get("AverageNs") or row.get("Average") or 0.0)
             us = avg_ns / 1e3 / 8
             kernel = re.search(r"k_\w+", name)
-            print(json.dumps({"kernel": kernel.group(0) if kernel else name, "calls": int(row.get("Calls", 0)), "us_per_4k_frame": round(us, 2),
+            print(json.dumps({"kernel": kernel.group(0) if kernel else name, "pix_fmt": "i420" if "i420" in name else fmt, "calls": int(row.get("Calls", 0)), "us_per_4k_frame": round(us, 2),
                               "TB_per_s": round(bytes_per_frame / (us * 1e-6) / 1e12, 3),
                               "frac_of_6.29TBps": round(bytes_per_frame / COPY_BPS / (us * 1e-6), 3)}))
 
@@ -94,8 +128,10 @@ def main():
     s.add_argument("--frames", type=int, default=256)
     s.add_argument("--distinct", type=int, default=32)
     s.add_argument("--reps", type=int, default=3)
+    s.add_argument("--pix-fmt", nargs="+", default=None, help="raw formats to stream with io_format='yuv' (the baseline is io_format='i420')")
     k = sub.add_parser("kernels")
     k.add_argument("--iters", type=int, default=20)
+    k.add_argument("--pix-fmt", nargs="+", default=None, help="raw formats to run through the avx_yuv_to_rgb_u8 / avx_rgb_to_yuv_u8 kernels too")
     r = sub.add_parser("report")
     r.add_argument("csv")
     args = ap.parse_args()

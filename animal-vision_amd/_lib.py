@@ -17,6 +17,8 @@ AVX_MAX_KSIZE = 33
 # enum avx_pix_fmt (include/avx.h), by ffmpeg's -pix_fmt names
 AVX_PIX_FMTS = {"yuv420p": 0, "nv12": 1, "yuv422p": 2, "yuv444p": 3, "gray": 4, "yuv420p10le": 5, "yuv422p10le": 6, "yuv444p10le": 7,
                 "p010le": 8}
+AVX_TRANSFERS = {"pq": 1, "hlg": 2}      # enum avx_transfer
+AVX_TONEMAPS = {"clip": 0, "mobius": 1}  # enum avx_tonemap
 
 
 class AvxError(RuntimeError):
@@ -292,6 +294,7 @@ _SIGS = {
     "avx_yuv_frame_size": (_sz, [_i, _i, _i]),
     "avx_yuv_to_rgb_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "avx_rgb_to_yuv_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "avx_yuv_hdr_to_rgb_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

@@ -114,7 +114,8 @@ class FramePipeline:
     def __init__(self, op, H: int, W: int, *, ctx=None, depth: int = 3, split_compare: bool = False, draw_seam: bool = True,
                  labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed"), io_format: str = "rgb",
                  matrix: str = "bt601", yuv_range: str = "limited", split_baseline: bool = False, batch: int = 1,
-                 pix_fmt: Optional[str] = None):
+                 pix_fmt: Optional[str] = None, transfer: Optional[str] = None, tonemap: str = "mobius", peak_nits: float = 1000.0,
+                 sdr_white: float = 203.0, out_matrix: Optional[str] = None):
         """split_compare: emit make_split_frame(original, transformed) composed on the device (renderers/video.py:198-245:
         halves, seam, and the two corner labels -- `labels` = (left, right), None = none) instead of the transformed frame.
 
@@ -124,6 +125,11 @@ class FramePipeline:
         "yuv" -- as "i420", with flat payloads in the raw pixel format `pix_fmt` (one of yuv.PIX_FMTS: nv12, p010le, ...; DESIGN
         §4.9) and the conversions of csrc/yuv_raw.hip.  Format names go in `pix_fmt`, not in io_format.
 
+        transfer: "pq" or "hlg" -- the payloads are HDR (BT.2020, 10-bit `pix_fmt`, io_format="yuv"): the slot stream decodes
+        them through yuv.yuv_hdr_to_rgb_device with `tonemap`, `peak_nits` and `sdr_white` instead of `matrix`, and
+        the op sees tone-mapped SDR frames.  The output side is SDR: it is encoded by rgb_to_yuv_device in `out_matrix`, which
+        defaults to "bt709" with a transfer and to `matrix` without one.  With transfer=None nothing else changes.
+
         split_baseline: the split frame's left half is the op's own baseline -- `op.slot_baseline(k)`, the frame a species'
         visualize() returns first (a UV species' panorama-warped input, SpeciesStreamOp) -- instead of the input frame.
 
@@ -132,7 +138,7 @@ class FramePipeline:
         copy.  Frames are still emitted one by one in submission order; the last slot of a stream may carry fewer frames.  The
         op states how many frames one call takes in `max_batch` (absent: 1); an op that cannot take `batch` is refused here."""
         from .runtime import get_context
-        from .yuv import PIX_FMTS, _codes, frame_size, i420_size
+        from .yuv import PIX_FMTS, _codes, frame_size, hdr_codes, i420_size
 
         if io_format not in ("rgb", "i420", "yuv"):
             raise ValueError(f"io_format must be 'rgb', 'i420' or 'yuv' (got {io_format!r})")
@@ -141,6 +147,14 @@ class FramePipeline:
         if io_format != "yuv" and pix_fmt is not None:
             raise ValueError(f"pix_fmt goes with io_format='yuv' (got io_format={io_format!r})")
         _codes(matrix, yuv_range)
+        if transfer is not None:
+            if io_format != "yuv":
+                raise ValueError(f"transfer={transfer!r} goes with io_format='yuv' and a 10-bit pix_fmt (got io_format={io_format!r})")
+            hdr_codes(pix_fmt, transfer, yuv_range, tonemap, peak_nits, sdr_white)
+        if out_matrix is None:
+            out_matrix = "bt709" if transfer is not None else matrix
+        _codes(out_matrix, yuv_range)
+        self.transfer, self.tonemap, self.peak_nits, self.sdr_white, self.out_matrix = transfer, tonemap, float(peak_nits), float(sdr_white), out_matrix
         self.io_format, self.matrix, self.yuv_range, self.pix_fmt = io_format, matrix, yuv_range, pix_fmt
         self.op, self.H, self.W, self.depth = op, H, W, depth
         self.batch = int(batch)
@@ -204,7 +218,7 @@ class FramePipeline:
         """frames: (global index, HxWx3 uint8 -- or, io_format="i420" / "yuv", a flat payload) pairs owned by this rank;
         emit(index, out) in submission order, `out` in the same format."""
         from ._lib import lib
-        from .yuv import i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_to_rgb_device
+        from .yuv import i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_hdr_to_rgb_device, yuv_to_rgb_device
 
         ctx, n, t0 = self.ctx, 0, time.perf_counter()
         self._copy_s = 0.0
@@ -214,10 +228,15 @@ class FramePipeline:
         kw = dict(matrix=self.matrix, range=self.yuv_range)
         if self.io_format == "yuv":
             def to_rgb(s, m):
-                yuv_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
+                if self.transfer is not None:
+                    yuv_hdr_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, transfer=self.transfer, range=self.yuv_range,
+                                          tonemap=self.tonemap, peak_nits=self.peak_nits, sdr_white=self.sdr_white, stream=s.stream)
+                else:
+                    yuv_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
 
             def from_rgb(s, m):
-                rgb_to_yuv_device(ctx, self.pix_fmt, s.d_out, s.d_yuv_out, m, self.H, self.W, stream=s.stream, **kw)
+                rgb_to_yuv_device(ctx, self.pix_fmt, s.d_out, s.d_yuv_out, m, self.H, self.W, stream=s.stream, matrix=self.out_matrix,
+                                  range=self.yuv_range)
         else:
             def to_rgb(s, m):
                 i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
@@ -288,7 +307,8 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
     A renderer whose frames can stay I420 end to end (`yuv_hw` not None: renderers.VideoRenderer from a .y4m to a .y4m) hands
     over get_yuv() payloads, and the pipeline runs with io_format="i420" in the renderer's `matrix` and `yuv_range`.
     When that renderer names a raw pixel format (`yuv_pix_fmt`: raw video in and out in one format), the pipeline runs with
-    io_format="yuv" in that format.  split_baseline, batch (frames per slot and per op call): see FramePipeline."""
+    io_format="yuv" in that format, and with the renderer's HDR settings (`transfer`, `tonemap`, `peak_nits`, `sdr_white`,
+    `out_matrix`) when it has them.  split_baseline, batch (frames per slot and per op call): see FramePipeline."""
     self_sharding = getattr(renderer, "world", 1) == world and getattr(renderer, "rank", 0) == rank and hasattr(renderer, "last_index") and world > 1
     yuv_hw = getattr(renderer, "yuv_hw", None) if callable(getattr(renderer, "get_yuv", None)) else None
     get = renderer.get_yuv if yuv_hw is not None else renderer.get_image
@@ -299,8 +319,13 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
     elif yuv_hw is not None:
         H, W = yuv_hw
         fmt = getattr(renderer, "yuv_pix_fmt", None)
+        hdr = {}
+        if fmt and getattr(renderer, "transfer", None) is not None:
+            hdr = dict(transfer=renderer.transfer, tonemap=renderer.tonemap, peak_nits=renderer.peak_nits, sdr_white=renderer.sdr_white)
+        if fmt and getattr(renderer, "out_matrix", None) is not None:
+            hdr["out_matrix"] = renderer.out_matrix
         pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, io_format="yuv" if fmt else "i420",
-                             pix_fmt=fmt, matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline, batch=batch)
+                             pix_fmt=fmt, matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline, batch=batch, **hdr)
     else:
         H, W, _ = first.shape
         pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, split_baseline=split_baseline, batch=batch)

@@ -19,6 +19,11 @@ frames in one of yuv.PIX_FMTS (nv12, p010le, yuv422p, ...); `write_pix_fmt` writ
 `pix_fmt` when the sink is "-" or ends in .yuv.  get_image() and get_yuv() keep their contracts; a raw source into a .y4m sink
 goes through RGB.
 
+HDR sources: `transfer` ("pq" or "hlg") reads a raw 10-bit source as BT.2020 HDR video.  get_image() then returns
+the tone-mapped SDR frame of yuv.yuv_hdr_to_rgb (`tonemap`, `peak_nits`, `sdr_white`; `matrix` plays no part in the decode), so
+the per-frame species get it too, and every YUV sink is encoded in `out_matrix`: "bt709" by default with a transfer, `matrix`
+without one.
+
 Sharded streams (two keywords the reference does not have, both defaulted): with `world` > 1 this renderer
 serves and stores only the frames of rank `rank` (global frame i belongs to rank i mod world) -- every source here is
 index-addressable, so the other ranks' frames are never generated, read or decoded.  Outputs carry the GLOBAL frame
@@ -79,20 +84,29 @@ def is_y4m(path: Optional[str]) -> bool:
 class VideoRenderer(Renderer):
     def __init__(self, *, read_path: Optional[str] = None, write_path: Optional[str] = None, fps: Optional[int] = None,
                  window_name: str = "Video Analysis", rank: int = 0, world: int = 1, matrix: str = "bt601", range: Optional[str] = None,
-                 pix_fmt: Optional[str] = None, size: Optional[tuple] = None, write_pix_fmt: Optional[str] = None):
+                 pix_fmt: Optional[str] = None, size: Optional[tuple] = None, write_pix_fmt: Optional[str] = None,
+                 transfer: Optional[str] = None, tonemap: str = "mobius", peak_nits: float = 1000.0, sdr_white: float = 203.0,
+                 out_matrix: Optional[str] = None):
         if not (0 <= rank < world):
             raise ValueError(f"rank {rank} outside world {world}")
         if (pix_fmt is None) != (size is None):
             raise ValueError("a raw video source is named by both pix_fmt and size=(W, H)")
         if write_pix_fmt is None and pix_fmt is not None and is_raw_sink(write_path):
             write_pix_fmt = pix_fmt
-        from ..yuv import PIX_FMTS
+        from ..yuv import MATRICES, PIX_FMTS, hdr_codes
 
         for f in (pix_fmt, write_pix_fmt):
             if f is not None and f not in PIX_FMTS:
                 raise ValueError(f"pix_fmt must be one of {', '.join(PIX_FMTS)} (got {f!r})")
         if write_pix_fmt is not None and not write_path:
             raise ValueError("write_pix_fmt needs a write_path")
+        if transfer is not None:  # an HDR source: raw, 10-bit, BT.2020
+            hdr_codes(pix_fmt, transfer, range or "limited", tonemap, peak_nits, sdr_white)
+        if out_matrix is None:
+            out_matrix = "bt709" if transfer is not None else matrix
+        if out_matrix not in MATRICES:
+            raise ValueError(f"out_matrix must be one of {sorted(MATRICES)} (got {out_matrix!r})")
+        self.transfer, self.tonemap, self.peak_nits, self.sdr_white, self.out_matrix = transfer, tonemap, float(peak_nits), float(sdr_white), out_matrix
         self.pix_fmt, self.write_pix_fmt = pix_fmt, write_pix_fmt
         self.size = None if size is None else (int(size[0]), int(size[1]))
         self._raw = None             # renderers.rawvideo.RawVideoReader
@@ -196,8 +210,11 @@ class VideoRenderer(Renderer):
             f = self.get_yuv()
             if f is None:
                 return None
-            from ..yuv import yuv_to_rgb
+            from ..yuv import yuv_hdr_to_rgb, yuv_to_rgb
 
+            if self.transfer is not None:
+                return yuv_hdr_to_rgb(f, self._raw.height, self._raw.width, pix_fmt=self.pix_fmt, transfer=self.transfer, range=self.yuv_range,
+                                      tonemap=self.tonemap, peak_nits=self.peak_nits, sdr_white=self.sdr_white)
             return yuv_to_rgb(f, self._raw.height, self._raw.width, pix_fmt=self.pix_fmt, matrix=self.matrix, range=self.yuv_range)
         if self._y4m is not None:
             f = self.get_yuv()
@@ -266,7 +283,7 @@ class VideoRenderer(Renderer):
             H, W = frame.shape[:2]
             from ..yuv import rgb_to_i420
 
-            payload = rgb_to_i420(frame, matrix=self.matrix, range=self.yuv_range)
+            payload = rgb_to_i420(frame, matrix=self.out_matrix, range=self.yuv_range)
         elif frame.ndim == 1 and frame.dtype == np.uint8:
             if self._y4m_out is None and self._y4m is None:
                 raise ValueError("an I420 payload names no frame size: render an RGB frame first, or read from a .y4m")
@@ -288,7 +305,7 @@ class VideoRenderer(Renderer):
             H, W = frame.shape[:2]
             from ..yuv import rgb_to_yuv
 
-            payload = rgb_to_yuv(frame, pix_fmt=self.write_pix_fmt, matrix=self.matrix, range=self.yuv_range)
+            payload = rgb_to_yuv(frame, pix_fmt=self.write_pix_fmt, matrix=self.out_matrix, range=self.yuv_range)
         elif frame.ndim == 1 and frame.dtype == np.uint8:
             if self._raw_out is None and (self._raw is None or self.pix_fmt != self.write_pix_fmt):
                 raise ValueError(f"a {self.write_pix_fmt} payload names no frame size: render an RGB frame first, or read raw video in that format")

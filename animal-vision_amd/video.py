@@ -7,6 +7,11 @@ Raw (headerless) video, what `ffmpeg -f rawvideo` and hardware decoders write, i
 
     ffmpeg -i in.mkv -f rawvideo -pix_fmt p010le - | python -m animal_vision_amd.video - out.yuv --species Dog --pix-fmt p010le --size 3840x2160
 
+HDR footage (10-bit BT.2020 with a PQ or HLG transfer: HDR10, HLG broadcasts) is named by `--transfer`; it is tone-mapped to SDR on
+the device as it is decoded (`--tonemap`, `--peak-nits`, `--sdr-white`), and the output is SDR in `--out-matrix`:
+
+    ffmpeg -i hdr.mkv -f rawvideo -pix_fmt p010le - | python -m animal_vision_amd.video - out.yuv --species Dog --pix-fmt p010le --size 3840x2160 --transfer pq
+
 `--out-pix-fmt` names the output's format; it defaults to the input's when OUTPUT is "-" or ends in .yuv.  Raw in and raw out in one
 format keep the payload (1.5 B/px for nv12, 3 B/px for p010le) across the host and PCIe (FramePipeline io_format="yuv").
 
@@ -25,13 +30,14 @@ kernels n_frames = N.  The species of the per-frame loop have no batched form: f
 from __future__ import annotations
 
 import argparse
+import math
 import sys
 import time
 from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import AVX_PIX_FMTS
+from ._lib import AVX_PIX_FMTS, AVX_TONEMAPS, AVX_TRANSFERS
 from .gallery import _CLASS_NAMES, ensure_rgb_uint8, species_class
 
 SPECIES_NAMES = list(_CLASS_NAMES)  # all 36 display names
@@ -91,9 +97,36 @@ def _size_arg(text: str):
     return w, h
 
 
+class _VideoParser(argparse.ArgumentParser):
+    """The command's parser; parse_args also checks the options that depend on each other (the HDR ones, `--matrix bt2020`)."""
+
+    def parse_args(self, args=None, namespace=None):
+        args = super().parse_args(args, namespace)
+        if args.transfer is not None:
+            from .yuv import HDR_PIX_FMTS
+
+            if args.pix_fmt not in HDR_PIX_FMTS:
+                self.error(f"--transfer needs --pix-fmt naming a 10-bit format ({', '.join(HDR_PIX_FMTS)}); got --pix-fmt {args.pix_fmt}")
+            if args.matrix not in (None, "bt2020"):
+                self.error(f"--matrix {args.matrix} with --transfer: HDR video is decoded with the bt2020 matrix (--out-matrix names the output's)")
+        else:
+            if args.matrix == "bt2020":
+                self.error("--matrix bt2020 needs --transfer: bt2020 is decoded on the HDR path only")
+            for flag, v in (("--tonemap", args.tonemap), ("--peak-nits", args.peak_nits), ("--sdr-white", args.sdr_white)):
+                if v is not None:
+                    self.error(f"{flag} needs --transfer")
+        args.tonemap = args.tonemap or "mobius"
+        args.peak_nits = 1000.0 if args.peak_nits is None else args.peak_nits
+        args.sdr_white = 203.0 if args.sdr_white is None else args.sdr_white
+        if not (math.isfinite(args.peak_nits) and math.isfinite(args.sdr_white) and args.sdr_white > 0.0 and args.peak_nits > args.sdr_white):
+            self.error(f"--peak-nits and --sdr-white must be finite and positive, with --peak-nits above --sdr-white (got {args.peak_nits} and {args.sdr_white})")
+        if args.matrix is None or args.transfer is not None:
+            args.matrix = "bt601"  # what the SDR conversions use; the HDR decode takes no matrix
+        return args
+
+
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(prog="video", description="Run one species on every frame of a video (Y4M in and out, or the other "
-                                                          "VideoRenderer forms).")
+    ap = _VideoParser(prog="video", description="Run one species on every frame of a video (Y4M in and out, or the other VideoRenderer forms).")
     ap.add_argument("input", help=".y4m file, '-' (stdin: Y4M, or raw video with --pix-fmt), a raw video file (--pix-fmt), "
                                   "synthetic:<W>x<H>:<n>[:kind], .npy or an image directory")
     ap.add_argument("output", help=".y4m file, '-' (stdout: Y4M, or raw video with --pix-fmt / --out-pix-fmt), a raw video file, .npy or a "
@@ -103,13 +136,21 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--no-labels", action="store_true", help="no corner labels on the split frame")
     ap.add_argument("--depth", type=int, default=3, help="frames in flight on the device (streamed species)")
     ap.add_argument("--batch", type=_batch_arg, default=1, metavar="N", help="frames per slot and per launch chain, 1..16 (streamed species only)")
-    ap.add_argument("--matrix", default="bt601", choices=["bt601", "bt709"])
+    ap.add_argument("--matrix", default=None, choices=["bt601", "bt709", "bt2020"],
+                    help="YUV matrix (default bt601); with --transfer the decode is always bt2020, and only that may be named")
     ap.add_argument("--range", default=None, choices=["limited", "full"], help="YUV range (default: the input's XCOLORRANGE, else limited)")
     ap.add_argument("--pix-fmt", default=None, choices=list(AVX_PIX_FMTS), metavar="NAME",
                     help="read INPUT as raw video in this format (ffmpeg's -pix_fmt names: " + ", ".join(AVX_PIX_FMTS) + "); needs --size")
     ap.add_argument("--size", default=None, type=_size_arg, metavar="WxH", help="frame size of the raw input")
     ap.add_argument("--out-pix-fmt", default=None, choices=list(AVX_PIX_FMTS), metavar="NAME",
                     help="write OUTPUT as raw video in this format (default: --pix-fmt when OUTPUT is '-' or ends in .yuv)")
+    ap.add_argument("--transfer", default=None, choices=list(AVX_TRANSFERS),
+                    help="read INPUT as HDR video (BT.2020) with this transfer function and tone-map it to SDR; needs a 10-bit --pix-fmt")
+    ap.add_argument("--tonemap", default=None, choices=list(AVX_TONEMAPS), help="tone curve of --transfer (default mobius)")
+    ap.add_argument("--peak-nits", default=None, type=float, metavar="X", help="the clip's peak luminance, mapped to SDR white (default 1000)")
+    ap.add_argument("--sdr-white", default=None, type=float, metavar="X", help="the luminance shown as SDR white (default 203, BT.2408)")
+    ap.add_argument("--out-matrix", default=None, choices=["bt601", "bt709"],
+                    help="YUV matrix of the output (default: bt709 with --transfer, else --matrix)")
     return ap
 
 
@@ -131,7 +172,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
 
     def renderer():
         return VideoRenderer(read_path=args.input, write_path=args.output, window_name="AnimalCam", matrix=args.matrix, range=args.range,
-                             pix_fmt=args.pix_fmt, size=args.size, write_pix_fmt=args.out_pix_fmt)
+                             pix_fmt=args.pix_fmt, size=args.size, write_pix_fmt=args.out_pix_fmt, transfer=args.transfer, tonemap=args.tonemap,
+                             peak_nits=args.peak_nits, sdr_white=args.sdr_white, out_matrix=args.out_matrix)
 
     vr = renderer()
     vr.open()

@@ -1,5 +1,6 @@
 """YUV <-> RGB uint8 on the device, in the style of geometry.py: the I420 pair of the Y4M path (csrc/yuv.hip) and the raw video
-pixel formats -- nv12, p010le, 4:2:2, 4:4:4, gray, 10-bit planar -- of csrc/yuv_raw.hip (PIX_FMTS).
+pixel formats -- nv12, p010le, 4:2:2, 4:4:4, gray, 10-bit planar -- of csrc/yuv_raw.hip (PIX_FMTS), and the HDR decode
+of csrc/yuv_hdr.hip: 10-bit BT.2020 PQ / HLG payloads -> tone-mapped SDR RGB (yuv_hdr_to_rgb).
 
 The arithmetic (int32 fixed point, 16 fractional bits, BT.601 / BT.709, limited / full range) is defined in DESIGN §4.8; the
 coefficient tables are built by the C entry points from the (matrix, range) names below.  A payload is one frame's Y plane
@@ -10,12 +11,15 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import AVX_PIX_FMTS, lib
+from ._lib import AVX_PIX_FMTS, AVX_TONEMAPS, AVX_TRANSFERS, lib
 from .runtime import Context, DeviceBuffer, get_context
 
 MATRICES = {"bt601": 0, "bt709": 1}  # AVX_YUV_BT601, AVX_YUV_BT709
 RANGES = {"limited": 0, "full": 1}   # the full_range argument
 PIX_FMTS = tuple(AVX_PIX_FMTS)       # ffmpeg's -pix_fmt names of the raw formats (include/avx.h: enum avx_pix_fmt)
+TRANSFERS = ("pq", "hlg")            # HDR transfer functions of the HDR decode (enum avx_transfer)
+TONEMAPS = ("clip", "mobius")        # enum avx_tonemap
+HDR_PIX_FMTS = tuple(f for f in AVX_PIX_FMTS if f.endswith("10le"))  # the 10-bit formats: what the HDR decode reads
 
 
 def i420_size(H: int, W: int) -> int:
@@ -191,6 +195,64 @@ def rgb_to_yuv(rgb: np.ndarray, *, pix_fmt: str, matrix: str = "bt601", range: s
     try:
         rgb_to_yuv_device(ctx, pix_fmt, d_in, d_out, n, H, W, matrix=matrix, range=range)
         out = ctx.download(d_out, (n, fsz), np.uint8)
+    finally:
+        d_in.free()
+        d_out.free()
+    return out if batched else out[0]
+
+
+# ---------------------------------------------------------------- HDR in: PQ / HLG BT.2020 -> SDR RGB (csrc/yuv_hdr.hip) ----------
+def hdr_codes(pix_fmt: str, transfer: str, range: str = "limited", tonemap: str = "mobius", peak_nits: float = 1000.0, sdr_white: float = 203.0):
+    """Checks the settings of the HDR decode without touching the device; returns the C side's (fmt, full_range,
+    transfer, tonemap, peak_nits, sdr_white)."""
+    import math
+
+    if pix_fmt not in HDR_PIX_FMTS:
+        raise ValueError(f"the HDR decode reads the 10-bit formats {', '.join(HDR_PIX_FMTS)} (got pix_fmt={pix_fmt!r})")
+    if transfer not in TRANSFERS:
+        raise ValueError(f"transfer must be one of {', '.join(TRANSFERS)} (got {transfer!r})")
+    if tonemap not in TONEMAPS:
+        raise ValueError(f"tonemap must be one of {', '.join(TONEMAPS)} (got {tonemap!r})")
+    if range not in RANGES:
+        raise ValueError(f"range must be one of {sorted(RANGES)} (got {range!r})")
+    try:
+        peak, white = float(peak_nits), float(sdr_white)
+    except (TypeError, ValueError):
+        raise ValueError(f"peak_nits and sdr_white are numbers (got {peak_nits!r}, {sdr_white!r})")
+    if not (math.isfinite(peak) and math.isfinite(white) and white > 0.0 and peak > white):
+        raise ValueError(f"peak_nits and sdr_white must be finite and positive, with peak_nits > sdr_white (got {peak_nits!r}, {sdr_white!r})")
+    return AVX_PIX_FMTS[pix_fmt], RANGES[range], AVX_TRANSFERS[transfer], AVX_TONEMAPS[tonemap], peak, white
+
+
+def yuv_hdr_to_rgb_device(ctx: Context, pix_fmt: str, d_yuv: DeviceBuffer, d_rgb: DeviceBuffer, n_frames: int, H: int, W: int, *,
+                          transfer: str, range: str = "limited", tonemap: str = "mobius", peak_nits: float = 1000.0,
+                          sdr_white: float = 203.0, stream=None) -> None:
+    """n_frames 10-bit BT.2020 payloads in `pix_fmt` with the `transfer` curve -> tone-mapped sRGB uint8 frames."""
+    fmt, r, tr, tm, peak, white = hdr_codes(pix_fmt, transfer, range, tonemap, peak_nits, sdr_white)
+    _check_raw_sizes(pix_fmt, n_frames, H, W, d_rgb, d_yuv)
+    ctx._check(lib.avx_yuv_hdr_to_rgb_u8(ctx._h, fmt, d_yuv.ptr, d_rgb.ptr, int(n_frames), int(H), int(W), r, tr, tm, peak, white, ctx._s(stream)))
+
+
+def yuv_hdr_to_rgb(buf: np.ndarray, H: int, W: int, *, pix_fmt: str, transfer: str, range: str = "limited", tonemap: str = "mobius",
+                   peak_nits: float = 1000.0, sdr_white: float = 203.0, ctx: Optional[Context] = None) -> np.ndarray:
+    """HDR payload(s) -> SDR RGB uint8, with the payload and batch conventions of yuv_to_rgb: one frame (frame_size(pix_fmt, H, W)
+    bytes) -> (H, W, 3), or (N, frame_size) -> (N, H, W, 3)."""
+    hdr_codes(pix_fmt, transfer, range, tonemap, peak_nits, sdr_white)
+    fsz = frame_size(pix_fmt, H, W)
+    a = np.ascontiguousarray(buf)
+    if a.dtype != np.uint8:
+        raise TypeError(f"raw video payloads are uint8 (got {a.dtype})")
+    batched = a.ndim == 2 and a.shape[1] == fsz
+    if not batched and a.size != fsz:
+        raise ValueError(f"expected {fsz} bytes per {H}x{W} {pix_fmt} frame (or an (N, {fsz}) batch), got shape {a.shape}")
+    n = a.shape[0] if batched else 1
+    ctx = ctx or get_context()
+    d_in = ctx.upload(a)
+    d_out = ctx.malloc(n * H * W * 3)
+    try:
+        yuv_hdr_to_rgb_device(ctx, pix_fmt, d_in, d_out, n, H, W, transfer=transfer, range=range, tonemap=tonemap, peak_nits=peak_nits,
+                              sdr_white=sdr_white)
+        out = ctx.download(d_out, (n, H, W, 3), np.uint8)
     finally:
         d_in.free()
         d_out.free()

@@ -295,6 +295,18 @@ int avx_rgb_to_yuv_u8(avx_ctx* ctx, int fmt, const uint8_t* rgb_hwc, uint8_t* yu
 /* avx_yuv_coefficients at sample depth 8 or 10 (host only). */
 int avx_yuv_coefficients_d(int matrix, int full_range, int depth, int dec_out[6], int enc_out[10]);
 
+/* HDR video in (csrc/yuv_hdr.hip): one of the four 10-bit formats above, BT.2020 non-constant-luminance Y'CbCr with
+ * a PQ (SMPTE ST 2084) or HLG (BT.2100, OOTF at 1000 nits) transfer -> tone-mapped SDR sRGB, interleaved RGB uint8 as
+ * avx_yuv_to_rgb_u8 writes it.  Per pixel: R'G'B' clamped to [0, 1] -> display light / sdr_white -> all three channels scaled by
+ * t(m) / m, m their maximum (CLIP: t = min(m, 1); MOBIUS: the identity below 0.75, a Moebius curve above it that reaches 1 at
+ * peak_nits / sdr_white) -> BT.2020 to BT.709 primaries -> clamp -> sRGB encode.  The matrix is always BT.2020; peak_nits >
+ * sdr_white > 0, both finite.  An 8-bit format or GRAY, a bad transfer or tonemap, NULL or overlapping buffers, an odd payload
+ * address or a bad size return AVX_ERR_INVALID. */
+enum avx_transfer { AVX_TRANSFER_PQ = 1, AVX_TRANSFER_HLG = 2 };
+enum avx_tonemap { AVX_TONEMAP_CLIP = 0, AVX_TONEMAP_MOBIUS = 1 };
+int avx_yuv_hdr_to_rgb_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t* rgb_hwc, int n_frames, int H, int W, int full_range, int transfer,
+                          int tonemap, double peak_nits, double sdr_white, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

@@ -1,4 +1,4 @@
-"""I420 vs RGB host I/O of the 4K dog stream, and the YUV kernels' time per 4K frame (DESIGN §4.8, §4.9).  Not part of bench.py.
+"""I420 vs RGB host I/O of the 4K dog stream, and the YUV kernels' time per 4K frame (DESIGN §4.8, §4.9, §4.10).  Not part of bench.py.
 
   python tools/yuv_stream_bench.py stream  [--frames 256] [--distinct 32] [--reps 3] [--pix-fmt NAME ...]
       The dog stream at 3840x2160 with split-compare through FramePipeline (depth 3), fed from frames held in memory (`distinct`
@@ -7,10 +7,14 @@
       io_format="i420" (the baseline) and io_format="yuv" in every named raw format instead.
   python tools/yuv_stream_bench.py kernels [--iters 20] [--pix-fmt NAME ...]
       8-frame 4K batches through avx_i420_to_rgb_u8 and avx_rgb_to_i420_u8, for `rocprofv3 --kernel-trace --stats` to time; with
-      --pix-fmt, also through avx_yuv_to_rgb_u8 and avx_rgb_to_yuv_u8 in every named format, in the same process.
-  python tools/yuv_stream_bench.py report STATS_CSV
+      --pix-fmt, also through avx_yuv_to_rgb_u8 and avx_rgb_to_yuv_u8 in every named format, in the same process; with
+      --transfer pq hlg, every named 10-bit format also goes through avx_yuv_hdr_to_rgb_u8 with each transfer (the HDR decode of
+      §4.10), beside the SDR decode of the same payload.
+  python tools/yuv_stream_bench.py report STATS_CSV [--transfer NAME ...]
       The kernels' mean time per 4K frame from rocprofv3's kernel_stats.csv, and its share of 6.29 TB/s (the measured HBM copy
-      rate, MI355X) for the bytes each direction moves: the format's B/px plus 3 B/px of RGB."""
+      rate, MI355X) for the bytes each direction moves: the format's B/px plus 3 B/px of RGB.  An HDR decode kernel's line also
+      carries its transfer and its time over the SDR decode kernel's of the same format in the same run (both move the same
+      bytes, so the ratio is arithmetic); --transfer keeps only the named transfers' HDR lines."""
 import argparse
 import csv
 import json
@@ -65,7 +69,8 @@ def stream(args):
 
 def kernels(args):
     from animal_vision_amd.runtime import get_context
-    from animal_vision_amd.yuv import frame_size, i420_size, i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_to_rgb_device
+    from animal_vision_amd.yuv import (HDR_PIX_FMTS, frame_size, i420_size, i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device,
+                                       yuv_hdr_to_rgb_device, yuv_to_rgb_device)
 
     ctx = get_context()
     n = 8
@@ -80,10 +85,13 @@ def kernels(args):
         for _ in range(args.iters):
             rgb_to_yuv_device(ctx, p, d_rgb, d_raw, n, H, W)
             yuv_to_rgb_device(ctx, p, d_raw, d_rgb2, n, H, W)
+        for tr in (args.transfer or []) if p in HDR_PIX_FMTS else []:  # the same payload, read as HDR: the same bytes in and out
+            for _ in range(args.iters):
+                yuv_hdr_to_rgb_device(ctx, p, d_raw, d_rgb2, n, H, W, transfer=tr)
         ctx.sync()
         d_raw.free()
     ctx.sync()
-    print(json.dumps({"kernels": "done", "iters": args.iters, "batch": n, "pix_fmt": args.pix_fmt or []}))
+    print(json.dumps({"kernels": "done", "iters": args.iters, "batch": n, "pix_fmt": args.pix_fmt or [], "transfer": args.transfer or []}))
     for d in (d_rgb, d_yuv, d_rgb2):
         d.free()
 
@@ -103,22 +111,37 @@ def _raw_fmt_of(name):
     return _RAW_FMT.get((m.group(1), int(m.group(2)), int(m.group(3)), m.group(4) == "true", int(m.group(5)), m.group(6) == "true"))
 
 
+_TRANSFER = {1: "pq", 2: "hlg"}  # enum avx_transfer: the HDR kernels' template argument after the format
+
+
 def report(args):
     from animal_vision_amd.yuv import frame_size
 
+    rows = []
     with open(args.csv) as f:
         for row in csv.DictReader(f):
             name = row.get("Name") or row.get("KernelName") or ""
             fmt = "yuv420p" if "i420" in name else _raw_fmt_of(name)
             if fmt is None:
                 continue
-            bytes_per_frame = frame_size(fmt, H, W) + 3.0 * H * W  # the payload + 3 B/px of RGB, in one direction
-            avg_ns = float(row.get("AverageNs") or row.get("Average") or 0.0)
-            us = avg_ns / 1e3 / 8
             kernel = re.search(r"k_\w+", name)
-            print(json.dumps({"kernel": kernel.group(0) if kernel else name, "pix_fmt": "i420" if "i420" in name else fmt, "calls": int(row.get("Calls", 0)), "us_per_4k_frame": round(us, 2),
-                              "TB_per_s": round(bytes_per_frame / (us * 1e-6) / 1e12, 3),
-                              "frac_of_6.29TBps": round(bytes_per_frame / COPY_BPS / (us * 1e-6), 3)}))
+            hdr = re.search(r"_hdr_to_rgb_\w+<.*?Fmt<[^>]*>, (\d+)", name)
+            avg_ns = float(row.get("AverageNs") or row.get("Average") or 0.0)
+            rows.append({"kernel": kernel.group(0) if kernel else name, "pix_fmt": "i420" if "i420" in name else fmt,
+                         "transfer": _TRANSFER.get(int(hdr.group(1))) if hdr else None, "calls": int(row.get("Calls", 0)), "us": avg_ns / 1e3 / 8})
+    sdr = {r["pix_fmt"]: r["us"] for r in rows if r["transfer"] is None and "_to_rgb" in r["kernel"] and r["pix_fmt"] != "i420"}
+    for r in rows:
+        if r["transfer"] is not None and args.transfer and r["transfer"] not in args.transfer:
+            continue
+        fmt, us = "yuv420p" if r["pix_fmt"] == "i420" else r["pix_fmt"], r["us"]
+        bytes_per_frame = frame_size(fmt, H, W) + 3.0 * H * W  # the payload + 3 B/px of RGB, in one direction
+        out = {"kernel": r["kernel"], "pix_fmt": r["pix_fmt"], "calls": r["calls"], "us_per_4k_frame": round(us, 2),
+               "TB_per_s": round(bytes_per_frame / (us * 1e-6) / 1e12, 3), "frac_of_6.29TBps": round(bytes_per_frame / COPY_BPS / (us * 1e-6), 3)}
+        if r["transfer"] is not None:
+            out["transfer"] = r["transfer"]
+            if r["pix_fmt"] in sdr:
+                out["x_sdr_decode"] = round(us / sdr[r["pix_fmt"]], 2)
+        print(json.dumps(out))
 
 
 def main():
@@ -132,8 +155,10 @@ def main():
     k = sub.add_parser("kernels")
     k.add_argument("--iters", type=int, default=20)
     k.add_argument("--pix-fmt", nargs="+", default=None, help="raw formats to run through the avx_yuv_to_rgb_u8 / avx_rgb_to_yuv_u8 kernels too")
+    k.add_argument("--transfer", nargs="+", default=None, choices=["pq", "hlg"], help="also run the HDR decode of every named 10-bit format with these transfers")
     r = sub.add_parser("report")
     r.add_argument("csv")
+    r.add_argument("--transfer", nargs="+", default=None, choices=["pq", "hlg"], help="keep only these transfers' HDR kernels")
     args = ap.parse_args()
     {"stream": stream, "kernels": kernels, "report": report}[args.cmd](args)
 

@@ -96,8 +96,13 @@ int avx_const_upload(avx_ctx* ctx, avx_ws* ws, int slot, const void* host, size_
 int avx_lanes(avx_ctx* ctx, int want);  // creates the frame-lane streams on first use; returns how many exist (<= want), 0 on failure
 // mst_mfma.hip: reduce the per-workgroup Gram partials ([blocks][heads][34][32]) of a Gram pass into gram / nq / nk (k_mst_qkv_final)
 int avx_mst_qkv_final_launch(avx_ctx* ctx, const float* partial, int blocks, int heads, float* gram, float* nq, float* nk, hipStream_t s);
+// geom.hip: the INTER_AREA tables (general ratio) of an H x W -> Hd x Wd resize out of the stream workspace's table cache -- the
+// tables avx_resize_hwc itself runs with -- for kernels that fuse the reduction into another pass (yuv_scale.hip).  Same cache, same
+// lifetime rules as avx_resize_hwc's own lookups.
+struct avx_area_tab { const int* start; const int* cnt; const float* alpha; int maxcnt; };  // alpha [d][maxcnt]
+int avx_geom_area_tables(avx_ctx* ctx, avx_ws* ws, hipStream_t s, int H, int W, int Hd, int Wd, avx_area_tab* ax, avx_area_tab* ay);
 
-#define AVX_HIP(ctx, call)                                                                          \
+#define AVX_HIP(ctx, call)                                                                         \
     do {                                                                                            \
         hipError_t e__ = (call);                                                                    \
         if (e__ != hipSuccess)                                                                      \

@@ -398,6 +398,19 @@ int avx_geom_linear_tables(avx_ctx* ctx, avx_ws* ws, hipStream_t s, int H, int W
     return AVX_OK;
 }
 
+// The INTER_AREA tables (general ratio) of an H x W -> Hd x Wd resize, for yuv_scale.hip's fused decode: the cache's own entries,
+// so the bits avx_resize_hwc multiplies by.
+int avx_geom_area_tables(avx_ctx* ctx, avx_ws* ws, hipStream_t s, int H, int W, int Hd, int Wd, avx_area_tab* ax, avx_area_tab* ay) {
+    TableCache tc{ctx, ws, s};
+    int rc = tc.room();
+    if (rc) return rc;
+    AxisArea x{}, y{};
+    if ((rc = tc.area(W, Wd, &x)) || (rc = tc.area(H, Hd, &y))) return rc;
+    *ax = avx_area_tab{x.start, x.cnt, x.alpha, x.maxcnt};
+    *ay = avx_area_tab{y.start, y.cnt, y.alpha, y.maxcnt};
+    return AVX_OK;
+}
+
 extern "C" {
 
 int avx_resize_hwc(avx_ctx* ctx, const void* src, int dtype, int H, int W, int C, void* dst, int Hd, int Wd, int interp, void* stream) {

@@ -9,24 +9,12 @@
 //     odd last column / row is replicated into its block on encode;
 //   * vector path (the 4:2:0 formats when W % 16 == 0, H is even and both buffers are 16-byte aligned): one thread owns a 16-pixel
 //     x 2-row strip, as k_i420_to_rgb_v16 does, and moves it in 8- and 16-byte accesses (32 B of luma per row at 16 bits).
+#include "yuv_dec.h"  // DecC, dec_px, q16_to_u8, clampi: shared with yuv_scale.hip
 #include "yuv_formats.h"
 
 namespace {
 
-struct DecC { int cy, crv, cgu, cgv, cbu, yo, cc; };                    // cc: the chroma centre 2^(d-1)
 struct EncC { int yr, yg, yb, ur, ug, ub, vr, vg, vb, yo, cc, top; };  // top: 2^d - 1
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// clamp(x >> 16, 0, 255) as a clamp of the 16.16 value before the shift: the form DESIGN §4.8 settled on (see yuv.hip)
-__device__ __forceinline__ uint32_t q16_to_u8(int x) { return (uint32_t)(x < 0 ? 0 : (x > 0xffffff ? 0xffffff : x)) >> 16; }
-
-__device__ __forceinline__ void dec_px(const DecC& c, int Y, int u, int v, uint32_t& r, uint32_t& g, uint32_t& b) {
-    const int ly = c.cy * (Y - c.yo) + (1 << 15);
-    r = q16_to_u8(ly + c.crv * v);
-    g = q16_to_u8(ly + c.cgu * u + c.cgv * v);
-    b = q16_to_u8(ly + c.cbu * u);
-}
 
 __device__ __forceinline__ int enc_y(const EncC& c, int r, int g, int b) {
     return clampi(((c.yr * r + c.yg * g + c.yb * b + (1 << 15)) >> 16) + c.yo, c.top);

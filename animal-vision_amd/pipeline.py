@@ -105,6 +105,7 @@ class _Slot:
     d_yuv_in: object = None   # io_format="i420" / "yuv": the frame's payload on the device, in and out
     d_yuv_out: object = None
     d_left: object = None     # the left half of the split frame: d_in, or the op's baseline (split_baseline)
+    d_full: object = None     # scale=: the source-size RGB frames that avx_resize_hwc reduces into d_in (HDR and io_format="rgb")
 
 
 class FramePipeline:
@@ -115,7 +116,7 @@ class FramePipeline:
                  labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed"), io_format: str = "rgb",
                  matrix: str = "bt601", yuv_range: str = "limited", split_baseline: bool = False, batch: int = 1,
                  pix_fmt: Optional[str] = None, transfer: Optional[str] = None, tonemap: str = "mobius", peak_nits: float = 1000.0,
-                 sdr_white: float = 203.0, out_matrix: Optional[str] = None):
+                 sdr_white: float = 203.0, out_matrix: Optional[str] = None, scale: Optional[Tuple[int, int]] = None):
         """split_compare: emit make_split_frame(original, transformed) composed on the device (renderers/video.py:198-245:
         halves, seam, and the two corner labels -- `labels` = (left, right), None = none) instead of the transformed frame.
 
@@ -130,6 +131,14 @@ class FramePipeline:
         the op sees tone-mapped SDR frames.  The output side is SDR: it is encoded by rgb_to_yuv_device in `out_matrix`, which
         defaults to "bt709" with a transfer and to `matrix` without one.  With transfer=None nothing else changes.
 
+        scale: (Wd, Hd), in the order of the video command's --size -- frames are read at H x W and reduced to Hd x Wd (cv2's
+        INTER_AREA; never enlarged) on the slot stream before the op sees them.  H, W stay the source size; the
+        slot's RGB buffers, the op, the split composition, the labels and everything on the way out (`out_H`, `out_W`, the
+        emitted frames or payloads) have the scaled size.  io_format="yuv" / "i420" decode straight to the scaled frame
+        (yuv.yuv_to_rgb_scaled_device: one launch per slot, no full-size RGB frame); HDR payloads (`transfer`) and
+        io_format="rgb" frames land in a source-size buffer of the slot and go through avx_resize_hwc frame by frame.  With
+        scale=None nothing changes.
+
         split_baseline: the split frame's left half is the op's own baseline -- `op.slot_baseline(k)`, the frame a species'
         visualize() returns first (a UV species' panorama-warped input, SpeciesStreamOp) -- instead of the input frame.
 
@@ -138,7 +147,7 @@ class FramePipeline:
         copy.  Frames are still emitted one by one in submission order; the last slot of a stream may carry fewer frames.  The
         op states how many frames one call takes in `max_batch` (absent: 1); an op that cannot take `batch` is refused here."""
         from .runtime import get_context
-        from .yuv import PIX_FMTS, _codes, frame_size, hdr_codes, i420_size
+        from .yuv import PIX_FMTS, _codes, check_scale, frame_size, hdr_codes, i420_size
 
         if io_format not in ("rgb", "i420", "yuv"):
             raise ValueError(f"io_format must be 'rgb', 'i420' or 'yuv' (got {io_format!r})")
@@ -157,6 +166,15 @@ class FramePipeline:
         self.transfer, self.tonemap, self.peak_nits, self.sdr_white, self.out_matrix = transfer, tonemap, float(peak_nits), float(sdr_white), out_matrix
         self.io_format, self.matrix, self.yuv_range, self.pix_fmt = io_format, matrix, yuv_range, pix_fmt
         self.op, self.H, self.W, self.depth = op, H, W, depth
+        if scale is not None:
+            try:
+                Wd, Hd = scale
+            except (TypeError, ValueError):
+                raise ValueError(f"scale is (Wd, Hd) (got {scale!r})")
+            check_scale(H, W, Hd, Wd)
+            scale = (int(Wd), int(Hd))
+        self.scale = scale
+        self.out_H, self.out_W = (scale[1], scale[0]) if scale is not None else (H, W)
         self.batch = int(batch)
         if self.batch < 1:
             raise ValueError(f"batch must be at least 1 (got {batch})")
@@ -171,21 +189,29 @@ class FramePipeline:
         self.ctx = ctx or getattr(op, "ctx", None) or get_context()
         if getattr(op, "ctx", None) is None:
             op.ctx = self.ctx
-        nbytes = H * W * 3 * self.batch
+        oH, oW = self.out_H, self.out_W
+        nbytes = oH * oW * 3 * self.batch
         # ops that own their device frames (recorded species plans, animals/_uv_species.py::SpeciesStreamOp) lend them per slot
         lend = getattr(op, "slot_buffers", None)
         self._lent = lend is not None
         self.slots = []
-        self._io_shape = (H, W, 3) if io_format == "rgb" else ((i420_size(H, W),) if io_format == "i420" else (frame_size(pix_fmt, H, W),))
-        stage = (self.batch,) + self._io_shape
+
+        def io_shape(h, w):
+            return (h, w, 3) if io_format == "rgb" else ((i420_size(h, w),) if io_format == "i420" else (frame_size(pix_fmt, h, w),))
+
+        self._in_shape, self._io_shape = io_shape(H, W), io_shape(oH, oW)  # frames in (source size), frames out
+        full = scale is not None and (io_format == "rgb" or transfer is not None)
         for k in range(depth):
             d_in, d_out = lend(k) if lend else (self.ctx.malloc(nbytes), self.ctx.malloc(nbytes))
             if d_in.nbytes < nbytes or d_out.nbytes < nbytes:
                 raise ValueError(f"batch={self.batch}: {type(op).__name__}'s slot buffers hold fewer than {self.batch} frames")
-            s = _Slot(self.ctx.stream_create(), self.ctx.pinned(stage, np.uint8), self.ctx.pinned(stage, np.uint8), d_in, d_out)
+            s = _Slot(self.ctx.stream_create(), self.ctx.pinned((self.batch,) + self._in_shape, np.uint8),
+                      self.ctx.pinned((self.batch,) + self._io_shape, np.uint8), d_in, d_out)
             s.d_left = baseline(k) if baseline is not None else d_in
             if io_format != "rgb":
-                s.d_yuv_in, s.d_yuv_out = self.ctx.malloc(self.batch * self._io_shape[0]), self.ctx.malloc(self.batch * self._io_shape[0])
+                s.d_yuv_in, s.d_yuv_out = self.ctx.malloc(self.batch * self._in_shape[0]), self.ctx.malloc(self.batch * self._io_shape[0])
+            if full:
+                s.d_full = self.ctx.malloc(self.batch * H * W * 3)
             self.slots.append(s)
 
     def close(self):
@@ -201,6 +227,8 @@ class FramePipeline:
                 s.d_in.free(); s.d_out.free()
             if s.d_yuv_in is not None:
                 s.d_yuv_in.free(); s.d_yuv_out.free()
+            if s.d_full is not None:
+                s.d_full.free()
         self.slots = []
 
     def _retire(self, s: _Slot, emit: Callable[[int, np.ndarray], None]):
@@ -218,7 +246,8 @@ class FramePipeline:
         """frames: (global index, HxWx3 uint8 -- or, io_format="i420" / "yuv", a flat payload) pairs owned by this rank;
         emit(index, out) in submission order, `out` in the same format."""
         from ._lib import lib
-        from .yuv import i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_hdr_to_rgb_device, yuv_to_rgb_device
+        from .yuv import (i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_hdr_to_rgb_device, yuv_to_rgb_device,
+                          yuv_to_rgb_scaled_device)
 
         ctx, n, t0 = self.ctx, 0, time.perf_counter()
         self._copy_s = 0.0
@@ -226,43 +255,63 @@ class FramePipeline:
             s.busy, s.indices = False, []
         i420 = self.io_format != "rgb"  # payloads cross the host and PCIe; RGB exists on the device only
         kw = dict(matrix=self.matrix, range=self.yuv_range)
+        oH, oW = self.out_H, self.out_W
+        src_rgb_bytes = self.H * self.W * 3
+
+        def reduce_full(s, m):
+            """scale=: the m source-size frames of s.d_full -> s.d_in, cv2's INTER_AREA, frame by frame on the slot's stream."""
+            for f in range(m):
+                ctx._check(lib.avx_resize_hwc(ctx._h, s.d_full.ptr + f * src_rgb_bytes, 2, self.H, self.W, 3, s.d_in.ptr + f * oH * oW * 3, oH, oW, 3,
+                                              s.stream))
+
         if self.io_format == "yuv":
             def to_rgb(s, m):
                 if self.transfer is not None:
-                    yuv_hdr_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, transfer=self.transfer, range=self.yuv_range,
-                                          tonemap=self.tonemap, peak_nits=self.peak_nits, sdr_white=self.sdr_white, stream=s.stream)
+                    yuv_hdr_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in if self.scale is None else s.d_full, m, self.H, self.W,
+                                          transfer=self.transfer, range=self.yuv_range, tonemap=self.tonemap, peak_nits=self.peak_nits,
+                                          sdr_white=self.sdr_white, stream=s.stream)
+                    if self.scale is not None:
+                        reduce_full(s, m)
+                elif self.scale is not None:
+                    yuv_to_rgb_scaled_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, oH, oW, stream=s.stream, **kw)
                 else:
                     yuv_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
 
             def from_rgb(s, m):
-                rgb_to_yuv_device(ctx, self.pix_fmt, s.d_out, s.d_yuv_out, m, self.H, self.W, stream=s.stream, matrix=self.out_matrix,
+                rgb_to_yuv_device(ctx, self.pix_fmt, s.d_out, s.d_yuv_out, m, oH, oW, stream=s.stream, matrix=self.out_matrix,
                                   range=self.yuv_range)
         else:
             def to_rgb(s, m):
-                i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
+                if self.scale is not None:  # yuv420p is the I420 payload, byte for byte (include/avx.h)
+                    yuv_to_rgb_scaled_device(ctx, "yuv420p", s.d_yuv_in, s.d_in, m, self.H, self.W, oH, oW, stream=s.stream, **kw)
+                else:
+                    i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
 
             def from_rgb(s, m):
-                rgb_to_i420_device(ctx, s.d_out, s.d_yuv_out, m, self.H, self.W, stream=s.stream, **kw)
-        fbytes = int(np.prod(self._io_shape))
-        rgb_bytes = self.H * self.W * 3
+                rgb_to_i420_device(ctx, s.d_out, s.d_yuv_out, m, oH, oW, stream=s.stream, **kw)
+        in_bytes, fbytes = int(np.prod(self._in_shape)), int(np.prod(self._io_shape))
+        rgb_bytes = oH * oW * 3
 
         def submit(s: _Slot):
             """Everything one slot's frames need, in order on the slot's stream."""
             m = len(s.indices)
             if i420:
-                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_yuv_in.ptr, s.h_in.ptr, m * fbytes, s.stream))
+                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_yuv_in.ptr, s.h_in.ptr, m * in_bytes, s.stream))
                 to_rgb(s, m)
+            elif self.scale is not None:
+                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_full.ptr, s.h_in.ptr, m * in_bytes, s.stream))
+                reduce_full(s, m)
             else:
-                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_in.ptr, s.h_in.ptr, m * fbytes, s.stream))
-            self.op.run_device(s.d_in, s.d_out, m, self.H, self.W, stream=s.stream)
+                ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_in.ptr, s.h_in.ptr, m * in_bytes, s.stream))
+            self.op.run_device(s.d_in, s.d_out, m, oH, oW, stream=s.stream)
             if self.split_compare:
                 for f in range(m):
                     o = f * rgb_bytes
-                    ctx._check(lib.avx_split_compose_u8(ctx._h, s.d_left.ptr + o, s.d_out.ptr + o, s.d_out.ptr + o, self.H, self.W, int(self.draw_seam), s.stream))
+                    ctx._check(lib.avx_split_compose_u8(ctx._h, s.d_left.ptr + o, s.d_out.ptr + o, s.d_out.ptr + o, oH, oW, int(self.draw_seam), s.stream))
                     if self.labels[0] is not None or self.labels[1] is not None:
                         from .renderers.labels import draw_split_labels_device
 
-                        draw_split_labels_device(ctx, s.d_out.ptr + o, self.H, self.W, self.labels[0], self.labels[1], s.stream)
+                        draw_split_labels_device(ctx, s.d_out.ptr + o, oH, oW, self.labels[0], self.labels[1], s.stream)
             if i420:
                 from_rgb(s, m)
                 ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_yuv_out.ptr, m * fbytes, s.stream))
@@ -275,8 +324,8 @@ class FramePipeline:
             if s is None:
                 s = self.slots[k % self.depth]
                 self._retire(s, emit)
-            if frame.shape != self._io_shape or frame.dtype != np.uint8:
-                raise ValueError(f"frame {index}: expected uint8 {self._io_shape}, got {frame.dtype} {frame.shape}")
+            if frame.shape != self._in_shape or frame.dtype != np.uint8:
+                raise ValueError(f"frame {index}: expected uint8 {self._in_shape}, got {frame.dtype} {frame.shape}")
             tc = time.perf_counter()
             _pcopy(s.h_in.array[len(s.indices)], frame)
             self._copy_s += time.perf_counter() - tc
@@ -290,7 +339,7 @@ class FramePipeline:
             k += 1
         for j in range(self.depth):  # drain in submission order
             self._retire(self.slots[(k + j) % self.depth], emit)
-        return StreamStats(n, n * self.H * self.W, time.perf_counter() - t0, 1, self._copy_s)
+        return StreamStats(n, n * oH * oW, time.perf_counter() - t0, 1, self._copy_s)  # pixels the op saw
 
 
 def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int = 3, split_compare: bool = False, dist=None,
@@ -308,7 +357,9 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
     over get_yuv() payloads, and the pipeline runs with io_format="i420" in the renderer's `matrix` and `yuv_range`.
     When that renderer names a raw pixel format (`yuv_pix_fmt`: raw video in and out in one format), the pipeline runs with
     io_format="yuv" in that format, and with the renderer's HDR settings (`transfer`, `tonemap`, `peak_nits`, `sdr_white`,
-    `out_matrix`) when it has them.  split_baseline, batch (frames per slot and per op call): see FramePipeline."""
+    `out_matrix`) when it has them.  A renderer with a `scale` hands its payloads over at the source size and the
+    pipeline reduces them as it decodes (FramePipeline scale=); the frames get_image() returns are scaled already.
+    split_baseline, batch (frames per slot and per op call): see FramePipeline."""
     self_sharding = getattr(renderer, "world", 1) == world and getattr(renderer, "rank", 0) == rank and hasattr(renderer, "last_index") and world > 1
     yuv_hw = getattr(renderer, "yuv_hw", None) if callable(getattr(renderer, "get_yuv", None)) else None
     get = renderer.get_yuv if yuv_hw is not None else renderer.get_image
@@ -325,7 +376,8 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
         if fmt and getattr(renderer, "out_matrix", None) is not None:
             hdr["out_matrix"] = renderer.out_matrix
         pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, io_format="yuv" if fmt else "i420",
-                             pix_fmt=fmt, matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline, batch=batch, **hdr)
+                             pix_fmt=fmt, matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline, batch=batch,
+                             scale=getattr(renderer, "scale", None), **hdr)
     else:
         H, W, _ = first.shape
         pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, split_baseline=split_baseline, batch=batch)

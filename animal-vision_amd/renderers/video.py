@@ -24,6 +24,12 @@ the tone-mapped SDR frame of yuv.yuv_hdr_to_rgb (`tonemap`, `peak_nits`, `sdr_wh
 the per-frame species get it too, and every YUV sink is encoded in `out_matrix`: "bt709" by default with a transfer, `matrix`
 without one.
 
+Scaling: `scale=(Wd, Hd)` reduces every source's frames to Wd x Hd (cv2's INTER_AREA; enlarging is refused).
+get_image() returns scaled frames -- raw and .y4m sources through yuv.yuv_to_rgb_scaled, which decodes straight to the scaled
+frame; HDR sources through the HDR decode, then the resize; the other sources through the resize alone.  get_yuv() still hands
+over source-size payloads and `yuv_hw` still names the source size (pipeline.run_video reduces them as it decodes); `out_hw`
+names the size of what comes out, and every sink is written at that size.
+
 Sharded streams (two keywords the reference does not have, both defaulted): with `world` > 1 this renderer
 serves and stores only the frames of rank `rank` (global frame i belongs to rank i mod world) -- every source here is
 index-addressable, so the other ranks' frames are never generated, read or decoded.  Outputs carry the GLOBAL frame
@@ -86,7 +92,7 @@ class VideoRenderer(Renderer):
                  window_name: str = "Video Analysis", rank: int = 0, world: int = 1, matrix: str = "bt601", range: Optional[str] = None,
                  pix_fmt: Optional[str] = None, size: Optional[tuple] = None, write_pix_fmt: Optional[str] = None,
                  transfer: Optional[str] = None, tonemap: str = "mobius", peak_nits: float = 1000.0, sdr_white: float = 203.0,
-                 out_matrix: Optional[str] = None):
+                 out_matrix: Optional[str] = None, scale: Optional[tuple] = None):
         if not (0 <= rank < world):
             raise ValueError(f"rank {rank} outside world {world}")
         if (pix_fmt is None) != (size is None):
@@ -109,9 +115,20 @@ class VideoRenderer(Renderer):
         self.transfer, self.tonemap, self.peak_nits, self.sdr_white, self.out_matrix = transfer, tonemap, float(peak_nits), float(sdr_white), out_matrix
         self.pix_fmt, self.write_pix_fmt = pix_fmt, write_pix_fmt
         self.size = None if size is None else (int(size[0]), int(size[1]))
+        if scale is not None:
+            from ..yuv import check_scale
+
+            try:
+                Wd, Hd = scale
+            except (TypeError, ValueError):
+                raise ValueError(f"scale is (Wd, Hd) (got {scale!r})")
+            # a raw source names its size here; the other sources are checked when their size is known (open(), get_image())
+            check_scale(self.size[1] if self.size else Hd, self.size[0] if self.size else Wd, Hd, Wd)
+            scale = (int(Wd), int(Hd))
+        self.scale = scale
         self._raw = None             # renderers.rawvideo.RawVideoReader
         self._raw_out = None         # renderers.rawvideo.RawVideoWriter (created by the first render)
-        self._merge_size = self.size  # (W, H) of the raw sink's frames, for merge_shards()
+        self._merge_size = self.scale or self.size  # (W, H) of the raw sink's frames, for merge_shards()
         if write_path == "-" and world > 1:
             raise ValueError("stdout is one ordered stream: it can only be written with world = 1")
         self.read_path, self.write_path = read_path, write_path
@@ -145,6 +162,7 @@ class VideoRenderer(Renderer):
 
                 self._y4m = Y4MReader(p, rank=self.rank, world=self.world)
                 self.total_frames = self._y4m.total_frames
+                self._check_scale(self._y4m.header.height, self._y4m.header.width)
             elif p.startswith("synthetic:"):
                 parts = p.split(":")
                 w, h = (int(v) for v in parts[1].lower().split("x"))
@@ -186,6 +204,33 @@ class VideoRenderer(Renderer):
             return None
         return self._y4m.header.height, self._y4m.header.width
 
+    def _check_scale(self, H: int, W: int) -> None:
+        if self.scale is not None:
+            from ..yuv import check_scale
+
+            check_scale(H, W, self.scale[1], self.scale[0])
+
+    @property
+    def out_hw(self) -> Optional[tuple]:
+        """(H, W) of the frames get_image() returns and of everything the sinks are handed: `scale` when it is set, else the
+        source's size when it is known before the first frame (raw and .y4m sources), else None."""
+        if self.scale is not None:
+            return self.scale[1], self.scale[0]
+        if self._raw is not None:
+            return self._raw.height, self._raw.width
+        if self._y4m is not None:
+            return self._y4m.header.height, self._y4m.header.width
+        return None
+
+    def _scaled(self, f: Optional[np.ndarray]) -> Optional[np.ndarray]:
+        """An RGB frame of the source's size reduced to `scale` (INTER_AREA on the device)."""
+        if f is None or self.scale is None:
+            return f
+        self._check_scale(f.shape[0], f.shape[1])
+        if f.shape[:2] == (self.scale[1], self.scale[0]):
+            return f
+        return _resize_area_u8(f, self.scale[0], self.scale[1])
+
     @property
     def yuv_pix_fmt(self) -> Optional[str]:
         """The raw pixel format of the payloads get_yuv() hands over when `yuv_hw` is set; None = I420 (.y4m)."""
@@ -210,24 +255,30 @@ class VideoRenderer(Renderer):
             f = self.get_yuv()
             if f is None:
                 return None
-            from ..yuv import yuv_hdr_to_rgb, yuv_to_rgb
+            from ..yuv import yuv_hdr_to_rgb, yuv_to_rgb, yuv_to_rgb_scaled
 
             if self.transfer is not None:
-                return yuv_hdr_to_rgb(f, self._raw.height, self._raw.width, pix_fmt=self.pix_fmt, transfer=self.transfer, range=self.yuv_range,
-                                      tonemap=self.tonemap, peak_nits=self.peak_nits, sdr_white=self.sdr_white)
+                return self._scaled(yuv_hdr_to_rgb(f, self._raw.height, self._raw.width, pix_fmt=self.pix_fmt, transfer=self.transfer,
+                                                   range=self.yuv_range, tonemap=self.tonemap, peak_nits=self.peak_nits, sdr_white=self.sdr_white))
+            if self.scale is not None:
+                return yuv_to_rgb_scaled(f, self._raw.height, self._raw.width, self.scale[1], self.scale[0], pix_fmt=self.pix_fmt,
+                                         matrix=self.matrix, range=self.yuv_range)
             return yuv_to_rgb(f, self._raw.height, self._raw.width, pix_fmt=self.pix_fmt, matrix=self.matrix, range=self.yuv_range)
         if self._y4m is not None:
             f = self.get_yuv()
             if f is None:
                 return None
-            from ..yuv import i420_to_rgb
+            from ..yuv import i420_to_rgb, yuv_to_rgb_scaled
 
+            if self.scale is not None:  # yuv420p is the I420 payload, byte for byte
+                return yuv_to_rgb_scaled(f, self._y4m.header.height, self._y4m.header.width, self.scale[1], self.scale[0], pix_fmt="yuv420p",
+                                         matrix=self.matrix, range=self.yuv_range)
             return i420_to_rgb(f, self._y4m.header.height, self._y4m.header.width, matrix=self.matrix, range=self.yuv_range)
         if self._src is not None:
             f = self._src.get_image()
             if f is not None:
                 self.last_index = self._src.index
-            return f
+            return self._scaled(f)
         n = len(self._frames) if self._frames is not None else len(self._files)
         if self._i >= n:
             return None
@@ -239,7 +290,7 @@ class VideoRenderer(Renderer):
             f = np.asarray(Image.open(self._files[self._i]).convert("RGB"))
         self.last_index = self._i
         self._i += self.world
-        return f
+        return self._scaled(f)
 
     # ---- sink ------------------------------------------------------------------------------------------
     def _shard_path(self, rank: int) -> str:
@@ -288,7 +339,8 @@ class VideoRenderer(Renderer):
             if self._y4m_out is None and self._y4m is None:
                 raise ValueError("an I420 payload names no frame size: render an RGB frame first, or read from a .y4m")
             hdr = self._y4m_out.header if self._y4m_out is not None else self._y4m.header
-            H, W, payload = hdr.height, hdr.width, frame
+            H, W = (hdr.height, hdr.width) if self._y4m_out is not None or self.scale is None else self.out_hw  # payloads arrive scaled
+            payload = frame
         else:
             raise ValueError(f"a .y4m sink takes RGB uint8 HxWx3 frames or flat uint8 I420 payloads, got {frame.dtype} {frame.shape}")
         if self._y4m_out is None:
@@ -309,7 +361,7 @@ class VideoRenderer(Renderer):
         elif frame.ndim == 1 and frame.dtype == np.uint8:
             if self._raw_out is None and (self._raw is None or self.pix_fmt != self.write_pix_fmt):
                 raise ValueError(f"a {self.write_pix_fmt} payload names no frame size: render an RGB frame first, or read raw video in that format")
-            H, W = (self._raw_out.height, self._raw_out.width) if self._raw_out is not None else (self._raw.height, self._raw.width)
+            H, W = (self._raw_out.height, self._raw_out.width) if self._raw_out is not None else self.out_hw  # payloads arrive scaled
             payload = frame
         else:
             raise ValueError(f"a raw video sink takes RGB uint8 HxWx3 frames or flat uint8 {self.write_pix_fmt} payloads, got {frame.dtype} {frame.shape}")
@@ -376,7 +428,7 @@ class VideoRenderer(Renderer):
         self._src = self._frames = None
         if self._y4m_out is None and self._y4m is not None and is_y4m(self.write_path) and self.write_pix_fmt is None:
             # no frame was rendered: the sink is still a valid (empty) stream, its header at the source's size
-            self._open_y4m_sink(self._y4m.header.height, self._y4m.header.width)
+            self._open_y4m_sink(*self.out_hw)
         if self._y4m_out is not None:
             self._y4m_out.close()
             self._y4m_out = None
@@ -384,7 +436,7 @@ class VideoRenderer(Renderer):
             self._y4m.close()
             self._y4m = None
         if self._raw_out is None and self._raw is not None and self.write_pix_fmt is not None:
-            self._open_raw_sink(self._raw.height, self._raw.width)  # no frame was rendered: an empty file, not a missing one
+            self._open_raw_sink(*self.out_hw)  # no frame was rendered: an empty file, not a missing one
         if self._raw_out is not None:
             self._raw_out.close()
             self._raw_out = None

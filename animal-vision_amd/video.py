@@ -12,6 +12,11 @@ the device as it is decoded (`--tonemap`, `--peak-nits`, `--sdr-w
 
     ffmpeg -i hdr.mkv -f rawvideo -pix_fmt p010le - | python -m animal_vision_amd.video - out.yuv --species Dog --pix-fmt p010le --size 3840x2160 --transfer pq
 
+`--scale WxH` reduces the frames on the device as they are decoded (cv2's INTER_AREA, never enlarging), so that no
+`-vf scale` pass on the CPU is needed and 4K decoder output can run at 1080p; the species and the output have the scaled size:
+
+    ffmpeg -i in.mkv -f rawvideo -pix_fmt nv12 - | python -m animal_vision_amd.video - out.yuv --species HoneyBee --pix-fmt nv12 --size 3840x2160 --scale 1920x1080
+
 `--out-pix-fmt` names the output's format; it defaults to the input's when OUTPUT is "-" or ends in .yuv.  Raw in and raw out in one
 format keep the payload (1.5 B/px for nv12, 3 B/px for p010le) across the host and PCIe (FramePipeline io_format="yuv").
 
@@ -87,14 +92,21 @@ def _batch_arg(text: str) -> int:
     return v
 
 
-def _size_arg(text: str):
-    try:
-        w, h = (int(v) for v in text.lower().split("x"))
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"--size takes WxH, e.g. 3840x2160 (got {text!r})")
-    if w < 1 or h < 1:
-        raise argparse.ArgumentTypeError(f"--size must be positive (got {text!r})")
-    return w, h
+def _wxh_arg(flag: str, example: str):
+    def parse(text: str):
+        try:
+            w, h = (int(v) for v in text.lower().split("x"))
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"{flag} takes WxH, e.g. {example} (got {text!r})")
+        if w < 1 or h < 1:
+            raise argparse.ArgumentTypeError(f"{flag} must be positive (got {text!r})")
+        return w, h
+
+    return parse
+
+
+_size_arg = _wxh_arg("--size", "3840x2160")
+_scale_arg = _wxh_arg("--scale", "1920x1080")
 
 
 class _VideoParser(argparse.ArgumentParser):
@@ -122,6 +134,14 @@ class _VideoParser(argparse.ArgumentParser):
             self.error(f"--peak-nits and --sdr-white must be finite and positive, with --peak-nits above --sdr-white (got {args.peak_nits} and {args.sdr_white})")
         if args.matrix is None or args.transfer is not None:
             args.matrix = "bt601"  # what the SDR conversions use; the HDR decode takes no matrix
+        src = args.size  # the source's size where the command line names it: --size, or a synthetic: input
+        if src is None and args.input.startswith("synthetic:"):
+            try:
+                src = _size_arg(args.input.split(":")[1])
+            except (IndexError, argparse.ArgumentTypeError):
+                src = None
+        if args.scale is not None and src is not None and (args.scale[0] > src[0] or args.scale[1] > src[1]):
+            self.error(f"--scale {args.scale[0]}x{args.scale[1]} enlarges the {src[0]}x{src[1]} source: --scale only reduces")
         return args
 
 
@@ -142,6 +162,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--pix-fmt", default=None, choices=list(AVX_PIX_FMTS), metavar="NAME",
                     help="read INPUT as raw video in this format (ffmpeg's -pix_fmt names: " + ", ".join(AVX_PIX_FMTS) + "); needs --size")
     ap.add_argument("--size", default=None, type=_size_arg, metavar="WxH", help="frame size of the raw input")
+    ap.add_argument("--scale", default=None, type=_scale_arg, metavar="WxH",
+                    help="reduce every frame to this size on the device as it is decoded (INTER_AREA; never enlarges); the species and OUTPUT "
+                         "have this size")
     ap.add_argument("--out-pix-fmt", default=None, choices=list(AVX_PIX_FMTS), metavar="NAME",
                     help="write OUTPUT as raw video in this format (default: --pix-fmt when OUTPUT is '-' or ends in .yuv)")
     ap.add_argument("--transfer", default=None, choices=list(AVX_TRANSFERS),
@@ -173,10 +196,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     def renderer():
         return VideoRenderer(read_path=args.input, write_path=args.output, window_name="AnimalCam", matrix=args.matrix, range=args.range,
                              pix_fmt=args.pix_fmt, size=args.size, write_pix_fmt=args.out_pix_fmt, transfer=args.transfer, tonemap=args.tonemap,
-                             peak_nits=args.peak_nits, sdr_white=args.sdr_white, out_matrix=args.out_matrix)
+                             peak_nits=args.peak_nits, sdr_white=args.sdr_white, out_matrix=args.out_matrix, scale=args.scale)
 
-    vr = renderer()
-    vr.open()
+    try:
+        vr = renderer()
+        vr.open()
+    except ValueError as e:
+        if args.scale is None or "scale" not in str(e):
+            raise
+        raise SystemExit(f"video: --scale {args.scale[0]}x{args.scale[1]}: {e}")  # a .y4m header smaller than --scale
     animal = species_class(args.species)()
     if args.batch > 1 and route(animal) == "frame":  # before any frame is read
         vr.close()
@@ -187,6 +215,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         hw = None if vr.y4m_header is None else (vr.y4m_header.height, vr.y4m_header.width)
         if args.size is not None:
             hw = (args.size[1], args.size[0])
+        if hw is not None and args.scale is not None:
+            hw = (args.scale[1], args.scale[0])  # what the species runs on
         if hw is None:  # synthetic:, .npy or an image directory: peek at the size the stream op is built for, then start over
             first = vr.get_image()
             hw = None if first is None else first.shape[:2]

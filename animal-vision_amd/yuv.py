@@ -1,6 +1,8 @@
 """YUV <-> RGB uint8 on the device, in the style of geometry.py: the I420 pair of the Y4M path (csrc/yuv.hip) and the raw video
 pixel formats -- nv12, p010le, 4:2:2, 4:4:4, gray, 10-bit planar -- of csrc/yuv_raw.hip (PIX_FMTS), and the HDR decode
-of csrc/yuv_hdr.hip: 10-bit BT.2020 PQ / HLG payloads -> tone-mapped SDR RGB (yuv_hdr_to_rgb).
+of csrc/yuv_hdr.hip: 10-bit BT.2020 PQ / HLG payloads -> tone-mapped SDR RGB (yuv_hdr_to_rgb); and the scaled decode
+of csrc/yuv_scale.hip: a raw payload -> RGB at a smaller size in one launch, byte-equal to the decode followed by cv2's INTER_AREA
+resize (yuv_to_rgb_scaled).
 
 The arithmetic (int32 fixed point, 16 fractional bits, BT.601 / BT.709, limited / full range) is defined in DESIGN §4.8; the
 coefficient tables are built by the C entry points from the (matrix, range) names below.  A payload is one frame's Y plane
@@ -253,6 +255,64 @@ def yuv_hdr_to_rgb(buf: np.ndarray, H: int, W: int, *, pix_fmt: str, transfer: s
         yuv_hdr_to_rgb_device(ctx, pix_fmt, d_in, d_out, n, H, W, transfer=transfer, range=range, tonemap=tonemap, peak_nits=peak_nits,
                               sdr_white=sdr_white)
         out = ctx.download(d_out, (n, H, W, 3), np.uint8)
+    finally:
+        d_in.free()
+        d_out.free()
+    return out if batched else out[0]
+
+
+# ---------------------------------------------------------------- scaled decode: YUV -> RGB at a smaller size (csrc/yuv_scale.hip) --
+def check_scale(H: int, W: int, Hd: int, Wd: int) -> None:
+    """The sizes of a scaled decode: an H x W source reduced to Hd x Wd.  Enlarging on either axis (cv2 would switch
+    to INTER_LINEAR there) and non-positive sizes are a ValueError that names both sizes."""
+    try:
+        ok = all(int(v) == v for v in (H, W, Hd, Wd))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"sizes are integers (got {W!r}x{H!r} -> {Wd!r}x{Hd!r})")
+    if H < 1 or W < 1 or Hd < 1 or Wd < 1:
+        raise ValueError(f"sizes must be positive (got {W}x{H} -> {Wd}x{Hd})")
+    if Hd > H or Wd > W:
+        raise ValueError(f"scale {Wd}x{Hd} enlarges the {W}x{H} source: the scaled decode only reduces (INTER_AREA)")
+
+
+def yuv_to_rgb_scaled_device(ctx: Context, pix_fmt: str, d_yuv: DeviceBuffer, d_rgb: DeviceBuffer, n_frames: int, H: int, W: int, Hd: int,
+                             Wd: int, *, matrix: str = "bt601", range: str = "limited", stream=None) -> None:
+    """n_frames payloads of H x W in `pix_fmt` -> n_frames RGB uint8 frames of Hd x Wd, in one launch: byte for byte
+    yuv_to_rgb_device followed by geometry.resize(..., INTER_AREA) per frame."""
+    m, r = _codes(matrix, range)
+    check_scale(H, W, Hd, Wd)
+    if n_frames < 1:
+        raise ValueError(f"bad shape: {n_frames} frames of {H} x {W}")
+    fsz = frame_size(pix_fmt, H, W)
+    if d_rgb.nbytes < n_frames * Hd * Wd * 3 or d_yuv.nbytes < n_frames * fsz:
+        raise ValueError(f"{n_frames} frames of {H} x {W} -> {Hd} x {Wd} need {n_frames * Hd * Wd * 3} RGB and {n_frames * fsz} {pix_fmt} bytes; "
+                         f"the buffers hold {d_rgb.nbytes} and {d_yuv.nbytes}")
+    ctx._check(lib.avx_yuv_to_rgb_scaled_u8(ctx._h, _fmt_code(pix_fmt), d_yuv.ptr, d_rgb.ptr, int(n_frames), int(H), int(W), int(Hd), int(Wd),
+                                            m, r, ctx._s(stream)))
+
+
+def yuv_to_rgb_scaled(buf: np.ndarray, H: int, W: int, Hd: int, Wd: int, *, pix_fmt: str, matrix: str = "bt601", range: str = "limited",
+                      ctx: Optional[Context] = None) -> np.ndarray:
+    """Raw payload(s) of H x W in `pix_fmt` -> RGB uint8 of Hd x Wd, with the payload and batch conventions of yuv_to_rgb: one frame
+    -> (Hd, Wd, 3), or (N, frame_size) -> (N, Hd, Wd, 3)."""
+    _codes(matrix, range)
+    check_scale(H, W, Hd, Wd)
+    fsz = frame_size(pix_fmt, H, W)
+    a = np.ascontiguousarray(buf)
+    if a.dtype != np.uint8:
+        raise TypeError(f"raw video payloads are uint8 (got {a.dtype})")
+    batched = a.ndim == 2 and a.shape[1] == fsz
+    if not batched and a.size != fsz:
+        raise ValueError(f"expected {fsz} bytes per {H}x{W} {pix_fmt} frame (or an (N, {fsz}) batch), got shape {a.shape}")
+    n = a.shape[0] if batched else 1
+    ctx = ctx or get_context()
+    d_in = ctx.upload(a)
+    d_out = ctx.malloc(n * Hd * Wd * 3)
+    try:
+        yuv_to_rgb_scaled_device(ctx, pix_fmt, d_in, d_out, n, H, W, Hd, Wd, matrix=matrix, range=range)
+        out = ctx.download(d_out, (n, Hd, Wd, 3), np.uint8)
     finally:
         d_in.free()
         d_out.free()

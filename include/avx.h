@@ -307,6 +307,20 @@ enum avx_tonemap { AVX_TONEMAP_CLIP = 0, AVX_TONEMAP_MOBIUS = 1 };
 int avx_yuv_hdr_to_rgb_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t* rgb_hwc, int n_frames, int H, int W, int full_range, int transfer,
                           int tonemap, double peak_nits, double sdr_white, void* stream);
 
+/* Scaled decode (csrc/yuv_scale.hip): n_frames payloads of avx_yuv_frame_size(fmt, H, W) bytes -> n_frames frames of
+ * Hd x Wd interleaved RGB uint8 (n_frames * Hd * Wd * 3 bytes), 1 <= Hd <= H, 1 <= Wd <= W, in one launch.  Per frame the result
+ * is, byte for byte,
+ *     avx_resize_hwc(avx_yuv_to_rgb_u8(fmt, frame, H, W, matrix, full_range), dtype = 2 (uint8), C = 3, Hd, Wd, interp = 3 (INTER_AREA))
+ * without the full-size RGB frame ever being written: the decode of avx_yuv_to_rgb_u8 (chroma replicated over its block), then
+ * cv2's INTER_AREA -- when W / Wd and H / Hd are both integers, the integer sum of each isx x isy block per channel, rounded as
+ * (sum + 2) >> 2 for 2 x 2 and as rint(sum * (1.f / (isx * isy))) (half to even) otherwise; for any other ratio the float32
+ * weighted sums of avx_resize_hwc's general path, with its tables, in its order.  Hd == H and Wd == W gives avx_yuv_to_rgb_u8's
+ * frame.  AVX_ERR_INVALID (avx_last_error starts with the function's name) for a bad format, matrix, range or size, Hd > H or
+ * Wd > W (enlarging is not supported), an integer-ratio block of more than 65536 samples, NULL or overlapping buffers, and an odd
+ * payload address with a 16-bit format. */
+int avx_yuv_to_rgb_scaled_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t* rgb_hwc, int n_frames, int H, int W, int Hd, int Wd, int matrix,
+                             int full_range, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

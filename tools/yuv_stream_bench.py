@@ -5,16 +5,21 @@
       frames cycled, converted beforehand, so no disk or decode bounds it): io_format="rgb" and "i420" alternately, `reps`
       times each after one warm-up run each.  One JSON line per run: frames/s and host_copy_s.  With --pix-fmt the runs are
       io_format="i420" (the baseline) and io_format="yuv" in every named raw format instead.
-  python tools/yuv_stream_bench.py kernels [--iters 20] [--pix-fmt NAME ...]
+  python tools/yuv_stream_bench.py kernels [--iters 20] [--pix-fmt NAME ...] [--transfer NAME ...] [--scale WxH]
       8-frame 4K batches through avx_i420_to_rgb_u8 and avx_rgb_to_i420_u8, for `rocprofv3 --kernel-trace --stats` to time; with
       --pix-fmt, also through avx_yuv_to_rgb_u8 and avx_rgb_to_yuv_u8 in every named format, in the same process; with
       --transfer pq hlg, every named 10-bit format also goes through avx_yuv_hdr_to_rgb_u8 with each transfer (the HDR decode of
-      §4.10), beside the SDR decode of the same payload.
+      §4.10), beside the SDR decode of the same payload; with --scale WxH, every named format also goes through the scaled decode
+      of §4.11 (avx_yuv_to_rgb_scaled_u8, one launch per batch) and, in the same process, through the chain it replaces:
+      avx_yuv_to_rgb_u8 on the batch, then one avx_resize_hwc (uint8, INTER_AREA) per frame.  One JSON line per format carries
+      both as timed with stream events around the `iters` repetitions (launch gaps included).
   python tools/yuv_stream_bench.py report STATS_CSV [--transfer NAME ...]
       The kernels' mean time per 4K frame from rocprofv3's kernel_stats.csv, and its share of 6.29 TB/s (the measured HBM copy
       rate, MI355X) for the bytes each direction moves: the format's B/px plus 3 B/px of RGB.  An HDR decode kernel's line also
       carries its transfer and its time over the SDR decode kernel's of the same format in the same run (both move the same
-      bytes, so the ratio is arithmetic); --transfer keeps only the named transfers' HDR lines."""
+      bytes, so the ratio is arithmetic); --transfer keeps only the named transfers' HDR lines.  A scaled decode kernel's line
+      carries its time per 4K source frame, the chain's in the same run (the plain decode kernel of the format plus the uint8
+      INTER_AREA resize kernel, kernel time only) and chain / fused."""
 import argparse
 import csv
 import json
@@ -70,7 +75,8 @@ def stream(args):
 def kernels(args):
     from animal_vision_amd.runtime import get_context
     from animal_vision_amd.yuv import (HDR_PIX_FMTS, frame_size, i420_size, i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device,
-                                       yuv_hdr_to_rgb_device, yuv_to_rgb_device)
+                                       yuv_hdr_to_rgb_device, yuv_to_rgb_device, yuv_to_rgb_scaled_device)
+    from animal_vision_amd.geometry import INTER_AREA, resize_device
 
     ctx = get_context()
     n = 8
@@ -88,6 +94,32 @@ def kernels(args):
         for tr in (args.transfer or []) if p in HDR_PIX_FMTS else []:  # the same payload, read as HDR: the same bytes in and out
             for _ in range(args.iters):
                 yuv_hdr_to_rgb_device(ctx, p, d_raw, d_rgb2, n, H, W, transfer=tr)
+        if args.scale:
+            Wd, Hd = args.scale
+            d_small = ctx.malloc(n * Hd * Wd * 3)
+            small = [d_small.view(f * Hd * Wd * 3, Hd * Wd * 3) for f in range(n)]
+            full = [d_rgb2.view(f * H * W * 3, H * W * 3) for f in range(n)]
+
+            def fused():
+                yuv_to_rgb_scaled_device(ctx, p, d_raw, d_small, n, H, W, Hd, Wd)
+
+            def chain():
+                yuv_to_rgb_device(ctx, p, d_raw, d_rgb2, n, H, W)
+                for f in range(n):
+                    resize_device(ctx, full[f], np.uint8, H, W, 3, Hd, Wd, INTER_AREA, small[f])
+
+            ms = {}
+            for name, fn in (("fused", fused), ("chain", chain)):
+                fn()  # the first call of a geometry builds and uploads its tables
+                ctx.sync()
+                ctx.timer_start()
+                for _ in range(args.iters):
+                    fn()
+                ms[name] = ctx.timer_stop()
+            us = {k: v * 1e3 / (args.iters * n) for k, v in ms.items()}
+            print(json.dumps({"scaled_decode": p, "scale": f"{Wd}x{Hd}", "batch": n, "iters": args.iters, "fused_us_per_4k_frame": round(us["fused"], 2),
+                              "chain_us_per_4k_frame": round(us["chain"], 2), "chain_over_fused": round(us["chain"] / us["fused"], 2)}), flush=True)
+            d_small.free()
         ctx.sync()
         d_raw.free()
     ctx.sync()
@@ -118,9 +150,12 @@ def report(args):
     from animal_vision_amd.yuv import frame_size
 
     rows = []
+    resize_us = None  # the uint8 INTER_AREA resize kernel: one call per frame, whatever the format
     with open(args.csv) as f:
         for row in csv.DictReader(f):
             name = row.get("Name") or row.get("KernelName") or ""
+            if re.search(r"k_resize_area(_fast)?_f32<unsigned char>", name):
+                resize_us = float(row.get("AverageNs") or row.get("Average") or 0.0) / 1e3
             fmt = "yuv420p" if "i420" in name else _raw_fmt_of(name)
             if fmt is None:
                 continue
@@ -129,8 +164,18 @@ def report(args):
             avg_ns = float(row.get("AverageNs") or row.get("Average") or 0.0)
             rows.append({"kernel": kernel.group(0) if kernel else name, "pix_fmt": "i420" if "i420" in name else fmt,
                          "transfer": _TRANSFER.get(int(hdr.group(1))) if hdr else None, "calls": int(row.get("Calls", 0)), "us": avg_ns / 1e3 / 8})
-    sdr = {r["pix_fmt"]: r["us"] for r in rows if r["transfer"] is None and "_to_rgb" in r["kernel"] and r["pix_fmt"] != "i420"}
+    scaled = ("k_yuv420_to_rgb_half_vec", "k_yuv_to_rgb_area_int", "k_yuv_to_rgb_area_gen")  # csrc/yuv_scale.hip
+    sdr = {r["pix_fmt"]: r["us"] for r in rows
+           if r["transfer"] is None and "_to_rgb" in r["kernel"] and r["pix_fmt"] != "i420" and r["kernel"] not in scaled}
     for r in rows:
+        if r["kernel"] in scaled:  # beside the chain it replaces: the format's plain decode kernel + the resize kernel of the same run
+            out = {"kernel": r["kernel"], "pix_fmt": r["pix_fmt"], "calls": r["calls"], "us_per_4k_frame": round(r["us"], 2)}
+            if r["pix_fmt"] in sdr and resize_us is not None:
+                chain = sdr[r["pix_fmt"]] + resize_us
+                out.update(chain_decode_us=round(sdr[r["pix_fmt"]], 2), chain_resize_us=round(resize_us, 2), chain_us_per_4k_frame=round(chain, 2),
+                           chain_over_fused=round(chain / r["us"], 2))
+            print(json.dumps(out))
+            continue
         if r["transfer"] is not None and args.transfer and r["transfer"] not in args.transfer:
             continue
         fmt, us = "yuv420p" if r["pix_fmt"] == "i420" else r["pix_fmt"], r["us"]
@@ -156,6 +201,8 @@ def main():
     k.add_argument("--iters", type=int, default=20)
     k.add_argument("--pix-fmt", nargs="+", default=None, help="raw formats to run through the avx_yuv_to_rgb_u8 / avx_rgb_to_yuv_u8 kernels too")
     k.add_argument("--transfer", nargs="+", default=None, choices=["pq", "hlg"], help="also run the HDR decode of every named 10-bit format with these transfers")
+    k.add_argument("--scale", default=None, type=lambda t: tuple(int(v) for v in t.lower().split("x")), metavar="WxH",
+                   help="also run the scaled decode of every named format to this size, beside avx_yuv_to_rgb_u8 + avx_resize_hwc per frame")
     r = sub.add_parser("report")
     r.add_argument("csv")
     r.add_argument("--transfer", nargs="+", default=None, choices=["pq", "hlg"], help="keep only these transfers' HDR kernels")

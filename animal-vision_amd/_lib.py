@@ -269,6 +269,7 @@ _SIGS = {
     "avx_streak_planes_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "avx_rgb_to_hsi_lobes": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_float, _vp, _vp]),
     "avx_honeybee_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(HoneybeeDesc), _vp, _vp]),
+    "avx_catch_planes_up": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, ctypes.POINTER(ctypes.c_int), _vp]),
     "avx_uv_front_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "avx_uv_front_u8_batch": (_i, [_vp, _vp, _i, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     "avx_panorama_warp_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

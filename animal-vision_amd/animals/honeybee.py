@@ -61,7 +61,8 @@ class HoneyBee(Animal):
             return image, self._visualize_staged(image, floats=True)
         op = self._operator()
         if self.hsi_model is not None:
-            out = self.hsi_model.honeybee(image, op)
+            down = self.hsi_downsample and 0.05 <= self.hsi_scale < 1.0  # the network at reduced size, its catches enlarged (ml/predict.py)
+            out = self.hsi_model.honeybee(image, op, hsi_scale=self.hsi_scale if down else None)
         elif self.hsi_downsample and 0.05 <= self.hsi_scale < 1.0:
             out = self._visualize_staged(image, floats=False)
         else:

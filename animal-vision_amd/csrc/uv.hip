@@ -20,6 +20,9 @@
 
 using namespace avxk;
 
+// geom.hip: the INTER_LINEAR tables of an h x w -> H x W resize out of the stream workspace's table cache (TableCache::lin)
+int avx_geom_linear_tables(avx_ctx* ctx, avx_ws* ws, hipStream_t s, int H, int W, int Hd, int Wd, avx_lin_tab* ax, avx_lin_tab* ay);
+
 namespace {
 
 constexpr int kT = 256;
@@ -261,6 +264,70 @@ __global__ __launch_bounds__(kT) void k_plane_stats(const float* __restrict__ pl
         for (int k = 0; k < KMAX; ++k)
             if (k < K) { const float v = planes[(size_t)k * n + p]; mn[k] = fminf(mn[k], v); mx[k] = fmaxf(mx[k], v); sm[k] += (double)v; }
     block_stats_store<KMAX>(mn, mx, sm, K, partials);
+}
+
+// ---- three catch planes held at reduced size h x w -> H x W (cv2 INTER_LINEAR of a float32 plane: k_resize_linear_f32 with C = 1,
+//      value for value, through stack_lerp) and the statistics of the enlarged planes, in one pass: what avx_honeybee_u8 source 2 takes.
+// A thread produces runs of 4 destination pixels of one row for all three planes: the row's b0 / b1 and each pixel's source column and
+// a0 / a1 are formed once and shared by the planes.  Persistent grid-stride; the source planes (1/4 .. 1/100 of the frame) stay in cache,
+// the 12 B/px written are the traffic.  VEC (W % 4 == 0, planes_out 16-byte aligned): table rows and results as 16-byte accesses.
+template <bool VEC>
+__global__ __launch_bounds__(kT) void k_catch_planes_up(const float* __restrict__ src, int h, int w, float* __restrict__ dst, int H, int W, avx_lin_tab ax,
+                                                        avx_lin_tab ay, Stat3* partials) {
+    float mn[3], mx[3];
+    double sm[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { mn[k] = 3.4e38f; mx[k] = -3.4e38f; sm[k] = 0.0; }
+    const unsigned rpr = ((unsigned)W + 3u) >> 2, units = (unsigned)H * rpr;  // runs per row; the host checks H * (W + 3) < 2^31
+    const size_t ns = (size_t)h * w, nd = (size_t)H * W;
+    for (unsigned u = blockIdx.x * kT + threadIdx.x; u < units; u += gridDim.x * kT) {
+        const unsigned y = u / rpr;
+        const int x0 = (int)(u - y * rpr) * 4;
+        const int cnt = VEC ? 4 : (W - x0 < 4 ? W - x0 : 4);
+        const int sy0 = ay.ofs[y], sy1 = sy0 + 1 < h ? sy0 + 1 : sy0;
+        const float b1 = ay.f[y], b0 = 1.f - b1;
+        const float* R0 = src + (size_t)sy0 * w;
+        const float* R1 = src + (size_t)sy1 * w;
+        int sx[4];
+        float a1[4];
+        if (VEC) {
+            const int4 o4 = *reinterpret_cast<const int4*>(ax.ofs + x0);
+            const float4 f4 = *reinterpret_cast<const float4*>(ax.f + x0);
+            sx[0] = o4.x; sx[1] = o4.y; sx[2] = o4.z; sx[3] = o4.w;
+            a1[0] = f4.x; a1[1] = f4.y; a1[2] = f4.z; a1[3] = f4.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int x = i < cnt ? x0 + i : W - 1;  // past the row's end: its last pixel again (neither stored nor counted)
+                sx[i] = ax.ofs[x]; a1[i] = ax.f[x];
+            }
+        }
+        float v[3][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float a0 = 1.f - a1[i];
+            const bool inner = (i < cnt ? x0 + i : W - 1) < ax.dmax;
+            const int o = inner ? 1 : 0;  // the right-hand neighbour is only read where cv2 reads it
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float* S0 = R0 + (size_t)k * ns + sx[i];
+                const float* S1 = R1 + (size_t)k * ns + sx[i];
+                v[k][i] = stack_lerp(S0[0], S0[o], S1[0], S1[o], a0, a1[i], b0, b1, inner);  // stack_up.h: the one statement of this arithmetic
+                if (i < cnt) { mn[k] = fminf(mn[k], v[k][i]); mx[k] = fmaxf(mx[k], v[k][i]); sm[k] += (double)v[k][i]; }
+            }
+        }
+        float* D = dst + (size_t)y * W + x0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (VEC) *reinterpret_cast<float4*>(D + (size_t)k * nd) = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
+            else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (i < cnt) D[(size_t)k * nd + i] = v[k][i];
+            }
+        }
+    }
+    block_stats_store<3>(mn, mx, sm, 3, partials);
 }
 
 // Final reduction (one block) -> stats[k] = {min, max, mean, denominator}; the denominator is what the
@@ -1756,6 +1823,38 @@ int avx_plane_stats(avx_ctx* ctx, const float* planes, int K, size_t n, int adap
         AVX_HIP(ctx, hipMemcpyAsync(stats_host, u.stats, sizeof(float4) * K, hipMemcpyDeviceToHost, s));
         AVX_HIP(ctx, hipStreamSynchronize(s));
     }
+    return AVX_OK;
+}
+
+// Catch planes formed at reduced size -> frame size, with the statistics avx_honeybee_u8 source 2 reads; see include/avx.h.
+int avx_catch_planes_up(avx_ctx* ctx, const float* planes_small, int h, int w, float* planes_out, int H, int W, void* partials_out, int* n_partials,
+                        void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, planes_small && planes_out && partials_out && n_partials, "avx_catch_planes_up: NULL pointer");
+    AVX_REQUIRE(ctx, h > 0 && w > 0 && H > 0 && W > 0, "avx_catch_planes_up: sizes must be positive (got %d x %d -> %d x %d)", h, w, H, W);
+    AVX_REQUIRE(ctx, h <= H && w <= W, "avx_catch_planes_up: %d x %d -> %d x %d reduces: the planes are only enlarged", h, w, H, W);
+    AVX_REQUIRE(ctx, (size_t)H * ((size_t)W + 3) < ((size_t)1 << 31), "avx_catch_planes_up: destination larger than 2^31 pixels");
+    AVX_REQUIRE(ctx, (((uintptr_t)partials_out) & 15u) == 0, "avx_catch_planes_up: partials_out must be 16-byte aligned");
+    const int g = grid_for(ctx, ((size_t)W + 3) / 4 * (size_t)H);  // <= 8 per CU: source 2's limit on the records
+    {
+        const uintptr_t a0 = (uintptr_t)planes_small, a1 = a0 + sizeof(float) * 3 * (size_t)h * w;
+        const uintptr_t b0 = (uintptr_t)planes_out, b1 = b0 + sizeof(float) * 3 * (size_t)H * W;
+        const uintptr_t c0 = (uintptr_t)partials_out, c1 = c0 + sizeof(Stat3) * 3 * (size_t)g;
+        AVX_REQUIRE(ctx, (a1 <= b0 || b1 <= a0) && (a1 <= c0 || c1 <= a0) && (b1 <= c0 || c1 <= b0), "avx_catch_planes_up: overlapping buffers");
+    }
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    avx_ws* ws = avx_workspace(ctx, s);
+    if (!ws) return AVX_ERR_NOMEM;
+    avx_lin_tab ax{}, ay{};
+    int rc = avx_geom_linear_tables(ctx, ws, s, h, w, H, W, &ax, &ay);  // TableCache::lin: the tables avx_resize_hwc runs with
+    if (rc) return rc;
+    if ((W & 3) == 0 && (((uintptr_t)planes_out) & 15u) == 0)
+        hipLaunchKernelGGL(k_catch_planes_up<true>, dim3(g), dim3(kT), 0, s, planes_small, h, w, planes_out, H, W, ax, ay, (Stat3*)partials_out);
+    else
+        hipLaunchKernelGGL(k_catch_planes_up<false>, dim3(g), dim3(kT), 0, s, planes_small, h, w, planes_out, H, W, ax, ay, (Stat3*)partials_out);
+    AVX_HIP(ctx, hipGetLastError());
+    *n_partials = g;
     return AVX_OK;
 }
 

@@ -268,6 +268,21 @@ class HoneybeeOp:
         op.desc = d
         return op
 
+    def catch_clone(self) -> "HoneybeeOp":
+        """The same tail fed the three catch planes themselves as a 3-band cube with identity weights (run_device(hsi_ptr=planes,
+        hsi_layout=1): source 1 then integrates each plane into itself): for catches formed upstream under a configuration
+        takes_catches() excludes."""
+        import copy
+
+        op = copy.copy(self)
+        op.weights = np.eye(3, dtype=np.float32)
+        d = HoneybeeDesc()
+        ctypes.memmove(ctypes.byref(d), ctypes.byref(self.desc), ctypes.sizeof(HoneybeeDesc))
+        d.bands = 3
+        d.weights_host = _fptr(op.weights)
+        op.desc = d
+        return op
+
     max_batch = 16  # frames one run_device call takes from a pipeline slot (pipeline.FramePipeline(batch=))
 
     def run_device(self, d_in: Optional[DeviceBuffer], d_out: DeviceBuffer, n_frames: int, H: int, W: int, *, hsi_ptr: int = 0,

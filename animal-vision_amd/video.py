@@ -17,25 +17,34 @@ the device as it is decoded (`--tonemap`, `--peak-nits`, `--sdr-w
 
     ffmpeg -i in.mkv -f rawvideo -pix_fmt nv12 - | python -m animal_vision_amd.video - out.yuv --species HoneyBee --pix-fmt nv12 --size 3840x2160 --scale 1920x1080
 
+`--hsi-model seeded|PATH` (HoneyBee only) takes the 31-band cube from the MST++ network instead of the analytic lobes (DESIGN §4.3);
+`--hsi-scale S` (HoneyBee only, 0.05 <= S < 1) runs that conversion on the frame reduced by S and enlarges the three cone catches back
+(HoneyBee(hsi_downsample=True, hsi_scale=S); with the network: DESIGN §4.12).  No checkpoint ships with the package: PATH is a local
+.pth of the reference's MST++ training code, and `seeded` (random weights from a fixed seed) is for testing:
+
+    python -m animal_vision_amd.video in.y4m out.y4m --species HoneyBee --hsi-model mst_plus_plus.pth --hsi-scale 0.5
+
 `--out-pix-fmt` names the output's format; it defaults to the input's when OUTPUT is "-" or ends in .yuv.  Raw in and raw out in one
 format keep the payload (1.5 B/px for nv12, 3 B/px for p010le) across the host and PCIe (FramePipeline io_format="yuv").
 
 INPUT and OUTPUT are a .y4m file, "-" (stdin / stdout, Y4M), or the other forms renderers.VideoRenderer takes (synthetic:,
 .npy, an image directory).  Species are the display names of gallery.py's registry.  Routing:
-  * the dichromats but Cat (DichromatOp), HoneyBee (HoneybeeOp) and the plane-program UV species with a fixed plan
-    (SpeciesStreamOp) stream through pipeline.run_video: `--depth` frames in flight, split-compose and labels on the device
+  * the dichromats but Cat (DichromatOp), HoneyBee (HoneybeeOp; with --hsi-model: ml.MstHoneybeeStreamOp) and the plane-program UV
+    species with a fixed plan (SpeciesStreamOp) stream through pipeline.run_video: `--depth` frames in flight, split-compose and labels on the device
     (against each species' own baseline, as visualize() returns it: the plane-program species' is their panorama-warped
     input), and, from a .y4m to a .y4m, I420 across the host and PCIe (FramePipeline io_format="i420");
-  * every other species (Cat, whose baseline is the zoomed frame; MantisShrimp; RatUV, whose plan depends on the frame) runs
+  * every other species (Cat, whose baseline is the zoomed frame; MantisShrimp; RatUV, whose plan depends on the frame; HoneyBee
+    with --hsi-scale and no --hsi-model) runs
     visualize() per frame, and the split frame is composed from visualize's own (baseline, out) pair, as the reference does.
 
 `--batch N` (1..16) puts N frames into every pipeline slot: the plane-program species then run their launch chain once per N
 frames (planevm.DeviceBackend(frames=N): the frame is a grid dimension of the kernels), the dichromats and HoneyBee hand their
-kernels n_frames = N.  The species of the per-frame loop have no batched form: for them `--batch` above 1 is an error."""
+kernels n_frames = N (with --hsi-model the network still runs frame by frame on the slot's stream).  The species of the per-frame loop have no batched form: for them `--batch` above 1 is an error."""
 from __future__ import annotations
 
 import argparse
 import math
+import os
 import sys
 import time
 from typing import Optional, Sequence
@@ -48,8 +57,22 @@ from .gallery import _CLASS_NAMES, ensure_rgb_uint8, species_class
 SPECIES_NAMES = list(_CLASS_NAMES)  # all 36 display names
 
 
+def make_animal(args):
+    """The species the parsed command line names, configured by its flags (--hsi-model, --hsi-scale: HoneyBee)."""
+    cls = species_class(args.species)
+    kw = {}
+    if getattr(args, "hsi_scale", None) is not None:
+        kw.update(hsi_downsample=True, hsi_scale=args.hsi_scale)
+    if getattr(args, "hsi_model", None) is not None:
+        from .ml import MSTPlusPlusPredictor
+
+        kw["hsi_model"] = MSTPlusPlusPredictor(None if args.hsi_model == "seeded" else args.hsi_model, seed=0, half=True)
+    return cls(**kw)
+
+
 def route(animal) -> str:
-    """How the command runs `animal`: "dichromat" / "honeybee" / "plane" stream through run_video, "frame" runs visualize() per frame."""
+    """How the command runs `animal`: "dichromat" / "honeybee" / "honeybee_mst" / "plane" stream through run_video, "frame" runs
+    visualize() per frame."""
     from .animals import Cat, HoneyBee
     from .animals._dichromats import _Dichromat
     from .animals._uv_species import UVSpecies
@@ -57,7 +80,9 @@ def route(animal) -> str:
 
     if isinstance(animal, _Dichromat) and not isinstance(animal, Cat):
         return "dichromat"
-    if isinstance(animal, HoneyBee) and animal.hsi_model is None and not animal.hsi_downsample:
+    if isinstance(animal, HoneyBee) and animal.hsi_model is not None:
+        return "honeybee_mst"
+    if isinstance(animal, HoneyBee) and not animal.hsi_downsample:
         return "honeybee"
     if isinstance(animal, UVSpecies) and not isinstance(animal, RatUV):
         return "plane"
@@ -71,6 +96,11 @@ def stream_op(animal, H: int, W: int, depth: int, batch: int = 1):
     kind = route(animal)
     if kind in ("dichromat", "honeybee"):
         return animal._operator()
+    if kind == "honeybee_mst":  # the network per frame on the slot's stream; ValueError when hsi_scale leaves too small a frame
+        from .ml import MstHoneybeeStreamOp
+
+        down = animal.hsi_downsample and 0.05 <= animal.hsi_scale < 1.0
+        return MstHoneybeeStreamOp(animal.hsi_model, animal._operator(), H, W, depth=depth, hsi_scale=animal.hsi_scale if down else None, batch=batch)
     if kind == "plane":
         from .animals._uv_species import SpeciesStreamOp
 
@@ -89,6 +119,16 @@ def _batch_arg(text: str) -> int:
         raise argparse.ArgumentTypeError(f"--batch takes an integer (got {text!r})")
     if not 1 <= v <= AVX_EW_MAX_FRAMES:
         raise argparse.ArgumentTypeError(f"--batch must be 1..{AVX_EW_MAX_FRAMES} (got {v})")
+    return v
+
+
+def _hsi_scale_arg(text: str) -> float:
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--hsi-scale takes a number (got {text!r})")
+    if not 0.05 <= v < 1.0:  # HoneyBee's own range (honeybee.py:109): outside it the flag would be ignored
+        raise argparse.ArgumentTypeError(f"--hsi-scale must be at least 0.05 and below 1 (got {text!r})")
     return v
 
 
@@ -114,6 +154,11 @@ class _VideoParser(argparse.ArgumentParser):
 
     def parse_args(self, args=None, namespace=None):
         args = super().parse_args(args, namespace)
+        for flag, v in (("--hsi-model", args.hsi_model), ("--hsi-scale", args.hsi_scale)):
+            if v is not None and args.species != "HoneyBee":
+                self.error(f"{flag} configures HoneyBee's RGB-to-spectrum conversion: --species {args.species} has none")
+        if args.hsi_model not in (None, "seeded") and not os.path.isfile(args.hsi_model):
+            self.error(f"--hsi-model {args.hsi_model}: no such file (a local .pth checkpoint, or 'seeded')")
         if args.transfer is not None:
             from .yuv import HDR_PIX_FMTS
 
@@ -165,6 +210,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--scale", default=None, type=_scale_arg, metavar="WxH",
                     help="reduce every frame to this size on the device as it is decoded (INTER_AREA; never enlarges); the species and OUTPUT "
                          "have this size")
+    ap.add_argument("--hsi-model", default=None, metavar="seeded|PATH",
+                    help="HoneyBee only: take the 31-band cube from the MST++ network instead of the analytic lobes.  PATH is a local .pth "
+                         "checkpoint of the reference's MST++ (its state_dict / module. form); no checkpoint ships with this package, and "
+                         "'seeded' (random weights from a fixed seed) is for testing")
+    ap.add_argument("--hsi-scale", default=None, type=_hsi_scale_arg, metavar="S",
+                    help="HoneyBee only, 0.05 <= S < 1: convert RGB to spectrum on the frame reduced by S and enlarge the three cone catches "
+                         "(hsi_downsample).  With --hsi-model the network runs at the reduced size: a stated quality-for-speed choice")
     ap.add_argument("--out-pix-fmt", default=None, choices=list(AVX_PIX_FMTS), metavar="NAME",
                     help="write OUTPUT as raw video in this format (default: --pix-fmt when OUTPUT is '-' or ends in .yuv)")
     ap.add_argument("--transfer", default=None, choices=list(AVX_TRANSFERS),
@@ -205,7 +257,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if args.scale is None or "scale" not in str(e):
             raise
         raise SystemExit(f"video: --scale {args.scale[0]}x{args.scale[1]}: {e}")  # a .y4m header smaller than --scale
-    animal = species_class(args.species)()
+    animal = make_animal(args)
     if args.batch > 1 and route(animal) == "frame":  # before any frame is read
         vr.close()
         raise SystemExit(f"video: --batch {args.batch}: {args.species} runs visualize() per frame and has no batched form")
@@ -223,7 +275,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             vr.close()
             vr = renderer()
             vr.open()
-        op = None if hw is None else stream_op(animal, hw[0], hw[1], args.depth, args.batch)
+        try:
+            op = None if hw is None else stream_op(animal, hw[0], hw[1], args.depth, args.batch)
+        except ValueError as e:
+            if args.hsi_scale is None or "hsi_scale" not in str(e):
+                raise
+            raise SystemExit(f"video: --hsi-scale {args.hsi_scale:g}: {e}")  # the reduced frame is too small for the network
         if op is not None:
             try:
                 # the split frame's left half is visualize()'s baseline: the input for the dichromats and HoneyBee, the

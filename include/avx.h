@@ -209,6 +209,16 @@ typedef struct avx_honeybee_desc {
 int avx_honeybee_u8(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_hwc, int n_frames, int H, int W,
                     const avx_honeybee_desc* desc, float* debug_planes, void* stream);
 
+/* The three catch planes formed at reduced size (planes_small: 3 x h*w float32, device) enlarged to the frame (planes_out: 3 x H*W),
+ * h <= H and w <= W, with the statistics of the enlarged planes, in one launch (HoneyBee(hsi_model=, hsi_downsample=True)).
+ * Plane k of planes_out is, bit for bit, avx_resize_hwc(plane k, dtype 0, h, w, C = 1, out, H, W, interp 1): cv2's float32 INTER_LINEAR
+ * with the same tables (h == H and w == W: that resize's values, the plane itself).  partials_out (device, 16-byte aligned, room for
+ * 8 x CUs x 3 records of 16 bytes) receives *n_partials x 3 records {float min, max; double sum}, one triple per workgroup, no atomics:
+ * feed planes_out and them to avx_honeybee_u8 (source 2).  AVX_ERR_INVALID (avx_last_error starts with the function's name) for NULL
+ * pointers, non-positive sizes, h > H or w > W, overlapping buffers and a misaligned partials_out. */
+int avx_catch_planes_up(avx_ctx* ctx, const float* planes_small, int h, int w, float* planes_out, int H, int W, void* partials_out, int* n_partials,
+                        void* stream);
+
 /* ---- geometric resampling: cv2.resize / cv2.remap / cv2.Sobel call sites ----------------
  * OpenCV semantics restated from its published algorithm (OpenCV is not available to pin against). */
 

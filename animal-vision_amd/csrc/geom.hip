@@ -8,6 +8,7 @@
 // UNPINNED); plain float arithmetic in source order (-ffp-contract=off): bit-exact with the oracle.
 // Coefficient tables are O(W + H) and built on the host inside the entry points.
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <vector>
 
@@ -140,8 +141,16 @@ __global__ __launch_bounds__(kGT) void k_any_gt1(const uint8_t* __restrict__ in,
 struct WarpArgs { const uint8_t* in; float* out; int H, W, Ho, Wo; const float* xL; const float* xR; const float* ymap; const float* wL; const float* wR;
                   const uint32_t* flag; };
 
+// cvRound(v * 32) of a remap coordinate as x86 cv2 computes it: NaN and products outside int32 convert to INT_MIN, which the
+// saturation to short below turns into column / row -32768, so the pixel takes the border value.  (__float2int_rn alone
+// saturates +-inf and +-1e30 the same way but turns NaN into 0, which samples pixel (0, 0).)
+__device__ __forceinline__ int remap_round(float v) {
+    const float q = v * 32.f;
+    return (q >= -2147483648.f && q < 2147483648.f) ? __float2int_rn(q) : INT_MIN;
+}
+
 __device__ __forceinline__ void remap_px(const uint8_t* in, int H, int W, float mx, float my, float norm, float (&o)[3]) {
-    const int fx = __float2int_rn(mx * 32.f), fy = __float2int_rn(my * 32.f);
+    const int fx = remap_round(mx), fy = remap_round(my);
     int sx = fx >> 5, sy = fy >> 5;
     sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);
     sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
@@ -184,7 +193,7 @@ __global__ __launch_bounds__(kGT) void k_remap_planes(const float* __restrict__ 
                                                       float* __restrict__ dst, float border) {
     const size_t n = (size_t)H * W;
     for (size_t i = (size_t)blockIdx.x * kGT + threadIdx.x; i < n; i += (size_t)gridDim.x * kGT) {
-        const int fx = __float2int_rn(mapx[i] * 32.f), fy = __float2int_rn(mapy[i] * 32.f);
+        const int fx = remap_round(mapx[i]), fy = remap_round(mapy[i]);
         int sx = fx >> 5, sy = fy >> 5;
         sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);
         sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);

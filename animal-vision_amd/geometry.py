@@ -149,3 +149,26 @@ def sobel3(plane: np.ndarray, ctx: Optional[Context] = None):
         d_in.free()
         d_g.free()
     return g[0], g[1]
+
+
+def remap_linear_planes(planes: np.ndarray, mapx: np.ndarray, mapy: np.ndarray, border_value: float = 0.0, ctx: Optional[Context] = None) -> np.ndarray:
+    """cv2.remap(plane, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, border_value) of each of K float32 planes (K x H x W, or one
+    H x W plane) with per-pixel float32 maps that the planes share."""
+    ctx = ctx or get_context()
+    a = np.ascontiguousarray(planes, np.float32)
+    single = a.ndim == 2
+    a = a[None] if single else a
+    K, H, W = a.shape
+    mx, my = np.ascontiguousarray(mapx, np.float32), np.ascontiguousarray(mapy, np.float32)
+    assert mx.shape == (H, W) and my.shape == (H, W), "maps are H x W, the size of the planes"
+    bufs = []
+    try:
+        for h in (a, mx, my):
+            bufs.append(ctx.upload(h))
+        bufs.append(ctx.malloc(a.nbytes))
+        ctx._check(lib.avx_remap_linear_planes(ctx._h, bufs[0].ptr, K, H, W, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, float(border_value), ctx.stream))
+        out = ctx.download(bufs[3], (K, H, W), np.float32)
+    finally:
+        for b in bufs:
+            b.free()
+    return out[0] if single else out

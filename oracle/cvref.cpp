@@ -19,6 +19,9 @@ namespace {
 
 inline int cv_floor(double v) { return (int)std::floor(v); }
 inline int cv_round(double v) { return (int)std::lrint(v); }  // round half to even (default FP mode)
+// cvRound of a remap coordinate: x86 cv2 converts with cvtss2si, whose result for NaN and for values outside int32 is the
+// "integer indefinite" INT_MIN (lrint's result is unspecified there).  INT_MIN >> 5 saturates to -32768: the pixel is borderValue.
+inline int cv_round_coord(float v) { return (v >= -2147483648.f && v < 2147483648.f) ? (int)std::lrint(v) : INT32_MIN; }
 inline short sat_short(int v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
 inline int reflect101(int p, int len) {
     if (len == 1) return 0;
@@ -208,12 +211,13 @@ void cvref_resize_nearest_f32(const float* src, int H, int W, int C, float* dst,
 }
 
 // cv::remap(float HWC, mapx, mapy (CV_32FC1), INTER_LINEAR, BORDER_CONSTANT, borderValue): coordinates are
-// quantised to 1/32 px (cvRound(v*32)), weights come from the float table (1-fx)(1-fy) ... of that grid.
+// quantised to 1/32 px (cvRound(v*32); NaN and out-of-int32 products give INT_MIN, hence the border), weights come from the
+// float table (1-fx)(1-fy) ... of that grid.
 void cvref_remap_linear_f32(const float* src, int H, int W, int C, const float* mapx, const float* mapy, float* dst, int Hd, int Wd,
                             float border) {
     for (int y = 0; y < Hd; ++y)
         for (int x = 0; x < Wd; ++x) {
-            const int fx = cv_round(mapx[(size_t)y * Wd + x] * 32.f), fy = cv_round(mapy[(size_t)y * Wd + x] * 32.f);
+            const int fx = cv_round_coord(mapx[(size_t)y * Wd + x] * 32.f), fy = cv_round_coord(mapy[(size_t)y * Wd + x] * 32.f);
             const int sx = sat_short(fx >> 5), sy = sat_short(fy >> 5);
             const float tx = (fx & 31) * (1.f / 32), ty = (fy & 31) * (1.f / 32);
             const float w[4] = {(1.f - ty) * (1.f - tx), (1.f - ty) * tx, ty * (1.f - tx), ty * tx};

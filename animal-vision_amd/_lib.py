@@ -297,6 +297,7 @@ _SIGS = {
     "avx_rgb_to_yuv_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "avx_yuv_hdr_to_rgb_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
     "avx_yuv_to_rgb_scaled_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "avx_yuv_hdr_to_rgb_scaled_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

@@ -105,7 +105,7 @@ class _Slot:
     d_yuv_in: object = None   # io_format="i420" / "yuv": the frame's payload on the device, in and out
     d_yuv_out: object = None
     d_left: object = None     # the left half of the split frame: d_in, or the op's baseline (split_baseline)
-    d_full: object = None     # scale=: the source-size RGB frames that avx_resize_hwc reduces into d_in (HDR and io_format="rgb")
+    d_full: object = None     # scale= with io_format="rgb": the source-size RGB frames that avx_resize_hwc reduces into d_in
 
 
 class FramePipeline:
@@ -135,9 +135,9 @@ class FramePipeline:
         INTER_AREA; never enlarged) on the slot stream before the op sees them.  H, W stay the source size; the
         slot's RGB buffers, the op, the split composition, the labels and everything on the way out (`out_H`, `out_W`, the
         emitted frames or payloads) have the scaled size.  io_format="yuv" / "i420" decode straight to the scaled frame
-        (yuv.yuv_to_rgb_scaled_device: one launch per slot, no full-size RGB frame); HDR payloads (`transfer`) and
-        io_format="rgb" frames land in a source-size buffer of the slot and go through avx_resize_hwc frame by frame.  With
-        scale=None nothing changes.
+        (yuv.yuv_to_rgb_scaled_device, or with a `transfer` yuv.yuv_hdr_to_rgb_scaled_device, DESIGN §4.13: one launch per slot,
+        no full-size RGB frame); io_format="rgb" frames land in a source-size buffer of the slot and go through avx_resize_hwc
+        frame by frame.  With scale=None nothing changes.
 
         split_baseline: the split frame's left half is the op's own baseline -- `op.slot_baseline(k)`, the frame a species'
         visualize() returns first (a UV species' panorama-warped input, SpeciesStreamOp) -- instead of the input frame.
@@ -200,7 +200,7 @@ class FramePipeline:
             return (h, w, 3) if io_format == "rgb" else ((i420_size(h, w),) if io_format == "i420" else (frame_size(pix_fmt, h, w),))
 
         self._in_shape, self._io_shape = io_shape(H, W), io_shape(oH, oW)  # frames in (source size), frames out
-        full = scale is not None and (io_format == "rgb" or transfer is not None)
+        full = scale is not None and io_format == "rgb"
         for k in range(depth):
             d_in, d_out = lend(k) if lend else (self.ctx.malloc(nbytes), self.ctx.malloc(nbytes))
             if d_in.nbytes < nbytes or d_out.nbytes < nbytes:
@@ -246,8 +246,8 @@ class FramePipeline:
         """frames: (global index, HxWx3 uint8 -- or, io_format="i420" / "yuv", a flat payload) pairs owned by this rank;
         emit(index, out) in submission order, `out` in the same format."""
         from ._lib import lib
-        from .yuv import (i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_hdr_to_rgb_device, yuv_to_rgb_device,
-                          yuv_to_rgb_scaled_device)
+        from .yuv import (i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_hdr_to_rgb_device, yuv_hdr_to_rgb_scaled_device,
+                          yuv_to_rgb_device, yuv_to_rgb_scaled_device)
 
         ctx, n, t0 = self.ctx, 0, time.perf_counter()
         self._copy_s = 0.0
@@ -267,11 +267,12 @@ class FramePipeline:
         if self.io_format == "yuv":
             def to_rgb(s, m):
                 if self.transfer is not None:
-                    yuv_hdr_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in if self.scale is None else s.d_full, m, self.H, self.W,
-                                          transfer=self.transfer, range=self.yuv_range, tonemap=self.tonemap, peak_nits=self.peak_nits,
-                                          sdr_white=self.sdr_white, stream=s.stream)
+                    hdr = dict(transfer=self.transfer, range=self.yuv_range, tonemap=self.tonemap, peak_nits=self.peak_nits,
+                               sdr_white=self.sdr_white, stream=s.stream)
                     if self.scale is not None:
-                        reduce_full(s, m)
+                        yuv_hdr_to_rgb_scaled_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, oH, oW, **hdr)
+                    else:
+                        yuv_hdr_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, **hdr)
                 elif self.scale is not None:
                     yuv_to_rgb_scaled_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, oH, oW, stream=s.stream, **kw)
                 else:

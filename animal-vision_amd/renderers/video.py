@@ -26,9 +26,9 @@ without one.
 
 Scaling: `scale=(Wd, Hd)` reduces every source's frames to Wd x Hd (cv2's INTER_AREA; enlarging is refused).
 get_image() returns scaled frames -- raw and .y4m sources through yuv.yuv_to_rgb_scaled, which decodes straight to the scaled
-frame; HDR sources through the HDR decode, then the resize; the other sources through the resize alone.  get_yuv() still hands
-over source-size payloads and `yuv_hw` still names the source size (pipeline.run_video reduces them as it decodes); `out_hw`
-names the size of what comes out, and every sink is written at that size.
+frame; HDR sources through yuv.yuv_hdr_to_rgb_scaled, which does the same; the other sources through the resize
+alone.  get_yuv() still hands over source-size payloads and `yuv_hw` still names the source size (pipeline.run_video reduces them
+as it decodes); `out_hw` names the size of what comes out, and every sink is written at that size.
 
 Sharded streams (two keywords the reference does not have, both defaulted): with `world` > 1 this renderer
 serves and stores only the frames of rank `rank` (global frame i belongs to rank i mod world) -- every source here is
@@ -255,11 +255,14 @@ class VideoRenderer(Renderer):
             f = self.get_yuv()
             if f is None:
                 return None
-            from ..yuv import yuv_hdr_to_rgb, yuv_to_rgb, yuv_to_rgb_scaled
+            from ..yuv import yuv_hdr_to_rgb, yuv_hdr_to_rgb_scaled, yuv_to_rgb, yuv_to_rgb_scaled
 
             if self.transfer is not None:
-                return self._scaled(yuv_hdr_to_rgb(f, self._raw.height, self._raw.width, pix_fmt=self.pix_fmt, transfer=self.transfer,
-                                                   range=self.yuv_range, tonemap=self.tonemap, peak_nits=self.peak_nits, sdr_white=self.sdr_white))
+                hdr = dict(pix_fmt=self.pix_fmt, transfer=self.transfer, range=self.yuv_range, tonemap=self.tonemap, peak_nits=self.peak_nits,
+                           sdr_white=self.sdr_white)
+                if self.scale is not None:
+                    return yuv_hdr_to_rgb_scaled(f, self._raw.height, self._raw.width, self.scale[1], self.scale[0], **hdr)
+                return yuv_hdr_to_rgb(f, self._raw.height, self._raw.width, **hdr)
             if self.scale is not None:
                 return yuv_to_rgb_scaled(f, self._raw.height, self._raw.width, self.scale[1], self.scale[0], pix_fmt=self.pix_fmt,
                                          matrix=self.matrix, range=self.yuv_range)

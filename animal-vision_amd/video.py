@@ -17,6 +17,9 @@ the device as it is decoded (`--tonemap`, `--peak-nits`, `--sdr-w
 
     ffmpeg -i in.mkv -f rawvideo -pix_fmt nv12 - | python -m animal_vision_amd.video - out.yuv --species HoneyBee --pix-fmt nv12 --size 3840x2160 --scale 1920x1080
 
+With `--transfer` as well (4K HDR10 or HLG run at 1080p: `--pix-fmt p010le --transfer pq --scale 1920x1080`) the HDR decode and the
+reduction are one launch per batch too, and no 4K RGB frame is ever written.
+
 `--hsi-model seeded|PATH` (HoneyBee only) takes the 31-band cube from the MST++ network instead of the analytic lobes (DESIGN §4.3);
 `--hsi-scale S` (HoneyBee only, 0.05 <= S < 1) runs that conversion on the frame reduced by S and enlarges the three cone catches back
 (HoneyBee(hsi_downsample=True, hsi_scale=S); with the network: DESIGN §4.12).  No checkpoint ships with the package: PATH is a local

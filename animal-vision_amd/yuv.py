@@ -2,7 +2,8 @@
 pixel formats -- nv12, p010le, 4:2:2, 4:4:4, gray, 10-bit planar -- of csrc/yuv_raw.hip (PIX_FMTS), and the HDR decode
 of csrc/yuv_hdr.hip: 10-bit BT.2020 PQ / HLG payloads -> tone-mapped SDR RGB (yuv_hdr_to_rgb); and the scaled decode
 of csrc/yuv_scale.hip: a raw payload -> RGB at a smaller size in one launch, byte-equal to the decode followed by cv2's INTER_AREA
-resize (yuv_to_rgb_scaled).
+resize (yuv_to_rgb_scaled); and the scaled HDR decode of csrc/yuv_hdr_scale.hip: the two together, an HDR payload
+-> tone-mapped SDR RGB at a smaller size in one launch (yuv_hdr_to_rgb_scaled).
 
 The arithmetic (int32 fixed point, 16 fractional bits, BT.601 / BT.709, limited / full range) is defined in DESIGN §4.8; the
 coefficient tables are built by the C entry points from the (matrix, range) names below.  A payload is one frame's Y plane
@@ -312,6 +313,52 @@ def yuv_to_rgb_scaled(buf: np.ndarray, H: int, W: int, Hd: int, Wd: int, *, pix_
     d_out = ctx.malloc(n * Hd * Wd * 3)
     try:
         yuv_to_rgb_scaled_device(ctx, pix_fmt, d_in, d_out, n, H, W, Hd, Wd, matrix=matrix, range=range)
+        out = ctx.download(d_out, (n, Hd, Wd, 3), np.uint8)
+    finally:
+        d_in.free()
+        d_out.free()
+    return out if batched else out[0]
+
+
+# ---------------------------------------------------------------- scaled HDR decode (csrc/yuv_hdr_scale.hip) -----------------------
+def yuv_hdr_to_rgb_scaled_device(ctx: Context, pix_fmt: str, d_yuv: DeviceBuffer, d_rgb: DeviceBuffer, n_frames: int, H: int, W: int, Hd: int,
+                                 Wd: int, *, transfer: str, range: str = "limited", tonemap: str = "mobius", peak_nits: float = 1000.0,
+                                 sdr_white: float = 203.0, stream=None) -> None:
+    """n_frames 10-bit BT.2020 payloads of H x W in `pix_fmt` with the `transfer` curve -> n_frames tone-mapped sRGB uint8 frames of
+    Hd x Wd, in one launch: byte for byte yuv_hdr_to_rgb_device followed by geometry.resize(..., INTER_AREA) per frame."""
+    fmt, r, tr, tm, peak, white = hdr_codes(pix_fmt, transfer, range, tonemap, peak_nits, sdr_white)
+    check_scale(H, W, Hd, Wd)
+    if n_frames < 1:
+        raise ValueError(f"bad shape: {n_frames} frames of {H} x {W}")
+    fsz = frame_size(pix_fmt, H, W)
+    if d_rgb.nbytes < n_frames * Hd * Wd * 3 or d_yuv.nbytes < n_frames * fsz:
+        raise ValueError(f"{n_frames} frames of {H} x {W} -> {Hd} x {Wd} need {n_frames * Hd * Wd * 3} RGB and {n_frames * fsz} {pix_fmt} bytes; "
+                         f"the buffers hold {d_rgb.nbytes} and {d_yuv.nbytes}")
+    ctx._check(lib.avx_yuv_hdr_to_rgb_scaled_u8(ctx._h, fmt, d_yuv.ptr, d_rgb.ptr, int(n_frames), int(H), int(W), int(Hd), int(Wd), r, tr, tm,
+                                                peak, white, ctx._s(stream)))
+
+
+def yuv_hdr_to_rgb_scaled(buf: np.ndarray, H: int, W: int, Hd: int, Wd: int, *, pix_fmt: str, transfer: str, range: str = "limited",
+                          tonemap: str = "mobius", peak_nits: float = 1000.0, sdr_white: float = 203.0,
+                          ctx: Optional[Context] = None) -> np.ndarray:
+    """HDR payload(s) of H x W -> SDR RGB uint8 of Hd x Wd, with the payload and batch conventions of yuv_to_rgb: one frame ->
+    (Hd, Wd, 3), or (N, frame_size) -> (N, Hd, Wd, 3)."""
+    hdr_codes(pix_fmt, transfer, range, tonemap, peak_nits, sdr_white)
+    check_scale(H, W, Hd, Wd)
+    fsz = frame_size(pix_fmt, H, W)
+    a = np.ascontiguousarray(buf)
+    if a.dtype != np.uint8:
+        raise TypeError(f"raw video payloads are uint8 (got {a.dtype})")
+    batched = a.ndim == 2 and a.shape[1] == fsz
+    if not batched and a.size != fsz:
+        raise ValueError(f"expected {fsz} bytes per {H}x{W} {pix_fmt} frame (or an (N, {fsz}) batch), got shape {a.shape}")
+    n = a.shape[0] if batched else 1
+    ctx = ctx or get_context()
+    d_in = ctx.upload(a)
+    d_out = ctx.malloc(n * Hd * Wd * 3)
+    try:
+        yuv_hdr_to_rgb_scaled_device(ctx, pix_fmt, d_in, d_out, n, H, W, Hd, Wd, transfer=transfer, range=range, tonemap=tonemap,
+                                     peak_nits=peak_nits, sdr_white=sdr_white)
         out = ctx.download(d_out, (n, Hd, Wd, 3), np.uint8)
     finally:
         d_in.free()

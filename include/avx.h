@@ -331,6 +331,21 @@ int avx_yuv_hdr_to_rgb_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t* rg
 int avx_yuv_to_rgb_scaled_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t* rgb_hwc, int n_frames, int H, int W, int Hd, int Wd, int matrix,
                              int full_range, void* stream);
 
+/* Scaled HDR decode (csrc/yuv_hdr_scale.hip): n_frames 10-bit payloads of avx_yuv_frame_size(fmt, H, W) bytes ->
+ * n_frames frames of Hd x Wd interleaved RGB uint8 (n_frames * Hd * Wd * 3 bytes), 1 <= Hd <= H, 1 <= Wd <= W, in one launch.  Per
+ * frame the result is, byte for byte,
+ *     avx_resize_hwc(avx_yuv_hdr_to_rgb_u8(fmt, frame, H, W, full_range, transfer, tonemap, peak_nits, sdr_white),
+ *                    dtype = 2 (uint8), C = 3, Hd, Wd, interp = 3 (INTER_AREA))
+ * without the full-size RGB frame ever being written: every source pixel is decoded to its three uint8 codes exactly as
+ * avx_yuv_hdr_to_rgb_u8 decodes it, and cv2's INTER_AREA reduces those codes as avx_yuv_to_rgb_scaled_u8 describes (integer ratios:
+ * the integer block sum, (sum + 2) >> 2 for 2 x 2 and rint(sum * (1.f / (isx * isy))) otherwise; any other ratio: the float32
+ * weighted sums of avx_resize_hwc's general path).  Hd == H and Wd == W gives avx_yuv_hdr_to_rgb_u8's frame.  AVX_ERR_INVALID
+ * (avx_last_error starts with this function's name) for everything either of the two refuses: an 8-bit format or GRAY, a bad
+ * transfer, tonemap or range, peak_nits <= sdr_white or a non-finite or non-positive value, a bad size, Hd > H or Wd > W, an
+ * integer-ratio block of more than 65536 samples, NULL or overlapping buffers, and an odd payload address. */
+int avx_yuv_hdr_to_rgb_scaled_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t* rgb_hwc, int n_frames, int H, int W, int Hd, int Wd,
+                                 int full_range, int transfer, int tonemap, double peak_nits, double sdr_white, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

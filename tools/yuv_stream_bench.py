@@ -12,14 +12,20 @@
       §4.10), beside the SDR decode of the same payload; with --scale WxH, every named format also goes through the scaled decode
       of §4.11 (avx_yuv_to_rgb_scaled_u8, one launch per batch) and, in the same process, through the chain it replaces:
       avx_yuv_to_rgb_u8 on the batch, then one avx_resize_hwc (uint8, INTER_AREA) per frame.  One JSON line per format carries
-      both as timed with stream events around the `iters` repetitions (launch gaps included).
-  python tools/yuv_stream_bench.py report STATS_CSV [--transfer NAME ...]
+      both as timed with stream events around the `iters` repetitions (launch gaps included).  With both --transfer and --scale,
+      every named 10-bit format and transfer also goes through the scaled HDR decode of §4.13 (avx_yuv_hdr_to_rgb_scaled_u8, one
+      launch per batch) and through the chain it replaces -- avx_yuv_hdr_to_rgb_u8 on the batch, then one avx_resize_hwc per
+      frame -- on the same payloads; each of the `iters` repetitions is timed with its own pair of stream events, and the JSON
+      line carries the medians and chain_over_fused.
+  python tools/yuv_stream_bench.py report STATS_CSV [--transfer NAME ...] [--scale WxH]
       The kernels' mean time per 4K frame from rocprofv3's kernel_stats.csv, and its share of 6.29 TB/s (the measured HBM copy
       rate, MI355X) for the bytes each direction moves: the format's B/px plus 3 B/px of RGB.  An HDR decode kernel's line also
       carries its transfer and its time over the SDR decode kernel's of the same format in the same run (both move the same
       bytes, so the ratio is arithmetic); --transfer keeps only the named transfers' HDR lines.  A scaled decode kernel's line
       carries its time per 4K source frame, the chain's in the same run (the plain decode kernel of the format plus the uint8
-      INTER_AREA resize kernel, kernel time only) and chain / fused."""
+      INTER_AREA resize kernel, kernel time only) and chain / fused; a scaled HDR decode kernel's line (§4.13) the same beside
+      the HDR decode kernel of its format and transfer plus the resize kernel, and with --scale WxH (the run's) its share of
+      6.29 TB/s for the payload in plus 3 B per destination pixel out."""
 import argparse
 import csv
 import json
@@ -75,7 +81,7 @@ def stream(args):
 def kernels(args):
     from animal_vision_amd.runtime import get_context
     from animal_vision_amd.yuv import (HDR_PIX_FMTS, frame_size, i420_size, i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device,
-                                       yuv_hdr_to_rgb_device, yuv_to_rgb_device, yuv_to_rgb_scaled_device)
+                                       yuv_hdr_to_rgb_device, yuv_hdr_to_rgb_scaled_device, yuv_to_rgb_device, yuv_to_rgb_scaled_device)
     from animal_vision_amd.geometry import INTER_AREA, resize_device
 
     ctx = get_context()
@@ -119,6 +125,29 @@ def kernels(args):
             us = {k: v * 1e3 / (args.iters * n) for k, v in ms.items()}
             print(json.dumps({"scaled_decode": p, "scale": f"{Wd}x{Hd}", "batch": n, "iters": args.iters, "fused_us_per_4k_frame": round(us["fused"], 2),
                               "chain_us_per_4k_frame": round(us["chain"], 2), "chain_over_fused": round(us["chain"] / us["fused"], 2)}), flush=True)
+            for tr in (args.transfer or []) if p in HDR_PIX_FMTS else []:  # §4.13: the same payload, read as HDR
+
+                def hdr_fused():
+                    yuv_hdr_to_rgb_scaled_device(ctx, p, d_raw, d_small, n, H, W, Hd, Wd, transfer=tr)
+
+                def hdr_chain():
+                    yuv_hdr_to_rgb_device(ctx, p, d_raw, d_rgb2, n, H, W, transfer=tr)
+                    for f in range(n):
+                        resize_device(ctx, full[f], np.uint8, H, W, 3, Hd, Wd, INTER_AREA, small[f])
+
+                med = {}
+                for name, fn in (("fused", hdr_fused), ("chain", hdr_chain)):
+                    fn()
+                    ctx.sync()
+                    each = []
+                    for _ in range(args.iters):  # every repetition between its own pair of events: the median is quoted
+                        ctx.timer_start()
+                        fn()
+                        each.append(ctx.timer_stop())
+                    med[name] = float(np.median(each)) * 1e3 / n
+                print(json.dumps({"scaled_hdr_decode": p, "transfer": tr, "scale": f"{Wd}x{Hd}", "batch": n, "iters": args.iters,
+                                  "fused_us_per_4k_frame": round(med["fused"], 2), "chain_us_per_4k_frame": round(med["chain"], 2),
+                                  "chain_over_fused": round(med["chain"] / med["fused"], 2)}), flush=True)
             d_small.free()
         ctx.sync()
         d_raw.free()
@@ -165,6 +194,8 @@ def report(args):
             rows.append({"kernel": kernel.group(0) if kernel else name, "pix_fmt": "i420" if "i420" in name else fmt,
                          "transfer": _TRANSFER.get(int(hdr.group(1))) if hdr else None, "calls": int(row.get("Calls", 0)), "us": avg_ns / 1e3 / 8})
     scaled = ("k_yuv420_to_rgb_half_vec", "k_yuv_to_rgb_area_int", "k_yuv_to_rgb_area_gen")  # csrc/yuv_scale.hip
+    scaled_hdr = ("k_yuv420_hdr_to_rgb_half_vec", "k_yuv_hdr_to_rgb_area_int", "k_yuv_hdr_to_rgb_area_gen")  # csrc/yuv_hdr_scale.hip
+    hdr_us = {(r["pix_fmt"], r["transfer"]): r["us"] for r in rows if r["transfer"] is not None and r["kernel"] not in scaled_hdr}
     sdr = {r["pix_fmt"]: r["us"] for r in rows
            if r["transfer"] is None and "_to_rgb" in r["kernel"] and r["pix_fmt"] != "i420" and r["kernel"] not in scaled}
     for r in rows:
@@ -177,6 +208,18 @@ def report(args):
             print(json.dumps(out))
             continue
         if r["transfer"] is not None and args.transfer and r["transfer"] not in args.transfer:
+            continue
+        if r["kernel"] in scaled_hdr:  # beside the HDR decode kernel of the same format and transfer + the resize kernel of the same run
+            out = {"kernel": r["kernel"], "pix_fmt": r["pix_fmt"], "transfer": r["transfer"], "calls": r["calls"], "us_per_4k_frame": round(r["us"], 2)}
+            if args.scale:  # the bytes the fused kernel moves: the payload in, 3 B per destination pixel out (p010le at 2 x 2: 3.75 B/px)
+                nbytes = frame_size(r["pix_fmt"], H, W) + 3.0 * args.scale[0] * args.scale[1]
+                out.update(bytes_per_src_px=round(nbytes / (H * W), 3), **{"frac_of_6.29TBps": round(nbytes / COPY_BPS / (r["us"] * 1e-6), 3)})
+            key = (r["pix_fmt"], r["transfer"])
+            if key in hdr_us and resize_us is not None:
+                chain = hdr_us[key] + resize_us
+                out.update(chain_decode_us=round(hdr_us[key], 2), chain_resize_us=round(resize_us, 2), chain_us_per_4k_frame=round(chain, 2),
+                           chain_over_fused=round(chain / r["us"], 2))
+            print(json.dumps(out))
             continue
         fmt, us = "yuv420p" if r["pix_fmt"] == "i420" else r["pix_fmt"], r["us"]
         bytes_per_frame = frame_size(fmt, H, W) + 3.0 * H * W  # the payload + 3 B/px of RGB, in one direction
@@ -206,6 +249,8 @@ def main():
     r = sub.add_parser("report")
     r.add_argument("csv")
     r.add_argument("--transfer", nargs="+", default=None, choices=["pq", "hlg"], help="keep only these transfers' HDR kernels")
+    r.add_argument("--scale", default=None, type=lambda t: tuple(int(v) for v in t.lower().split("x")), metavar="WxH",
+                   help="the --scale of the run: a scaled HDR decode kernel's line then carries its share of the copy rate")
     args = ap.parse_args()
     {"stream": stream, "kernels": kernels, "report": report}[args.cmd](args)
 

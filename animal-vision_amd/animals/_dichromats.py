@@ -132,30 +132,22 @@ class Cat(_Dichromat):
             if np.issubdtype(image.dtype, np.floating):
                 return self._visualize_float(image)
             raise NotImplementedError(f"Cat: device path implemented for uint8 and float frames, got {image.dtype}")
-        from .. import geometry as G
-
+        # one frame through the stream operator's two launches (CatStreamOp): device tables and buffers are kept per size
         H, W = image.shape[:2]
-        scale = G.zoom_scale_from_cat_ratio(camera_hfov_deg=self.CAMERA_HFOV_DEG, cat_per_eye_half_fov_deg=self.CAT_PER_EYE_HALF_FOV_DEG,
-                                            cat_to_human_ratio=self.CAT_TO_HUMAN_RATIO)
-        human_zoomed = G.center_zoom(image, scale=scale)
-        op = self._operator()
-        if not self.ENABLE_FOV_WARP:
-            return human_zoomed, op(image)
-        ctx = op._ctx()
-        tables = G.binocular_warp_tables(H, W, W, H, self.CAMERA_HFOV_DEG, self.CAT_PER_EYE_HALF_FOV_DEG, self.CAT_OVERLAP_DEG)
-        d_in = ctx.upload(image)
-        d_warp = ctx.malloc(H * W * 3 * 4)
-        d_out = ctx.malloc(H * W * 3)
-        try:
-            G.binocular_warp_device(ctx, d_in, H, W, tables, H, W, d_warp)
-            op.desc.in_f32 = 1
-            try:
-                op.run_device(d_warp, d_out, 1, H, W)
-            finally:
-                op.desc.in_f32 = 0
-            cat_out = ctx.download(d_out, image.shape, np.uint8)
-        finally:
-            d_in.free(); d_warp.free(); d_out.free()
+        plans = self.__dict__.setdefault("_u8_plans", {})
+        key = (H, W, bool(self.ENABLE_FOV_WARP), self.CAMERA_HFOV_DEG, self.CAT_PER_EYE_HALF_FOV_DEG, self.CAT_OVERLAP_DEG, self.CAT_TO_HUMAN_RATIO)
+        sop = plans.get(key)
+        if sop is None:
+            if len(plans) >= 4:
+                plans.pop(next(iter(plans))).close()
+            sop = plans[key] = CatStreamOp(self, H, W, depth=1, batch=1)
+        ctx = sop.ctx
+        d_in, d_out = sop.slot_buffers(0)
+        ctx.upload(image, d_in)
+        sop.run_device(d_in, d_out, 1, H, W)
+        cat_out = ctx.download(d_out, image.shape, np.uint8)
+        d_base = sop.slot_baseline(0)
+        human_zoomed = image if d_base is d_in else ctx.download(d_base, image.shape, np.uint8)  # center_zoom at scale <= 1: the frame itself
         return human_zoomed, cat_out
 
     def _visualize_float(self, image: np.ndarray):
@@ -209,3 +201,69 @@ class Cat(_Dichromat):
         be.run_device()
         out = ctx.download(be.d_out, image.shape, np.float32)
         return human_zoomed.astype(image.dtype, copy=False), out.astype(image.dtype, copy=False)
+
+
+class CatStreamOp:
+    """Cat as a frame-loop operator (pipeline.FramePipeline's protocol, like SpeciesStreamOp): per slot `batch` contiguous uint8
+    frames in, out and baseline on the device; once per op the five binocular warp tables.  run_device enqueues two launches on
+    the slot's stream: avx_center_zoom_u8 into the slot's baseline (visualize()'s first frame, the split frame's left half) and
+    avx_cat_wide_u8 (csrc/cat_wide.hip: warp, colour tail, blur and encode fused).  With cat.ENABLE_FOV_WARP false the wide view is
+    the ordinary dichromat kernel on the uint8 frames; with a zoom scale <= 1 the baseline is the input itself.  The buffers are
+    plain allocations of the op, which outlive the slot streams."""
+
+    def __init__(self, cat: Cat, H: int, W: int, depth: int = 3, batch: int = 1, ctx=None):
+        from .. import geometry as G
+
+        if batch < 1:
+            raise ValueError(f"batch must be at least 1 (got {batch})")
+        self.cat, self.H, self.W = cat, int(H), int(W)
+        self.batch = self.max_batch = int(batch)
+        self._op = cat._operator() if ctx is None else DichromatOp(cat.SPEC, ctx)
+        self.ctx = self._op._ctx()
+        self.warp = bool(cat.ENABLE_FOV_WARP)
+        self.rect = self.crop_rect(cat, self.H, self.W)
+        nbytes = self.batch * self.H * self.W * 3
+        self._bufs = [(self.ctx.malloc(nbytes), self.ctx.malloc(nbytes)) for _ in range(depth)]
+        self._base = [self.ctx.malloc(nbytes) if self.rect is not None else None for _ in range(depth)]
+        self._by_in = {d_in.ptr: k for k, (d_in, _) in enumerate(self._bufs)}
+        self._tables, self._table_ptrs = None, None
+        if self.warp:
+            tables = G.binocular_warp_tables(self.H, self.W, self.W, self.H, cat.CAMERA_HFOV_DEG, cat.CAT_PER_EYE_HALF_FOV_DEG, cat.CAT_OVERLAP_DEG)
+            self._tables, self._table_ptrs = G.binocular_warp_tables_device(self.ctx, tables)
+
+    @staticmethod
+    def crop_rect(cat: Cat, H: int, W: int):
+        """The crop (x0, y0, cw, ch) of the H x W frame that the baseline enlarges (cat.py:74-79), or None at a zoom scale <= 1:
+        the baseline is the input.  Host arithmetic only."""
+        from .. import geometry as G
+
+        scale = G.zoom_scale_from_cat_ratio(camera_hfov_deg=cat.CAMERA_HFOV_DEG, cat_per_eye_half_fov_deg=cat.CAT_PER_EYE_HALF_FOV_DEG,
+                                            cat_to_human_ratio=cat.CAT_TO_HUMAN_RATIO)
+        return G.center_zoom_rect(H, W, scale)
+
+    def slot_buffers(self, k: int):
+        return self._bufs[k]
+
+    def slot_baseline(self, k: int):
+        """Slot k's baseline frames (uint8, on the device): the centre-zoomed input, or the slot's input at a zoom scale <= 1."""
+        return self._base[k] if self.rect is not None else self._bufs[k][0]
+
+    def run_device(self, d_in, d_out, n_frames: int, H: int, W: int, stream=None):
+        from .. import geometry as G
+
+        assert 1 <= n_frames <= self.batch and (H, W) == (self.H, self.W)
+        if self.rect is not None:
+            G.center_zoom_device(self.ctx, d_in, self._base[self._by_in[d_in.ptr]], n_frames, H, W, self.rect, stream)
+        if self.warp:
+            G.cat_wide_device(self.ctx, d_in, d_out, n_frames, H, W, self._op.desc, self._table_ptrs, stream)
+        else:
+            self._op.run_device(d_in, d_out, n_frames, H, W, stream=stream)
+
+    def close(self):
+        for pair in self._bufs:
+            for b in pair:
+                b.free()
+        for b in self._base + [self._tables]:
+            if b is not None:
+                b.free()
+        self._bufs, self._base, self._tables = [], [], None

@@ -59,8 +59,7 @@ __global__ __launch_bounds__(kThreads) void dichromat_simple_kernel(DichromatArg
             float c0, c1, c2;
             if (a.in_f32) {  // float32 frame already in [0,1]: srgb_to_linear (animal_utils.py:5-11) in float32
                 const float* pf = reinterpret_cast<const float*>(a.in) + ((size_t)f * a.H * a.W + (size_t)gy * a.W + gx) * 3;
-                auto eotf = [](float v) { return v <= 0.04045f ? v / 12.92f : powf((v + 0.055f) / 1.055f, 2.4f); };
-                c0 = eotf(pf[0]); c1 = eotf(pf[1]); c2 = eotf(pf[2]);
+                c0 = srgb_eotf_f32(pf[0]); c1 = srgb_eotf_f32(pf[1]); c2 = srgb_eotf_f32(pf[2]);
                 seen_gt1 = 1;  // the frame is normalised already: never the all-<=1 branch
             } else {
                 const uint8_t* p = fin + ((size_t)gy * a.W + gx) * 3;
@@ -78,14 +77,7 @@ __global__ __launch_bounds__(kThreads) void dichromat_simple_kernel(DichromatArg
                 o1 = fma_t(c2, a.M[5], fma_t(c1, a.M[4], c0 * a.M[3]));
                 o2 = fma_t(c2, a.M[8], fma_t(c1, a.M[7], c0 * a.M[6]));
             } else {
-                const float l = fma_t(c2, a.M[2], fma_t(c1, a.M[1], c0 * a.M[0]));
-                const float m = fma_t(c2, a.M[5], fma_t(c1, a.M[4], c0 * a.M[3]));
-                const float s = fma_t(c2, a.M[8], fma_t(c1, a.M[7], c0 * a.M[6]));
-                const float lm = a.alpha * l + a.one_minus_alpha * m;  // separate mul, mul, add (cat.py:99)
-                const double dlm = (double)lm, ds = (double)s;
-                o0 = (T)__builtin_fma(ds, a.Bk[2], __builtin_fma(dlm, a.Bk[1], dlm * a.Bk[0]));
-                o1 = (T)__builtin_fma(ds, a.Bk[5], __builtin_fma(dlm, a.Bk[4], dlm * a.Bk[3]));
-                o2 = (T)__builtin_fma(ds, a.Bk[8], __builtin_fma(dlm, a.Bk[7], dlm * a.Bk[6]));
+                cat_merge_stage<T>(c0, c1, c2, a, o0, o1, o2);  // dichromat_common.h
             }
             A[i] = o0;
             A[AH * AW + i] = o1;

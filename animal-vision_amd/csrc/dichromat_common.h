@@ -44,6 +44,24 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
+// srgb_to_linear (animal_utils.py:5-11) of a float32 sample in [0,1], in float32 with the device powf: the decode of a
+// frame that is float already (in_f32: the reference kernel; avx_cat_wide_u8's warped samples).
+__device__ __forceinline__ float srgb_eotf_f32(float v) { return v <= 0.04045f ? v / 12.92f : powf((v + 0.055f) / 1.055f, 2.4f); }
+
+// AVX_COLOR_CAT_MERGE of one decoded sample (cat.py:95-101): RGB->LMS as a float32 FMA chain, the L/M merge as separate
+// mul, mul, add (cat.py:99), LMS->RGB as a float64 FMA chain.
+template <typename T>
+__device__ __forceinline__ void cat_merge_stage(float c0, float c1, float c2, const DichromatArgs& a, T& o0, T& o1, T& o2) {
+    const float l = fma_t(c2, a.M[2], fma_t(c1, a.M[1], c0 * a.M[0]));
+    const float m = fma_t(c2, a.M[5], fma_t(c1, a.M[4], c0 * a.M[3]));
+    const float s = fma_t(c2, a.M[8], fma_t(c1, a.M[7], c0 * a.M[6]));
+    const float lm = a.alpha * l + a.one_minus_alpha * m;
+    const double dlm = (double)lm, ds = (double)s;
+    o0 = (T)__builtin_fma(ds, a.Bk[2], __builtin_fma(dlm, a.Bk[1], dlm * a.Bk[0]));
+    o1 = (T)__builtin_fma(ds, a.Bk[5], __builtin_fma(dlm, a.Bk[4], dlm * a.Bk[3]));
+    o2 = (T)__builtin_fma(ds, a.Bk[8], __builtin_fma(dlm, a.Bk[7], dlm * a.Bk[6]));
+}
+
 // "Am I the last workgroup to arrive?" for grids of hundreds to thousands of workgroups.  One counter serialises every arrival at one address (agent-scope atomics
 // are performed at the memory side: ~10-25 ns each back to back, i.e. 10-25 us for 1,024 workgroups -- most of the duration of the small reduction kernels that end
 // with it); here a workgroup arrives at counter 1 + (block % kTicketFan) and only the one that completes its group goes on to counter 0: <= nblocks / 32 + 32 arrivals

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "dichromat_common.h"
+#include "remap_common.h"
 #include "resize_common.h"
 #include "stack_up.h"
 
@@ -141,34 +142,7 @@ __global__ __launch_bounds__(kGT) void k_any_gt1(const uint8_t* __restrict__ in,
 struct WarpArgs { const uint8_t* in; float* out; int H, W, Ho, Wo; const float* xL; const float* xR; const float* ymap; const float* wL; const float* wR;
                   const uint32_t* flag; };
 
-// cvRound(v * 32) of a remap coordinate as x86 cv2 computes it: NaN and products outside int32 convert to INT_MIN, which the
-// saturation to short below turns into column / row -32768, so the pixel takes the border value.  (__float2int_rn alone
-// saturates +-inf and +-1e30 the same way but turns NaN into 0, which samples pixel (0, 0).)
-__device__ __forceinline__ int remap_round(float v) {
-    const float q = v * 32.f;
-    return (q >= -2147483648.f && q < 2147483648.f) ? __float2int_rn(q) : INT_MIN;
-}
-
-__device__ __forceinline__ void remap_px(const uint8_t* in, int H, int W, float mx, float my, float norm, float (&o)[3]) {
-    const int fx = remap_round(mx), fy = remap_round(my);
-    int sx = fx >> 5, sy = fy >> 5;
-    sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);
-    sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
-    const float tx = (fx & 31) * (1.f / 32), ty = (fy & 31) * (1.f / 32);
-    const float w0 = (1.f - ty) * (1.f - tx), w1 = (1.f - ty) * tx, w2 = ty * (1.f - tx), w3 = ty * tx;
-    if (sx >= W || sx + 1 < 0 || sy >= H || sy + 1 < 0) { o[0] = o[1] = o[2] = 0.f; return; }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        auto at = [&](int yy, int xx) {
-            if ((unsigned)xx >= (unsigned)W || (unsigned)yy >= (unsigned)H) return 0.f;  // BORDER_CONSTANT, value 0
-            const float v = (float)in[((size_t)yy * W + xx) * 3 + c];
-            const float n = norm == 1.f ? v : v / 255.0f;                                // get_normalized_image
-            return n < 0.f ? 0.f : (n > 1.f ? 1.f : n);
-        };
-        o[c] = at(sy, sx) * w0 + at(sy, sx + 1) * w1 + at(sy + 1, sx) * w2 + at(sy + 1, sx + 1) * w3;
-    }
-}
-
+// remap_round / remap_px / binocular_blend: remap_common.h (shared with cat_wide.hip)
 __global__ __launch_bounds__(kGT) void k_binocular_warp(WarpArgs a) {
     const float norm = *a.flag ? 255.f : 1.f;  // all bytes <= 1: get_normalized_image does not divide
     const size_t total = (size_t)a.Ho * a.Wo;
@@ -180,10 +154,7 @@ __global__ __launch_bounds__(kGT) void k_binocular_warp(WarpArgs a) {
         const float wl = a.wL[x], wr = a.wR[x];
         const float wsum = (wl + wr) + 1e-8f;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = (l[c] * wl + r[c] * wr) / wsum;
-            a.out[i * 3 + c] = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-        }
+        for (int c = 0; c < 3; ++c) a.out[i * 3 + c] = binocular_blend(l[c], r[c], wl, wr, wsum);
     }
 }
 

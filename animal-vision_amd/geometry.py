@@ -70,15 +70,29 @@ def panorama_warp(img_lin: np.ndarray, *, scale_x: float) -> np.ndarray:
     return widened[:, start : start + W, :]
 
 
+def center_zoom_rect(H: int, W: int, scale: float) -> Optional[Tuple[int, int, int, int]]:
+    """The crop (x0, y0, cw, ch) that center_zoom resizes back to (W, H); None when scale <= 1 (the frame is returned as it is)."""
+    if scale <= 1.0:
+        return None
+    cw, ch = max(1, int(round(W / scale))), max(1, int(round(H / scale)))
+    return (W - cw) // 2, (H - ch) // 2, cw, ch
+
+
 def center_zoom(image: np.ndarray, scale: float) -> np.ndarray:
     """animals/cat_widevision_utils.py:11-29: crop the centre (W/scale, H/scale), INTER_LINEAR back to (W, H)."""
     assert image.ndim >= 2, "HxW or HxWxC"
-    if scale <= 1.0:
+    rect = center_zoom_rect(image.shape[0], image.shape[1], scale)
+    if rect is None:
         return image
     H, W = image.shape[:2]
-    cw, ch = max(1, int(round(W / scale))), max(1, int(round(H / scale)))
-    x0, y0 = (W - cw) // 2, (H - ch) // 2
+    x0, y0, cw, ch = rect
     return resize(np.ascontiguousarray(image[y0 : y0 + ch, x0 : x0 + cw]), (W, H), INTER_LINEAR)
+
+
+def center_zoom_device(ctx: Context, d_in: DeviceBuffer, d_out: DeviceBuffer, n_frames: int, H: int, W: int, rect, stream=None):
+    """center_zoom of n_frames uint8 HxWx3 frames resident on the device, one launch (avx_center_zoom_u8); rect: center_zoom_rect's."""
+    x0, y0, cw, ch = rect
+    ctx._check(lib.avx_center_zoom_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, x0, y0, cw, ch, ctx._s(stream)))
 
 
 def zoom_scale_from_cat_ratio(*, camera_hfov_deg: float, cat_per_eye_half_fov_deg: float, cat_to_human_ratio: float) -> float:
@@ -116,6 +130,26 @@ def binocular_warp_device(ctx: Context, d_in: DeviceBuffer, H: int, W: int, tabl
     xL, xR, ymap, wL, wR = tables
     ctx._check(lib.avx_binocular_warp_u8(ctx._h, d_in.ptr, H, W, xL.ctypes.data, xR.ctypes.data, ymap.ctypes.data, wL.ctypes.data, wR.ctypes.data,
                                          out_h, out_w, d_out.ptr, ctx._s(stream)))
+
+
+def binocular_warp_tables_device(ctx: Context, tables) -> Tuple[DeviceBuffer, list]:
+    """binocular_warp_tables' five vectors in one device allocation: (buffer, [xL, xR, ymap, wL, wR] device addresses)."""
+    sizes = [(v.nbytes + 255) & ~255 for v in tables]
+    host = np.zeros(sum(sizes), np.uint8)
+    ptrs, o = [], 0
+    for v, n in zip(tables, sizes):
+        host[o : o + v.nbytes] = np.ascontiguousarray(v, np.float32).view(np.uint8)
+        ptrs.append(o)
+        o += n
+    buf = ctx.upload(host)
+    return buf, [buf.ptr + o for o in ptrs]
+
+
+def cat_wide_device(ctx: Context, d_in: DeviceBuffer, d_out: DeviceBuffer, n_frames: int, H: int, W: int, desc, table_ptrs, stream=None):
+    """Cat's wide view of n_frames uint8 HxWx3 frames resident on the device, one fused launch (avx_cat_wide_u8): the bytes of
+    binocular_warp_device + DichromatOp.run_device(in_f32) frame by frame.  table_ptrs: binocular_warp_tables_device's addresses."""
+    xL, xR, ymap, wL, wR = table_ptrs
+    ctx._check(lib.avx_cat_wide_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, ctypes.byref(desc), xL, xR, ymap, wL, wR, ctx._s(stream)))
 
 
 def animal_fov_binocular_warp_u8(image: np.ndarray, *, fov_in_deg: float, per_eye_half_fov_deg: float, overlap_deg: float,

@@ -32,17 +32,19 @@ format keep the payload (1.5 B/px for nv12, 3 B/px for p010le) across the host a
 
 INPUT and OUTPUT are a .y4m file, "-" (stdin / stdout, Y4M), or the other forms renderers.VideoRenderer takes (synthetic:,
 .npy, an image directory).  Species are the display names of gallery.py's registry.  Routing:
-  * the dichromats but Cat (DichromatOp), HoneyBee (HoneybeeOp; with --hsi-model: ml.MstHoneybeeStreamOp) and the plane-program UV
+  * the dichromats (DichromatOp; Cat: CatStreamOp, the fused wide-view kernel of DESIGN §4.14), HoneyBee (HoneybeeOp; with
+    --hsi-model: ml.MstHoneybeeStreamOp) and the plane-program UV
     species with a fixed plan (SpeciesStreamOp) stream through pipeline.run_video: `--depth` frames in flight, split-compose and labels on the device
     (against each species' own baseline, as visualize() returns it: the plane-program species' is their panorama-warped
-    input), and, from a .y4m to a .y4m, I420 across the host and PCIe (FramePipeline io_format="i420");
-  * every other species (Cat, whose baseline is the zoomed frame; MantisShrimp; RatUV, whose plan depends on the frame; HoneyBee
+    input, Cat's the centre-zoomed input), and, from a .y4m to a .y4m, I420 across the host and PCIe (FramePipeline io_format="i420");
+  * every other species (MantisShrimp; RatUV, whose plan depends on the frame; HoneyBee
     with --hsi-scale and no --hsi-model) runs
     visualize() per frame, and the split frame is composed from visualize's own (baseline, out) pair, as the reference does.
 
 `--batch N` (1..16) puts N frames into every pipeline slot: the plane-program species then run their launch chain once per N
 frames (planevm.DeviceBackend(frames=N): the frame is a grid dimension of the kernels), the dichromats and HoneyBee hand their
-kernels n_frames = N (with --hsi-model the network still runs frame by frame on the slot's stream).  The species of the per-frame loop have no batched form: for them `--batch` above 1 is an error."""
+kernels n_frames = N (with --hsi-model the network still runs frame by frame on the slot's stream; Cat's zoom and wide-view
+launches take the N frames of a slot each).  The species of the per-frame loop have no batched form: for them `--batch` above 1 is an error."""
 from __future__ import annotations
 
 import argparse
@@ -74,8 +76,9 @@ def make_animal(args):
 
 
 def route(animal) -> str:
-    """How the command runs `animal`: "dichromat" / "honeybee" / "honeybee_mst" / "plane" stream through run_video, "frame" runs
-    visualize() per frame."""
+    """The kind of `animal`'s frame operator: "dichromat" / "honeybee" / "honeybee_mst" / "plane" name the ops that stream through
+    run_video as they are; "frame" is every other species.  Of those Cat streams too, through an operator of its own
+    (CatStreamOp: has_stream_op, stream_op); the rest run visualize() per frame."""
     from .animals import Cat, HoneyBee
     from .animals._dichromats import _Dichromat
     from .animals._uv_species import UVSpecies
@@ -92,10 +95,25 @@ def route(animal) -> str:
     return "frame"
 
 
+def has_stream_op(animal) -> bool:
+    """Whether stream_op gives `animal` an operator for run_video (and so --batch, --depth and payload I/O): every route but
+    "frame", and Cat."""
+    from .animals import Cat
+
+    return isinstance(animal, Cat) or route(animal) != "frame"
+
+
 def stream_op(animal, H: int, W: int, depth: int, batch: int = 1):
     """The op run_video streams for `animal`, or None when the species goes through the per-frame loop.  batch: frames per
     pipeline slot -- the plane-program species record their plans for that many frames; the dichromat and honeybee ops take
-    n_frames per call as they are; a species of the per-frame loop cannot batch (ValueError)."""
+    n_frames per call as they are; Cat's operator holds `batch` frames per slot; a species of the per-frame loop cannot batch
+    (ValueError)."""
+    from .animals import Cat
+
+    if isinstance(animal, Cat):
+        from .animals._dichromats import CatStreamOp
+
+        return CatStreamOp(animal, H, W, depth=depth, batch=batch)
     kind = route(animal)
     if kind in ("dichromat", "honeybee"):
         return animal._operator()
@@ -244,7 +262,6 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     args = parse_args(argv)
     if args.depth < 1:
         raise SystemExit("video: --depth must be at least 1")
-    from .animals._uv_species import SpeciesStreamOp
     from .pipeline import run_video
     from .renderers import VideoRenderer, split_compose
 
@@ -261,7 +278,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             raise
         raise SystemExit(f"video: --scale {args.scale[0]}x{args.scale[1]}: {e}")  # a .y4m header smaller than --scale
     animal = make_animal(args)
-    if args.batch > 1 and route(animal) == "frame":  # before any frame is read
+    if args.batch > 1 and not has_stream_op(animal):  # before any frame is read
         vr.close()
         raise SystemExit(f"video: --batch {args.batch}: {args.species} runs visualize() per frame and has no batched form")
     labels = None if args.no_labels else ("Original", "Transformed")
@@ -287,11 +304,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if op is not None:
             try:
                 # the split frame's left half is visualize()'s baseline: the input for the dichromats and HoneyBee, the
-                # panorama-warped input for the plane-program species (their plans' baseline frames)
+                # panorama-warped input for the plane-program species (their plans' baseline frames), the zoomed input for Cat
                 stats = run_video(op, vr, depth=args.depth, split_compare=args.split_compare, labels=labels,
-                                  split_baseline=isinstance(op, SpeciesStreamOp), batch=args.batch)
+                                  split_baseline=hasattr(op, "slot_baseline"), batch=args.batch)
             finally:
-                if isinstance(op, SpeciesStreamOp):
+                if hasattr(op, "close"):
                     op.close()
             frames = stats.frames
         else:

@@ -233,6 +233,27 @@ int avx_resize_hwc(avx_ctx* ctx, const void* src, int dtype, int H, int W, int C
 int avx_binocular_warp_u8(avx_ctx* ctx, const uint8_t* in_hwc, int H, int W, const float* xL_host, const float* xR_host, const float* ymap_host,
                           const float* wL_host, const float* wR_host, int Ho, int Wo, float* out_hwc_f32, void* stream);
 
+/* Cat's wide view (animals/cat.py:82-109) of n_frames contiguous uint8 HWC frames in one launch (csrc/cat_wide.hip); the
+ * output has the input's size.  Defined as the chain, frame by frame,
+ *     avx_binocular_warp_u8(frame, H, W, tables, Ho = H, Wo = W) -> float32 frame -> avx_dichromat_u8(desc with in_f32 = 1)
+ * and byte for byte equal to it on the same device.  desc: AVX_COLOR_CAT_MERGE, AVX_POST_GAUSS (odd ksize <= AVX_MAX_KSIZE) or
+ * AVX_POST_NONE, no chroma compression; in_f32 and variant are ignored.  d_xL, d_xR, d_wL, d_wR (W floats each) and d_ymap (H floats)
+ * are DEVICE pointers the caller owns and keeps alive until the work has run (geometry.binocular_warp_tables' vectors).  Asynchronous on
+ * `stream`: a memset, one pass that finds each frame's "any byte > 1" flag and the fused launch -- no stream synchronisation, no
+ * host-to-device copy and, once the stream workspace holds n_frames flags, no allocation.  AVX_ERR_INVALID (avx_last_error starts
+ * with the function's name) for NULL pointers, n_frames < 0, H or W <= 0 and a desc of the wrong struct_size, colour mode, post mode
+ * or ksize; n_frames == 0 is AVX_OK without a launch. */
+int avx_cat_wide_u8(avx_ctx* ctx, const uint8_t* in_hwc_u8, uint8_t* out_hwc_u8, int n_frames, int H, int W, const avx_dichromat_desc* desc,
+                    const float* d_xL, const float* d_xR, const float* d_ymap, const float* d_wL, const float* d_wR, void* stream);
+
+/* center_zoom (cat_widevision_utils.py:11-29) of n_frames contiguous uint8 HWC frames in one launch: each output frame is
+ * cv2.resize(frame[y0:y0+ch, x0:x0+cw], (W, H), INTER_LINEAR), byte for byte avx_resize_hwc(dtype 2, interp 1) of the contiguous crop,
+ * with that call's tables (the stream workspace's cache: built and uploaded the first time a geometry is seen); the crop is read in
+ * place through the frame's row stride.  AVX_ERR_INVALID for NULL or aliased pointers, n_frames < 0, H or W <= 0, cw or ch < 1 and a
+ * crop that leaves the frame, before any launch; n_frames == 0 is AVX_OK without a launch. */
+int avx_center_zoom_u8(avx_ctx* ctx, const uint8_t* in_hwc_u8, uint8_t* out_hwc_u8, int n_frames, int H, int W, int x0, int y0, int cw, int ch,
+                       void* stream);
+
 /* VideoRenderer.make_split_frame (renderers/video.py:198-245) for two frames of the same size, without the
  * Hershey-font labels: left half `original`, right half `modified`, optional 1-px white seam at W//2.
  * out_hwc may alias modified_hwc (each byte is read before it is written by the same thread). */

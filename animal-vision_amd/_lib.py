@@ -250,6 +250,7 @@ _SIGS = {
     "avx_host_free": (_i, [_vp, _vp]),
     "avx_memcpy_h2d": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "avx_memcpy_d2h": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "avx_memcpy_d2d": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "avx_memset": (_i, [_vp, _vp, _i, _sz, _vp]),
     "avx_stream_create": (_i, [_vp, ctypes.POINTER(_vp)]),
     "avx_stream_destroy": (_i, [_vp, _vp]),
@@ -290,6 +291,13 @@ _SIGS = {
     "avx_split_compose_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "avx_draw_label_u8": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_int), _fp, _i, ctypes.c_float, ctypes.c_float, _i, _vp]),
     "avx_gallery_compose_u8": (_i, [_vp, ctypes.POINTER(GalleryTile), _i, _fp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _vp, _i, _i, _vp]),
+    "avx_wall_max_tiles": (_i, []),
+    "avx_wall_layout_create": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _fp, _i, _i, _i, _i,
+                                    ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_vp)]),
+    "avx_wall_layout_destroy": (_i, [_vp, _vp]),
+    "avx_wall_canvas_size": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "avx_wall_layout_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_sz)]),
+    "avx_wall_compose_u8": (_i, [_vp, _vp, ctypes.POINTER(_vp), _sz, _i, _vp, _sz, _vp]),
     "avx_i420_to_rgb_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "avx_rgb_to_i420_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "avx_yuv_coefficients": (_i, [_i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

@@ -280,6 +280,13 @@ int avx_memcpy_d2h(avx_ctx* ctx, void* dst_host, const void* src, size_t bytes, 
     return AVX_OK;
 }
 
+int avx_memcpy_d2d(avx_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, dst && src, "avx_memcpy_d2d: NULL pointer");
+    AVX_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, avx_pick_stream(ctx, stream)));
+    return AVX_OK;
+}
+
 int avx_memset(avx_ctx* ctx, void* dst, int value, size_t bytes, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
     AVX_REQUIRE(ctx, dst != nullptr, "avx_memset: NULL pointer");

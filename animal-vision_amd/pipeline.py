@@ -145,7 +145,13 @@ class FramePipeline:
         batch: frames per slot.  A slot's pinned staging and device buffers hold `batch` contiguous frames: one H2D copy, one
         op.run_device(..., n, ...), the split composition and labels per frame, the I420 conversions over the n frames, one D2H
         copy.  Frames are still emitted one by one in submission order; the last slot of a stream may carry fewer frames.  The
-        op states how many frames one call takes in `max_batch` (absent: 1); an op that cannot take `batch` is refused here."""
+        op states how many frames one call takes in `max_batch` (absent: 1); an op that cannot take `batch` is refused here.
+
+        An op whose output is not the size of its input says so with `out_shape(H, W) -> (Hc, Wc)` (wall.WallStreamOp: the labelled
+        grid of several species): the slot's d_out, the pinned output staging, the encode of from_rgb and the emitted frames or
+        payloads then have that size, and so have `out_H` / `out_W`; `op_H` / `op_W` name what the op is handed, and StreamStats
+        still counts those pixels.  split_compare composes two frames of one size: with such an op it is refused.  An op without
+        out_shape changes nothing here."""
         from .runtime import get_context
         from .yuv import PIX_FMTS, _codes, check_scale, frame_size, hdr_codes, i420_size
 
@@ -174,7 +180,11 @@ class FramePipeline:
             check_scale(H, W, Hd, Wd)
             scale = (int(Wd), int(Hd))
         self.scale = scale
-        self.out_H, self.out_W = (scale[1], scale[0]) if scale is not None else (H, W)
+        self.op_H, self.op_W = (scale[1], scale[0]) if scale is not None else (H, W)  # what the op is handed
+        shape_of = getattr(op, "out_shape", None)
+        if shape_of is not None and split_compare:
+            raise ValueError(f"split_compare: {type(op).__name__}'s output has a size of its own (out_shape); there is no frame to compare it with")
+        self.out_H, self.out_W = (int(v) for v in shape_of(self.op_H, self.op_W)) if shape_of is not None else (self.op_H, self.op_W)
         self.batch = int(batch)
         if self.batch < 1:
             raise ValueError(f"batch must be at least 1 (got {batch})")
@@ -189,8 +199,8 @@ class FramePipeline:
         self.ctx = ctx or getattr(op, "ctx", None) or get_context()
         if getattr(op, "ctx", None) is None:
             op.ctx = self.ctx
-        oH, oW = self.out_H, self.out_W
-        nbytes = oH * oW * 3 * self.batch
+        iH, iW, oH, oW = self.op_H, self.op_W, self.out_H, self.out_W
+        nbytes, out_nbytes = iH * iW * 3 * self.batch, oH * oW * 3 * self.batch
         # ops that own their device frames (recorded species plans, animals/_uv_species.py::SpeciesStreamOp) lend them per slot
         lend = getattr(op, "slot_buffers", None)
         self._lent = lend is not None
@@ -202,8 +212,8 @@ class FramePipeline:
         self._in_shape, self._io_shape = io_shape(H, W), io_shape(oH, oW)  # frames in (source size), frames out
         full = scale is not None and io_format == "rgb"
         for k in range(depth):
-            d_in, d_out = lend(k) if lend else (self.ctx.malloc(nbytes), self.ctx.malloc(nbytes))
-            if d_in.nbytes < nbytes or d_out.nbytes < nbytes:
+            d_in, d_out = lend(k) if lend else (self.ctx.malloc(nbytes), self.ctx.malloc(out_nbytes))
+            if d_in.nbytes < nbytes or d_out.nbytes < out_nbytes:
                 raise ValueError(f"batch={self.batch}: {type(op).__name__}'s slot buffers hold fewer than {self.batch} frames")
             s = _Slot(self.ctx.stream_create(), self.ctx.pinned((self.batch,) + self._in_shape, np.uint8),
                       self.ctx.pinned((self.batch,) + self._io_shape, np.uint8), d_in, d_out)
@@ -255,13 +265,13 @@ class FramePipeline:
             s.busy, s.indices = False, []
         i420 = self.io_format != "rgb"  # payloads cross the host and PCIe; RGB exists on the device only
         kw = dict(matrix=self.matrix, range=self.yuv_range)
-        oH, oW = self.out_H, self.out_W
+        iH, iW, oH, oW = self.op_H, self.op_W, self.out_H, self.out_W  # the op's input (the scaled frame), its output
         src_rgb_bytes = self.H * self.W * 3
 
         def reduce_full(s, m):
             """scale=: the m source-size frames of s.d_full -> s.d_in, cv2's INTER_AREA, frame by frame on the slot's stream."""
             for f in range(m):
-                ctx._check(lib.avx_resize_hwc(ctx._h, s.d_full.ptr + f * src_rgb_bytes, 2, self.H, self.W, 3, s.d_in.ptr + f * oH * oW * 3, oH, oW, 3,
+                ctx._check(lib.avx_resize_hwc(ctx._h, s.d_full.ptr + f * src_rgb_bytes, 2, self.H, self.W, 3, s.d_in.ptr + f * iH * iW * 3, iH, iW, 3,
                                               s.stream))
 
         if self.io_format == "yuv":
@@ -270,11 +280,11 @@ class FramePipeline:
                     hdr = dict(transfer=self.transfer, range=self.yuv_range, tonemap=self.tonemap, peak_nits=self.peak_nits,
                                sdr_white=self.sdr_white, stream=s.stream)
                     if self.scale is not None:
-                        yuv_hdr_to_rgb_scaled_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, oH, oW, **hdr)
+                        yuv_hdr_to_rgb_scaled_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, iH, iW, **hdr)
                     else:
                         yuv_hdr_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, **hdr)
                 elif self.scale is not None:
-                    yuv_to_rgb_scaled_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, oH, oW, stream=s.stream, **kw)
+                    yuv_to_rgb_scaled_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, iH, iW, stream=s.stream, **kw)
                 else:
                     yuv_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
 
@@ -284,7 +294,7 @@ class FramePipeline:
         else:
             def to_rgb(s, m):
                 if self.scale is not None:  # yuv420p is the I420 payload, byte for byte (include/avx.h)
-                    yuv_to_rgb_scaled_device(ctx, "yuv420p", s.d_yuv_in, s.d_in, m, self.H, self.W, oH, oW, stream=s.stream, **kw)
+                    yuv_to_rgb_scaled_device(ctx, "yuv420p", s.d_yuv_in, s.d_in, m, self.H, self.W, iH, iW, stream=s.stream, **kw)
                 else:
                     i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
 
@@ -304,7 +314,7 @@ class FramePipeline:
                 reduce_full(s, m)
             else:
                 ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_in.ptr, s.h_in.ptr, m * in_bytes, s.stream))
-            self.op.run_device(s.d_in, s.d_out, m, oH, oW, stream=s.stream)
+            self.op.run_device(s.d_in, s.d_out, m, iH, iW, stream=s.stream)
             if self.split_compare:
                 for f in range(m):
                     o = f * rgb_bytes
@@ -340,7 +350,7 @@ class FramePipeline:
             k += 1
         for j in range(self.depth):  # drain in submission order
             self._retire(self.slots[(k + j) % self.depth], emit)
-        return StreamStats(n, n * oH * oW, time.perf_counter() - t0, 1, self._copy_s)  # pixels the op saw
+        return StreamStats(n, n * iH * iW, time.perf_counter() - t0, 1, self._copy_s)  # pixels the op saw
 
 
 def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int = 3, split_compare: bool = False, dist=None,
@@ -360,7 +370,8 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
     io_format="yuv" in that format, and with the renderer's HDR settings (`transfer`, `tonemap`, `peak_nits`, `sdr_white`,
     `out_matrix`) when it has them.  A renderer with a `scale` hands its payloads over at the source size and the
     pipeline reduces them as it decodes (FramePipeline scale=); the frames get_image() returns are scaled already.
-    split_baseline, batch (frames per slot and per op call): see FramePipeline."""
+    split_baseline, batch (frames per slot and per op call): see FramePipeline.  Where the op has an output size of its own
+    (FramePipeline: out_shape) the renderer is told so (set_output_size) before the first frame is rendered."""
     self_sharding = getattr(renderer, "world", 1) == world and getattr(renderer, "rank", 0) == rank and hasattr(renderer, "last_index") and world > 1
     yuv_hw = getattr(renderer, "yuv_hw", None) if callable(getattr(renderer, "get_yuv", None)) else None
     get = renderer.get_yuv if yuv_hw is not None else renderer.get_image
@@ -382,6 +393,9 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
     else:
         H, W, _ = first.shape
         pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, split_baseline=split_baseline, batch=batch)
+
+    if pipe is not None and (pipe.out_H, pipe.out_W) != (pipe.op_H, pipe.op_W) and hasattr(renderer, "set_output_size"):
+        renderer.set_output_size(pipe.out_H, pipe.out_W)  # an op with out_shape: the sinks take the pipeline's output size, not the input's
 
     def frames():
         i, f = 0, first

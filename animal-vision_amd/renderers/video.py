@@ -28,7 +28,8 @@ Scaling: `scale=(Wd, Hd)` reduces every source's frames to Wd x 
 get_image() returns scaled frames -- raw and .y4m sources through yuv.yuv_to_rgb_scaled, which decodes straight to the scaled
 frame; HDR sources through yuv.yuv_hdr_to_rgb_scaled, which does the same; the other sources through the resize
 alone.  get_yuv() still hands over source-size payloads and `yuv_hw` still names the source size (pipeline.run_video reduces them
-as it decodes); `out_hw` names the size of what comes out, and every sink is written at that size.
+as it decodes); `out_hw` names the size of what comes out, and every sink is written at that size -- unless the operator that runs
+between source and sink has an output size of its own (the species wall): set_output_size() then names the sinks' size (`sink_hw`).
 
 Sharded streams (two keywords the reference does not have, both defaulted): with `world` > 1 this renderer
 serves and stores only the frames of rank `rank` (global frame i belongs to rank i mod world) -- every source here is
@@ -129,6 +130,7 @@ class VideoRenderer(Renderer):
         self._raw = None             # renderers.rawvideo.RawVideoReader
         self._raw_out = None         # renderers.rawvideo.RawVideoWriter (created by the first render)
         self._merge_size = self.scale or self.size  # (W, H) of the raw sink's frames, for merge_shards()
+        self._sink_hw = None         # set_output_size(): the sinks' frame size where it is not out_hw
         if write_path == "-" and world > 1:
             raise ValueError("stdout is one ordered stream: it can only be written with world = 1")
         self.read_path, self.write_path = read_path, write_path
@@ -221,6 +223,18 @@ class VideoRenderer(Renderer):
         if self._y4m is not None:
             return self._y4m.header.height, self._y4m.header.width
         return None
+
+    def set_output_size(self, H: int, W: int) -> None:
+        """The size of what the sinks are handed when it is not the size of the frames read: an operator with a size of its own
+        (pipeline.FramePipeline with an op that has out_shape, e.g. the species wall).  pipeline.run_video calls it with the
+        pipeline's out_H, out_W; payloads rendered afterwards, and the header of a sink that no frame reached, have this size."""
+        self._sink_hw = (int(H), int(W))
+        self._merge_size = (int(W), int(H))
+
+    @property
+    def sink_hw(self) -> Optional[tuple]:
+        """(H, W) of what the sinks are handed: set_output_size()'s, else out_hw."""
+        return self._sink_hw if self._sink_hw is not None else self.out_hw
 
     def _scaled(self, f: Optional[np.ndarray]) -> Optional[np.ndarray]:
         """An RGB frame of the source's size reduced to `scale` (INTER_AREA on the device)."""
@@ -342,7 +356,7 @@ class VideoRenderer(Renderer):
             if self._y4m_out is None and self._y4m is None:
                 raise ValueError("an I420 payload names no frame size: render an RGB frame first, or read from a .y4m")
             hdr = self._y4m_out.header if self._y4m_out is not None else self._y4m.header
-            H, W = (hdr.height, hdr.width) if self._y4m_out is not None or self.scale is None else self.out_hw  # payloads arrive scaled
+            H, W = (hdr.height, hdr.width) if self._y4m_out is not None or (self.scale is None and self._sink_hw is None) else self.sink_hw  # payloads arrive scaled
             payload = frame
         else:
             raise ValueError(f"a .y4m sink takes RGB uint8 HxWx3 frames or flat uint8 I420 payloads, got {frame.dtype} {frame.shape}")
@@ -364,7 +378,7 @@ class VideoRenderer(Renderer):
         elif frame.ndim == 1 and frame.dtype == np.uint8:
             if self._raw_out is None and (self._raw is None or self.pix_fmt != self.write_pix_fmt):
                 raise ValueError(f"a {self.write_pix_fmt} payload names no frame size: render an RGB frame first, or read raw video in that format")
-            H, W = (self._raw_out.height, self._raw_out.width) if self._raw_out is not None else self.out_hw  # payloads arrive scaled
+            H, W = (self._raw_out.height, self._raw_out.width) if self._raw_out is not None else self.sink_hw  # payloads arrive scaled
             payload = frame
         else:
             raise ValueError(f"a raw video sink takes RGB uint8 HxWx3 frames or flat uint8 {self.write_pix_fmt} payloads, got {frame.dtype} {frame.shape}")
@@ -431,7 +445,7 @@ class VideoRenderer(Renderer):
         self._src = self._frames = None
         if self._y4m_out is None and self._y4m is not None and is_y4m(self.write_path) and self.write_pix_fmt is None:
             # no frame was rendered: the sink is still a valid (empty) stream, its header at the source's size
-            self._open_y4m_sink(*self.out_hw)
+            self._open_y4m_sink(*self.sink_hw)
         if self._y4m_out is not None:
             self._y4m_out.close()
             self._y4m_out = None
@@ -439,7 +453,7 @@ class VideoRenderer(Renderer):
             self._y4m.close()
             self._y4m = None
         if self._raw_out is None and self._raw is not None and self.write_pix_fmt is not None:
-            self._open_raw_sink(*self.out_hw)  # no frame was rendered: an empty file, not a missing one
+            self._open_raw_sink(*self.sink_hw)  # no frame was rendered: an empty file, not a missing one
         if self._raw_out is not None:
             self._raw_out.close()
             self._raw_out = None

@@ -170,6 +170,45 @@ _size_arg = _wxh_arg("--size", "3840x2160")
 _scale_arg = _wxh_arg("--scale", "1920x1080")
 
 
+def check_io_options(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
+    """The checks of the I/O options that depend on each other (the HDR ones, `--matrix bt2020`, `--scale` against a size the
+    command line names), with their defaults filled in; shared by the `video` and `wall` commands.  Errors go through ap.error."""
+    if args.transfer is not None:
+        from .yuv import HDR_PIX_FMTS
+
+        if args.pix_fmt not in HDR_PIX_FMTS:
+            ap.error(f"--transfer needs --pix-fmt naming a 10-bit format ({', '.join(HDR_PIX_FMTS)}); got --pix-fmt {args.pix_fmt}")
+        if args.matrix not in (None, "bt2020"):
+            ap.error(f"--matrix {args.matrix} with --transfer: HDR video is decoded with the bt2020 matrix (--out-matrix names the output's)")
+    else:
+        if args.matrix == "bt2020":
+            ap.error("--matrix bt2020 needs --transfer: bt2020 is decoded on the HDR path only")
+        for flag, v in (("--tonemap", args.tonemap), ("--peak-nits", args.peak_nits), ("--sdr-white", args.sdr_white)):
+            if v is not None:
+                ap.error(f"{flag} needs --transfer")
+    args.tonemap = args.tonemap or "mobius"
+    args.peak_nits = 1000.0 if args.peak_nits is None else args.peak_nits
+    args.sdr_white = 203.0 if args.sdr_white is None else args.sdr_white
+    if not (math.isfinite(args.peak_nits) and math.isfinite(args.sdr_white) and args.sdr_white > 0.0 and args.peak_nits > args.sdr_white):
+        ap.error(f"--peak-nits and --sdr-white must be finite and positive, with --peak-nits above --sdr-white (got {args.peak_nits} and {args.sdr_white})")
+    if args.matrix is None or args.transfer is not None:
+        args.matrix = "bt601"  # what the SDR conversions use; the HDR decode takes no matrix
+    src = args.size  # the source's size where the command line names it: --size, or a synthetic: input
+    if src is None and args.input.startswith("synthetic:"):
+        try:
+            src = _size_arg(args.input.split(":")[1])
+        except (IndexError, argparse.ArgumentTypeError):
+            src = None
+    if args.scale is not None and src is not None and (args.scale[0] > src[0] or args.scale[1] > src[1]):
+        ap.error(f"--scale {args.scale[0]}x{args.scale[1]} enlarges the {src[0]}x{src[1]} source: --scale only reduces")
+
+
+def check_raw_options(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
+    """`--pix-fmt` and `--size` name raw video only together."""
+    if (args.pix_fmt is None) != (args.size is None):
+        ap.error("--pix-fmt and --size go together: raw video carries neither its format nor its size")
+
+
 class _VideoParser(argparse.ArgumentParser):
     """The command's parser; parse_args also checks the options that depend on each other (the HDR ones, `--matrix bt2020`)."""
 
@@ -180,46 +219,20 @@ class _VideoParser(argparse.ArgumentParser):
                 self.error(f"{flag} configures HoneyBee's RGB-to-spectrum conversion: --species {args.species} has none")
         if args.hsi_model not in (None, "seeded") and not os.path.isfile(args.hsi_model):
             self.error(f"--hsi-model {args.hsi_model}: no such file (a local .pth checkpoint, or 'seeded')")
-        if args.transfer is not None:
-            from .yuv import HDR_PIX_FMTS
-
-            if args.pix_fmt not in HDR_PIX_FMTS:
-                self.error(f"--transfer needs --pix-fmt naming a 10-bit format ({', '.join(HDR_PIX_FMTS)}); got --pix-fmt {args.pix_fmt}")
-            if args.matrix not in (None, "bt2020"):
-                self.error(f"--matrix {args.matrix} with --transfer: HDR video is decoded with the bt2020 matrix (--out-matrix names the output's)")
-        else:
-            if args.matrix == "bt2020":
-                self.error("--matrix bt2020 needs --transfer: bt2020 is decoded on the HDR path only")
-            for flag, v in (("--tonemap", args.tonemap), ("--peak-nits", args.peak_nits), ("--sdr-white", args.sdr_white)):
-                if v is not None:
-                    self.error(f"{flag} needs --transfer")
-        args.tonemap = args.tonemap or "mobius"
-        args.peak_nits = 1000.0 if args.peak_nits is None else args.peak_nits
-        args.sdr_white = 203.0 if args.sdr_white is None else args.sdr_white
-        if not (math.isfinite(args.peak_nits) and math.isfinite(args.sdr_white) and args.sdr_white > 0.0 and args.peak_nits > args.sdr_white):
-            self.error(f"--peak-nits and --sdr-white must be finite and positive, with --peak-nits above --sdr-white (got {args.peak_nits} and {args.sdr_white})")
-        if args.matrix is None or args.transfer is not None:
-            args.matrix = "bt601"  # what the SDR conversions use; the HDR decode takes no matrix
-        src = args.size  # the source's size where the command line names it: --size, or a synthetic: input
-        if src is None and args.input.startswith("synthetic:"):
-            try:
-                src = _size_arg(args.input.split(":")[1])
-            except (IndexError, argparse.ArgumentTypeError):
-                src = None
-        if args.scale is not None and src is not None and (args.scale[0] > src[0] or args.scale[1] > src[1]):
-            self.error(f"--scale {args.scale[0]}x{args.scale[1]} enlarges the {src[0]}x{src[1]} source: --scale only reduces")
+        check_io_options(self, args)
         return args
 
 
-def build_parser() -> argparse.ArgumentParser:
-    ap = _VideoParser(prog="video", description="Run one species on every frame of a video (Y4M in and out, or the other VideoRenderer forms).")
+def add_io_arguments(ap: argparse.ArgumentParser) -> None:
+    """INPUT and OUTPUT, as the `video` and `wall` commands take them."""
     ap.add_argument("input", help=".y4m file, '-' (stdin: Y4M, or raw video with --pix-fmt), a raw video file (--pix-fmt), "
                                   "synthetic:<W>x<H>:<n>[:kind], .npy or an image directory")
     ap.add_argument("output", help=".y4m file, '-' (stdout: Y4M, or raw video with --pix-fmt / --out-pix-fmt), a raw video file, .npy or a "
                                    "directory of PNG frames")
-    ap.add_argument("--species", required=True, choices=SPECIES_NAMES, metavar="NAME", help="display name, e.g. Dog, HoneyBee, 'Mantis Shrimp'")
-    ap.add_argument("--split-compare", action="store_true", help="left half original, right half transformed (the reference's output)")
-    ap.add_argument("--no-labels", action="store_true", help="no corner labels on the split frame")
+
+
+def add_input_options(ap: argparse.ArgumentParser) -> None:
+    """The options of the frame pipeline and of the input side (--depth ... --scale), shared by `video` and `wall`."""
     ap.add_argument("--depth", type=int, default=3, help="frames in flight on the device (streamed species)")
     ap.add_argument("--batch", type=_batch_arg, default=1, metavar="N", help="frames per slot and per launch chain, 1..16 (streamed species only)")
     ap.add_argument("--matrix", default=None, choices=["bt601", "bt709", "bt2020"],
@@ -231,13 +244,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--scale", default=None, type=_scale_arg, metavar="WxH",
                     help="reduce every frame to this size on the device as it is decoded (INTER_AREA; never enlarges); the species and OUTPUT "
                          "have this size")
-    ap.add_argument("--hsi-model", default=None, metavar="seeded|PATH",
-                    help="HoneyBee only: take the 31-band cube from the MST++ network instead of the analytic lobes.  PATH is a local .pth "
-                         "checkpoint of the reference's MST++ (its state_dict / module. form); no checkpoint ships with this package, and "
-                         "'seeded' (random weights from a fixed seed) is for testing")
-    ap.add_argument("--hsi-scale", default=None, type=_hsi_scale_arg, metavar="S",
-                    help="HoneyBee only, 0.05 <= S < 1: convert RGB to spectrum on the frame reduced by S and enlarge the three cone catches "
-                         "(hsi_downsample).  With --hsi-model the network runs at the reduced size: a stated quality-for-speed choice")
+
+
+def add_output_options(ap: argparse.ArgumentParser) -> None:
+    """The options of the HDR decode and of the output side (--out-pix-fmt ... --out-matrix), shared by `video` and `wall`."""
     ap.add_argument("--out-pix-fmt", default=None, choices=list(AVX_PIX_FMTS), metavar="NAME",
                     help="write OUTPUT as raw video in this format (default: --pix-fmt when OUTPUT is '-' or ends in .yuv)")
     ap.add_argument("--transfer", default=None, choices=list(AVX_TRANSFERS),
@@ -247,14 +257,30 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sdr-white", default=None, type=float, metavar="X", help="the luminance shown as SDR white (default 203, BT.2408)")
     ap.add_argument("--out-matrix", default=None, choices=["bt601", "bt709"],
                     help="YUV matrix of the output (default: bt709 with --transfer, else --matrix)")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = _VideoParser(prog="video", description="Run one species on every frame of a video (Y4M in and out, or the other VideoRenderer forms).")
+    add_io_arguments(ap)
+    ap.add_argument("--species", required=True, choices=SPECIES_NAMES, metavar="NAME", help="display name, e.g. Dog, HoneyBee, 'Mantis Shrimp'")
+    ap.add_argument("--split-compare", action="store_true", help="left half original, right half transformed (the reference's output)")
+    ap.add_argument("--no-labels", action="store_true", help="no corner labels on the split frame")
+    add_input_options(ap)
+    ap.add_argument("--hsi-model", default=None, metavar="seeded|PATH",
+                    help="HoneyBee only: take the 31-band cube from the MST++ network instead of the analytic lobes.  PATH is a local .pth "
+                         "checkpoint of the reference's MST++ (its state_dict / module. form); no checkpoint ships with this package, and "
+                         "'seeded' (random weights from a fixed seed) is for testing")
+    ap.add_argument("--hsi-scale", default=None, type=_hsi_scale_arg, metavar="S",
+                    help="HoneyBee only, 0.05 <= S < 1: convert RGB to spectrum on the frame reduced by S and enlarge the three cone catches "
+                         "(hsi_downsample).  With --hsi-model the network runs at the reduced size: a stated quality-for-speed choice")
+    add_output_options(ap)
     return ap
 
 
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap = build_parser()
     args = ap.parse_args(argv)
-    if (args.pix_fmt is None) != (args.size is None):
-        ap.error("--pix-fmt and --size go together: raw video carries neither its format nor its size")
+    check_raw_options(ap, args)
     return args
 
 

@@ -57,6 +57,7 @@ int avx_host_alloc(avx_ctx* ctx, size_t bytes, void** out_hptr); /* pinned host 
 int avx_host_free(avx_ctx* ctx, void* hptr);
 int avx_memcpy_h2d(avx_ctx* ctx, void* dst, const void* src_host, size_t bytes, void* stream);
 int avx_memcpy_d2h(avx_ctx* ctx, void* dst_host, const void* src, size_t bytes, void* stream);
+int avx_memcpy_d2d(avx_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream); /* device to device, asynchronous on stream */
 int avx_memset(avx_ctx* ctx, void* dst, int value, size_t bytes, void* stream);
 int avx_stream_create(avx_ctx* ctx, void** out_stream);
 int avx_stream_destroy(avx_ctx* ctx, void* stream);
@@ -289,6 +290,34 @@ typedef struct avx_gallery_tile {
  * canvas must not overlap a source. */
 int avx_gallery_compose_u8(avx_ctx* ctx, const avx_gallery_tile* tiles_host, int n_tiles, const float* segments_host, int n_segments,
                            int strip_h, int pad, int cols, const int bg_rgb[3], uint8_t* canvas_hwc, int Hc, int Wc, void* stream);
+
+/* The species wall: avx_gallery_compose_u8's sheet for a batch of video frames whose tiles are all uint8 H x W x 3
+ * sources of one size, resized to one h x w.  A layout holds everything that does not change from frame to frame -- the resize
+ * mode (avx_gallery_compose_u8's choice: copy, integer-ratio INTER_AREA, general INTER_AREA, INTER_LINEAR when enlarging), the
+ * axis tables, the label segments of the n_tiles tiles (seg_offset / seg_count: rows of segments_host per tile; both may be NULL
+ * with n_segments == 0) and the grid -- on the device.  avx_wall_layout_create is the only call here that allocates, uploads
+ * and synchronises.  The canvas is the gallery's (rows * cell_h + pad) x (cols * cell_w + pad) with each dimension rounded up to
+ * even; the added row or column is bg (4:2:0 sinks get even sizes). */
+typedef struct avx_wall_layout avx_wall_layout;
+int avx_wall_max_tiles(void);                       /* tiles one layout takes (source pointers are kernel arguments): 64 */
+int avx_wall_layout_create(avx_ctx* ctx, int H, int W, int h, int w, int n_tiles, const int* seg_offset, const int* seg_count,
+                           const float* segments_host, int n_segments, int strip_h, int pad, int cols, const int bg_rgb[3],
+                           avx_wall_layout** out_layout);
+int avx_wall_layout_destroy(avx_ctx* ctx, avx_wall_layout* layout);
+int avx_wall_canvas_size(const avx_wall_layout* layout, int* Hc, int* Wc);
+/* What the layout chose (each pointer may be NULL): mode 0 copy / 1 integer-ratio area / 2 area / 3 linear; staged: 1 when a
+ * workgroup's band of source rows goes through LDS, 0 when it does not fit and the samples read the source; the pixels of one
+ * workgroup's piece of a canvas row; the dynamic LDS of a workgroup in bytes. */
+int avx_wall_layout_info(const avx_wall_layout* layout, int* mode, int* staged, int* piece_px, size_t* lds_bytes);
+/* n_frames (<= AVX_EW_MAX_FRAMES) canvases in ONE launch (the frame is a grid dimension): frame f of tile i is read at
+ * src[i] + f * src_frame_stride, its canvas written at canvas + f * canvas_frame_stride (strides in bytes, >= a frame).  src is a
+ * host array of the layout's n_tiles device pointers; they travel as kernel arguments, so the call does no copy, no allocation
+ * and no synchronisation.  Every canvas is byte for byte what avx_gallery_compose_u8 writes for the same tiles, labels, strip_h,
+ * pad, cols and bg on the gallery's extent, and bg outside it.  n_frames == 0: AVX_OK, nothing launched.  AVX_ERR_INVALID before
+ * any launch: NULL pointers, a source overlapping the canvas, strides below a frame, n_frames above the cap, a layout of another
+ * context. */
+int avx_wall_compose_u8(avx_ctx* ctx, const avx_wall_layout* layout, const uint8_t* const* src, size_t src_frame_stride, int n_frames,
+                        uint8_t* canvas, size_t canvas_frame_stride, void* stream);
 
 /* YUV 4:2:0 <-> RGB (Y4M video I/O).  `yuv` is the Y4M payload of n_frames frames back to back: a Y plane of H x W, then U,
  * then V, each ceil(H/2) x ceil(W/2), no padding; `rgb_hwc` is n_frames x H x W x 3.  int32 fixed point with 16 fractional

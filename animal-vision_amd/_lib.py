@@ -170,6 +170,14 @@ class GalleryTile(ctypes.Structure):
     ]
 
 
+class FrameMetricsRecord(ctypes.Structure):
+    """avx_frame_metrics (include/avx.h)."""
+
+    _fields_ = [("abs_hist", (ctypes.c_uint32 * 256) * 3), ("ssim", ctypes.c_double * 3)]
+
+
+AVX_METRICS_MAX_FRAMES = 16  # frames of one avx_frame_metrics_u8 call
+
 class EwInsn(ctypes.Structure):
     _fields_ = [("op", ctypes.c_uint8), ("dst", ctypes.c_uint8), ("a", ctypes.c_uint8), ("b", ctypes.c_uint8), ("imm", ctypes.c_uint32)]
 
@@ -308,6 +316,7 @@ _SIGS = {
     "avx_yuv_hdr_to_rgb_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
     "avx_yuv_to_rgb_scaled_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "avx_yuv_hdr_to_rgb_scaled_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
+    "avx_frame_metrics_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,283 @@
+"""The `compare` command: PSNR, SSIM and code differences of two videos, frame by frame, on the device:
+
+    python -m animal_vision_amd.compare full.y4m half.y4m --csv quality.csv
+    python -m animal_vision_amd.compare a.yuv b.yuv --pix-fmt nv12 --size 3840x2160 --max-abs 1 --max-beyond1 0.002
+
+A and B are any two source forms of renderers.VideoRenderer (.y4m, raw video with --pix-fmt and --size, .npy, an image directory,
+synthetic:); the input-side options of `video` (--pix-fmt, --size, --matrix, --range, --transfer and its options, --scale) apply to
+both.  Frames are compared as a species of `video` would see them: RGB uint8 after decode, tone map and scale.  An input that hands
+over payloads (a .y4m or raw SDR input without --scale) sends them across PCIe and is decoded by yuv.py's device functions into the
+batch buffer; every other input's get_image() frames are uploaded.  Two buffer sets, each with a stream of its own, alternate: the
+upload of batch i + 1 overlaps the kernel of batch i.
+
+One CSV line per frame goes to stdout (or --csv FILE): frame,psnr_r,psnr_g,psnr_b,psnr,ssim_r,ssim_g,ssim_b,ssim,max_abs,beyond1
+(beyond1: the share of samples more than one code apart).  A summary line goes to stderr.  --min-psnr, --min-ssim, --max-abs and
+--max-beyond1 make the command a check: status 1 when a frame violates one (the first such frame is named on stderr).  Inputs of
+different frame sizes are an error before any frame is compared; of different lengths, the common prefix is compared and the status
+is 2 unless --shortest is given."""
+from __future__ import annotations
+
+import argparse
+import itertools
+import math
+import sys
+import time
+from typing import Iterator, Optional, Sequence
+
+import numpy as np
+
+from .metrics import RECORD_BYTES, FrameMetrics, _psnr, frame_metrics_launch, records_from_bytes
+from .video import _size_arg, add_input_options, add_output_options, check_io_options, check_raw_options
+
+CSV_HEADER = "frame,psnr_r,psnr_g,psnr_b,psnr,ssim_r,ssim_g,ssim_b,ssim,max_abs,beyond1"
+_OUTPUT_ONLY = (("--out-pix-fmt", "out_pix_fmt"), ("--out-matrix", "out_matrix"), ("--depth", "depth"))
+
+
+def _num(v: float) -> str:
+    return "inf" if math.isinf(v) else ("nan" if math.isnan(v) else f"{v:.6f}")
+
+
+def format_row(index: int, m: FrameMetrics) -> str:
+    """The CSV line of frame `index`."""
+    p = m.psnr_channels
+    return ",".join([str(index), _num(p[0]), _num(p[1]), _num(p[2]), _num(m.psnr), _num(m.ssim[0]), _num(m.ssim[1]), _num(m.ssim[2]),
+                     _num(m.ssim_mean), str(m.max_abs), f"{m.share_beyond(1):.6g}"])
+
+
+class _CompareParser(argparse.ArgumentParser):
+    def parse_args(self, args=None, namespace=None):
+        args = super().parse_args(args, namespace)
+        for flag, dest in _OUTPUT_ONLY:
+            if getattr(args, dest) is not None:
+                self.error(f"{flag} belongs to a command that writes video: compare writes none")
+        if args.no_ssim and args.min_ssim is not None:
+            self.error("--min-ssim needs the SSIM that --no-ssim skips")
+        if args.a == "-" and args.b == "-":
+            self.error("A and B cannot both be stdin")
+        args.input = args.a  # what check_io_options reads the source size of a synthetic: input from
+        check_io_options(self, args)
+        check_raw_options(self, args)
+        if args.scale is not None and args.size is None and args.b.startswith("synthetic:"):
+            try:
+                src = _size_arg(args.b.split(":")[1])
+            except (IndexError, argparse.ArgumentTypeError):
+                src = None
+            if src is not None and (args.scale[0] > src[0] or args.scale[1] > src[1]):
+                self.error(f"--scale {args.scale[0]}x{args.scale[1]} enlarges the {src[0]}x{src[1]} source: --scale only reduces")
+        return args
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = _CompareParser(prog="compare", description="PSNR, SSIM and code differences of two videos, frame by frame, on the device.")
+    ap.add_argument("a", metavar="A", help=".y4m file, raw video (--pix-fmt), synthetic:<W>x<H>:<n>[:kind], .npy or an image directory")
+    ap.add_argument("b", metavar="B", help="the same forms; the input options apply to both")
+    add_input_options(ap)
+    add_output_options(ap)
+    ap.set_defaults(batch=8, depth=None)
+    ap.add_argument("--no-ssim", action="store_true", help="histograms (PSNR, max_abs, beyond1) only")
+    ap.add_argument("--csv", default=None, metavar="FILE", help="write the per-frame lines here instead of stdout")
+    ap.add_argument("--shortest", action="store_true", help="inputs of different lengths: compare the common prefix without complaint")
+    ap.add_argument("--min-psnr", type=float, default=None, metavar="X", help="status 1 when a frame's PSNR (all channels) is below X dB")
+    ap.add_argument("--min-ssim", type=float, default=None, metavar="X", help="status 1 when a frame's mean SSIM is below X")
+    ap.add_argument("--max-abs", type=int, default=None, metavar="K", help="status 1 when a frame has samples more than K codes apart")
+    ap.add_argument("--max-beyond1", type=float, default=None, metavar="S", help="status 1 when more than the share S of a frame's samples is beyond +-1 code")
+    return ap
+
+
+def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
+    return build_parser().parse_args(argv)
+
+
+def violation(args, m: FrameMetrics) -> Optional[str]:
+    """What frame record `m` violates of the command line's limits, None when nothing."""
+    if args.min_psnr is not None and m.psnr < args.min_psnr:
+        return f"PSNR {_num(m.psnr)} dB is below --min-psnr {args.min_psnr:g}"
+    if args.min_ssim is not None and not m.ssim_mean >= args.min_ssim:
+        return f"SSIM {_num(m.ssim_mean)} is below --min-ssim {args.min_ssim:g}"
+    if args.max_abs is not None and m.max_abs > args.max_abs:
+        return f"largest difference {m.max_abs} is above --max-abs {args.max_abs}"
+    if args.max_beyond1 is not None and m.share_beyond(1) > args.max_beyond1:
+        return f"share beyond +-1 code {m.share_beyond(1):.6g} is above --max-beyond1 {args.max_beyond1:g}"
+    return None
+
+
+# ------------------------------------------------------------------------------------------------ the device loop
+def _renderer(args, path: str):
+    from .renderers import VideoRenderer
+
+    return VideoRenderer(read_path=path, write_path=None, matrix=args.matrix, range=args.range, pix_fmt=args.pix_fmt, size=args.size,
+                         transfer=args.transfer, tonemap=args.tonemap, peak_nits=args.peak_nits, sdr_white=args.sdr_white, scale=args.scale)
+
+
+def _open(args, path: str):
+    """The opened renderer of `path` and the (H, W) of the frames it will be compared at."""
+    vr = _renderer(args, path)
+    vr.open()
+    hw = vr.out_hw
+    if hw is None:  # synthetic:, .npy or an image directory: peek at the first frame, then start over
+        first = vr.get_image()
+        hw = None if first is None else tuple(first.shape[:2])
+        vr.close()
+        vr = _renderer(args, path)
+        vr.open()
+    return vr, hw
+
+
+class _Side:
+    """One input: its staging (pinned) and device buffers, one of each per buffer set."""
+
+    def __init__(self, ctx, vr, H: int, W: int, batch: int, sets: int):
+        from .yuv import frame_size
+
+        self.ctx, self.vr, self.H, self.W = ctx, vr, H, W
+        self.payload = vr.yuv_hw is not None and vr.scale is None and vr.transfer is None
+        self.fmt = vr.yuv_pix_fmt  # None: I420 (.y4m)
+        self.unit = frame_size(self.fmt or "yuv420p", H, W) if self.payload else H * W * 3
+        self.host = [ctx.pinned((batch, self.unit), np.uint8) for _ in range(sets)]
+        self.d_rgb = [ctx.malloc(batch * H * W * 3) for _ in range(sets)]
+        self.d_in = [ctx.malloc(batch * self.unit) for _ in range(sets)] if self.payload else self.d_rgb
+
+    def fill(self, k: int, limit: int) -> int:
+        """Read up to `limit` frames into set k's staging; how many came."""
+        n = 0
+        while n < limit:
+            f = self.vr.get_yuv() if self.payload else self.vr.get_image()
+            if f is None:
+                break
+            f = np.asarray(f)
+            if not self.payload and (f.dtype != np.uint8 or f.shape != (self.H, self.W, 3)):
+                raise SystemExit(f"compare: {self.vr.read_path}: frame {self.vr.last_index} is {f.dtype} {f.shape}, not uint8 {(self.H, self.W, 3)}")
+            self.host[k].array[n] = f.reshape(-1)
+            n += 1
+        return n
+
+    def enqueue(self, k: int, n: int, stream) -> None:
+        from ._lib import lib
+        from .yuv import i420_to_rgb_device, yuv_to_rgb_device
+
+        ctx = self.ctx
+        ctx._check(lib.avx_memcpy_h2d(ctx._h, self.d_in[k].ptr, self.host[k].ptr, n * self.unit, stream))
+        if self.payload and self.fmt is None:
+            i420_to_rgb_device(ctx, self.d_in[k], self.d_rgb[k], n, self.H, self.W, matrix=self.vr.matrix, range=self.vr.yuv_range, stream=stream)
+        elif self.payload:
+            yuv_to_rgb_device(ctx, self.fmt, self.d_in[k], self.d_rgb[k], n, self.H, self.W, matrix=self.vr.matrix, range=self.vr.yuv_range,
+                              stream=stream)
+
+    def free(self) -> None:
+        for b in self.d_rgb + (self.d_in if self.payload else []):
+            b.free()
+        for h in self.host:
+            h.free()
+
+
+def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
+    """The records of the common prefix of args.a and args.b, in frame order.  info["longer"] names the input ("A" / "B") that had
+    frames left over, when one had."""
+    from ._lib import lib
+    from .runtime import get_context
+
+    va, hwa = _open(args, args.a)
+    vb, hwb = _open(args, args.b)
+    sides = []
+    try:
+        if hwa is not None and hwb is not None and tuple(hwa) != tuple(hwb):
+            raise SystemExit(f"compare: frame sizes differ: A is {hwa[1]}x{hwa[0]}, B is {hwb[1]}x{hwb[0]}")
+        if hwa is None or hwb is None:  # an empty input
+            if hwa is not None or hwb is not None:
+                info["longer"] = "A" if hwa is not None else "B"
+            return
+        H, W = hwa
+        ctx, batch, sets = get_context(), args.batch, 2
+        sides = [_Side(ctx, va, H, W, batch, sets), _Side(ctx, vb, H, W, batch, sets)]
+        streams = [ctx.stream_create() for _ in range(sets)]
+        d_out = [ctx.malloc(batch * RECORD_BYTES) for _ in range(sets)]
+        h_out = [ctx.pinned((batch * RECORD_BYTES,), np.uint8) for _ in range(sets)]
+        pending = [0] * sets
+
+        def harvest(k):
+            ctx.sync(streams[k])
+            n, pending[k] = pending[k], 0
+            return records_from_bytes(h_out[k].array, n) if n else []
+
+        try:
+            i = 0
+            while True:
+                k = i % sets
+                yield from harvest(k)  # the set's previous batch: its buffers are free again afterwards
+                na, nb = sides[0].fill(k, batch), sides[1].fill(k, batch)
+                n = min(na, nb)
+                if n:
+                    for s in sides:
+                        s.enqueue(k, n, streams[k])
+                    frame_metrics_launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, d_out[k], ssim=not args.no_ssim, stream=streams[k])
+                    ctx._check(lib.avx_memcpy_d2h(ctx._h, h_out[k].ptr, d_out[k].ptr, n * RECORD_BYTES, streams[k]))
+                    pending[k] = n
+                i += 1
+                if na != nb:
+                    info["longer"] = "A" if na > nb else "B"
+                if n < batch:
+                    break
+            for j in range(sets):
+                yield from harvest((i + j) % sets)
+        finally:
+            for k in range(sets):
+                ctx.sync(streams[k])
+                ctx.stream_destroy(streams[k])
+            for b in d_out:
+                b.free()
+            for h in h_out:
+                h.free()
+    finally:
+        for s in sides:
+            s.free()
+        va.close()
+        vb.close()
+
+
+# ------------------------------------------------------------------------------------------------ the command
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    args = parse_args(argv)
+    info: dict = {}
+    frames, first_bad, worst_abs, min_ssim, sum_ssim = 0, None, 0, math.inf, 0.0
+    sse = samples = beyond = 0
+    t0 = time.perf_counter()
+    records = stream_metrics(args, info)
+    head = list(itertools.islice(records, 1))  # the inputs are opened and their sizes checked before anything is written
+    out = open(args.csv, "w") if args.csv else sys.stdout
+    try:
+        out.write(CSV_HEADER + "\n")
+        for m in itertools.chain(head, records):
+            out.write(format_row(frames, m) + "\n")
+            if first_bad is None:
+                why = violation(args, m)
+                if why is not None:
+                    first_bad = (frames, why)
+            sse += sum(m.sse)
+            samples += 3 * m.samples
+            beyond += m.count_beyond(1)
+            worst_abs = max(worst_abs, m.max_abs)
+            if not args.no_ssim:
+                sum_ssim += m.ssim_mean
+                min_ssim = min(min_ssim, m.ssim_mean)
+            frames += 1
+    finally:
+        if out is not sys.stdout:
+            out.close()
+        else:
+            out.flush()
+    dt = time.perf_counter() - t0
+    ssim_txt = "SSIM skipped" if args.no_ssim or not frames else f"SSIM mean {sum_ssim / frames:.6f} min {min_ssim:.6f}"
+    print(f"compare: {frames} frames, PSNR {_num(_psnr(sse, samples)) if frames else 'nan'} dB, {ssim_txt}, largest difference {worst_abs}, "
+          f"beyond +-1 code {beyond / samples if samples else 0.0:.6g}, {frames / dt if dt > 0 else 0.0:.1f} fps", file=sys.stderr)
+    status = 0
+    if info.get("longer") and not args.shortest:
+        print(f"compare: {info['longer']} has more frames than the other input: compared the first {frames} (--shortest accepts that)", file=sys.stderr)
+        status = 2
+    if first_bad is not None:
+        print(f"compare: frame {first_bad[0]}: {first_bad[1]}", file=sys.stderr)
+        status = 1
+    return status
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,324 @@
+// csrc/metrics.hip -- frame comparison on the device: per frame and channel the exact histogram of absolute code
+// differences of two uint8 RGB batches, and the mean SSIM (Wang et al. 2004: 11 x 11 Gaussian window, sigma 1.5, valid positions).
+//
+// k_metrics_tile: one workgroup per (32 x 32 tile of window positions, frame).  The 42 x 42 patch of both frames goes into LDS once,
+// as bytes and for the three channels together (a patch row is 126 contiguous bytes of the interleaved frame); the histogram of the
+// samples the tile owns is counted on the way.  Per channel the row pass writes the five moment planes a, b, a^2, b^2, ab (42 x 32
+// floats each) into LDS and the column pass keeps its 4 x 5 sums in registers; the samples are centred by 128 before they are squared,
+// so the float32 moments keep their digits where variance and covariance need them.  The SSIM of a position is formed in float32
+// (the products' rounding errors recovered with fma), the positions are summed in float64: a workgroup reduces its own in a fixed order
+// to one double per channel, and k_metrics_final sums the tiles of a (frame, channel) in a fixed order: no floating-point atomics, so
+// a frame's record does not depend on the batch it was in.
+// k_metrics_hist is the histogram alone (with_ssim == 0, or a frame with no window position).
+#include "avx_internal.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int kT = 32;                 // tile: kT x kT window positions
+constexpr int kK = 11;                 // window
+constexpr int kP = kT + kK - 1;        // patch side: 42
+constexpr int kRaw = kP * 3 + 6;       // bytes of a patch row in LDS (132: rows land one bank apart)
+constexpr int kThreads = 256;
+constexpr int kBins = 3 * 256;
+
+struct Taps { float w[kK]; };
+
+__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;
+}
+
+__device__ __forceinline__ void hist_flush(const unsigned* hist, avx_frame_metrics* rec, int tid) {
+    unsigned* dst = &rec->abs_hist[0][0];
+    for (int i = tid; i < kBins; i += kThreads) {
+        const unsigned v = hist[i];
+        if (v) atomicAdd(dst + i, v);
+    }
+}
+
+// one sample pair into the workgroup's histogram; zeros, by far the commonest difference of two renderings of one clip, are
+// counted in a register
+__device__ __forceinline__ void hist_add(unsigned* hist, int c, int a, int b, unsigned& zeros) {
+    const int d = a > b ? a - b : b - a;
+    if (d == 0) ++zeros;
+    else atomicAdd(&hist[c * 256 + d], 1u);
+}
+
+// Row pass of NOUT adjacent positions of patch row `row`, from column x on, for channel C: the NOUT + 10 samples of both frames,
+// centred by 128, and their products stay in registers; the five moment sums go to hp[plane][row][x ...].  NOUT == 4 (x a multiple
+// of 4) reads the bytes as the 11 aligned words that hold them, NOUT == 2 byte by byte.
+template <int NOUT, int C>
+__device__ __forceinline__ void row_item(const uint8_t* raw_a, const uint8_t* raw_b, float* hp, const Taps& tp, int row, int x) {
+    constexpr int NS = NOUT + kK - 1;
+    float a[NS], b[NS];
+    if (NOUT == 4) {
+        const uint32_t* wa = reinterpret_cast<const uint32_t*>(raw_a + row * kRaw + x * 3);
+        const uint32_t* wb = reinterpret_cast<const uint32_t*>(raw_b + row * kRaw + x * 3);
+        uint32_t va[11], vb[11];
+#pragma unroll
+        for (int i = 0; i < 11; ++i) va[i] = wa[i], vb[i] = wb[i];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int byte = 3 * j + C;
+            a[j] = (float)((va[byte >> 2] >> (8 * (byte & 3))) & 255u) - 128.0f;
+            b[j] = (float)((vb[byte >> 2] >> (8 * (byte & 3))) & 255u) - 128.0f;
+        }
+    } else {
+        const uint8_t* ra = raw_a + row * kRaw + x * 3 + C;
+        const uint8_t* rb = raw_b + row * kRaw + x * 3 + C;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            a[j] = (float)ra[3 * j] - 128.0f;
+            b[j] = (float)rb[3 * j] - 128.0f;
+        }
+    }
+    float m[5][NOUT];
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) {
+        m[0][o] = tp.w[0] * a[o];
+        m[1][o] = tp.w[0] * b[o];
+        m[2][o] = tp.w[0] * (a[o] * a[o]);
+        m[3][o] = tp.w[0] * (b[o] * b[o]);
+        m[4][o] = tp.w[0] * (a[o] * b[o]);
+#pragma unroll
+        for (int k = 1; k < kK; ++k) {
+            const float u = a[o + k], v = b[o + k];
+            m[0][o] = fmaf(tp.w[k], u, m[0][o]);
+            m[1][o] = fmaf(tp.w[k], v, m[1][o]);
+            m[2][o] = fmaf(tp.w[k], u * u, m[2][o]);
+            m[3][o] = fmaf(tp.w[k], v * v, m[3][o]);
+            m[4][o] = fmaf(tp.w[k], u * v, m[4][o]);
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < 5; ++p) {
+        float* dst = hp + (p * kP + row) * kT + x;
+        if (NOUT == 4) *reinterpret_cast<float4*>(dst) = make_float4(m[p][0], m[p][1], m[p][2], m[p][3]);
+        else *reinterpret_cast<float2*>(dst) = make_float2(m[p][0], m[p][1]);
+    }
+}
+
+// One channel of a tile: row pass into hp, column pass in registers, the SSIM of the thread's 4 positions, the workgroup's sum.
+template <bool EDGE, int C>
+__device__ __forceinline__ void channel_pass(int H, int W, int x0, int y0, const Taps& tp, const uint8_t* raw_a, const uint8_t* raw_b, float* hp,
+                                             double* red, double* part) {
+    const int tid = threadIdx.x;
+    // ---- row pass: the first kT patch rows as 256 items of 4 positions, the other 10 as 160 items of 2: every wave stays busy ----
+    row_item<4, C>(raw_a, raw_b, hp, tp, tid >> 3, (tid & 7) * 4);
+    if (tid < (kP - kT) * (kT / 2)) row_item<2, C>(raw_a, raw_b, hp, tp, kT + (tid >> 4), (tid & 15) * 2);
+    __syncthreads();
+    // ---- column pass: 4 positions of one column per thread ----
+    const int col = tid & (kT - 1), seg = tid >> 5;
+    float acc[5][4];
+#pragma unroll
+    for (int p = 0; p < 5; ++p) {
+        float v[14];
+#pragma unroll
+        for (int k = 0; k < 14; ++k) v[k] = hp[(p * kP + seg * 4 + k) * kT + col];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            float s = tp.w[0] * v[o];
+#pragma unroll
+            for (int k = 1; k < kK; ++k) s = fmaf(tp.w[k], v[o + k], s);
+            acc[p][o] = s;
+        }
+    }
+    // ---- SSIM.  E[x^2] - mu^2 loses nothing to float32: the rounding error of the product is recovered with an fma and taken
+    // off the difference, so variance and covariance carry a relative error of 2^-23, not one of the size of mu^2. ----
+    const float C1 = 6.5025f, C2 = 58.5225f;  // (0.01 * 255)^2, (0.03 * 255)^2
+    double sum = 0.0;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        if (EDGE && !(x0 + col < W - (kK - 1) && y0 + seg * 4 + o < H - (kK - 1))) continue;
+        const float ma = acc[0][o], mb = acc[1][o];
+        const float paa = ma * ma, pbb = mb * mb, pab = ma * mb;
+        const float va = (acc[2][o] - paa) - fmaf(ma, ma, -paa);
+        const float vb = (acc[3][o] - pbb) - fmaf(mb, mb, -pbb);
+        const float cab = (acc[4][o] - pab) - fmaf(ma, mb, -pab);
+        const float ua = ma + 128.0f, ub = mb + 128.0f;
+        const float num = (2.0f * (ua * ub) + C1) * (2.0f * cab + C2);
+        const float den = ((ua * ua + ub * ub) + C1) * ((va + vb) + C2);
+        sum += (double)(num / den);
+    }
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
+    if ((tid & 63) == 0) red[tid >> 6] = sum;
+    __syncthreads();  // also: every column pass has read hp before the next channel's row pass writes it
+    if (tid == 0) *part = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+template <bool EDGE>
+__device__ __forceinline__ void tile_body(const uint8_t* __restrict__ fa, const uint8_t* __restrict__ fb, int H, int W, int x0, int y0,
+                                          int own_w, int own_h, const Taps& tp, uint8_t* raw_a, uint8_t* raw_b, float* hp, unsigned* hist,
+                                          double* red, double* part, size_t part_stride) {
+    const int tid = threadIdx.x;
+    // ---- patch -> LDS (bytes, three channels), histogram of the owned samples ----
+    unsigned z0 = 0, z1 = 0, z2 = 0;
+    for (int p = tid; p < kP * kP; p += kThreads) {
+        const int py = p / kP, px = p - py * kP;
+        int a0 = 128, a1 = 128, a2 = 128, b0 = 128, b1 = 128, b2 = 128;  // outside the frame: centred zero, never part of a valid window
+        if (!EDGE || (y0 + py < H && x0 + px < W)) {
+            const size_t off = ((size_t)(y0 + py) * W + (x0 + px)) * 3;
+            a0 = fa[off], a1 = fa[off + 1], a2 = fa[off + 2];
+            b0 = fb[off], b1 = fb[off + 1], b2 = fb[off + 2];
+            if (px < own_w && py < own_h) {
+                hist_add(hist, 0, a0, b0, z0);
+                hist_add(hist, 1, a1, b1, z1);
+                hist_add(hist, 2, a2, b2, z2);
+            }
+        }
+        uint8_t* wa = raw_a + py * kRaw + px * 3;
+        uint8_t* wb = raw_b + py * kRaw + px * 3;
+        wa[0] = (uint8_t)a0, wa[1] = (uint8_t)a1, wa[2] = (uint8_t)a2;
+        wb[0] = (uint8_t)b0, wb[1] = (uint8_t)b1, wb[2] = (uint8_t)b2;
+    }
+    z0 = wave_sum_u32(z0), z1 = wave_sum_u32(z1), z2 = wave_sum_u32(z2);
+    if ((tid & 63) == 0) {
+        if (z0) atomicAdd(&hist[0], z0);
+        if (z1) atomicAdd(&hist[256], z1);
+        if (z2) atomicAdd(&hist[512], z2);
+    }
+    __syncthreads();
+
+    channel_pass<EDGE, 0>(H, W, x0, y0, tp, raw_a, raw_b, hp, red, part);
+    channel_pass<EDGE, 1>(H, W, x0, y0, tp, raw_a, raw_b, hp, red, part + part_stride);
+    channel_pass<EDGE, 2>(H, W, x0, y0, tp, raw_a, raw_b, hp, red, part + 2 * part_stride);
+}
+
+__global__ __launch_bounds__(kThreads) void k_metrics_tile(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int H, int W, Taps tp,
+                                                           double* __restrict__ partials, avx_frame_metrics* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) uint8_t raw_a[kP * kRaw];
+    __shared__ __attribute__((aligned(16))) uint8_t raw_b[kP * kRaw];
+    __shared__ __attribute__((aligned(16))) float hp[5 * kP * kT];
+    __shared__ unsigned hist[kBins];
+    __shared__ double red[kThreads / 64];
+    const int tid = threadIdx.x, f = blockIdx.z;
+    for (int i = tid; i < kBins; i += kThreads) hist[i] = 0;
+    __syncthreads();
+    const int x0 = blockIdx.x * kT, y0 = blockIdx.y * kT;
+    // the samples this tile counts: its kT x kT corner of the patch, and the rest of the frame for the last tile of a row / column
+    const int own_w = blockIdx.x == gridDim.x - 1 ? W - x0 : kT, own_h = blockIdx.y == gridDim.y - 1 ? H - y0 : kT;
+    const size_t fo = (size_t)f * H * W * 3;
+    const size_t ntiles = (size_t)gridDim.x * gridDim.y;
+    double* part = partials + (size_t)f * 3 * ntiles + ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+    if (x0 + kP <= W && y0 + kP <= H)  // the whole patch lies in the frame: no bounds tests
+        tile_body<false>(a + fo, b + fo, H, W, x0, y0, own_w, own_h, tp, raw_a, raw_b, hp, hist, red, part, ntiles);
+    else
+        tile_body<true>(a + fo, b + fo, H, W, x0, y0, own_w, own_h, tp, raw_a, raw_b, hp, hist, red, part, ntiles);
+    hist_flush(hist, out + f, tid);  // the last barrier of tile_body is behind every histogram update
+}
+
+// sum of the tile partials of one (channel, frame) in a fixed order: thread t adds tiles t, t + 256, ..., then a fixed tree
+__global__ __launch_bounds__(kThreads) void k_metrics_final(const double* __restrict__ partials, size_t ntiles, double count,
+                                                            avx_frame_metrics* __restrict__ out) {
+    __shared__ double red[kThreads];
+    const int tid = threadIdx.x, c = blockIdx.x, f = blockIdx.y;
+    const double* p = partials + ((size_t)f * 3 + c) * ntiles;
+    double s = 0.0;
+    for (size_t t = tid; t < ntiles; t += kThreads) s += p[t];
+    red[tid] = s;
+    __syncthreads();
+    for (int o = kThreads / 2; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) out[f].ssim[c] = red[0] / count;
+}
+
+// histogram alone: grid (blocks, frames); VEC: 16 bytes of both frames per thread and step
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_metrics_hist(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, size_t frame_bytes,
+                                                           avx_frame_metrics* __restrict__ out) {
+    __shared__ unsigned hist[kBins];
+    const int tid = threadIdx.x, f = blockIdx.y;
+    for (int i = tid; i < kBins; i += kThreads) hist[i] = 0;
+    __syncthreads();
+    const uint8_t* fa = a + (size_t)f * frame_bytes;
+    const uint8_t* fb = b + (size_t)f * frame_bytes;
+    unsigned z0 = 0, z1 = 0, z2 = 0;  // zeros per channel, in registers
+    const size_t step = (size_t)gridDim.x * kThreads;
+    if (VEC) {
+        const size_t n = frame_bytes / 16;
+        for (size_t i = (size_t)blockIdx.x * kThreads + tid; i < n; i += step) {
+            const uint4 va = reinterpret_cast<const uint4*>(fa)[i], vb = reinterpret_cast<const uint4*>(fb)[i];
+            const unsigned wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
+            const int c0 = (int)((i * 16) % 3);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int c = (c0 + k) % 3;
+                const int x = (wa[k >> 2] >> (8 * (k & 3))) & 255, y = (wb[k >> 2] >> (8 * (k & 3))) & 255;
+                const int d = x > y ? x - y : y - x;
+                if (d == 0) z0 += c == 0, z1 += c == 1, z2 += c == 2;
+                else atomicAdd(&hist[c * 256 + d], 1u);
+            }
+        }
+    } else {
+        for (size_t i = (size_t)blockIdx.x * kThreads + tid; i < frame_bytes; i += step) {
+            const int c = (int)(i % 3), x = fa[i], y = fb[i];
+            const int d = x > y ? x - y : y - x;
+            if (d == 0) z0 += c == 0, z1 += c == 1, z2 += c == 2;
+            else atomicAdd(&hist[c * 256 + d], 1u);
+        }
+    }
+    z0 = wave_sum_u32(z0), z1 = wave_sum_u32(z1), z2 = wave_sum_u32(z2);
+    if ((tid & 63) == 0) {
+        if (z0) atomicAdd(&hist[0], z0);
+        if (z1) atomicAdd(&hist[256], z1);
+        if (z2) atomicAdd(&hist[512], z2);
+    }
+    __syncthreads();
+    hist_flush(hist, out + f, tid);
+    if (blockIdx.x == 0 && tid < 3) out[f].ssim[tid] = __longlong_as_double(0x7ff8000000000000LL);
+}
+
+}  // namespace
+
+extern "C" int avx_frame_metrics_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int with_ssim,
+                                    avx_frame_metrics* out_dev, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, a_hwc && b_hwc && out_dev, "avx_frame_metrics_u8: NULL buffer (a %p, b %p, out %p)", (const void*)a_hwc, (const void*)b_hwc,
+                (void*)out_dev);
+    AVX_REQUIRE(ctx, n_frames >= 1 && n_frames <= 16, "avx_frame_metrics_u8: n_frames must be 1..16 (got %d)", n_frames);
+    AVX_REQUIRE(ctx, H >= 1 && W >= 1 && (uint64_t)H * (uint64_t)W < (1ull << 32), "avx_frame_metrics_u8: bad frame size %d x %d (H * W must be below 2^32)",
+                H, W);
+    AVX_REQUIRE(ctx, ((uintptr_t)out_dev & 7) == 0, "avx_frame_metrics_u8: out_dev must be 8-byte aligned");
+    const bool ssim = with_ssim != 0 && H >= kK && W >= kK;
+    const unsigned ntx = ssim ? (unsigned)((W - (kK - 1) + kT - 1) / kT) : 0, nty = ssim ? (unsigned)((H - (kK - 1) + kT - 1) / kT) : 0;
+    AVX_REQUIRE(ctx, nty <= 65535u, "avx_frame_metrics_u8: %d rows are more than the SSIM kernel's grid takes (%d)", H, 65535 * kT + kK - 1);
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    double* partials = nullptr;
+    const size_t ntiles = (size_t)ntx * nty;
+    if (ssim) {
+        avx_ws* ws = avx_workspace(ctx, s);
+        if (!ws) return AVX_ERR_NOMEM;
+        const int rc = avx_ensure_scratch(ctx, ws, sizeof(double) * 3 * ntiles * (size_t)n_frames);
+        if (rc) return rc;
+        partials = (double*)ws->d_scratch;
+    }
+    AVX_HIP(ctx, hipMemsetAsync(out_dev, 0, sizeof(avx_frame_metrics) * (size_t)n_frames, s));
+    if (ssim) {
+        double g[kK], sum = 0.0;
+        for (int k = 0; k < kK; ++k) sum += g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
+        Taps tp;
+        for (int k = 0; k < kK; ++k) tp.w[k] = (float)(g[k] / sum);
+        hipLaunchKernelGGL(k_metrics_tile, dim3(ntx, nty, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, H, W, tp, partials, out_dev);
+        AVX_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_metrics_final, dim3(3, n_frames), dim3(kThreads), 0, s, (const double*)partials, ntiles,
+                           (double)(H - (kK - 1)) * (double)(W - (kK - 1)), out_dev);
+    } else {
+        const size_t fbytes = (size_t)H * W * 3;
+        const bool vec = fbytes % 16 == 0 && (((uintptr_t)a_hwc | (uintptr_t)b_hwc) & 15) == 0;
+        const size_t units = vec ? fbytes / 16 : fbytes;
+        size_t blocks = (units + kThreads - 1) / kThreads;
+        const size_t cap = (size_t)ctx->num_cus * 8;
+        if (blocks > cap) blocks = cap;
+        if (vec)
+            hipLaunchKernelGGL(k_metrics_hist<true>, dim3((unsigned)blocks, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, fbytes, out_dev);
+        else
+            hipLaunchKernelGGL(k_metrics_hist<false>, dim3((unsigned)blocks, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, fbytes, out_dev);
+    }
+    AVX_HIP(ctx, hipGetLastError());
+    return AVX_OK;
+}

@@ -396,6 +396,26 @@ int avx_yuv_to_rgb_scaled_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t*
 int avx_yuv_hdr_to_rgb_scaled_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t* rgb_hwc, int n_frames, int H, int W, int Hd, int Wd,
                                  int full_range, int transfer, int tonemap, double peak_nits, double sdr_white, void* stream);
 
+/* Frame comparison (csrc/metrics.hip): what two batches of uint8 RGB frames differ by, per frame and channel. */
+typedef struct avx_frame_metrics {
+    uint32_t abs_hist[3][256]; /* [c][k]: samples of channel c with |a - b| == k; each row sums to H*W */
+    double   ssim[3];          /* mean SSIM of channel c over the (H-10) x (W-10) window positions;    */
+                               /* NaN when with_ssim == 0 or H < 11 or W < 11                          */
+} avx_frame_metrics;
+
+/* a_hwc, b_hwc: n_frames contiguous H x W x 3 uint8 frames on the device; out_dev: n_frames records on the device (8-byte aligned).
+ * Asynchronous on `stream`.  1 <= n_frames <= 16, H*W < 2^32.  The histogram is exact and covers every sample: SSE, PSNR, the
+ * largest difference and the share of samples beyond +-k codes follow from it without rounding.  SSIM is Wang et al. 2004 as
+ * skimage computes it with gaussian_weights=True, use_sample_covariance=False: per channel an 11 x 11 separable Gaussian window,
+ * sigma 1.5, taps normalised to sum 1 in float64; valid positions only; C1 = (0.01*255)^2, C2 = (0.03*255)^2;
+ * (2 mu_a mu_b + C1)(2 s_ab + C2) / ((mu_a^2 + mu_b^2 + C1)(s_a^2 + s_b^2 + C2)) with s^2 = E[x^2] - mu^2; the mean over positions.
+ * The moments and the quotient are float32, on samples centred by 128; every sum over positions is float64 in a fixed order
+ * (no floating-point atomics): a frame's record is bit-identical whichever batch and batch position it was computed in, and from run
+ * to run; identical frames give exactly 1.0.  AVX_ERR_INVALID (avx_last_error starts with this function's name) for a NULL
+ * buffer, n_frames outside 1..16 and a bad size; nothing is launched then. */
+int avx_frame_metrics_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W,
+                         int with_ssim, avx_frame_metrics* out_dev, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

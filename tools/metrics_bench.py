@@ -1,0 +1,107 @@
+"""Time of the frame-metrics kernel and of the compare command.  Not part of bench.py.
+
+  python tools/metrics_bench.py kernel [--reps 7]
+      avx_frame_metrics_u8 on frames resident on the device, 1080p and 4K, batches of 1 and 8, with and without SSIM: every
+      repetition between its own pair of stream events (the record memset and the final-reduction launch included), after one warm-up
+      call.  One JSON line per configuration: median (min-max) in us per frame, and what the 6 B/px both frames hold would take at
+      6.29 TB/s (the measured HBM copy rate, MI355X).  The frames are noise against the same noise +-2 codes: most differences are 0,
+      1 or 2, as between two renderings of one clip, which is also the worst case of the histogram's LDS atomics.
+  python tools/metrics_bench.py command [--frames 32] [--reps 3] [--dir DIR]
+      Two 4K nv12 files of `frames` frames in DIR (default: /dev/shm when there is one, so they are read from memory) through
+      python -m animal_vision_amd.compare's main(), --batch 8, with and without SSIM: frames per second of the whole command (read,
+      upload, decode, compare, CSV), `reps` runs each after one warm-up run."""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+COPY_BPS = 6.29e12
+SIZES = {"1080p": (1080, 1920), "4k": (2160, 3840)}
+
+
+def _pair(n, H, W, seed=0):
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8)
+    b = np.clip(a.astype(np.int16) + rng.integers(-2, 3, a.shape, dtype=np.int16), 0, 255).astype(np.uint8)
+    return a, b
+
+
+def kernel(args):
+    from animal_vision_amd.metrics import RECORD_BYTES, frame_metrics_launch
+    from animal_vision_amd.runtime import get_context
+
+    ctx = get_context()
+    for name, (H, W) in SIZES.items():
+        a, b = _pair(8, H, W)
+        d_a, d_b, d_out = ctx.upload(a), ctx.upload(b), ctx.malloc(8 * RECORD_BYTES)
+        for n in (1, 8):
+            for ssim in (True, False):
+                frame_metrics_launch(ctx, d_a, d_b, n, H, W, d_out, ssim=ssim)  # warm-up: the workspace is sized here
+                ctx.sync()
+                each = []
+                for _ in range(args.reps):
+                    ctx.timer_start()
+                    frame_metrics_launch(ctx, d_a, d_b, n, H, W, d_out, ssim=ssim)
+                    each.append(ctx.timer_stop() * 1e3 / n)
+                floor = 6.0 * H * W / COPY_BPS * 1e6
+                print(json.dumps({"size": name, "batch": n, "ssim": ssim, "reps": args.reps, "us_per_frame_median": round(float(np.median(each)), 1),
+                                  "us_per_frame_min": round(min(each), 1), "us_per_frame_max": round(max(each), 1),
+                                  "us_6B_per_px_at_6.29TBps": round(floor, 1), "x_copy_floor": round(float(np.median(each)) / floor, 1)}), flush=True)
+        for d in (d_a, d_b, d_out):
+            d.free()
+
+
+def command(args):
+    from animal_vision_amd import compare
+    from animal_vision_amd.yuv import rgb_to_yuv
+
+    H, W = SIZES["4k"]
+    base = args.dir or ("/dev/shm" if os.path.isdir("/dev/shm") else None)
+    with tempfile.TemporaryDirectory(dir=base) as d:
+        a, b = _pair(4, H, W)
+        pa, pb = [rgb_to_yuv(f, pix_fmt="nv12") for f in a], [rgb_to_yuv(f, pix_fmt="nv12") for f in b]
+        for path, pay in ((os.path.join(d, "a.yuv"), pa), (os.path.join(d, "b.yuv"), pb)):
+            with open(path, "wb") as f:
+                for i in range(args.frames):
+                    f.write(pay[i % len(pay)].tobytes())
+        argv = [os.path.join(d, "a.yuv"), os.path.join(d, "b.yuv"), "--pix-fmt", "nv12", "--size", f"{W}x{H}", "--batch", "8",
+                "--csv", os.path.join(d, "out.csv")]
+        for extra in ([], ["--no-ssim"]):
+            fps = []
+            for rep in range(args.reps + 1):
+                t0 = time.perf_counter()
+                with contextlib.redirect_stderr(io.StringIO()):
+                    status = compare.main(argv + extra)
+                dt = time.perf_counter() - t0
+                assert status == 0, status
+                if rep:  # the first run is the warm-up
+                    fps.append(args.frames / dt)
+            print(json.dumps({"command": "compare", "size": "4k", "pix_fmt": "nv12", "frames": args.frames, "batch": 8, "ssim": not extra,
+                              "reps": args.reps, "fps_median": round(float(np.median(fps)), 1), "fps_min": round(min(fps), 1),
+                              "fps_max": round(max(fps), 1)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    k = sub.add_parser("kernel")
+    k.add_argument("--reps", type=int, default=7)
+    c = sub.add_parser("command")
+    c.add_argument("--frames", type=int, default=32)
+    c.add_argument("--reps", type=int, default=3)
+    c.add_argument("--dir", default=None)
+    args = ap.parse_args()
+    {"kernel": kernel, "command": command}[args.cmd](args)
+
+
+if __name__ == "__main__":
+    main()

@@ -2,6 +2,7 @@
 
     python -m animal_vision_amd.compare full.y4m half.y4m --csv quality.csv
     python -m animal_vision_amd.compare a.yuv b.yuv --pix-fmt nv12 --size 3840x2160 --max-abs 1 --max-beyond1 0.002
+    python -m animal_vision_amd.compare a.yuv b.yuv --pix-fmt p010le --size 3840x2160 --planes yuv --max-abs 1
 
 A and B are any two source forms of renderers.VideoRenderer (.y4m, raw video with --pix-fmt and --size, .npy, an image directory,
 synthetic:); the input-side options of `video` (--pix-fmt, --size, --matrix, --range, --transfer and its options, --scale) apply to
@@ -14,22 +15,30 @@ One CSV line per frame goes to stdout (or --csv FILE): frame,psnr_r,psnr_g,psnr_
 (beyond1: the share of samples more than one code apart).  A summary line goes to stderr.  --min-psnr, --min-ssim, --max-abs and
 --max-beyond1 make the command a check: status 1 when a frame violates one (the first such frame is named on stderr).  Inputs of
 different frame sizes are an error before any frame is compared; of different lengths, the common prefix is compared and the status
-is 2 unless --shortest is given."""
+is 2 unless --shortest is given.
+
+--planes yuv compares video in its own Y, U and V planes instead: both inputs hand over payloads (.y4m, or raw video with
+--pix-fmt and --size; a .y4m is I420 whatever --pix-fmt says), which go into the batch buffers and straight to avx_plane_metrics -- no
+decode, no RGB buffer, 10-bit files in 10-bit codes.  The lines are frame,psnr_y,psnr_u,psnr_v,psnr,ssim_y,ssim_u,ssim_v,ssim,max_abs,
+beyond1 (psnr: pooled over all samples, ffmpeg's `average`; ssim: the planes weighted by their sample counts; absent planes: nan)."""
 from __future__ import annotations
 
 import argparse
 import itertools
 import math
+import os
 import sys
 import time
 from typing import Iterator, Optional, Sequence
 
 import numpy as np
 
-from .metrics import RECORD_BYTES, FrameMetrics, _psnr, frame_metrics_launch, records_from_bytes
+from .metrics import (PLANE_RECORD_BYTES, RECORD_BYTES, FrameMetrics, PlaneMetrics, _psnr, check_plane_formats, frame_metrics_launch,
+                      plane_metrics_launch, plane_records_from_bytes, records_from_bytes)
 from .video import _size_arg, add_input_options, add_output_options, check_io_options, check_raw_options
 
 CSV_HEADER = "frame,psnr_r,psnr_g,psnr_b,psnr,ssim_r,ssim_g,ssim_b,ssim,max_abs,beyond1"
+CSV_HEADER_YUV = "frame,psnr_y,psnr_u,psnr_v,psnr,ssim_y,ssim_u,ssim_v,ssim,max_abs,beyond1"
 _OUTPUT_ONLY = (("--out-pix-fmt", "out_pix_fmt"), ("--out-matrix", "out_matrix"), ("--depth", "depth"))
 
 
@@ -44,6 +53,40 @@ def format_row(index: int, m: FrameMetrics) -> str:
                      _num(m.ssim_mean), str(m.max_abs), f"{m.share_beyond(1):.6g}"])
 
 
+def format_row_planes(index: int, m: PlaneMetrics) -> str:
+    """The CSV line of frame `index` with --planes yuv."""
+    p = m.psnr_planes
+    return ",".join([str(index), _num(p[0]), _num(p[1]), _num(p[2]), _num(m.psnr), _num(m.ssim[0]), _num(m.ssim[1]), _num(m.ssim[2]),
+                     _num(m.ssim_mean), str(m.max_abs), f"{m.share_beyond(1):.6g}"])
+
+
+def _is_y4m_file(path: str) -> bool:
+    return path.lower().endswith(".y4m")
+
+
+def plane_format(args, path: str) -> str:
+    """The pixel format `path` hands its payloads over in with --planes yuv: a .y4m file (and stdin without --pix-fmt) is I420."""
+    return "yuv420p" if _is_y4m_file(path) or args.pix_fmt is None else args.pix_fmt
+
+
+def _check_planes_yuv(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
+    """--planes yuv: payloads as stored, so nothing that works on RGB, and two formats of one depth and subsampling."""
+    if args.scale is not None:
+        ap.error("--scale reduces RGB frames: --planes yuv compares the planes as stored")
+    for flag, v in (("--transfer", args.transfer), ("--tonemap", args.tonemap), ("--peak-nits", args.peak_nits), ("--sdr-white", args.sdr_white)):
+        if v is not None:
+            ap.error(f"{flag} tone-maps to SDR RGB: --planes yuv compares HDR files as stored")
+    for name, path in (("A", args.a), ("B", args.b)):
+        if path.startswith("synthetic:") or path.lower().endswith(".npy") or os.path.isdir(path):
+            ap.error(f"{name} ({path}): .npy, image directories and synthetic: carry RGB; --planes yuv needs a .y4m or raw video (--pix-fmt, --size)")
+        if not _is_y4m_file(path) and path != "-" and args.pix_fmt is None:
+            ap.error(f"{name} ({path}): --planes yuv needs a .y4m, or raw video with --pix-fmt and --size")
+    try:
+        check_plane_formats(plane_format(args, args.a), plane_format(args, args.b))
+    except ValueError as e:
+        ap.error(f"--planes yuv: A and B: {e}")
+
+
 class _CompareParser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         args = super().parse_args(args, namespace)
@@ -54,6 +97,8 @@ class _CompareParser(argparse.ArgumentParser):
             self.error("--min-ssim needs the SSIM that --no-ssim skips")
         if args.a == "-" and args.b == "-":
             self.error("A and B cannot both be stdin")
+        if args.planes == "yuv":
+            _check_planes_yuv(self, args)
         args.input = args.a  # what check_io_options reads the source size of a synthetic: input from
         check_io_options(self, args)
         check_raw_options(self, args)
@@ -74,6 +119,11 @@ def build_parser() -> argparse.ArgumentParser:
     add_input_options(ap)
     add_output_options(ap)
     ap.set_defaults(batch=8, depth=None)
+    ap.add_argument("--planes", default="rgb", choices=["rgb", "yuv"],
+                    help="rgb (default): compare RGB uint8 after decode, tone map and scale.  yuv: compare the Y, U and V planes as stored, at "
+                         "8 or 10 bits, in native codes (PSNR-Y/U/V; .y4m or raw video only; a .y4m is I420 whatever --pix-fmt says, so it "
+                         "compares against a raw nv12 or yuv420p file); --matrix and --range are accepted and have no effect, --scale and "
+                         "--transfer are errors")
     ap.add_argument("--no-ssim", action="store_true", help="histograms (PSNR, max_abs, beyond1) only")
     ap.add_argument("--csv", default=None, metavar="FILE", help="write the per-frame lines here instead of stdout")
     ap.add_argument("--shortest", action="store_true", help="inputs of different lengths: compare the common prefix without complaint")
@@ -105,6 +155,9 @@ def violation(args, m: FrameMetrics) -> Optional[str]:
 def _renderer(args, path: str):
     from .renderers import VideoRenderer
 
+    if getattr(args, "planes", "rgb") == "yuv":
+        raw = not _is_y4m_file(path) and args.pix_fmt is not None
+        return VideoRenderer(read_path=path, write_path=None, pix_fmt=args.pix_fmt if raw else None, size=args.size if raw else None)
     return VideoRenderer(read_path=path, write_path=None, matrix=args.matrix, range=args.range, pix_fmt=args.pix_fmt, size=args.size,
                          transfer=args.transfer, tonemap=args.tonemap, peak_nits=args.peak_nits, sdr_white=args.sdr_white, scale=args.scale)
 
@@ -170,6 +223,42 @@ class _Side:
             h.free()
 
 
+class _PlaneSide:
+    """One input of --planes yuv: payloads only, staged (pinned) and uploaded as they are stored; one buffer of each per set."""
+
+    def __init__(self, ctx, vr, H: int, W: int, batch: int, sets: int):
+        from .yuv import frame_size
+
+        if vr.yuv_hw is None:
+            raise SystemExit(f"compare: {vr.read_path}: --planes yuv needs a .y4m or raw video input")
+        self.ctx, self.vr = ctx, vr
+        self.fmt = vr.yuv_pix_fmt or "yuv420p"
+        self.unit = frame_size(self.fmt, H, W)
+        self.host = [ctx.pinned((batch, self.unit), np.uint8) for _ in range(sets)]
+        self.d_in = [ctx.malloc(batch * self.unit) for _ in range(sets)]
+
+    def fill(self, k: int, limit: int) -> int:
+        n = 0
+        while n < limit:
+            f = self.vr.get_yuv()
+            if f is None:
+                break
+            self.host[k].array[n] = np.asarray(f).reshape(-1)
+            n += 1
+        return n
+
+    def enqueue(self, k: int, n: int, stream) -> None:
+        from ._lib import lib
+
+        self.ctx._check(lib.avx_memcpy_h2d(self.ctx._h, self.d_in[k].ptr, self.host[k].ptr, n * self.unit, stream))
+
+    def free(self) -> None:
+        for b in self.d_in:
+            b.free()
+        for h in self.host:
+            h.free()
+
+
 def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
     """The records of the common prefix of args.a and args.b, in frame order.  info["longer"] names the input ("A" / "B") that had
     frames left over, when one had."""
@@ -188,15 +277,21 @@ def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
             return
         H, W = hwa
         ctx, batch, sets = get_context(), args.batch, 2
-        sides = [_Side(ctx, va, H, W, batch, sets), _Side(ctx, vb, H, W, batch, sets)]
+        yuv = getattr(args, "planes", "rgb") == "yuv"
+        rec_bytes = PLANE_RECORD_BYTES if yuv else RECORD_BYTES
+        side = _PlaneSide if yuv else _Side
+        sides.append(side(ctx, va, H, W, batch, sets))
+        sides.append(side(ctx, vb, H, W, batch, sets))
         streams = [ctx.stream_create() for _ in range(sets)]
-        d_out = [ctx.malloc(batch * RECORD_BYTES) for _ in range(sets)]
-        h_out = [ctx.pinned((batch * RECORD_BYTES,), np.uint8) for _ in range(sets)]
+        d_out = [ctx.malloc(batch * rec_bytes) for _ in range(sets)]
+        h_out = [ctx.pinned((batch * rec_bytes,), np.uint8) for _ in range(sets)]
         pending = [0] * sets
 
         def harvest(k):
             ctx.sync(streams[k])
             n, pending[k] = pending[k], 0
+            if yuv:
+                return plane_records_from_bytes(h_out[k].array, n, sides[0].fmt, H, W) if n else []
             return records_from_bytes(h_out[k].array, n) if n else []
 
         try:
@@ -209,8 +304,13 @@ def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
                 if n:
                     for s in sides:
                         s.enqueue(k, n, streams[k])
-                    frame_metrics_launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, d_out[k], ssim=not args.no_ssim, stream=streams[k])
-                    ctx._check(lib.avx_memcpy_d2h(ctx._h, h_out[k].ptr, d_out[k].ptr, n * RECORD_BYTES, streams[k]))
+                    if yuv:
+                        plane_metrics_launch(ctx, sides[0].fmt, sides[0].d_in[k], sides[1].d_in[k], n, H, W, d_out[k], pix_fmt_b=sides[1].fmt,
+                                             ssim=not args.no_ssim, stream=streams[k])
+                    else:
+                        frame_metrics_launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, d_out[k], ssim=not args.no_ssim,
+                                             stream=streams[k])
+                    ctx._check(lib.avx_memcpy_d2h(ctx._h, h_out[k].ptr, d_out[k].ptr, n * rec_bytes, streams[k]))
                     pending[k] = n
                 i += 1
                 if na != nb:
@@ -235,8 +335,15 @@ def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
 
 
 # ------------------------------------------------------------------------------------------------ the command
+def _psnr_peak(sse: int, n: int, peak: int) -> float:
+    return math.inf if sse == 0 else 10.0 * math.log10(float(peak) ** 2 * n / sse)
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     args = parse_args(argv)
+    yuv = args.planes == "yuv"
+    sse_y = samples_y = 0  # --planes yuv: the luma plane's share of the pooled sums, and the depth the records name
+    depth = None
     info: dict = {}
     frames, first_bad, worst_abs, min_ssim, sum_ssim = 0, None, 0, math.inf, 0.0
     sse = samples = beyond = 0
@@ -245,15 +352,19 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     head = list(itertools.islice(records, 1))  # the inputs are opened and their sizes checked before anything is written
     out = open(args.csv, "w") if args.csv else sys.stdout
     try:
-        out.write(CSV_HEADER + "\n")
+        out.write((CSV_HEADER_YUV if yuv else CSV_HEADER) + "\n")
         for m in itertools.chain(head, records):
-            out.write(format_row(frames, m) + "\n")
+            out.write((format_row_planes(frames, m) if yuv else format_row(frames, m)) + "\n")
             if first_bad is None:
                 why = violation(args, m)
                 if why is not None:
                     first_bad = (frames, why)
             sse += sum(m.sse)
-            samples += 3 * m.samples
+            if yuv:
+                samples += m.samples
+                sse_y, samples_y, depth = sse_y + m.sse[0], samples_y + m.plane_samples[0], m.depth
+            else:
+                samples += 3 * m.samples
             beyond += m.count_beyond(1)
             worst_abs = max(worst_abs, m.max_abs)
             if not args.no_ssim:
@@ -267,7 +378,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             out.flush()
     dt = time.perf_counter() - t0
     ssim_txt = "SSIM skipped" if args.no_ssim or not frames else f"SSIM mean {sum_ssim / frames:.6f} min {min_ssim:.6f}"
-    print(f"compare: {frames} frames, PSNR {_num(_psnr(sse, samples)) if frames else 'nan'} dB, {ssim_txt}, largest difference {worst_abs}, "
+    if yuv:
+        peak = (1 << depth) - 1 if frames else 255
+        psnr_txt = (f"PSNR-Y {_num(_psnr_peak(sse_y, samples_y, peak)) if frames else 'nan'} dB, "
+                    f"PSNR {_num(_psnr_peak(sse, samples, peak)) if frames else 'nan'} dB ({depth if frames else '?'}-bit)")
+    else:
+        psnr_txt = f"PSNR {_num(_psnr(sse, samples)) if frames else 'nan'} dB"
+    print(f"compare: {frames} frames, {psnr_txt}, {ssim_txt}, largest difference {worst_abs}, "
           f"beyond +-1 code {beyond / samples if samples else 0.0:.6g}, {frames / dt if dt > 0 else 0.0:.1f} fps", file=sys.stderr)
     status = 0
     if info.get("longer") and not args.shortest:

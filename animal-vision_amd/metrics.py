@@ -4,7 +4,11 @@ on the host without rounding) and the mean SSIM (Wang et al. 2004: 11 x 11 Gauss
 skimage computes with gaussian_weights=True, use_sample_covariance=False).
 
 frame_metrics_device works on frames that are on the device already; frame_metrics takes arrays.  python -m animal_vision_amd.compare
-is the command built on them."""
+is the command built on them.
+
+plane_metrics (csrc/plane_metrics.hip) is the same comparison of video payloads in their own Y, U and V planes, at 8 or
+10 bits, without any conversion: PlaneMetrics, plane_metrics_launch, plane_metrics_device and plane_metrics are the counterparts of
+the four above."""
 from __future__ import annotations
 
 import ctypes
@@ -13,7 +17,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._lib import AVX_METRICS_MAX_FRAMES, FrameMetricsRecord, lib
+from ._lib import AVX_METRICS_MAX_FRAMES, AVX_PIX_FMTS, FrameMetricsRecord, PlaneMetricsRecord, lib
 from .runtime import Context, DeviceBuffer, get_context
 
 MAX_FRAMES = AVX_METRICS_MAX_FRAMES
@@ -162,3 +166,211 @@ def frame_metrics(a, b, *, ssim: bool = True, ctx: Optional[Context] = None):
         d_a.free()
         d_b.free()
     return out if batched else out[0]
+
+
+# ------------------------------------------------------------------------------------------------ YUV planes
+PLANE_RECORD_BYTES = ctypes.sizeof(PlaneMetricsRecord)  # 3 * 1024 uint32, then 3 doubles
+_PLANE_DTYPE = np.dtype([("abs_hist", np.uint32, (3, 1024)), ("ssim", np.float64, (3,))])
+assert _PLANE_DTYPE.itemsize == PLANE_RECORD_BYTES
+# pix_fmt: (log2 horizontal chroma subsampling, log2 vertical, sample depth, luma only) -- csrc/yuv_formats.h
+_PLANE_FORMATS = {"yuv420p": (1, 1, 8, False), "nv12": (1, 1, 8, False), "yuv422p": (1, 0, 8, False), "yuv444p": (0, 0, 8, False),
+                  "gray": (0, 0, 8, True), "yuv420p10le": (1, 1, 10, False), "yuv422p10le": (1, 0, 10, False),
+                  "yuv444p10le": (0, 0, 10, False), "p010le": (1, 1, 10, False)}
+assert set(_PLANE_FORMATS) == set(AVX_PIX_FMTS)
+
+
+def plane_geometry(pix_fmt: str, H: int, W: int):
+    """(depth, (Y, U, V sample counts)) of one H x W frame in `pix_fmt`; absent planes count 0."""
+    if pix_fmt not in _PLANE_FORMATS:
+        raise ValueError(f"pix_fmt must be one of {', '.join(_PLANE_FORMATS)} (got {pix_fmt!r})")
+    sx, sy, depth, luma = _PLANE_FORMATS[pix_fmt]
+    c = 0 if luma else (-(-H >> sy)) * (-(-W >> sx))
+    return depth, (H * W, c, c)
+
+
+def check_plane_formats(pix_fmt: str, pix_fmt_b: Optional[str] = None) -> str:
+    """The format of B (pix_fmt when None); ValueError when the two disagree in sample depth or chroma subsampling."""
+    pix_fmt_b = pix_fmt if pix_fmt_b is None else pix_fmt_b
+    for f in (pix_fmt, pix_fmt_b):
+        if f not in _PLANE_FORMATS:
+            raise ValueError(f"pix_fmt must be one of {', '.join(_PLANE_FORMATS)} (got {f!r})")
+    if _PLANE_FORMATS[pix_fmt] != _PLANE_FORMATS[pix_fmt_b]:
+        raise ValueError(f"{pix_fmt} and {pix_fmt_b} disagree in sample depth or chroma subsampling: planes are compared as stored")
+    return pix_fmt_b
+
+
+class PlaneMetrics:
+    """One frame's record in YUV planes: abs_hist[p][k] = samples of plane p (Y, U, V) with |a - b| == k in native codes (3 x bins
+    uint64, bins = 2^depth), ssim[p] = mean SSIM of plane p (NaN where it was not computed or the plane is absent), plane_samples =
+    the planes' sample counts, planes = "yuv" or "y".  Everything else is derived from the histogram, in integers where it is a
+    count."""
+
+    __slots__ = ("abs_hist", "ssim", "depth", "plane_samples", "planes")
+
+    def __init__(self, abs_hist, ssim=(math.nan, math.nan, math.nan), depth: int = 8, plane_samples=None):
+        if depth not in (8, 10):
+            raise ValueError(f"depth is 8 or 10 (got {depth})")
+        h = np.asarray(abs_hist)
+        if h.ndim != 2 or h.shape[0] != 3 or h.shape[1] < (1 << depth) or h[:, 1 << depth:].any():
+            raise ValueError(f"abs_hist is 3 x {1 << depth} at {depth} bits (got {h.shape})")
+        self.abs_hist = h[:, : 1 << depth].astype(np.uint64)
+        self.ssim = tuple(float(v) for v in ssim)
+        if len(self.ssim) != 3:
+            raise ValueError(f"ssim holds three values (got {len(self.ssim)})")
+        self.depth = int(depth)
+        sums = tuple(int(v) for v in self.abs_hist.sum(axis=1))
+        self.plane_samples = sums if plane_samples is None else tuple(int(v) for v in plane_samples)
+        if self.plane_samples != sums:
+            raise ValueError(f"the histogram rows sum to {sums}, the planes hold {self.plane_samples} samples")
+        self.planes = "yuv" if self.plane_samples[1] or self.plane_samples[2] else "y"
+
+    @property
+    def peak(self) -> int:
+        return (1 << self.depth) - 1
+
+    @property
+    def samples(self) -> int:
+        """Samples of all planes together."""
+        return sum(self.plane_samples)
+
+    @property
+    def sse(self) -> tuple:
+        """Per plane: the sum of squared differences, sum_k k^2 * hist[p][k]."""
+        k2 = np.arange(1 << self.depth, dtype=np.uint64) ** 2
+        return tuple(int((self.abs_hist[p] * k2).sum()) for p in range(3))
+
+    def _psnr(self, sse: int, n: int) -> float:
+        if n == 0:
+            return math.nan
+        return math.inf if sse == 0 else 10.0 * math.log10(float(self.peak) ** 2 * n / sse)
+
+    @property
+    def psnr_planes(self) -> tuple:
+        """Per plane: 10 log10(peak^2 N_p / SSE_p), inf at SSE = 0, NaN for an absent plane."""
+        return tuple(self._psnr(s, n) for s, n in zip(self.sse, self.plane_samples))
+
+    @property
+    def psnr(self) -> float:
+        """Pooled over all samples of all planes (ffmpeg's `average`)."""
+        return self._psnr(sum(self.sse), self.samples)
+
+    @property
+    def max_abs(self) -> int:
+        nz = np.nonzero(self.abs_hist.sum(axis=0))[0]
+        return int(nz[-1]) if len(nz) else 0
+
+    def count_beyond(self, k: int) -> int:
+        """Samples (all planes) with |a - b| > k native codes."""
+        return int(self.abs_hist[:, max(0, int(k) + 1):].sum())
+
+    def share_beyond(self, k: int) -> float:
+        n = self.samples
+        return self.count_beyond(k) / n if n else 0.0
+
+    @property
+    def ssim_mean(self) -> float:
+        """The planes' SSIM weighted by their sample counts ((4 Y + U + V) / 6 at 4:2:0); NaN planes are left out."""
+        num = den = 0.0
+        for v, n in zip(self.ssim, self.plane_samples):
+            if not math.isnan(v) and n:
+                num, den = num + v * n, den + n
+        return num / den if den else math.nan
+
+    def __eq__(self, other):
+        if not isinstance(other, PlaneMetrics):
+            return NotImplemented
+        return (self.depth == other.depth and np.array_equal(self.abs_hist, other.abs_hist)
+                and np.array(self.ssim).tobytes() == np.array(other.ssim).tobytes())
+
+    def __repr__(self):
+        return f"PlaneMetrics({self.depth}-bit {self.planes}, psnr={self.psnr:.4f}, ssim={self.ssim_mean:.6f}, max_abs={self.max_abs})"
+
+
+def _check_plane_call(pix_fmt: str, pix_fmt_b: str, n_frames: int, H: int, W: int, d_a: DeviceBuffer, d_b: DeviceBuffer):
+    from .yuv import frame_size
+
+    check_plane_formats(pix_fmt, pix_fmt_b)
+    if not 1 <= n_frames <= MAX_FRAMES:
+        raise ValueError(f"n_frames must be 1..{MAX_FRAMES} (got {n_frames})")
+    if H < 1 or W < 1:
+        raise ValueError(f"bad frame size {H} x {W}")
+    need_a, need_b = n_frames * frame_size(pix_fmt, H, W), n_frames * frame_size(pix_fmt_b, H, W)
+    if d_a.nbytes < need_a or d_b.nbytes < need_b:
+        raise ValueError(f"{n_frames} frames of {H} x {W} need {need_a} ({pix_fmt}) and {need_b} ({pix_fmt_b}) bytes; the buffers hold "
+                         f"{d_a.nbytes} and {d_b.nbytes}")
+
+
+def plane_metrics_launch(ctx: Context, pix_fmt: str, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_out: DeviceBuffer,
+                         *, pix_fmt_b: Optional[str] = None, ssim: bool = True, stream=None) -> None:
+    """Enqueue the comparison of n_frames payloads on `stream`; d_out takes n_frames records of PLANE_RECORD_BYTES
+    (plane_records_from_bytes reads them).  Nothing is downloaded and nothing waits."""
+    pix_fmt_b = pix_fmt if pix_fmt_b is None else pix_fmt_b
+    _check_plane_call(pix_fmt, pix_fmt_b, n_frames, H, W, d_a, d_b)
+    if d_out.nbytes < n_frames * PLANE_RECORD_BYTES:
+        raise ValueError(f"{n_frames} records need {n_frames * PLANE_RECORD_BYTES} bytes; the buffer holds {d_out.nbytes}")
+    ctx._check(lib.avx_plane_metrics(ctx._h, AVX_PIX_FMTS[pix_fmt], d_a.ptr, AVX_PIX_FMTS[pix_fmt_b], d_b.ptr, int(n_frames), int(H), int(W),
+                                     1 if ssim else 0, d_out.ptr, ctx._s(stream)))
+
+
+def plane_records_from_bytes(buf: np.ndarray, n_frames: int, pix_fmt: str, H: int, W: int) -> List[PlaneMetrics]:
+    """n_frames downloaded records (uint8) of H x W frames in `pix_fmt` -> PlaneMetrics."""
+    depth, counts = plane_geometry(pix_fmt, H, W)
+    recs = np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n_frames * PLANE_RECORD_BYTES], dtype=_PLANE_DTYPE)
+    return [PlaneMetrics(r["abs_hist"], r["ssim"], depth, counts) for r in recs]
+
+
+def plane_metrics_device(ctx: Context, pix_fmt: str, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, *,
+                         pix_fmt_b: Optional[str] = None, ssim: bool = True, stream=None) -> List[PlaneMetrics]:
+    """Compare n_frames (1..16) contiguous payloads of d_a (pix_fmt) with those of d_b (pix_fmt_b); downloads the records."""
+    pix_fmt_b = pix_fmt if pix_fmt_b is None else pix_fmt_b
+    _check_plane_call(pix_fmt, pix_fmt_b, n_frames, H, W, d_a, d_b)
+    d_out = ctx.malloc(n_frames * PLANE_RECORD_BYTES)
+    try:
+        plane_metrics_launch(ctx, pix_fmt, d_a, d_b, n_frames, H, W, d_out, pix_fmt_b=pix_fmt_b, ssim=ssim, stream=stream)
+        raw = ctx.download(d_out, (n_frames * PLANE_RECORD_BYTES,), np.uint8, stream=stream)
+    finally:
+        d_out.free()
+    return plane_records_from_bytes(raw, n_frames, pix_fmt, H, W)
+
+
+def check_payloads(a, b, pix_fmt: str, pix_fmt_b: str, H: int, W: int):
+    """Two uint8 payload arrays (n x frame_size, or one flat payload each) -> contiguous 2-D arrays.  ValueError naming both
+    otherwise, before any device work."""
+    from .yuv import frame_size
+
+    check_plane_formats(pix_fmt, pix_fmt_b)
+    if H < 1 or W < 1:
+        raise ValueError(f"bad frame size {H} x {W}")
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != np.uint8 or b.dtype != np.uint8:
+        raise ValueError(f"payloads are uint8 (got a: {a.dtype} {a.shape}, b: {b.dtype} {b.shape})")
+    sa, sb = frame_size(pix_fmt, H, W), frame_size(pix_fmt_b, H, W)
+    if a.ndim not in (1, 2) or b.ndim not in (1, 2) or a.shape[-1] != sa or b.shape[-1] != sb:
+        raise ValueError(f"a {H} x {W} frame is {sa} bytes of {pix_fmt} and {sb} bytes of {pix_fmt_b} (got a: {a.shape}, b: {b.shape})")
+    a, b = a.reshape(-1, sa), b.reshape(-1, sb)
+    if len(a) != len(b) or len(a) == 0:
+        raise ValueError(f"a and b differ in length, or are empty (a: {len(a)} frames, b: {len(b)} frames)")
+    return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+def plane_metrics(a, b, *, pix_fmt: str, H: int, W: int, pix_fmt_b: Optional[str] = None, ssim: bool = True,
+                  ctx: Optional[Context] = None) -> List[PlaneMetrics]:
+    """a, b: uint8 payloads of H x W frames (n x frame_size, or one flat payload) in pix_fmt and pix_fmt_b (default: pix_fmt) -> a
+    list of n PlaneMetrics; uploaded in chunks of at most 16 frames."""
+    pix_fmt_b = pix_fmt if pix_fmt_b is None else pix_fmt_b
+    a, b = check_payloads(a, b, pix_fmt, pix_fmt_b, int(H), int(W))
+    N = len(a)
+    ctx = ctx or get_context()
+    chunk = min(N, MAX_FRAMES)
+    d_a, d_b = ctx.malloc(chunk * a.shape[1]), ctx.malloc(chunk * b.shape[1])
+    out: List[PlaneMetrics] = []
+    try:
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            ctx.upload(a[i : i + n], d_a)
+            ctx.upload(b[i : i + n], d_b)
+            out += plane_metrics_device(ctx, pix_fmt, d_a, d_b, n, H, W, pix_fmt_b=pix_fmt_b, ssim=ssim)
+    finally:
+        d_a.free()
+        d_b.free()
+    return out

@@ -416,6 +416,31 @@ typedef struct avx_frame_metrics {
 int avx_frame_metrics_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W,
                          int with_ssim, avx_frame_metrics* out_dev, void* stream);
 
+/* Comparison in YUV planes (csrc/plane_metrics.hip): what two batches of video payloads differ by, per frame and
+ * plane, in their own samples: no matrix, no range, no chroma upsampling, no rounding to 8 bits. */
+typedef struct avx_plane_metrics_rec {
+    uint32_t abs_hist[3][1024]; /* [p][k], p = Y, U, V: samples of plane p with |a - b| == k; 8-bit formats use bins 0..255 */
+    double   ssim[3];           /* mean SSIM of plane p over its (h_p - 10) x (w_p - 10) window positions; NaN when with_ssim == 0, */
+                                /* the plane is absent (GRAY: U, V) or smaller than 11 in either dimension                          */
+} avx_plane_metrics_rec;
+
+/* a, b: n_frames payloads of avx_yuv_frame_size(fmt, H, W) bytes on the device, in any avx_pix_fmt layout; fmt_a and fmt_b may
+ * differ where they agree in sample depth and chroma subsampling (YUV420P against NV12, YUV420P10LE against P010LE).  out_dev:
+ * n_frames records on the device (8-byte aligned).  Asynchronous on `stream`.  1 <= n_frames <= 16.  Samples are read as the
+ * decoders read them: bytes at 8 bits, little-endian uint16 at 10 bits, P010LE shifted right by 6 (its low six bits are ignored).
+ * A planar 10-bit sample above 1023 is invalid input: its difference is clamped into bin 1023, so no count is ever written outside
+ * the histogram.  Plane sizes: Y is H x W, U and V are ceil(H / 2^sy) x ceil(W / 2^sx).  The histogram is exact and covers every
+ * sample of every plane (each row sums to that plane's sample count, rows of absent planes are zero).  SSIM is that of
+ * avx_frame_metrics_u8 per plane at the plane's own size, with dynamic range L = 2^d - 1: C1 = (0.01 L)^2, C2 = (0.03 L)^2.  At 8
+ * bits the moments and the quotient are float32 on samples centred by 128; at 10 bits they are float64 (a fixed centre does not keep
+ * float32 within 1e-5 there).  Every sum over positions is float64 in a fixed order (no floating-point atomics): a frame's record
+ * is bit-identical whichever batch and batch position it was computed in, and from run to run; identical planes give exactly 1.0.
+ * AVX_ERR_INVALID (avx_last_error starts with this function's name) for a NULL buffer, n_frames outside 1..16, a bad format or
+ * size (1 .. 32768 each way; a plane stays below 2^32 samples), formats that disagree in depth or subsampling, and an odd payload
+ * address with a 16-bit format; nothing is launched then. */
+int avx_plane_metrics(avx_ctx* ctx, int fmt_a, const uint8_t* a, int fmt_b, const uint8_t* b, int n_frames, int H, int W,
+                      int with_ssim, avx_plane_metrics_rec* out_dev, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

@@ -6,6 +6,13 @@
       call.  One JSON line per configuration: median (min-max) in us per frame, and what the 6 B/px both frames hold would take at
       6.29 TB/s (the measured HBM copy rate, MI355X).  The frames are noise against the same noise +-2 codes: most differences are 0,
       1 or 2, as between two renderings of one clip, which is also the worst case of the histogram's LDS atomics.
+  python tools/metrics_bench.py planes [--reps 7]
+      avx_plane_metrics on nv12 and p010le pairs resident on the device, 4K and 1080p, batches of 8, the histogram
+      alone and with SSIM, interleaved in one process with the RGB route on the same payloads (yuv_to_rgb_device for both sides, then
+      avx_frame_metrics_u8; at 10 bits the RGB route compares what is left after rounding to 8 bits): per repetition each of the four
+      forms once, each between its own pair of stream events, after one warm-up call of each.  One JSON line per (format, size, ssim):
+      median (min-max) of both routes in us per frame, their ratio, and what the payload bytes of both sides (2 x 1.5 B/px for nv12,
+      2 x 3 B/px for p010le) would take at 6.29 TB/s.  The pairs are noise against the same noise +-2 codes in every plane.
   python tools/metrics_bench.py command [--frames 32] [--reps 3] [--dir DIR]
       Two 4K nv12 files of `frames` frames in DIR (default: /dev/shm when there is one, so they are read from memory) through
       python -m animal_vision_amd.compare's main(), --batch 8, with and without SSIM: frames per second of the whole command (read,
@@ -60,6 +67,65 @@ def kernel(args):
             d.free()
 
 
+def _plane_pair(fmt, n, H, W, seed=0):
+    """n payload pairs of `fmt`: noise, and the same noise +-2 codes in every sample."""
+    wide = fmt == "p010le"
+    top, ns = (1023, H * W * 3 // 2) if wide else (255, H * W * 3 // 2)
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, top + 1, (n, ns), dtype=np.int16)
+    b = np.clip(a + rng.integers(-2, 3, a.shape, dtype=np.int16), 0, top)
+    if wide:
+        return (a.astype("<u2") << 6).view(np.uint8).reshape(n, -1), (b.astype("<u2") << 6).view(np.uint8).reshape(n, -1)
+    return a.astype(np.uint8), b.astype(np.uint8)
+
+
+def planes(args):
+    from animal_vision_amd.metrics import PLANE_RECORD_BYTES, RECORD_BYTES, frame_metrics_launch, plane_metrics_launch
+    from animal_vision_amd.runtime import get_context
+    from animal_vision_amd.yuv import yuv_to_rgb_device
+
+    ctx, n = get_context(), 8
+    for name, (H, W) in (("4k", SIZES["4k"]), ("1080p", SIZES["1080p"])):
+        d_ra, d_rb = ctx.malloc(n * H * W * 3), ctx.malloc(n * H * W * 3)
+        d_out, d_pout = ctx.malloc(n * RECORD_BYTES), ctx.malloc(n * PLANE_RECORD_BYTES)
+        for fmt in ("nv12", "p010le"):
+            a, b = _plane_pair(fmt, n, H, W)
+            d_a, d_b = ctx.upload(a), ctx.upload(b)
+
+            def plane_route(ssim):
+                plane_metrics_launch(ctx, fmt, d_a, d_b, n, H, W, d_pout, ssim=ssim)
+
+            def rgb_route(ssim):
+                yuv_to_rgb_device(ctx, fmt, d_a, d_ra, n, H, W)
+                yuv_to_rgb_device(ctx, fmt, d_b, d_rb, n, H, W)
+                frame_metrics_launch(ctx, d_ra, d_rb, n, H, W, d_out, ssim=ssim)
+
+            forms = [(route, ssim) for ssim in (False, True) for route in (plane_route, rgb_route)]
+            times = {k: [] for k in range(len(forms))}
+            for route, ssim in forms:  # warm-up: the workspace is sized here
+                route(ssim)
+            ctx.sync()
+            for _ in range(args.reps):
+                for k, (route, ssim) in enumerate(forms):
+                    ctx.timer_start()
+                    route(ssim)
+                    times[k].append(ctx.timer_stop() * 1e3 / n)
+            floor = a.shape[1] * 2 / COPY_BPS * 1e6
+            for k in (0, 2):
+                pl, rg = times[k], times[k + 1]
+                print(json.dumps({"planes": fmt, "size": name, "batch": n, "ssim": forms[k][1], "reps": args.reps,
+                                  "plane_us_per_frame_median": round(float(np.median(pl)), 1), "plane_us_min": round(min(pl), 1),
+                                  "plane_us_max": round(max(pl), 1), "rgb_route_us_per_frame_median": round(float(np.median(rg)), 1),
+                                  "rgb_route_us_min": round(min(rg), 1), "rgb_route_us_max": round(max(rg), 1),
+                                  "rgb_over_plane": round(float(np.median(rg)) / float(np.median(pl)), 2),
+                                  "us_payload_bytes_at_6.29TBps": round(floor, 1),
+                                  "plane_x_copy_floor": round(float(np.median(pl)) / floor, 1)}), flush=True)
+            d_a.free()
+            d_b.free()
+        for d in (d_ra, d_rb, d_out, d_pout):
+            d.free()
+
+
 def command(args):
     from animal_vision_amd import compare
     from animal_vision_amd.yuv import rgb_to_yuv
@@ -95,12 +161,14 @@ def main():
     sub = ap.add_subparsers(dest="cmd", required=True)
     k = sub.add_parser("kernel")
     k.add_argument("--reps", type=int, default=7)
+    pl = sub.add_parser("planes")
+    pl.add_argument("--reps", type=int, default=7)
     c = sub.add_parser("command")
     c.add_argument("--frames", type=int, default=32)
     c.add_argument("--reps", type=int, default=3)
     c.add_argument("--dir", default=None)
     args = ap.parse_args()
-    {"kernel": kernel, "command": command}[args.cmd](args)
+    {"kernel": kernel, "planes": planes, "command": command}[args.cmd](args)
 
 
 if __name__ == "__main__":

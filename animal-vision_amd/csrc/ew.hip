@@ -13,9 +13,14 @@
 // (deterministic two-level reduction; results land in a device-side scalar table that later programs read, so no
 // value ever visits the host).
 //
-// Arithmetic contract: every instruction is one IEEE float32 operation, in the order NumPy evaluates the
-// reference's expression (-ffp-contract=off: nothing fuses); transcendental functions are the device's (1-2 ulp
-// from NumPy's): within 1e-4 relative of the reference, the UV path's bar.  uint8 encode = the exact threshold table.
+// Arithmetic contract (DESIGN.md 4.6 "The plane-program ISA"; tests/_ew_ref.py is its NumPy model, tests/test_ew_isa_gpu.py
+// holds this file to it): every instruction is one IEEE float32 operation, denormals kept, in the order NumPy evaluates the
+// reference's expression (-ffp-contract=off: nothing fuses).  + - * / sqrt floor ceil are correctly rounded; MIN / MAX are
+// fminf / fmaxf (a NaN operand is ignored, the sign of min(-0, +0) is unspecified); comparisons with a NaN give 0, NOT(NaN) = 0,
+// AND / OR take NaN as true, SELECT on a NaN condition takes operand b, CLIP01(NaN) = NaN.  Transcendental functions are the
+// device library's: within 2 ulp of the exact function (measured: exp 0.81, log 1.87, sin / cos 1.40, tanh 1.20, pow 1.27), atan2f
+// within 3 (measured 2.26) -- within 1e-4 relative of the reference, the UV path's bar.  uint8 encode = the exact threshold table
+// (NaN -> 0).  Only the binary opcodes take an immediate operand, and only one.
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(kET) void k_ew(const EwArgs a) {
                         EW_FOR if (valid[k]) ((float*)p.ptr)[(size_t)ii[k] * p.stride] = xs[k];
                     } else {
 #pragma unroll
-                        EW_FOR if (valid[k]) ((uint8_t*)p.ptr)[(size_t)ii[k] * p.stride] = (uint8_t)quantize_coarse<float, kCoarseNFix>(xs[k], thr, coarse, a.lo_key);
+                        EW_FOR if (valid[k]) ((uint8_t*)p.ptr)[(size_t)ii[k] * p.stride] = ew_encode(xs[k], thr, coarse, a.lo_key);
                     }
                     continue;
                 }
@@ -125,7 +130,7 @@ __global__ __launch_bounds__(kET) void k_ew(const EwArgs a) {
                 case AVX_EW_ATAN2: EW_BIN(atan2f(x, y));
                 case AVX_EW_NEG: EW_UN(-x);
                 case AVX_EW_ABS: EW_UN(fabsf(x));
-                case AVX_EW_SQRT: EW_UN(__fsqrt_rn(x));
+                case AVX_EW_SQRT: EW_UN(sqrtf(x));  // correctly rounded (__fsqrt_rn is the 1-ulp hardware approximation unless OCML_BASIC_ROUNDED_OPERATIONS is set)
                 case AVX_EW_EXP: EW_UN(expf(x));
                 case AVX_EW_LOG: EW_UN(logf(x));
                 case AVX_EW_SIN: EW_UN(sinf(x));
@@ -273,11 +278,14 @@ extern "C" int avx_ew_run_batch(avx_ctx* ctx, const avx_ew_program* p, int n_fra
         const avx_ew_insn in = p->insn_host[i];
         AVX_REQUIRE(ctx, in.dst < AVX_EW_MAX_REGS && in.a < AVX_EW_MAX_REGS && in.b < AVX_EW_MAX_REGS, "avx_ew_run: register index out of range");
         const int opc = in.op & AVX_EW_OPCODE_MASK;
+        // only the binary opcodes (ADD..ATAN2, LT..OR) take an immediate operand, and only one: a unary opcode would compute
+        // op(imm) here while its generated kernel reads the register
         if ((in.op & (AVX_EW_IMM_A | AVX_EW_IMM_B)) != 0)
-            AVX_REQUIRE(ctx, opc >= AVX_EW_ADD && opc <= AVX_EW_OR && opc != AVX_EW_NOT && (in.op & (AVX_EW_IMM_A | AVX_EW_IMM_B)) != (AVX_EW_IMM_A | AVX_EW_IMM_B),
+            AVX_REQUIRE(ctx, ((opc >= AVX_EW_ADD && opc <= AVX_EW_ATAN2) || (opc >= AVX_EW_LT && opc <= AVX_EW_OR)) &&
+                                 (in.op & (AVX_EW_IMM_A | AVX_EW_IMM_B)) != (AVX_EW_IMM_A | AVX_EW_IMM_B),
                         "avx_ew_run: immediate operand on an opcode that takes none");
         if (opc == AVX_EW_LOAD || opc == AVX_EW_STORE) {
-            AVX_REQUIRE(ctx, (int)in.imm < p->n_planes, "avx_ew_run: plane index out of range");
+            AVX_REQUIRE(ctx, in.imm < (uint32_t)p->n_planes, "avx_ew_run: plane index out of range");
             const int kind = a.planes[in.imm].kind;
             if (kind == AVX_EW_PLANE_COL || kind == AVX_EW_PLANE_ROW) a.uses_xy = 1;
             if (opc == AVX_EW_STORE) {
@@ -290,7 +298,7 @@ extern "C" int avx_ew_run_batch(avx_ctx* ctx, const avx_ew_program* p, int n_fra
                 AVX_REQUIRE(ctx, kind != AVX_EW_PLANE_U8_ENC, "avx_ew_run: load from an encode-only plane");
             }
         }
-        if (opc == AVX_EW_SCALAR) AVX_REQUIRE(ctx, p->scalars_dev && (int)in.imm < p->n_scalars, "avx_ew_run: scalar slot out of range");
+        if (opc == AVX_EW_SCALAR) AVX_REQUIRE(ctx, p->scalars_dev && p->n_scalars > 0 && in.imm < (uint32_t)p->n_scalars, "avx_ew_run: scalar slot out of range");
         if (opc == AVX_EW_SELECT) AVX_REQUIRE(ctx, (in.imm & 0xff) < AVX_EW_MAX_REGS, "avx_ew_run: register index out of range");
         AVX_REQUIRE(ctx, opc >= AVX_EW_CONST && opc <= AVX_EW_ACCSUM, "avx_ew_run: unknown opcode");
         a.insn[i] = in;

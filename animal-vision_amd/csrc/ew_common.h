@@ -41,6 +41,12 @@ __device__ __forceinline__ avx_ew_plane ew_plane_of(const EwArgs& a, int j, unsi
 __device__ __forceinline__ float acc_init(int kind) { return kind == AVX_EW_ACC_MIN ? INFINITY : (kind == AVX_EW_ACC_MAX ? -INFINITY : 0.f); }
 __device__ __forceinline__ float acc_merge(int kind, float a, float b) { return kind == AVX_EW_ACC_MIN ? fminf(a, b) : (kind == AVX_EW_ACC_MAX ? fmaxf(a, b) : a + b); }
 
+// STORE to an AVX_EW_PLANE_U8_ENC plane: the threshold-table code of clip(v, 0, 1).  A NaN encodes as 0: clip() passes it through, and its
+// bucket key would index far behind the coarse table.
+__device__ __forceinline__ uint8_t ew_encode(float v, const float* __restrict__ thr, const uint8_t* __restrict__ coarse, uint32_t lo_key) {
+    return (uint8_t)avxk::quantize_coarse<float, avxk::kCoarseNFix>(v == v ? v : 0.f, thr, coarse, lo_key);
+}
+
 // The tail of a program with reductions, as in k_ew: per-thread accumulators (acc[k][0..PX)) -> partial[block][k] -> the last
 // workgroup (ticket) folds the per-block partials into the scalar table.  Same merge order as the interpreter, so a program gives
 // the same scalars through either kernel.

@@ -97,34 +97,9 @@ def _factor(n):
     return h, n // h
 
 
-def _reduction_program(H, W, planes, scalars_ptr, n_scalars):
-    """x * col + row, times a per-frame scalar (slot 8); stored, and min / max / sum of it plus the mean of x accumulated into
-    slots 0..3.  Its structure is recorded in csrc/ew_programs.txt, so it has a generated kernel."""
-    from animal_vision_amd._lib import EW, EW_ACC, EwInsn, EwPlane, EwProgram
-
-    ins = [(EW["LOAD"], 0, 0, 0, 0), (EW["LOAD"], 1, 0, 0, 1), (EW["LOAD"], 2, 0, 0, 2), (EW["MUL"], 3, 0, 1, 0), (EW["ADD"], 3, 3, 2, 0),
-           (EW["SCALAR"], 4, 0, 0, 8), (EW["MUL"], 3, 3, 4, 0), (EW["STORE"], 0, 3, 0, 3),
-           (EW["ACCMIN"], 5, 3, 0, 0), (EW["ACCMAX"], 6, 3, 0, 0), (EW["ACCSUM"], 7, 3, 0, 0), (EW["ACCSUM"], 8, 0, 0, 0)]
-    a_ins = (EwInsn * len(ins))(*[EwInsn(*t) for t in ins])
-    a_pl = (EwPlane * len(planes))(*[EwPlane(*t) for t in planes])
-    acc = [5, EW_ACC["min"], 0, 6, EW_ACC["max"], 1, 7, EW_ACC["sum"], 2, 8, EW_ACC["mean"], 3]
-    a_acc = (ctypes.c_int32 * len(acc))(*acc)
-    p = EwProgram()
-    p.struct_size = ctypes.sizeof(EwProgram)
-    p.H, p.W = H, W
-    p.n_insn, p.insn_host = len(ins), ctypes.cast(a_ins, ctypes.POINTER(EwInsn))
-    p.n_planes, p.planes_host = len(planes), ctypes.cast(a_pl, ctypes.POINTER(EwPlane))
-    p.n_acc, p.acc_host = 4, ctypes.cast(a_acc, ctypes.POINTER(ctypes.c_int32))
-    p.scalars_dev, p.n_scalars = scalars_ptr, n_scalars
-    return p, (a_ins, a_pl, a_acc)
-
-
-def _spec_stats():
-    from animal_vision_amd._lib import lib
-
-    h, m = ctypes.c_ulonglong(), ctypes.c_ulonglong()
-    lib.avx_ew_spec_stats(ctypes.byref(h), ctypes.byref(m))
-    return h.value, m.value
+# the builder of the recorded reduction program and the hit / miss counters live in tests/_ew_ref.py (test_ew_isa_gpu.py shares them)
+from _ew_ref import reduction_program as _reduction_program  # noqa: E402
+from _ew_ref import spec_stats as _spec_stats  # noqa: E402
 
 
 @pytest.mark.parametrize("n", [(1 << 20) - 1, 1920 * 1080, 3840 * 2160 + 3])

@@ -30,7 +30,7 @@ ACC_MIN, ACC_MAX, ACC_SUM, ACC_MEAN = range(4)
 BINARY = {ADD: "x + y", SUB: "x - y", MUL: "x * y", DIV: "x / y", MIN: "fminf(x, y)", MAX: "fmaxf(x, y)", POW: "powf(x, y)", ATAN2: "atan2f(x, y)",
           LT: "x < y ? 1.f : 0.f", LE: "x <= y ? 1.f : 0.f", GT: "x > y ? 1.f : 0.f", GE: "x >= y ? 1.f : 0.f", EQ: "x == y ? 1.f : 0.f",
           AND: "(x != 0.f && y != 0.f) ? 1.f : 0.f", OR: "(x != 0.f || y != 0.f) ? 1.f : 0.f"}
-UNARY = {NEG: "-x", ABS: "fabsf(x)", SQRT: "__fsqrt_rn(x)", EXP: "expf(x)", LOG: "logf(x)", SIN: "sinf(x)", COS: "cosf(x)", FLOOR: "floorf(x)",
+UNARY = {NEG: "-x", ABS: "fabsf(x)", SQRT: "sqrtf(x)", EXP: "expf(x)", LOG: "logf(x)", SIN: "sinf(x)", COS: "cosf(x)", FLOOR: "floorf(x)",
          CEIL: "ceilf(x)", CLIP01: "x < 0.f ? 0.f : (x > 1.f ? 1.f : x)", TANH: "tanhf(x)", NOT: "x != 0.f ? 0.f : 1.f"}
 M64 = (1 << 64) - 1
 
@@ -119,6 +119,8 @@ def emit(idx, ins, kinds, acc):
     for pc, (op, d, ra, rb, simm) in enumerate(ins):
         o = op & 0x3f
         ia, ib = bool(op & IMM_A), bool(op & IMM_B)
+        # avx_ew_run refuses anything else: only a binary opcode takes an immediate operand, and only one
+        assert not (ia or ib) or (o in BINARY and not (ia and ib)), f"program {idx}, instruction {pc}: immediate flag on opcode {o}"
         v = f"v{pc}"
         if o in (CONST, SCALAR):
             w(f"        float {v}[PX]; EWG_FOR {v}[k] = i{pc};")
@@ -136,7 +138,7 @@ def emit(idx, ins, kinds, acc):
                 w(f"        EWG_FOR if (valid[k]) ((float*){p}.ptr)[(size_t)ii[k] * {p}.stride] = {s}[k];")
             else:
                 assert kind == P_U8_ENC
-                w(f"        EWG_FOR if (valid[k]) ((uint8_t*){p}.ptr)[(size_t)ii[k] * {p}.stride] = (uint8_t)quantize_coarse<float, kCoarseNFix>({s}[k], thr, coarse, a.lo_key);")
+                w(f"        EWG_FOR if (valid[k]) ((uint8_t*){p}.ptr)[(size_t)ii[k] * {p}.stride] = ew_encode({s}[k], thr, coarse, a.lo_key);")
             continue
         elif o in BINARY:
             x = f"i{pc}" if ia else f"{src(ra)}[k]"

@@ -176,7 +176,7 @@ class FrameMetricsRecord(ctypes.Structure):
     _fields_ = [("abs_hist", (ctypes.c_uint32 * 256) * 3), ("ssim", ctypes.c_double * 3)]
 
 
-AVX_METRICS_MAX_FRAMES = 16  # frames of one avx_frame_metrics_u8 / avx_plane_metrics call
+AVX_METRICS_MAX_FRAMES = 16  # frames of one avx_frame_metrics_u8 / avx_plane_metrics / avx_frame_metrics_ms_u8 call
 
 
 class PlaneMetricsRecord(ctypes.Structure):
@@ -186,6 +186,15 @@ class PlaneMetricsRecord(ctypes.Structure):
 
 
 assert ctypes.sizeof(PlaneMetricsRecord) == 3 * 1024 * 4 + 3 * 8  # 12,312 bytes: the header's record, no padding
+
+
+class MsSsimRecord(ctypes.Structure):
+    """avx_ms_ssim_rec (include/avx.h): [channel][scale]."""
+
+    _fields_ = [("cs", (ctypes.c_double * 5) * 3), ("ssim", (ctypes.c_double * 5) * 3)]
+
+
+assert ctypes.sizeof(MsSsimRecord) == 240
 
 class EwInsn(ctypes.Structure):
     _fields_ = [("op", ctypes.c_uint8), ("dst", ctypes.c_uint8), ("a", ctypes.c_uint8), ("b", ctypes.c_uint8), ("imm", ctypes.c_uint32)]
@@ -327,6 +336,7 @@ _SIGS = {
     "avx_yuv_hdr_to_rgb_scaled_u8": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
     "avx_frame_metrics_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "avx_plane_metrics": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "avx_frame_metrics_ms_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

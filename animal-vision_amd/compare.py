@@ -20,7 +20,12 @@ is 2 unless --shortest is given.
 --planes yuv compares video in its own Y, U and V planes instead: both inputs hand over payloads (.y4m, or raw video with
 --pix-fmt and --size; a .y4m is I420 whatever --pix-fmt says), which go into the batch buffers and straight to avx_plane_metrics -- no
 decode, no RGB buffer, 10-bit files in 10-bit codes.  The lines are frame,psnr_y,psnr_u,psnr_v,psnr,ssim_y,ssim_u,ssim_v,ssim,max_abs,
-beyond1 (psnr: pooled over all samples, ffmpeg's `average`; ssim: the planes weighted by their sample counts; absent planes: nan)."""
+beyond1 (psnr: pooled over all samples, ffmpeg's `average`; ssim: the planes weighted by their sample counts; absent planes: nan).
+
+--ms-ssim adds MS-SSIM over five scales (Wang, Simoncelli, Bovik 2003) of the RGB frames: the columns ms_ssim_r,
+ms_ssim_g,ms_ssim_b,ms_ssim behind the others (which stay, byte for byte, what the run without it prints), mean and minimum in the
+summary, and --min-ms-ssim X as a limit (it implies --ms-ssim).  Five scales need frames of at least 176 x 176 (after --scale);
+--no-ssim and --planes yuv are refused with it."""
 from __future__ import annotations
 
 import argparse
@@ -33,12 +38,14 @@ from typing import Iterator, Optional, Sequence
 
 import numpy as np
 
-from .metrics import (PLANE_RECORD_BYTES, RECORD_BYTES, FrameMetrics, PlaneMetrics, _psnr, check_plane_formats, frame_metrics_launch,
-                      plane_metrics_launch, plane_records_from_bytes, records_from_bytes)
+from .metrics import (MS_MIN_SIDE, MS_RECORD_BYTES, PLANE_RECORD_BYTES, RECORD_BYTES, FrameMetrics, MsSsim, PlaneMetrics, _psnr,
+                      check_plane_formats, frame_metrics_launch, frame_metrics_ms_launch, ms_records_from_bytes, plane_metrics_launch,
+                      plane_records_from_bytes, records_from_bytes)
 from .video import _size_arg, add_input_options, add_output_options, check_io_options, check_raw_options
 
 CSV_HEADER = "frame,psnr_r,psnr_g,psnr_b,psnr,ssim_r,ssim_g,ssim_b,ssim,max_abs,beyond1"
 CSV_HEADER_YUV = "frame,psnr_y,psnr_u,psnr_v,psnr,ssim_y,ssim_u,ssim_v,ssim,max_abs,beyond1"
+CSV_MS_COLUMNS = ",ms_ssim_r,ms_ssim_g,ms_ssim_b,ms_ssim"  # --ms-ssim: behind CSV_HEADER
 _OUTPUT_ONLY = (("--out-pix-fmt", "out_pix_fmt"), ("--out-matrix", "out_matrix"), ("--depth", "depth"))
 
 
@@ -58,6 +65,12 @@ def format_row_planes(index: int, m: PlaneMetrics) -> str:
     p = m.psnr_planes
     return ",".join([str(index), _num(p[0]), _num(p[1]), _num(p[2]), _num(m.psnr), _num(m.ssim[0]), _num(m.ssim[1]), _num(m.ssim[2]),
                      _num(m.ssim_mean), str(m.max_abs), f"{m.share_beyond(1):.6g}"])
+
+
+def format_ms_columns(ms: MsSsim) -> str:
+    """What --ms-ssim appends to the CSV line of a frame."""
+    c = ms.ms_ssim_channels
+    return "," + ",".join([_num(c[0]), _num(c[1]), _num(c[2]), _num(ms.ms_ssim)])
 
 
 def _is_y4m_file(path: str) -> bool:
@@ -87,6 +100,25 @@ def _check_planes_yuv(ap: argparse.ArgumentParser, args: argparse.Namespace) -> 
         ap.error(f"--planes yuv: A and B: {e}")
 
 
+def _check_ms_ssim(ap: argparse.ArgumentParser, args: argparse.Namespace) -> None:
+    """--ms-ssim: five scales of RGB frames, on top of the SSIM record."""
+    if args.no_ssim:
+        ap.error("--ms-ssim builds on the SSIM record that --no-ssim skips: give one of the two")
+    if args.planes == "yuv":
+        ap.error("--ms-ssim compares RGB frames: --planes yuv is not supported with it")
+    size = args.scale if args.scale is not None else args.size  # (W, H) where the command line states it
+    if size is None:
+        for path in (args.a, args.b):
+            if path.startswith("synthetic:"):
+                try:
+                    size = _size_arg(path.split(":")[1])
+                except (IndexError, argparse.ArgumentTypeError):
+                    size = None
+                break
+    if size is not None and (size[0] < MS_MIN_SIDE or size[1] < MS_MIN_SIDE):
+        ap.error(f"--ms-ssim: five scales need frames of at least {MS_MIN_SIDE}x{MS_MIN_SIDE}; these are {size[0]}x{size[1]}")
+
+
 class _CompareParser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         args = super().parse_args(args, namespace)
@@ -97,6 +129,10 @@ class _CompareParser(argparse.ArgumentParser):
             self.error("--min-ssim needs the SSIM that --no-ssim skips")
         if args.a == "-" and args.b == "-":
             self.error("A and B cannot both be stdin")
+        if hasattr(args, "min_ms_ssim"):
+            args.ms_ssim = True
+        if getattr(args, "ms_ssim", False):
+            _check_ms_ssim(self, args)
         if args.planes == "yuv":
             _check_planes_yuv(self, args)
         args.input = args.a  # what check_io_options reads the source size of a synthetic: input from
@@ -125,10 +161,15 @@ def build_parser() -> argparse.ArgumentParser:
                          "compares against a raw nv12 or yuv420p file); --matrix and --range are accepted and have no effect, --scale and "
                          "--transfer are errors")
     ap.add_argument("--no-ssim", action="store_true", help="histograms (PSNR, max_abs, beyond1) only")
+    # both MS-SSIM options leave no attribute behind when they are not given: without them the namespace is what it always was
+    ap.add_argument("--ms-ssim", action="store_true", default=argparse.SUPPRESS,
+                    help="also MS-SSIM over five scales (columns ms_ssim_r,ms_ssim_g,ms_ssim_b,ms_ssim behind the others); RGB frames of at "
+                         "least 176x176 only: --no-ssim and --planes yuv are errors with it")
     ap.add_argument("--csv", default=None, metavar="FILE", help="write the per-frame lines here instead of stdout")
     ap.add_argument("--shortest", action="store_true", help="inputs of different lengths: compare the common prefix without complaint")
     ap.add_argument("--min-psnr", type=float, default=None, metavar="X", help="status 1 when a frame's PSNR (all channels) is below X dB")
     ap.add_argument("--min-ssim", type=float, default=None, metavar="X", help="status 1 when a frame's mean SSIM is below X")
+    ap.add_argument("--min-ms-ssim", type=float, default=argparse.SUPPRESS, metavar="X", help="status 1 when a frame's MS-SSIM is below X; implies --ms-ssim")
     ap.add_argument("--max-abs", type=int, default=None, metavar="K", help="status 1 when a frame has samples more than K codes apart")
     ap.add_argument("--max-beyond1", type=float, default=None, metavar="S", help="status 1 when more than the share S of a frame's samples is beyond +-1 code")
     return ap
@@ -138,12 +179,14 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     return build_parser().parse_args(argv)
 
 
-def violation(args, m: FrameMetrics) -> Optional[str]:
-    """What frame record `m` violates of the command line's limits, None when nothing."""
+def violation(args, m: FrameMetrics, ms: Optional[MsSsim] = None) -> Optional[str]:
+    """What frame record `m` (and, with --ms-ssim, `ms`) violates of the command line's limits, None when nothing."""
     if args.min_psnr is not None and m.psnr < args.min_psnr:
         return f"PSNR {_num(m.psnr)} dB is below --min-psnr {args.min_psnr:g}"
     if args.min_ssim is not None and not m.ssim_mean >= args.min_ssim:
         return f"SSIM {_num(m.ssim_mean)} is below --min-ssim {args.min_ssim:g}"
+    if ms is not None and getattr(args, "min_ms_ssim", None) is not None and not ms.ms_ssim >= args.min_ms_ssim:
+        return f"MS-SSIM {_num(ms.ms_ssim)} is below --min-ms-ssim {args.min_ms_ssim:g}"
     if args.max_abs is not None and m.max_abs > args.max_abs:
         return f"largest difference {m.max_abs} is above --max-abs {args.max_abs}"
     if args.max_beyond1 is not None and m.share_beyond(1) > args.max_beyond1:
@@ -260,8 +303,8 @@ class _PlaneSide:
 
 
 def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
-    """The records of the common prefix of args.a and args.b, in frame order.  info["longer"] names the input ("A" / "B") that had
-    frames left over, when one had."""
+    """The records of the common prefix of args.a and args.b, in frame order; with --ms-ssim every item is the pair (FrameMetrics,
+    MsSsim).  info["longer"] names the input ("A" / "B") that had frames left over, when one had."""
     from ._lib import lib
     from .runtime import get_context
 
@@ -278,6 +321,9 @@ def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
         H, W = hwa
         ctx, batch, sets = get_context(), args.batch, 2
         yuv = getattr(args, "planes", "rgb") == "yuv"
+        ms = bool(getattr(args, "ms_ssim", False))
+        if ms and (H < MS_MIN_SIDE or W < MS_MIN_SIDE):
+            raise SystemExit(f"compare: --ms-ssim: five scales need frames of at least {MS_MIN_SIDE}x{MS_MIN_SIDE}; these are {W}x{H}")
         rec_bytes = PLANE_RECORD_BYTES if yuv else RECORD_BYTES
         side = _PlaneSide if yuv else _Side
         sides.append(side(ctx, va, H, W, batch, sets))
@@ -285,6 +331,8 @@ def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
         streams = [ctx.stream_create() for _ in range(sets)]
         d_out = [ctx.malloc(batch * rec_bytes) for _ in range(sets)]
         h_out = [ctx.pinned((batch * rec_bytes,), np.uint8) for _ in range(sets)]
+        d_ms = [ctx.malloc(batch * MS_RECORD_BYTES) for _ in range(sets)] if ms else []
+        h_ms = [ctx.pinned((batch * MS_RECORD_BYTES,), np.uint8) for _ in range(sets)] if ms else []
         pending = [0] * sets
 
         def harvest(k):
@@ -292,6 +340,8 @@ def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
             n, pending[k] = pending[k], 0
             if yuv:
                 return plane_records_from_bytes(h_out[k].array, n, sides[0].fmt, H, W) if n else []
+            if ms:
+                return list(zip(records_from_bytes(h_out[k].array, n), ms_records_from_bytes(h_ms[k].array, n))) if n else []
             return records_from_bytes(h_out[k].array, n) if n else []
 
         try:
@@ -307,6 +357,9 @@ def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
                     if yuv:
                         plane_metrics_launch(ctx, sides[0].fmt, sides[0].d_in[k], sides[1].d_in[k], n, H, W, d_out[k], pix_fmt_b=sides[1].fmt,
                                              ssim=not args.no_ssim, stream=streams[k])
+                    elif ms:
+                        frame_metrics_ms_launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, d_out[k], d_ms[k], stream=streams[k])
+                        ctx._check(lib.avx_memcpy_d2h(ctx._h, h_ms[k].ptr, d_ms[k].ptr, n * MS_RECORD_BYTES, streams[k]))
                     else:
                         frame_metrics_launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, d_out[k], ssim=not args.no_ssim,
                                              stream=streams[k])
@@ -323,9 +376,9 @@ def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
             for k in range(sets):
                 ctx.sync(streams[k])
                 ctx.stream_destroy(streams[k])
-            for b in d_out:
+            for b in d_out + d_ms:
                 b.free()
-            for h in h_out:
+            for h in h_out + h_ms:
                 h.free()
     finally:
         for s in sides:
@@ -341,7 +394,8 @@ def _psnr_peak(sse: int, n: int, peak: int) -> float:
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
     args = parse_args(argv)
-    yuv = args.planes == "yuv"
+    yuv, with_ms = args.planes == "yuv", bool(getattr(args, "ms_ssim", False))
+    min_ms, sum_ms = math.inf, 0.0
     sse_y = samples_y = 0  # --planes yuv: the luma plane's share of the pooled sums, and the depth the records name
     depth = None
     info: dict = {}
@@ -352,11 +406,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     head = list(itertools.islice(records, 1))  # the inputs are opened and their sizes checked before anything is written
     out = open(args.csv, "w") if args.csv else sys.stdout
     try:
-        out.write((CSV_HEADER_YUV if yuv else CSV_HEADER) + "\n")
+        out.write((CSV_HEADER_YUV if yuv else CSV_HEADER) + (CSV_MS_COLUMNS if with_ms else "") + "\n")
         for m in itertools.chain(head, records):
-            out.write((format_row_planes(frames, m) if yuv else format_row(frames, m)) + "\n")
+            ms = None
+            if with_ms:
+                m, ms = m
+                sum_ms += ms.ms_ssim
+                min_ms = min(min_ms, ms.ms_ssim)
+            out.write((format_row_planes(frames, m) if yuv else format_row(frames, m)) + (format_ms_columns(ms) if with_ms else "") + "\n")
             if first_bad is None:
-                why = violation(args, m)
+                why = violation(args, m, ms)
                 if why is not None:
                     first_bad = (frames, why)
             sse += sum(m.sse)
@@ -378,6 +437,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             out.flush()
     dt = time.perf_counter() - t0
     ssim_txt = "SSIM skipped" if args.no_ssim or not frames else f"SSIM mean {sum_ssim / frames:.6f} min {min_ssim:.6f}"
+    if with_ms and frames:
+        ssim_txt += f", MS-SSIM mean {sum_ms / frames:.6f} min {min_ms:.6f}"
     if yuv:
         peak = (1 << depth) - 1 if frames else 255
         psnr_txt = (f"PSNR-Y {_num(_psnr_peak(sse_y, samples_y, peak)) if frames else 'nan'} dB, "

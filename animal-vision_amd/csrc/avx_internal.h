@@ -101,6 +101,13 @@ int avx_mst_qkv_final_launch(avx_ctx* ctx, const float* partial, int blocks, int
 // lifetime rules as avx_resize_hwc's own lookups.
 struct avx_area_tab { const int* start; const int* cnt; const float* alpha; int maxcnt; };  // alpha [d][maxcnt]
 int avx_geom_area_tables(avx_ctx* ctx, avx_ws* ws, hipStream_t s, int H, int W, int Hd, int Wd, avx_area_tab* ax, avx_area_tab* ay);
+// metrics.hip, for ms_ssim.hip: what avx_frame_metrics_u8 launches with with_ssim = 1 on frames of at least 11 x 11 (the record memset,
+// k_metrics_tile, k_metrics_final), the arguments checked by the caller.  partials: (ms ? 6 : 3) * avx_metrics_scale0_tiles(H, W) *
+// n_frames doubles.  With ms the tile kernel also sums cs, and cs[c][0] and ssim[c][0] of ms[f] are written (ssim[c][0] is the value
+// out_dev[f].ssim[c] receives); out_dev receives the same bytes either way.
+int avx_metrics_scale0_launch(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, double* partials,
+                              avx_frame_metrics* out_dev, avx_ms_ssim_rec* ms, hipStream_t s);
+size_t avx_metrics_scale0_tiles(int H, int W);
 
 #define AVX_HIP(ctx, call)                                                                         \
     do {                                                                                            \

@@ -10,6 +10,9 @@
 // to one double per channel, and k_metrics_final sums the tiles of a (frame, channel) in a fixed order: no floating-point atomics, so
 // a frame's record does not depend on the batch it was in.
 // k_metrics_hist is the histogram alone (with_ssim == 0, or a frame with no window position).
+// WITH_CS (avx_metrics_scale0_launch with a record of ms_ssim.hip) is the same tile code that also sums the contrast-
+// structure term cs = (2 s_ab + C2) / (s_a^2 + s_b^2 + C2) of every position: scale 0 of MS-SSIM.  The SSIM sums are formed by the
+// same operations in the same order in both instantiations (nothing is contracted: -ffp-contract=off), so they are bit-identical.
 #include "avx_internal.h"
 
 #include <cmath>
@@ -101,9 +104,9 @@ __device__ __forceinline__ void row_item(const uint8_t* raw_a, const uint8_t* ra
 }
 
 // One channel of a tile: row pass into hp, column pass in registers, the SSIM of the thread's 4 positions, the workgroup's sum.
-template <bool EDGE, int C>
+template <bool EDGE, int C, bool WITH_CS>
 __device__ __forceinline__ void channel_pass(int H, int W, int x0, int y0, const Taps& tp, const uint8_t* raw_a, const uint8_t* raw_b, float* hp,
-                                             double* red, double* part) {
+                                             double* red, double* part, size_t cs_offset) {
     const int tid = threadIdx.x;
     // ---- row pass: the first kT patch rows as 256 items of 4 positions, the other 10 as 160 items of 2: every wave stays busy ----
     row_item<4, C>(raw_a, raw_b, hp, tp, tid >> 3, (tid & 7) * 4);
@@ -128,7 +131,7 @@ __device__ __forceinline__ void channel_pass(int H, int W, int x0, int y0, const
     // ---- SSIM.  E[x^2] - mu^2 loses nothing to float32: the rounding error of the product is recovered with an fma and taken
     // off the difference, so variance and covariance carry a relative error of 2^-23, not one of the size of mu^2. ----
     const float C1 = 6.5025f, C2 = 58.5225f;  // (0.01 * 255)^2, (0.03 * 255)^2
-    double sum = 0.0;
+    double sum = 0.0, sum_cs = 0.0;
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         if (EDGE && !(x0 + col < W - (kK - 1) && y0 + seg * 4 + o < H - (kK - 1))) continue;
@@ -141,14 +144,23 @@ __device__ __forceinline__ void channel_pass(int H, int W, int x0, int y0, const
         const float num = (2.0f * (ua * ub) + C1) * (2.0f * cab + C2);
         const float den = ((ua * ua + ub * ub) + C1) * ((va + vb) + C2);
         sum += (double)(num / den);
+        if (WITH_CS) sum_cs += (double)((2.0f * cab + C2) / ((va + vb) + C2));
     }
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
+    if (WITH_CS)
+        for (int o = 32; o > 0; o >>= 1) sum_cs += __shfl_down(sum_cs, o);
+    if ((tid & 63) == 0) {
+        red[tid >> 6] = sum;
+        if (WITH_CS) red[kThreads / 64 + (tid >> 6)] = sum_cs;
+    }
     __syncthreads();  // also: every column pass has read hp before the next channel's row pass writes it
-    if (tid == 0) *part = ((red[0] + red[1]) + red[2]) + red[3];
+    if (tid == 0) {
+        *part = ((red[0] + red[1]) + red[2]) + red[3];
+        if (WITH_CS) part[cs_offset] = ((red[4] + red[5]) + red[6]) + red[7];
+    }
 }
 
-template <bool EDGE>
+template <bool EDGE, bool WITH_CS>
 __device__ __forceinline__ void tile_body(const uint8_t* __restrict__ fa, const uint8_t* __restrict__ fb, int H, int W, int x0, int y0,
                                           int own_w, int own_h, const Taps& tp, uint8_t* raw_a, uint8_t* raw_b, float* hp, unsigned* hist,
                                           double* red, double* part, size_t part_stride) {
@@ -181,18 +193,21 @@ __device__ __forceinline__ void tile_body(const uint8_t* __restrict__ fa, const 
     }
     __syncthreads();
 
-    channel_pass<EDGE, 0>(H, W, x0, y0, tp, raw_a, raw_b, hp, red, part);
-    channel_pass<EDGE, 1>(H, W, x0, y0, tp, raw_a, raw_b, hp, red, part + part_stride);
-    channel_pass<EDGE, 2>(H, W, x0, y0, tp, raw_a, raw_b, hp, red, part + 2 * part_stride);
+    // WITH_CS: the cs sum of channel c lies three rows of partials behind its SSIM sum
+    channel_pass<EDGE, 0, WITH_CS>(H, W, x0, y0, tp, raw_a, raw_b, hp, red, part, 3 * part_stride);
+    channel_pass<EDGE, 1, WITH_CS>(H, W, x0, y0, tp, raw_a, raw_b, hp, red, part + part_stride, 3 * part_stride);
+    channel_pass<EDGE, 2, WITH_CS>(H, W, x0, y0, tp, raw_a, raw_b, hp, red, part + 2 * part_stride, 3 * part_stride);
 }
 
+// partials: [frame][row][tile] doubles, rows 0..2 the SSIM sums of the channels and, WITH_CS, rows 3..5 their cs sums
+template <bool WITH_CS>
 __global__ __launch_bounds__(kThreads) void k_metrics_tile(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int H, int W, Taps tp,
                                                            double* __restrict__ partials, avx_frame_metrics* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) uint8_t raw_a[kP * kRaw];
     __shared__ __attribute__((aligned(16))) uint8_t raw_b[kP * kRaw];
     __shared__ __attribute__((aligned(16))) float hp[5 * kP * kT];
     __shared__ unsigned hist[kBins];
-    __shared__ double red[kThreads / 64];
+    __shared__ double red[(WITH_CS ? 2 : 1) * (kThreads / 64)];
     const int tid = threadIdx.x, f = blockIdx.z;
     for (int i = tid; i < kBins; i += kThreads) hist[i] = 0;
     __syncthreads();
@@ -201,20 +216,22 @@ __global__ __launch_bounds__(kThreads) void k_metrics_tile(const uint8_t* __rest
     const int own_w = blockIdx.x == gridDim.x - 1 ? W - x0 : kT, own_h = blockIdx.y == gridDim.y - 1 ? H - y0 : kT;
     const size_t fo = (size_t)f * H * W * 3;
     const size_t ntiles = (size_t)gridDim.x * gridDim.y;
-    double* part = partials + (size_t)f * 3 * ntiles + ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+    double* part = partials + (size_t)f * (WITH_CS ? 6 : 3) * ntiles + ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
     if (x0 + kP <= W && y0 + kP <= H)  // the whole patch lies in the frame: no bounds tests
-        tile_body<false>(a + fo, b + fo, H, W, x0, y0, own_w, own_h, tp, raw_a, raw_b, hp, hist, red, part, ntiles);
+        tile_body<false, WITH_CS>(a + fo, b + fo, H, W, x0, y0, own_w, own_h, tp, raw_a, raw_b, hp, hist, red, part, ntiles);
     else
-        tile_body<true>(a + fo, b + fo, H, W, x0, y0, own_w, own_h, tp, raw_a, raw_b, hp, hist, red, part, ntiles);
+        tile_body<true, WITH_CS>(a + fo, b + fo, H, W, x0, y0, own_w, own_h, tp, raw_a, raw_b, hp, hist, red, part, ntiles);
     hist_flush(hist, out + f, tid);  // the last barrier of tile_body is behind every histogram update
 }
 
-// sum of the tile partials of one (channel, frame) in a fixed order: thread t adds tiles t, t + 256, ..., then a fixed tree
+// sum of the tile partials of one (row of partials, frame) in a fixed order: thread t adds tiles t, t + 256, ..., then a fixed tree.
+// grid (3, frames): the SSIM of the channels; grid (6, frames) with ms: rows 3..5 are the cs sums, and scale 0 of ms[f] is filled.
 __global__ __launch_bounds__(kThreads) void k_metrics_final(const double* __restrict__ partials, size_t ntiles, double count,
-                                                            avx_frame_metrics* __restrict__ out) {
+                                                            avx_frame_metrics* __restrict__ out, avx_ms_ssim_rec* __restrict__ ms) {
     __shared__ double red[kThreads];
-    const int tid = threadIdx.x, c = blockIdx.x, f = blockIdx.y;
-    const double* p = partials + ((size_t)f * 3 + c) * ntiles;
+    const int tid = threadIdx.x, f = blockIdx.y;
+    const int c = blockIdx.x % 3;
+    const double* p = partials + ((size_t)f * gridDim.x + blockIdx.x) * ntiles;
     double s = 0.0;
     for (size_t t = tid; t < ntiles; t += kThreads) s += p[t];
     red[tid] = s;
@@ -223,7 +240,15 @@ __global__ __launch_bounds__(kThreads) void k_metrics_final(const double* __rest
         if (tid < o) red[tid] += red[tid + o];
         __syncthreads();
     }
-    if (tid == 0) out[f].ssim[c] = red[0] / count;
+    if (tid == 0) {
+        const double v = red[0] / count;
+        if (blockIdx.x < 3) {
+            out[f].ssim[c] = v;
+            if (ms) ms[f].ssim[c][0] = v;
+        } else {
+            ms[f].cs[c][0] = v;
+        }
+    }
 }
 
 // histogram alone: grid (blocks, frames); VEC: 16 bytes of both frames per thread and step
@@ -274,6 +299,33 @@ __global__ __launch_bounds__(kThreads) void k_metrics_hist(const uint8_t* __rest
 
 }  // namespace
 
+// avx_internal.h: the record memset, k_metrics_tile and k_metrics_final of n_frames frames with window positions, arguments checked
+// by the caller; partials: (ms ? 6 : 3) * tiles * n_frames doubles
+int avx_metrics_scale0_launch(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, double* partials,
+                              avx_frame_metrics* out_dev, avx_ms_ssim_rec* ms, hipStream_t s) {
+    const unsigned ntx = (unsigned)((W - (kK - 1) + kT - 1) / kT), nty = (unsigned)((H - (kK - 1) + kT - 1) / kT);
+    const size_t ntiles = (size_t)ntx * nty;
+    AVX_HIP(ctx, hipMemsetAsync(out_dev, 0, sizeof(avx_frame_metrics) * (size_t)n_frames, s));
+    double g[kK], sum = 0.0;
+    for (int k = 0; k < kK; ++k) sum += g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
+    Taps tp;
+    for (int k = 0; k < kK; ++k) tp.w[k] = (float)(g[k] / sum);
+    if (ms)
+        hipLaunchKernelGGL(k_metrics_tile<true>, dim3(ntx, nty, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, H, W, tp, partials, out_dev);
+    else
+        hipLaunchKernelGGL(k_metrics_tile<false>, dim3(ntx, nty, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, H, W, tp, partials, out_dev);
+    AVX_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_metrics_final, dim3(ms ? 6 : 3, n_frames), dim3(kThreads), 0, s, (const double*)partials, ntiles,
+                       (double)(H - (kK - 1)) * (double)(W - (kK - 1)), out_dev, ms);
+    AVX_HIP(ctx, hipGetLastError());
+    return AVX_OK;
+}
+
+// tiles of a frame with window positions: what a row of partials holds
+size_t avx_metrics_scale0_tiles(int H, int W) {
+    return (size_t)((W - (kK - 1) + kT - 1) / kT) * (size_t)((H - (kK - 1) + kT - 1) / kT);
+}
+
 extern "C" int avx_frame_metrics_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int with_ssim,
                                     avx_frame_metrics* out_dev, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
@@ -288,37 +340,24 @@ extern "C" int avx_frame_metrics_u8(avx_ctx* ctx, const uint8_t* a_hwc, const ui
     AVX_REQUIRE(ctx, nty <= 65535u, "avx_frame_metrics_u8: %d rows are more than the SSIM kernel's grid takes (%d)", H, 65535 * kT + kK - 1);
     AVX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = avx_pick_stream(ctx, stream);
-    double* partials = nullptr;
-    const size_t ntiles = (size_t)ntx * nty;
     if (ssim) {
         avx_ws* ws = avx_workspace(ctx, s);
         if (!ws) return AVX_ERR_NOMEM;
-        const int rc = avx_ensure_scratch(ctx, ws, sizeof(double) * 3 * ntiles * (size_t)n_frames);
+        const int rc = avx_ensure_scratch(ctx, ws, sizeof(double) * 3 * (size_t)ntx * nty * (size_t)n_frames);
         if (rc) return rc;
-        partials = (double*)ws->d_scratch;
+        return avx_metrics_scale0_launch(ctx, a_hwc, b_hwc, n_frames, H, W, (double*)ws->d_scratch, out_dev, nullptr, s);
     }
     AVX_HIP(ctx, hipMemsetAsync(out_dev, 0, sizeof(avx_frame_metrics) * (size_t)n_frames, s));
-    if (ssim) {
-        double g[kK], sum = 0.0;
-        for (int k = 0; k < kK; ++k) sum += g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-        Taps tp;
-        for (int k = 0; k < kK; ++k) tp.w[k] = (float)(g[k] / sum);
-        hipLaunchKernelGGL(k_metrics_tile, dim3(ntx, nty, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, H, W, tp, partials, out_dev);
-        AVX_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_metrics_final, dim3(3, n_frames), dim3(kThreads), 0, s, (const double*)partials, ntiles,
-                           (double)(H - (kK - 1)) * (double)(W - (kK - 1)), out_dev);
-    } else {
-        const size_t fbytes = (size_t)H * W * 3;
-        const bool vec = fbytes % 16 == 0 && (((uintptr_t)a_hwc | (uintptr_t)b_hwc) & 15) == 0;
-        const size_t units = vec ? fbytes / 16 : fbytes;
-        size_t blocks = (units + kThreads - 1) / kThreads;
-        const size_t cap = (size_t)ctx->num_cus * 8;
-        if (blocks > cap) blocks = cap;
-        if (vec)
-            hipLaunchKernelGGL(k_metrics_hist<true>, dim3((unsigned)blocks, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, fbytes, out_dev);
-        else
-            hipLaunchKernelGGL(k_metrics_hist<false>, dim3((unsigned)blocks, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, fbytes, out_dev);
-    }
+    const size_t fbytes = (size_t)H * W * 3;
+    const bool vec = fbytes % 16 == 0 && (((uintptr_t)a_hwc | (uintptr_t)b_hwc) & 15) == 0;
+    const size_t units = vec ? fbytes / 16 : fbytes;
+    size_t blocks = (units + kThreads - 1) / kThreads;
+    const size_t cap = (size_t)ctx->num_cus * 8;
+    if (blocks > cap) blocks = cap;
+    if (vec)
+        hipLaunchKernelGGL(k_metrics_hist<true>, dim3((unsigned)blocks, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, fbytes, out_dev);
+    else
+        hipLaunchKernelGGL(k_metrics_hist<false>, dim3((unsigned)blocks, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, fbytes, out_dev);
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
 }

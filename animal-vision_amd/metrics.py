@@ -8,7 +8,10 @@ is the command built on them.
 
 plane_metrics (csrc/plane_metrics.hip) is the same comparison of video payloads in their own Y, U and V planes, at 8 or
 10 bits, without any conversion: PlaneMetrics, plane_metrics_launch, plane_metrics_device and plane_metrics are the counterparts of
-the four above."""
+the four above.
+
+MsSsim (csrc/ms_ssim.hip) is MS-SSIM over five scales (Wang, Simoncelli, Bovik 2003) of the same RGB frames:
+frame_metrics_ms_launch / frame_metrics_ms_device return it beside the FrameMetrics of the same call, ms_ssim takes arrays."""
 from __future__ import annotations
 
 import ctypes
@@ -17,7 +20,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._lib import AVX_METRICS_MAX_FRAMES, AVX_PIX_FMTS, FrameMetricsRecord, PlaneMetricsRecord, lib
+from ._lib import AVX_METRICS_MAX_FRAMES, AVX_PIX_FMTS, FrameMetricsRecord, MsSsimRecord, PlaneMetricsRecord, lib
 from .runtime import Context, DeviceBuffer, get_context
 
 MAX_FRAMES = AVX_METRICS_MAX_FRAMES
@@ -374,3 +377,111 @@ def plane_metrics(a, b, *, pix_fmt: str, H: int, W: int, pix_fmt_b: Optional[str
         d_a.free()
         d_b.free()
     return out
+
+
+# ------------------------------------------------------------------------------------------------ MS-SSIM
+MS_RECORD_BYTES = ctypes.sizeof(MsSsimRecord)  # cs[3][5], ssim[3][5]: 30 doubles
+_MS_DTYPE = np.dtype([("cs", np.float64, (3, 5)), ("ssim", np.float64, (3, 5))])
+assert _MS_DTYPE.itemsize == MS_RECORD_BYTES == 240
+MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)  # Wang, Simoncelli, Bovik 2003, scales 0..4
+MS_MIN_SIDE = 176  # scale 4 is floor(H / 16) x floor(W / 16) and needs one 11 x 11 window position
+
+
+class MsSsim:
+    """One frame's per-scale means: cs[c][j] = mean contrast-structure term of channel c at scale j, ssim[c][j] = mean SSIM there
+    (3 x 5 float64 each, as the device wrote them: not clamped).  The product over the scales is formed here, in float64."""
+
+    __slots__ = ("cs", "ssim")
+
+    def __init__(self, cs, ssim):
+        self.cs, self.ssim = np.array(cs, dtype=np.float64), np.array(ssim, dtype=np.float64)
+        if self.cs.shape != (3, 5) or self.ssim.shape != (3, 5):
+            raise ValueError(f"cs and ssim are 3 x 5 (got {self.cs.shape} and {self.ssim.shape})")
+
+    @property
+    def ms_ssim_channels(self) -> tuple:
+        """Per channel: prod_{j<4} max(cs[j], 0)^w_j * max(ssim[4], 0)^w_4 (the clamp is TensorFlow's and pytorch-msssim's)."""
+        out = []
+        for c in range(3):
+            v = max(float(self.ssim[c][4]), 0.0) ** MS_WEIGHTS[4]
+            for j in range(4):
+                v *= max(float(self.cs[c][j]), 0.0) ** MS_WEIGHTS[j]
+            out.append(v)
+        return tuple(out)
+
+    @property
+    def ms_ssim(self) -> float:
+        """The mean of the three channels."""
+        v = self.ms_ssim_channels
+        return (v[0] + v[1] + v[2]) / 3.0
+
+    def __eq__(self, other):
+        if not isinstance(other, MsSsim):
+            return NotImplemented
+        return self.cs.tobytes() == other.cs.tobytes() and self.ssim.tobytes() == other.ssim.tobytes()
+
+    def __repr__(self):
+        return f"MsSsim(ms_ssim={self.ms_ssim:.6f})"
+
+
+def check_ms_size(H: int, W: int) -> None:
+    """ValueError for a frame too small for five scales."""
+    if H < MS_MIN_SIDE or W < MS_MIN_SIDE:
+        raise ValueError(f"MS-SSIM over five scales needs frames of at least {MS_MIN_SIDE} x {MS_MIN_SIDE} (got {H} x {W})")
+
+
+def frame_metrics_ms_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_out: DeviceBuffer,
+                            d_ms: DeviceBuffer, *, stream=None) -> None:
+    """Enqueue the comparison with MS-SSIM of n_frames frames on `stream`; d_out takes n_frames records of RECORD_BYTES (the bytes
+    frame_metrics_launch writes), d_ms n_frames of MS_RECORD_BYTES (ms_records_from_bytes reads them).  Nothing is downloaded and
+    nothing waits."""
+    _check_call(n_frames, H, W, d_a, d_b)
+    check_ms_size(H, W)
+    if d_out.nbytes < n_frames * RECORD_BYTES or d_ms.nbytes < n_frames * MS_RECORD_BYTES:
+        raise ValueError(f"{n_frames} records need {n_frames * RECORD_BYTES} and {n_frames * MS_RECORD_BYTES} bytes; the buffers hold "
+                         f"{d_out.nbytes} and {d_ms.nbytes}")
+    ctx._check(lib.avx_frame_metrics_ms_u8(ctx._h, d_a.ptr, d_b.ptr, int(n_frames), int(H), int(W), d_out.ptr, d_ms.ptr, ctx._s(stream)))
+
+
+def ms_records_from_bytes(buf: np.ndarray, n_frames: int) -> List[MsSsim]:
+    """n_frames downloaded MS-SSIM records (uint8) -> MsSsim."""
+    recs = np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n_frames * MS_RECORD_BYTES], dtype=_MS_DTYPE)
+    return [MsSsim(r["cs"], r["ssim"]) for r in recs]
+
+
+def frame_metrics_ms_device(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, *, stream=None):
+    """Compare n_frames (1..16) contiguous H x W x 3 uint8 frames of d_a with those of d_b; downloads both kinds of records:
+    (list of FrameMetrics, list of MsSsim)."""
+    _check_call(n_frames, H, W, d_a, d_b)
+    check_ms_size(H, W)
+    d_out, d_ms = ctx.malloc(n_frames * RECORD_BYTES), ctx.malloc(n_frames * MS_RECORD_BYTES)
+    try:
+        frame_metrics_ms_launch(ctx, d_a, d_b, n_frames, H, W, d_out, d_ms, stream=stream)
+        raw = ctx.download(d_out, (n_frames * RECORD_BYTES,), np.uint8, stream=stream)
+        raw_ms = ctx.download(d_ms, (n_frames * MS_RECORD_BYTES,), np.uint8, stream=stream)
+    finally:
+        d_out.free()
+        d_ms.free()
+    return records_from_bytes(raw, n_frames), ms_records_from_bytes(raw_ms, n_frames)
+
+
+def ms_ssim(a, b, *, ctx: Optional[Context] = None):
+    """a, b: uint8 H x W x 3 -> MsSsim, or N x H x W x 3 -> a list of N; uploaded in chunks of at most 16 frames.  ValueError for
+    frames below 176 x 176, before any device work."""
+    a, b, batched = check_pair(a, b)
+    N, H, W = a.shape[:3]
+    check_ms_size(H, W)
+    ctx = ctx or get_context()
+    chunk = min(N, MAX_FRAMES)
+    d_a, d_b = ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * H * W * 3)
+    out: List[MsSsim] = []
+    try:
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            ctx.upload(a[i : i + n], d_a)
+            ctx.upload(b[i : i + n], d_b)
+            out += frame_metrics_ms_device(ctx, d_a, d_b, n, H, W)[1]
+    finally:
+        d_a.free()
+        d_b.free()
+    return out if batched else out[0]

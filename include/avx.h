@@ -441,6 +441,32 @@ typedef struct avx_plane_metrics_rec {
 int avx_plane_metrics(avx_ctx* ctx, int fmt_a, const uint8_t* a, int fmt_b, const uint8_t* b, int n_frames, int H, int W,
                       int with_ssim, avx_plane_metrics_rec* out_dev, void* stream);
 
+/* MS-SSIM, five scales (csrc/ms_ssim.hip; Wang, Simoncelli, Bovik 2003): the per-scale means of two batches of uint8
+ * RGB frames, per frame and channel.  The product over the scales is formed by the caller (metrics.MsSsim). */
+typedef struct avx_ms_ssim_rec {
+    double cs[3][5];   /* [c][j]: mean of cs = (2 s_ab + C2) / (s_a^2 + s_b^2 + C2) over the window positions of scale j */
+    double ssim[3][5]; /* [c][j]: mean of l * cs, l = (2 mu_a mu_b + C1) / (mu_a^2 + mu_b^2 + C1); neither is clamped  */
+} avx_ms_ssim_rec;     /* 240 bytes */
+
+/* a_hwc, b_hwc: n_frames contiguous H x W x 3 uint8 frames on the device; out_dev: n_frames avx_frame_metrics, ms_out_dev: n_frames
+ * avx_ms_ssim_rec, both on the device and 8-byte aligned.  Asynchronous on `stream`; nothing waits on the host and, once the
+ * stream's workspace has grown to the batch, nothing is allocated.  1 <= n_frames <= 16, H >= 176 and W >= 176 (scale 4 is
+ * floor(H/16) x floor(W/16) and needs one window position), H*W < 2^32.
+ * Scale 0 of a channel is the channel; scale j+1 is the 2 x 2 mean of scale j at floor(h/2) x floor(w/2), a trailing odd row or
+ * column dropped -- equivalently the sum of an origin-aligned 2^j x 2^j block divided by 4^j, which is how the scales are stored:
+ * exact integer sums in uint16.  At every scale the window, the constants (L = 255) and the valid positions are those of
+ * avx_frame_metrics_u8.  MS-SSIM of a channel = prod_{j<4} max(cs[c][j], 0)^w_j * max(ssim[c][4], 0)^w_4 with
+ * w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333); the frame value is the mean of the channels.
+ * out_dev receives exactly the bytes avx_frame_metrics_u8(..., with_ssim = 1, ...) writes for the same input, and
+ * ms_out_dev[f].ssim[c][0] is bit-identical to out_dev[f].ssim[c]: scale 0 is that kernel's tile code, instantiated to sum cs as
+ * well (float32 moments on samples centred by 128).  Scales 1..4 carry up to 8 fractional bits: their moments, the window sums
+ * and the quotients are float64.  Every sum over positions is float64 in a fixed order (no floating-point atomics): a frame's
+ * record is bit-identical whichever batch and batch position it was computed in, and from run to run; identical frames give
+ * exactly 1.0 at every scale.  AVX_ERR_INVALID (avx_last_error starts with this function's name) for a NULL buffer, n_frames
+ * outside 1..16, H or W below 176 and H*W >= 2^32; nothing is launched then. */
+int avx_frame_metrics_ms_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W,
+                            avx_frame_metrics* out_dev, avx_ms_ssim_rec* ms_out_dev, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

@@ -13,10 +13,15 @@
       forms once, each between its own pair of stream events, after one warm-up call of each.  One JSON line per (format, size, ssim):
       median (min-max) of both routes in us per frame, their ratio, and what the payload bytes of both sides (2 x 1.5 B/px for nv12,
       2 x 3 B/px for p010le) would take at 6.29 TB/s.  The pairs are noise against the same noise +-2 codes in every plane.
+  python tools/metrics_bench.py ms [--reps 7]
+      avx_frame_metrics_ms_u8 (MS-SSIM over five scales) on RGB pairs resident on the device, 4K and 1080p, batches of
+      8, interleaved in one process with avx_frame_metrics_u8(with_ssim = 1) on the same frames: per repetition each of the two once,
+      each between its own pair of stream events, after one warm-up call of each.  One JSON line per size: median (min-max) of both
+      in us per frame and their ratio.  The pairs are noise against the same noise +-2 codes.
   python tools/metrics_bench.py command [--frames 32] [--reps 3] [--dir DIR]
       Two 4K nv12 files of `frames` frames in DIR (default: /dev/shm when there is one, so they are read from memory) through
-      python -m animal_vision_amd.compare's main(), --batch 8, with and without SSIM: frames per second of the whole command (read,
-      upload, decode, compare, CSV), `reps` runs each after one warm-up run."""
+      python -m animal_vision_amd.compare's main(), --batch 8, with SSIM, without it and with --ms-ssim: frames per second of the
+      whole command (read, upload, decode, compare, CSV), `reps` runs each after one warm-up run."""
 import argparse
 import contextlib
 import io
@@ -126,6 +131,40 @@ def planes(args):
             d.free()
 
 
+def ms(args):
+    from animal_vision_amd.metrics import MS_RECORD_BYTES, RECORD_BYTES, frame_metrics_launch, frame_metrics_ms_launch
+    from animal_vision_amd.runtime import get_context
+
+    ctx, n = get_context(), 8
+    for name, (H, W) in (("4k", SIZES["4k"]), ("1080p", SIZES["1080p"])):
+        a, b = _pair(n, H, W)
+        d_a, d_b, d_out, d_ms = ctx.upload(a), ctx.upload(b), ctx.malloc(n * RECORD_BYTES), ctx.malloc(n * MS_RECORD_BYTES)
+
+        def ms_route():
+            frame_metrics_ms_launch(ctx, d_a, d_b, n, H, W, d_out, d_ms)
+
+        def ssim_route():
+            frame_metrics_launch(ctx, d_a, d_b, n, H, W, d_out, ssim=True)
+
+        forms = [ms_route, ssim_route]
+        times = [[], []]
+        for route in forms:  # warm-up: the workspace is sized here
+            route()
+        ctx.sync()
+        for _ in range(args.reps):
+            for k, route in enumerate(forms):
+                ctx.timer_start()
+                route()
+                times[k].append(ctx.timer_stop() * 1e3 / n)
+        m, s = times
+        print(json.dumps({"ms_ssim": True, "size": name, "batch": n, "reps": args.reps, "ms_us_per_frame_median": round(float(np.median(m)), 1),
+                          "ms_us_min": round(min(m), 1), "ms_us_max": round(max(m), 1), "ssim_us_per_frame_median": round(float(np.median(s)), 1),
+                          "ssim_us_min": round(min(s), 1), "ssim_us_max": round(max(s), 1),
+                          "ms_over_ssim": round(float(np.median(m)) / float(np.median(s)), 2)}), flush=True)
+        for d in (d_a, d_b, d_out, d_ms):
+            d.free()
+
+
 def command(args):
     from animal_vision_amd import compare
     from animal_vision_amd.yuv import rgb_to_yuv
@@ -141,7 +180,7 @@ def command(args):
                     f.write(pay[i % len(pay)].tobytes())
         argv = [os.path.join(d, "a.yuv"), os.path.join(d, "b.yuv"), "--pix-fmt", "nv12", "--size", f"{W}x{H}", "--batch", "8",
                 "--csv", os.path.join(d, "out.csv")]
-        for extra in ([], ["--no-ssim"]):
+        for extra in ([], ["--no-ssim"], ["--ms-ssim"]):
             fps = []
             for rep in range(args.reps + 1):
                 t0 = time.perf_counter()
@@ -151,7 +190,8 @@ def command(args):
                 assert status == 0, status
                 if rep:  # the first run is the warm-up
                     fps.append(args.frames / dt)
-            print(json.dumps({"command": "compare", "size": "4k", "pix_fmt": "nv12", "frames": args.frames, "batch": 8, "ssim": not extra,
+            print(json.dumps({"command": "compare", "size": "4k", "pix_fmt": "nv12", "frames": args.frames, "batch": 8, "ssim": extra != ["--no-ssim"],
+                              "ms_ssim": extra == ["--ms-ssim"],
                               "reps": args.reps, "fps_median": round(float(np.median(fps)), 1), "fps_min": round(min(fps), 1),
                               "fps_max": round(max(fps), 1)}), flush=True)
 
@@ -163,12 +203,14 @@ def main():
     k.add_argument("--reps", type=int, default=7)
     pl = sub.add_parser("planes")
     pl.add_argument("--reps", type=int, default=7)
+    m = sub.add_parser("ms")
+    m.add_argument("--reps", type=int, default=7)
     c = sub.add_parser("command")
     c.add_argument("--frames", type=int, default=32)
     c.add_argument("--reps", type=int, default=3)
     c.add_argument("--dir", default=None)
     args = ap.parse_args()
-    {"kernel": kernel, "planes": planes, "command": command}[args.cmd](args)
+    {"kernel": kernel, "planes": planes, "ms": ms, "command": command}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -77,10 +77,38 @@ int mst_tile_order() {
 // no other wave touches (its bytes are another octet's); (2b) after a barrier the second GEMM reads its B fragments from that map with the
 // same 16-byte reads the depthwise conv used to issue.  One ADDRESS register serves all of 2a (row pair, column shift and octet are
 // immediates), the taps need no LDS, and the vector unit is left with the GELUs.
+// DWS (round 6): the unit as TWO matrix instructions.  pack_dw_mfma's rows hold one non-zero per 8-channel K-octet, so shifts 0 and 1 together are a 2:4-sparse
+// K = 64 operand: one v_smfmac_f32_16x16x64_f16, whose 16-value B operand is the two 16-byte reads of shifts 0 and 1 in eight consecutive registers (the lane-constant
+// addresses do not change), behind ONE dense instruction for shift 2.  The dense one goes first: it takes C = 0 as an inline constant, while the sparse instruction
+// accumulates in place -- in the other order the accumulator would have to be zeroed with four vector moves per unit, on the unit that binds these kernels.  The
+// fragments (ml/mst_plus_plus.py::pack_dw_smfmac, same [octet][3][64] shape) are a[0] = compressed sparse operand, a[1] = dense shift 2, a[2].x = index word.
+// Measured beside the phase 2a GELU mix at 4 waves per SIMD: 71.7 ns per unit against 75.9 for three dense instructions; the sparse instruction alone costs about
+// 1.6 dense ones, not 1 (tools/experiments/smfmac_dw_probe.hip, profiles/r06/probe_smfmac_dw.txt).
+typedef _Float16 half16_t __attribute__((ext_vector_type(16)));
+template <bool DWS>
+__device__ __forceinline__ float4_t dw_unit(const half8_t (&a)[3], const uint4 (&bq)[3]) {
+    float4_t acc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (DWS) {
+        const half8_t b0 = __builtin_bit_cast(half8_t, bq[0]), b1 = __builtin_bit_cast(half8_t, bq[1]);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], __builtin_bit_cast(half8_t, bq[2]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_smfmac_f32_16x16x64_f16(a[0], __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15), acc,
+                                                       (int)__builtin_bit_cast(uint4, a[2]).x, 0, 0);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], __builtin_bit_cast(half8_t, bq[i]), acc, 0, 0, 0);
+    }
+    return acc;
+}
+// fragment i of a unit, this lane's 16 bytes at p; of DWS's third one only the index word is fetched (one register in flight and live, not four)
+template <bool DWS>
+__device__ __forceinline__ half8_t dw_frag(const uint4* p, int i) {
+    if (DWS && i == 2) return __builtin_bit_cast(half8_t, uint4{*reinterpret_cast<const unsigned*>(p), 0u, 0u, 0u});
+    return __builtin_bit_cast(half8_t, *p);
+}
 // NW: waves per workgroup.  8 everywhere in round 2; 16 (one 1024-thread workgroup per CU, 128 registers per lane) for the 62-channel blocks since round 3: their
 // 143 KB of LDS admit one workgroup per CU, and at 8 waves the vector unit saw 2 waves per SIMD -- half of what it needs to issue back to back.  With 16 waves a pass's
 // 16 octets map one to a wave in phase 2a, the 44 phase 1 items are 3 + 3 + 3 + 2 per channel tile, and in phase 2b a wave owns a row pair x ONE 32-channel output tile.
-template <int C, int HPASS, int MINW, bool DWM, bool STAMP = false, int NW = 8>
+template <int C, int HPASS, int MINW, bool DWM, bool STAMP = false, int NW = 8, bool DWS = false>
 __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* __restrict__ x /*[B][H][W][C]*/, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           float eps, const uint4* __restrict__ w1pack /*[4C/32][C/16][64]*/, const __half* __restrict__ taps /*[9][4C]*/,
                                                           const uint4* __restrict__ w2pack /*[C/32][4C/16][64]*/, __half* __restrict__ out /*[B][H][W][C], != x*/, int B,
@@ -92,7 +120,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
     static_assert(C == 32 || C == 64 || C == 128, "31-, 62- or 124-channel blocks (stored 32 / 64 / 128 wide)");
     constexpr int NTHR = 64 * NW, NGW = (NGRP + NW - 1) / NW;  // threads; halo pixel groups per wave
     constexpr int NTW = NT / (NW / 8), NOCTW = HPASS / (8 * NW);  // 32-channel output tiles per wave (phase 2b / epilogue); octets per wave and pass (phase 2a)
-    static_assert((NW == 8 || NW == 16) && NT % (NW / 8) == 0 && (!DWM || HPASS % (8 * NW) == 0) && (DWM || NW == 8), "wave split");
+    static_assert((NW == 8 || NW == 16) && NT % (NW / 8) == 0 && (!DWM || HPASS % (8 * NW) == 0) && (DWM || NW == 8) && (DWM || !DWS), "wave split");
     constexpr bool PREFETCH = C <= 64;  // the next tile's raw rows wait in registers during phase 2 (C = 128: 64 registers that the accumulators need)
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned char* yt = smem;                                       // [NGRP * 32][YPITCH]  LayerNorm'd rows, float16
@@ -289,7 +317,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
 #pragma unroll
                 for (int o2 = 0; o2 < NOCTW; ++o2)
 #pragma unroll
-                    for (int i = 0; i < 3; ++i) af[o2][i] = __builtin_bit_cast(half8_t, dwpack[((size_t)(pass * (HPASS / 8) + NW * o2 + wave) * 3 + i) * 64 + lane]);
+                    for (int i = 0; i < 3; ++i) af[o2][i] = dw_frag<DWS>(dwpack + ((size_t)(pass * (HPASS / 8) + NW * o2 + wave) * 3 + i) * 64 + lane, i);
             }
             // ---- phase 1: hidden = GELU(W1 y) for hidden channels [HPASS pass + 32 ct, + 32), ct = wave % NCT, pixel groups wave / NCT, + 8 / NCT, ... ----
             {
@@ -371,9 +399,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
 #pragma unroll
                     for (int u = 0; u < NU; ++u) {
                         const int o2 = u / (FTH / 2);
-                        float4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[o2][i], __builtin_bit_cast(half8_t, bq[i]), acc, 0, 0, 0);
+                        const float4_t acc = dw_unit<DWS>(af[o2], bq);
                         if (u + 1 < NU) rd(u + 1);
                         __builtin_amdgcn_sched_barrier(0);
                         if (u > 0) finish(u - 1, prev);
@@ -386,9 +412,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
                     for (int u = 0; u < NU; ++u) {
                         const int o2 = u / (FTH / 2);
                         rd(u);
-                        float4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[o2][i], __builtin_bit_cast(half8_t, bq[i]), acc, 0, 0, 0);
+                        const float4_t acc = dw_unit<DWS>(af[o2], bq);
                         finish(u, acc);
                     }
                 }
@@ -746,7 +770,8 @@ int launch_attn_tail(avx_ctx* ctx, const void* v, const void* x, const void* mpa
 //   * v is formed from x as it arrives: a lane's prefetched half row of its halo pixel IS its B operand (W_v packed in that K order,
 //     pack_fragments16(halfrow=True)); the x tile never sits in LDS.
 // NW: waves per workgroup (8; 16 for the 62-channel blocks, whose LDS footprint admits one workgroup per CU: two waves per octet as at C = 32, four waves per SIMD)
-template <int C, int TR, int MINW, bool STAMP = false, int NW = 8>
+// DWS: both convs take the two-instruction unit (dw_unit above; dw1 / dw2 are then pack_dw_smfmac fragments); in conv2 the order is dense shift 2, sparse, projection.
+template <int C, int TR, int MINW, bool STAMP = false, int NW = 8, bool DWS = false>
 __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half* __restrict__ x /*[B][H][W][C]*/, const uint4* __restrict__ wvpack /*[C/32][C/16][64], half-row K order*/,
                                                                 const uint4* __restrict__ mpack /*[C/8][C/16][64]*/, const uint4* __restrict__ dw1 /*[C/8][3][64]*/,
                                                                 const uint4* __restrict__ dw2 /*[C/8][3][64]*/, const float* __restrict__ bias /*[C] or NULL*/,
@@ -787,8 +812,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
     auto load_frags = [&](int oc) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            a1[i] = __builtin_bit_cast(half8_t, dw1[((size_t)oc * 3 + i) * 64 + lane]);
-            a2[i] = __builtin_bit_cast(half8_t, dw2[((size_t)oc * 3 + i) * 64 + lane]);
+            a1[i] = dw_frag<DWS>(dw1 + ((size_t)oc * 3 + i) * 64 + lane, i);
+            a2[i] = dw_frag<DWS>(dw2 + ((size_t)oc * 3 + i) * 64 + lane, i);
         }
 #pragma unroll
         for (int t2 = 0; t2 < NK; ++t2) am[t2] = __builtin_bit_cast(half8_t, mpack[((size_t)oc * NK + t2) * 64 + lane]);
@@ -928,9 +953,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
             float4_t prev = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int u = 0; u < NMID; ++u) {
-                float4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 3; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[i], __builtin_bit_cast(half8_t, bq[i]), acc, 0, 0, 0);
+                const float4_t acc = dw_unit<DWS>(a1, bq);
                 if (u + 1 < NMID) rd(u + 1);
                 __builtin_amdgcn_sched_barrier(0);
                 if (u > 0) finish(u - 1, prev);
@@ -972,9 +995,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
 #pragma unroll
                 for (int u = 0; u < NOUT; ++u) {
                     const uint2 xu = xn;
-                    float4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[i], __builtin_bit_cast(half8_t, bq[i]), acc, 0, 0, 0);
+                    float4_t acc = dw_unit<DWS>(a2, bq);
 #pragma unroll
                     for (int t2 = 0; t2 < NK; ++t2) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(am[t2], __builtin_bit_cast(half8_t, bg[t2]), acc, 0, 0, 0);
                     if (u + 1 < NOUT) rd(u + 1);
@@ -988,9 +1009,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
 #pragma unroll
                 for (int u = 0; u < NOUT; ++u) {
                     const uint2 xu = STASH ? xn : xr[STASH ? 0 : u];
-                    float4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[i], __builtin_bit_cast(half8_t, bq[i]), acc, 0, 0, 0);
+                    float4_t acc = dw_unit<DWS>(a2, bq);
 #pragma unroll
                     for (int t2 = 0; t2 < NK; ++t2) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(am[t2], __builtin_bit_cast(half8_t, bg[t2]), acc, 0, 0, 0);
                     if (u + 1 < NOUT) rd(u + 1);
@@ -1013,7 +1032,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
     }
 }
 
-template <int C, int TR, int MINW, int NW = 8>
+template <int C, int TR, int MINW, int NW = 8, bool DWS = false>
 int launch_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack, const void* mpack, const void* dw1, const void* dw2, const float* bias, void* out, int B, int H, int W,
                         hipStream_t s) {
     constexpr int PP = C * 2 + 16, RP = (18 * PP + 255) / 256 * 256;
@@ -1023,7 +1042,7 @@ int launch_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack, const v
     AVX_REQUIRE(ctx, total <= 0x7fffffffl, "avx_mst_attn_tail_mx: 2^31 tiles or more");
     const unsigned blocks = (unsigned)(total < cap ? total : cap);
     if (getenv("AVX_TAIL_STAMPS")) {  // diagnostic: per-segment cycles of every wave, summed and printed
-        auto ks = k_mst_attn_tail_mx<C, TR, MINW, true, NW>;
+        auto ks = k_mst_attn_tail_mx<C, TR, MINW, true, NW, DWS>;
         unsigned long long* d_st = nullptr;
         const size_t n = (size_t)blocks * NW * 8;
         AVX_HIP(ctx, hipMalloc((void**)&d_st, n * sizeof(unsigned long long)));
@@ -1042,7 +1061,7 @@ int launch_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack, const v
         (void)hipFree(d_st);
         return AVX_OK;
     }
-    auto k = k_mst_attn_tail_mx<C, TR, MINW, false, NW>;
+    auto k = k_mst_attn_tail_mx<C, TR, MINW, false, NW, DWS>;
     AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * NW), lds, s, (const __half*)x, (const uint4*)wvpack, (const uint4*)mpack, (const uint4*)dw1,
                        (const uint4*)dw2, bias, (__half*)out, B, H, W, (unsigned long long*)nullptr, mst_tile_order());
@@ -1549,7 +1568,7 @@ __global__ __launch_bounds__(256) void k_mst_conv_in_u8_mfma(const uint8_t* __re
 }  // namespace
 
 static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* taps_9xhid, const void* dwpack,
-                            const void* w2pack, void* out, int B, int H, int W, int C, void* stream);
+                            const void* w2pack, void* out, int B, int H, int W, int C, void* stream, bool sparse = false);
 
 // What the matrix-pipe kernels expect of their weights (csrc/mst_common.h, prescaled GELU): avx_mst_ffn_fused_mx takes W1 / s, the depthwise weights as they are
 // and W2 * s; avx_mst_attn_tail_mx takes pos_emb's first depthwise weights / s and the second * s.  s = 4 (1 when built with -DAVX_GELU_PRE=0).
@@ -1589,8 +1608,16 @@ extern "C" int avx_mst_ffn_fused_mx(avx_ctx* ctx, const void* x, const float* ga
     return ffn_fused_launch(ctx, x, gamma, beta, eps, w1pack, nullptr, dwpack, w2pack, out, B, H, W, C, stream);
 }
 
+// The same with the depthwise conv as one dense + one 2:4-sparse matrix instruction per unit (k_mst_ffn_fused<DWS>): dwpack = ml/mst_plus_plus.py::pack_dw_smfmac's fragments.
+extern "C" int avx_mst_ffn_fused_sp(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* dwpack,
+                                    const void* w2pack, void* out, int B, int H, int W, int C, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, dwpack && (((uintptr_t)dwpack) & 15u) == 0, "avx_mst_ffn_fused_sp: dwpack NULL or not 16-byte aligned");
+    return ffn_fused_launch(ctx, x, gamma, beta, eps, w1pack, nullptr, dwpack, w2pack, out, B, H, W, C, stream, true);
+}
+
 static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* taps_9xhid, const void* dwpack,
-                            const void* w2pack, void* out, int B, int H, int W, int C, void* stream) {
+                            const void* w2pack, void* out, int B, int H, int W, int C, void* stream, bool sparse) {
     AVX_REQUIRE(ctx, x && gamma && beta && w1pack && w2pack && out && B > 0 && H > 0 && W > 0, "avx_mst_ffn_fused: NULL pointer or empty tensor");
     AVX_REQUIRE(ctx, C == 32 || C == 64 || C == 128, "avx_mst_ffn_fused: C=%d (32, 64 or 128: 31-channel groups stored 32 wide)", C);
     AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)w1pack | (uintptr_t)w2pack | (uintptr_t)out | (uintptr_t)taps_9xhid)) & 15u) == 0,
@@ -1608,28 +1635,31 @@ static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, con
     AVX_REQUIRE(ctx, total <= 0x7fffffffl, "avx_mst_ffn_fused: 2^31 tiles or more");
     const dim3 grid((unsigned)(total < cap ? total : cap));
     const int order = mst_tile_order();
-#define AVX_FFN1(CV, HP, MW, DW, NWV)                                                                                                            \
+#define AVX_FFN1S(CV, HP, MW, DW, NWV, SP)                                                                                                       \
     {                                                                                                                                            \
-        auto k = k_mst_ffn_fused<CV, HP, MW, DW, false, NWV>;                                                                                    \
+        auto k = k_mst_ffn_fused<CV, HP, MW, DW, false, NWV, SP>;                                                                                \
         AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
         hipLaunchKernelGGL(k, grid, dim3(64 * NWV), lds, s, (const __half*)x, gamma, beta, eps, (const uint4*)w1pack, (const __half*)taps_9xhid, \
                            (const uint4*)w2pack, (__half*)out, B, H, W, (const uint4*)dwpack, (unsigned long long*)nullptr, order);              \
     }
-#define AVX_FFN(CV, HP, MW) { if (dwpack) AVX_FFN1(CV, HP, MW, true, 8) else AVX_FFN1(CV, HP, MW, false, 8) }
+#define AVX_FFN1(CV, HP, MW, DW, NWV) AVX_FFN1S(CV, HP, MW, DW, NWV, false)
+#define AVX_FFN(CV, HP, MW) { if (dwpack && sparse) AVX_FFN1S(CV, HP, MW, true, 8, true) else if (dwpack) AVX_FFN1(CV, HP, MW, true, 8) else AVX_FFN1(CV, HP, MW, false, 8) }
     if (dwpack && getenv("AVX_FFN_STAMPS") && ((C == 32 && small) || C == 64 || C == 128)) {  // diagnostic: per-segment cycles of every wave, summed and printed
         unsigned long long* d_st = nullptr;
         const int nwv = nw16 ? 16 : 8;
         const size_t n = (size_t)grid.x * nwv * 8;
         AVX_HIP(ctx, hipMalloc((void**)&d_st, n * sizeof(unsigned long long)));
-#define AVX_FFN_ST(CV, HP, MW, NWV)                                                                                                              \
+#define AVX_FFN_ST1(CV, HP, MW, NWV, SP)                                                                                                         \
     {                                                                                                                                            \
-        auto k = k_mst_ffn_fused<CV, HP, MW, true, true, NWV>;                                                                                   \
+        auto k = k_mst_ffn_fused<CV, HP, MW, true, true, NWV, SP>;                                                                               \
         AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
         hipLaunchKernelGGL(k, grid, dim3(64 * NWV), lds, s, (const __half*)x, gamma, beta, eps, (const uint4*)w1pack, (const __half*)taps_9xhid, \
                            (const uint4*)w2pack, (__half*)out, B, H, W, (const uint4*)dwpack, d_st, order);                                      \
     }
+#define AVX_FFN_ST(CV, HP, MW, NWV) { if (sparse) AVX_FFN_ST1(CV, HP, MW, NWV, true) else AVX_FFN_ST1(CV, HP, MW, NWV, false) }
         if (C == 32) AVX_FFN_ST(32, 64, 4, 8) else if (nw16) AVX_FFN_ST(64, 128, 1, 16) else if (C == 64) AVX_FFN_ST(64, 128, 2, 8) else AVX_FFN_ST(128, 64, 2, 8)
 #undef AVX_FFN_ST
+#undef AVX_FFN_ST1
         AVX_HIP(ctx, hipStreamSynchronize(s));
         unsigned long long* h_st = (unsigned long long*)malloc(n * sizeof(unsigned long long));
         AVX_HIP(ctx, hipMemcpy(h_st, d_st, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -1644,10 +1674,12 @@ static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, con
         free(h_st);
         (void)hipFree(d_st);
     } else if (C == 32 && small) AVX_FFN(32, 64, 4) else if (C == 32) AVX_FFN(32, 128, 2)
+    else if (nw16 && sparse) AVX_FFN1S(64, 128, 1, true, 16, true)
     else if (nw16) AVX_FFN1(64, 128, 1, true, 16)
     else if (C == 64) AVX_FFN(64, 128, 2) else AVX_FFN(128, 64, 2)
 #undef AVX_FFN
 #undef AVX_FFN1
+#undef AVX_FFN1S
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
 }
@@ -1684,9 +1716,9 @@ extern "C" int avx_mst_attn_tail_x(avx_ctx* ctx, const void* x, const void* wvpa
 
 // The tail with both depthwise convs and the projection on the matrix pipe (k_mst_attn_tail_mx): dw1pack / dw2pack = pos_emb's two depthwise
 // weights as pack_dw_mfma fragments, mpack_mx = avx_mst_attn_pack_mx's output.  out != x.
-extern "C" int avx_mst_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack,
-                                    const float* bias, void* out, int B, int H, int W, int C, void* stream) {
-    if (!ctx) return AVX_ERR_INVALID;
+template <bool DWS>
+static int attn_tail_mx_launch(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack, const float* bias, void* out,
+                               int B, int H, int W, int C, void* stream) {
     AVX_REQUIRE(ctx, x && wvpack16 && mpack_mx && dw1pack && dw2pack && out && B > 0 && H > 0 && W > 0, "avx_mst_attn_tail_mx: NULL pointer or empty tensor");
     AVX_REQUIRE(ctx, C == 32 || C == 64 || C == 128, "avx_mst_attn_tail_mx: C=%d (32, 64 or 128)", C);
     AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)wvpack16 | (uintptr_t)mpack_mx | (uintptr_t)out | (uintptr_t)dw1pack | (uintptr_t)dw2pack)) & 15u) == 0,
@@ -1694,11 +1726,22 @@ extern "C" int avx_mst_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvp
     AVX_REQUIRE(ctx, x != out, "avx_mst_attn_tail_mx: tiles read their neighbours' rows of x: the output cannot be x");
     AVX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = avx_pick_stream(ctx, stream);
-    if (C == 32) return launch_attn_tail_mx<32, 16, 4>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, s);
-    if (C == 128) return launch_attn_tail_mx<128, 8, 2>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, s);  // 14 x 8 tiles: 137 KB of LDS, two octets per wave
+    if (C == 32) return launch_attn_tail_mx<32, 16, 4, 8, DWS>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, s);
+    if (C == 128) return launch_attn_tail_mx<128, 8, 2, 8, DWS>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, s);  // 14 x 8 tiles: 137 KB of LDS, two octets per wave
     // 16 waves per workgroup (AVX_MST_TAIL_NW=16) measured no faster than 8 at C = 64 (258 vs 257 us per 4K launch: the kernel is not bound by occupancy): 8 it stays
-    if (getenv("AVX_MST_TAIL_NW") && atoi(getenv("AVX_MST_TAIL_NW")) == 16) return launch_attn_tail_mx<64, 16, 1, 16>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, s);
-    return launch_attn_tail_mx<64, 16, 2>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, s);
+    if (getenv("AVX_MST_TAIL_NW") && atoi(getenv("AVX_MST_TAIL_NW")) == 16) return launch_attn_tail_mx<64, 16, 1, 16, DWS>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, s);
+    return launch_attn_tail_mx<64, 16, 2, 8, DWS>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, s);
+}
+extern "C" int avx_mst_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack,
+                                    const float* bias, void* out, int B, int H, int W, int C, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    return attn_tail_mx_launch<false>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, C, stream);
+}
+// The same with both depthwise convs as one dense + one 2:4-sparse matrix instruction per unit (k_mst_attn_tail_mx<DWS>): dw1pack / dw2pack = pack_dw_smfmac fragments.
+extern "C" int avx_mst_attn_tail_sp(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack,
+                                    const float* bias, void* out, int B, int H, int W, int C, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    return attn_tail_mx_launch<true>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, C, stream);
 }
 
 extern "C" int avx_mst_conv3x3_lds(avx_ctx* ctx, const void* x, const void* wpack16, const void* add, void* out, int B, int H, int W, int C, void* stream) {

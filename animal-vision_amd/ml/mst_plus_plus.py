@@ -157,6 +157,45 @@ def pack_dw_mfma(w: torch.Tensor) -> torch.Tensor:
     return out.contiguous()
 
 
+def pack_dw_smfmac(w: torch.Tensor) -> torch.Tensor:
+    """(Ch, 1, 3, 3) float16 depthwise 3x3 weight -> the fragments of the TWO-instruction unit of csrc/mst_fused.hip (DWS): one dense
+    v_mfma_f32_16x16x32_f16 for column shift 2 and one 2:4-sparse v_smfmac_f32_16x16x64_f16 for shifts 0 and 1, as
+    [Ch/8 octets][3][64 lanes][8] float16 (the shape of pack_dw_mfma's result; the kernels load it the same way):
+      [o][0]  the compressed sparse A fragment,  [o][1]  the dense shift-2 fragment (= pack_dw_mfma(w)[o][2]),
+      [o][2]  the index word of the sparse instruction in its first 32 bits (cbsz = abid = 0: the low 16 bits are read), zeros behind it.
+    Operand layout of the sparse instruction as measured (tools/experiments/smfmac_dw_probe.hip, profiles/r06/probe_smfmac_dw.txt): the B
+    operand of lane (n, q) is 16 values, here elements 0 .. 7 = input row q at shift 0 and 8 .. 15 = row q at shift 1 (two 16-byte LDS reads
+    with pack_dw_mfma's lane-constant addresses); element e of the A operand of lane (m, qa), with t = bits 2 e, 2 e + 1 of the index word, meets
+    B element 8 (qa // 2) + 4 ((e % 4) // 2) + t of lane group 2 (qa % 2) + e // 4.  So lane (m = 8 s + c, qa) carries shift qa // 2 of input rows
+    2 (qa % 2) and 2 (qa % 2) + 1: four elements each, of which the pair c // 4 holds w[8 o + c][r - s][qa // 2] under index c % 4 and a zero.
+    A zero value contributes nothing whatever its index, so all-zero groups carry the indices (0, 1)."""
+    ch = w.shape[0]
+    assert ch % 8 == 0 and tuple(w.shape[1:]) == (1, 3, 3)
+    dev = w.device
+    lane = torch.arange(64, device=dev)
+    m, qa = lane % 16, lane // 16
+    s_, c = m // 8, m % 8
+    w8 = w.reshape(ch // 8, 8, 3, 3)                                # [o][c][dy][dx]
+    out = torch.zeros((ch // 8, 3, 64, 8), dtype=w.dtype, device=dev)
+    out[:, 1] = pack_dw_mfma(w)[:, 2]
+    t = c % 4
+    idx = torch.full((64,), 0x4444, dtype=torch.int64, device=dev)  # every pair (0, 1)
+    for hh in range(2):
+        r = 2 * (qa % 2) + hh
+        dy = r - s_
+        ok = (dy >= 0) & (dy <= 2)
+        vals = w8[:, c, dy.clamp(0, 2), qa // 2]                    # (O, 64)
+        vals = torch.where(ok[None, :], vals, torch.zeros_like(vals))
+        e = 4 * hh + 2 * (c // 4) + (t == 3).long()                 # index 0 .. 2: first element of its pair, the second carries (0, index 3); index 3: second, the first carries (0, index 2)
+        out[:, 0, lane, e] = vals
+        pair = torch.where(t == 3, 2 | (3 << 2), t | (3 << 2))      # the pair's four index bits
+        sh = 4 * (2 * hh + c // 4)
+        idx = (idx & ~(0xF << sh)) | (pair << sh)
+    lo = (((idx & 0xFFFF) ^ 0x8000) - 0x8000).to(torch.int16)       # the low half of the 32-bit index word, as the signed 16-bit pattern (the high half stays zero)
+    out.view(torch.int16)[:, 2, :, 0] = lo[None]                    # written as bits: never through float16 arithmetic
+    return out.contiguous()
+
+
 def fold_layernorm(w1_kn: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, scale: float) -> torch.Tensor:
     """(K = c input channels, N) weight of the 1x1 conv behind a LayerNorm -> float32 (K, N) weight for avx_mst_ffn_fused_mx, whose LayerNorm only centres and
     scales (include/avx.h): row k times gamma[k], row 31 (the first 32-wide group's padding channel; the kernel feeds it a 1) = beta @ W, everything / scale."""
@@ -194,6 +233,10 @@ class _AvxOps:
         self._ffn = os.environ.get("AVX_MST_NO_FFN_FUSED", "") == ""  # A/B: the whole FeedForward in one kernel, hidden tile in LDS
         self._gelu_pre = None
         self._dwmx = os.environ.get("AVX_MST_NO_DW_MFMA", "") == ""  # A/B: depthwise 3x3 convs on the matrix pipe (round 3)
+        self._dwsp = os.environ.get("AVX_MST_NO_DW_SPARSE", "") == ""  # A/B: the depthwise units as one dense + one 2:4-sparse matrix instruction (round 6)
+        # widths at which the sparse form measured faster than the dense one, kernel against kernel in one process (profiles/r06/ab_dw_sparse_kernels.txt)
+        self.DW_SPARSE_FFN_C = (32, 64, 128)
+        self.DW_SPARSE_TAIL_C = (32, 64)  # C = 128: 1.5 % slower (two octets per wave, fragments reloaded per octet)
         self._specfuse = os.environ.get("AVX_MST_NO_SPEC_FUSE", "") == ""  # A/B: the spectral integration as conv_out's epilogue (the cube is never written)
         self.FFN_FUSED_C = tuple(int(v) for v in os.environ.get("AVX_MST_FFN_FUSED_C", "32,64,128").split(",") if v)
         self._ctx = {}
@@ -456,17 +499,18 @@ class _AvxOps:
         return out
 
     def attn_tail_mx(self, x: torch.Tensor, wvpack16: torch.Tensor, mpack_mx: torch.Tensor, dw1: torch.Tensor, dw2: torch.Tensor, bias: torch.Tensor,
-                     out: torch.Tensor = None) -> torch.Tensor:
+                     out: torch.Tensor = None, sparse: bool = False) -> torch.Tensor:
         """pos_emb(v) + v @ M + bias + x with v = float16(x @ W_v) formed inside the kernel and both depthwise convs on the matrix pipe, on one
-        (h, w, c) float16 frame (csrc/mst_fused.hip::k_mst_attn_tail_mx)."""
+        (h, w, c) float16 frame (csrc/mst_fused.hip::k_mst_attn_tail_mx).  sparse: dw1 / dw2 are pack_dw_smfmac fragments (avx_mst_attn_tail_sp)."""
         from .._lib import lib
 
         h, w, c = x.shape
         assert x.is_contiguous()
         out = torch.empty_like(x) if out is None else out
         ctx = self.ctx(x.device)
-        ctx._check(lib.avx_mst_attn_tail_mx(ctx._h, x.data_ptr(), wvpack16.data_ptr(), mpack_mx.data_ptr(), dw1.data_ptr(), dw2.data_ptr(), bias.data_ptr(),
-                                            out.data_ptr(), 1, h, w, c, torch.cuda.current_stream(x.device).cuda_stream))
+        fn = lib.avx_mst_attn_tail_sp if sparse else lib.avx_mst_attn_tail_mx
+        ctx._check(fn(ctx._h, x.data_ptr(), wvpack16.data_ptr(), mpack_mx.data_ptr(), dw1.data_ptr(), dw2.data_ptr(), bias.data_ptr(),
+                      out.data_ptr(), 1, h, w, c, torch.cuda.current_stream(x.device).cuda_stream))
         return out
 
     def attn_tail(self, v: torch.Tensor, x: torch.Tensor, mpack16: torch.Tensor, taps1: torch.Tensor, taps2: torch.Tensor, bias: torch.Tensor,
@@ -511,9 +555,10 @@ class _AvxOps:
         return out
 
     def ffn_fused(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, w1p: torch.Tensor, taps: torch.Tensor, w2p: torch.Tensor,
-                  eps: float = 1e-5, dwpack: torch.Tensor = None) -> torch.Tensor:
+                  eps: float = 1e-5, dwpack: torch.Tensor = None, sparse: bool = False) -> torch.Tensor:
         """x + FeedForward(LayerNorm(x)) on (b, h, w, c) float16 in ONE kernel, the 4c hidden tile in LDS (csrc/mst_fused.hip).
-        dwpack (pack_dw_mfma): the depthwise conv runs on the matrix pipe (avx_mst_ffn_fused_mx); else taps ([9][4c]) on the vector unit."""
+        dwpack (pack_dw_mfma): the depthwise conv runs on the matrix pipe (avx_mst_ffn_fused_mx); else taps ([9][4c]) on the vector unit.
+        sparse: dwpack is pack_dw_smfmac's (avx_mst_ffn_fused_sp: one dense + one 2:4-sparse instruction per unit)."""
         from .._lib import lib
 
         b, h, w, c = x.shape
@@ -522,8 +567,8 @@ class _AvxOps:
         ctx = self.ctx(x.device)
         st = torch.cuda.current_stream(x.device).cuda_stream
         if dwpack is not None:
-            ctx._check(lib.avx_mst_ffn_fused_mx(ctx._h, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, w1p.data_ptr(), dwpack.data_ptr(), w2p.data_ptr(),
-                                                out.data_ptr(), b, h, w, c, st))
+            fn = lib.avx_mst_ffn_fused_sp if sparse else lib.avx_mst_ffn_fused_mx
+            ctx._check(fn(ctx._h, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, w1p.data_ptr(), dwpack.data_ptr(), w2p.data_ptr(), out.data_ptr(), b, h, w, c, st))
         else:
             ctx._check(lib.avx_mst_ffn_fused(ctx._h, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, w1p.data_ptr(), taps.data_ptr(), w2p.data_ptr(),
                                              out.data_ptr(), b, h, w, c, st))
@@ -738,10 +783,12 @@ class MSTPlusPlus(torch.nn.Module):
                 if tailx and _AVX._dwmx:  # both depthwise convs and the projection on the matrix pipe
                     wv16 = self._prep(p + ".wv.frag16h", lambda: pack_fragments16(wqkv[:, 2 * c :].contiguous(), halfrow=True))
                     gs = _AVX.gelu_prescale()  # the GELU between the two convs works on x / gs (csrc/mst_common.h): first conv / gs, second * gs
-                    d1 = self._prep(k1 + f".dwmx/{gs}", lambda: pack_dw_mfma((self._w(k1, (0,)).float() / gs).to(x.dtype)))
-                    d2 = self._prep(k2 + f".dwmx*{gs}", lambda: pack_dw_mfma((self._w(k2, (0,)).float() * gs).to(x.dtype)))
+                    sp = _AVX._dwsp and c in _AVX.DW_SPARSE_TAIL_C
+                    pk, tag = (pack_dw_smfmac, ".dwsp") if sp else (pack_dw_mfma, ".dwmx")
+                    d1 = self._prep(k1 + f"{tag}/{gs}", lambda: pk((self._w(k1, (0,)).float() / gs).to(x.dtype)))
+                    d2 = self._prep(k2 + f"{tag}*{gs}", lambda: pk((self._w(k2, (0,)).float() * gs).to(x.dtype)))
                     for i in range(b):
-                        _AVX.attn_tail_mx(xc[i], wv16, _AVX.attn_pack_mx(gram[i], nq[i], nk[i], resc, wpt), d1, d2, bias32, out[i])
+                        _AVX.attn_tail_mx(xc[i], wv16, _AVX.attn_pack_mx(gram[i], nq[i], nk[i], resc, wpt), d1, d2, bias32, out[i], sparse=sp)
                     return out
                 if tailx:
                     wv16 = self._prep(p + ".wv.frag16", lambda: pack_fragments16(wqkv[:, 2 * c :].contiguous()))
@@ -813,6 +860,8 @@ class MSTPlusPlus(torch.nn.Module):
                 gs = _AVX.gelu_prescale()  # both GELUs work on x / gs (csrc/mst_common.h): W1 / gs, the depthwise conv as it is (linear: x2 / gs again), W2 * gs
                 w1s = self._prep(p + f".w1.frag16.ln/{gs}", lambda: pack_fragments16(fold_layernorm(self._w(p + ".fn.net.0.weight", (0, 1)).reshape(4 * c, c).t(), g32, b32, gs).to(x.dtype)))
                 w2s = self._prep(p + f".w2.frag16*{gs}", lambda: pack_fragments16((w2.float() * gs).to(x.dtype).contiguous()))
+                if _AVX._dwsp and c in _AVX.DW_SPARSE_FFN_C:
+                    return _AVX.ffn_fused(x, g32, b32, w1s, None, w2s, dwpack=self._prep(key + ".dwsp", lambda: pack_dw_smfmac(self._w(key, (0,)))), sparse=True)
                 return _AVX.ffn_fused(x, g32, b32, w1s, None, w2s, dwpack=self._prep(key + ".dwmx", lambda: pack_dw_mfma(self._w(key, (0,)))))
             w1q = self._prep(p + ".w1.frag16", lambda: pack_fragments16(self._w(p + ".fn.net.0.weight", (0, 1)).reshape(4 * c, c).t().contiguous()))
             w2q = self._prep(p + ".w2.frag16", lambda: pack_fragments16(w2))

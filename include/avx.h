@@ -678,6 +678,11 @@ int avx_mst_attn_tail_x(avx_ctx* ctx, const void* x, const void* wvpack16, const
  * avx_mst_attn_tail_x.  C = 32, 64 or 128; out != x. */
 int avx_mst_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack,
                          const float* bias, void* out, int B, int H, int W, int C, void* stream);
+/* The same with each depthwise unit as TWO matrix instructions (round 6): one dense v_mfma_f32_16x16x32_f16 for column shift 2, then one 2:4-sparse
+ * v_smfmac_f32_16x16x64_f16 for shifts 0 and 1 (a row of the weight operand holds one non-zero per 8-channel K-octet).  dw1pack / dw2pack:
+ * ml/mst_plus_plus.py::pack_dw_smfmac fragments, scaled as for avx_mst_attn_tail_mx.  Same result up to the summation order of the nine taps. */
+int avx_mst_attn_tail_sp(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack,
+                         const float* bias, void* out, int B, int H, int W, int C, void* stream);
 /* avx_mst_attn_pack16's matrix M in the fragment order avx_mst_attn_tail_mx takes: [C/8][C/16][64][8] float16 (4 C^2 entries, half of them
  * the zeros of the block-diagonal form). */
 int avx_mst_attn_pack_mx(avx_ctx* ctx, const float* gram, const float* nq, const float* nk, const float* rescale, const float* wproj_t, int C, void* mpack,
@@ -704,6 +709,9 @@ int avx_mst_ffn_fused(avx_ctx* ctx, const void* x, const float* gamma, const flo
  * outputs).  dwpack: the depthwise weights as A fragments, [4C/8 octets][3 shifts][64 lanes][8] float16
  * (ml/mst_plus_plus.py::pack_dw_mfma).  Same result up to the summation order of the nine taps (float32 accumulation in both). */
 int avx_mst_ffn_fused_mx(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* dwpack,
+                         const void* w2pack, void* out, int B, int H, int W, int C, void* stream);
+/* avx_mst_ffn_fused_mx with the two-instruction depthwise unit of avx_mst_attn_tail_sp; dwpack: ml/mst_plus_plus.py::pack_dw_smfmac (same shape). */
+int avx_mst_ffn_fused_sp(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* dwpack,
                          const void* w2pack, void* out, int B, int H, int W, int C, void* stream);
 /* The matrix-pipe kernels evaluate GELU on PRESCALED operands (csrc/mst_common.h: x / s enters, gelu(x) / s leaves; two packed instructions fewer per pair).
  * s = avx_mst_gelu_prescale() (4: a power of two, exact in float16; 1 when the library was built without the prescaled form), and the caller scales the

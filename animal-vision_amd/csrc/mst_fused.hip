@@ -1085,18 +1085,97 @@ int launch_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack, const v
 // of the cropped frame, with the per-workgroup min / max / sum the von Kries step needs (Stat3 as in csrc/uv.hip).  The cube is never written: 531 MB less to
 // write and 531 MB less to read per 4K frame, one launch less.
 struct SpecStat3 { float mn, mx; double sum; };  // == csrc/uv.hip::Stat3
-template <int MINW, bool GRAM, bool SPEC = false>
+
+// ---- conv_in (3 -> 31 channels, 3x3) of the uint8 frame for 32 pixels of one wave: the arithmetic of k_mst_conv_in_u8_mfma (below), shared with its consumers ----
+// Lane (p, h) carries pixel p's taps 5 h ... 5 h + 4 (h = 1: four taps and a zero) as 15 K slots + a zero, float16(u8 * (1 / 255)); the two A fragments hold
+// the 27 x 32 table in that slot order, their rows permuted so that the lane ends up with channels 16 h ... 16 h + 15 of its pixel -- the layout of a residual
+// operand and of a halo-tile row.  A source pixel travels as one dword: bytes 0-2 its channels (0 = a tap that contributes nothing: float16(0 * (1 / 255)) = +0).
+struct ConvInFrame { const uint8_t* frame; int H, W, pt, pl, Hp, Wp; };  // the frame, its reflect pads (top, left) and the padded size
+__device__ __forceinline__ half8_t conv_in_afrag(const float* __restrict__ w /*[27][32]*/, int lane, int s) {
+    const int p = lane & 31, h = lane >> 5;
+    const int col = 16 * ((p % 8) / 4) + 4 * (p / 8) + p % 4;  // output channel of this lane's A row
+    const int tap0 = 5 * h, ntap = 5 - h;
+    half8_t a;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int q = 8 * s + j, k = 3 * tap0 + q;  // slot q of this half = (tap tap0 + q / 3, channel q % 3)
+        a[j] = q < 3 * ntap ? (_Float16)w[k * 32 + col] : (_Float16)0.f;
+    }
+    return a;
+}
+// the three bytes of frame pixel idx (the last pixel's dword would end one byte past the frame: it is read one byte early and shifted)
+__device__ __forceinline__ unsigned conv_in_px(const uint8_t* __restrict__ frame, int idx, int last) {
+    const int late = idx == last ? 1 : 0;
+    unsigned v;
+    __builtin_memcpy(&v, frame + (unsigned)(idx * 3 - late), 4);  // (the entry points refuse frames of 2 GiB and more)
+    return (late ? v >> 8 : v) & 0xffffffu;
+}
+// source pixel of padded-frame position (yy, xx): reflected (no edge repeat) back into the frame, 0 outside the padded frame (the conv's zero padding applies there)
+__device__ __forceinline__ unsigned conv_in_src(const ConvInFrame& f, int yy, int xx, bool want = true) {
+    const bool ok = want && yy >= 0 && yy < f.Hp && xx >= 0 && xx < f.Wp;
+    int sy = (ok ? yy : 0) - f.pt, sx = (ok ? xx : 0) - f.pl;
+    sy = sy < 0 ? -sy : (sy >= f.H ? 2 * (f.H - 1) - sy : sy);
+    sx = sx < 0 ? -sx : (sx >= f.W ? 2 * (f.W - 1) - sx : sx);
+    const unsigned v = conv_in_px(f.frame, sy * f.W + sx, f.H * f.W - 1);
+    return ok ? v : 0u;
+}
+// this lane's five source pixels for the output pixel at padded-frame position (y, x)
+__device__ __forceinline__ void conv_in_fetch(const ConvInFrame& f, int y, int x, int h, unsigned raw[5]) {
+#pragma unroll
+    for (int t = 0; t < 5; ++t) {
+        const int tap = 5 * h + (t < 5 - h ? t : 0);
+        raw[t] = conv_in_src(f, y + tap / 3 - 1, x + tap % 3 - 1, t < 5 - h);
+    }
+}
+// ... -> channels 16 h ... 16 h + 15 of the lane's pixel as float16 (o[0]: the first eight)
+__device__ __forceinline__ void conv_in_mfma(const unsigned raw[5], half8_t a0, half8_t a1, uint4 o[2]) {
+    const float inv255 = 1.0f / 255.0f;
+    float v[16];
+    v[15] = 0.f;
+#pragma unroll
+    for (int t = 0; t < 5; ++t)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[3 * t + c] = (float)((raw[t] >> (8 * c)) & 0xffu) * inv255;
+    const half8_t b0 = __builtin_bit_cast(half8_t, uint4{pack_f16(v[0], v[1]), pack_f16(v[2], v[3]), pack_f16(v[4], v[5]), pack_f16(v[6], v[7])});
+    const half8_t b1 = __builtin_bit_cast(half8_t, uint4{pack_f16(v[8], v[9]), pack_f16(v[10], v[11]), pack_f16(v[12], v[13]), pack_f16(v[14], v[15])});
+    float16_t d;
+#pragma unroll
+    for (int vv = 0; vv < 16; ++vv) d[vv] = 0.f;
+    d = mfma16(a0, b0, d);
+    d = mfma16(a1, b1, d);
+    unsigned q[8];
+#pragma unroll
+    for (int vv = 0; vv < 8; ++vv) q[vv] = pack_f16(d[2 * vv], d[2 * vv + 1]);
+    o[0] = uint4{q[0], q[1], q[2], q[3]};
+    o[1] = uint4{q[4], q[5], q[6], q[7]};
+}
+
+// CINR (round 7): the residual `add` is conv_in's output and is not read but recomputed from the uint8 frame -- a wave's 32 output pixels are one conv_in
+// evaluation, whose result lands in the residual's register layout.  CINX: the INPUT is conv_in's output: the 18 x 18 halo tile is produced in place, 11
+// evaluations over the 8 waves, from the tile's 20 x 20 source pixels (staged in LDS as one dword each, the next tile's in flight during this tile's MFMAs).
+// Two paddings meet there: a conv_in tap outside the PADDED frame contributes 0 (one inside the padding takes the reflected pixel), and a halo pixel of the
+// 3 x 3 conv outside the padded frame IS zero, not conv_in evaluated there.  With both, conv_in's tensor (64 B/px) is neither written nor read.
+template <int MINW, bool GRAM, bool SPEC = false, bool CINR = false, bool CINX = false>
 __global__ __launch_bounds__(kFT, MINW) void k_mst_conv3x3_lds(const __half* __restrict__ x /*[B][H][W][32]*/, const uint4* __restrict__ wpack /*[9][2][64]*/,
                                                                const __half* __restrict__ add /*or NULL*/, __half* __restrict__ out, int B, int H, int W,
                                                                const uint4* __restrict__ wqk /*[2][2][64]: pack_qkv16's q and k tiles*/, float* __restrict__ partial /*[blocks][34][32]*/,
                                                                const float* __restrict__ specw = nullptr /*SPEC: [32 bands][4]: the three catches' weights, band-major*/,
                                                                float* __restrict__ planes = nullptr /*SPEC: [3][Hc * Wc]*/, SpecStat3* __restrict__ spart = nullptr /*SPEC: [blocks][3]*/,
-                                                               int crop_t = 0, int crop_l = 0, int Hc = 0, int Wc = 0, int order = AVX_TILE_ORDER_RASTER /*GRAM / SPEC: raster only (their per-workgroup partial sums pin the summation order)*/) {
-    constexpr int C = 32, PP = C * 2 + 16, RP = (HS * PP + 255) / 256 * 256, NFILL = (HS * HS * 4 + kFT - 1) / kFT;
+                                                               int crop_t = 0, int crop_l = 0, int Hc = 0, int Wc = 0, int order = AVX_TILE_ORDER_RASTER /*GRAM / SPEC: raster only (their per-workgroup partial sums pin the summation order)*/,
+                                                               ConvInFrame cf = ConvInFrame{nullptr, 0, 0, 0, 0, 0, 0} /*CINR / CINX: H x W is its padded size*/, const float* __restrict__ cw = nullptr /*CINR / CINX: [27][32]*/) {
+    static_assert(!(CINR && CINX), "the frame stands in for the residual or for the input");
+    constexpr bool CIN = CINR || CINX;
+    constexpr int C = 32, PP = C * 2 + 16, RP = (HS * PP + 255) / 256 * 256, NFILL = CINX ? 1 : (HS * HS * 4 + kFT - 1) / kFT;
+    constexpr int SS = HS + 2;  // CINX: side of the tile's source window (the halo tile's own halo)
     __shared__ __align__(16) unsigned char xt[HS * RP];
     __shared__ uint4 wl[18 * 64];  // the 18 A fragments (9 taps x 2 K-steps): in registers they cost 72 VGPRs and a wave of occupancy
+    __shared__ uint4 cwl[CIN ? 2 * 64 : 1];  // conv_in's two A fragments
+    __shared__ unsigned st[CINX ? SS * SS : 1];  // CINX: the source window, one dword per pixel
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 31, h = lane >> 5;
     for (int i = tid; i < 18 * 64; i += kFT) wl[i] = wpack[i];
+    if constexpr (CIN) {
+        if (tid < 2 * 64) cwl[tid] = __builtin_bit_cast(uint4, conv_in_afrag(cw, lane, wave));
+    }
     __shared__ uint4 wq[GRAM ? 4 * 64 : 1];
     float16_t G;
     float nq = 0.f, nk = 0.f;
@@ -1116,11 +1195,17 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_conv3x3_lds(const __half* __r
         f_rel[k] = (unsigned)(((q / HS) * W + q % HS) * C + 8 * part) * 2u;
     }
     auto fetch = [&](const Tile& t) {
+        int tq = tid;
+        if constexpr (CINR) asm volatile("" : "+v"(tq));  // CINR at six waves has no registers for this thread's constants: they are formed per tile (f_rel too)
         if (t.y0 >= 1 && t.y0 + HS - 1 <= H && t.x0 >= 1 && t.x0 + HS - 1 <= W) {  // halo inside the frame: scalar origin + fixed lane offsets
             const char* origin = reinterpret_cast<const char*>(x + ((t.b * H + t.y0 - 1) * (size_t)W + t.x0 - 1) * C);
 #pragma unroll
             for (int k = 0; k < NFILL; ++k) {
                 unsigned o = f_rel[k];
+                if constexpr (CINR) {
+                    const int it = tq + k * kFT, itc = it < HS * HS * 4 ? it : 0, q = itc >> 2, part = itc & 3;
+                    o = (unsigned)(((q / HS) * W + q % HS) * C + 8 * part) * 2u;
+                }
                 asm volatile("" : "+v"(o));  // keeps the zero-extension here (see k_mst_attn_tail)
                 pre[k] = *reinterpret_cast<const uint4*>(origin + o);
             }
@@ -1128,7 +1213,7 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_conv3x3_lds(const __half* __r
         }
 #pragma unroll
         for (int k = 0; k < NFILL; ++k) {
-            const int it = tid + k * kFT, q = it >> 2, part = it & 3;
+            const int it = tq + k * kFT, q = it >> 2, part = it & 3;
             const int yy = t.y0 - 1 + q / HS, xx = t.x0 - 1 + q % HS;
             const bool ok = it < HS * HS * 4 && yy >= 0 && yy < H && xx >= 0 && xx < W;
             const int yc = yy < 0 ? 0 : (yy >= H ? H - 1 : yy), xc = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
@@ -1137,27 +1222,102 @@ __global__ __launch_bounds__(kFT, MINW) void k_mst_conv3x3_lds(const __half* __r
             pre[k] = r;
         }
     };
+    // CINX: this thread's pixel of the tile's SS x SS source window (padded-frame positions y0 - 2 ..., x0 - 2 ...), the next tile's in flight as pre[] is
+    unsigned praw = 0u;
+    const int s_i = tid / SS, s_j = tid - s_i * SS;
+    auto fetch_src = [&](const Tile& t) {
+        if (tid >= SS * SS) return;
+        const int sy0 = t.y0 - 2 - cf.pt, sx0 = t.x0 - 2 - cf.pl;
+        if (sy0 >= 0 && sy0 + SS < cf.H && sx0 >= 0 && sx0 + SS <= cf.W) {  // the window lies in the unpadded frame, clear of its last row: no reflection, no pixel's dword ends past the frame
+            unsigned v;
+            __builtin_memcpy(&v, cf.frame + (unsigned)(((sy0 + s_i) * cf.W + sx0 + s_j) * 3), 4);
+            praw = v;  // the fourth byte is masked where praw is used: touching the value here would wait for the load at once, and it would not be in flight under the MFMAs
+            return;
+        }
+        praw = conv_in_src(cf, t.y0 - 2 + s_i, t.x0 - 2 + s_j);
+    };
+    // CINR: the five source pixels of this lane's output pixel of tile t, requested a tile ahead like pre[] (five registers, against the sixteen conv_in's
+    // accumulator would hold next to the conv's own at the end of the tile)
+    unsigned rraw[5] = {0u, 0u, 0u, 0u, 0u};
+    auto fetch_res = [&](const Tile& t) {
+        unsigned* raw = rraw;
+        int lq = tid;
+        asm volatile("" : "+v"(lq));  // what follows is formed anew per tile: hoisted out of the tile loop, the lane's constants cost more registers than the kernel has
+        const int h = (lq >> 5) & 1, yl = t.y0 + 2 * (lq >> 6) + ((lq >> 4) & 1), xl = t.x0 + (lq & 15);
+        const bool alive = yl < H && xl < W;
+        const int yo = alive ? yl : 0, xo = alive ? xl : 0;
+        const int sy0 = t.y0 - 1 - cf.pt, sx0 = t.x0 - 1 - cf.pl;
+        if (sy0 >= 0 && sy0 + HS < cf.H && sx0 >= 0 && sx0 + HS <= cf.W) {  // as above, for the tile's HS x HS window: every output pixel is live, every tap a frame pixel
+            const int at = (yo - cf.pt) * cf.W + xo - cf.pl;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const int tap = h ? (k < 4 ? 5 + k : 5) : k;
+                unsigned v;
+                __builtin_memcpy(&v, cf.frame + (unsigned)((at + (tap / 3 - 1) * cf.W + tap % 3 - 1) * 3), 4);
+                raw[k] = v;  // masked (and the fifth slot of lane half 1 zeroed) where rraw is used, so that the loads stay in flight under the MFMAs
+            }
+            return;
+        }
+        conv_in_fetch(cf, yo, xo, h, raw);
+    };
     TileWalk ahead;  // after its first step: the NEXT tile (this one's coordinates are in t)
     ahead.init(blockIdx.x, gridDim.x, B, ty, tx, (GRAM || SPEC) ? (int)AVX_TILE_ORDER_RASTER : order);
     if (!ahead.live) return;
     Tile t = tile_at(ahead, TS, TS);
     ahead.advance();
-    fetch(t);
+    if constexpr (CINX) fetch_src(t);
+    else fetch(t);
+    if constexpr (CINR) fetch_res(t);
     for (;;) {
+        if constexpr (CINX) {
+            if (tid < SS * SS) st[tid] = praw & 0xffffffu;
+            __syncthreads();
+            const half8_t a0 = __builtin_bit_cast(half8_t, cwl[lane]), a1 = __builtin_bit_cast(half8_t, cwl[64 + lane]);
+            for (int g = wave; g < (HS * HS + 31) / 32; g += kFT / 64) {  // 11 evaluations of 32 halo pixels over the 8 waves
+                const int q = g * 32 + p, qc = q < HS * HS ? q : 0, hi = qc / HS, hj = qc - hi * HS;
+                unsigned raw[5];
 #pragma unroll
-        for (int k = 0; k < NFILL; ++k) {
-            const int it = tid + k * kFT, q = it >> 2, part = it & 3;
-            if (it < HS * HS * 4) *reinterpret_cast<uint4*>(xt + (size_t)(q / HS) * RP + (size_t)(q % HS) * PP + 16 * part) = pre[k];
+                for (int k = 0; k < 5; ++k) {
+                    const int o0 = (k / 3) * SS + k % 3, o1 = ((5 + (k < 4 ? k : 0)) / 3) * SS + (5 + (k < 4 ? k : 0)) % 3;  // tap (ky, kx) of halo pixel (hi, hj) = window pixel (hi + ky, hj + kx)
+                    const unsigned v = st[hi * SS + hj + (h ? o1 : o0)];
+                    raw[k] = (h && k == 4) ? 0u : v;
+                }
+                uint4 o[2];
+                conv_in_mfma(raw, a0, a1, o);
+                const int yy = t.y0 - 1 + hi, xx = t.x0 - 1 + hj;
+                if (!(yy >= 0 && yy < H && xx >= 0 && xx < W)) o[0] = o[1] = uint4{0, 0, 0, 0};  // the 3 x 3 conv's own zero padding: not conv_in evaluated out there
+                if (q < HS * HS) {
+                    uint4* dst = reinterpret_cast<uint4*>(xt + (size_t)hi * RP + (size_t)hj * PP + 32 * h);
+                    dst[0] = o[0]; dst[1] = o[1];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NFILL; ++k) {
+                const int it = tid + k * kFT, q = it >> 2, part = it & 3;
+                if (it < HS * HS * 4) *reinterpret_cast<uint4*>(xt + (size_t)(q / HS) * RP + (size_t)(q % HS) * PP + 16 * part) = pre[k];
+            }
         }
         __syncthreads();
-        if (ahead.live) fetch(tile_at(ahead, TS, TS));
         {
             const int r = 2 * wave + (p >> 4), c = p & 15;
             const int yo = t.y0 + r, xo = t.x0 + c;
             const bool live = yo < H && xo < W;
-            const size_t off = ((t.b * H + (live ? yo : 0)) * (size_t)W + (live ? xo : 0)) * C + 16 * h;
             uint4 ar[2] = {uint4{0, 0, 0, 0}, uint4{0, 0, 0, 0}};
-            if (add) { ar[0] = reinterpret_cast<const uint4*>(add + off)[0]; ar[1] = reinterpret_cast<const uint4*>(add + off)[1]; }
+            if constexpr (CINR) {  // the residual: pre[] is in the LDS and the conv's accumulator not yet live -- conv_in's fits in between
+#pragma unroll
+                for (int k = 0; k < 5; ++k) rraw[k] = (h && k == 4) ? 0u : rraw[k] & 0xffffffu;
+                conv_in_mfma(rraw, __builtin_bit_cast(half8_t, cwl[lane]), __builtin_bit_cast(half8_t, cwl[64 + lane]), ar);
+            }
+            if (ahead.live) {
+                if constexpr (CINR) fetch_res(tile_at(ahead, TS, TS));
+                if constexpr (CINX) fetch_src(tile_at(ahead, TS, TS));
+                else fetch(tile_at(ahead, TS, TS));
+            }
+            const size_t off = ((t.b * H + (live ? yo : 0)) * (size_t)W + (live ? xo : 0)) * C + 16 * h;
+            if constexpr (!CIN) {  // (CINX: the embedding conv has no residual, and a load the compiler cannot rule out makes it wait for the prefetch in front of the stores)
+                if (add) { ar[0] = reinterpret_cast<const uint4*>(add + off)[0]; ar[1] = reinterpret_cast<const uint4*>(add + off)[1]; }
+            }
             float16_t d;
 #pragma unroll
             for (int v = 0; v < 16; ++v) d[v] = 0.f;
@@ -1514,53 +1674,19 @@ __global__ __launch_bounds__(256) void k_mst_conv_in_u8(const uint8_t* __restric
 __global__ __launch_bounds__(256) void k_mst_conv_in_u8_mfma(const uint8_t* __restrict__ frame /*[H][W][3]*/, const float* __restrict__ w /*[27][32]*/,
                                                              __half* __restrict__ out /*[Hp][Wp][32]*/, int H, int W, int pt, int pl, int Hp, int Wp) {
     const int lane = threadIdx.x & 63, p = lane & 31, h = lane >> 5;
-    const int col = 16 * ((p % 8) / 4) + 4 * (p / 8) + p % 4;  // output channel of this lane's A row
-    const int tap0 = 5 * h, ntap = 5 - h;                      // this lane half's taps: [tap0, tap0 + ntap)
-    half8_t af[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int q = 8 * s + j, k = 3 * tap0 + q;  // slot q of this half = (tap tap0 + q / 3, channel q % 3)
-            af[s][j] = q < 3 * ntap ? (_Float16)w[k * 32 + col] : (_Float16)0.f;
-        }
-    int dy[5], dx[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t) {
-        const int tap = tap0 + (t < ntap ? t : 0);
-        dy[t] = tap / 3 - 1; dx[t] = tap % 3 - 1;
-    }
+    const half8_t a0 = conv_in_afrag(w, lane, 0), a1 = conv_in_afrag(w, lane, 1);
+    const ConvInFrame cf{frame, H, W, pt, pl, Hp, Wp};
     const size_t total = (size_t)Hp * Wp, ngroups = (total + 31) / 32;
-    const float inv255 = 1.0f / 255.0f;
     for (size_t g = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < ngroups; g += (size_t)gridDim.x * 4) {
         const size_t i = g * 32 + p, ic = i < total ? i : total - 1;
         const int y = (int)(ic / Wp), x = (int)(ic - (size_t)y * Wp);
-        float v[16];
-        v[15] = 0.f;
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-            const int yy = y + dy[t], xx = x + dx[t];
-            const bool ok = t < ntap && yy >= 0 && yy < Hp && xx >= 0 && xx < Wp;  // the conv's zero padding applies to the PADDED frame
-            int sy = (ok ? yy : 0) - pt, sx = (ok ? xx : 0) - pl;                  // reflect (no edge repeat) back into the frame
-            sy = sy < 0 ? -sy : (sy >= H ? 2 * (H - 1) - sy : sy);
-            sx = sx < 0 ? -sx : (sx >= W ? 2 * (W - 1) - sx : sx);
-            const uint8_t* q = frame + ((size_t)sy * W + sx) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[3 * t + c] = ok ? (float)q[c] * inv255 : 0.f;
-        }
-        const half8_t b0 = __builtin_bit_cast(half8_t, uint4{pack_f16(v[0], v[1]), pack_f16(v[2], v[3]), pack_f16(v[4], v[5]), pack_f16(v[6], v[7])});
-        const half8_t b1 = __builtin_bit_cast(half8_t, uint4{pack_f16(v[8], v[9]), pack_f16(v[10], v[11]), pack_f16(v[12], v[13]), pack_f16(v[14], v[15])});
-        float16_t d;
-#pragma unroll
-        for (int vv = 0; vv < 16; ++vv) d[vv] = 0.f;
-        d = mfma16(af[0], b0, d);
-        d = mfma16(af[1], b1, d);
+        unsigned raw[5];
+        conv_in_fetch(cf, y, x, h, raw);
+        uint4 o[2];
+        conv_in_mfma(raw, a0, a1, o);  // the evaluation k_mst_conv3x3_lds<CINR / CINX> runs in place of reading `out`
         if (i < total) {
-            unsigned o[8];
-#pragma unroll
-            for (int vv = 0; vv < 8; ++vv) o[vv] = pack_f16(d[2 * vv], d[2 * vv + 1]);
-            reinterpret_cast<uint4*>(out + i * 32 + 16 * h)[0] = uint4{o[0], o[1], o[2], o[3]};
-            reinterpret_cast<uint4*>(out + i * 32 + 16 * h)[1] = uint4{o[4], o[5], o[6], o[7]};
+            reinterpret_cast<uint4*>(out + i * 32 + 16 * h)[0] = o[0];
+            reinterpret_cast<uint4*>(out + i * 32 + 16 * h)[1] = o[1];
         }
     }
 }
@@ -1836,6 +1962,96 @@ extern "C" int avx_mst_conv_in_u8(avx_ctx* ctx, const uint8_t* frame_hwc, int H,
     }
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
+}
+
+// ---- the three consumers of conv_in's output, taking the uint8 frame in its place (k_mst_conv3x3_lds<CINR / CINX>): conv_in's tensor is never stored ----
+// The frame is validated as avx_mst_conv_in_u8 validates it; the conv runs on the padded frame, (H + pad_top + pad_bottom) x (W + pad_left + pad_right), one frame per call.
+static int conv_in_frame_check(avx_ctx* ctx, const char* fn, const uint8_t* frame_hwc, int H, int W, int pad_top, int pad_bottom, int pad_left, int pad_right, const float* w_27x32_dev,
+                               ConvInFrame* cf) {
+    AVX_REQUIRE(ctx, frame_hwc && w_27x32_dev && H > 1 && W > 1, "%s: NULL pointer or a frame too small to reflect", fn);
+    AVX_REQUIRE(ctx, pad_top >= 0 && pad_bottom >= 0 && pad_left >= 0 && pad_right >= 0 && pad_top < H && pad_bottom < H && pad_left < W && pad_right < W,
+                "%s: reflect padding must be smaller than the frame", fn);
+    AVX_REQUIRE(ctx, (long)(H + pad_top + pad_bottom) * (W + pad_left + pad_right) * 3 < (1l << 31), "%s: frame larger than 2 GiB", fn);
+    *cf = ConvInFrame{frame_hwc, H, W, pad_top, pad_left, H + pad_top + pad_bottom, W + pad_left + pad_right};
+    return AVX_OK;
+}
+
+// avx_mst_conv_in_u8 + avx_mst_conv3x3_lds(x, wpack16, add = conv_in's output, out): x / out [Hp][Wp][32]
+extern "C" int avx_mst_conv3x3_lds_cin(avx_ctx* ctx, const void* x, const void* wpack16, const uint8_t* frame_hwc, int H, int W, int pad_top, int pad_bottom, int pad_left,
+                                       int pad_right, const float* w_27x32_dev, void* out, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, x && wpack16 && out, "avx_mst_conv3x3_lds_cin: NULL pointer");
+    ConvInFrame cf;
+    int rc = conv_in_frame_check(ctx, "avx_mst_conv3x3_lds_cin", frame_hwc, H, W, pad_top, pad_bottom, pad_left, pad_right, w_27x32_dev, &cf);
+    if (rc) return rc;
+    AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)wpack16 | (uintptr_t)out)) & 15u) == 0, "avx_mst_conv3x3_lds_cin: pointers must be 16-byte aligned");
+    AVX_REQUIRE(ctx, x != out, "avx_mst_conv3x3_lds_cin: in-place convolution is not possible");
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    const long total = (long)((cf.Hp + TS - 1) / TS) * ((cf.Wp + TS - 1) / TS);
+    const long cap = (long)ctx->num_cus * 3;
+    hipLaunchKernelGGL((k_mst_conv3x3_lds<6, false, false, true>), dim3((unsigned)(total < cap ? total : cap)), dim3(kFT), 0, s, (const __half*)x, (const uint4*)wpack16, (const __half*)nullptr,
+                       (__half*)out, 1, cf.Hp, cf.Wp, (const uint4*)nullptr, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (SpecStat3*)nullptr, 0, 0, 0, 0, mst_tile_order(), cf,
+                       w_27x32_dev);
+    AVX_HIP(ctx, hipGetLastError());
+    return AVX_OK;
+}
+
+// avx_mst_conv_in_u8 + avx_mst_conv3x3_lds_spectral(x, wpack16, add = conv_in's output, ...): the same planes and partial records
+extern "C" int avx_mst_conv3x3_lds_spectral_cin(avx_ctx* ctx, const void* x, const void* wpack16, const uint8_t* frame_hwc, int H, int W, int pad_top, int pad_bottom, int pad_left,
+                                                int pad_right, const float* w_27x32_dev, const float* weights_host, int crop_t, int crop_l, int Hc, int Wc, float* planes_out,
+                                                void* partials_out, int* n_partials, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, x && wpack16 && weights_host && planes_out && partials_out && n_partials, "avx_mst_conv3x3_lds_spectral_cin: NULL pointer");
+    ConvInFrame cf;
+    int rc = conv_in_frame_check(ctx, "avx_mst_conv3x3_lds_spectral_cin", frame_hwc, H, W, pad_top, pad_bottom, pad_left, pad_right, w_27x32_dev, &cf);
+    if (rc) return rc;
+    AVX_REQUIRE(ctx, crop_t >= 0 && crop_l >= 0 && Hc > 0 && Wc > 0 && crop_t + Hc <= cf.Hp && crop_l + Wc <= cf.Wp, "avx_mst_conv3x3_lds_spectral_cin: the crop window must lie inside the padded frame");
+    AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)wpack16 | (uintptr_t)partials_out)) & 15u) == 0, "avx_mst_conv3x3_lds_spectral_cin: pointers must be 16-byte aligned");
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    avx_ws* ws = avx_workspace(ctx, s);
+    if (!ws) return AVX_ERR_NOMEM;
+    float wT[32 * 4];  // as avx_mst_conv3x3_lds_spectral
+    for (int b = 0; b < 32; ++b)
+        for (int k = 0; k < 4; ++k) wT[b * 4 + k] = k < 3 ? weights_host[(size_t)k * 32 + b] : 0.0f;
+    float* dwT = nullptr;
+    rc = avx_const_upload(ctx, ws, 2, wT, sizeof(wT), s, (void**)&dwT);
+    if (rc) return rc;
+    const long total = (long)((cf.Hp + TS - 1) / TS) * ((cf.Wp + TS - 1) / TS);
+    const long cap = (long)ctx->num_cus * 2;
+    const long blocks = total < cap ? total : cap;
+    *n_partials = (int)blocks;
+    hipLaunchKernelGGL((k_mst_conv3x3_lds<4, false, true, true>), dim3((unsigned)blocks), dim3(kFT), 0, s, (const __half*)x, (const uint4*)wpack16, (const __half*)nullptr, (__half*)nullptr, 1,
+                       cf.Hp, cf.Wp, (const uint4*)nullptr, (float*)nullptr, (const float*)dwT, planes_out, (SpecStat3*)partials_out, crop_t, crop_l, Hc, Wc, (int)AVX_TILE_ORDER_RASTER, cf,
+                       w_27x32_dev);
+    AVX_HIP(ctx, hipGetLastError());
+    return AVX_OK;
+}
+
+// avx_mst_conv_in_u8 + avx_mst_conv3x3_lds_gram(x = conv_in's output, wpack16, add = NULL, out, ...): out [Hp][Wp][32], the same Gram matrix and column norms
+extern "C" int avx_mst_conv3x3_lds_gram_cin(avx_ctx* ctx, const uint8_t* frame_hwc, int H, int W, int pad_top, int pad_bottom, int pad_left, int pad_right, const float* w_27x32_dev,
+                                            const void* wpack16, void* out, const void* wqk16, float* gram, float* nq, float* nk, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, wpack16 && out && wqk16 && gram && nq && nk, "avx_mst_conv3x3_lds_gram_cin: NULL pointer");
+    ConvInFrame cf;
+    int rc = conv_in_frame_check(ctx, "avx_mst_conv3x3_lds_gram_cin", frame_hwc, H, W, pad_top, pad_bottom, pad_left, pad_right, w_27x32_dev, &cf);
+    if (rc) return rc;
+    AVX_REQUIRE(ctx, ((((uintptr_t)wpack16 | (uintptr_t)out | (uintptr_t)wqk16)) & 15u) == 0, "avx_mst_conv3x3_lds_gram_cin: pointers must be 16-byte aligned");
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    avx_ws* ws = avx_workspace(ctx, s);
+    if (!ws) return AVX_ERR_NOMEM;
+    const long total = (long)((cf.Hp + TS - 1) / TS) * ((cf.Wp + TS - 1) / TS);
+    const long cap = (long)ctx->num_cus * 2;
+    const long blocks = total < cap ? total : cap;
+    rc = avx_ensure_scratch(ctx, ws, sizeof(float) * (size_t)blocks * 34 * 32);
+    if (rc) return rc;
+    float* partial = (float*)ws->d_scratch;
+    hipLaunchKernelGGL((k_mst_conv3x3_lds<4, true, false, false, true>), dim3((unsigned)blocks), dim3(kFT), 0, s, (const __half*)nullptr, (const uint4*)wpack16, (const __half*)nullptr, (__half*)out, 1,
+                       cf.Hp, cf.Wp, (const uint4*)wqk16, partial, (const float*)nullptr, (float*)nullptr, (SpecStat3*)nullptr, 0, 0, 0, 0, (int)AVX_TILE_ORDER_RASTER, cf, w_27x32_dev);
+    AVX_HIP(ctx, hipGetLastError());
+    return avx_mst_qkv_final_launch(ctx, partial, (int)blocks, 1, gram, nq, nk, s);
 }
 
 extern "C" int avx_mst_down4x4(avx_ctx* ctx, const void* x, const void* wpack16, void* out, int B, int H, int W, int C, void* stream) {

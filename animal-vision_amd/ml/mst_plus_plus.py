@@ -238,6 +238,7 @@ class _AvxOps:
         self.DW_SPARSE_FFN_C = (32, 64, 128)
         self.DW_SPARSE_TAIL_C = (32, 64)  # C = 128: 1.5 % slower (two octets per wave, fragments reloaded per octet)
         self._specfuse = os.environ.get("AVX_MST_NO_SPEC_FUSE", "") == ""  # A/B: the spectral integration as conv_out's epilogue (the cube is never written)
+        self._cinfuse = os.environ.get("AVX_MST_NO_CONV_IN_FUSE", "") == ""  # A/B: conv_in recomputed from the uint8 frame in its three consumers, its output never stored (round 7)
         self.FFN_FUSED_C = tuple(int(v) for v in os.environ.get("AVX_MST_FFN_FUSED_C", "32,64,128").split(",") if v)
         self._ctx = {}
 
@@ -429,6 +430,7 @@ class _AvxOps:
     def conv3x3_lds_spectral(self, x: torch.Tensor, wpack16: torch.Tensor, add: torch.Tensor, weights, crop):
         """conv3x3_lds with the spectral integration of its output as the epilogue (csrc/mst_fused.hip::k_mst_conv3x3_lds<., false, true>): the cube is never
         written.  x / add: (1, h, w, 32) float16; weights: (3, 32) float32 NumPy (illuminant folded in); crop = (top, left, H, W) of the unpadded frame.
+        add may also be (frame, pads, w_27x32), what conv_in_u8 takes: the residual is then conv_in of that uint8 frame, formed in the kernel (conv3x3_lds_spectral_cin).
         -> (planes (3, H, W) float32, partials (n, 3, 2) float64-sized records, n): what HoneybeeOp.run_device(catches=...) takes."""
         import ctypes
 
@@ -436,6 +438,8 @@ class _AvxOps:
 
         from .._lib import lib
 
+        if isinstance(add, tuple):  # the residual is conv_in of a uint8 frame, given as (frame, pads, w_27x32): formed in the kernel, never stored
+            return self.conv3x3_lds_spectral_cin(x, wpack16, add, weights, crop)
         b, h, w, c = x.shape
         assert b == 1 and c == 32 and x.is_contiguous() and (add is None or add.is_contiguous())
         t, l, H, W = crop
@@ -449,6 +453,64 @@ class _AvxOps:
         ctx._check(lib.avx_mst_conv3x3_lds_spectral(ctx._h, x.data_ptr(), wpack16.data_ptr(), add.data_ptr() if add is not None else None, h, w, c,
                                                     wh.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), t, l, H, W, planes.data_ptr(), partials.data_ptr(), ctypes.byref(n),
                                                     torch.cuda.current_stream(x.device).cuda_stream))
+        return planes, partials, int(n.value)
+
+    # ---- conv_in's three consumers on the uint8 frame itself (csrc/mst_fused.hip::k_mst_conv3x3_lds<CINR / CINX>) ----
+    # src = (frame (H, W, 3) uint8, pads (top, bottom, left, right), w_27x32): what conv_in_u8 takes.  Each equals conv_in_u8 followed by the method it is
+    # named after, bit for bit; conv_in's output is not written.
+    def conv3x3_lds_gram_cin(self, src, wpack16: torch.Tensor, wqk16: torch.Tensor):
+        """conv3x3_lds_gram(conv_in_u8(*src), wpack16, None, wqk16)."""
+        from .._lib import lib
+
+        frame, (t, b, l, r), w27 = src
+        H, W, _ = frame.shape
+        frame = frame.contiguous()
+        out = torch.empty((1, H + t + b, W + l + r, 32), dtype=torch.float16, device=frame.device)
+        g = torch.empty((1, 1, 32, 32), dtype=torch.float32, device=frame.device)
+        nq = torch.empty((1, 32), dtype=torch.float32, device=frame.device)
+        nk = torch.empty((1, 32), dtype=torch.float32, device=frame.device)
+        ctx = self.ctx(frame.device)
+        ctx._check(lib.avx_mst_conv3x3_lds_gram_cin(ctx._h, frame.data_ptr(), H, W, t, b, l, r, w27.data_ptr(), wpack16.data_ptr(), out.data_ptr(), wqk16.data_ptr(),
+                                                    g.data_ptr(), nq.data_ptr(), nk.data_ptr(), torch.cuda.current_stream(frame.device).cuda_stream))
+        return out, g, nq, nk
+
+    def conv3x3_lds_cin(self, x: torch.Tensor, wpack16: torch.Tensor, src) -> torch.Tensor:
+        """conv3x3_lds(x, wpack16, add=conv_in_u8(*src))."""
+        from .._lib import lib
+
+        frame, (t, b, l, r), w27 = src
+        H, W, _ = frame.shape
+        assert x.shape == (1, H + t + b, W + l + r, 32)
+        x, frame = x.contiguous(), frame.contiguous()
+        out = torch.empty_like(x)
+        ctx = self.ctx(x.device)
+        ctx._check(lib.avx_mst_conv3x3_lds_cin(ctx._h, x.data_ptr(), wpack16.data_ptr(), frame.data_ptr(), H, W, t, b, l, r, w27.data_ptr(), out.data_ptr(),
+                                               torch.cuda.current_stream(x.device).cuda_stream))
+        return out
+
+    def conv3x3_lds_spectral_cin(self, x: torch.Tensor, wpack16: torch.Tensor, src, weights, crop):
+        """conv3x3_lds_spectral(x, wpack16, conv_in_u8(*src), weights, crop)."""
+        import ctypes
+
+        import numpy as np
+
+        from .._lib import lib
+
+        frame, (t, b, l, r), w27 = src
+        H, W, _ = frame.shape
+        assert x.shape == (1, H + t + b, W + l + r, 32) and x.is_contiguous()
+        frame = frame.contiguous()
+        ct, cl, Hc, Wc = crop
+        ctx = self.ctx(x.device)
+        planes = torch.empty((3, Hc, Wc), dtype=torch.float32, device=x.device)
+        ncu = torch.cuda.get_device_properties(x.device).multi_processor_count
+        partials = torch.empty((ncu * 3, 3, 2), dtype=torch.float64, device=x.device)  # as conv3x3_lds_spectral
+        wh = np.ascontiguousarray(weights, dtype=np.float32)
+        assert wh.shape == (3, 32)
+        n = ctypes.c_int(0)
+        ctx._check(lib.avx_mst_conv3x3_lds_spectral_cin(ctx._h, x.data_ptr(), wpack16.data_ptr(), frame.data_ptr(), H, W, t, b, l, r, w27.data_ptr(),
+                                                        wh.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ct, cl, Hc, Wc, planes.data_ptr(), partials.data_ptr(), ctypes.byref(n),
+                                                        torch.cuda.current_stream(x.device).cuda_stream))
         return planes, partials, int(n.value)
 
     def conv3x3_lds(self, x: torch.Tensor, wpack16: torch.Tensor, add: torch.Tensor = None) -> torch.Tensor:
@@ -894,16 +956,18 @@ class MSTPlusPlus(torch.nn.Module):
         x = self._ms_msa(x, p + ".blocks.0.0", heads, pre)
         return self._ffn(x, p + ".blocks.0.1")
 
-    def _mst(self, x: torch.Tensor, p: str) -> torch.Tensor:
+    def _mst(self, x: torch.Tensor, p: str, src=None) -> torch.Tensor:
+        """One U-shaped stage.  src = (frame, pads, w_27x32) instead of x (None): the stage's input is conv_in of that uint8 frame, which the embedding conv and
+        the mapping conv's residual recompute themselves (can_fuse_conv_in_consumers)."""
         pre = None
         ekey, a0 = p + ".embedding.weight", f"{p}.encoder_layers.0.0.blocks.0.0"
-        if _AVX.fused_ok(x) and x.shape[-1] == 32 and _AVX._conv_lds and _AVX._convgram and _AVX._qkv16 and _AVX._tail and _AVX._tailx:
+        if src is not None or (_AVX.fused_ok(x) and x.shape[-1] == 32 and _AVX._conv_lds and _AVX._convgram and _AVX._qkv16 and _AVX._tail and _AVX._tailx):
             # the embedding conv hands the first block its Gram matrix and column norms: the block's own pass over the conv's output is not run
             wq = self._prep(ekey + ".frag9k16", lambda: torch.stack([pack_fragments16(self._w(ekey, (0, 1))[:, :, t // 3, t % 3].t().contiguous()) for t in range(9)]).contiguous())
             wqkv = self._prep(a0 + ".qkv", lambda: torch.cat([self._w(a0 + ".to_q.weight", (0, 1)), self._w(a0 + ".to_k.weight", (0, 1)),
                                                               self._w(a0 + ".to_v.weight", (0, 1))], 0).t().contiguous())
             wqk = self._prep(a0 + ".qkv.frag16", lambda: pack_qkv16(wqkv))  # tiles 0 (q) and 1 (k) are what the epilogue reads
-            fea, g, nq, nk = _AVX.conv3x3_lds_gram(x, wq, None, wqk)
+            fea, g, nq, nk = _AVX.conv3x3_lds_gram(x, wq, None, wqk) if src is None else _AVX.conv3x3_lds_gram_cin(src, wq, wqk)
             pre = (g, nq, nk)
         else:
             fea = self._conv3(x, ekey)
@@ -964,6 +1028,8 @@ class MSTPlusPlus(torch.nn.Module):
                 cat = torch.cat([up, skip], dim=-1)
                 fea = (cat.reshape(b, h * w, c2) @ wf).reshape(b, h, w, c2 // 2)
             fea = self._msab(fea, f"{p}.decoder_layers.{i}.2", heads)
+        if src is not None:
+            return _AVX.conv3x3_lds_cin(fea, self._frag9k16(p + ".mapping.weight"), src)
         return self._conv3(fea, p + ".mapping.weight", add=x)
 
     @torch.no_grad()
@@ -973,25 +1039,34 @@ class MSTPlusPlus(torch.nn.Module):
         spectral = (3, 32) float32 weights: the cube is not returned (nor written) but integrated in conv_out's epilogue ->
         (planes (3, H, W) float32 of the UNPADDED frame, partials, n_partials) (see _AvxOps.conv3x3_lds_spectral)."""
         w27 = self._prep("conv_in.w27x32", lambda: self._w("conv_in.weight", (0,)).permute(2, 3, 1, 0).reshape(27, PAD).float().contiguous())
-        x = _AVX.conv_in_u8(frame, pads, w27)
-        assert x.shape[1] % 8 == 0 and x.shape[2] % 8 == 0, "pad the frame to a multiple of 8 (predict_torch.py pads to 16)"
-        if spectral is None:
-            return self._body(x)
         H, W, _ = frame.shape
-        return self._body(x, spectral=(spectral, (pads[0], pads[2], H, W)))
+        assert (H + pads[0] + pads[1]) % 8 == 0 and (W + pads[2] + pads[3]) % 8 == 0, "pad the frame to a multiple of 8 (predict_torch.py pads to 16)"
+        spec = None if spectral is None else (spectral, (pads[0], pads[2], H, W))
+        if self.can_fuse_conv_in_consumers():  # conv_in's output is not materialised: body.0's embedding, body.0's mapping residual and conv_out's residual take the frame
+            return self._body(None, spectral=spec, src=(frame, tuple(pads), w27))
+        return self._body(_AVX.conv_in_u8(frame, pads, w27), spectral=spec)
+
+    def can_fuse_conv_in_consumers(self) -> bool:
+        return (self.can_fuse_conv_in() and self.stage >= 1 and _AVX._cinfuse and _AVX._conv_lds and _AVX._convgram and _AVX._qkv16 and _AVX._tail and _AVX._tailx)
 
     def can_fuse_spectral(self) -> bool:
         return self.can_fuse_conv_in() and _AVX._conv_lds and _AVX._specfuse
 
-    def _body(self, x: torch.Tensor, spectral=None):
+    def _frag9k16(self, key: str) -> torch.Tensor:
+        """A 31 -> 31 channel 3x3 conv's weight as the nine taps' K = 16 fragments (what the conv3x3_lds kernels take)."""
+        return self._prep(key + ".frag9k16", lambda: torch.stack([pack_fragments16(self._w(key, (0, 1))[:, :, t // 3, t % 3].t().contiguous()) for t in range(9)]).contiguous())
+
+    def _body(self, x: torch.Tensor, spectral=None, src=None):
+        """src (see _mst) in place of x: conv_in's output exists nowhere; the first stage and conv_out's residual form it from the frame."""
         hfe = x
         for s in range(self.stage):
-            hfe = self._mst(hfe, f"body.{s}")
+            hfe = self._mst(hfe, f"body.{s}", src if s == 0 else None)
+        key = "conv_out.weight"
         if spectral is not None:  # conv_out + x with the spectral integration as its epilogue
-            key = "conv_out.weight"
-            wq = self._prep(key + ".frag9k16", lambda: torch.stack([pack_fragments16(self._w(key, (0, 1))[:, :, t // 3, t % 3].t().contiguous()) for t in range(9)]).contiguous())
-            return _AVX.conv3x3_lds_spectral(hfe.contiguous(), wq, x.contiguous(), spectral[0], spectral[1])
-        return self._conv3(hfe, "conv_out.weight", add=x)
+            return _AVX.conv3x3_lds_spectral(hfe.contiguous(), self._frag9k16(key), src if src is not None else x.contiguous(), spectral[0], spectral[1])
+        if src is not None:
+            return _AVX.conv3x3_lds_cin(hfe, self._frag9k16(key), src)
+        return self._conv3(hfe, key, add=x)
 
     def can_fuse_conv_in(self) -> bool:
         ref = self._p("conv_in.weight")
@@ -1055,4 +1130,8 @@ def hbm_bytes_per_px(stage: int = 3) -> float:
     # uint8 frame -> conv_in output (one kernel, else float32 NCHW + conv); conv_out + x (with the spectral integration as its epilogue the cube is
     # not written: 12 bytes of catch planes per pixel instead of 64)
     head = ((3 + t32) if _AVX._conv_in else (3 + 12) + (12 + t32)) + ((2 * t32 + 12) if (_AVX._specfuse and _AVX._conv_lds and _AVX._conv_in) else 3 * t32)
+    if stage >= 1 and _AVX._cinfuse and _AVX._conv_in and _AVX._conv_lds and _AVX._convgram and _AVX._qkv16 and _AVX._tail and _AVX._tailx:
+        # conv_in's output is never stored (MSTPlusPlus.can_fuse_conv_in_consumers): its write and its three reads go, and conv_in's own 3-byte read of the frame;
+        # the first embedding, the first mapping conv and conv_out read the 3-byte frame instead
+        head += 3 * 3 - (4 * t32 + 3)
     return stage * (per_stage + convs) + head

@@ -651,6 +651,19 @@ int avx_mst_conv3x3_lds(avx_ctx* ctx, const void* x, const void* wpack16, const 
  * tiles of pack_qkv16) as its epilogue: the output is not read again for it.  One frame (the Gram matrix is per frame). */
 int avx_mst_conv3x3_lds_gram(avx_ctx* ctx, const void* x, const void* wpack16, const void* add, void* out, int H, int W, int C, const void* wqk16, float* gram,
                              float* nq, float* nk, void* stream);
+/* The three consumers of conv_in's output taking the uint8 frame in its place: each equals avx_mst_conv_in_u8 followed by the entry point it is named after, bit for
+ * bit, and conv_in's tensor is neither written nor read.  The frame, its pads and the 27 x 32 table are avx_mst_conv_in_u8's and are validated as there; x / out are
+ * (H + pad_top + pad_bottom) x (W + pad_left + pad_right) x 32 float16, one frame per call.
+ *   _cin           out = conv3x3(x) + conv_in(frame)                       (MST.mapping(fea) + x of the first stage)
+ *   _spectral_cin  spectral integration of conv3x3(x) + conv_in(frame)     (conv_out + x; the crop window is given on the padded frame)
+ *   _gram_cin      out = conv3x3(conv_in(frame)) and its Gram pass         (the first stage's embedding) */
+int avx_mst_conv3x3_lds_cin(avx_ctx* ctx, const void* x, const void* wpack16, const uint8_t* frame_hwc, int H, int W, int pad_top, int pad_bottom, int pad_left, int pad_right,
+                            const float* w_27x32_dev, void* out, void* stream);
+int avx_mst_conv3x3_lds_spectral_cin(avx_ctx* ctx, const void* x, const void* wpack16, const uint8_t* frame_hwc, int H, int W, int pad_top, int pad_bottom, int pad_left,
+                                     int pad_right, const float* w_27x32_dev, const float* weights_host, int crop_t, int crop_l, int Hc, int Wc, float* planes_out,
+                                     void* partials_out, int* n_partials, void* stream);
+int avx_mst_conv3x3_lds_gram_cin(avx_ctx* ctx, const uint8_t* frame_hwc, int H, int W, int pad_top, int pad_bottom, int pad_left, int pad_right, const float* w_27x32_dev,
+                                 const void* wpack16, void* out, const void* wqk16, float* gram, float* nq, float* nk, void* stream);
 /* The same for the decoder's step back to full resolution: avx_mst_convt2x2_fuse at C = 64 with the following block's Gram pass as its epilogue. */
 int avx_mst_convt2x2_fuse_gram(avx_ctx* ctx, const void* x, const void* wpack, const float* bias, const void* skip, const void* wskip, void* out, int H, int W, int C,
                                const void* wqk16, float* gram, float* nq, float* nk, void* stream);

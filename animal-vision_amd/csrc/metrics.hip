@@ -1,45 +1,21 @@
 // csrc/metrics.hip -- frame comparison on the device: per frame and channel the exact histogram of absolute code
-// differences of two uint8 RGB batches, and the mean SSIM (Wang et al. 2004: 11 x 11 Gaussian window, sigma 1.5, valid positions).
+// differences of two uint8 RGB batches, and the mean SSIM (ssim_window.h: the tile scheme, its passes and its sums).
 //
 // k_metrics_tile: one workgroup per (32 x 32 tile of window positions, frame).  The 42 x 42 patch of both frames goes into LDS once,
 // as bytes and for the three channels together (a patch row is 126 contiguous bytes of the interleaved frame); the histogram of the
-// samples the tile owns is counted on the way.  Per channel the row pass writes the five moment planes a, b, a^2, b^2, ab (42 x 32
-// floats each) into LDS and the column pass keeps its 4 x 5 sums in registers; the samples are centred by 128 before they are squared,
-// so the float32 moments keep their digits where variance and covariance need them.  The SSIM of a position is formed in float32
-// (the products' rounding errors recovered with fma), the positions are summed in float64: a workgroup reduces its own in a fixed order
-// to one double per channel, and k_metrics_final sums the tiles of a (frame, channel) in a fixed order: no floating-point atomics, so
-// a frame's record does not depend on the batch it was in.
+// samples the tile owns is counted on the way.  The passes then run per channel, in float32: the samples are centred by 128 before
+// they are squared, so the moments keep their digits where variance and covariance need them, and the SSIM of a position is formed
+// in float32 with the products' rounding errors recovered with fma.  k_metrics_final sums the tiles of a (frame, channel).
 // k_metrics_hist is the histogram alone (with_ssim == 0, or a frame with no window position).
 // WITH_CS (avx_metrics_scale0_launch with a record of ms_ssim.hip) is the same tile code that also sums the contrast-
 // structure term cs = (2 s_ab + C2) / (s_a^2 + s_b^2 + C2) of every position: scale 0 of MS-SSIM.  The SSIM sums are formed by the
 // same operations in the same order in both instantiations (nothing is contracted: -ffp-contract=off), so they are bit-identical.
-#include "avx_internal.h"
-
-#include <cmath>
+#include "ssim_window.h"
 
 namespace {
 
-constexpr int kT = 32;                 // tile: kT x kT window positions
-constexpr int kK = 11;                 // window
-constexpr int kP = kT + kK - 1;        // patch side: 42
 constexpr int kRaw = kP * 3 + 6;       // bytes of a patch row in LDS (132: rows land one bank apart)
-constexpr int kThreads = 256;
 constexpr int kBins = 3 * 256;
-
-struct Taps { float w[kK]; };
-
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
-__device__ __forceinline__ void hist_flush(const unsigned* hist, avx_frame_metrics* rec, int tid) {
-    unsigned* dst = &rec->abs_hist[0][0];
-    for (int i = tid; i < kBins; i += kThreads) {
-        const unsigned v = hist[i];
-        if (v) atomicAdd(dst + i, v);
-    }
-}
 
 // one sample pair into the workgroup's histogram; zeros, by far the commonest difference of two renderings of one clip, are
 // counted in a register
@@ -49,11 +25,10 @@ __device__ __forceinline__ void hist_add(unsigned* hist, int c, int a, int b, un
     else atomicAdd(&hist[c * 256 + d], 1u);
 }
 
-// Row pass of NOUT adjacent positions of patch row `row`, from column x on, for channel C: the NOUT + 10 samples of both frames,
-// centred by 128, and their products stay in registers; the five moment sums go to hp[plane][row][x ...].  NOUT == 4 (x a multiple
-// of 4) reads the bytes as the 11 aligned words that hold them, NOUT == 2 byte by byte.
+// Row item of NOUT adjacent positions of patch row `row`, from column x on, for channel C: the NOUT + 10 samples of both frames,
+// centred by 128.  NOUT == 4 (x a multiple of 4) reads the bytes as the 11 aligned words that hold them, NOUT == 2 byte by byte.
 template <int NOUT, int C>
-__device__ __forceinline__ void row_item(const uint8_t* raw_a, const uint8_t* raw_b, float* hp, const Taps& tp, int row, int x) {
+__device__ __forceinline__ void row_item(const uint8_t* raw_a, const uint8_t* raw_b, float* hp, const Taps<float>& tp, int row, int x) {
     constexpr int NS = NOUT + kK - 1;
     float a[NS], b[NS];
     if (NOUT == 4) {
@@ -77,61 +52,23 @@ __device__ __forceinline__ void row_item(const uint8_t* raw_a, const uint8_t* ra
             b[j] = (float)rb[3 * j] - 128.0f;
         }
     }
-    float m[5][NOUT];
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-        m[0][o] = tp.w[0] * a[o];
-        m[1][o] = tp.w[0] * b[o];
-        m[2][o] = tp.w[0] * (a[o] * a[o]);
-        m[3][o] = tp.w[0] * (b[o] * b[o]);
-        m[4][o] = tp.w[0] * (a[o] * b[o]);
-#pragma unroll
-        for (int k = 1; k < kK; ++k) {
-            const float u = a[o + k], v = b[o + k];
-            m[0][o] = fmaf(tp.w[k], u, m[0][o]);
-            m[1][o] = fmaf(tp.w[k], v, m[1][o]);
-            m[2][o] = fmaf(tp.w[k], u * u, m[2][o]);
-            m[3][o] = fmaf(tp.w[k], v * v, m[3][o]);
-            m[4][o] = fmaf(tp.w[k], u * v, m[4][o]);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < 5; ++p) {
-        float* dst = hp + (p * kP + row) * kT + x;
-        if (NOUT == 4) *reinterpret_cast<float4*>(dst) = make_float4(m[p][0], m[p][1], m[p][2], m[p][3]);
-        else *reinterpret_cast<float2*>(dst) = make_float2(m[p][0], m[p][1]);
-    }
+    row_moments<float, NOUT>(a, b, tp, hp, row, x);
 }
 
 // One channel of a tile: row pass into hp, column pass in registers, the SSIM of the thread's 4 positions, the workgroup's sum.
 template <bool EDGE, int C, bool WITH_CS>
-__device__ __forceinline__ void channel_pass(int H, int W, int x0, int y0, const Taps& tp, const uint8_t* raw_a, const uint8_t* raw_b, float* hp,
+__device__ __forceinline__ void channel_pass(int H, int W, int x0, int y0, const Taps<float>& tp, const uint8_t* raw_a, const uint8_t* raw_b, float* hp,
                                              double* red, double* part, size_t cs_offset) {
     const int tid = threadIdx.x;
-    // ---- row pass: the first kT patch rows as 256 items of 4 positions, the other 10 as 160 items of 2: every wave stays busy ----
-    row_item<4, C>(raw_a, raw_b, hp, tp, tid >> 3, (tid & 7) * 4);
-    if (tid < (kP - kT) * (kT / 2)) row_item<2, C>(raw_a, raw_b, hp, tp, kT + (tid >> 4), (tid & 15) * 2);
+    row_pass([&](auto n, int row, int x) { row_item<decltype(n)::value, C>(raw_a, raw_b, hp, tp, row, x); });
     __syncthreads();
-    // ---- column pass: 4 positions of one column per thread ----
     const int col = tid & (kT - 1), seg = tid >> 5;
     float acc[5][4];
-#pragma unroll
-    for (int p = 0; p < 5; ++p) {
-        float v[14];
-#pragma unroll
-        for (int k = 0; k < 14; ++k) v[k] = hp[(p * kP + seg * 4 + k) * kT + col];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            float s = tp.w[0] * v[o];
-#pragma unroll
-            for (int k = 1; k < kK; ++k) s = fmaf(tp.w[k], v[o + k], s);
-            acc[p][o] = s;
-        }
-    }
+    column_pass(hp, tp, col, seg, acc);
     // ---- SSIM.  E[x^2] - mu^2 loses nothing to float32: the rounding error of the product is recovered with an fma and taken
     // off the difference, so variance and covariance carry a relative error of 2^-23, not one of the size of mu^2. ----
     const float C1 = 6.5025f, C2 = 58.5225f;  // (0.01 * 255)^2, (0.03 * 255)^2
-    double sum = 0.0, sum_cs = 0.0;
+    double sum[WITH_CS ? 2 : 1] = {};         // SSIM and, WITH_CS, cs
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         if (EDGE && !(x0 + col < W - (kK - 1) && y0 + seg * 4 + o < H - (kK - 1))) continue;
@@ -143,26 +80,19 @@ __device__ __forceinline__ void channel_pass(int H, int W, int x0, int y0, const
         const float ua = ma + 128.0f, ub = mb + 128.0f;
         const float num = (2.0f * (ua * ub) + C1) * (2.0f * cab + C2);
         const float den = ((ua * ua + ub * ub) + C1) * ((va + vb) + C2);
-        sum += (double)(num / den);
-        if (WITH_CS) sum_cs += (double)((2.0f * cab + C2) / ((va + vb) + C2));
+        sum[0] += (double)(num / den);
+        if constexpr (WITH_CS) sum[1] += (double)((2.0f * cab + C2) / ((va + vb) + C2));
     }
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
-    if (WITH_CS)
-        for (int o = 32; o > 0; o >>= 1) sum_cs += __shfl_down(sum_cs, o);
-    if ((tid & 63) == 0) {
-        red[tid >> 6] = sum;
-        if (WITH_CS) red[kThreads / 64 + (tid >> 6)] = sum_cs;
-    }
-    __syncthreads();  // also: every column pass has read hp before the next channel's row pass writes it
+    workgroup_sum(sum, red);  // its barrier: every column pass has read hp before the next channel's row pass writes it
     if (tid == 0) {
-        *part = ((red[0] + red[1]) + red[2]) + red[3];
-        if (WITH_CS) part[cs_offset] = ((red[4] + red[5]) + red[6]) + red[7];
+        *part = sum[0];
+        if constexpr (WITH_CS) part[cs_offset] = sum[1];
     }
 }
 
 template <bool EDGE, bool WITH_CS>
 __device__ __forceinline__ void tile_body(const uint8_t* __restrict__ fa, const uint8_t* __restrict__ fb, int H, int W, int x0, int y0,
-                                          int own_w, int own_h, const Taps& tp, uint8_t* raw_a, uint8_t* raw_b, float* hp, unsigned* hist,
+                                          int own_w, int own_h, const Taps<float>& tp, uint8_t* raw_a, uint8_t* raw_b, float* hp, unsigned* hist,
                                           double* red, double* part, size_t part_stride) {
     const int tid = threadIdx.x;
     // ---- patch -> LDS (bytes, three channels), histogram of the owned samples ----
@@ -201,7 +131,7 @@ __device__ __forceinline__ void tile_body(const uint8_t* __restrict__ fa, const 
 
 // partials: [frame][row][tile] doubles, rows 0..2 the SSIM sums of the channels and, WITH_CS, rows 3..5 their cs sums
 template <bool WITH_CS>
-__global__ __launch_bounds__(kThreads) void k_metrics_tile(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int H, int W, Taps tp,
+__global__ __launch_bounds__(kThreads) void k_metrics_tile(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int H, int W, Taps<float> tp,
                                                            double* __restrict__ partials, avx_frame_metrics* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) uint8_t raw_a[kP * kRaw];
     __shared__ __attribute__((aligned(16))) uint8_t raw_b[kP * kRaw];
@@ -221,27 +151,19 @@ __global__ __launch_bounds__(kThreads) void k_metrics_tile(const uint8_t* __rest
         tile_body<false, WITH_CS>(a + fo, b + fo, H, W, x0, y0, own_w, own_h, tp, raw_a, raw_b, hp, hist, red, part, ntiles);
     else
         tile_body<true, WITH_CS>(a + fo, b + fo, H, W, x0, y0, own_w, own_h, tp, raw_a, raw_b, hp, hist, red, part, ntiles);
-    hist_flush(hist, out + f, tid);  // the last barrier of tile_body is behind every histogram update
+    hist_flush(hist, kBins, &out[f].abs_hist[0][0]);  // the last barrier of tile_body is behind every histogram update
 }
 
-// sum of the tile partials of one (row of partials, frame) in a fixed order: thread t adds tiles t, t + 256, ..., then a fixed tree.
+// sum of the tile partials of one (row of partials, frame).
 // grid (3, frames): the SSIM of the channels; grid (6, frames) with ms: rows 3..5 are the cs sums, and scale 0 of ms[f] is filled.
 __global__ __launch_bounds__(kThreads) void k_metrics_final(const double* __restrict__ partials, size_t ntiles, double count,
                                                             avx_frame_metrics* __restrict__ out, avx_ms_ssim_rec* __restrict__ ms) {
     __shared__ double red[kThreads];
     const int tid = threadIdx.x, f = blockIdx.y;
     const int c = blockIdx.x % 3;
-    const double* p = partials + ((size_t)f * gridDim.x + blockIdx.x) * ntiles;
-    double s = 0.0;
-    for (size_t t = tid; t < ntiles; t += kThreads) s += p[t];
-    red[tid] = s;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
+    const double s = tile_partials_sum(partials + ((size_t)f * gridDim.x + blockIdx.x) * ntiles, ntiles, red);
     if (tid == 0) {
-        const double v = red[0] / count;
+        const double v = s / count;
         if (blockIdx.x < 3) {
             out[f].ssim[c] = v;
             if (ms) ms[f].ssim[c][0] = v;
@@ -293,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void k_metrics_hist(const uint8_t* __rest
         if (z2) atomicAdd(&hist[512], z2);
     }
     __syncthreads();
-    hist_flush(hist, out + f, tid);
+    hist_flush(hist, kBins, &out[f].abs_hist[0][0]);
     if (blockIdx.x == 0 && tid < 3) out[f].ssim[tid] = __longlong_as_double(0x7ff8000000000000LL);
 }
 
@@ -303,13 +225,13 @@ __global__ __launch_bounds__(kThreads) void k_metrics_hist(const uint8_t* __rest
 // by the caller; partials: (ms ? 6 : 3) * tiles * n_frames doubles
 int avx_metrics_scale0_launch(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, double* partials,
                               avx_frame_metrics* out_dev, avx_ms_ssim_rec* ms, hipStream_t s) {
-    const unsigned ntx = (unsigned)((W - (kK - 1) + kT - 1) / kT), nty = (unsigned)((H - (kK - 1) + kT - 1) / kT);
+    const unsigned ntx = ssim_tiles(W), nty = ssim_tiles(H);
     const size_t ntiles = (size_t)ntx * nty;
     AVX_HIP(ctx, hipMemsetAsync(out_dev, 0, sizeof(avx_frame_metrics) * (size_t)n_frames, s));
-    double g[kK], sum = 0.0;
-    for (int k = 0; k < kK; ++k) sum += g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-    Taps tp;
-    for (int k = 0; k < kK; ++k) tp.w[k] = (float)(g[k] / sum);
+    double w[kK];
+    ssim_window_taps(w);
+    Taps<float> tp;
+    for (int k = 0; k < kK; ++k) tp.w[k] = (float)w[k];
     if (ms)
         hipLaunchKernelGGL(k_metrics_tile<true>, dim3(ntx, nty, n_frames), dim3(kThreads), 0, s, a_hwc, b_hwc, H, W, tp, partials, out_dev);
     else
@@ -323,7 +245,7 @@ int avx_metrics_scale0_launch(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t*
 
 // tiles of a frame with window positions: what a row of partials holds
 size_t avx_metrics_scale0_tiles(int H, int W) {
-    return (size_t)((W - (kK - 1) + kT - 1) / kT) * (size_t)((H - (kK - 1) + kT - 1) / kT);
+    return (size_t)ssim_tiles(W) * ssim_tiles(H);
 }
 
 extern "C" int avx_frame_metrics_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int with_ssim,
@@ -336,7 +258,7 @@ extern "C" int avx_frame_metrics_u8(avx_ctx* ctx, const uint8_t* a_hwc, const ui
                 H, W);
     AVX_REQUIRE(ctx, ((uintptr_t)out_dev & 7) == 0, "avx_frame_metrics_u8: out_dev must be 8-byte aligned");
     const bool ssim = with_ssim != 0 && H >= kK && W >= kK;
-    const unsigned ntx = ssim ? (unsigned)((W - (kK - 1) + kT - 1) / kT) : 0, nty = ssim ? (unsigned)((H - (kK - 1) + kT - 1) / kT) : 0;
+    const unsigned ntx = ssim ? ssim_tiles(W) : 0, nty = ssim ? ssim_tiles(H) : 0;
     AVX_REQUIRE(ctx, nty <= 65535u, "avx_frame_metrics_u8: %d rows are more than the SSIM kernel's grid takes (%d)", H, 65535 * kT + kK - 1);
     AVX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = avx_pick_stream(ctx, stream);

@@ -10,23 +10,15 @@
 // the sum of an origin-aligned 2^j x 2^j block divided by 4^j: the workgroup emits the 16 x 16, 8 x 8, 4 x 4 and 2 x 2 block sums of
 // its tile for the three channels of both frames, as exact integers (<= 255 * 256) in uint16 planes, without touching a neighbour.
 // k_ms_levels: one workgroup per (32 x 32 tile of window positions of one of the scales 1..4, channel, frame), the tiles of the four
-// scales numbered through in one grid.  It is plane_metrics.hip's 10-bit tile code without the histogram: the 42 x 42 patch of both
-// planes into LDS as the 16-bit sums, the row pass writes the five moment planes, the column pass keeps 4 x 5 sums in registers.
-// A sample is its sum times 4^-j, centred by 128: up to 8 fractional bits, so samples and products are exact in float64 and the
-// moments, the window sums and the quotients are float64.  Positions are summed in float64 in a fixed order: two doubles (cs, l * cs)
-// per workgroup, then k_ms_final over the tiles of a (scale, channel, frame); no floating-point atomics, so a frame's record does not
-// depend on the batch it was in.
-#include "avx_internal.h"
-
-#include <cmath>
+// scales numbered through in one grid, on ssim_window.h's scheme in float64, without a histogram: the 42 x 42 patch of both planes
+// goes into LDS as the 16-bit sums.  A sample is its sum times 4^-j, centred by 128: up to 8 fractional bits, so samples and
+// products are exact in float64 and the moments, the window sums and the quotients are float64.  A workgroup sums two terms (cs,
+// l * cs); k_ms_final sums the tiles of a (scale, channel, frame).
+#include "ssim_window.h"
 
 namespace {
 
-constexpr int kT = 32;                 // tile: kT x kT window positions
-constexpr int kK = 11;                 // window
-constexpr int kP = kT + kK - 1;        // patch side: 42
 constexpr int kRawS = kP + 2;          // samples of a patch row in LDS (44: every row starts on an 8-byte boundary)
-constexpr int kThreads = 256;
 constexpr int kMinSide = 176;          // scale 4 is floor(H / 16) x floor(W / 16) and needs one window position
 constexpr int kS = 32;                 // pyramid: source tile side
 constexpr int kSrcRow = kS * 3 + 4;    // bytes of a source tile row in LDS (100: a multiple of 4, rows land one bank apart)
@@ -121,12 +113,10 @@ __global__ __launch_bounds__(kThreads) void k_ms_pyramid(const uint8_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------------------------ scales 1..4
-struct Taps { double w[kK]; };
-
-// Row pass of NOUT adjacent positions of patch row `row`, from column x on (x even): the NOUT + 10 samples of both planes as the
-// aligned words that hold them, scaled, centred by 128, and their products stay in registers; the five moment sums go to hp.
+// Row item of NOUT adjacent positions of patch row `row`, from column x on (x even): the NOUT + 10 samples of both planes as the
+// aligned words that hold them, scaled, centred by 128
 template <int NOUT>
-__device__ __forceinline__ void row_item(const uint16_t* raw_a, const uint16_t* raw_b, double* hp, const Taps& tp, double inv, int row, int x) {
+__device__ __forceinline__ void row_item(const uint16_t* raw_a, const uint16_t* raw_b, double* hp, const Taps<double>& tp, double inv, int row, int x) {
     constexpr int NS = NOUT + kK - 1;  // 14 or 12 samples: 7 or 6 aligned words
     const uint32_t* wa = reinterpret_cast<const uint32_t*>(raw_a + row * kRawS + x);
     const uint32_t* wb = reinterpret_cast<const uint32_t*>(raw_b + row * kRawS + x);
@@ -137,36 +127,13 @@ __device__ __forceinline__ void row_item(const uint16_t* raw_a, const uint16_t* 
         a[2 * i] = (double)(va & 0xffffu) * inv - 128.0, a[2 * i + 1] = (double)(va >> 16) * inv - 128.0;
         b[2 * i] = (double)(vb & 0xffffu) * inv - 128.0, b[2 * i + 1] = (double)(vb >> 16) * inv - 128.0;
     }
-    double m[5][NOUT];
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-        m[0][o] = tp.w[0] * a[o];
-        m[1][o] = tp.w[0] * b[o];
-        m[2][o] = tp.w[0] * (a[o] * a[o]);
-        m[3][o] = tp.w[0] * (b[o] * b[o]);
-        m[4][o] = tp.w[0] * (a[o] * b[o]);
-#pragma unroll
-        for (int k = 1; k < kK; ++k) {
-            const double u = a[o + k], v = b[o + k];
-            m[0][o] = __builtin_fma(tp.w[k], u, m[0][o]);
-            m[1][o] = __builtin_fma(tp.w[k], v, m[1][o]);
-            m[2][o] = __builtin_fma(tp.w[k], u * u, m[2][o]);
-            m[3][o] = __builtin_fma(tp.w[k], v * v, m[3][o]);
-            m[4][o] = __builtin_fma(tp.w[k], u * v, m[4][o]);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < 5; ++p) {
-        double* dst = hp + (p * kP + row) * kT + x;
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) dst[o] = m[p][o];
-    }
+    row_moments<double, NOUT>(a, b, tp, hp, row, x);
 }
 
 // the tile's sums of cs and of l * cs into out[0], out[1] (thread 0)
 template <bool EDGE>
 __device__ __forceinline__ void level_tile(const uint16_t* __restrict__ pa, const uint16_t* __restrict__ pb, int H, int W, int x0, int y0, double inv,
-                                           const Taps& tp, uint16_t* raw_a, uint16_t* raw_b, double* hp, double* red, double* out, size_t out_stride) {
+                                           const Taps<double>& tp, uint16_t* raw_a, uint16_t* raw_b, double* hp, double* red, double* out, size_t out_stride) {
     const int tid = threadIdx.x;
     // ---- patch -> LDS; outside the plane: the centre (128 * 4^j <= 32768), never part of a valid window ----
     const uint16_t centre = (uint16_t)(128.0 / inv);
@@ -181,29 +148,14 @@ __device__ __forceinline__ void level_tile(const uint16_t* __restrict__ pa, cons
         raw_b[py * kRawS + px] = b;
     }
     __syncthreads();
-    // ---- row pass: the first kT patch rows as 256 items of 4 positions, the other 10 as 160 items of 2 ----
-    row_item<4>(raw_a, raw_b, hp, tp, inv, tid >> 3, (tid & 7) * 4);
-    if (tid < (kP - kT) * (kT / 2)) row_item<2>(raw_a, raw_b, hp, tp, inv, kT + (tid >> 4), (tid & 15) * 2);
+    row_pass([&](auto n, int row, int x) { row_item<decltype(n)::value>(raw_a, raw_b, hp, tp, inv, row, x); });
     __syncthreads();
-    // ---- column pass: 4 positions of one column per thread ----
     const int col = tid & (kT - 1), seg = tid >> 5;
     double acc[5][4];
-#pragma unroll
-    for (int p = 0; p < 5; ++p) {
-        double v[14];
-#pragma unroll
-        for (int k = 0; k < 14; ++k) v[k] = hp[(p * kP + seg * 4 + k) * kT + col];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            double s = tp.w[0] * v[o];
-#pragma unroll
-            for (int k = 1; k < kK; ++k) s = __builtin_fma(tp.w[k], v[o + k], s);
-            acc[p][o] = s;
-        }
-    }
+    column_pass(hp, tp, col, seg, acc);
     // ---- cs and l * cs.  E[x^2] - mu^2 in float64: its error is 2^-53 of mu^2 <= 2^14 against C2 = 58.5 ----
     const double C1 = (0.01 * 255.0) * (0.01 * 255.0), C2 = (0.03 * 255.0) * (0.03 * 255.0);
-    double sum_cs = 0.0, sum_ss = 0.0;
+    double sum[2] = {};  // cs, l * cs
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         if (EDGE && !(x0 + col < W - (kK - 1) && y0 + seg * 4 + o < H - (kK - 1))) continue;
@@ -212,15 +164,13 @@ __device__ __forceinline__ void level_tile(const uint16_t* __restrict__ pa, cons
         const double ua = ma + 128.0, ub = mb + 128.0;
         const double l = (2.0 * (ua * ub) + C1) / ((ua * ua + ub * ub) + C1);
         const double cs = (2.0 * cab + C2) / ((va + vb) + C2);
-        sum_cs += cs;
-        sum_ss += l * cs;
+        sum[0] += cs;
+        sum[1] += l * cs;
     }
-    for (int o = 32; o > 0; o >>= 1) sum_cs += __shfl_down(sum_cs, o), sum_ss += __shfl_down(sum_ss, o);
-    if ((tid & 63) == 0) red[tid >> 6] = sum_cs, red[4 + (tid >> 6)] = sum_ss;
-    __syncthreads();
+    workgroup_sum(sum, red);
     if (tid == 0) {
-        out[0] = ((red[0] + red[1]) + red[2]) + red[3];
-        out[out_stride] = ((red[4] + red[5]) + red[6]) + red[7];
+        out[0] = sum[0];
+        out[out_stride] = sum[1];
     }
 }
 
@@ -242,7 +192,7 @@ __global__ __launch_bounds__(kThreads) void k_ms_levels(const uint16_t* __restri
     const size_t plane = (size_t)H * W;
     const uint16_t* pa = pyr + lv.off[k] + (size_t)((f * 2 + 0) * 3 + c) * plane;
     const uint16_t* pb = pyr + lv.off[k] + (size_t)((f * 2 + 1) * 3 + c) * plane;
-    Taps taps;
+    Taps<double> taps;
 #pragma unroll
     for (int i = 0; i < kK; ++i) taps.w[i] = lv.taps[i];
     const size_t nt = lv.t0[4];
@@ -253,25 +203,16 @@ __global__ __launch_bounds__(kThreads) void k_ms_levels(const uint16_t* __restri
         level_tile<true>(pa, pb, H, W, x0, y0, lv.inv[k], taps, raw_a, raw_b, hp, red, out, nt);
 }
 
-// grid (4 scales, 3 channels, frames): the tile partials of a scale in a fixed order (thread t adds tiles t, t + 256, ..., then a
-// fixed tree), cs and l * cs side by side
+// grid (4 scales, 3 channels, frames): the sums of a scale's tile partials, cs and l * cs
 __global__ __launch_bounds__(kThreads) void k_ms_final(const double* __restrict__ partials, Levels lv, avx_ms_ssim_rec* __restrict__ ms) {
     __shared__ double red[2][kThreads];
     const int tid = threadIdx.x, k = blockIdx.x, c = blockIdx.y, f = blockIdx.z;
-    const size_t nt = lv.t0[4];
-    const double* pc = partials + ((size_t)(f * 3 + c) * 2) * nt;
-    const double* ps = pc + nt;
-    double s_cs = 0.0, s_ss = 0.0;
-    for (unsigned t = lv.t0[k] + tid; t < lv.t0[k + 1]; t += kThreads) s_cs += pc[t], s_ss += ps[t];
-    red[0][tid] = s_cs, red[1][tid] = s_ss;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if (tid < o) red[0][tid] += red[0][tid + o], red[1][tid] += red[1][tid + o];
-        __syncthreads();
-    }
+    const size_t nt = lv.t0[4], n = lv.t0[k + 1] - lv.t0[k];
+    const double* pc = partials + ((size_t)(f * 3 + c) * 2) * nt + lv.t0[k];
+    const double s_cs = tile_partials_sum(pc, n, red[0]), s_ss = tile_partials_sum(pc + nt, n, red[1]);
     if (tid == 0) {
-        ms[f].cs[c][k + 1] = red[0][0] / lv.count[k];
-        ms[f].ssim[c][k + 1] = red[1][0] / lv.count[k];
+        ms[f].cs[c][k + 1] = s_cs / lv.count[k];
+        ms[f].ssim[c][k + 1] = s_ss / lv.count[k];
     }
 }
 
@@ -291,18 +232,14 @@ extern "C" int avx_frame_metrics_ms_u8(avx_ctx* ctx, const uint8_t* a_hwc, const
     AVX_REQUIRE(ctx, (((uintptr_t)out_dev | (uintptr_t)ms_out_dev) & 7) == 0, "avx_frame_metrics_ms_u8: out_dev and ms_out_dev must be 8-byte aligned");
 
     Levels lv{};
-    {
-        double g[kK], sum = 0.0;
-        for (int k = 0; k < kK; ++k) sum += g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-        for (int k = 0; k < kK; ++k) lv.taps[k] = g[k] / sum;
-    }
+    ssim_window_taps(lv.taps);
     size_t pyr_elems = 0;
     for (int k = 0; k < 4; ++k) {
         lv.h[k] = H >> (k + 1), lv.w[k] = W >> (k + 1);
         lv.off[k] = pyr_elems;
         pyr_elems += (size_t)n_frames * 6 * (size_t)lv.h[k] * lv.w[k];
-        lv.ntx[k] = (unsigned)((lv.w[k] - (kK - 1) + kT - 1) / kT);
-        lv.t0[k + 1] = lv.t0[k] + lv.ntx[k] * (unsigned)((lv.h[k] - (kK - 1) + kT - 1) / kT);
+        lv.ntx[k] = ssim_tiles(lv.w[k]);
+        lv.t0[k + 1] = lv.t0[k] + lv.ntx[k] * ssim_tiles(lv.h[k]);
         lv.inv[k] = 1.0 / (double)(1 << (2 * (k + 1)));
         lv.count[k] = (double)(lv.h[k] - (kK - 1)) * (double)(lv.w[k] - (kK - 1));
     }

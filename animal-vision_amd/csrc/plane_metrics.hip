@@ -3,31 +3,20 @@
 // (Wang et al. 2004: 11 x 11 Gaussian window, sigma 1.5, valid positions, dynamic range 2^d - 1).  Nothing is converted: the samples
 // are read as the decoders read them (yuv_formats.h), every plane at its own size.
 //
-// k_plane_tile<T, SHA, SHB>: one workgroup per (32 x 32 tile of window positions, plane, frame), as k_metrics_tile: the 42 x 42 patch
-// of both planes goes into LDS once as 16-bit samples, the histogram of the samples the tile owns is counted on the way (zeros in a
-// register), the row pass writes the five moment planes a, b, a^2, b^2, ab into LDS and the column pass keeps its 4 x 5 sums in
-// registers.  The moment type M is float at 8 bits (samples centred by 128, the products' rounding errors recovered with fma: the
-// arithmetic of metrics.hip) and double at 10 bits: a fixed centre does not keep float32 within the bound there (flat 1023 against
-// flat 1022 is 3.3e-5 off), and samples and products below 2^20 are exact in double.  Positions are summed in float64 in a fixed order:
-// one double per workgroup, then k_plane_final over the tiles of a (frame, plane); no floating-point atomics, so a frame's record does
-// not depend on the batch it was in.
+// k_plane_tile<T, SHA, SHB>: one workgroup per (32 x 32 tile of window positions, plane, frame), on ssim_window.h's scheme: the
+// 42 x 42 patch of both planes goes into LDS once as 16-bit samples, the histogram of the samples the tile owns is counted on the
+// way (zeros in a register).  The moment type M is float at 8 bits (samples centred by 128, the products' rounding errors recovered
+// with fma: the arithmetic of metrics.hip) and double at 10 bits: a fixed centre does not keep float32 within the bound there (flat
+// 1023 against flat 1022 is 3.3e-5 off), and samples and products below 2^20 are exact in double.  k_plane_final sums the tiles of
+// a (frame, plane).
 // k_plane_hist<T, SHA, SHB>: the histogram alone (with_ssim == 0, or a plane with no window position): a plane is a flat run of
 // samples; 16-byte loads where both sides are contiguous and aligned.
+#include "ssim_window.h"
 #include "yuv_formats.h"
-
-#include <cmath>
-#include <type_traits>
 
 namespace {
 
-constexpr int kT = 32;                 // tile: kT x kT window positions
-constexpr int kK = 11;                 // window
-constexpr int kP = kT + kK - 1;        // patch side: 42
 constexpr int kRawS = kP + 2;          // samples of a patch row in LDS (44: every row starts on an 8-byte boundary)
-constexpr int kThreads = 256;
-
-template <typename M>
-struct Taps { M w[kK]; };
 
 // where plane p of one side lies in its frame: sample i of row y is at byte off + (y * w + i) * step * sizeof(T)
 struct Side { size_t frame_bytes; size_t off[3]; int step[3]; };
@@ -43,14 +32,6 @@ struct Run { size_t off_a, off_b, n; int step_a, step_b, row0, rows, vec; };
 struct HistRuns { size_t frame_bytes_a, frame_bytes_b; Run r[3]; };
 struct FinalPlanes { unsigned nt[3], nt_max; double count[3]; };
 
-__device__ __forceinline__ float fma_m(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fma_m(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
 template <typename T, int SH>
 __device__ __forceinline__ int load_sample(const uint8_t* p) {
     if constexpr (sizeof(T) == 1) return (int)*p;
@@ -64,6 +45,8 @@ __device__ __forceinline__ int diff_bin(int a, int b) {
     return d < BINS ? d : BINS - 1;
 }
 
+// Row item of NOUT adjacent positions of patch row `row`, from column x on (x even): the NOUT + 10 samples of both planes as the
+// aligned words that hold them, centred
 template <typename M, int CENTRE, int NOUT>
 __device__ __forceinline__ void row_item(const uint16_t* raw_a, const uint16_t* raw_b, M* hp, const Taps<M>& tp, int row, int x) {
     constexpr int NS = NOUT + kK - 1;  // 14 or 12 samples: 7 or 6 aligned words
@@ -76,30 +59,7 @@ __device__ __forceinline__ void row_item(const uint16_t* raw_a, const uint16_t* 
         a[2 * i] = (M)((int)(va & 0xffffu) - CENTRE), a[2 * i + 1] = (M)((int)(va >> 16) - CENTRE);
         b[2 * i] = (M)((int)(vb & 0xffffu) - CENTRE), b[2 * i + 1] = (M)((int)(vb >> 16) - CENTRE);
     }
-    M m[5][NOUT];
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-        m[0][o] = tp.w[0] * a[o];
-        m[1][o] = tp.w[0] * b[o];
-        m[2][o] = tp.w[0] * (a[o] * a[o]);
-        m[3][o] = tp.w[0] * (b[o] * b[o]);
-        m[4][o] = tp.w[0] * (a[o] * b[o]);
-#pragma unroll
-        for (int k = 1; k < kK; ++k) {
-            const M u = a[o + k], v = b[o + k];
-            m[0][o] = fma_m(tp.w[k], u, m[0][o]);
-            m[1][o] = fma_m(tp.w[k], v, m[1][o]);
-            m[2][o] = fma_m(tp.w[k], u * u, m[2][o]);
-            m[3][o] = fma_m(tp.w[k], v * v, m[3][o]);
-            m[4][o] = fma_m(tp.w[k], u * v, m[4][o]);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < 5; ++p) {
-        M* dst = hp + (p * kP + row) * kT + x;
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) dst[o] = m[p][o];
-    }
+    row_moments<M, NOUT>(a, b, tp, hp, row, x);
 }
 
 // The SSIM of one position from its five window means (of centred samples).  float: E[x^2] - mu^2 loses nothing, the rounding error
@@ -152,36 +112,19 @@ __device__ __forceinline__ double tile_body(const uint8_t* __restrict__ pa, cons
     if ((tid & 63) == 0 && zeros) atomicAdd(&hist[0], zeros);
     __syncthreads();
 
-    // ---- row pass: the first kT patch rows as 256 items of 4 positions, the other 10 as 160 items of 2 ----
-    row_item<M, CENTRE, 4>(raw_a, raw_b, hp, tp, tid >> 3, (tid & 7) * 4);
-    if (tid < (kP - kT) * (kT / 2)) row_item<M, CENTRE, 2>(raw_a, raw_b, hp, tp, kT + (tid >> 4), (tid & 15) * 2);
+    row_pass([&](auto n, int row, int x) { row_item<M, CENTRE, decltype(n)::value>(raw_a, raw_b, hp, tp, row, x); });
     __syncthreads();
-    // ---- column pass: 4 positions of one column per thread ----
     const int col = tid & (kT - 1), seg = tid >> 5;
     M acc[5][4];
-#pragma unroll
-    for (int p = 0; p < 5; ++p) {
-        M v[14];
-#pragma unroll
-        for (int k = 0; k < 14; ++k) v[k] = hp[(p * kP + seg * 4 + k) * kT + col];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            M s = tp.w[0] * v[o];
-#pragma unroll
-            for (int k = 1; k < kK; ++k) s = fma_m(tp.w[k], v[o + k], s);
-            acc[p][o] = s;
-        }
-    }
-    double sum = 0.0;
+    column_pass(hp, tp, col, seg, acc);
+    double sum[1] = {};
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         if (EDGE && !(x0 + col < W - (kK - 1) && y0 + seg * 4 + o < H - (kK - 1))) continue;
-        sum += ssim_at<M, CENTRE, PEAK>(acc[0][o], acc[1][o], acc[2][o], acc[3][o], acc[4][o]);
+        sum[0] += ssim_at<M, CENTRE, PEAK>(acc[0][o], acc[1][o], acc[2][o], acc[3][o], acc[4][o]);
     }
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
+    workgroup_sum(sum, red);
+    return sum[0];
 }
 
 // grid (tiles of the largest plane, 3 planes, frames): a workgroup beyond its plane's tiles has nothing to do
@@ -217,15 +160,10 @@ __global__ __launch_bounds__(kThreads) void k_plane_tile(const uint8_t* __restri
     else
         s = tile_body<T, SHA, SHB, true>(pa, pb, tp.a.step[p], tp.b.step[p], H, W, x0, y0, own_w, own_h, taps, raw_a, raw_b, hp, hist, red);
     if (tid == 0) partials[((size_t)f * 3 + p) * tp.nt_max + tile] = s;
-    unsigned* dst = &out[f].abs_hist[p][0];  // the last barrier of tile_body is behind every histogram update
-    for (int i = tid; i < BINS; i += kThreads) {
-        const unsigned v = hist[i];
-        if (v) atomicAdd(dst + i, v);
-    }
+    hist_flush(hist, BINS, &out[f].abs_hist[p][0]);  // the last barrier of tile_body is behind every histogram update
 }
 
-// sum of the tile partials of one (plane, frame) in a fixed order: thread t adds tiles t, t + 256, ..., then a fixed tree; NaN for a
-// plane without window positions
+// sum of the tile partials of one (plane, frame); NaN for a plane without window positions
 __global__ __launch_bounds__(kThreads) void k_plane_final(const double* __restrict__ partials, FinalPlanes fp, avx_plane_metrics_rec* __restrict__ out) {
     __shared__ double red[kThreads];
     const int tid = threadIdx.x, p = blockIdx.x, f = blockIdx.y;
@@ -234,16 +172,8 @@ __global__ __launch_bounds__(kThreads) void k_plane_final(const double* __restri
         if (tid == 0) out[f].ssim[p] = __longlong_as_double(0x7ff8000000000000LL);
         return;
     }
-    const double* src = partials + ((size_t)f * 3 + p) * fp.nt_max;
-    double s = 0.0;
-    for (unsigned t = tid; t < nt; t += kThreads) s += src[t];
-    red[tid] = s;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) out[f].ssim[p] = red[0] / fp.count[p];
+    const double s = tile_partials_sum(partials + ((size_t)f * 3 + p) * fp.nt_max, nt, red);
+    if (tid == 0) out[f].ssim[p] = s / fp.count[p];
 }
 
 // histogram alone: grid (blocks, runs, frames)
@@ -347,18 +277,14 @@ extern "C" int avx_plane_metrics(avx_ctx* ctx, int fmt_a, const uint8_t* a, int 
     const int cw = (W + (1 << ta.sx) - 1) >> ta.sx, ch = (H + (1 << ta.sy) - 1) >> ta.sy;
     TilePlanes tp{};
     tp.a = side_of(ta, H, W), tp.b = side_of(tb, H, W);
-    {
-        double g[kK], sum = 0.0;
-        for (int k = 0; k < kK; ++k) sum += g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-        for (int k = 0; k < kK; ++k) tp.taps[k] = g[k] / sum;
-    }
+    ssim_window_taps(tp.taps);
     FinalPlanes fp{};
     bool any_tile = false, any_hist = false;
     for (int p = 0; p < planes; ++p) {
         tp.h[p] = p ? ch : H, tp.w[p] = p ? cw : W;
         if (with_ssim != 0 && tp.h[p] >= kK && tp.w[p] >= kK) {
-            tp.ntx[p] = (unsigned)((tp.w[p] - (kK - 1) + kT - 1) / kT);
-            tp.nt[p] = tp.ntx[p] * (unsigned)((tp.h[p] - (kK - 1) + kT - 1) / kT);
+            tp.ntx[p] = ssim_tiles(tp.w[p]);
+            tp.nt[p] = tp.ntx[p] * ssim_tiles(tp.h[p]);
             fp.count[p] = (double)(tp.h[p] - (kK - 1)) * (double)(tp.w[p] - (kK - 1));
             any_tile = true;
         } else {

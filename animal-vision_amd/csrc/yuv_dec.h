@@ -1,8 +1,9 @@
 // csrc/yuv_dec.h -- the per-pixel YUV -> RGB decode of DESIGN §4.9, shared by the kernel families that restate it (yuv_raw.hip: the
-// plain decode; yuv_scale.hip: the decode fused with the INTER_AREA reduction, §4.11) so that both compute the same bits.  In an
-// anonymous namespace, as yuv_formats.h: each translation unit gets its own copy.
+// plain decode; yuv_scale.hip: the decode fused with the INTER_AREA reduction, §4.11) so that both compute the same bits, and the
+// stage that hands it to the shared walks (yuv_walks.h).  In an anonymous namespace, as yuv_formats.h: each translation unit gets
+// its own copy.
 #pragma once
-#include "avx_internal.h"
+#include "yuv_formats.h"
 
 namespace {
 
@@ -18,6 +19,23 @@ __device__ __forceinline__ void dec_px(const DecC& c, int Y, int u, int v, uint3
     r = q16_to_u8(ly + c.crv * v);
     g = q16_to_u8(ly + c.cgu * u + c.cgv * v);
     b = q16_to_u8(ly + c.cbu * u);
+}
+
+// The SDR colour stage of the walks of yuv_walks.h: chroma terms are the centred pair; a gray frame's stay {0, 0}.
+struct DecStage {
+    struct Chroma { int u, v; };
+    const DecC& c;
+    __device__ __forceinline__ Chroma chroma(int u_raw, int v_raw) const { return {u_raw - c.cc, v_raw - c.cc}; }
+    __device__ __forceinline__ void px(int y_raw, const Chroma& k, uint32_t& r, uint32_t& g, uint32_t& b) const {
+        dec_px(c, y_raw, k.u, k.v, r, g, b);
+    }
+};
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
+DecC dec_constants(int matrix, int full_range, int depth) {
+    int d[6], e[10];
+    avx_yuv_coefficients_d(matrix, full_range, depth, d, e);
+    return {d[0], d[1], d[2], d[3], d[4], d[5], 1 << (depth - 1)};
 }
 
 }  // namespace

@@ -82,6 +82,24 @@ __device__ __forceinline__ void stage_tables(const Quant& q, uint32_t* coarse_w,
     __syncthreads();
 }
 
+// The HDR colour stage of the walks of yuv_walks.h, over the tables a kernel staged into its LDS: chroma terms are the block's
+// terms of R', G', B', formed once per block.
+template <int TR>
+struct HdrStage {
+    struct Chroma { float dr, dg, db; };
+    const HdrC& c;
+    const float* thr;
+    const uint8_t* coarse;
+    uint32_t lo_key;
+    __device__ __forceinline__ Chroma chroma(int u_raw, int v_raw) const {
+        const float cb = (float)(u_raw - 512) * c.cs, cr = (float)(v_raw - 512) * c.cs;
+        return {c.rv * cr, c.gu * cb + c.gv * cr, c.bu * cb};
+    }
+    __device__ __forceinline__ void px(int y_raw, const Chroma& k, uint32_t& r, uint32_t& g, uint32_t& b) const {
+        hdr_px<TR>(c, thr, coarse, lo_key, (float)(y_raw - c.yo) * c.ys, k.dr, k.dg, k.db, r, g, b);
+    }
+};
+
 // ---- host side -------------------------------------------------------------------------------------------------------------
 bool inv3(const double (&a)[3][3], double (&o)[3][3]) {
     const double c00 = a[1][1] * a[2][2] - a[1][2] * a[2][1], c01 = a[1][2] * a[2][0] - a[1][0] * a[2][2], c02 = a[1][0] * a[2][1] - a[1][1] * a[2][0];

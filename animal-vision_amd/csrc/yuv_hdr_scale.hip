@@ -2,20 +2,14 @@
 // Hd x Wd, in one launch per batch.
 //
 // The definition, byte for byte, is the chain it replaces: avx_yuv_hdr_to_rgb_u8 (yuv_hdr.hip, §4.10) into a full-size RGB frame,
-// then avx_resize_hwc(uint8, INTER_AREA) of that frame (geom.hip, resize_common.h).  These kernels restate both steps per
-// destination pixel, as yuv_scale.hip does for the SDR decode (§4.11), and never write the full-size frame:
-//   * the decode is hdr_px (yuv_hdr_px.h), the function yuv_hdr.hip calls, with the chroma terms dr, dg, db formed once per chroma
-//     block: source pixel (sx, sy) takes chroma (sx >> SX, sy >> SY).  It returns three uint8 codes; the reduction works on codes;
-//   * integer ratios: the int sum of the isx x isy codes per channel, then (sum + 2) >> 2 for 2 x 2 and
-//     rintf((float)sum * (1.f / area)) otherwise -- k_yuv_to_rgb_area_int's;
-//   * any other ratio: area_sum with the table cache's own per-axis tables, in k_yuv_to_rgb_area_gen's order.
-// Streaming kernels in the style of yuv_scale.hip and yuv_hdr.hip: templates over the Fmt traits and the transfer, kYT threads,
-// raw_grid, grid-stride over the batch, no scratch; the quantiser's 3 KiB of tables are the only LDS.
+// then avx_resize_hwc(uint8, INTER_AREA) of that frame (geom.hip, resize_common.h).  The kernels restate both steps per destination
+// pixel and never write the full-size frame: the integer-ratio walk of yuv_walks.h, the one yuv_scale.hip runs for the SDR decode
+// (§4.11), on HdrStage (yuv_hdr_px.h), the stage yuv_hdr.hip decodes with; the 2 x 2 vector kernel and the general-ratio kernel are
+// this file's own, on hdr_px (§4.13 says why: the latter restates k_yuv_to_rgb_area_gen's area_sum order and is kept in step with it).
+// The decode returns uint8 codes and the reductions work on codes.  No scratch; the quantiser's 3 KiB of tables are the only LDS.
 // tests/test_hdr_scale_gpu.py holds them to the chain bit for bit.
-#include <cfloat>
-
-#include "resize_common.h"
 #include "yuv_hdr_px.h"
+#include "yuv_walks.h"
 
 namespace {
 
@@ -30,59 +24,27 @@ __device__ __forceinline__ void load_terms(const HdrC& c, const typename F::T* f
     dr = c.rv * cr; dg = c.gu * cb + c.gv * cr; db = c.bu * cb;
 }
 
-// ---- integer ratio: one thread per destination pixel, the four 10-bit formats, any size ----------------------------------------
 template <class F, int TR>
 __global__ __launch_bounds__(kYT) void k_yuv_hdr_to_rgb_area_int(const uint8_t* __restrict__ yuv, uint8_t* __restrict__ rgb, size_t units, int H,
                                                                   int W, int Hd, int Wd, int isx, int isy, HdrC c, Quant q) {
-    using T = typename F::T;
-    static_assert(!F::LUMA && sizeof(T) == 2, "10-bit formats with chroma only");
+    static_assert(!F::LUMA && sizeof(typename F::T) == 2, "10-bit formats with chroma only");
     __shared__ uint32_t coarse_w[kCoarseTableBytes / 4];
     __shared__ float thr[256];
     stage_tables(q, coarse_w, thr);
-    const uint8_t* coarse = (const uint8_t*)coarse_w;
-    constexpr int BW = 1 << F::SX, BH = 1 << F::SY;
-    const int cw = (W + BW - 1) >> F::SX, ch = (H + BH - 1) >> F::SY;
-    const size_t ysz = (size_t)H * W, csz = (size_t)ch * cw, fsz = (ysz + 2 * csz) * sizeof(T);
-    const size_t dsz = (size_t)Hd * Wd;
-    const bool two = isx == 2 && isy == 2;       // ResizeAreaFastVec, 8-bit 2 x 2
-    const float scale = 1.f / (isx * isy);       // k_resize_area_fast_f32's
-    for (size_t t = (size_t)blockIdx.x * kYT + threadIdx.x; t < units; t += (size_t)gridDim.x * kYT) {
-        const size_t f = t / dsz;
-        const size_t r = t - f * dsz;
-        const int dy = (int)(r / Wd), dx = (int)(r - (size_t)dy * Wd);
-        const T* fr = (const T*)(yuv + f * fsz);
-        int sr = 0, sg = 0, sb = 0, cbx = -1, cby = -1;
-        float dr = 0.f, dg = 0.f, db = 0.f;
-        for (int j = 0; j < isy; ++j) {
-            const int y = dy * isy + j;          // < H: H = isy Hd
-            const T* yrow = fr + (size_t)y * W;
-            for (int k = 0; k < isx; ++k) {
-                const int x = dx * isx + k;      // < W
-                const int bx = x >> F::SX, by = y >> F::SY;
-                if (bx != cbx || by != cby) {    // reloaded, and the terms recomputed, only when the chroma block changes
-                    cbx = bx; cby = by;
-                    load_terms<F>(c, fr, ysz, csz, (size_t)by * cw + bx, dr, dg, db);
-                }
-                uint32_t pr, pg, pb;
-                hdr_px<TR>(c, thr, coarse, q.lo_key, (float)((int)(yrow[x] >> F::SH) - c.yo) * c.ys, dr, dg, db, pr, pg, pb);
-                sr += (int)pr; sg += (int)pg; sb += (int)pb;
-            }
-        }
-        uint8_t* d = rgb + t * 3;
-        if (two) { d[0] = (uint8_t)((sr + 2) >> 2); d[1] = (uint8_t)((sg + 2) >> 2); d[2] = (uint8_t)((sb + 2) >> 2); }
-        else { put_area(d, (float)sr * scale); put_area(d + 1, (float)sg * scale); put_area(d + 2, (float)sb * scale); }
-    }
+    walk_area_int<F>(yuv, rgb, units, H, W, Hd, Wd, isx, isy, HdrStage<TR>{c, thr, (const uint8_t*)coarse_w, q.lo_key});
 }
 
-// ---- 2 x 2 of yuv420p10le and p010le, vector path: PD destination pixels of one row per thread ----------------------------------
-// An output pixel is exactly one chroma block: its chroma terms are formed once and shared by its four hdr_px.  W % (4 PD) == 0,
-// H even, both buffers 16-byte aligned (half_vec below): every run is aligned to its access.  Same sums, same (sum + 2) >> 2 as
-// k_yuv_hdr_to_rgb_area_int: byte-identical output.
 #ifndef AVX_HDR_HALF_PD
 #define AVX_HDR_HALF_PD 8
 #endif
 constexpr int kHalfPD = AVX_HDR_HALF_PD;  // 8 or 4 destination pixels per thread; DESIGN §4.13 has the figures of both
 
+// ---- 2 x 2 of yuv420p10le and p010le, vector path: PD destination pixels of one row per thread ----------------------------------
+// An output pixel is exactly one chroma block: its chroma terms are formed once and shared by its four hdr_px.  W % (4 PD) == 0,
+// H even, both buffers 16-byte aligned (half_vec): every run is aligned to its access.  Same sums, same (sum + 2) >> 2 as
+// walk_area_int: byte-identical output.  The layout, the chroma fetch and the stores are written out here, not taken from
+// yuv_walks.h: the instances sit at 70-71 VGPRs, just below the step from 7 waves to 6 (above 72), and on Frame one of them
+// crosses it.
 template <class F, int TR, int PD>
 __global__ __launch_bounds__(kYT) void k_yuv420_hdr_to_rgb_half_vec(const uint8_t* __restrict__ yuv, uint8_t* __restrict__ rgb, size_t units, int H,
                                                                      int W, HdrC c, Quant q) {
@@ -201,34 +163,6 @@ __global__ __launch_bounds__(kYT) void k_yuv_hdr_to_rgb_area_gen(const uint8_t* 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 constexpr const char* kFn = "avx_yuv_hdr_to_rgb_scaled_u8";
 
-// everything avx_yuv_hdr_to_rgb_u8 and avx_yuv_to_rgb_scaled_u8 refuse, under this function's name
-int hdr_scale_check(avx_ctx* ctx, int fmt, const uint8_t* yuv, const uint8_t* rgb, int n_frames, int H, int W, int Hd, int Wd, int full_range,
-                    int transfer, int tonemap, double peak_nits, double sdr_white) {
-    AVX_REQUIRE(ctx, fmt_ok(fmt) && kTraits[fmt].depth == 10,
-                "%s: pixel format %d (the 10-bit formats of enum avx_pix_fmt: %d yuv420p10le, %d yuv422p10le, %d yuv444p10le, %d p010le)", kFn, fmt,
-                AVX_PIX_YUV420P10LE, AVX_PIX_YUV422P10LE, AVX_PIX_YUV444P10LE, AVX_PIX_P010LE);
-    AVX_REQUIRE(ctx, yuv && rgb, "%s: NULL buffer", kFn);
-    AVX_REQUIRE(ctx, n_frames >= 1 && H >= 1 && W >= 1 && H <= (1 << 15) && W <= (1 << 15), "%s: bad shape (%d frames of %d x %d)", kFn, n_frames, H, W);
-    AVX_REQUIRE(ctx, Hd >= 1 && Wd >= 1, "%s: bad destination size %d x %d", kFn, Hd, Wd);
-    AVX_REQUIRE(ctx, Hd <= H && Wd <= W, "%s: %d x %d -> %d x %d enlarges (INTER_AREA reduces; enlarging is not supported)", kFn, H, W, Hd, Wd);
-    AVX_REQUIRE(ctx, (size_t)n_frames * H * W * 3 < ((size_t)1 << 40), "%s: %d frames of %d x %d is too large", kFn, n_frames, H, W);
-    const size_t ny = (size_t)n_frames * frame_size(kTraits[fmt], H, W), nr = (size_t)n_frames * Hd * Wd * 3;
-    AVX_REQUIRE(ctx, yuv + ny <= rgb || rgb + nr <= yuv, "%s: the source and destination must not overlap", kFn);
-    AVX_REQUIRE(ctx, ((uintptr_t)yuv & 1) == 0, "%s: 16-bit samples need a 2-byte aligned payload", kFn);
-    AVX_REQUIRE(ctx, full_range == 0 || full_range == 1, "%s: full_range %d (0 limited, 1 full)", kFn, full_range);
-    AVX_REQUIRE(ctx, transfer == AVX_TRANSFER_PQ || transfer == AVX_TRANSFER_HLG, "%s: transfer %d (1 pq, 2 hlg)", kFn, transfer);
-    AVX_REQUIRE(ctx, tonemap == AVX_TONEMAP_CLIP || tonemap == AVX_TONEMAP_MOBIUS, "%s: tonemap %d (0 clip, 1 mobius)", kFn, tonemap);
-    AVX_REQUIRE(ctx, std::isfinite(peak_nits) && std::isfinite(sdr_white) && sdr_white > 0.0 && peak_nits > sdr_white,
-                "%s: peak_nits %g and sdr_white %g must be finite, positive and peak_nits > sdr_white", kFn, peak_nits, sdr_white);
-    return AVX_OK;
-}
-
-// the vector path's condition: a 4:2:0 format at exactly 2 x 2, W a multiple of the 2 kHalfPD source columns' 16-byte runs, H even
-bool half_vec(const Traits& t, const void* a, const void* b, int H, int W, int isx, int isy) {
-    return t.sx == 1 && t.sy == 1 && isx == 2 && isy == 2 && W % (4 * kHalfPD) == 0 && H % 2 == 0 && ((uintptr_t)a & 15) == 0 &&
-           ((uintptr_t)b & 15) == 0;
-}
-
 struct Job { avx_ctx* ctx; hipStream_t s; const uint8_t* yuv; uint8_t* rgb; int n, H, W, Hd, Wd; HdrC c; Quant q; };
 
 template <class F, int TR>
@@ -253,57 +187,33 @@ void launch_gen(const Job& j, const AxisArea& ax, const AxisArea& ay) {
                        j.Wd, ax, ay, j.c, j.q);
 }
 
-template <int TR>
-void dispatch_int(int fmt, const Job& j, bool vec, int isx, int isy) {
-    switch (fmt) {
-        case AVX_PIX_YUV420P10LE: launch_int<F420_10, TR>(j, vec, isx, isy); break;
-        case AVX_PIX_YUV422P10LE: launch_int<F422_10, TR>(j, vec, isx, isy); break;
-        case AVX_PIX_YUV444P10LE: launch_int<F444_10, TR>(j, vec, isx, isy); break;
-        default: launch_int<FP010, TR>(j, vec, isx, isy); break;
-    }
-}
-
-template <int TR>
-void dispatch_gen(int fmt, const Job& j, const AxisArea& ax, const AxisArea& ay) {
-    switch (fmt) {
-        case AVX_PIX_YUV420P10LE: launch_gen<F420_10, TR>(j, ax, ay); break;
-        case AVX_PIX_YUV422P10LE: launch_gen<F422_10, TR>(j, ax, ay); break;
-        case AVX_PIX_YUV444P10LE: launch_gen<F444_10, TR>(j, ax, ay); break;
-        default: launch_gen<FP010, TR>(j, ax, ay); break;
-    }
-}
-
 }  // namespace
 
 extern "C" int avx_yuv_hdr_to_rgb_scaled_u8(avx_ctx* ctx, int fmt, const uint8_t* yuv, uint8_t* rgb_hwc, int n_frames, int H, int W, int Hd, int Wd,
                                             int full_range, int transfer, int tonemap, double peak_nits, double sdr_white, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
-    int rc = hdr_scale_check(ctx, fmt, yuv, rgb_hwc, n_frames, H, W, Hd, Wd, full_range, transfer, tonemap, peak_nits, sdr_white);
+    int rc = hdr_check(ctx, kFn, fmt, yuv, rgb_hwc, n_frames, H, W, Hd, Wd, full_range, transfer, tonemap, peak_nits, sdr_white);
     if (rc) return rc;
     if (Hd == H && Wd == W)  // the 1 x 1 block is rintf(sum * 1.f): the plain decode, which has the wider kernels for it
         return avx_yuv_hdr_to_rgb_u8(ctx, fmt, yuv, rgb_hwc, n_frames, H, W, full_range, transfer, tonemap, peak_nits, sdr_white, stream);
-    // avx_resize_hwc's own test for the integer-ratio route
-    const double sx = (double)W / Wd, sy = (double)H / Hd;
-    const int isx = (int)std::lrint(sx), isy = (int)std::lrint(sy);
-    const bool integer = std::fabs(sx - isx) < DBL_EPSILON && std::fabs(sy - isy) < DBL_EPSILON;
-    AVX_REQUIRE(ctx, !integer || (size_t)isx * isy <= 65536, "%s: a %d x %d block is more than 65536 samples per output pixel", kFn, isx, isy);
+    const AreaRoute a = area_route(H, W, Hd, Wd);
+    AVX_REQUIRE(ctx, !a.integer || (size_t)a.isx * a.isy <= 65536, "%s: a %d x %d block is more than 65536 samples per output pixel", kFn, a.isx, a.isy);
     AVX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = avx_pick_stream(ctx, stream);
     const Job j = {ctx, s, yuv, rgb_hwc, n_frames, H, W, Hd, Wd, hdr_constants(full_range, transfer, tonemap, peak_nits, sdr_white),
                    {ctx->d_enc_thr_f32, ctx->d_coarse_f32, ctx->coarse_lo_key[0]}};
-    if (integer) {
-        const bool vec = half_vec(kTraits[fmt], yuv, rgb_hwc, H, W, isx, isy);
-        if (transfer == AVX_TRANSFER_PQ) dispatch_int<AVX_TRANSFER_PQ>(fmt, j, vec, isx, isy);
-        else dispatch_int<AVX_TRANSFER_HLG>(fmt, j, vec, isx, isy);
+    const bool pq = transfer == AVX_TRANSFER_PQ;
+    if (a.integer) {
+        const bool vec = half_vec(kTraits[fmt], yuv, rgb_hwc, H, W, a.isx, a.isy, kHalfPD);
+#define AVX_HDR_INT(F) (pq ? launch_int<F, AVX_TRANSFER_PQ>(j, vec, a.isx, a.isy) : launch_int<F, AVX_TRANSFER_HLG>(j, vec, a.isx, a.isy))
+        AVX_FMT10_DISPATCH(fmt, AVX_HDR_INT)
+#undef AVX_HDR_INT
     } else {
-        avx_ws* ws = avx_workspace(ctx, s);
-        if (!ws) return AVX_ERR_NOMEM;
-        avx_area_tab tx{}, ty{};
-        if ((rc = avx_geom_area_tables(ctx, ws, s, H, W, Hd, Wd, &tx, &ty))) return rc;
-        const AxisArea ax{const_cast<int*>(tx.start), const_cast<int*>(tx.cnt), const_cast<float*>(tx.alpha), tx.maxcnt};
-        const AxisArea ay{const_cast<int*>(ty.start), const_cast<int*>(ty.cnt), const_cast<float*>(ty.alpha), ty.maxcnt};
-        if (transfer == AVX_TRANSFER_PQ) dispatch_gen<AVX_TRANSFER_PQ>(fmt, j, ax, ay);
-        else dispatch_gen<AVX_TRANSFER_HLG>(fmt, j, ax, ay);
+        AxisArea ax, ay;
+        if ((rc = area_axes(ctx, s, H, W, Hd, Wd, &ax, &ay))) return rc;
+#define AVX_HDR_GEN(F) (pq ? launch_gen<F, AVX_TRANSFER_PQ>(j, ax, ay) : launch_gen<F, AVX_TRANSFER_HLG>(j, ax, ay))
+        AVX_FMT10_DISPATCH(fmt, AVX_HDR_GEN)
+#undef AVX_HDR_GEN
     }
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;

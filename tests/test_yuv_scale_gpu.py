@@ -134,10 +134,11 @@ def _scaled_at_offsets(ctx, buf, fmt, H, W, Hd, Wd, src_off, dst_off):
 
 
 @pytest.mark.parametrize("fmt", FMTS_420)
-@pytest.mark.parametrize("H,W", [(64, 128), (1080, 1920)])
+@pytest.mark.parametrize("H,W", [(2, 32), (64, 128), (32, 48), (1080, 1920)])
 def test_vector_path_equals_the_chain_and_the_block_path(fmt, H, W):
-    """W % 32 == 0 and H even with 16-byte aligned buffers: the 2 x 2 vector kernel.  The same frame from a payload, then from a
-    destination, 8 bytes off alignment takes the one-thread-per-pixel kernel: the bytes must be equal."""
+    """W % 32 == 0 and H even with 16-byte aligned buffers: the 2 x 2 vector kernel; (2, 32) is a single unit, one row pair.  The
+    same frame from a payload, then from a destination, 8 bytes off alignment takes the one-thread-per-pixel kernel: the bytes must
+    be equal.  (32, 48): W % 32 != 0, the per-pixel kernel at every offset."""
     from animal_vision_amd.runtime import get_context
 
     ctx = get_context()

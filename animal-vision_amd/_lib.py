@@ -196,6 +196,17 @@ class MsSsimRecord(ctypes.Structure):
 
 assert ctypes.sizeof(MsSsimRecord) == 240
 
+
+class DiffRecord(ctypes.Structure):
+    """avx_diff_rec (include/avx.h)."""
+
+    _fields_ = [("max_d", ctypes.c_uint32), ("max_x", ctypes.c_uint32), ("max_y", ctypes.c_uint32), ("beyond", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(DiffRecord) == 16
+AVX_DIFF_MODES = {"abs": 0, "heat": 1, "ssim": 2}  # enum avx_diff_mode
+AVX_DIFF_LAYOUTS = {"map": 0, "side": 1}           # enum avx_diff_layout
+
 class EwInsn(ctypes.Structure):
     _fields_ = [("op", ctypes.c_uint8), ("dst", ctypes.c_uint8), ("a", ctypes.c_uint8), ("b", ctypes.c_uint8), ("imm", ctypes.c_uint32)]
 
@@ -337,6 +348,7 @@ _SIGS = {
     "avx_frame_metrics_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "avx_plane_metrics": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "avx_frame_metrics_ms_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "avx_diff_map_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _i, _i, _vp, _vp, _vp, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

@@ -14,7 +14,6 @@
 
 namespace {
 
-constexpr int kRaw = kP * 3 + 6;       // bytes of a patch row in LDS (132: rows land one bank apart)
 constexpr int kBins = 3 * 256;
 
 // one sample pair into the workgroup's histogram; zeros, by far the commonest difference of two renderings of one clip, are
@@ -25,63 +24,24 @@ __device__ __forceinline__ void hist_add(unsigned* hist, int c, int a, int b, un
     else atomicAdd(&hist[c * 256 + d], 1u);
 }
 
-// Row item of NOUT adjacent positions of patch row `row`, from column x on, for channel C: the NOUT + 10 samples of both frames,
-// centred by 128.  NOUT == 4 (x a multiple of 4) reads the bytes as the 11 aligned words that hold them, NOUT == 2 byte by byte.
-template <int NOUT, int C>
-__device__ __forceinline__ void row_item(const uint8_t* raw_a, const uint8_t* raw_b, float* hp, const Taps<float>& tp, int row, int x) {
-    constexpr int NS = NOUT + kK - 1;
-    float a[NS], b[NS];
-    if (NOUT == 4) {
-        const uint32_t* wa = reinterpret_cast<const uint32_t*>(raw_a + row * kRaw + x * 3);
-        const uint32_t* wb = reinterpret_cast<const uint32_t*>(raw_b + row * kRaw + x * 3);
-        uint32_t va[11], vb[11];
-#pragma unroll
-        for (int i = 0; i < 11; ++i) va[i] = wa[i], vb[i] = wb[i];
-#pragma unroll
-        for (int j = 0; j < NS; ++j) {
-            const int byte = 3 * j + C;
-            a[j] = (float)((va[byte >> 2] >> (8 * (byte & 3))) & 255u) - 128.0f;
-            b[j] = (float)((vb[byte >> 2] >> (8 * (byte & 3))) & 255u) - 128.0f;
-        }
-    } else {
-        const uint8_t* ra = raw_a + row * kRaw + x * 3 + C;
-        const uint8_t* rb = raw_b + row * kRaw + x * 3 + C;
-#pragma unroll
-        for (int j = 0; j < NS; ++j) {
-            a[j] = (float)ra[3 * j] - 128.0f;
-            b[j] = (float)rb[3 * j] - 128.0f;
-        }
-    }
-    row_moments<float, NOUT>(a, b, tp, hp, row, x);
-}
-
 // One channel of a tile: row pass into hp, column pass in registers, the SSIM of the thread's 4 positions, the workgroup's sum.
 template <bool EDGE, int C, bool WITH_CS>
 __device__ __forceinline__ void channel_pass(int H, int W, int x0, int y0, const Taps<float>& tp, const uint8_t* raw_a, const uint8_t* raw_b, float* hp,
                                              double* red, double* part, size_t cs_offset) {
     const int tid = threadIdx.x;
-    row_pass([&](auto n, int row, int x) { row_item<decltype(n)::value, C>(raw_a, raw_b, hp, tp, row, x); });
+    row_pass([&](auto n, int row, int x) { rgb_row_item<decltype(n)::value, C>(raw_a, raw_b, hp, tp, row, x); });
     __syncthreads();
     const int col = tid & (kT - 1), seg = tid >> 5;
     float acc[5][4];
     column_pass(hp, tp, col, seg, acc);
-    // ---- SSIM.  E[x^2] - mu^2 loses nothing to float32: the rounding error of the product is recovered with an fma and taken
-    // off the difference, so variance and covariance carry a relative error of 2^-23, not one of the size of mu^2. ----
-    const float C1 = 6.5025f, C2 = 58.5225f;  // (0.01 * 255)^2, (0.03 * 255)^2
-    double sum[WITH_CS ? 2 : 1] = {};         // SSIM and, WITH_CS, cs
+    // ---- SSIM of the thread's positions: ssim_window.h's float32 arithmetic of one position ----
+    double sum[WITH_CS ? 2 : 1] = {};  // SSIM and, WITH_CS, cs
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         if (EDGE && !(x0 + col < W - (kK - 1) && y0 + seg * 4 + o < H - (kK - 1))) continue;
-        const float ma = acc[0][o], mb = acc[1][o];
-        const float paa = ma * ma, pbb = mb * mb, pab = ma * mb;
-        const float va = (acc[2][o] - paa) - fmaf(ma, ma, -paa);
-        const float vb = (acc[3][o] - pbb) - fmaf(mb, mb, -pbb);
-        const float cab = (acc[4][o] - pab) - fmaf(ma, mb, -pab);
-        const float ua = ma + 128.0f, ub = mb + 128.0f;
-        const float num = (2.0f * (ua * ub) + C1) * (2.0f * cab + C2);
-        const float den = ((ua * ua + ub * ub) + C1) * ((va + vb) + C2);
-        sum[0] += (double)(num / den);
-        if constexpr (WITH_CS) sum[1] += (double)((2.0f * cab + C2) / ((va + vb) + C2));
+        float cs = 0.0f;
+        sum[0] += (double)ssim_position_f32<WITH_CS>(acc[0][o], acc[1][o], acc[2][o], acc[3][o], acc[4][o], &cs);
+        if constexpr (WITH_CS) sum[1] += (double)cs;
     }
     workgroup_sum(sum, red);  // its barrier: every column pass has read hp before the next channel's row pass writes it
     if (tid == 0) {

@@ -10,7 +10,9 @@
 // term of each position from them.  The positions are summed in float64 in a fixed order: a workgroup reduces its own to one double
 // per sum, and the file's *_final kernel adds the tiles of a record entry with tile_partials_sum: no floating-point atomics.
 // What differs between the files stays in them: how a patch gets into LDS and its samples from there into registers, the histogram
-// of each layout, and the arithmetic of a position.
+// of each layout, and the arithmetic of a position.  diff_map.hip (k_diff_ssim_tile: the SSIM of every position as a picture) runs
+// the passes on metrics.hip's RGB byte patches and keeps the positions instead of summing them; what those two share beyond the
+// passes -- the row item of a byte patch and the float32 arithmetic of a position -- is here too, in one copy.
 #pragma once
 #include <cmath>
 #include <type_traits>
@@ -102,6 +104,57 @@ __device__ __forceinline__ void column_pass(const M* hp, const Taps<M>& tp, int 
             acc[p][o] = s;
         }
     }
+}
+
+// ---- uint8 RGB frames in float32: what metrics.hip (the record) and diff_map.hip (the map) share beyond the passes ----
+constexpr int kRaw = kP * 3 + 6;       // bytes of a patch row in LDS (132: rows land one bank apart)
+
+// Row item of NOUT adjacent positions of patch row `row`, from column x on, for channel C: the NOUT + 10 samples of both frames,
+// centred by 128.  NOUT == 4 (x a multiple of 4) reads the bytes as the 11 aligned words that hold them, NOUT == 2 byte by byte.
+template <int NOUT, int C>
+__device__ __forceinline__ void rgb_row_item(const uint8_t* raw_a, const uint8_t* raw_b, float* hp, const Taps<float>& tp, int row, int x) {
+    constexpr int NS = NOUT + kK - 1;
+    float a[NS], b[NS];
+    if (NOUT == 4) {
+        const uint32_t* wa = reinterpret_cast<const uint32_t*>(raw_a + row * kRaw + x * 3);
+        const uint32_t* wb = reinterpret_cast<const uint32_t*>(raw_b + row * kRaw + x * 3);
+        uint32_t va[11], vb[11];
+#pragma unroll
+        for (int i = 0; i < 11; ++i) va[i] = wa[i], vb[i] = wb[i];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int byte = 3 * j + C;
+            a[j] = (float)((va[byte >> 2] >> (8 * (byte & 3))) & 255u) - 128.0f;
+            b[j] = (float)((vb[byte >> 2] >> (8 * (byte & 3))) & 255u) - 128.0f;
+        }
+    } else {
+        const uint8_t* ra = raw_a + row * kRaw + x * 3 + C;
+        const uint8_t* rb = raw_b + row * kRaw + x * 3 + C;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            a[j] = (float)ra[3 * j] - 128.0f;
+            b[j] = (float)rb[3 * j] - 128.0f;
+        }
+    }
+    row_moments<float, NOUT>(a, b, tp, hp, row, x);
+}
+
+// The SSIM of one position of uint8 RGB frames in float32 (metrics.hip: the record; diff_map.hip: the map), from its five window sums
+// of samples centred by 128: ma, mb the means, eaa, ebb, eab the second moments.  E[x^2] - mu^2 loses nothing to float32: the rounding
+// error of the product is recovered with an fma and taken off the difference, so variance and covariance carry a relative error of
+// 2^-23, not one of the size of mu^2.  WITH_CS: *cs receives the contrast-structure term (2 s_ab + C2) / (s_a^2 + s_b^2 + C2).
+template <bool WITH_CS>
+__device__ __forceinline__ float ssim_position_f32(float ma, float mb, float eaa, float ebb, float eab, float* cs) {
+    const float C1 = 6.5025f, C2 = 58.5225f;  // (0.01 * 255)^2, (0.03 * 255)^2
+    const float paa = ma * ma, pbb = mb * mb, pab = ma * mb;
+    const float va = (eaa - paa) - fmaf(ma, ma, -paa);
+    const float vb = (ebb - pbb) - fmaf(mb, mb, -pbb);
+    const float cab = (eab - pab) - fmaf(ma, mb, -pab);
+    const float ua = ma + 128.0f, ub = mb + 128.0f;
+    const float num = (2.0f * (ua * ub) + C1) * (2.0f * cab + C2);
+    const float den = ((ua * ua + ub * ub) + C1) * ((va + vb) + C2);
+    if constexpr (WITH_CS) *cs = (2.0f * cab + C2) / ((va + vb) + C2);
+    return num / den;
 }
 
 // The workgroup's sums of N doubles per thread, in a fixed order: a __shfl_down tree per wave, then the four waves in order.  Every

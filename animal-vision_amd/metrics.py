@@ -11,16 +11,22 @@ plane_metrics (csrc/plane_metrics.hip) is the same comparison of 
 the four above.
 
 MsSsim (csrc/ms_ssim.hip) is MS-SSIM over five scales (Wang, Simoncelli, Bovik 2003) of the same RGB frames:
-frame_metrics_ms_launch / frame_metrics_ms_device return it beside the FrameMetrics of the same call, ms_ssim takes arrays."""
+frame_metrics_ms_launch / frame_metrics_ms_device return it beside the FrameMetrics of the same call, ms_ssim takes arrays.
+
+Difference maps (csrc/diff_map.hip) say where the frames differ: diff_map_launch enqueues the per-pixel map ("abs",
+"heat" or "ssim"; alone or A | B | map side by side) and a DiffRecord per frame, diff_map and ssim_map take arrays.
+python -m animal_vision_amd.diff is the command built on them."""
 from __future__ import annotations
 
 import ctypes
 import math
+import numbers
 from typing import List, Optional
 
 import numpy as np
 
-from ._lib import AVX_METRICS_MAX_FRAMES, AVX_PIX_FMTS, FrameMetricsRecord, MsSsimRecord, PlaneMetricsRecord, lib
+from ._lib import AVX_DIFF_LAYOUTS, AVX_DIFF_MODES, AVX_METRICS_MAX_FRAMES, AVX_PIX_FMTS, FrameMetricsRecord, MsSsimRecord, PlaneMetricsRecord, lib
+from ._lib import DiffRecord as DiffRecordStruct
 from .runtime import Context, DeviceBuffer, get_context
 
 MAX_FRAMES = AVX_METRICS_MAX_FRAMES
@@ -485,3 +491,128 @@ def ms_ssim(a, b, *, ctx: Optional[Context] = None):
         d_a.free()
         d_b.free()
     return out if batched else out[0]
+
+
+# ------------------------------------------------------------------------------------------------ difference maps
+DIFF_RECORD_BYTES = ctypes.sizeof(DiffRecordStruct)  # max_d, max_x, max_y, beyond: 4 uint32
+_DIFF_DTYPE = np.dtype([("max_d", np.uint32), ("max_x", np.uint32), ("max_y", np.uint32), ("beyond", np.uint32)])
+assert _DIFF_DTYPE.itemsize == DIFF_RECORD_BYTES == 16
+DIFF_MODES, DIFF_LAYOUTS = tuple(AVX_DIFF_MODES), tuple(AVX_DIFF_LAYOUTS)
+DIFF_DEFAULT_GAIN = {"abs": 32, "heat": 32, "ssim": 4.0}
+SSIM_WINDOW = 11  # the SSIM mode needs one window position: frames of at least 11 x 11
+
+
+class DiffRecord:
+    """One frame's record of a difference map: max_d = the largest d = max_c |a_c - b_c| of the frame, (max_x, max_y) = the first
+    pixel in raster order that attains it ((0, 0) when max_d is 0), beyond = the number of pixels with d above the threshold."""
+
+    __slots__ = ("max_d", "max_x", "max_y", "beyond")
+
+    def __init__(self, max_d: int, max_x: int, max_y: int, beyond: int):
+        self.max_d, self.max_x, self.max_y, self.beyond = int(max_d), int(max_x), int(max_y), int(beyond)
+
+    def astuple(self) -> tuple:
+        return self.max_d, self.max_x, self.max_y, self.beyond
+
+    def __eq__(self, other):
+        if not isinstance(other, DiffRecord):
+            return NotImplemented
+        return self.astuple() == other.astuple()
+
+    def __repr__(self):
+        return f"DiffRecord(max_d={self.max_d}, at=({self.max_x}, {self.max_y}), beyond={self.beyond})"
+
+
+def check_diff_options(mode: str, gain, threshold, layout: str, H: Optional[int] = None, W: Optional[int] = None):
+    """The gain (the mode's default when None) as the number the library takes, after the checks of avx_diff_map_u8 that need no
+    device; ValueError naming the option otherwise."""
+    if mode not in AVX_DIFF_MODES:
+        raise ValueError(f"mode must be one of {', '.join(AVX_DIFF_MODES)} (got {mode!r})")
+    if layout not in AVX_DIFF_LAYOUTS:
+        raise ValueError(f"layout must be one of {', '.join(AVX_DIFF_LAYOUTS)} (got {layout!r})")
+    if isinstance(threshold, bool) or not isinstance(threshold, numbers.Integral) or not 0 <= threshold <= 254:
+        raise ValueError(f"threshold must be an integer 0..254 (got {threshold!r})")
+    gain = DIFF_DEFAULT_GAIN[mode] if gain is None else gain
+    if mode == "ssim":
+        if not (isinstance(gain, numbers.Real) and 0.0 < gain <= 16.0):
+            raise ValueError(f"the gain of mode ssim must be above 0 and at most 16 (got {gain!r})")
+        if H is not None and W is not None and (H < SSIM_WINDOW or W < SSIM_WINDOW):
+            raise ValueError(f"mode ssim needs frames of at least {SSIM_WINDOW} x {SSIM_WINDOW} (got {H} x {W})")
+    elif not (isinstance(gain, numbers.Real) and float(gain).is_integer() and 1 <= gain <= 255):
+        raise ValueError(f"the gain of mode {mode} must be an integer 1..255 (got {gain!r})")
+    return float(gain)
+
+
+def diff_map_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_out: DeviceBuffer, d_rec: DeviceBuffer,
+                    *, mode: str = "heat", gain=None, threshold: int = 1, layout: str = "map", d_ssim_map: Optional[DeviceBuffer] = None,
+                    stream=None) -> None:
+    """Enqueue the difference maps of n_frames frames on `stream`: d_out takes n_frames frames of H x W x 3 (layout "map") or
+    H x 3W x 3 ("side": A | B | map), d_rec n_frames records of DIFF_RECORD_BYTES (diff_records_from_bytes reads them), d_ssim_map
+    (mode "ssim" only) the float32 SSIM of every window position, n_frames x (H - 10) x (W - 10) x 3.  Nothing is downloaded and
+    nothing waits."""
+    _check_call(n_frames, H, W, d_a, d_b)
+    g = check_diff_options(mode, gain, threshold, layout, H, W)
+    need = n_frames * H * W * 3 * (3 if layout == "side" else 1)
+    if d_out.nbytes < need or d_rec.nbytes < n_frames * DIFF_RECORD_BYTES:
+        raise ValueError(f"{n_frames} {layout} frames and records need {need} and {n_frames * DIFF_RECORD_BYTES} bytes; the buffers hold "
+                         f"{d_out.nbytes} and {d_rec.nbytes}")
+    if d_ssim_map is not None:
+        if mode != "ssim":
+            raise ValueError(f"d_ssim_map goes with mode ssim only (got mode {mode!r})")
+        need = n_frames * (H - 10) * (W - 10) * 3 * 4
+        if d_ssim_map.nbytes < need:
+            raise ValueError(f"the SSIM of {n_frames} frames' positions needs {need} bytes; the buffer holds {d_ssim_map.nbytes}")
+    ctx._check(lib.avx_diff_map_u8(ctx._h, d_a.ptr, d_b.ptr, int(n_frames), int(H), int(W), AVX_DIFF_MODES[mode], g, int(threshold),
+                                   AVX_DIFF_LAYOUTS[layout], d_out.ptr, d_rec.ptr, None if d_ssim_map is None else d_ssim_map.ptr, ctx._s(stream)))
+
+
+def diff_records_from_bytes(buf: np.ndarray, n_frames: int) -> List[DiffRecord]:
+    """n_frames downloaded records (uint8) -> DiffRecord."""
+    recs = np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n_frames * DIFF_RECORD_BYTES], dtype=_DIFF_DTYPE)
+    return [DiffRecord(r["max_d"], r["max_x"], r["max_y"], r["beyond"]) for r in recs]
+
+
+def _diff_chunks(a, b, mode, gain, threshold, layout, ctx, with_float):
+    """diff_map and ssim_map: the stack in chunks of at most 16 frames -> (frames, records, float maps or None)."""
+    N, H, W = a.shape[:3]
+    ctx = ctx or get_context()
+    chunk = min(N, MAX_FRAMES)
+    wide = 3 if layout == "side" else 1
+    d_a, d_b, d_out = ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * H * W * 3 * wide)
+    d_rec = ctx.malloc(chunk * DIFF_RECORD_BYTES)
+    d_map = ctx.malloc(chunk * (H - 10) * (W - 10) * 12) if with_float else None
+    frames, recs = np.empty((N, H, W * wide, 3), np.uint8), []
+    maps = np.empty((N, H - 10, W - 10, 3), np.float32) if with_float else None
+    try:
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            ctx.upload(a[i : i + n], d_a)
+            ctx.upload(b[i : i + n], d_b)
+            diff_map_launch(ctx, d_a, d_b, n, H, W, d_out, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_ssim_map=d_map)
+            ctx.download(d_out, (n, H, W * wide, 3), np.uint8, out=frames[i : i + n])
+            recs += diff_records_from_bytes(ctx.download(d_rec, (n * DIFF_RECORD_BYTES,), np.uint8), n)
+            if with_float:
+                ctx.download(d_map, (n, H - 10, W - 10, 3), np.float32, out=maps[i : i + n])
+    finally:
+        for d in (d_a, d_b, d_out, d_rec, d_map):
+            if d is not None:
+                d.free()
+    return frames, recs, maps
+
+
+def diff_map(a, b, *, mode: str = "heat", gain=None, threshold: int = 1, layout: str = "map", ctx: Optional[Context] = None):
+    """a, b: uint8 H x W x 3 -> (the map, uint8 H x W x 3 -- H x 3W x 3 with layout "side" --, its DiffRecord), or N x H x W x 3 ->
+    (N maps, a list of N records); uploaded in chunks of at most 16 frames.  mode: "abs", "heat" or "ssim"; gain: the mode's
+    default (32, 32, 4) when None.  ValueError for a bad option or shape before any device work."""
+    a, b, batched = check_pair(a, b)
+    check_diff_options(mode, gain, threshold, layout, a.shape[1], a.shape[2])
+    frames, recs, _ = _diff_chunks(a, b, mode, gain, threshold, layout, ctx, False)
+    return (frames, recs) if batched else (frames[0], recs[0])
+
+
+def ssim_map(a, b, *, ctx: Optional[Context] = None) -> np.ndarray:
+    """a, b: uint8 H x W x 3 or N x H x W x 3 (at least 11 x 11) -> the SSIM of every window position and channel as the map kernel
+    forms it, float32 N x (H - 10) x (W - 10) x 3 (N = 1 for one frame): the values whose mean is FrameMetrics.ssim."""
+    a, b, _ = check_pair(a, b)
+    check_diff_options("ssim", None, 1, "map", a.shape[1], a.shape[2])
+    return _diff_chunks(a, b, "ssim", None, 1, "map", ctx, True)[2]

@@ -353,10 +353,13 @@ class VideoRenderer(Renderer):
 
             payload = rgb_to_i420(frame, matrix=self.out_matrix, range=self.yuv_range)
         elif frame.ndim == 1 and frame.dtype == np.uint8:
-            if self._y4m_out is None and self._y4m is None:
-                raise ValueError("an I420 payload names no frame size: render an RGB frame first, or read from a .y4m")
-            hdr = self._y4m_out.header if self._y4m_out is not None else self._y4m.header
-            H, W = (hdr.height, hdr.width) if self._y4m_out is not None or (self.scale is None and self._sink_hw is None) else self.sink_hw  # payloads arrive scaled
+            if self._y4m_out is None and self._y4m is None and self._sink_hw is None:
+                raise ValueError("an I420 payload names no frame size: render an RGB frame first, read from a .y4m, or call set_output_size()")
+            if self._y4m_out is not None or (self.scale is None and self._sink_hw is None):
+                hdr = self._y4m_out.header if self._y4m_out is not None else self._y4m.header
+                H, W = hdr.height, hdr.width
+            else:
+                H, W = self.sink_hw  # payloads arrive scaled, or at the size set_output_size() named
             payload = frame
         else:
             raise ValueError(f"a .y4m sink takes RGB uint8 HxWx3 frames or flat uint8 I420 payloads, got {frame.dtype} {frame.shape}")
@@ -376,8 +379,9 @@ class VideoRenderer(Renderer):
 
             payload = rgb_to_yuv(frame, pix_fmt=self.write_pix_fmt, matrix=self.out_matrix, range=self.yuv_range)
         elif frame.ndim == 1 and frame.dtype == np.uint8:
-            if self._raw_out is None and (self._raw is None or self.pix_fmt != self.write_pix_fmt):
-                raise ValueError(f"a {self.write_pix_fmt} payload names no frame size: render an RGB frame first, or read raw video in that format")
+            if self._raw_out is None and self._sink_hw is None and (self._raw is None or self.pix_fmt != self.write_pix_fmt):
+                raise ValueError(f"a {self.write_pix_fmt} payload names no frame size: render an RGB frame first, read raw video in that "
+                                 "format, or call set_output_size()")
             H, W = (self._raw_out.height, self._raw_out.width) if self._raw_out is not None else self.sink_hw  # payloads arrive scaled
             payload = frame
         else:

@@ -467,6 +467,33 @@ typedef struct avx_ms_ssim_rec {
 int avx_frame_metrics_ms_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W,
                             avx_frame_metrics* out_dev, avx_ms_ssim_rec* ms_out_dev, void* stream);
 
+/* Difference maps (csrc/diff_map.hip): where two batches of uint8 RGB frames differ, as a picture per frame, and per
+ * frame the largest difference, its first pixel and the pixels beyond a threshold. */
+enum avx_diff_mode { AVX_DIFF_ABS = 0, AVX_DIFF_HEAT = 1, AVX_DIFF_SSIM = 2 };
+enum avx_diff_layout { AVX_DIFF_MAP = 0, AVX_DIFF_SIDE = 1 };
+typedef struct { uint32_t max_d, max_x, max_y, beyond; } avx_diff_rec;
+
+/* a_hwc, b_hwc: n_frames contiguous H x W x 3 uint8 frames on the device; out_hwc: n_frames frames of H x W x 3 (AVX_DIFF_MAP) or
+ * H x 3W x 3 (AVX_DIFF_SIDE: A | B | map, written by the same launch); rec_dev: n_frames records on the device (8-byte aligned).
+ * Asynchronous on `stream`.  1 <= n_frames <= 16, H*W < 2^32.  With d_c = |a_c - b_c| and d = max_c d_c of a pixel, G = gain and
+ * K = threshold (0..254):
+ *   AVX_DIFF_ABS  (G an integer 1..255): out_c = min(255, G d_c).
+ *   AVX_DIFF_HEAT (G an integer 1..255): d <= K: out = (g, g, g), g = ((77 a_r + 150 a_g + 29 a_b + 128) >> 8) >> 2, a dim grey of
+ *       A; d > K: out = pal(min(255, G (d - K))), pal(v) = (min(255, 3v), clamp(3v - 255, 0, 255), clamp(3v - 510, 0, 255)).
+ *   AVX_DIFF_SSIM (0 < G <= 16, H >= 11 and W >= 11): the local SSIM of avx_frame_metrics_u8 (the same float32 arithmetic of a
+ *       position).  Pixel (y, x) takes window position (clamp(y - 5, 0, H - 11), clamp(x - 5, 0, W - 11)); with s_c that position's
+ *       SSIM in channel c, sbar = ((s_r + s_g) + s_b) / 3 and v = clamp(floor((255 G) (1 - sbar) + 0.5), 0, 255), all float32,
+ *       out = pal(v).  Identical frames give an all-black map.  ssim_map_dev, when not NULL (this mode only; 4-byte aligned),
+ *       receives the s_c themselves: float32 [frame][H - 10][W - 10][3].
+ * The record is written in every mode: max_d the largest d of the frame, (max_x, max_y) the first pixel in raster order that
+ * attains it ((0, 0) when max_d is 0), beyond the number of PIXELS with d > K (avx_frame_metrics' histogram counts samples).  Maps and
+ * records are integers or fixed-order float32: a frame's output does not depend on its batch or on the run.
+ * AVX_ERR_INVALID (avx_last_error starts with this function's name) for a NULL buffer, n_frames outside 1..16, a bad size, mode or
+ * layout, a gain outside the mode's range (or not an integer in the ABS and HEAT modes), a threshold outside 0..254, the SSIM mode
+ * below 11 x 11, ssim_map_dev in another mode, and out_hwc overlapping an input; nothing is launched then. */
+int avx_diff_map_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int mode, float gain, int threshold,
+                    int layout, uint8_t* out_hwc, avx_diff_rec* rec_dev, float* ssim_map_dev, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

@@ -207,6 +207,18 @@ assert ctypes.sizeof(DiffRecord) == 16
 AVX_DIFF_MODES = {"abs": 0, "heat": 1, "ssim": 2}  # enum avx_diff_mode
 AVX_DIFF_LAYOUTS = {"map": 0, "side": 1}           # enum avx_diff_layout
 
+
+class DeltaERecord(ctypes.Structure):
+    """avx_delta_e_rec (include/avx.h)."""
+
+    _fields_ = [("hist", ctypes.c_uint32 * 256), ("sum", ctypes.c_double), ("max_de", ctypes.c_float), ("max_x", ctypes.c_uint32),
+                ("max_y", ctypes.c_uint32), ("beyond", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(DeltaERecord) == 1048
+AVX_DELTA_E_MODES = {"heat": 0, "plain": 1}   # enum avx_delta_e_mode
+AVX_DELTA_E_LAYOUTS = {"map": 0, "side": 1}   # enum avx_delta_e_layout
+
 class EwInsn(ctypes.Structure):
     _fields_ = [("op", ctypes.c_uint8), ("dst", ctypes.c_uint8), ("a", ctypes.c_uint8), ("b", ctypes.c_uint8), ("imm", ctypes.c_uint32)]
 
@@ -349,6 +361,7 @@ _SIGS = {
     "avx_plane_metrics": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "avx_frame_metrics_ms_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "avx_diff_map_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _i, _i, _vp, _vp, _vp, _vp]),
+    "avx_delta_e_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

@@ -15,19 +15,12 @@
 // larger d and, among equals, the earlier pixel; a workgroup reduces keys (max) and counts (sum) by wave shuffles and four LDS words,
 // then thread 0 applies one 64-bit atomicMax and one atomicAdd to the frame's record, whose first 8 bytes hold the key until
 // k_diff_final turns it into (max_d, max_x, max_y).  Integer max and sum: the order of the atomics does not matter.
+#include "map_common.h"
 #include "ssim_window.h"
 
 namespace {
 
 __device__ __forceinline__ int iabs_diff(int a, int b) { return a > b ? a - b : b - a; }
-
-// pal(v) = (min(255, 3v), clamp(3v - 255, 0, 255), clamp(3v - 510, 0, 255)): black - red - yellow - white; the sum is 3v
-__device__ __forceinline__ void pal(int v, uint32_t& r, uint32_t& g, uint32_t& b) {
-    const int t = 3 * v;
-    r = (uint32_t)min(255, t);
-    g = (uint32_t)min(255, max(0, t - 255));
-    b = (uint32_t)max(0, t - 510);
-}
 
 // one pixel of the ABS / HEAT maps; d = max_c |a_c - b_c|
 template <int MODE>
@@ -38,8 +31,7 @@ __device__ __forceinline__ int diff_px(int ar, int ag, int ab, int br, int bg, i
         r = (uint32_t)min(255, G * dr), g = (uint32_t)min(255, G * dg), b = (uint32_t)min(255, G * db);
     } else {
         pal(min(255, G * (d - K)), r, g, b);
-        const uint32_t grey = (uint32_t)(((77 * ar + 150 * ag + 29 * ab + 128) >> 8) >> 2);
-        if (d <= K) r = g = b = grey;
+        if (d <= K) r = g = b = dim_grey(ar, ag, ab);
     }
     return d;
 }
@@ -259,11 +251,6 @@ template <int MODE, bool SIDE>
 void launch_stream(bool vec, dim3 grid, hipStream_t s, const uint8_t* a, const uint8_t* b, int H, int W, int G, int K, uint8_t* out, avx_diff_rec* rec) {
     if (vec) hipLaunchKernelGGL((k_diff_stream<MODE, SIDE, true>), grid, dim3(kThreads), 0, s, a, b, H, W, G, K, out, rec);
     else hipLaunchKernelGGL((k_diff_stream<MODE, SIDE, false>), grid, dim3(kThreads), 0, s, a, b, H, W, G, K, out, rec);
-}
-
-bool overlaps(const void* p, size_t np, const void* q, size_t nq) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + nq && b < a + np;
 }
 
 }  // namespace

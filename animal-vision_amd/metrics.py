@@ -15,7 +15,11 @@ frame_metrics_ms_launch / frame_metrics_ms_device return it beside the FrameMetr
 
 Difference maps (csrc/diff_map.hip) say where the frames differ: diff_map_launch enqueues the per-pixel map ("abs",
 "heat" or "ssim"; alone or A | B | map side by side) and a DiffRecord per frame, diff_map and ssim_map take arrays.
-python -m animal_vision_amd.diff is the command built on them."""
+python -m animal_vision_amd.diff is the command built on them.
+
+Colour difference maps (csrc/delta_e.hip) say how far apart the frames are in perceptual units: CIEDE2000 in CIELAB per
+pixel.  delta_e_launch enqueues the float32 values, the map ("heat" or "plain"; alone or A | B | map) and a DeltaE record per frame;
+delta_e, delta_e_map and delta_e_values take arrays.  python -m animal_vision_amd.deltae is the command built on them."""
 from __future__ import annotations
 
 import ctypes
@@ -25,7 +29,8 @@ from typing import List, Optional
 
 import numpy as np
 
-from ._lib import AVX_DIFF_LAYOUTS, AVX_DIFF_MODES, AVX_METRICS_MAX_FRAMES, AVX_PIX_FMTS, FrameMetricsRecord, MsSsimRecord, PlaneMetricsRecord, lib
+from ._lib import AVX_DELTA_E_LAYOUTS, AVX_DELTA_E_MODES, AVX_DIFF_LAYOUTS, AVX_DIFF_MODES, AVX_METRICS_MAX_FRAMES, AVX_PIX_FMTS, FrameMetricsRecord, MsSsimRecord, PlaneMetricsRecord, lib
+from ._lib import DeltaERecord as DeltaERecordStruct
 from ._lib import DiffRecord as DiffRecordStruct
 from .runtime import Context, DeviceBuffer, get_context
 
@@ -616,3 +621,154 @@ def ssim_map(a, b, *, ctx: Optional[Context] = None) -> np.ndarray:
     a, b, _ = check_pair(a, b)
     check_diff_options("ssim", None, 1, "map", a.shape[1], a.shape[2])
     return _diff_chunks(a, b, "ssim", None, 1, "map", ctx, True)[2]
+
+
+# ------------------------------------------------------------------------------------------------ colour difference maps
+DELTA_E_RECORD_BYTES = ctypes.sizeof(DeltaERecordStruct)  # hist[256] uint32, sum double, max_de float, max_x, max_y, beyond uint32
+_DELTA_E_DTYPE = np.dtype([("hist", np.uint32, (256,)), ("sum", np.float64), ("max_de", np.float32), ("max_x", np.uint32), ("max_y", np.uint32),
+                           ("beyond", np.uint32)])
+assert _DELTA_E_DTYPE.itemsize == DELTA_E_RECORD_BYTES == 1048
+DELTA_E_MODES, DELTA_E_LAYOUTS = tuple(AVX_DELTA_E_MODES), tuple(AVX_DELTA_E_LAYOUTS)
+DELTA_E_DEFAULT_GAIN = 10.0
+DELTA_E_DEFAULT_THRESHOLD = 1.0  # about one just-noticeable difference
+
+
+class DeltaE:
+    """One frame's record of a colour difference map: hist[k] = pixels with min(255, floor(2 dE)) == k (bins 0.5 wide, the last one
+    open), sum = the float64 sum of the pixels' float32 dE, max_de = the largest with (max_x, max_y) the first pixel in raster order
+    that attains it ((0, 0) when it is 0), beyond = pixels with dE above the threshold.  mean and percentile follow here."""
+
+    __slots__ = ("hist", "sum", "max_de", "max_x", "max_y", "beyond")
+
+    def __init__(self, hist, sum, max_de, max_x, max_y, beyond):  # noqa: A002  (the record's field is called sum)
+        h = np.asarray(hist)
+        if h.shape != (256,):
+            raise ValueError(f"hist holds 256 bins (got {h.shape})")
+        self.hist = h.astype(np.uint64)
+        self.sum, self.max_de = float(sum), float(max_de)
+        self.max_x, self.max_y, self.beyond = int(max_x), int(max_y), int(beyond)
+
+    @property
+    def pixels(self) -> int:
+        """H * W."""
+        return int(self.hist.sum())
+
+    @property
+    def mean(self) -> float:
+        n = self.pixels
+        return self.sum / n if n else 0.0
+
+    def percentile(self, q: float) -> float:
+        """The upper edge (k + 1) / 2 of the first bin k whose cumulative count reaches ceil(q H W), 0 < q <= 1; where that is the
+        open last bin, max_de."""
+        if not 0.0 < q <= 1.0:
+            raise ValueError(f"q must be above 0 and at most 1 (got {q!r})")
+        need = math.ceil(q * self.pixels)
+        k = int(np.searchsorted(np.cumsum(self.hist), need, side="left"))
+        return self.max_de if k >= 255 else (k + 1) / 2.0
+
+    def _key(self):
+        return self.hist.tobytes(), np.float64(self.sum).tobytes(), np.float32(self.max_de).tobytes(), self.max_x, self.max_y, self.beyond
+
+    def __eq__(self, other):
+        if not isinstance(other, DeltaE):
+            return NotImplemented
+        return self._key() == other._key()
+
+    def __repr__(self):
+        return f"DeltaE(mean={self.mean:.4f}, max_de={self.max_de:.4f}, at=({self.max_x}, {self.max_y}), beyond={self.beyond})"
+
+
+def check_delta_e_options(mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map"):
+    """(gain, threshold) as the numbers the library takes -- the default gain (10) when None -- after the checks of avx_delta_e_u8
+    that need no device; ValueError naming the option otherwise."""
+    if mode not in AVX_DELTA_E_MODES:
+        raise ValueError(f"mode must be one of {', '.join(AVX_DELTA_E_MODES)} (got {mode!r})")
+    if layout not in AVX_DELTA_E_LAYOUTS:
+        raise ValueError(f"layout must be one of {', '.join(AVX_DELTA_E_LAYOUTS)} (got {layout!r})")
+    gain = DELTA_E_DEFAULT_GAIN if gain is None else gain
+    if isinstance(gain, bool) or not isinstance(gain, numbers.Real) or not (math.isfinite(gain) and 0.0 < gain <= 255.0):
+        raise ValueError(f"gain must be above 0 and at most 255 (got {gain!r})")
+    if isinstance(threshold, bool) or not isinstance(threshold, numbers.Real) or not (math.isfinite(threshold) and threshold >= 0.0):
+        raise ValueError(f"threshold must be finite and at least 0 (got {threshold!r})")
+    return float(gain), float(threshold)
+
+
+def delta_e_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_map: Optional[DeviceBuffer],
+                   d_rec: DeviceBuffer, *, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map",
+                   d_float: Optional[DeviceBuffer] = None, stream=None) -> None:
+    """Enqueue the colour difference of n_frames frames on `stream`: d_rec takes n_frames records of DELTA_E_RECORD_BYTES
+    (delta_e_records_from_bytes reads them); d_map, when not None, n_frames frames of H x W x 3 (layout "map") or H x 3W x 3 ("side":
+    A | B | map); d_float, when not None, the float32 dE of every pixel, n_frames x H x W.  Nothing is downloaded and nothing waits."""
+    _check_call(n_frames, H, W, d_a, d_b)
+    g, t = check_delta_e_options(mode, gain, threshold, layout)
+    if d_rec.nbytes < n_frames * DELTA_E_RECORD_BYTES:
+        raise ValueError(f"{n_frames} records need {n_frames * DELTA_E_RECORD_BYTES} bytes; the buffer holds {d_rec.nbytes}")
+    need = n_frames * H * W * 3 * (3 if layout == "side" else 1)
+    if d_map is not None and d_map.nbytes < need:
+        raise ValueError(f"{n_frames} {layout} frames need {need} bytes; the buffer holds {d_map.nbytes}")
+    if d_float is not None and d_float.nbytes < n_frames * H * W * 4:
+        raise ValueError(f"the values of {n_frames} frames need {n_frames * H * W * 4} bytes; the buffer holds {d_float.nbytes}")
+    ctx._check(lib.avx_delta_e_u8(ctx._h, d_a.ptr, d_b.ptr, int(n_frames), int(H), int(W), AVX_DELTA_E_MODES[mode], g, t, AVX_DELTA_E_LAYOUTS[layout],
+                                  None if d_map is None else d_map.ptr, d_rec.ptr, None if d_float is None else d_float.ptr, ctx._s(stream)))
+
+
+def delta_e_records_from_bytes(buf: np.ndarray, n_frames: int) -> List[DeltaE]:
+    """n_frames downloaded records (uint8) -> DeltaE."""
+    recs = np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n_frames * DELTA_E_RECORD_BYTES], dtype=_DELTA_E_DTYPE)
+    return [DeltaE(r["hist"], r["sum"], r["max_de"], r["max_x"], r["max_y"], r["beyond"]) for r in recs]
+
+
+def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_float):
+    """delta_e, delta_e_map and delta_e_values: the stack in chunks of at most 16 frames -> (maps or None, records, values or None)."""
+    N, H, W = a.shape[:3]
+    ctx = ctx or get_context()
+    chunk = min(N, MAX_FRAMES)
+    wide = 3 if layout == "side" else 1
+    d_a, d_b, d_rec = ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * DELTA_E_RECORD_BYTES)
+    d_map = ctx.malloc(chunk * H * W * 3 * wide) if with_map else None
+    d_val = ctx.malloc(chunk * H * W * 4) if with_float else None
+    maps = np.empty((N, H, W * wide, 3), np.uint8) if with_map else None
+    vals = np.empty((N, H, W), np.float32) if with_float else None
+    recs: List[DeltaE] = []
+    try:
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            ctx.upload(a[i : i + n], d_a)
+            ctx.upload(b[i : i + n], d_b)
+            delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_float=d_val)
+            if with_map:
+                ctx.download(d_map, (n, H, W * wide, 3), np.uint8, out=maps[i : i + n])
+            recs += delta_e_records_from_bytes(ctx.download(d_rec, (n * DELTA_E_RECORD_BYTES,), np.uint8), n)
+            if with_float:
+                ctx.download(d_val, (n, H, W), np.float32, out=vals[i : i + n])
+    finally:
+        for d in (d_a, d_b, d_rec, d_map, d_val):
+            if d is not None:
+                d.free()
+    return maps, recs, vals
+
+
+def delta_e(a, b, *, threshold=DELTA_E_DEFAULT_THRESHOLD, ctx: Optional[Context] = None):
+    """a, b: uint8 sRGB H x W x 3 -> the DeltaE record, or N x H x W x 3 -> a list of N; no map is computed.  Uploaded in chunks of at
+    most 16 frames.  ValueError for a bad option or shape before any device work."""
+    a, b, batched = check_pair(a, b)
+    check_delta_e_options("heat", None, threshold, "map")
+    recs = _delta_e_chunks(a, b, "heat", None, threshold, "map", ctx, False, False)[1]
+    return recs if batched else recs[0]
+
+
+def delta_e_map(a, b, *, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map", ctx: Optional[Context] = None):
+    """a, b: uint8 sRGB H x W x 3 -> (the map, uint8 H x W x 3 -- H x 3W x 3 with layout "side" --, its DeltaE record), or
+    N x H x W x 3 -> (N maps, a list of N records).  mode: "heat" or "plain"; gain: 10 when None."""
+    a, b, batched = check_pair(a, b)
+    check_delta_e_options(mode, gain, threshold, layout)
+    maps, recs, _ = _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, True, False)
+    return (maps, recs) if batched else (maps[0], recs[0])
+
+
+def delta_e_values(a, b, *, ctx: Optional[Context] = None) -> np.ndarray:
+    """a, b: uint8 sRGB H x W x 3 -> the CIEDE2000 difference of every pixel, float32 H x W; N x H x W x 3 -> N x H x W."""
+    a, b, batched = check_pair(a, b)
+    vals = _delta_e_chunks(a, b, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True)[2]
+    return vals if batched else vals[0]

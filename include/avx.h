@@ -494,6 +494,48 @@ typedef struct { uint32_t max_d, max_x, max_y, beyond; } avx_diff_rec;
 int avx_diff_map_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int mode, float gain, int threshold,
                     int layout, uint8_t* out_hwc, avx_diff_rec* rec_dev, float* ssim_map_dev, void* stream);
 
+/* Colour difference maps (csrc/delta_e.hip): how far apart, in perceptual units, the pixels of two batches of uint8
+ * sRGB frames are -- CIEDE2000 (dE00) in CIELAB under D65 -- as float32 values, as a picture per frame and as a record per frame. */
+enum avx_delta_e_mode { AVX_DELTA_E_HEAT = 0, AVX_DELTA_E_PLAIN = 1 };
+enum avx_delta_e_layout { AVX_DELTA_E_MAP = 0, AVX_DELTA_E_SIDE = 1 };
+typedef struct avx_delta_e_rec {
+    uint32_t hist[256]; /* pixels with min(255, floor(2 dE)) == k: bins 0.5 wide, the last one open; sums to H*W */
+    double sum;         /* the sum of the float32 dE of every pixel, in a fixed order */
+    float max_de;       /* the largest dE of the frame */
+    uint32_t max_x, max_y; /* the first pixel in raster order that attains it; (0, 0) when max_de is 0 */
+    uint32_t beyond;    /* pixels with dE > threshold */
+} avx_delta_e_rec;
+
+/* a_hwc, b_hwc: n_frames contiguous H x W x 3 uint8 frames on the device; rec_dev: n_frames records on the device (8-byte aligned);
+ * map_out: NULL (records only), or n_frames frames of H x W x 3 (AVX_DELTA_E_MAP) or H x 3W x 3 (AVX_DELTA_E_SIDE: A | B | map,
+ * written by the same launch); de_out: NULL, or the float32 dE of every pixel, [frame][H][W] (4-byte aligned).  Asynchronous on
+ * `stream`.  1 <= n_frames <= 16, H*W < 2^32.  All arithmetic is float32.
+ * Lab of a pixel (r8, g8, b8): lin(code) is the sRGB decode of c = code / 255 -- c / 12.92 where c <= 0.04045, else
+ * ((c + 0.055) / 1.055)^2.4 --, a 256-entry float32 table whose entries are the float64 values rounded once.  M' is the sRGB -> XYZ
+ * (D65) matrix (0.4124564 0.3575761 0.1804375; 0.2126729 0.7151522 0.0721750; 0.0193339 0.1191920 0.9503041) with every row divided by
+ * its own sum, so that white is (1, 1, 1).  With (r, g, b) = lin of the codes, t_i = g + M'_i0 (r - g) + M'_i2 (b - g) for i = X, Y,
+ * Z: the form anchored on green is part of the definition -- r = g = b gives t_X = t_Y = t_Z exactly, so greys have a = b = 0
+ * exactly; the plain product M' (r, g, b) leaves a share of the greys with a tiny chroma of random hue.  f(t) = cbrt(t) where
+ * t > (6/29)^3, else t / (3 (6/29)^2) + 4/29;  L = 116 f_Y - 16, a = 500 (f_X - f_Y), b = 200 (f_Y - f_Z).
+ * dE00 of two Lab triples: Sharma, Wu, Dalal 2005 with k_L = k_C = k_H = 1 and that paper's conventions: h' = atan2(b, a') mod 360
+ * degrees and 0 where a' = b = 0; dh' = 0 where C'1 C'2 = 0, else folded into (-180, 180]; the mean hue is h'1 + h'2 where
+ * C'1 C'2 = 0, (h'1 + h'2) / 2 where |h'1 - h'2| <= 180, otherwise (sum + 360) / 2 where the sum is below 360, else (sum - 360) / 2;
+ * the radicand is clamped at 0 before the root.  Two pixels of equal codes give exactly 0.
+ * The map, with G = gain (0 < G <= 255), T = threshold (finite, >= 0) and pal and the dim grey those of avx_diff_map_u8:
+ *   AVX_DELTA_E_HEAT:  dE <= T: (g, g, g), g = ((77 a_r + 150 a_g + 29 a_b + 128) >> 8) >> 2;  dE > T: pal(v),
+ *                      v = min(255, floor(G (dE - T) + 0.5)).
+ *   AVX_DELTA_E_PLAIN: pal(min(255, floor(G dE + 0.5))) everywhere; identical frames give a black map.
+ * The quantiser is float32 with one rounding per operation: the subtraction, the product and the sum with 0.5 are each rounded, the
+ * multiply and the add are NOT fused (__fmul_rn, __fadd_rn).
+ * The record is written whatever map_out is.  Counts are integers; the sum is formed from per-workgroup float64 partials (a
+ * workgroup owns 4096 consecutive pixels, a thread adds its pixels in raster order) added in index order, without float atomics: a
+ * frame's record, map and values do not depend on its batch, its place in the batch, the alignment of the buffers or the run.
+ * AVX_ERR_INVALID (avx_last_error starts with this function's name) for a NULL ctx, input or record pointer, n_frames outside 1..16,
+ * a bad size, mode or layout, a gain outside (0, 255] or not finite, a negative or non-finite threshold, a misaligned rec_dev or
+ * de_out, and map_out overlapping an input; nothing is launched or written then. */
+int avx_delta_e_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int mode, float gain, float threshold,
+                   int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

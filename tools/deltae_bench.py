@@ -1,0 +1,123 @@
+"""Time of the colour difference kernel.  Not part of bench.py.
+
+  python tools/deltae_bench.py kernel [--reps 7]
+      avx_delta_e_u8 on frames resident on the device, 4K and 1080p, batches of 8: records only (no map), the heat map, the heat map
+      side by side, and records only on a pair whose upper half is identical (those pixels are 0 by definition and skip the
+      arithmetic), interleaved in one process with avx_frame_metrics_u8(with_ssim = 1) on the same frames -- per repetition each form
+      once, each between its own pair of stream events (the record memset and the final launch included), after one warm-up call of
+      each.  One JSON line per (size, form): median (min-max) in us per frame, ns per pixel, and the ratio to the SSIM record kernel.
+      The frames are noise against the same noise +-2 codes: fewer than 1 % of the pixels are equal, so every wave does the arithmetic.
+  python tools/deltae_bench.py command [--frames 32] [--reps 3] [--dir DIR]
+      Two 4K nv12 files of `frames` frames in DIR (default: /dev/shm when there is one, so they are read from and written to memory)
+      through python -m animal_vision_amd.deltae's main(), --batch 8 --depth 2: no OUT (statistics only), heat into a raw nv12 file (the
+      map encoded on the device, 1.5 B/px back across PCIe), heat side by side into nv12, and heat into a .npy file (RGB, 3 B/px
+      back): frames per second of the whole command (read, upload, decode, dE, encode, download, write), `reps` runs each after one
+      warm-up run."""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+SIZES = {"1080p": (1080, 1920), "4k": (2160, 3840)}
+
+
+def _pair(n, H, W, seed=0):
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8)
+    b = np.clip(a.astype(np.int16) + rng.integers(-2, 3, a.shape, dtype=np.int16), 0, 255).astype(np.uint8)
+    return a, b
+
+
+def kernel(args):
+    from animal_vision_amd.metrics import DELTA_E_RECORD_BYTES, RECORD_BYTES, delta_e_launch, frame_metrics_launch
+    from animal_vision_amd.runtime import get_context
+
+    ctx, n = get_context(), 8
+    for name, (H, W) in (("4k", SIZES["4k"]), ("1080p", SIZES["1080p"])):
+        a, b = _pair(n, H, W)
+        half = b.copy()
+        half[:, : H // 2] = a[:, : H // 2]
+        d_a, d_b, d_half, d_out = ctx.upload(a), ctx.upload(b), ctx.upload(half), ctx.malloc(3 * n * H * W * 3)
+        d_rec, d_metrics = ctx.malloc(n * DELTA_E_RECORD_BYTES), ctx.malloc(n * RECORD_BYTES)
+
+        def route(d_other, d_map, layout):
+            return lambda: delta_e_launch(ctx, d_a, d_other, n, H, W, d_map, d_rec, mode="heat", layout=layout)
+
+        forms = [("records", route(d_b, None, "map")), ("heat map", route(d_b, d_out, "map")), ("heat side", route(d_b, d_out, "side")),
+                 ("records, upper half identical", route(d_half, None, "map")),
+                 ("ssim record", lambda: frame_metrics_launch(ctx, d_a, d_b, n, H, W, d_metrics, ssim=True))]
+        times = [[] for _ in forms]
+        for _, r in forms:  # warm-up: code objects are loaded and the workspaces are sized here
+            r()
+        ctx.sync()
+        for _ in range(args.reps):
+            for k, (_, r) in enumerate(forms):
+                ctx.timer_start()
+                r()
+                times[k].append(ctx.timer_stop() * 1e3 / n)
+        record = float(np.median(times[-1]))
+        for (form, _), t in zip(forms, times):
+            med = float(np.median(t))
+            print(json.dumps({"size": name, "form": form, "batch": n, "reps": args.reps, "us_per_frame_median": round(med, 1), "us_per_frame_min": round(min(t), 1),
+                              "us_per_frame_max": round(max(t), 1), "ns_per_px": round(med * 1e3 / (H * W), 4), "over_ssim_record_kernel": round(med / record, 2)}),
+                  flush=True)
+        for d in (d_a, d_b, d_half, d_out, d_rec, d_metrics):
+            d.free()
+
+
+def command(args):
+    from animal_vision_amd import deltae
+    from animal_vision_amd.yuv import rgb_to_yuv
+
+    H, W = SIZES["4k"]
+    base = args.dir or ("/dev/shm" if os.path.isdir("/dev/shm") else None)
+    with tempfile.TemporaryDirectory(dir=base) as d:
+        a, b = _pair(4, H, W)
+        pa, pb = [rgb_to_yuv(f, pix_fmt="nv12") for f in a], [rgb_to_yuv(f, pix_fmt="nv12") for f in b]
+        for path, pay in ((os.path.join(d, "a.yuv"), pa), (os.path.join(d, "b.yuv"), pb)):
+            with open(path, "wb") as f:
+                for i in range(args.frames):
+                    f.write(pay[i % len(pay)].tobytes())
+        argv = [os.path.join(d, "a.yuv"), os.path.join(d, "b.yuv")]
+        opts = ["--pix-fmt", "nv12", "--size", f"{W}x{H}", "--batch", "8", "--csv", os.path.join(d, "de.csv")]
+        for out, extra in ((None, []), ("out.yuv", ["--depth", "2"]), ("out.yuv", ["--depth", "2", "--layout", "side"]), ("out.npy", ["--depth", "2"])):
+            fps = []
+            for rep in range(args.reps + 1):
+                t0 = time.perf_counter()
+                with contextlib.redirect_stderr(io.StringIO()):
+                    status = deltae.main(argv + ([os.path.join(d, out)] if out else []) + opts + extra)
+                dt = time.perf_counter() - t0
+                assert status == 0, status
+                if out:
+                    os.remove(os.path.join(d, out))
+                if rep:  # the first run is the warm-up
+                    fps.append(args.frames / dt)
+            print(json.dumps({"command": "deltae", "size": "4k", "pix_fmt": "nv12", "frames": args.frames, "batch": 8, "depth": 2,
+                              "sink": "none" if out is None else ("nv12" if out.endswith(".yuv") else "npy"), "options": extra, "reps": args.reps,
+                              "fps_median": round(float(np.median(fps)), 1), "fps_min": round(min(fps), 1), "fps_max": round(max(fps), 1)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    k = sub.add_parser("kernel")
+    k.add_argument("--reps", type=int, default=7)
+    c = sub.add_parser("command")
+    c.add_argument("--frames", type=int, default=32)
+    c.add_argument("--reps", type=int, default=3)
+    c.add_argument("--dir", default=None)
+    args = ap.parse_args()
+    {"kernel": kernel, "command": command}[args.cmd](args)
+
+
+if __name__ == "__main__":
+    main()

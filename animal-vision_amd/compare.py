@@ -29,19 +29,17 @@ summary, and --min-ms-ssim X as a limit (it implies --ms-ssim).  Five scales nee
 from __future__ import annotations
 
 import argparse
-import itertools
 import math
 import os
 import sys
 import time
 from typing import Iterator, Optional, Sequence
 
-import numpy as np
-
 from .metrics import (MS_MIN_SIDE, MS_RECORD_BYTES, PLANE_RECORD_BYTES, RECORD_BYTES, FrameMetrics, MsSsim, PlaneMetrics, _psnr,
                       check_plane_formats, frame_metrics_launch, frame_metrics_ms_launch, ms_records_from_bytes, plane_metrics_launch,
                       plane_records_from_bytes, records_from_bytes)
-from .video import _size_arg, add_input_options, add_output_options, check_io_options, check_raw_options
+from .pairs import add_inputs, check_inputs, check_stdin, exit_status, named_size, num, opened, stream_pairs
+from .video import add_input_options, add_output_options
 
 CSV_HEADER = "frame,psnr_r,psnr_g,psnr_b,psnr,ssim_r,ssim_g,ssim_b,ssim,max_abs,beyond1"
 CSV_HEADER_YUV = "frame,psnr_y,psnr_u,psnr_v,psnr,ssim_y,ssim_u,ssim_v,ssim,max_abs,beyond1"
@@ -49,28 +47,24 @@ CSV_MS_COLUMNS = ",ms_ssim_r,ms_ssim_g,ms_ssim_b,ms_ssim"  # --ms-ssim: behind C
 _OUTPUT_ONLY = (("--out-pix-fmt", "out_pix_fmt"), ("--out-matrix", "out_matrix"), ("--depth", "depth"))
 
 
-def _num(v: float) -> str:
-    return "inf" if math.isinf(v) else ("nan" if math.isnan(v) else f"{v:.6f}")
-
-
 def format_row(index: int, m: FrameMetrics) -> str:
     """The CSV line of frame `index`."""
     p = m.psnr_channels
-    return ",".join([str(index), _num(p[0]), _num(p[1]), _num(p[2]), _num(m.psnr), _num(m.ssim[0]), _num(m.ssim[1]), _num(m.ssim[2]),
-                     _num(m.ssim_mean), str(m.max_abs), f"{m.share_beyond(1):.6g}"])
+    return ",".join([str(index), num(p[0]), num(p[1]), num(p[2]), num(m.psnr), num(m.ssim[0]), num(m.ssim[1]), num(m.ssim[2]),
+                     num(m.ssim_mean), str(m.max_abs), f"{m.share_beyond(1):.6g}"])
 
 
 def format_row_planes(index: int, m: PlaneMetrics) -> str:
     """The CSV line of frame `index` with --planes yuv."""
     p = m.psnr_planes
-    return ",".join([str(index), _num(p[0]), _num(p[1]), _num(p[2]), _num(m.psnr), _num(m.ssim[0]), _num(m.ssim[1]), _num(m.ssim[2]),
-                     _num(m.ssim_mean), str(m.max_abs), f"{m.share_beyond(1):.6g}"])
+    return ",".join([str(index), num(p[0]), num(p[1]), num(p[2]), num(m.psnr), num(m.ssim[0]), num(m.ssim[1]), num(m.ssim[2]),
+                     num(m.ssim_mean), str(m.max_abs), f"{m.share_beyond(1):.6g}"])
 
 
 def format_ms_columns(ms: MsSsim) -> str:
     """What --ms-ssim appends to the CSV line of a frame."""
     c = ms.ms_ssim_channels
-    return "," + ",".join([_num(c[0]), _num(c[1]), _num(c[2]), _num(ms.ms_ssim)])
+    return "," + ",".join([num(c[0]), num(c[1]), num(c[2]), num(ms.ms_ssim)])
 
 
 def _is_y4m_file(path: str) -> bool:
@@ -106,15 +100,8 @@ def _check_ms_ssim(ap: argparse.ArgumentParser, args: argparse.Namespace) -> Non
         ap.error("--ms-ssim builds on the SSIM record that --no-ssim skips: give one of the two")
     if args.planes == "yuv":
         ap.error("--ms-ssim compares RGB frames: --planes yuv is not supported with it")
-    size = args.scale if args.scale is not None else args.size  # (W, H) where the command line states it
-    if size is None:
-        for path in (args.a, args.b):
-            if path.startswith("synthetic:"):
-                try:
-                    size = _size_arg(path.split(":")[1])
-                except (IndexError, argparse.ArgumentTypeError):
-                    size = None
-                break
+    # (W, H) where the command line states it: --scale, --size, or the first synthetic: input
+    size = args.scale or named_size(args, args.a if args.a.startswith("synthetic:") else args.b)
     if size is not None and (size[0] < MS_MIN_SIDE or size[1] < MS_MIN_SIDE):
         ap.error(f"--ms-ssim: five scales need frames of at least {MS_MIN_SIDE}x{MS_MIN_SIDE}; these are {size[0]}x{size[1]}")
 
@@ -127,31 +114,20 @@ class _CompareParser(argparse.ArgumentParser):
                 self.error(f"{flag} belongs to a command that writes video: compare writes none")
         if args.no_ssim and args.min_ssim is not None:
             self.error("--min-ssim needs the SSIM that --no-ssim skips")
-        if args.a == "-" and args.b == "-":
-            self.error("A and B cannot both be stdin")
+        check_stdin(self, args)
         if hasattr(args, "min_ms_ssim"):
             args.ms_ssim = True
         if getattr(args, "ms_ssim", False):
             _check_ms_ssim(self, args)
         if args.planes == "yuv":
             _check_planes_yuv(self, args)
-        args.input = args.a  # what check_io_options reads the source size of a synthetic: input from
-        check_io_options(self, args)
-        check_raw_options(self, args)
-        if args.scale is not None and args.size is None and args.b.startswith("synthetic:"):
-            try:
-                src = _size_arg(args.b.split(":")[1])
-            except (IndexError, argparse.ArgumentTypeError):
-                src = None
-            if src is not None and (args.scale[0] > src[0] or args.scale[1] > src[1]):
-                self.error(f"--scale {args.scale[0]}x{args.scale[1]} enlarges the {src[0]}x{src[1]} source: --scale only reduces")
+        check_inputs(self, args)
         return args
 
 
 def build_parser() -> argparse.ArgumentParser:
     ap = _CompareParser(prog="compare", description="PSNR, SSIM and code differences of two videos, frame by frame, on the device.")
-    ap.add_argument("a", metavar="A", help=".y4m file, raw video (--pix-fmt), synthetic:<W>x<H>:<n>[:kind], .npy or an image directory")
-    ap.add_argument("b", metavar="B", help="the same forms; the input options apply to both")
+    add_inputs(ap)
     add_input_options(ap)
     add_output_options(ap)
     ap.set_defaults(batch=8, depth=None)
@@ -182,11 +158,11 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
 def violation(args, m: FrameMetrics, ms: Optional[MsSsim] = None) -> Optional[str]:
     """What frame record `m` (and, with --ms-ssim, `ms`) violates of the command line's limits, None when nothing."""
     if args.min_psnr is not None and m.psnr < args.min_psnr:
-        return f"PSNR {_num(m.psnr)} dB is below --min-psnr {args.min_psnr:g}"
+        return f"PSNR {num(m.psnr)} dB is below --min-psnr {args.min_psnr:g}"
     if args.min_ssim is not None and not m.ssim_mean >= args.min_ssim:
-        return f"SSIM {_num(m.ssim_mean)} is below --min-ssim {args.min_ssim:g}"
+        return f"SSIM {num(m.ssim_mean)} is below --min-ssim {args.min_ssim:g}"
     if ms is not None and getattr(args, "min_ms_ssim", None) is not None and not ms.ms_ssim >= args.min_ms_ssim:
-        return f"MS-SSIM {_num(ms.ms_ssim)} is below --min-ms-ssim {args.min_ms_ssim:g}"
+        return f"MS-SSIM {num(ms.ms_ssim)} is below --min-ms-ssim {args.min_ms_ssim:g}"
     if args.max_abs is not None and m.max_abs > args.max_abs:
         return f"largest difference {m.max_abs} is above --max-abs {args.max_abs}"
     if args.max_beyond1 is not None and m.share_beyond(1) > args.max_beyond1:
@@ -195,196 +171,35 @@ def violation(args, m: FrameMetrics, ms: Optional[MsSsim] = None) -> Optional[st
 
 
 # ------------------------------------------------------------------------------------------------ the device loop
-def _renderer(args, path: str):
-    from .renderers import VideoRenderer
-
-    if getattr(args, "planes", "rgb") == "yuv":
-        raw = not _is_y4m_file(path) and args.pix_fmt is not None
-        return VideoRenderer(read_path=path, write_path=None, pix_fmt=args.pix_fmt if raw else None, size=args.size if raw else None)
-    return VideoRenderer(read_path=path, write_path=None, matrix=args.matrix, range=args.range, pix_fmt=args.pix_fmt, size=args.size,
-                         transfer=args.transfer, tonemap=args.tonemap, peak_nits=args.peak_nits, sdr_white=args.sdr_white, scale=args.scale)
-
-
-def _open(args, path: str):
-    """The opened renderer of `path` and the (H, W) of the frames it will be compared at."""
-    vr = _renderer(args, path)
-    vr.open()
-    hw = vr.out_hw
-    if hw is None:  # synthetic:, .npy or an image directory: peek at the first frame, then start over
-        first = vr.get_image()
-        hw = None if first is None else tuple(first.shape[:2])
-        vr.close()
-        vr = _renderer(args, path)
-        vr.open()
-    return vr, hw
-
-
-class _Side:
-    """One input: its staging (pinned) and device buffers, one of each per buffer set."""
-
-    def __init__(self, ctx, vr, H: int, W: int, batch: int, sets: int):
-        from .yuv import frame_size
-
-        self.ctx, self.vr, self.H, self.W = ctx, vr, H, W
-        self.payload = vr.yuv_hw is not None and vr.scale is None and vr.transfer is None
-        self.fmt = vr.yuv_pix_fmt  # None: I420 (.y4m)
-        self.unit = frame_size(self.fmt or "yuv420p", H, W) if self.payload else H * W * 3
-        self.host = [ctx.pinned((batch, self.unit), np.uint8) for _ in range(sets)]
-        self.d_rgb = [ctx.malloc(batch * H * W * 3) for _ in range(sets)]
-        self.d_in = [ctx.malloc(batch * self.unit) for _ in range(sets)] if self.payload else self.d_rgb
-
-    def fill(self, k: int, limit: int) -> int:
-        """Read up to `limit` frames into set k's staging; how many came."""
-        n = 0
-        while n < limit:
-            f = self.vr.get_yuv() if self.payload else self.vr.get_image()
-            if f is None:
-                break
-            f = np.asarray(f)
-            if not self.payload and (f.dtype != np.uint8 or f.shape != (self.H, self.W, 3)):
-                raise SystemExit(f"compare: {self.vr.read_path}: frame {self.vr.last_index} is {f.dtype} {f.shape}, not uint8 {(self.H, self.W, 3)}")
-            self.host[k].array[n] = f.reshape(-1)
-            n += 1
-        return n
-
-    def enqueue(self, k: int, n: int, stream) -> None:
-        from ._lib import lib
-        from .yuv import i420_to_rgb_device, yuv_to_rgb_device
-
-        ctx = self.ctx
-        ctx._check(lib.avx_memcpy_h2d(ctx._h, self.d_in[k].ptr, self.host[k].ptr, n * self.unit, stream))
-        if self.payload and self.fmt is None:
-            i420_to_rgb_device(ctx, self.d_in[k], self.d_rgb[k], n, self.H, self.W, matrix=self.vr.matrix, range=self.vr.yuv_range, stream=stream)
-        elif self.payload:
-            yuv_to_rgb_device(ctx, self.fmt, self.d_in[k], self.d_rgb[k], n, self.H, self.W, matrix=self.vr.matrix, range=self.vr.yuv_range,
-                              stream=stream)
-
-    def free(self) -> None:
-        for b in self.d_rgb + (self.d_in if self.payload else []):
-            b.free()
-        for h in self.host:
-            h.free()
-
-
-class _PlaneSide:
-    """One input of --planes yuv: payloads only, staged (pinned) and uploaded as they are stored; one buffer of each per set."""
-
-    def __init__(self, ctx, vr, H: int, W: int, batch: int, sets: int):
-        from .yuv import frame_size
-
-        if vr.yuv_hw is None:
-            raise SystemExit(f"compare: {vr.read_path}: --planes yuv needs a .y4m or raw video input")
-        self.ctx, self.vr = ctx, vr
-        self.fmt = vr.yuv_pix_fmt or "yuv420p"
-        self.unit = frame_size(self.fmt, H, W)
-        self.host = [ctx.pinned((batch, self.unit), np.uint8) for _ in range(sets)]
-        self.d_in = [ctx.malloc(batch * self.unit) for _ in range(sets)]
-
-    def fill(self, k: int, limit: int) -> int:
-        n = 0
-        while n < limit:
-            f = self.vr.get_yuv()
-            if f is None:
-                break
-            self.host[k].array[n] = np.asarray(f).reshape(-1)
-            n += 1
-        return n
-
-    def enqueue(self, k: int, n: int, stream) -> None:
-        from ._lib import lib
-
-        self.ctx._check(lib.avx_memcpy_h2d(self.ctx._h, self.d_in[k].ptr, self.host[k].ptr, n * self.unit, stream))
-
-    def free(self) -> None:
-        for b in self.d_in:
-            b.free()
-        for h in self.host:
-            h.free()
-
-
 def stream_metrics(args, info: dict) -> Iterator[FrameMetrics]:
     """The records of the common prefix of args.a and args.b, in frame order; with --ms-ssim every item is the pair (FrameMetrics,
-    MsSsim).  info["longer"] names the input ("A" / "B") that had frames left over, when one had."""
-    from ._lib import lib
-    from .runtime import get_context
+    MsSsim).  info["longer"] names the input ("A" / "B") that had frames left over, when one had.  The loop is pairs.stream_pairs."""
+    yuv = getattr(args, "planes", "rgb") == "yuv"
+    ms = bool(getattr(args, "ms_ssim", False))
 
-    va, hwa = _open(args, args.a)
-    vb, hwb = _open(args, args.b)
-    sides = []
-    try:
-        if hwa is not None and hwb is not None and tuple(hwa) != tuple(hwb):
-            raise SystemExit(f"compare: frame sizes differ: A is {hwa[1]}x{hwa[0]}, B is {hwb[1]}x{hwb[0]}")
-        if hwa is None or hwb is None:  # an empty input
-            if hwa is not None or hwb is not None:
-                info["longer"] = "A" if hwa is not None else "B"
-            return
-        H, W = hwa
-        ctx, batch, sets = get_context(), args.batch, 2
-        yuv = getattr(args, "planes", "rgb") == "yuv"
-        ms = bool(getattr(args, "ms_ssim", False))
+    def prepare(H, W):
         if ms and (H < MS_MIN_SIDE or W < MS_MIN_SIDE):
             raise SystemExit(f"compare: --ms-ssim: five scales need frames of at least {MS_MIN_SIDE}x{MS_MIN_SIDE}; these are {W}x{H}")
-        rec_bytes = PLANE_RECORD_BYTES if yuv else RECORD_BYTES
-        side = _PlaneSide if yuv else _Side
-        sides.append(side(ctx, va, H, W, batch, sets))
-        sides.append(side(ctx, vb, H, W, batch, sets))
-        streams = [ctx.stream_create() for _ in range(sets)]
-        d_out = [ctx.malloc(batch * rec_bytes) for _ in range(sets)]
-        h_out = [ctx.pinned((batch * rec_bytes,), np.uint8) for _ in range(sets)]
-        d_ms = [ctx.malloc(batch * MS_RECORD_BYTES) for _ in range(sets)] if ms else []
-        h_ms = [ctx.pinned((batch * MS_RECORD_BYTES,), np.uint8) for _ in range(sets)] if ms else []
-        pending = [0] * sets
 
-        def harvest(k):
-            ctx.sync(streams[k])
-            n, pending[k] = pending[k], 0
+        def enqueue(k, n, stream, sides, outs):
+            a, b = sides
             if yuv:
-                return plane_records_from_bytes(h_out[k].array, n, sides[0].fmt, H, W) if n else []
-            if ms:
-                return list(zip(records_from_bytes(h_out[k].array, n), ms_records_from_bytes(h_ms[k].array, n))) if n else []
-            return records_from_bytes(h_out[k].array, n) if n else []
+                plane_metrics_launch(a.ctx, a.fmt, a.d_in[k], b.d_in[k], n, H, W, outs[0], pix_fmt_b=b.fmt, ssim=not args.no_ssim, stream=stream)
+            elif ms:
+                frame_metrics_ms_launch(a.ctx, a.d_rgb[k], b.d_rgb[k], n, H, W, outs[0], outs[1], stream=stream)
+            else:
+                frame_metrics_launch(a.ctx, a.d_rgb[k], b.d_rgb[k], n, H, W, outs[0], ssim=not args.no_ssim, stream=stream)
 
-        try:
-            i = 0
-            while True:
-                k = i % sets
-                yield from harvest(k)  # the set's previous batch: its buffers are free again afterwards
-                na, nb = sides[0].fill(k, batch), sides[1].fill(k, batch)
-                n = min(na, nb)
-                if n:
-                    for s in sides:
-                        s.enqueue(k, n, streams[k])
-                    if yuv:
-                        plane_metrics_launch(ctx, sides[0].fmt, sides[0].d_in[k], sides[1].d_in[k], n, H, W, d_out[k], pix_fmt_b=sides[1].fmt,
-                                             ssim=not args.no_ssim, stream=streams[k])
-                    elif ms:
-                        frame_metrics_ms_launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, d_out[k], d_ms[k], stream=streams[k])
-                        ctx._check(lib.avx_memcpy_d2h(ctx._h, h_ms[k].ptr, d_ms[k].ptr, n * MS_RECORD_BYTES, streams[k]))
-                    else:
-                        frame_metrics_launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, d_out[k], ssim=not args.no_ssim,
-                                             stream=streams[k])
-                    ctx._check(lib.avx_memcpy_d2h(ctx._h, h_out[k].ptr, d_out[k].ptr, n * rec_bytes, streams[k]))
-                    pending[k] = n
-                i += 1
-                if na != nb:
-                    info["longer"] = "A" if na > nb else "B"
-                if n < batch:
-                    break
-            for j in range(sets):
-                yield from harvest((i + j) % sets)
-        finally:
-            for k in range(sets):
-                ctx.sync(streams[k])
-                ctx.stream_destroy(streams[k])
-            for b in d_out + d_ms:
-                b.free()
-            for h in h_out + h_ms:
-                h.free()
-    finally:
-        for s in sides:
-            s.free()
-        va.close()
-        vb.close()
+        def harvest(n, arrays):
+            if yuv:
+                return plane_records_from_bytes(arrays[0], n, plane_format(args, args.a), H, W)
+            if ms:
+                return list(zip(records_from_bytes(arrays[0], n), ms_records_from_bytes(arrays[1], n)))
+            return records_from_bytes(arrays[0], n)
+
+        return [(PLANE_RECORD_BYTES if yuv else RECORD_BYTES, True)] + ([(MS_RECORD_BYTES, True)] if ms else []), enqueue, harvest
+
+    return stream_pairs(args, info, "compare", prepare, stored=yuv)
 
 
 # ------------------------------------------------------------------------------------------------ the command
@@ -402,12 +217,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     frames, first_bad, worst_abs, min_ssim, sum_ssim = 0, None, 0, math.inf, 0.0
     sse = samples = beyond = 0
     t0 = time.perf_counter()
-    records = stream_metrics(args, info)
-    head = list(itertools.islice(records, 1))  # the inputs are opened and their sizes checked before anything is written
+    records = opened(stream_metrics(args, info))
     out = open(args.csv, "w") if args.csv else sys.stdout
     try:
         out.write((CSV_HEADER_YUV if yuv else CSV_HEADER) + (CSV_MS_COLUMNS if with_ms else "") + "\n")
-        for m in itertools.chain(head, records):
+        for m in records:
             ms = None
             if with_ms:
                 m, ms = m
@@ -441,20 +255,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ssim_txt += f", MS-SSIM mean {sum_ms / frames:.6f} min {min_ms:.6f}"
     if yuv:
         peak = (1 << depth) - 1 if frames else 255
-        psnr_txt = (f"PSNR-Y {_num(_psnr_peak(sse_y, samples_y, peak)) if frames else 'nan'} dB, "
-                    f"PSNR {_num(_psnr_peak(sse, samples, peak)) if frames else 'nan'} dB ({depth if frames else '?'}-bit)")
+        psnr_txt = (f"PSNR-Y {num(_psnr_peak(sse_y, samples_y, peak)) if frames else 'nan'} dB, "
+                    f"PSNR {num(_psnr_peak(sse, samples, peak)) if frames else 'nan'} dB ({depth if frames else '?'}-bit)")
     else:
-        psnr_txt = f"PSNR {_num(_psnr(sse, samples)) if frames else 'nan'} dB"
+        psnr_txt = f"PSNR {num(_psnr(sse, samples)) if frames else 'nan'} dB"
     print(f"compare: {frames} frames, {psnr_txt}, {ssim_txt}, largest difference {worst_abs}, "
           f"beyond +-1 code {beyond / samples if samples else 0.0:.6g}, {frames / dt if dt > 0 else 0.0:.1f} fps", file=sys.stderr)
-    status = 0
-    if info.get("longer") and not args.shortest:
-        print(f"compare: {info['longer']} has more frames than the other input: compared the first {frames} (--shortest accepts that)", file=sys.stderr)
-        status = 2
-    if first_bad is not None:
-        print(f"compare: frame {first_bad[0]}: {first_bad[1]}", file=sys.stderr)
-        status = 1
-    return status
+    return exit_status("compare", args, info, frames, first_bad)
 
 
 if __name__ == "__main__":

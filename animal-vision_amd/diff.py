@@ -30,17 +30,17 @@ i.  For .y4m and raw sinks the maps are encoded on the device and the payload is
 from __future__ import annotations
 
 import argparse
-import itertools
 import sys
 import time
 from typing import Iterator, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .compare import _open, _Side
 from .metrics import (DIFF_DEFAULT_GAIN, DIFF_LAYOUTS, DIFF_MODES, DIFF_RECORD_BYTES, SSIM_WINDOW, DiffRecord, check_diff_options,
                       diff_map_launch, diff_records_from_bytes)
-from .video import _size_arg, add_input_options, add_output_options, check_io_options, check_raw_options
+from .pairs import (add_inputs, check_depth, check_inputs, check_stdin, exit_status, named_size, open_sink, opened, sink_format,  # noqa: F401
+                    stream_map_pairs)
+from .video import add_input_options, add_output_options
 
 CSV_HEADER = "frame,max_d,x,y,beyond"
 
@@ -50,39 +50,20 @@ def format_row(index: int, r: DiffRecord) -> str:
     return f"{index},{r.max_d},{r.max_x},{r.max_y},{r.beyond}"
 
 
-def _named_size(args, path: str) -> Optional[Tuple[int, int]]:
-    """(W, H) of `path`'s frames where the command line states it: --size, or a synthetic: input."""
-    if args.size is not None:
-        return args.size
-    if path.startswith("synthetic:"):
-        try:
-            return _size_arg(path.split(":")[1])
-        except (IndexError, argparse.ArgumentTypeError):
-            return None
-    return None
-
-
 class _DiffParser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         args = super().parse_args(args, namespace)
-        if args.a == "-" and args.b == "-":
-            self.error("A and B cannot both be stdin")
-        if not 1 <= args.depth <= 8:
-            self.error(f"--depth must be 1..8 buffer sets (got {args.depth})")
+        check_stdin(self, args)
+        check_depth(self, args)
         if args.mode != "ssim" and args.gain is not None and not args.gain.is_integer():
             self.error(f"--gain {args.gain:g}: --mode {args.mode} multiplies code differences and takes an integer 1..255")
         try:
             args.gain = check_diff_options(args.mode, args.gain, args.threshold, args.layout)
         except ValueError as e:
             self.error(f"--gain / --threshold: {e}")
-        args.input = args.a  # what check_io_options reads the source size of a synthetic: input from
-        check_io_options(self, args)
-        check_raw_options(self, args)
+        check_inputs(self, args)
         for path in (args.a, args.b):
-            src = _named_size(args, path)
-            if args.scale is not None and src is not None and (args.scale[0] > src[0] or args.scale[1] > src[1]):
-                self.error(f"--scale {args.scale[0]}x{args.scale[1]} enlarges the {src[0]}x{src[1]} source: --scale only reduces")
-            size = args.scale if args.scale is not None else src
+            size = args.scale if args.scale is not None else named_size(args, path)
             if args.mode == "ssim" and size is not None and (size[0] < SSIM_WINDOW or size[1] < SSIM_WINDOW):
                 self.error(f"--mode ssim needs frames of at least {SSIM_WINDOW}x{SSIM_WINDOW}; these are {size[0]}x{size[1]}")
         return args
@@ -90,8 +71,7 @@ class _DiffParser(argparse.ArgumentParser):
 
 def build_parser() -> argparse.ArgumentParser:
     ap = _DiffParser(prog="diff", description="Where two videos differ: a video of per-pixel difference or SSIM maps, computed on the device.")
-    ap.add_argument("a", metavar="A", help=".y4m file, raw video (--pix-fmt), synthetic:<W>x<H>:<n>[:kind], .npy or an image directory")
-    ap.add_argument("b", metavar="B", help="the same forms; the input options apply to both")
+    add_inputs(ap)
     ap.add_argument("out", metavar="OUT", help=".y4m file, '-' (stdout: Y4M, or raw video with --pix-fmt / --out-pix-fmt), a raw video file, .npy "
                                                "or a directory of PNG frames")
     add_input_options(ap)
@@ -116,130 +96,38 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     return build_parser().parse_args(argv)
 
 
-def sink_format(args) -> Optional[str]:
-    """What OUT takes: "i420" (a .y4m sink), a raw pixel format name, or None for RGB frames (.npy, a PNG directory)."""
-    from .renderers.video import is_raw_sink, is_y4m
-
-    fmt = args.out_pix_fmt
-    if fmt is None and args.pix_fmt is not None and is_raw_sink(args.out):
-        fmt = args.pix_fmt
-    if fmt is not None:
-        return fmt
-    return "i420" if is_y4m(args.out) else None
-
-
-def _out_matrix(args) -> str:
-    return args.out_matrix or ("bt709" if args.transfer is not None else args.matrix)
-
-
 # ------------------------------------------------------------------------------------------------ the device loop
 def stream_maps(args, info: dict, fmt: Optional[str] = None) -> Iterator[Tuple[np.ndarray, DiffRecord]]:
     """(output frame, record) of the common prefix of args.a and args.b, in frame order.  The frame is RGB uint8 H x W x 3 (H x 3W x 3
     with --layout side) when fmt is None, else the flat payload the device encoded it to ("i420", or a raw pixel format name).
     info["hw"] is the output frames' (H, W) once the first item is there; info["longer"] names the input ("A" / "B") that had frames
-    left over, when one had."""
-    from ._lib import lib
-    from .runtime import get_context
-    from .yuv import frame_size, i420_size, rgb_to_i420_device, rgb_to_yuv_device
-
-    va, hwa = _open(args, args.a)
-    vb, hwb = _open(args, args.b)
-    sides = []
-    try:
-        if hwa is not None and hwb is not None and tuple(hwa) != tuple(hwb):
-            raise SystemExit(f"diff: frame sizes differ: A is {hwa[1]}x{hwa[0]}, B is {hwb[1]}x{hwb[0]}")
-        if hwa is None or hwb is None:  # an empty input
-            if hwa is not None or hwb is not None:
-                info["longer"] = "A" if hwa is not None else "B"
-            return
-        H, W = hwa
+    left over, when one had.  The loop is pairs.stream_map_pairs."""
+    def check_size(H, W):
         if args.mode == "ssim" and (H < SSIM_WINDOW or W < SSIM_WINDOW):
             raise SystemExit(f"diff: --mode ssim needs frames of at least {SSIM_WINDOW}x{SSIM_WINDOW}; these are {W}x{H}")
-        Wo = 3 * W if args.layout == "side" else W
-        info["hw"] = (H, Wo)
-        ctx, batch, sets = get_context(), args.batch, args.depth
-        unit = H * Wo * 3 if fmt is None else (i420_size(H, Wo) if fmt == "i420" else frame_size(fmt, H, Wo))
-        matrix, yrange = _out_matrix(args), args.range or "limited"
-        sides.append(_Side(ctx, va, H, W, batch, sets))
-        sides.append(_Side(ctx, vb, H, W, batch, sets))
-        streams = [ctx.stream_create() for _ in range(sets)]
-        d_map = [ctx.malloc(batch * H * Wo * 3) for _ in range(sets)]
-        d_pay = [ctx.malloc(batch * unit) for _ in range(sets)] if fmt is not None else d_map
-        d_rec = [ctx.malloc(batch * DIFF_RECORD_BYTES) for _ in range(sets)]
-        h_out = [ctx.pinned((batch, unit), np.uint8) for _ in range(sets)]
-        h_rec = [ctx.pinned((batch * DIFF_RECORD_BYTES,), np.uint8) for _ in range(sets)]
-        pending = [0] * sets
 
-        def harvest(k):
-            ctx.sync(streams[k])
-            n, pending[k] = pending[k], 0
-            recs = diff_records_from_bytes(h_rec[k].array, n) if n else []
-            shape = (H, Wo, 3) if fmt is None else (unit,)
-            return [(np.array(h_out[k].array[j]).reshape(shape), recs[j]) for j in range(n)]  # copies: the set is filled again
+    def launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, stream):
+        diff_map_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, mode=args.mode, gain=args.gain, threshold=args.threshold, layout=args.layout,
+                        stream=stream)
 
-        try:
-            i = 0
-            while True:
-                k = i % sets
-                yield from harvest(k)  # the set's previous batch: its buffers are free again afterwards
-                na, nb = sides[0].fill(k, batch), sides[1].fill(k, batch)
-                n = min(na, nb)
-                if n:
-                    for s in sides:
-                        s.enqueue(k, n, streams[k])
-                    diff_map_launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, d_map[k], d_rec[k], mode=args.mode, gain=args.gain,
-                                    threshold=args.threshold, layout=args.layout, stream=streams[k])
-                    if fmt == "i420":
-                        rgb_to_i420_device(ctx, d_map[k], d_pay[k], n, H, Wo, matrix=matrix, range=yrange, stream=streams[k])
-                    elif fmt is not None:
-                        rgb_to_yuv_device(ctx, fmt, d_map[k], d_pay[k], n, H, Wo, matrix=matrix, range=yrange, stream=streams[k])
-                    ctx._check(lib.avx_memcpy_d2h(ctx._h, h_out[k].ptr, d_pay[k].ptr, n * unit, streams[k]))
-                    ctx._check(lib.avx_memcpy_d2h(ctx._h, h_rec[k].ptr, d_rec[k].ptr, n * DIFF_RECORD_BYTES, streams[k]))
-                    pending[k] = n
-                i += 1
-                if na != nb:
-                    info["longer"] = "A" if na > nb else "B"
-                if n < batch:
-                    break
-            for j in range(sets):
-                yield from harvest((i + j) % sets)
-        finally:
-            for k in range(sets):
-                ctx.sync(streams[k])
-                ctx.stream_destroy(streams[k])
-            for b in d_map + d_rec + (d_pay if fmt is not None else []):
-                b.free()
-            for h in h_out + h_rec:
-                h.free()
-    finally:
-        for s in sides:
-            s.free()
-        va.close()
-        vb.close()
+    return stream_map_pairs(args, info, "diff", fmt, launch, DIFF_RECORD_BYTES, diff_records_from_bytes, check_size)
 
 
 # ------------------------------------------------------------------------------------------------ the command
 def main(argv: Optional[Sequence[str]] = None) -> int:
     args = parse_args(argv)
-    from .renderers import VideoRenderer
-
     fmt = sink_format(args)
     info: dict = {}
     frames = beyond = 0
     worst = (0, 0, 0, 0)  # max_d, frame, x, y
     t0 = time.perf_counter()
-    items = stream_maps(args, info, fmt)
-    head = list(itertools.islice(items, 1))  # the inputs are opened and their sizes checked before anything is written
-    sink = VideoRenderer(read_path=None, write_path=args.out, write_pix_fmt=None if fmt in (None, "i420") else fmt, matrix=_out_matrix(args),
-                         range=args.range, out_matrix=_out_matrix(args))
-    sink.open()
+    items = opened(stream_maps(args, info, fmt))
+    sink = open_sink(args, fmt, info)
     csv = open(args.csv, "w") if args.csv else None
     try:
         if csv:
             csv.write(CSV_HEADER + "\n")
-        if fmt is not None and "hw" in info:
-            sink.set_output_size(*info["hw"])  # payloads name no size of their own
-        for frame, r in itertools.chain(head, items):
+        for frame, r in items:
             sink.render(frame)
             if csv:
                 csv.write(format_row(frames, r) + "\n")
@@ -255,10 +143,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     where = f" (frame {worst[1]}, pixel x {worst[2]} y {worst[3]})" if worst[0] else ""
     print(f"diff: {frames} frames, largest difference {worst[0]}{where}, {beyond} pixels beyond {args.threshold}, "
           f"{frames / dt if dt > 0 else 0.0:.1f} fps", file=sys.stderr)
-    if info.get("longer") and not args.shortest:
-        print(f"diff: {info['longer']} has more frames than the other input: compared the first {frames} (--shortest accepts that)", file=sys.stderr)
-        return 2
-    return 0
+    return exit_status("diff", args, info, frames)
 
 
 if __name__ == "__main__":

@@ -117,6 +117,33 @@ def _check_call(n_frames: int, H: int, W: int, d_a: DeviceBuffer, d_b: DeviceBuf
         raise ValueError(f"{n_frames} frames of {H} x {W} need {need} bytes each; the buffers hold {d_a.nbytes} and {d_b.nbytes}")
 
 
+def _records(buf: np.ndarray, n: int, nbytes: int, dtype: np.dtype) -> np.ndarray:
+    """The first n records of `nbytes` each in a downloaded uint8 buffer, as a structured array (a copy)."""
+    return np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n * nbytes], dtype=dtype)
+
+
+def _walk(ctx: Optional[Context], a: np.ndarray, b: np.ndarray, per_chunk, extra=()) -> None:
+    """The array-level entry points' loop: a and b (N frames or payloads each) go up in chunks of at most MAX_FRAMES, and
+    per_chunk(ctx, i, n, d_a, d_b, *d_extra) works on the n frames from frame i on.  The device buffers hold min(N, MAX_FRAMES)
+    frames; `extra` names further ones in bytes per frame (None: no buffer, None is passed).  All are freed however it ends."""
+    ctx = ctx or get_context()
+    N = len(a)
+    chunk = min(N, MAX_FRAMES)
+    bufs: List[Optional[DeviceBuffer]] = []
+    try:
+        for nbytes in (a[0].nbytes, b[0].nbytes, *extra):
+            bufs.append(None if nbytes is None else ctx.malloc(chunk * nbytes))
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            ctx.upload(a[i : i + n], bufs[0])
+            ctx.upload(b[i : i + n], bufs[1])
+            per_chunk(ctx, i, n, *bufs)
+    finally:
+        for d in bufs:
+            if d is not None:
+                d.free()
+
+
 def frame_metrics_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_out: DeviceBuffer, *,
                          ssim: bool = True, stream=None) -> None:
     """Enqueue the comparison of n_frames frames on `stream`; d_out takes n_frames records of RECORD_BYTES (records_from_bytes reads
@@ -129,8 +156,7 @@ def frame_metrics_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_f
 
 def records_from_bytes(buf: np.ndarray, n_frames: int) -> List[FrameMetrics]:
     """n_frames downloaded records (uint8) -> FrameMetrics."""
-    recs = np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n_frames * RECORD_BYTES], dtype=_RECORD_DTYPE)
-    return [FrameMetrics(r["abs_hist"], r["ssim"]) for r in recs]
+    return [FrameMetrics(r["abs_hist"], r["ssim"]) for r in _records(buf, n_frames, RECORD_BYTES, _RECORD_DTYPE)]
 
 
 def frame_metrics_device(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, *, ssim: bool = True,
@@ -165,20 +191,9 @@ def check_pair(a, b):
 def frame_metrics(a, b, *, ssim: bool = True, ctx: Optional[Context] = None):
     """a, b: uint8 H x W x 3 -> FrameMetrics, or N x H x W x 3 -> a list of N; uploaded in chunks of at most 16 frames."""
     a, b, batched = check_pair(a, b)
-    N, H, W = a.shape[:3]
-    ctx = ctx or get_context()
-    chunk = min(N, MAX_FRAMES)
-    d_a, d_b = ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * H * W * 3)
+    H, W = a.shape[1:3]
     out: List[FrameMetrics] = []
-    try:
-        for i in range(0, N, chunk):
-            n = min(chunk, N - i)
-            ctx.upload(a[i : i + n], d_a)
-            ctx.upload(b[i : i + n], d_b)
-            out += frame_metrics_device(ctx, d_a, d_b, n, H, W, ssim=ssim)
-    finally:
-        d_a.free()
-        d_b.free()
+    _walk(ctx, a, b, lambda ctx, i, n, d_a, d_b: out.extend(frame_metrics_device(ctx, d_a, d_b, n, H, W, ssim=ssim)))
     return out if batched else out[0]
 
 
@@ -329,8 +344,7 @@ def plane_metrics_launch(ctx: Context, pix_fmt: str, d_a: DeviceBuffer, d_b: Dev
 def plane_records_from_bytes(buf: np.ndarray, n_frames: int, pix_fmt: str, H: int, W: int) -> List[PlaneMetrics]:
     """n_frames downloaded records (uint8) of H x W frames in `pix_fmt` -> PlaneMetrics."""
     depth, counts = plane_geometry(pix_fmt, H, W)
-    recs = np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n_frames * PLANE_RECORD_BYTES], dtype=_PLANE_DTYPE)
-    return [PlaneMetrics(r["abs_hist"], r["ssim"], depth, counts) for r in recs]
+    return [PlaneMetrics(r["abs_hist"], r["ssim"], depth, counts) for r in _records(buf, n_frames, PLANE_RECORD_BYTES, _PLANE_DTYPE)]
 
 
 def plane_metrics_device(ctx: Context, pix_fmt: str, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, *,
@@ -373,20 +387,8 @@ def plane_metrics(a, b, *, pix_fmt: str, H: int, W: int, pix_fmt_b: Optional[str
     list of n PlaneMetrics; uploaded in chunks of at most 16 frames."""
     pix_fmt_b = pix_fmt if pix_fmt_b is None else pix_fmt_b
     a, b = check_payloads(a, b, pix_fmt, pix_fmt_b, int(H), int(W))
-    N = len(a)
-    ctx = ctx or get_context()
-    chunk = min(N, MAX_FRAMES)
-    d_a, d_b = ctx.malloc(chunk * a.shape[1]), ctx.malloc(chunk * b.shape[1])
     out: List[PlaneMetrics] = []
-    try:
-        for i in range(0, N, chunk):
-            n = min(chunk, N - i)
-            ctx.upload(a[i : i + n], d_a)
-            ctx.upload(b[i : i + n], d_b)
-            out += plane_metrics_device(ctx, pix_fmt, d_a, d_b, n, H, W, pix_fmt_b=pix_fmt_b, ssim=ssim)
-    finally:
-        d_a.free()
-        d_b.free()
+    _walk(ctx, a, b, lambda ctx, i, n, d_a, d_b: out.extend(plane_metrics_device(ctx, pix_fmt, d_a, d_b, n, H, W, pix_fmt_b=pix_fmt_b, ssim=ssim)))
     return out
 
 
@@ -456,8 +458,7 @@ def frame_metrics_ms_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, 
 
 def ms_records_from_bytes(buf: np.ndarray, n_frames: int) -> List[MsSsim]:
     """n_frames downloaded MS-SSIM records (uint8) -> MsSsim."""
-    recs = np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n_frames * MS_RECORD_BYTES], dtype=_MS_DTYPE)
-    return [MsSsim(r["cs"], r["ssim"]) for r in recs]
+    return [MsSsim(r["cs"], r["ssim"]) for r in _records(buf, n_frames, MS_RECORD_BYTES, _MS_DTYPE)]
 
 
 def frame_metrics_ms_device(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, *, stream=None):
@@ -480,21 +481,10 @@ def ms_ssim(a, b, *, ctx: Optional[Context] = None):
     """a, b: uint8 H x W x 3 -> MsSsim, or N x H x W x 3 -> a list of N; uploaded in chunks of at most 16 frames.  ValueError for
     frames below 176 x 176, before any device work."""
     a, b, batched = check_pair(a, b)
-    N, H, W = a.shape[:3]
+    H, W = a.shape[1:3]
     check_ms_size(H, W)
-    ctx = ctx or get_context()
-    chunk = min(N, MAX_FRAMES)
-    d_a, d_b = ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * H * W * 3)
     out: List[MsSsim] = []
-    try:
-        for i in range(0, N, chunk):
-            n = min(chunk, N - i)
-            ctx.upload(a[i : i + n], d_a)
-            ctx.upload(b[i : i + n], d_b)
-            out += frame_metrics_ms_device(ctx, d_a, d_b, n, H, W)[1]
-    finally:
-        d_a.free()
-        d_b.free()
+    _walk(ctx, a, b, lambda ctx, i, n, d_a, d_b: out.extend(frame_metrics_ms_device(ctx, d_a, d_b, n, H, W)[1]))
     return out if batched else out[0]
 
 
@@ -573,35 +563,24 @@ def diff_map_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames
 
 def diff_records_from_bytes(buf: np.ndarray, n_frames: int) -> List[DiffRecord]:
     """n_frames downloaded records (uint8) -> DiffRecord."""
-    recs = np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n_frames * DIFF_RECORD_BYTES], dtype=_DIFF_DTYPE)
-    return [DiffRecord(r["max_d"], r["max_x"], r["max_y"], r["beyond"]) for r in recs]
+    return [DiffRecord(r["max_d"], r["max_x"], r["max_y"], r["beyond"]) for r in _records(buf, n_frames, DIFF_RECORD_BYTES, _DIFF_DTYPE)]
 
 
 def _diff_chunks(a, b, mode, gain, threshold, layout, ctx, with_float):
     """diff_map and ssim_map: the stack in chunks of at most 16 frames -> (frames, records, float maps or None)."""
     N, H, W = a.shape[:3]
-    ctx = ctx or get_context()
-    chunk = min(N, MAX_FRAMES)
     wide = 3 if layout == "side" else 1
-    d_a, d_b, d_out = ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * H * W * 3 * wide)
-    d_rec = ctx.malloc(chunk * DIFF_RECORD_BYTES)
-    d_map = ctx.malloc(chunk * (H - 10) * (W - 10) * 12) if with_float else None
     frames, recs = np.empty((N, H, W * wide, 3), np.uint8), []
     maps = np.empty((N, H - 10, W - 10, 3), np.float32) if with_float else None
-    try:
-        for i in range(0, N, chunk):
-            n = min(chunk, N - i)
-            ctx.upload(a[i : i + n], d_a)
-            ctx.upload(b[i : i + n], d_b)
-            diff_map_launch(ctx, d_a, d_b, n, H, W, d_out, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_ssim_map=d_map)
-            ctx.download(d_out, (n, H, W * wide, 3), np.uint8, out=frames[i : i + n])
-            recs += diff_records_from_bytes(ctx.download(d_rec, (n * DIFF_RECORD_BYTES,), np.uint8), n)
-            if with_float:
-                ctx.download(d_map, (n, H - 10, W - 10, 3), np.float32, out=maps[i : i + n])
-    finally:
-        for d in (d_a, d_b, d_out, d_rec, d_map):
-            if d is not None:
-                d.free()
+
+    def per_chunk(ctx, i, n, d_a, d_b, d_out, d_rec, d_map):
+        diff_map_launch(ctx, d_a, d_b, n, H, W, d_out, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_ssim_map=d_map)
+        ctx.download(d_out, (n, H, W * wide, 3), np.uint8, out=frames[i : i + n])
+        recs.extend(diff_records_from_bytes(ctx.download(d_rec, (n * DIFF_RECORD_BYTES,), np.uint8), n))
+        if with_float:
+            ctx.download(d_map, (n, H - 10, W - 10, 3), np.float32, out=maps[i : i + n])
+
+    _walk(ctx, a, b, per_chunk, (H * W * 3 * wide, DIFF_RECORD_BYTES, (H - 10) * (W - 10) * 12 if with_float else None))
     return frames, recs, maps
 
 
@@ -715,37 +694,27 @@ def delta_e_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames:
 
 def delta_e_records_from_bytes(buf: np.ndarray, n_frames: int) -> List[DeltaE]:
     """n_frames downloaded records (uint8) -> DeltaE."""
-    recs = np.frombuffer(np.ascontiguousarray(buf).tobytes()[: n_frames * DELTA_E_RECORD_BYTES], dtype=_DELTA_E_DTYPE)
-    return [DeltaE(r["hist"], r["sum"], r["max_de"], r["max_x"], r["max_y"], r["beyond"]) for r in recs]
+    return [DeltaE(r["hist"], r["sum"], r["max_de"], r["max_x"], r["max_y"], r["beyond"])
+            for r in _records(buf, n_frames, DELTA_E_RECORD_BYTES, _DELTA_E_DTYPE)]
 
 
 def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_float):
     """delta_e, delta_e_map and delta_e_values: the stack in chunks of at most 16 frames -> (maps or None, records, values or None)."""
     N, H, W = a.shape[:3]
-    ctx = ctx or get_context()
-    chunk = min(N, MAX_FRAMES)
     wide = 3 if layout == "side" else 1
-    d_a, d_b, d_rec = ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * DELTA_E_RECORD_BYTES)
-    d_map = ctx.malloc(chunk * H * W * 3 * wide) if with_map else None
-    d_val = ctx.malloc(chunk * H * W * 4) if with_float else None
     maps = np.empty((N, H, W * wide, 3), np.uint8) if with_map else None
     vals = np.empty((N, H, W), np.float32) if with_float else None
     recs: List[DeltaE] = []
-    try:
-        for i in range(0, N, chunk):
-            n = min(chunk, N - i)
-            ctx.upload(a[i : i + n], d_a)
-            ctx.upload(b[i : i + n], d_b)
-            delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_float=d_val)
-            if with_map:
-                ctx.download(d_map, (n, H, W * wide, 3), np.uint8, out=maps[i : i + n])
-            recs += delta_e_records_from_bytes(ctx.download(d_rec, (n * DELTA_E_RECORD_BYTES,), np.uint8), n)
-            if with_float:
-                ctx.download(d_val, (n, H, W), np.float32, out=vals[i : i + n])
-    finally:
-        for d in (d_a, d_b, d_rec, d_map, d_val):
-            if d is not None:
-                d.free()
+
+    def per_chunk(ctx, i, n, d_a, d_b, d_rec, d_map, d_val):
+        delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_float=d_val)
+        if with_map:
+            ctx.download(d_map, (n, H, W * wide, 3), np.uint8, out=maps[i : i + n])
+        recs.extend(delta_e_records_from_bytes(ctx.download(d_rec, (n * DELTA_E_RECORD_BYTES,), np.uint8), n))
+        if with_float:
+            ctx.download(d_val, (n, H, W), np.float32, out=vals[i : i + n])
+
+    _walk(ctx, a, b, per_chunk, (DELTA_E_RECORD_BYTES, H * W * 3 * wide if with_map else None, H * W * 4 if with_float else None))
     return maps, recs, vals
 
 

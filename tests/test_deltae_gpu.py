@@ -321,7 +321,7 @@ def _y4m_frames(path):
 
 
 def test_command_npy_sink_csv_and_stdout(clips, capsys, tmp_path):
-    from animal_vision_amd.deltae import _num
+    from animal_vision_amd.pairs import num as _num
     from animal_vision_amd.metrics import delta_e, delta_e_map
 
     d, a, b = clips
@@ -419,3 +419,18 @@ def test_command_lengths_sizes_and_limits(clips, capsys, tmp_path):
         assert status == 1 and text in err and len(stdout.splitlines()) == 13, argv
     status, _, err = _deltae(capsys, [d / "a.npy", d / "b.npy", "--max-de", "200", "--max-mean", "200", "--max-p95", "200"])
     assert status == 0 and "frame 5:" not in err
+
+
+def test_command_output_does_not_depend_on_batch_and_depth(capsys, tmp_path):
+    """The shared device loop (pairs.stream_pairs): the maps and the CSV are the same bytes however the nine frames are cut into
+    batches and spread over buffer sets -- one set, three sets, a batch per frame, the whole clip in one batch."""
+    got = []
+    for batch, depth in ((8, 2), (1, 1), (3, 3), (9, 1)):
+        out, csv = tmp_path / f"o_{batch}_{depth}.npy", tmp_path / f"w_{batch}_{depth}.csv"
+        status, stdout, err = _deltae(capsys, ["synthetic:64x48:9:noise", "synthetic:64x48:9:structured", out, "--csv", csv, "--batch", batch, "--depth", depth])
+        assert status == 0 and stdout == "" and "deltae: 9 frames" in err
+        got.append((out.read_bytes(), csv.read_bytes()))
+    assert np.load(tmp_path / "o_8_2.npy").shape == (9, 48, 64, 3) and np.load(tmp_path / "o_8_2.npy").any()
+    assert len(got[0][1].splitlines()) == 10
+    for other in got[1:]:
+        assert other == got[0]

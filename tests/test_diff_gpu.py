@@ -386,3 +386,18 @@ def test_command_lengths_and_sizes(clips, capsys, tmp_path):
     np.save(tmp_path / "tiny.npy", a[:2, :10, :30])
     with pytest.raises(SystemExit, match="--mode ssim needs frames of at least 11x11; these are 30x10"):
         _diff(capsys, [tmp_path / "tiny.npy", tmp_path / "tiny.npy", tmp_path / "r.npy", "--mode", "ssim"])
+
+
+def test_command_output_does_not_depend_on_batch_and_depth(capsys, tmp_path):
+    """The shared device loop (pairs.stream_pairs): the maps and the CSV are the same bytes however the nine frames are cut into
+    batches and spread over buffer sets -- one set, three sets, a batch per frame, the whole clip in one batch."""
+    got = []
+    for batch, depth in ((8, 2), (1, 1), (3, 3), (9, 1)):
+        out, csv = tmp_path / f"o_{batch}_{depth}.npy", tmp_path / f"w_{batch}_{depth}.csv"
+        status, stdout, err = _diff(capsys, ["synthetic:64x48:9:noise", "synthetic:64x48:9:structured", out, "--csv", csv, "--batch", batch, "--depth", depth])
+        assert status == 0 and stdout == "" and "diff: 9 frames" in err
+        got.append((out.read_bytes(), csv.read_bytes()))
+    assert np.load(tmp_path / "o_8_2.npy").shape == (9, 48, 64, 3) and np.load(tmp_path / "o_8_2.npy").any()
+    assert len(got[0][1].splitlines()) == 10
+    for other in got[1:]:
+        assert other == got[0]

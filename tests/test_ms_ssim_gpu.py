@@ -205,7 +205,8 @@ def _compare(capsys, argv):
 
 
 def test_command_ms_ssim(clips, capsys, tmp_path):
-    from animal_vision_amd.compare import CSV_HEADER, CSV_MS_COLUMNS, _num
+    from animal_vision_amd.compare import CSV_HEADER, CSV_MS_COLUMNS
+    from animal_vision_amd.pairs import num as _num
     from animal_vision_amd.metrics import ms_ssim
 
     d, a, b = clips

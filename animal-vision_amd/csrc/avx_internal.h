@@ -20,9 +20,10 @@ struct avx_ws {
     size_t h_row_tab_bytes = 0, h_row_tab_cap = 0;
     // Small constant tables of a caller's pipeline (matrices, weights, coordinate rows): device copy + host mirror per slot,
     // uploaded only when the bytes change (avx_const_upload).  Slots: 0 UV matrix / weights, 1 band-major spectral weights (k_spectral_nhwc_h), 2-7 mantis tables,
-    // 8-9 label stroke segments (labels.hip), 10 montage descriptors + segments + resize tables (gallery.hip).
+    // 8-9 label stroke segments (labels.hip), 10 montage descriptors + segments + resize tables (gallery.hip),
+    // 11 the S-CIELAB filter taps (scielab.hip).
     struct const_slot { void* dev = nullptr; void* host = nullptr; size_t bytes = 0, cap = 0; };
-    static constexpr int kConstSlots = 11;
+    static constexpr int kConstSlots = 12;
     const_slot consts[kConstSlots];
     void* uv_small = nullptr;        // UV path: partial statistics, histogram, select state, percentiles
     void* d_scratch = nullptr;       // scratch arena (UV path planes)

@@ -16,31 +16,18 @@
 // k_delta_e_final adds a frame's partials in index order: no float atomics.  The largest dE is one 64-bit integer maximum over
 // (float bits of dE << 32) | (0xFFFFFFFF - pixel index): dE is never negative, so its bits order as its value, and among equals the
 // earlier pixel wins; the key lies in the bytes of (max_de, max_x) until k_delta_e_final takes it apart.
-#include "lab_tables.h"
-#include "map_common.h"
-#include "ssim_window.h"
+// The Lab transfer function, ciede2000, the key, the colour of a map pixel, the workgroup's share of the record and k_delta_e_final are
+// delta_e_common.h's, shared with scielab.hip.
+#include "delta_e_common.h"
 
 namespace {
 
 constexpr int kPerThread = 16;
 constexpr int kChunk = kThreads * kPerThread;  // pixels of a workgroup: 12288 bytes of each frame, a multiple of 48
-constexpr float kPi = 3.14159265358979f, kTwoPi = 6.28318530717959f;
-
 // M': the sRGB -> XYZ (D65) matrix with every row divided by its own sum; columns 0 and 2, the anchored form needs no other
-constexpr double kSX = 0.4124564 + 0.3575761 + 0.1804375, kSY = 0.2126729 + 0.7151522 + 0.0721750, kSZ = 0.0193339 + 0.1191920 + 0.9503041;
 constexpr float kX0 = (float)(0.4124564 / kSX), kX2 = (float)(0.1804375 / kSX);
 constexpr float kY0 = (float)(0.2126729 / kSY), kY2 = (float)(0.0721750 / kSY);
 constexpr float kZ0 = (float)(0.0193339 / kSZ), kZ2 = (float)(0.9503041 / kSZ);
-constexpr float kLabEps = (float)(216.0 / 24389.0);      // (6/29)^3
-constexpr float kLabSlope = (float)(841.0 / 108.0);      // 1 / (3 (6/29)^2)
-constexpr float kLabOffset = (float)(4.0 / 29.0);
-constexpr float k25p7 = 6103515625.0f;                   // 25^7
-
-// one rounding each, 1 ulp: v_sqrt_f32, v_rcp_f32
-__device__ __forceinline__ float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
-__device__ __forceinline__ float fdiv(float x, float y) { return x * __builtin_amdgcn_rcpf(y); }
-
-__device__ __forceinline__ float lab_f(float t) { return t > kLabEps ? cbrtf(t) : t * kLabSlope + kLabOffset; }
 
 // r, g, b: decoded (linear) samples.  t_i = g + M'_i0 (r - g) + M'_i2 (b - g): r = g = b gives t_X = t_Y = t_Z = g exactly, a = b = 0
 __device__ __forceinline__ void lab_of(float r, float g, float b, float& L, float& A, float& B) {
@@ -51,59 +38,6 @@ __device__ __forceinline__ void lab_of(float r, float g, float b, float& L, floa
     L = 116.0f * fy - 16.0f;
     A = 500.0f * (fx - fy);
     B = 200.0f * (fy - fz);
-}
-
-// h' in [0, 2 pi], 0 where the chroma is 0
-__device__ __forceinline__ float hue_of(float b, float ap, float cp) {
-    float h = atan2f(b, ap);
-    h = h < 0.0f ? h + kTwoPi : h;
-    return cp == 0.0f ? 0.0f : h;
-}
-
-__device__ __forceinline__ float pow7(float c) {
-    const float c2 = c * c, c4 = c2 * c2;
-    return (c4 * c2) * c;
-}
-
-// Sharma, Wu, Dalal 2005, k_L = k_C = k_H = 1; hue in radians
-__device__ __forceinline__ float ciede2000(float L1, float a1, float b1, float L2, float a2, float b2) {
-    const float C1 = fsqrt(a1 * a1 + b1 * b1), C2 = fsqrt(a2 * a2 + b2 * b2);
-    const float cb7 = pow7(0.5f * (C1 + C2));
-    const float G1 = 1.0f + 0.5f * (1.0f - fsqrt(fdiv(cb7, cb7 + k25p7)));
-    const float a1p = G1 * a1, a2p = G1 * a2;
-    const float C1p = fsqrt(a1p * a1p + b1 * b1), C2p = fsqrt(a2p * a2p + b2 * b2);
-    const float h1 = hue_of(b1, a1p, C1p), h2 = hue_of(b2, a2p, C2p);
-    const float dL = L2 - L1, dC = C2p - C1p, CC = C1p * C2p;
-    float dh = h2 - h1, hb = h1 + h2;
-    if (CC == 0.0f) {
-        dh = 0.0f;
-    } else if (fabsf(dh) <= kPi) {
-        hb = 0.5f * hb;
-    } else {
-        hb = hb < kTwoPi ? 0.5f * (hb + kTwoPi) : 0.5f * (hb - kTwoPi);
-        dh = dh > 0.0f ? dh - kTwoPi : dh + kTwoPi;
-    }
-    const float dH = 2.0f * fsqrt(CC) * sinf(0.5f * dh);
-    const float Lb = 0.5f * (L1 + L2), Cb = 0.5f * (C1p + C2p);
-    // cos(hb - 30), cos(2 hb), cos(3 hb + 6), cos(4 hb - 63) (degrees) from sin and cos of hb
-    float s1, c1;
-    sincosf(hb, &s1, &c1);
-    const float c2 = 2.0f * c1 * c1 - 1.0f, s2 = 2.0f * s1 * c1;
-    const float c3 = c2 * c1 - s2 * s1, s3 = s2 * c1 + c2 * s1;
-    const float c4 = 2.0f * c2 * c2 - 1.0f, s4 = 2.0f * s2 * c2;
-    const float T = (((1.0f - 0.17f * (c1 * 0.866025403784439f + s1 * 0.5f)) + 0.24f * c2) + 0.32f * (c3 * 0.994521895368273f - s3 * 0.104528463267653f)) -
-                    0.20f * (c4 * 0.453990499739547f + s4 * 0.891006524188368f);
-    const float u = (hb - 4.79965544298441f) * 2.29183118052329f;  // (hb - 275 deg) / 25 deg
-    const float two_dtheta = 1.04719755119660f * expf(-(u * u));   // 2 * 30 deg * exp(.)
-    const float cp7 = pow7(Cb);
-    const float RC = 2.0f * fsqrt(fdiv(cp7, cp7 + k25p7));
-    const float lm2 = (Lb - 50.0f) * (Lb - 50.0f);
-    const float SL = 1.0f + fdiv(0.015f * lm2, fsqrt(20.0f + lm2));
-    const float SC = 1.0f + 0.045f * Cb, SH = 1.0f + 0.015f * Cb * T;
-    const float RT = -sinf(two_dtheta) * RC;
-    const float tL = fdiv(dL, SL), tC = fdiv(dC, SC), tH = fdiv(dH, SH);
-    const float rad = ((tL * tL + tC * tC) + tH * tH) + RT * (tC * tH);
-    return fsqrt(fmaxf(rad, 0.0f));
 }
 
 struct DeArgs {
@@ -166,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void k_delta_e(DeArgs p) {
         else atomicAdd(&hist[bin], 1u);
         sum += (double)de;
         beyond += de > T ? 1u : 0u;
-        const unsigned long long k = ((unsigned long long)__float_as_uint(de) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(base + i));
+        const unsigned long long k = de_key(de, (uint32_t)(base + i));
         key = k > key ? k : key;
         if (de_out) de_out[i] = de;
         if (p.out) {
@@ -174,13 +108,10 @@ __global__ __launch_bounds__(kThreads) void k_delta_e(DeArgs p) {
             const float x = p.mode == AVX_DELTA_E_HEAT ? __fsub_rn(de, T) : de;
             const float v = fminf(floorf(__fadd_rn(__fmul_rn(G, x), 0.5f)), 255.0f);
             uint32_t r, g, b;
-            pal((int)fmaxf(v, 0.0f), r, g, b);
-            if (p.mode == AVX_DELTA_E_HEAT && !(de > T)) r = g = b = dim_grey(ar, ag, ab);
+            de_colour(v, de, T, p.mode, ar, ag, ab, r, g, b);
             so[3 * i] = (uint8_t)r, so[3 * i + 1] = (uint8_t)g, so[3 * i + 2] = (uint8_t)b;
         }
     }
-    zeros = wave_sum_u32(zeros);
-    if ((tid & 63) == 0 && zeros) atomicAdd(&hist[0], zeros);
     __syncthreads();
 
     // ---- the panels out of LDS ----
@@ -215,45 +146,10 @@ __global__ __launch_bounds__(kThreads) void k_delta_e(DeArgs p) {
     }
 
     // ---- the record ----
-    avx_delta_e_rec* rec = p.rec + f;
-    double s[1] = {sum};
-    workgroup_sum(s, red);
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long k = __shfl_down(key, o);
-        key = k > key ? k : key;
-        beyond += __shfl_down(beyond, o);
-    }
-    if ((tid & 63) == 0) wred[tid >> 6] = key, bred[tid >> 6] = beyond;
-    __syncthreads();
-    if (tid == 0) {
-        p.partials[(size_t)f * gridDim.x + blockIdx.x] = s[0];
-        unsigned long long k = wred[0];
-        unsigned n = bred[0];
-        for (int w = 1; w < kThreads / 64; ++w) k = wred[w] > k ? wred[w] : k, n += bred[w];
-        if (k >> 32) atomicMax(reinterpret_cast<unsigned long long*>(&rec->max_de), k);  // dE == 0 everywhere leaves the zeroed record
-        if (n) atomicAdd(&rec->beyond, n);
-    }
-    hist_flush(hist, 256, rec->hist);
-}
-
-// grid (frames): the frame's partials in index order -> sum; the key in the bytes of (max_de, max_x) -> (max_de, max_x, max_y)
-__global__ __launch_bounds__(kThreads) void k_delta_e_final(const double* __restrict__ partials, size_t nchunks, int W, avx_delta_e_rec* __restrict__ rec) {
-    __shared__ double red[kThreads];
-    const int f = blockIdx.x;
-    const double s = tile_partials_sum(partials + (size_t)f * nchunks, nchunks, red);
-    if (threadIdx.x == 0) {
-        const unsigned long long key = *reinterpret_cast<const unsigned long long*>(&rec[f].max_de);
-        const uint32_t bits = (uint32_t)(key >> 32), index = 0xFFFFFFFFu - (uint32_t)key;
-        rec[f].sum = s;
-        rec[f].max_de = __uint_as_float(bits);
-        rec[f].max_x = bits ? index % (uint32_t)W : 0u;
-        rec[f].max_y = bits ? index / (uint32_t)W : 0u;
-    }
+    de_record_share(sum, key, beyond, zeros, hist, red, wred, bred, p.partials + ((size_t)f * gridDim.x + blockIdx.x), p.rec + f);
 }
 
 }  // namespace
-
-static_assert(sizeof(avx_delta_e_rec) == 1048 && offsetof(avx_delta_e_rec, max_de) == 1032, "avx_delta_e_rec: the key needs 8 aligned bytes at max_de");
 
 extern "C" int avx_delta_e_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int mode, float gain, float threshold,
                               int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream) {

@@ -24,7 +24,17 @@ The CSV columns are frame,de_mean,de_p50,de_p95,de_max,x,y,beyond: the mean dE o
 off a histogram of 0.5-wide bins (the upper edge of the bin that holds it), the largest dE and the first pixel (raster order) that
 attains it, and the number of pixels with dE > T.  --max-mean, --max-p95 and --max-de set limits: status 1, and a line on stderr that
 names the first frame that breaks one.  A summary line goes to stderr.  Inputs of different frame sizes are an error before anything
-is written; of different lengths, the common prefix is compared and the status is 2 unless --shortest is given."""
+is written; of different lengths, the common prefix is compared and the status is 2 unless --shortest is given.
+
+--ppd X switches to S-CIELAB (Zhang & Wandell 1996): both frames are first filtered in an opponent colour space by the
+eye's contrast sensitivity for a viewer who sees X pixels per degree of visual angle, and dE00 is taken on the filtered frames.  A
+per-pixel dE charges resampling, ringing and blur at the pixel scale in full even where nobody could resolve them; with --ppd they
+count for what is left of them at that distance.  X = pixels per unit length x viewing distance x tan 1 degree: a 1080-line picture
+seen from three picture heights is about 57, and 60 is the usual round number; no default is applied, because the answer depends on
+it.  Finite, from 2 to 128.  Everything else keeps its meaning: the columns, the limits, --threshold, the modes, the layouts (the dim
+grey and the A and B panels are the unfiltered frames), all sources and sinks.  Without --ppd nothing changes.
+
+    python -m animal_vision_amd.deltae full.y4m half.y4m --ppd 60 --max-p95 2"""
 from __future__ import annotations
 
 import argparse
@@ -36,7 +46,7 @@ from typing import Iterator, Optional, Sequence, Tuple
 import numpy as np
 
 from .metrics import (DELTA_E_DEFAULT_GAIN, DELTA_E_DEFAULT_THRESHOLD, DELTA_E_LAYOUTS, DELTA_E_MODES, DELTA_E_RECORD_BYTES, DeltaE,
-                      check_delta_e_options, delta_e_launch, delta_e_records_from_bytes)
+                      check_delta_e_options, check_ppd, delta_e_launch, delta_e_records_from_bytes, scielab_launch)
 from .pairs import (add_inputs, check_depth, check_inputs, check_stdin, exit_status, num, open_sink, opened, sink_format,  # noqa: F401
                     stream_map_pairs)
 from .video import add_input_options, add_output_options
@@ -78,6 +88,11 @@ class _DeltaEParser(argparse.ArgumentParser):
             args.gain, args.threshold = check_delta_e_options(args.mode, args.gain, args.threshold, args.layout)
         except ValueError as e:
             self.error(f"--gain / --threshold: {e}")
+        if args.ppd is not None:
+            try:
+                args.ppd = check_ppd(args.ppd)
+            except ValueError as e:
+                self.error(f"--ppd: {e}")
         for flag, v in (("--max-mean", args.max_mean), ("--max-p95", args.max_p95), ("--max-de", args.max_de)):
             if v is not None and not (math.isfinite(v) and v >= 0.0):
                 self.error(f"{flag} must be finite and at least 0 (got {v:g})")
@@ -101,6 +116,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--threshold", type=float, default=DELTA_E_DEFAULT_THRESHOLD, metavar="T",
                     help=f"finite, at least 0 (default {DELTA_E_DEFAULT_THRESHOLD:g}, about one just-noticeable difference): heat colours the pixels "
                          "with dE above T; the `beyond` column counts them")
+    ap.add_argument("--ppd", type=float, default=None, metavar="X",
+                    help="S-CIELAB: filter both frames by the eye's contrast sensitivity at X pixels per degree of visual angle before dE is taken "
+                         "(X = pixels per unit length x viewing distance x tan 1 degree; a 1080-line picture seen from three picture heights is "
+                         "about 57; take 60 when in doubt).  Finite, from 2 to 128.  Default: none, the plain per-pixel dE")
     ap.add_argument("--layout", default=None, choices=list(DELTA_E_LAYOUTS), help="map (default): the map alone.  side: A | B | map, three times as wide")
     ap.add_argument("--csv", default=None, metavar="FILE",
                     help=f"write {CSV_HEADER} per frame here; without OUT the default is stdout, with OUT nothing is written unless this is given")
@@ -120,10 +139,14 @@ def stream_records(args, info: dict, fmt: Optional[str] = None) -> Iterator[Tupl
     """(output frame, record) of the common prefix of args.a and args.b, in frame order.  Without args.out the frame is None and no map
     is computed.  Otherwise it is RGB uint8 H x W x 3 (H x 3W x 3 with --layout side) when fmt is None, else the flat payload the
     device encoded it to ("i420", or a raw pixel format name).  info["hw"] is the output frames' (H, W) once the first item is there;
-    info["longer"] names the input ("A" / "B") that had frames left over, when one had.  The loop is pairs.stream_map_pairs."""
+    info["longer"] names the input ("A" / "B") that had frames left over, when one had.  The loop is pairs.stream_map_pairs; args.ppd
+    picks the launch: delta_e_launch when None, else scielab_launch."""
     def launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, stream):
-        delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, mode=args.mode, gain=args.gain, threshold=args.threshold, layout=args.layout,
-                       stream=stream)
+        kw = dict(mode=args.mode, gain=args.gain, threshold=args.threshold, layout=args.layout, stream=stream)
+        if getattr(args, "ppd", None) is None:
+            delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, **kw)
+        else:
+            scielab_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, ppd=args.ppd, **kw)
 
     return stream_map_pairs(args, info, "deltae", fmt, launch, DELTA_E_RECORD_BYTES, delta_e_records_from_bytes)
 
@@ -166,7 +189,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             csv.close()
     dt = time.perf_counter() - t0
     where = f" (frame {worst[1]}, pixel x {worst[2]} y {worst[3]})" if worst[0] else ""
-    print(f"deltae: {frames} frames, mean dE {num(sum_mean / frames) if frames else 'nan'}, largest dE {num(worst[0])}{where}, "
+    what = "dE" if args.ppd is None else f"S-CIELAB dE (ppd {args.ppd:g})"
+    print(f"deltae: {frames} frames, mean {what} {num(sum_mean / frames) if frames else 'nan'}, largest dE {num(worst[0])}{where}, "
           f"{beyond} pixels beyond {args.threshold:g}, {frames / dt if dt > 0 else 0.0:.1f} fps", file=sys.stderr)
     return exit_status("deltae", args, info, frames, first_bad)
 

@@ -19,7 +19,11 @@ python -m animal_vision_amd.diff is the command built on them.
 
 Colour difference maps (csrc/delta_e.hip) say how far apart the frames are in perceptual units: CIEDE2000 in CIELAB per
 pixel.  delta_e_launch enqueues the float32 values, the map ("heat" or "plain"; alone or A | B | map) and a DeltaE record per frame;
-delta_e, delta_e_map and delta_e_values take arrays.  python -m animal_vision_amd.deltae is the command built on them."""
+delta_e, delta_e_map and delta_e_values take arrays.  python -m animal_vision_amd.deltae is the command built on them.
+
+S-CIELAB (csrc/scielab.hip) is the same difference for a viewer at a stated distance: both frames are filtered by the
+eye's contrast sensitivity at `ppd` pixels per degree before dE00 is taken.  scielab_launch, scielab, scielab_map and scielab_values
+are the counterparts of the four above and return the same DeltaE records; `deltae --ppd` is the command."""
 from __future__ import annotations
 
 import ctypes
@@ -698,8 +702,9 @@ def delta_e_records_from_bytes(buf: np.ndarray, n_frames: int) -> List[DeltaE]:
             for r in _records(buf, n_frames, DELTA_E_RECORD_BYTES, _DELTA_E_DTYPE)]
 
 
-def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_float):
-    """delta_e, delta_e_map and delta_e_values: the stack in chunks of at most 16 frames -> (maps or None, records, values or None)."""
+def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_float, ppd=None):
+    """delta_e, delta_e_map, delta_e_values and (with ppd) their scielab counterparts: the stack in chunks of at most 16 frames ->
+    (maps or None, records, values or None)."""
     N, H, W = a.shape[:3]
     wide = 3 if layout == "side" else 1
     maps = np.empty((N, H, W * wide, 3), np.uint8) if with_map else None
@@ -707,7 +712,10 @@ def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_flo
     recs: List[DeltaE] = []
 
     def per_chunk(ctx, i, n, d_a, d_b, d_rec, d_map, d_val):
-        delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_float=d_val)
+        if ppd is None:
+            delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_float=d_val)
+        else:
+            scielab_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, ppd=ppd, mode=mode, gain=gain, threshold=threshold, layout=layout, d_float=d_val)
         if with_map:
             ctx.download(d_map, (n, H, W * wide, 3), np.uint8, out=maps[i : i + n])
         recs.extend(delta_e_records_from_bytes(ctx.download(d_rec, (n * DELTA_E_RECORD_BYTES,), np.uint8), n))
@@ -740,4 +748,63 @@ def delta_e_values(a, b, *, ctx: Optional[Context] = None) -> np.ndarray:
     """a, b: uint8 sRGB H x W x 3 -> the CIEDE2000 difference of every pixel, float32 H x W; N x H x W x 3 -> N x H x W."""
     a, b, batched = check_pair(a, b)
     vals = _delta_e_chunks(a, b, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True)[2]
+    return vals if batched else vals[0]
+
+
+# ------------------------------------------------------------------------------------------------ S-CIELAB (DESIGN §4.21)
+SCIELAB_MIN_PPD, SCIELAB_MAX_PPD = 2.0, 128.0
+
+
+def check_ppd(ppd) -> float:
+    """ppd -- pixels per degree of visual angle: pixels per unit length x viewing distance x tan 1 degree -- as the number the library
+    takes, after avx_scielab_u8's check: a finite number from 2 to 128.  ValueError naming it otherwise."""
+    if isinstance(ppd, bool) or not isinstance(ppd, numbers.Real) or not (math.isfinite(ppd) and SCIELAB_MIN_PPD <= ppd <= SCIELAB_MAX_PPD):
+        raise ValueError(f"ppd must be a finite number from {SCIELAB_MIN_PPD:g} to {SCIELAB_MAX_PPD:g} (got {ppd!r})")
+    return float(ppd)
+
+
+def scielab_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_map: Optional[DeviceBuffer],
+                   d_rec: DeviceBuffer, *, ppd, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map",
+                   d_float: Optional[DeviceBuffer] = None, stream=None) -> None:
+    """delta_e_launch with both frames filtered for a viewer at `ppd` pixels per degree first (S-CIELAB): the same buffers, records
+    and map.  Nothing is downloaded and nothing waits."""
+    _check_call(n_frames, H, W, d_a, d_b)
+    ppd = check_ppd(ppd)
+    g, t = check_delta_e_options(mode, gain, threshold, layout)
+    if d_rec.nbytes < n_frames * DELTA_E_RECORD_BYTES:
+        raise ValueError(f"{n_frames} records need {n_frames * DELTA_E_RECORD_BYTES} bytes; the buffer holds {d_rec.nbytes}")
+    need = n_frames * H * W * 3 * (3 if layout == "side" else 1)
+    if d_map is not None and d_map.nbytes < need:
+        raise ValueError(f"{n_frames} {layout} frames need {need} bytes; the buffer holds {d_map.nbytes}")
+    if d_float is not None and d_float.nbytes < n_frames * H * W * 4:
+        raise ValueError(f"the values of {n_frames} frames need {n_frames * H * W * 4} bytes; the buffer holds {d_float.nbytes}")
+    ctx._check(lib.avx_scielab_u8(ctx._h, d_a.ptr, d_b.ptr, int(n_frames), int(H), int(W), ppd, AVX_DELTA_E_MODES[mode], g, t,
+                                  AVX_DELTA_E_LAYOUTS[layout], None if d_map is None else d_map.ptr, d_rec.ptr,
+                                  None if d_float is None else d_float.ptr, ctx._s(stream)))
+
+
+def scielab(a, b, *, ppd, threshold=DELTA_E_DEFAULT_THRESHOLD, ctx: Optional[Context] = None):
+    """delta_e at `ppd` pixels per degree: a, b uint8 sRGB H x W x 3 -> the DeltaE record, or N x H x W x 3 -> a list of N.  ValueError
+    for a bad option or shape before any device work."""
+    a, b, batched = check_pair(a, b)
+    ppd = check_ppd(ppd)
+    check_delta_e_options("heat", None, threshold, "map")
+    recs = _delta_e_chunks(a, b, "heat", None, threshold, "map", ctx, False, False, ppd)[1]
+    return recs if batched else recs[0]
+
+
+def scielab_map(a, b, *, ppd, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map", ctx: Optional[Context] = None):
+    """delta_e_map at `ppd` pixels per degree; the dim grey and the A and B panels are the unfiltered frames'."""
+    a, b, batched = check_pair(a, b)
+    ppd = check_ppd(ppd)
+    check_delta_e_options(mode, gain, threshold, layout)
+    maps, recs, _ = _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, True, False, ppd)
+    return (maps, recs) if batched else (maps[0], recs[0])
+
+
+def scielab_values(a, b, *, ppd, ctx: Optional[Context] = None) -> np.ndarray:
+    """delta_e_values at `ppd` pixels per degree: the S-CIELAB dE00 of every pixel, float32 H x W or N x H x W."""
+    a, b, batched = check_pair(a, b)
+    ppd = check_ppd(ppd)
+    vals = _delta_e_chunks(a, b, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True, ppd)[2]
     return vals if batched else vals[0]

@@ -536,6 +536,30 @@ typedef struct avx_delta_e_rec {
 int avx_delta_e_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int mode, float gain, float threshold,
                    int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream);
 
+/* S-CIELAB colour difference maps (csrc/scielab.hip; Zhang & Wandell 1996): avx_delta_e_u8 for a viewer at a stated
+ * distance.  Both frames are filtered in an opponent colour space by the contrast sensitivity of the eye at `ppd` pixels per degree of
+ * visual angle (pixels per unit length x viewing distance x tan 1 degree), and dE00 is taken per pixel on the filtered frames, so
+ * that differences too fine to be resolved from there count for little.  Buffers, n_frames, mode, gain, threshold, layout, map_out,
+ * rec_dev, de_out, the record, the quantiser, the palette and the errors are those of avx_delta_e_u8; the dim grey of the heat mode
+ * and the A and B panels of the side layout are the unfiltered frames'.  2 <= ppd <= 128 and finite.
+ * With lin the decode table of avx_delta_e_u8 and M its sRGB -> XYZ matrix: o = P M lin, P = (0.279 0.72 -0.107; -0.449 0.29 -0.077;
+ * 0.086 -0.59 0.501) (luminance, red-green, blue-yellow).  Each channel is filtered by a sum of separable Gaussians given as (weight,
+ * spread in degrees): luminance (0.921, 0.0283), (0.105, 0.133), (-0.108, 4.336); red-green (0.531, 0.0392), (0.330, 0.494);
+ * blue-yellow (0.488, 0.0536), (0.371, 0.386); the weights of a channel are divided by their sum.  A term is g[x] g[y] with
+ * g[x] = exp(-x^2 / (spread ppd)^2) on x = -R .. R, R = ceil(ppd / 2), normalised to unit sum over that support; the filtered channel
+ * is sum_i w_i (g_i *x g_i *y o), rows first, the border clamped to the nearest pixel in both directions; frames smaller than the
+ * support are legal.  t = diag(1 / rowsum(M)) P^-1 o_filtered, and Lab follows from t by f as in avx_delta_e_u8, the linear branch
+ * also for the negative t the filters can produce; the form anchored on green does not apply.  Taps, weights, P M and P^-1 are formed
+ * in float64 and rounded once to float32; the sums are float32 fused multiply-adds over the taps in index order.
+ * Every pixel of either frame goes through the same operations, so a pixel whose (2R + 1)^2 neighbourhood is the same in A and B has
+ * dE exactly 0, and identical frames give an all-zero record and a black PLAIN map.  As for avx_delta_e_u8, a frame's record, map and
+ * values do not depend on its batch, its place in the batch, the alignment of the buffers or the run.  The workspace scratch holds 56
+ * bytes per pixel of a frame pair; a batch is walked in groups of pairs, sized by H and W alone, that keep it at or below 1 GiB (one
+ * pair above 19 Mpixel is walked alone and takes more).
+ * AVX_ERR_INVALID (avx_last_error starts with this function's name) as for avx_delta_e_u8, and for a ppd outside 2..128 or not finite. */
+int avx_scielab_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, double ppd, int mode, float gain,
+                   float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

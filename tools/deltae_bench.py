@@ -1,22 +1,26 @@
-"""Time of the colour difference kernel.  Not part of bench.py.
+"""Time of the colour difference kernels.  Not part of bench.py.
 
-  python tools/deltae_bench.py kernel [--reps 7]
+  python tools/deltae_bench.py kernel [--reps 7] [--ppd 60 [--ppd 30 ...]]
       avx_delta_e_u8 on frames resident on the device, 4K and 1080p, batches of 8: records only (no map), the heat map, the heat map
       side by side, and records only on a pair whose upper half is identical (those pixels are 0 by definition and skip the
       arithmetic), interleaved in one process with avx_frame_metrics_u8(with_ssim = 1) on the same frames -- per repetition each form
       once, each between its own pair of stream events (the record memset and the final launch included), after one warm-up call of
       each.  One JSON line per (size, form): median (min-max) in us per frame, ns per pixel, and the ratio to the SSIM record kernel.
       The frames are noise against the same noise +-2 codes: fewer than 1 % of the pixels are equal, so every wave does the arithmetic.
-  python tools/deltae_bench.py command [--frames 32] [--reps 3] [--dir DIR]
+      Each --ppd X adds avx_scielab_u8 at X pixels per degree to the same interleaved repetitions, records only and with the heat map
+      (the row pass, the column pass and the final launch between one pair of events); its lines also carry the ratio to the plain dE
+      records and the fused multiply-adds per pixel pair of the two filter passes, 28 (2 ceil(X / 2) + 1).
+  python tools/deltae_bench.py command [--frames 32] [--reps 3] [--dir DIR] [--ppd X]
       Two 4K nv12 files of `frames` frames in DIR (default: /dev/shm when there is one, so they are read from and written to memory)
       through python -m animal_vision_amd.deltae's main(), --batch 8 --depth 2: no OUT (statistics only), heat into a raw nv12 file (the
       map encoded on the device, 1.5 B/px back across PCIe), heat side by side into nv12, and heat into a .npy file (RGB, 3 B/px
       back): frames per second of the whole command (read, upload, decode, dE, encode, download, write), `reps` runs each after one
-      warm-up run."""
+      warm-up run.  With --ppd X the statistics-only and the nv12 heat runs are repeated with --ppd X."""
 import argparse
 import contextlib
 import io
 import json
+import math
 import os
 import sys
 import tempfile
@@ -38,7 +42,7 @@ def _pair(n, H, W, seed=0):
 
 
 def kernel(args):
-    from animal_vision_amd.metrics import DELTA_E_RECORD_BYTES, RECORD_BYTES, delta_e_launch, frame_metrics_launch
+    from animal_vision_amd.metrics import DELTA_E_RECORD_BYTES, RECORD_BYTES, delta_e_launch, frame_metrics_launch, scielab_launch
     from animal_vision_amd.runtime import get_context
 
     ctx, n = get_context(), 8
@@ -52,9 +56,14 @@ def kernel(args):
         def route(d_other, d_map, layout):
             return lambda: delta_e_launch(ctx, d_a, d_other, n, H, W, d_map, d_rec, mode="heat", layout=layout)
 
+        def filtered(ppd, d_map):
+            return lambda: scielab_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, ppd=ppd, mode="heat", layout="map")
+
         forms = [("records", route(d_b, None, "map")), ("heat map", route(d_b, d_out, "map")), ("heat side", route(d_b, d_out, "side")),
-                 ("records, upper half identical", route(d_half, None, "map")),
-                 ("ssim record", lambda: frame_metrics_launch(ctx, d_a, d_b, n, H, W, d_metrics, ssim=True))]
+                 ("records, upper half identical", route(d_half, None, "map"))]
+        for ppd in args.ppd or []:
+            forms += [(f"scielab records, ppd {ppd:g}", filtered(ppd, None)), (f"scielab heat map, ppd {ppd:g}", filtered(ppd, d_out))]
+        forms.append(("ssim record", lambda: frame_metrics_launch(ctx, d_a, d_b, n, H, W, d_metrics, ssim=True)))
         times = [[] for _ in forms]
         for _, r in forms:  # warm-up: code objects are loaded and the workspaces are sized here
             r()
@@ -64,12 +73,15 @@ def kernel(args):
                 ctx.timer_start()
                 r()
                 times[k].append(ctx.timer_stop() * 1e3 / n)
-        record = float(np.median(times[-1]))
+        record, plain = float(np.median(times[-1])), float(np.median(times[0]))
         for (form, _), t in zip(forms, times):
             med = float(np.median(t))
-            print(json.dumps({"size": name, "form": form, "batch": n, "reps": args.reps, "us_per_frame_median": round(med, 1), "us_per_frame_min": round(min(t), 1),
-                              "us_per_frame_max": round(max(t), 1), "ns_per_px": round(med * 1e3 / (H * W), 4), "over_ssim_record_kernel": round(med / record, 2)}),
-                  flush=True)
+            line = {"size": name, "form": form, "batch": n, "reps": args.reps, "us_per_frame_median": round(med, 1), "us_per_frame_min": round(min(t), 1),
+                    "us_per_frame_max": round(max(t), 1), "ns_per_px": round(med * 1e3 / (H * W), 4), "over_ssim_record_kernel": round(med / record, 2)}
+            if form.startswith("scielab"):
+                fma = 28 * (2 * math.ceil(float(form.rsplit(" ", 1)[1]) / 2) + 1)  # 7 terms x 2 sides x 2 passes, per tap
+                line.update(over_plain_records=round(med / plain, 2), filter_fma_per_px=fma, filter_tflops=round(2 * fma * H * W / med * 1e-6, 2))
+            print(json.dumps(line), flush=True)
         for d in (d_a, d_b, d_half, d_out, d_rec, d_metrics):
             d.free()
 
@@ -89,7 +101,10 @@ def command(args):
                     f.write(pay[i % len(pay)].tobytes())
         argv = [os.path.join(d, "a.yuv"), os.path.join(d, "b.yuv")]
         opts = ["--pix-fmt", "nv12", "--size", f"{W}x{H}", "--batch", "8", "--csv", os.path.join(d, "de.csv")]
-        for out, extra in ((None, []), ("out.yuv", ["--depth", "2"]), ("out.yuv", ["--depth", "2", "--layout", "side"]), ("out.npy", ["--depth", "2"])):
+        runs = [(None, []), ("out.yuv", ["--depth", "2"]), ("out.yuv", ["--depth", "2", "--layout", "side"]), ("out.npy", ["--depth", "2"])]
+        if args.ppd is not None:
+            runs += [(None, ["--ppd", f"{args.ppd:g}"]), ("out.yuv", ["--depth", "2", "--ppd", f"{args.ppd:g}"])]
+        for out, extra in runs:
             fps = []
             for rep in range(args.reps + 1):
                 t0 = time.perf_counter()
@@ -111,10 +126,12 @@ def main():
     sub = ap.add_subparsers(dest="cmd", required=True)
     k = sub.add_parser("kernel")
     k.add_argument("--reps", type=int, default=7)
+    k.add_argument("--ppd", type=float, action="append", default=None, help="add avx_scielab_u8 at this many pixels per degree (repeatable)")
     c = sub.add_parser("command")
     c.add_argument("--frames", type=int, default=32)
     c.add_argument("--reps", type=int, default=3)
     c.add_argument("--dir", default=None)
+    c.add_argument("--ppd", type=float, default=None, help="repeat the statistics-only and the nv12 heat runs with --ppd")
     args = ap.parse_args()
     {"kernel": kernel, "command": command}[args.cmd](args)
 

@@ -183,16 +183,9 @@ class Side:
 
     def enqueue(self, k: int, n: int, stream) -> None:
         """Upload set k's n staged frames and, where they are payloads to decode, decode them into d_rgb[k]."""
-        from .yuv import i420_to_rgb_device, yuv_to_rgb_device
-
         copy(self.ctx, "h2d", self.d_in[k], self.host[k], n * self.unit, stream)
         if self.payload and not self.stored:
-            vr = self.vr
-            if vr.yuv_pix_fmt is None:
-                i420_to_rgb_device(self.ctx, self.d_in[k], self.d_rgb[k], n, self.H, self.W, matrix=vr.matrix, range=vr.yuv_range, stream=stream)
-            else:
-                yuv_to_rgb_device(self.ctx, self.fmt, self.d_in[k], self.d_rgb[k], n, self.H, self.W, matrix=vr.matrix, range=vr.yuv_range,
-                                  stream=stream)
+            self.vr.decode.launch(self.ctx, self.d_in[k], self.d_rgb[k], n, self.H, self.W, stream)
 
     def free(self) -> None:
         for b in self.d_rgb + (self.d_in if self.payload else []) + self.host:
@@ -271,7 +264,7 @@ def stream_map_pairs(args, info: dict, name: str, fmt: Optional[str], launch: Ca
     None, else the flat payload the device encoded the map to ("i420", or a raw pixel format name).  info["hw"] is the output
     frames' (H, W) once the first item is there.  launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, stream) enqueues the command's
     kernel (d_map: None without a map); records(bytes, n) reads n records of rec_bytes; check_size(H, W) refuses a frame size."""
-    from .yuv import frame_size, i420_size, rgb_to_i420_device, rgb_to_yuv_device
+    from .yuv import Encode
 
     def prepare(H, W):
         if check_size is not None:
@@ -279,18 +272,16 @@ def stream_map_pairs(args, info: dict, name: str, fmt: Optional[str], launch: Ca
         with_map = args.out is not None
         Wo = 3 * W if args.layout == "side" else W
         info["hw"] = (H, Wo)
-        unit = H * Wo * 3 if fmt is None else (i420_size(H, Wo) if fmt == "i420" else frame_size(fmt, H, Wo))
-        matrix, yrange = out_matrix(args), args.range or "limited"
+        encode = None if fmt is None else Encode(None if fmt == "i420" else fmt, out_matrix(args), args.range or "limited")
+        unit = H * Wo * 3 if fmt is None else encode.frame_bytes(H, Wo)
         # the map (downloaded as it is where the sink takes RGB), the payload it is encoded to, the records
         outputs = ([(H * Wo * 3, fmt is None)] if with_map else []) + ([(unit, True)] if fmt is not None else []) + [(rec_bytes, True)]
 
         def enqueue(k, n, stream, sides, outs):
             ctx = sides[0].ctx
             launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, outs[0] if with_map else None, outs[-1], stream)
-            if fmt == "i420":
-                rgb_to_i420_device(ctx, outs[0], outs[1], n, H, Wo, matrix=matrix, range=yrange, stream=stream)
-            elif fmt is not None:
-                rgb_to_yuv_device(ctx, fmt, outs[0], outs[1], n, H, Wo, matrix=matrix, range=yrange, stream=stream)
+            if encode is not None:
+                encode.launch(ctx, outs[0], outs[1], n, H, Wo, stream)
 
         def harvest(n, arrays):
             recs = records(arrays[-1], n)

@@ -116,7 +116,7 @@ class FramePipeline:
                  labels: Optional[Tuple[Optional[str], Optional[str]]] = ("Original", "Transformed"), io_format: str = "rgb",
                  matrix: str = "bt601", yuv_range: str = "limited", split_baseline: bool = False, batch: int = 1,
                  pix_fmt: Optional[str] = None, transfer: Optional[str] = None, tonemap: str = "mobius", peak_nits: float = 1000.0,
-                 sdr_white: float = 203.0, out_matrix: Optional[str] = None, scale: Optional[Tuple[int, int]] = None):
+                 sdr_white: float = 203.0, out_matrix: Optional[str] = None, scale: Optional[Tuple[int, int]] = None, decode=None, encode=None):
         """split_compare: emit make_split_frame(original, transformed) composed on the device (renderers/video.py:198-245:
         halves, seam, and the two corner labels -- `labels` = (left, right), None = none) instead of the transformed frame.
 
@@ -127,17 +127,20 @@ class FramePipeline:
         §4.9) and the conversions of csrc/yuv_raw.hip.  Format names go in `pix_fmt`, not in io_format.
 
         transfer: "pq" or "hlg" -- the payloads are HDR (BT.2020, 10-bit `pix_fmt`, io_format="yuv"): the slot stream decodes
-        them through yuv.yuv_hdr_to_rgb_device with `tonemap`, `peak_nits` and `sdr_white` instead of `matrix`, and
-        the op sees tone-mapped SDR frames.  The output side is SDR: it is encoded by rgb_to_yuv_device in `out_matrix`, which
-        defaults to "bt709" with a transfer and to `matrix` without one.  With transfer=None nothing else changes.
+        them with `tonemap`, `peak_nits` and `sdr_white` instead of `matrix`, and the op sees tone-mapped SDR frames.
+        The output side is SDR: it is encoded in `out_matrix`, which defaults to "bt709" with a transfer and to `matrix` without
+        one.  With transfer=None nothing else changes.
 
         scale: (Wd, Hd), in the order of the video command's --size -- frames are read at H x W and reduced to Hd x Wd (cv2's
         INTER_AREA; never enlarged) on the slot stream before the op sees them.  H, W stay the source size; the
         slot's RGB buffers, the op, the split composition, the labels and everything on the way out (`out_H`, `out_W`, the
         emitted frames or payloads) have the scaled size.  io_format="yuv" / "i420" decode straight to the scaled frame
-        (yuv.yuv_to_rgb_scaled_device, or with a `transfer` yuv.yuv_hdr_to_rgb_scaled_device, DESIGN §4.13: one launch per slot,
-        no full-size RGB frame); io_format="rgb" frames land in a source-size buffer of the slot and go through avx_resize_hwc
-        frame by frame.  With scale=None nothing changes.
+        (with a `transfer` §4.13: one launch per slot, no full-size RGB frame); io_format="rgb" frames land in a
+        source-size buffer of the slot and go through avx_resize_hwc frame by frame.  With scale=None nothing changes.
+
+        decode, encode: a yuv.Decode and a yuv.Encode, in place of all the format keywords above (naming both is refused).  The
+        keywords are turned into the same pair (yuv.codec); `decode` and `encode` hold it, and their launch() is what the slot stream
+        runs, so which C entry point a combination reaches is decided in yuv.py alone.
 
         split_baseline: the split frame's left half is the op's own baseline -- `op.slot_baseline(k)`, the frame a species'
         visualize() returns first (a UV species' panorama-warped input, SpeciesStreamOp) -- instead of the input frame.
@@ -148,39 +151,41 @@ class FramePipeline:
         op states how many frames one call takes in `max_batch` (absent: 1); an op that cannot take `batch` is refused here.
 
         An op whose output is not the size of its input says so with `out_shape(H, W) -> (Hc, Wc)` (wall.WallStreamOp: the labelled
-        grid of several species): the slot's d_out, the pinned output staging, the encode of from_rgb and the emitted frames or
+        grid of several species): the slot's d_out, the pinned output staging, the encode and the emitted frames or
         payloads then have that size, and so have `out_H` / `out_W`; `op_H` / `op_W` name what the op is handed, and StreamStats
         still counts those pixels.  split_compare composes two frames of one size: with such an op it is refused.  An op without
         out_shape changes nothing here."""
         from .runtime import get_context
-        from .yuv import PIX_FMTS, _codes, check_scale, frame_size, hdr_codes, i420_size
+        from .yuv import PIX_FMTS, codec
 
-        if io_format not in ("rgb", "i420", "yuv"):
-            raise ValueError(f"io_format must be 'rgb', 'i420' or 'yuv' (got {io_format!r})")
-        if io_format == "yuv" and pix_fmt not in PIX_FMTS:
-            raise ValueError(f"io_format='yuv' needs pix_fmt, one of {', '.join(PIX_FMTS)} (got {pix_fmt!r})")
-        if io_format != "yuv" and pix_fmt is not None:
-            raise ValueError(f"pix_fmt goes with io_format='yuv' (got io_format={io_format!r})")
-        _codes(matrix, yuv_range)
-        if transfer is not None:
-            if io_format != "yuv":
+        if decode is not None or encode is not None:
+            import inspect
+
+            given = dict(io_format=io_format, pix_fmt=pix_fmt, matrix=matrix, yuv_range=yuv_range, transfer=transfer, tonemap=tonemap,
+                         peak_nits=peak_nits, sdr_white=sdr_white, out_matrix=out_matrix, scale=scale)
+            defaults = inspect.signature(FramePipeline.__init__).parameters
+            named = [k for k, v in given.items() if v != defaults[k].default]
+            if named or decode is None or encode is None:
+                raise ValueError("decode= and encode= go together and take the place of the format keywords "
+                                 f"(got {', '.join(named) or 'one of the two'})")
+            io_format, pix_fmt = ("i420" if decode.pix_fmt is None else "yuv"), decode.pix_fmt
+        else:
+            if io_format not in ("rgb", "i420", "yuv"):
+                raise ValueError(f"io_format must be 'rgb', 'i420' or 'yuv' (got {io_format!r})")
+            if io_format == "yuv" and pix_fmt not in PIX_FMTS:
+                raise ValueError(f"io_format='yuv' needs pix_fmt, one of {', '.join(PIX_FMTS)} (got {pix_fmt!r})")
+            if io_format != "yuv" and pix_fmt is not None:
+                raise ValueError(f"pix_fmt goes with io_format='yuv' (got io_format={io_format!r})")
+            if transfer is not None and io_format != "yuv":
                 raise ValueError(f"transfer={transfer!r} goes with io_format='yuv' and a 10-bit pix_fmt (got io_format={io_format!r})")
-            hdr_codes(pix_fmt, transfer, yuv_range, tonemap, peak_nits, sdr_white)
-        if out_matrix is None:
-            out_matrix = "bt709" if transfer is not None else matrix
-        _codes(out_matrix, yuv_range)
-        self.transfer, self.tonemap, self.peak_nits, self.sdr_white, self.out_matrix = transfer, tonemap, float(peak_nits), float(sdr_white), out_matrix
-        self.io_format, self.matrix, self.yuv_range, self.pix_fmt = io_format, matrix, yuv_range, pix_fmt
+            # io_format="rgb" holds the pair too: its settings are checked all the same, and its Decode carries the scale
+            decode, encode = codec(pix_fmt, matrix, yuv_range, transfer, tonemap, peak_nits, sdr_white, out_matrix, scale)
+        self.decode, self.encode, self.io_format, self.pix_fmt = decode, encode, io_format, pix_fmt
+        self.matrix, self.yuv_range, self.out_matrix = decode.matrix, decode.range, encode.matrix
+        self.transfer, self.tonemap, self.peak_nits, self.sdr_white = decode.transfer, decode.tonemap, float(decode.peak_nits), float(decode.sdr_white)
         self.op, self.H, self.W, self.depth = op, H, W, depth
-        if scale is not None:
-            try:
-                Wd, Hd = scale
-            except (TypeError, ValueError):
-                raise ValueError(f"scale is (Wd, Hd) (got {scale!r})")
-            check_scale(H, W, Hd, Wd)
-            scale = (int(Wd), int(Hd))
-        self.scale = scale
-        self.op_H, self.op_W = (scale[1], scale[0]) if scale is not None else (H, W)  # what the op is handed
+        self.op_H, self.op_W = decode.out_hw(H, W)  # what the op is handed
+        self.scale = scale = None if decode.scale is None else (self.op_W, self.op_H)
         shape_of = getattr(op, "out_shape", None)
         if shape_of is not None and split_compare:
             raise ValueError(f"split_compare: {type(op).__name__}'s output has a size of its own (out_shape); there is no frame to compare it with")
@@ -205,11 +210,10 @@ class FramePipeline:
         lend = getattr(op, "slot_buffers", None)
         self._lent = lend is not None
         self.slots = []
-
-        def io_shape(h, w):
-            return (h, w, 3) if io_format == "rgb" else ((i420_size(h, w),) if io_format == "i420" else (frame_size(pix_fmt, h, w),))
-
-        self._in_shape, self._io_shape = io_shape(H, W), io_shape(oH, oW)  # frames in (source size), frames out
+        if io_format == "rgb":
+            self._in_shape, self._io_shape = (H, W, 3), (oH, oW, 3)  # frames in (source size), frames out
+        else:
+            self._in_shape, self._io_shape = (decode.frame_bytes(H, W),), (encode.frame_bytes(oH, oW),)
         full = scale is not None and io_format == "rgb"
         for k in range(depth):
             d_in, d_out = lend(k) if lend else (self.ctx.malloc(nbytes), self.ctx.malloc(out_nbytes))
@@ -256,15 +260,12 @@ class FramePipeline:
         """frames: (global index, HxWx3 uint8 -- or, io_format="i420" / "yuv", a flat payload) pairs owned by this rank;
         emit(index, out) in submission order, `out` in the same format."""
         from ._lib import lib
-        from .yuv import (i420_to_rgb_device, rgb_to_i420_device, rgb_to_yuv_device, yuv_hdr_to_rgb_device, yuv_hdr_to_rgb_scaled_device,
-                          yuv_to_rgb_device, yuv_to_rgb_scaled_device)
 
         ctx, n, t0 = self.ctx, 0, time.perf_counter()
         self._copy_s = 0.0
         for s in self.slots:  # a run that ended in an error may have left a half-filled slot behind
             s.busy, s.indices = False, []
         i420 = self.io_format != "rgb"  # payloads cross the host and PCIe; RGB exists on the device only
-        kw = dict(matrix=self.matrix, range=self.yuv_range)
         iH, iW, oH, oW = self.op_H, self.op_W, self.out_H, self.out_W  # the op's input (the scaled frame), its output
         src_rgb_bytes = self.H * self.W * 3
 
@@ -274,32 +275,6 @@ class FramePipeline:
                 ctx._check(lib.avx_resize_hwc(ctx._h, s.d_full.ptr + f * src_rgb_bytes, 2, self.H, self.W, 3, s.d_in.ptr + f * iH * iW * 3, iH, iW, 3,
                                               s.stream))
 
-        if self.io_format == "yuv":
-            def to_rgb(s, m):
-                if self.transfer is not None:
-                    hdr = dict(transfer=self.transfer, range=self.yuv_range, tonemap=self.tonemap, peak_nits=self.peak_nits,
-                               sdr_white=self.sdr_white, stream=s.stream)
-                    if self.scale is not None:
-                        yuv_hdr_to_rgb_scaled_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, iH, iW, **hdr)
-                    else:
-                        yuv_hdr_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, **hdr)
-                elif self.scale is not None:
-                    yuv_to_rgb_scaled_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, iH, iW, stream=s.stream, **kw)
-                else:
-                    yuv_to_rgb_device(ctx, self.pix_fmt, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
-
-            def from_rgb(s, m):
-                rgb_to_yuv_device(ctx, self.pix_fmt, s.d_out, s.d_yuv_out, m, oH, oW, stream=s.stream, matrix=self.out_matrix,
-                                  range=self.yuv_range)
-        else:
-            def to_rgb(s, m):
-                if self.scale is not None:  # yuv420p is the I420 payload, byte for byte (include/avx.h)
-                    yuv_to_rgb_scaled_device(ctx, "yuv420p", s.d_yuv_in, s.d_in, m, self.H, self.W, iH, iW, stream=s.stream, **kw)
-                else:
-                    i420_to_rgb_device(ctx, s.d_yuv_in, s.d_in, m, self.H, self.W, stream=s.stream, **kw)
-
-            def from_rgb(s, m):
-                rgb_to_i420_device(ctx, s.d_out, s.d_yuv_out, m, oH, oW, stream=s.stream, **kw)
         in_bytes, fbytes = int(np.prod(self._in_shape)), int(np.prod(self._io_shape))
         rgb_bytes = oH * oW * 3
 
@@ -308,7 +283,7 @@ class FramePipeline:
             m = len(s.indices)
             if i420:
                 ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_yuv_in.ptr, s.h_in.ptr, m * in_bytes, s.stream))
-                to_rgb(s, m)
+                self.decode.launch(ctx, s.d_yuv_in, s.d_in, m, self.H, self.W, s.stream)
             elif self.scale is not None:
                 ctx._check(lib.avx_memcpy_h2d(ctx._h, s.d_full.ptr, s.h_in.ptr, m * in_bytes, s.stream))
                 reduce_full(s, m)
@@ -324,7 +299,7 @@ class FramePipeline:
 
                         draw_split_labels_device(ctx, s.d_out.ptr + o, oH, oW, self.labels[0], self.labels[1], s.stream)
             if i420:
-                from_rgb(s, m)
+                self.encode.launch(ctx, s.d_out, s.d_yuv_out, m, oH, oW, s.stream)
                 ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_yuv_out.ptr, m * fbytes, s.stream))
             else:
                 ctx._check(lib.avx_memcpy_d2h(ctx._h, s.h_out.ptr, s.d_out.ptr, m * fbytes, s.stream))
@@ -365,11 +340,10 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
     ordered stream ("host re-orders outputs by frame index before render()").
 
     A renderer whose frames can stay I420 end to end (`yuv_hw` not None: renderers.VideoRenderer from a .y4m to a .y4m) hands
-    over get_yuv() payloads, and the pipeline runs with io_format="i420" in the renderer's `matrix` and `yuv_range`.
-    When that renderer names a raw pixel format (`yuv_pix_fmt`: raw video in and out in one format), the pipeline runs with
-    io_format="yuv" in that format, and with the renderer's HDR settings (`transfer`, `tonemap`, `peak_nits`, `sdr_white`,
-    `out_matrix`) when it has them.  A renderer with a `scale` hands its payloads over at the source size and the
-    pipeline reduces them as it decodes (FramePipeline scale=); the frames get_image() returns are scaled already.
+    over get_yuv() payloads, and the pipeline runs with the renderer's own `decode` and `encode` (yuv.Decode, yuv.Encode): I420, or the
+    raw pixel format the renderer names (raw video in and out in one format), with its HDR settings when it has
+    them.  A renderer with a `scale` hands its payloads over at the source size and the pipeline reduces them as it decodes
+    (DESIGN §4.11); the frames get_image() returns are scaled already.
     split_baseline, batch (frames per slot and per op call): see FramePipeline.  Where the op has an output size of its own
     (FramePipeline: out_shape) the renderer is told so (set_output_size) before the first frame is rendered."""
     self_sharding = getattr(renderer, "world", 1) == world and getattr(renderer, "rank", 0) == rank and hasattr(renderer, "last_index") and world > 1
@@ -381,15 +355,8 @@ def run_video(animal_op, renderer, *, rank: int = 0, world: int = 1, depth: int 
         pipe = None
     elif yuv_hw is not None:
         H, W = yuv_hw
-        fmt = getattr(renderer, "yuv_pix_fmt", None)
-        hdr = {}
-        if fmt and getattr(renderer, "transfer", None) is not None:
-            hdr = dict(transfer=renderer.transfer, tonemap=renderer.tonemap, peak_nits=renderer.peak_nits, sdr_white=renderer.sdr_white)
-        if fmt and getattr(renderer, "out_matrix", None) is not None:
-            hdr["out_matrix"] = renderer.out_matrix
-        pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, io_format="yuv" if fmt else "i420",
-                             pix_fmt=fmt, matrix=renderer.matrix, yuv_range=renderer.yuv_range, split_baseline=split_baseline, batch=batch,
-                             scale=getattr(renderer, "scale", None), **hdr)
+        pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, split_baseline=split_baseline, batch=batch,
+                             decode=renderer.decode, encode=renderer.encode)
     else:
         H, W, _ = first.shape
         pipe = FramePipeline(animal_op, H, W, depth=depth, split_compare=split_compare, labels=labels, split_baseline=split_baseline, batch=batch)

@@ -11,8 +11,9 @@ No preview window (no GUI); `window_name` is accepted and ignored.
 
 Y4M (renderers/y4m.py): get_image() still returns RGB uint8 HxWx3, converted from the I420 payload on the device (yuv.py);
 get_yuv() hands over the payload itself, and render() takes RGB frames (converted on the device) or payloads.  `matrix` and
-`range` name the conversion; range None = the source's XCOLORRANGE tag, else limited.  The sink echoes the
-source's header (size, rate, aspect, colour range, unknown tags) when the source is a .y4m.
+`range` name the conversion; range None = the source's XCOLORRANGE tag, else limited.  Every conversion goes through
+the `decode` and `encode` properties (yuv.Decode, yuv.Encode), which the constructor's settings are made into once.  The sink
+echoes the source's header (size, rate, aspect, colour range, unknown tags) when the source is a .y4m.
 
 Raw video (renderers/rawvideo.py): `pix_fmt` and `size=(W, H)` read `read_path` (a file, "-" or a FIFO) as headerless
 frames in one of yuv.PIX_FMTS (nv12, p010le, yuv422p, ...); `write_pix_fmt` writes `write_path` the same way, and defaults to
@@ -20,16 +21,16 @@ frames in one of yuv.PIX_FMTS (nv12, p010le, yuv422p, ...); `write_pix_fmt` writ
 goes through RGB.
 
 HDR sources: `transfer` ("pq" or "hlg") reads a raw 10-bit source as BT.2020 HDR video.  get_image() then returns
-the tone-mapped SDR frame of yuv.yuv_hdr_to_rgb (`tonemap`, `peak_nits`, `sdr_white`; `matrix` plays no part in the decode), so
+the tone-mapped SDR frame of the HDR decode (`tonemap`, `peak_nits`, `sdr_white`; `matrix` plays no part in the decode), so
 the per-frame species get it too, and every YUV sink is encoded in `out_matrix`: "bt709" by default with a transfer, `matrix`
 without one.
 
 Scaling: `scale=(Wd, Hd)` reduces every source's frames to Wd x Hd (cv2's INTER_AREA; enlarging is refused).
-get_image() returns scaled frames -- raw and .y4m sources through yuv.yuv_to_rgb_scaled, which decodes straight to the scaled
-frame; HDR sources through yuv.yuv_hdr_to_rgb_scaled, which does the same; the other sources through the resize
-alone.  get_yuv() still hands over source-size payloads and `yuv_hw` still names the source size (pipeline.run_video reduces them
-as it decodes); `out_hw` names the size of what comes out, and every sink is written at that size -- unless the operator that runs
-between source and sink has an output size of its own (the species wall): set_output_size() then names the sinks' size (`sink_hw`).
+get_image() returns scaled frames -- raw and .y4m sources, HDR ones too, through the scaled decode, which goes
+straight to the scaled frame; the other sources through the resize alone.  get_yuv() still hands over source-size payloads and
+`yuv_hw` still names the source size (pipeline.run_video reduces them as it decodes); `out_hw` names the size of what comes out,
+and every sink is written at that size -- unless the operator that runs between source and sink has an output size of its own (the
+species wall): set_output_size() then names the sinks' size (`sink_hw`).
 
 Sharded streams (two keywords the reference does not have, both defaulted): with `world` > 1 this renderer
 serves and stores only the frames of rank `rank` (global frame i belongs to rank i mod world) -- every source here is
@@ -39,6 +40,7 @@ memory-mapped shard per rank (streamed to disk frame by frame, never held in RAM
 by pipeline.run_video after the ranks' closing collective -- interleaves them into the one ordered stream."""
 from __future__ import annotations
 
+import dataclasses
 import os
 from typing import List, Optional
 
@@ -100,32 +102,21 @@ class VideoRenderer(Renderer):
             raise ValueError("a raw video source is named by both pix_fmt and size=(W, H)")
         if write_pix_fmt is None and pix_fmt is not None and is_raw_sink(write_path):
             write_pix_fmt = pix_fmt
-        from ..yuv import MATRICES, PIX_FMTS, hdr_codes
+        from ..yuv import codec
 
-        for f in (pix_fmt, write_pix_fmt):
-            if f is not None and f not in PIX_FMTS:
-                raise ValueError(f"pix_fmt must be one of {', '.join(PIX_FMTS)} (got {f!r})")
+        # the settings of every conversion, checked here; the range may still come from a .y4m header (the decode and encode properties)
+        self._decode, enc = codec(pix_fmt, matrix, range or "limited", transfer, tonemap, peak_nits, sdr_white, out_matrix, scale)
+        self._encode = dataclasses.replace(enc, pix_fmt=write_pix_fmt if write_path else pix_fmt)  # the sink's format; the source's without a sink
         if write_pix_fmt is not None and not write_path:
             raise ValueError("write_pix_fmt needs a write_path")
-        if transfer is not None:  # an HDR source: raw, 10-bit, BT.2020
-            hdr_codes(pix_fmt, transfer, range or "limited", tonemap, peak_nits, sdr_white)
-        if out_matrix is None:
-            out_matrix = "bt709" if transfer is not None else matrix
-        if out_matrix not in MATRICES:
-            raise ValueError(f"out_matrix must be one of {sorted(MATRICES)} (got {out_matrix!r})")
-        self.transfer, self.tonemap, self.peak_nits, self.sdr_white, self.out_matrix = transfer, tonemap, float(peak_nits), float(sdr_white), out_matrix
+        self.transfer, self.tonemap, self.peak_nits, self.sdr_white, self.out_matrix = transfer, tonemap, float(peak_nits), float(sdr_white), enc.matrix
         self.pix_fmt, self.write_pix_fmt = pix_fmt, write_pix_fmt
         self.size = None if size is None else (int(size[0]), int(size[1]))
         if scale is not None:
-            from ..yuv import check_scale
-
-            try:
-                Wd, Hd = scale
-            except (TypeError, ValueError):
-                raise ValueError(f"scale is (Wd, Hd) (got {scale!r})")
             # a raw source names its size here; the other sources are checked when their size is known (open(), get_image())
-            check_scale(self.size[1] if self.size else Hd, self.size[0] if self.size else Wd, Hd, Wd)
-            scale = (int(Wd), int(Hd))
+            Ws, Hs = self.size or self._decode.scale
+            Hd, Wd = self._decode.out_hw(Hs, Ws)
+            scale = (Wd, Hd)
         self.scale = scale
         self._raw = None             # renderers.rawvideo.RawVideoReader
         self._raw_out = None         # renderers.rawvideo.RawVideoWriter (created by the first render)
@@ -188,6 +179,19 @@ class VideoRenderer(Renderer):
         if self._range is not None:
             return self._range
         return "full" if self._y4m is not None and self._y4m.header.full_range else "limited"
+
+    @property
+    def decode(self):
+        """The yuv.Decode of this source's payloads (raw video, or the I420 of a .y4m) into the frames get_image() returns: what
+        get_image() runs, and what pipeline.run_video and the pair commands launch on payloads they upload themselves.  Read it after
+        open(): the range may be the .y4m header's."""
+        return dataclasses.replace(self._decode, range=self.yuv_range)
+
+    @property
+    def encode(self):
+        """The yuv.Encode of RGB frames into what the sink takes -- write_pix_fmt, else I420 -- or, without a sink, into the source's
+        format (payloads in, payloads out), in `out_matrix`.  Read it after open(), as `decode`."""
+        return dataclasses.replace(self._encode, range=self.yuv_range)
 
     @property
     def y4m_header(self):
@@ -265,32 +269,12 @@ class VideoRenderer(Renderer):
         return f
 
     def get_image(self) -> Optional[np.ndarray]:
-        if self._raw is not None:
+        if self._raw is not None or self._y4m is not None:
             f = self.get_yuv()
             if f is None:
                 return None
-            from ..yuv import yuv_hdr_to_rgb, yuv_hdr_to_rgb_scaled, yuv_to_rgb, yuv_to_rgb_scaled
-
-            if self.transfer is not None:
-                hdr = dict(pix_fmt=self.pix_fmt, transfer=self.transfer, range=self.yuv_range, tonemap=self.tonemap, peak_nits=self.peak_nits,
-                           sdr_white=self.sdr_white)
-                if self.scale is not None:
-                    return yuv_hdr_to_rgb_scaled(f, self._raw.height, self._raw.width, self.scale[1], self.scale[0], **hdr)
-                return yuv_hdr_to_rgb(f, self._raw.height, self._raw.width, **hdr)
-            if self.scale is not None:
-                return yuv_to_rgb_scaled(f, self._raw.height, self._raw.width, self.scale[1], self.scale[0], pix_fmt=self.pix_fmt,
-                                         matrix=self.matrix, range=self.yuv_range)
-            return yuv_to_rgb(f, self._raw.height, self._raw.width, pix_fmt=self.pix_fmt, matrix=self.matrix, range=self.yuv_range)
-        if self._y4m is not None:
-            f = self.get_yuv()
-            if f is None:
-                return None
-            from ..yuv import i420_to_rgb, yuv_to_rgb_scaled
-
-            if self.scale is not None:  # yuv420p is the I420 payload, byte for byte
-                return yuv_to_rgb_scaled(f, self._y4m.header.height, self._y4m.header.width, self.scale[1], self.scale[0], pix_fmt="yuv420p",
-                                         matrix=self.matrix, range=self.yuv_range)
-            return i420_to_rgb(f, self._y4m.header.height, self._y4m.header.width, matrix=self.matrix, range=self.yuv_range)
+            src = self._raw if self._raw is not None else self._y4m.header
+            return self.decode.arrays(f, src.height, src.width)
         if self._src is not None:
             f = self._src.get_image()
             if f is not None:
@@ -349,9 +333,7 @@ class VideoRenderer(Renderer):
             if frame.dtype != np.uint8 or frame.shape[2] != 3:
                 raise ValueError(f"a .y4m sink takes RGB uint8 HxWx3 frames or I420 payloads, got {frame.dtype} {frame.shape}")
             H, W = frame.shape[:2]
-            from ..yuv import rgb_to_i420
-
-            payload = rgb_to_i420(frame, matrix=self.out_matrix, range=self.yuv_range)
+            payload = self.encode.arrays(frame)
         elif frame.ndim == 1 and frame.dtype == np.uint8:
             if self._y4m_out is None and self._y4m is None and self._sink_hw is None:
                 raise ValueError("an I420 payload names no frame size: render an RGB frame first, read from a .y4m, or call set_output_size()")
@@ -375,9 +357,7 @@ class VideoRenderer(Renderer):
         frame = np.asarray(frame)
         if frame.ndim == 3 and frame.dtype == np.uint8 and frame.shape[2] == 3:
             H, W = frame.shape[:2]
-            from ..yuv import rgb_to_yuv
-
-            payload = rgb_to_yuv(frame, pix_fmt=self.write_pix_fmt, matrix=self.out_matrix, range=self.yuv_range)
+            payload = self.encode.arrays(frame)
         elif frame.ndim == 1 and frame.dtype == np.uint8:
             if self._raw_out is None and self._sink_hw is None and (self._raw is None or self.pix_fmt != self.write_pix_fmt):
                 raise ValueError(f"a {self.write_pix_fmt} payload names no frame size: render an RGB frame first, read raw video in that "

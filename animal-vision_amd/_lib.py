@@ -393,8 +393,11 @@ _SIGS = {
     "avx_mst_conv3x3_lds_spectral": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _fp, _i, _i, _i, _i, _vp, _vp, ctypes.POINTER(ctypes.c_int), _vp]),
     "avx_mst_ffn_fused_mx": (_i, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "avx_mst_ffn_fused_sp": (_i, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "avx_mst_ffn_fused_mx_col": (_i, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "avx_mst_ffn_fused_sp_col": (_i, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "avx_mst_gelu_prescale": (ctypes.c_float, []),
     "avx_mst_tile_order": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_longlong), _i, ctypes.POINTER(ctypes.c_int)]),
+    "avx_mst_tile_order_col": (_i, [_i, _i, _i, _i, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_ubyte), _i, ctypes.POINTER(ctypes.c_int)]),
     "avx_mst_dw_gemm_add": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "avx_dwconv3x3_nhwc_add": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "avx_dwconv3x3_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

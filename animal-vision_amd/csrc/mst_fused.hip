@@ -58,7 +58,8 @@ __device__ __forceinline__ float16_t mfma16(half8_t a, half8_t b, float16_t c) {
 
 struct Tile { int x0, y0; long b; };
 // TileWalk (mst_tile_order.h): the tiles of a (frames x ty x tx) grid this workgroup visits, raster or XCD-aware order, WITHOUT a division per tile.
-__device__ __forceinline__ Tile tile_at(const TileWalk& wk, int side_x, int side_y) { return Tile{wk.xi * side_x, wk.yi * side_y, (long)wk.b}; }
+template <class Walk>
+__device__ __forceinline__ Tile tile_at(const Walk& wk, int side_x, int side_y) { return Tile{wk.xi * side_x, wk.yi * side_y, (long)wk.b}; }
 // AVX_MST_TILE_ORDER=raster (read per call, like the AVX_MST_NO_* switches): the round-2 order, so that one process can compare both.  The results do not depend on it.
 int mst_tile_order() {
     const char* e = getenv("AVX_MST_TILE_ORDER");
@@ -108,19 +109,30 @@ __device__ __forceinline__ half8_t dw_frag(const uint4* p, int i) {
 // NW: waves per workgroup.  8 everywhere in round 2; 16 (one 1024-thread workgroup per CU, 128 registers per lane) for the 62-channel blocks since round 3: their
 // 143 KB of LDS admit one workgroup per CU, and at 8 waves the vector unit saw 2 waves per SIMD -- half of what it needs to issue back to back.  With 16 waves a pass's
 // 16 octets map one to a wave in phase 2a, the 44 phase 1 items are 3 + 3 + 3 + 2 per channel tile, and in phase 2b a wave owns a row pair x ONE 32-channel output tile.
-template <int C, int HPASS, int MINW, bool DWM, bool STAMP = false, int NW = 8, bool DWS = false>
+// MARCH (round 10): the column-marching form.  Tiles are 16 x 14 and a workgroup walks a run of the column-major order (ColumnWalk) downwards, so the hidden rows of
+// image rows y0 - 1 and y0 -- halo rows 0 and 1 -- are halo rows 14 and 15 of the tile above, which phase 2a's in-place stores (rows 0 ... 13) leave intact.  A
+// steady step therefore runs LayerNorm and phase 1 on halo rows 2 ... 15 only: 18 x 14 = 252 pixels = 8 groups of 32, TWO phase 1 items and ONE LayerNorm group
+// per wave where the 16-row tile's 324 pixels need three and two.  ht is reused by every pass, so phase 2b parks the
+// two rows of each pass in `carry`, and phase 1 of the same pass of the next tile brings them back behind the top barrier: no barrier is added to a step.  At a
+// segment start (a workgroup's first tile, the top of a column) the two rows are not on chip: they are primed -- LayerNorm + phase 1 of those 36 pixels per pass,
+// straight into `carry` -- at the price of two barriers and no prefetch, about once in 70 tiles at 4K.  Every hidden pixel, the second GEMM's K order and the
+// residual are what the 16-row kernel computes: the results are the same to the bit.
+template <bool MARCH> struct FfnWalk { typedef TileWalk type; };
+template <> struct FfnWalk<true> { typedef ColumnWalk type; };
+template <int C, int HPASS, int MINW, bool DWM, bool STAMP = false, int NW = 8, bool DWS = false, bool MARCH = false>
 __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* __restrict__ x /*[B][H][W][C]*/, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           float eps, const uint4* __restrict__ w1pack /*[4C/32][C/16][64]*/, const __half* __restrict__ taps /*[9][4C]*/,
                                                           const uint4* __restrict__ w2pack /*[C/32][4C/16][64]*/, __half* __restrict__ out /*[B][H][W][C], != x*/, int B,
                                                           int H, int W, const uint4* __restrict__ dwpack /*[4C/8][3][64], DWM only*/, unsigned long long* __restrict__ stamps /*STAMP: [blocks][8 waves][8 segments] cycles*/, int order /*AVX_TILE_ORDER_*/) {
     // tile = TS (16) columns x FTH rows (16; 14 is the measured-and-rejected alternative, see kFfnTH)
-    constexpr int FTH = kFfnTH, HSY = FTH + 2, NHALO = HS * HSY, NGRP = (NHALO + 31) / 32;
+    // MARCH: 14 rows; a step computes halo rows ROW0 = 2 ... 15 (NHALO pixels), rows 0 and 1 are carried
+    constexpr int FTH = MARCH ? 14 : kFfnTH, HSY = FTH + 2, ROW0 = MARCH ? 2 : 0, NHALO = HS * (HSY - ROW0), NGRP = (NHALO + 31) / 32;
     constexpr int HID = 4 * C, NPASS = HID / HPASS, KS1 = C / 16, KS2 = HPASS / 16, NT = C / 32, YPITCH = C * 2 + 16, LNV = C / 16;
     constexpr int HPITCH = HPASS * 2 + 16, RPITCH = (HS * HPITCH + 255) / 256 * 256 /* a halo ROW: HS pixels */, NCT = HPASS / 32;  // channel tiles of 32 per pass
     static_assert(C == 32 || C == 64 || C == 128, "31-, 62- or 124-channel blocks (stored 32 / 64 / 128 wide)");
     constexpr int NTHR = 64 * NW, NGW = (NGRP + NW - 1) / NW;  // threads; halo pixel groups per wave
     constexpr int NTW = NT / (NW / 8), NOCTW = HPASS / (8 * NW);  // 32-channel output tiles per wave (phase 2b / epilogue); octets per wave and pass (phase 2a)
-    static_assert((NW == 8 || NW == 16) && NT % (NW / 8) == 0 && (!DWM || HPASS % (8 * NW) == 0) && (DWM || NW == 8) && (DWM || !DWS), "wave split");
+    static_assert((NW == 8 || NW == 16) && NT % (NW / 8) == 0 && (!DWM || HPASS % (8 * NW) == 0) && (DWM || NW == 8) && (DWM || !DWS) && (DWM || !MARCH), "wave split");
     constexpr bool PREFETCH = C <= 64;  // the next tile's raw rows wait in registers during phase 2 (C = 128: 64 registers that the accumulators need)
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned char* yt = smem;                                       // [NGRP * 32][YPITCH]  LayerNorm'd rows, float16
@@ -129,6 +141,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
     float* gl = reinterpret_cast<float*>(tapl + (DWM ? 0 : 9 * HID));  // [C] gamma, [C] beta
     constexpr bool W2LDS = NW == 16;  // 128 registers per lane: the second GEMM's fragments of a pass wait in LDS (16 KB), not in 32 registers through phase 2a
     uint4* w2l = reinterpret_cast<uint4*>(gl + 2 * C);               // W2LDS: [NT][KS2][64] this pass's W2 fragments
+    constexpr int NPRIME = 2 * HS, CARRY = NPRIME * HPITCH;           // MARCH: the 36 carried pixels (halo rows 0 and 1); their bytes per pass
+    unsigned char* carry = reinterpret_cast<unsigned char*>(w2l + (W2LDS ? NT * KS2 * 64 : 0));  // MARCH: [NPASS][2][HS px][HPITCH]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 31, h = lane >> 5;
     // STAMP (diagnostic instantiation, AVX_FFN_STAMPS=1): cycles this wave spends per segment -- 0 top barrier, 1 phase 1, 2 barrier, 3 phase 2a (or the
     // whole vector-unit phase 2), 4 barrier, 5 phase 2b, 6 epilogue, 7 LayerNorm + fetch
@@ -156,8 +170,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
         f_rel[gi] = (unsigned)(((qq / HS) * W + qq % HS) * C + h * (C / 2)) * 2u;
     }
     auto fetch = [&](const Tile& t) {
-        if (t.y0 >= 1 && t.y0 + HSY - 1 <= H && t.x0 >= 1 && t.x0 + HS - 1 <= W) {  // all but the frame's border tiles: no clamping, no 64-bit lane arithmetic
-            const char* origin = reinterpret_cast<const char*>(x + ((t.b * H + t.y0 - 1) * (size_t)W + t.x0 - 1) * C);
+        if (t.y0 + ROW0 >= 1 && t.y0 + HSY - 1 <= H && t.x0 >= 1 && t.x0 + HS - 1 <= W) {  // all but the frame's border tiles: no clamping, no 64-bit lane arithmetic
+            const char* origin = reinterpret_cast<const char*>(x + ((t.b * H + t.y0 - 1 + ROW0) * (size_t)W + t.x0 - 1) * C);
 #pragma unroll
             for (int gi = 0; gi < NGW; ++gi) {
                 if (wave + NW * gi >= NGRP) break;
@@ -174,7 +188,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
             const int g = wave + NW * gi;
             if (g >= NGRP) break;
             const int q = 32 * g + p, qq = q < NHALO ? q : NHALO - 1;
-            int yy = t.y0 - 1 + qq / HS, xx = t.x0 - 1 + qq % HS;
+            int yy = t.y0 - 1 + ROW0 + qq / HS, xx = t.x0 - 1 + qq % HS;
             yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
             xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
             const uint4* src = reinterpret_cast<const uint4*>(x + ((t.b * H + yy) * (size_t)W + xx) * C + h * (C / 2));
@@ -182,7 +196,20 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
             for (int v = 0; v < LNV; ++v) raw[gi][v] = src[v];
         }
     };
-    auto layernorm = [&]() {  // lane (p, h) holds channels [h * C/2, (h + 1) * C/2) of halo pixel 32 g + p
+    constexpr int NGPRIME = (NPRIME + 31) / 32;  // MARCH, segment start: the pixel groups of halo rows 0 and 1 (waves 0 and 1 fetch and normalise them)
+    auto fetch_prime = [&](const Tile& t) {
+        if (wave >= NGPRIME) return;
+        int td = tid;
+        asm volatile("" : "+v"(td));  // a segment start is rare: nothing of it may sit in a register through the tile loop, so its lane constants start from here
+        const int q = 32 * (td >> 6) + (td & 31), qq = q < NPRIME ? q : NPRIME - 1, hl = (td >> 5) & 1;
+        int yy = t.y0 - 1 + qq / HS, xx = t.x0 - 1 + qq % HS;
+        yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
+        xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
+        const uint4* src = reinterpret_cast<const uint4*>(x + ((t.b * H + yy) * (size_t)W + xx) * C + hl * (C / 2));
+#pragma unroll
+        for (int v = 0; v < LNV; ++v) raw[0][v] = src[v];
+    };
+    auto layernorm = [&](int ngrp) {  // lane (p, h) holds channels [h * C/2, (h + 1) * C/2) of halo pixel 32 g + p; groups below ngrp (NGRP; NGPRIME when priming)
         if constexpr (DWM) {
             // Folded form (round 3): gamma and beta live in the first GEMM's weights -- W1' = W1 diag(gamma), and W1 beta rides in row 31 of W1' (the first group's padding
             // channel), whose operand element is set to 1 here -- so what is left per element is the centring, the square and one scaling: 3.5 instead of 5.5 vector
@@ -190,7 +217,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
 #pragma unroll
             for (int gi = 0; gi < NGW; ++gi) {
                 const int g = wave + NW * gi;
-                if (g >= NGRP) break;
+                if (g >= ngrp) break;
                 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
                 constexpr unsigned kOnes = 0x3c003c00u;
                 auto is_pad = [&](int i) { return ((h * (C / 2) + i) & 31) == 31; };
@@ -207,7 +234,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
                     s2 = __builtin_fmaf(d[i], d[i], s2);
                 }
                 const float rstd = rsqrtf((s2 + __shfl_xor(s2, 32)) / cnt + eps);
-                unsigned char* dst = yt + (size_t)(32 * g + p) * YPITCH + h * C;
+                int pl = p;
+                if constexpr (MARCH) asm volatile("" : "+v"(pl));  // the address is formed here, once per tile, not kept through the tile loop (C = 64: a register the loop does not have)
+                unsigned char* dst = yt + (size_t)(32 * g + pl) * YPITCH + h * C;
 #pragma unroll
                 for (int v = 0; v < LNV; ++v) {
                     unsigned o[4];
@@ -279,6 +308,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
         for (int s = 0; s < KS1; ++s) w1f[s] = __builtin_bit_cast(half8_t, w1pack[((size_t)(pass * NCT + wave % NCT) * KS1 + s) * 64 + lane]);
     };
     constexpr bool W1AHEAD = DWM && C == 64 && NPASS > 1 && NW == 8;  // C = 32 / 128: the fragments' registers are needed in between (they would spill): loaded at the top of phase 1
+    static_assert(!(MARCH && W1AHEAD), "the marching form loads W1 at the top of phase 1 (priming replaces the fragments)");
     if constexpr (W1AHEAD) load_w1(0);
     // phase 1 items of this wave (pixel groups wave / NCT + j * 8 / NCT): where a lane's pixel sits in the hidden tile and in the image
     constexpr int NITEM = (NGRP + NW / NCT - 1) / (NW / NCT);
@@ -287,19 +317,71 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
     for (int j = 0; j < NITEM; ++j) {
         const int g = wave / NCT + j * (NW / NCT), q = 32 * g + p, qc = q < NHALO ? q : 0;
         p1_g[j] = g < NGRP ? g : -1;
-        p1_dst[j] = (g < NGRP && q < NHALO) ? (qc / HS) * RPITCH + (qc % HS) * HPITCH + 32 * h : -1;
-        p1_dy[j] = qc / HS - 1; p1_dx[j] = qc % HS - 1;
+        p1_dst[j] = (g < NGRP && q < NHALO) ? (ROW0 + qc / HS) * RPITCH + (qc % HS) * HPITCH + 32 * h : -1;
+        p1_dy[j] = ROW0 + qc / HS - 1; p1_dx[j] = qc % HS - 1;
     }
-    TileWalk ahead;  // after its first step: the NEXT tile (this one's coordinates are in t).  (Round 3's pair of 64-bit walks measured 2 % slower than a division per tile in THIS kernel; this one walk of 32-bit state measures level with it: profiles/r04/ab_tile_order.txt)
-    ahead.init(blockIdx.x, gridDim.x, B, ty, tx, order);
+    // one phase 1 item: hidden = GELU(W1' y) of pixel group g (32 lanes-pairs of yt) for this wave's channel tile, 32 bytes per lane to base + off (off < 0: a slot past the region's last pixel); masked: zeros where (yy, xx) is outside the image
+    auto p1_item = [&](int g, unsigned char* base, int off, bool masked, int yy, int xx) {
+        float16_t d;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) d[v] = 0.f;
+        const unsigned char* ysrc = yt + (size_t)(32 * g + p) * YPITCH + 16 * h;
+#pragma unroll
+        for (int s = 0; s < KS1; ++s) d = mfma16(w1f[s], __builtin_bit_cast(half8_t, *reinterpret_cast<const uint4*>(ysrc + 32 * s)), d);
+        if (off >= 0) {
+            unsigned char* dst = base + off;
+            uint32_t keep = 0xffffffffu;
+            if (masked) keep = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? 0xffffffffu : 0u;  // border tiles: zeros outside the image
+            // GELU of the 16 results, GP1 pairs at a time step-major (gelu_multi): as many as the registers allow without spilling
+            constexpr int GP1 = (C == 64 && NW == 8) ? 4 : (C == 32 ? 2 : 1);  // C = 32 / 128: no register to spare (more than one pair in flight spills)
+            unsigned pk[8];
+#pragma unroll
+            for (int v0 = 0; v0 < 8; v0 += GP1) {
+                float2_t gq[GP1];
+#pragma unroll
+                for (int v = 0; v < GP1; ++v) gq[v] = float2_t{d[2 * (v0 + v)], d[2 * (v0 + v) + 1]};
+                if constexpr (DWM) gelu_mx<GP1>(gq); else gelu_multi<GP1>(gq);
+#pragma unroll
+                for (int v = 0; v < GP1; ++v) pk[v0 + v] = pack_f16(gq[v].x, gq[v].y);
+            }
+            uint4 u0 = uint4{pk[0], pk[1], pk[2], pk[3]}, u1 = uint4{pk[4], pk[5], pk[6], pk[7]};
+            if (masked) { u0.x &= keep; u0.y &= keep; u0.z &= keep; u0.w &= keep; u1.x &= keep; u1.y &= keep; u1.z &= keep; u1.w &= keep; }
+            reinterpret_cast<uint4*>(dst)[0] = u0;
+            reinterpret_cast<uint4*>(dst)[1] = u1;
+        }
+    };
+    // MARCH, segment start: the hidden rows of image rows y0 - 1 and y0 (halo rows 0 and 1) of every pass, into the carry area.  yt is free here (see the loop's end);
+    // the first barrier also keeps these stores behind phase 2b's copy of the previous tile's rows, the second frees yt for the tile's own LayerNorm.
+    auto prime = [&](const Tile& t) {
+        fetch_prime(t);
+        layernorm(NGPRIME);
+        __syncthreads();
+        const int g = wave / NCT;
+        int td = tid;
+        asm volatile("" : "+v"(td));  // as in fetch_prime
+        const int wl = td >> 6, q = 32 * (wl / NCT) + (td & 31), qc = q < NPRIME ? q : 0, yy = t.y0 - 1 + qc / HS, xx = t.x0 - 1 + qc % HS;
+        const int off = q < NPRIME ? qc * HPITCH + 32 * ((td >> 5) & 1) + 64 * (wl % NCT) : -1;
+        if (g < NGPRIME) {  // wave-uniform
+#pragma unroll 1
+            for (int pass = 0; pass < NPASS; ++pass) {
+                load_w1(pass);
+                p1_item(g, carry + (size_t)pass * CARRY, off, true, yy, xx);
+            }
+        }
+        __syncthreads();
+    };
+    typename FfnWalk<MARCH>::type ahead;  // after its first step: the NEXT tile (this one's coordinates are in t).  (Round 3's pair of 64-bit walks measured 2 % slower than a division per tile in THIS kernel; this one walk of 32-bit state measures level with it: profiles/r04/ab_tile_order.txt)
+    if constexpr (MARCH) ahead.init(blockIdx.x, gridDim.x, B, ty, tx);
+    else ahead.init(blockIdx.x, gridDim.x, B, ty, tx, order);
     if (!ahead.live) return;
     Tile t = tile_at(ahead, TS, FTH);
     ahead.advance();
+    if constexpr (MARCH) prime(t);  // a walk's first tile starts a segment
     fetch(t);
     __syncthreads();  // tables are in LDS
-    layernorm();
+    layernorm(NGRP);
     for (;;) {
-        const bool halo_inside = t.y0 >= 1 && t.y0 + HSY - 1 <= H && t.x0 >= 1 && t.x0 + HS - 1 <= W;  // scalar
+        const bool halo_inside = t.y0 + ROW0 >= 1 && t.y0 + HSY - 1 <= H && t.x0 >= 1 && t.x0 + HS - 1 <= W;  // scalar
         float16_t D[NTW];
 #pragma unroll
         for (int n = 0; n < NTW; ++n)
@@ -323,45 +405,29 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
             {
                 const int ct = wave % NCT;
                 if constexpr (!W1AHEAD) load_w1(pass);
+                if constexpr (MARCH) {  // halo rows 0 and 1 of this pass: the tile above parked them (or prime() computed them); 16 bytes per thread, behind the top barrier
+                    constexpr int NV = NPRIME * (HPASS / 8);
+                    static_assert(NV <= NTHR, "one 16-byte piece per thread");
+                    int i = tid;
+                    asm volatile("" : "+v"(i));  // keeps the two addresses out of the registers that live through the tile loop
+                    if (i < NV) {
+                        const int px = i / (HPASS / 8), o = i % (HPASS / 8);
+                        *reinterpret_cast<uint4*>(ht + (size_t)(px / HS) * RPITCH + (size_t)(px % HS) * HPITCH + 16 * o) =
+                            *reinterpret_cast<const uint4*>(carry + (size_t)pass * CARRY + (size_t)px * HPITCH + 16 * o);
+                    }
+                }
 #pragma unroll
                 for (int j = 0; j < NITEM; ++j) {
                     if (p1_g[j] < 0) continue;  // wave-uniform
-                    float16_t d;
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) d[v] = 0.f;
-                    const unsigned char* ysrc = yt + (size_t)(32 * p1_g[j] + p) * YPITCH + 16 * h;
-#pragma unroll
-                    for (int s = 0; s < KS1; ++s) d = mfma16(w1f[s], __builtin_bit_cast(half8_t, *reinterpret_cast<const uint4*>(ysrc + 32 * s)), d);
-                    if (p1_dst[j] >= 0) {
-                        uint32_t keep = 0xffffffffu;
-                        if (!halo_inside) {  // border tiles: zeros outside the image
-                            const int yy = t.y0 + p1_dy[j], xx = t.x0 + p1_dx[j];
-                            keep = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? 0xffffffffu : 0u;
-                        }
-                        // GELU of the 16 results, GP1 pairs at a time step-major (gelu_multi): as many as the registers allow without spilling
-                        constexpr int GP1 = (C == 64 && NW == 8) ? 4 : (C == 32 ? 2 : 1);  // C = 32 / 128: no register to spare (more than one pair in flight spills)
-                        unsigned pk[8];
-#pragma unroll
-                        for (int v0 = 0; v0 < 8; v0 += GP1) {
-                            float2_t gq[GP1];
-#pragma unroll
-                            for (int v = 0; v < GP1; ++v) gq[v] = float2_t{d[2 * (v0 + v)], d[2 * (v0 + v) + 1]};
-                            if constexpr (DWM) gelu_mx<GP1>(gq); else gelu_multi<GP1>(gq);
-#pragma unroll
-                            for (int v = 0; v < GP1; ++v) pk[v0 + v] = pack_f16(gq[v].x, gq[v].y);
-                        }
-                        uint4 u0 = uint4{pk[0], pk[1], pk[2], pk[3]}, u1 = uint4{pk[4], pk[5], pk[6], pk[7]};
-                        if (!halo_inside) { u0.x &= keep; u0.y &= keep; u0.z &= keep; u0.w &= keep; u1.x &= keep; u1.y &= keep; u1.z &= keep; u1.w &= keep; }
-                        unsigned char* dst = ht + p1_dst[j] + 64 * ct;
-                        reinterpret_cast<uint4*>(dst)[0] = u0;
-                        reinterpret_cast<uint4*>(dst)[1] = u1;
-                    }
+                    p1_item(p1_g[j], ht + 64 * ct, p1_dst[j], !halo_inside, t.y0 + p1_dy[j], t.x0 + p1_dx[j]);
                 }
             }
             stamp(1);
             __syncthreads();  // ht complete
             stamp(2);
-            if (PREFETCH && pass == NPASS - 1 && ahead.live) fetch(tile_at(ahead, TS, FTH));  // next tile's raw rows: in flight during phase 2
+            bool ahead_fetch = ahead.live;
+            if constexpr (MARCH) ahead_fetch = ahead_fetch && !ahead.seg;  // a segment start fetches behind its priming
+            if (PREFETCH && pass == NPASS - 1 && ahead_fetch) fetch(tile_at(ahead, TS, FTH));  // next tile's raw rows: in flight during phase 2
             if constexpr (NPASS > 1 && !W2LDS) load_w2(pass);
             if constexpr (DWM) {
                 // ---- phase 2a: depthwise 3x3 on the matrix pipe + GELU, in place in the hidden tile (see the kernel's head comment) ----
@@ -392,7 +458,10 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
 #ifndef AVX_FFN_PIPE_ALL
 #define AVX_FFN_PIPE_ALL 0
 #endif
-                constexpr bool PIPE = C == 64 || AVX_FFN_PIPE_ALL;  // C = 32 / 128: not a register to spare (the lagging accumulator spills); measured, same-box A/B
+#ifndef AVX_FFN_MARCH_PIPE32
+#define AVX_FFN_MARCH_PIPE32 1
+#endif
+                constexpr bool PIPE = C == 64 || AVX_FFN_PIPE_ALL || (MARCH && C == 32 && AVX_FFN_MARCH_PIPE32);  // C = 32 / 128: not a register to spare (the lagging accumulator spills); measured, same-box A/B
                 if constexpr (PIPE) {
                     rd(0);
                     float4_t prev = {0.f, 0.f, 0.f, 0.f};
@@ -423,7 +492,22 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
                 // ---- phase 2b: second GEMM, this wave's 32 output pixels (rows 2 wave, 2 wave + 1), B fragments from the map ----
                 const int r = 2 * w8 + (p >> 4), c = p & 15;
                 const unsigned char* zb = ht + (size_t)r * RPITCH + (size_t)c * HPITCH + 16 * h;
-                if (2 * w8 < FTH) {  // wave-uniform (FTH = 14: the eighth row pair does not exist)
+                // MARCH: halo rows 14 and 15 of this pass (phase 2a left them as phase 1 wrote them) go to the carry area for the tile below.  Where every wave runs
+                // the product (see below): 16 bytes per thread, read in front of the second GEMM's operands and stored behind its MFMAs, so the copy waits for
+                // nothing.  Where the eighth wave of each eight idles: that wave copies them.
+                constexpr int NVC = NPRIME * (HPASS / 8);
+                constexpr bool SPREAD = MARCH && !W2LDS;
+                uint4 cv = uint4{0u, 0u, 0u, 0u};
+                int ci = tid;
+                if constexpr (SPREAD) {
+                    asm volatile("" : "+v"(ci));  // as in phase 1: no address of the copy lives through the tile loop
+                    if (ci < NVC) cv = *reinterpret_cast<const uint4*>(ht + (size_t)(FTH + (ci / (HPASS / 8)) / HS) * RPITCH + (size_t)((ci / (HPASS / 8)) % HS) * HPITCH + 16 * (ci % (HPASS / 8)));
+                }
+                // wave-uniform (FTH = 14: the eighth row pair does not exist).  MARCH with the W2 fragments in registers: the eighth wave runs the product all the
+                // same, on halo rows 14 and 15 (inside ht; the epilogue drops the result): under a condition the compiler sinks the fragments' loads into this block,
+                // and every wave waits for them here (measured: phase 2b 2.7 % -> 13.8 % of the kernel's cycles).  Fragments in LDS: nothing to sink, and the eight
+                // MFMAs of an idle wave would stand between the other waves and the next barrier.
+                if (SPREAD || 2 * w8 < FTH) {
 #pragma unroll
                 for (int s = 0; s < KS2; ++s) {
                     const half8_t bf = __builtin_bit_cast(half8_t, *reinterpret_cast<const uint4*>(zb + 32 * s));
@@ -433,6 +517,16 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
                         else D[n] = mfma16(w2f[n * KS2 + s], bf, D[n]);
                     }
                 }
+                }
+                if constexpr (SPREAD) {
+                    if (ci < NVC) *reinterpret_cast<uint4*>(carry + (size_t)pass * CARRY + (size_t)(ci / (HPASS / 8)) * HPITCH + 16 * (ci % (HPASS / 8))) = cv;
+                } else if constexpr (MARCH) {
+                    if (2 * w8 >= FTH)
+                        for (int i = (wave / 8) * 64 + lane; i < NVC; i += 64 * (NW / 8)) {
+                            const int px = i / (HPASS / 8), o = i % (HPASS / 8);
+                            *reinterpret_cast<uint4*>(carry + (size_t)pass * CARRY + (size_t)px * HPITCH + 16 * o) =
+                                *reinterpret_cast<const uint4*>(ht + (size_t)(FTH + px / HS) * RPITCH + (size_t)(px % HS) * HPITCH + 16 * o);
+                        }
                 }
             } else
             // ---- phase 2: depthwise 3x3 + GELU + W2, this wave's 32 output pixels (rows 2 wave, 2 wave + 1) ----
@@ -492,9 +586,13 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_ffn_fused(const __half* _
         stamp(6);
         if (!ahead.live) break;
         t = tile_at(ahead, TS, FTH);
+        bool fetch_now = !PREFETCH;
+        if constexpr (MARCH) {
+            if (ahead.seg) { prime(t); fetch_now = true; }
+        }
         ahead.advance();
-        if (!PREFETCH) fetch(t);
-        layernorm();  // yt is free: every wave is past the last pass's first barrier, after which nobody reads it
+        if (fetch_now) fetch(t);
+        layernorm(NGRP);  // yt is free: every wave is past the last pass's first barrier, after which nobody reads it
     }
     if constexpr (STAMP) {
         if (lane == 0 && stamps)
@@ -1694,7 +1792,7 @@ __global__ __launch_bounds__(256) void k_mst_conv_in_u8_mfma(const uint8_t* __re
 }  // namespace
 
 static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* taps_9xhid, const void* dwpack,
-                            const void* w2pack, void* out, int B, int H, int W, int C, void* stream, bool sparse = false);
+                            const void* w2pack, void* out, int B, int H, int W, int C, void* stream, bool sparse = false, bool march = false, int max_workgroups = 0);
 
 // What the matrix-pipe kernels expect of their weights (csrc/mst_common.h, prescaled GELU): avx_mst_ffn_fused_mx takes W1 / s, the depthwise weights as they are
 // and W2 * s; avx_mst_attn_tail_mx takes pos_emb's first depthwise weights / s and the second * s.  s = 4 (1 when built with -DAVX_GELU_PRE=0).
@@ -1713,6 +1811,30 @@ extern "C" int avx_mst_tile_order(int frames, int ty, int tx, int nwg, int raste
             if (visit && k < steps_cap) visit[(size_t)wg * steps_cap + k] = ((long long)wk.b * ty + wk.yi) * tx + wk.xi;
         if (visit)
             for (int r = k; r < steps_cap; ++r) visit[(size_t)wg * steps_cap + r] = -1;
+        most = k > most ? k : most;
+    }
+    if (steps_out) *steps_out = most;
+    return AVX_OK;
+}
+
+// The column march of the marching FeedForward kernel (ColumnWalk), the same way; seg[wg * steps_cap + k] = 1 where that tile starts a segment (its two top halo
+// rows are primed, not carried), 0 elsewhere and past the walk's end.
+extern "C" int avx_mst_tile_order_col(int frames, int ty, int tx, int nwg, long long* visit, unsigned char* seg, int steps_cap, int* steps_out) {
+    if (frames <= 0 || ty <= 0 || tx <= 0 || nwg <= 0 || ((visit || seg) && steps_cap <= 0) || (long long)frames * ty * tx > 0x7fffffffll) return AVX_ERR_INVALID;
+    int most = 0;
+    for (int wg = 0; wg < nwg; ++wg) {
+        ColumnWalk wk;
+        wk.init((unsigned)wg, (unsigned)nwg, frames, ty, tx);
+        int k = 0;
+        for (; wk.live; wk.advance(), ++k)
+            if (k < steps_cap) {
+                if (visit) visit[(size_t)wg * steps_cap + k] = ((long long)wk.b * ty + wk.yi) * tx + wk.xi;
+                if (seg) seg[(size_t)wg * steps_cap + k] = wk.seg ? 1 : 0;
+            }
+        for (int r = k; r < steps_cap; ++r) {
+            if (visit) visit[(size_t)wg * steps_cap + r] = -1;
+            if (seg) seg[(size_t)wg * steps_cap + r] = 0;
+        }
         most = k > most ? k : most;
     }
     if (steps_out) *steps_out = most;
@@ -1742,8 +1864,25 @@ extern "C" int avx_mst_ffn_fused_sp(avx_ctx* ctx, const void* x, const float* ga
     return ffn_fused_launch(ctx, x, gamma, beta, eps, w1pack, nullptr, dwpack, w2pack, out, B, H, W, C, stream, true);
 }
 
+// avx_mst_ffn_fused_mx / _sp as a march down tile columns (k_mst_ffn_fused<MARCH>): the same weights, the same results to the bit.  C = 32 or 64 (C = 128 stays on
+// the 16-row kernel).  max_workgroups > 0 caps the grid below the launcher's own cap (tests: few workgroups marching over small frames).
+extern "C" int avx_mst_ffn_fused_mx_col(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* dwpack,
+                                        const void* w2pack, void* out, int B, int H, int W, int C, int max_workgroups, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, dwpack && (((uintptr_t)dwpack) & 15u) == 0, "avx_mst_ffn_fused_mx_col: dwpack NULL or not 16-byte aligned");
+    AVX_REQUIRE(ctx, (C == 32 || C == 64) && max_workgroups >= 0, "avx_mst_ffn_fused_mx_col: C=%d (32 or 64), max_workgroups=%d (>= 0)", C, max_workgroups);
+    return ffn_fused_launch(ctx, x, gamma, beta, eps, w1pack, nullptr, dwpack, w2pack, out, B, H, W, C, stream, false, true, max_workgroups);
+}
+extern "C" int avx_mst_ffn_fused_sp_col(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* dwpack,
+                                        const void* w2pack, void* out, int B, int H, int W, int C, int max_workgroups, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, dwpack && (((uintptr_t)dwpack) & 15u) == 0, "avx_mst_ffn_fused_sp_col: dwpack NULL or not 16-byte aligned");
+    AVX_REQUIRE(ctx, (C == 32 || C == 64) && max_workgroups >= 0, "avx_mst_ffn_fused_sp_col: C=%d (32 or 64), max_workgroups=%d (>= 0)", C, max_workgroups);
+    return ffn_fused_launch(ctx, x, gamma, beta, eps, w1pack, nullptr, dwpack, w2pack, out, B, H, W, C, stream, true, true, max_workgroups);
+}
+
 static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* taps_9xhid, const void* dwpack,
-                            const void* w2pack, void* out, int B, int H, int W, int C, void* stream, bool sparse) {
+                            const void* w2pack, void* out, int B, int H, int W, int C, void* stream, bool sparse, bool march, int max_workgroups) {
     AVX_REQUIRE(ctx, x && gamma && beta && w1pack && w2pack && out && B > 0 && H > 0 && W > 0, "avx_mst_ffn_fused: NULL pointer or empty tensor");
     AVX_REQUIRE(ctx, C == 32 || C == 64 || C == 128, "avx_mst_ffn_fused: C=%d (32, 64 or 128: 31-channel groups stored 32 wide)", C);
     AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)w1pack | (uintptr_t)w2pack | (uintptr_t)out | (uintptr_t)taps_9xhid)) & 15u) == 0,
@@ -1751,23 +1890,29 @@ static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, con
     AVX_REQUIRE(ctx, x != out, "avx_mst_ffn_fused: neighbouring tiles read each other's halo: the output cannot be the input");
     AVX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = avx_pick_stream(ctx, stream);
-    const long total = (long)B * ((H + kFfnTH - 1) / kFfnTH) * ((W + TS - 1) / TS);
+    const int fth = march ? 14 : kFfnTH;  // the marching form: 16 x 14 tiles, LayerNorm'd rows and phase 1 for 8 pixel groups a step, two carried rows per pass
+    const long total = (long)B * ((H + fth - 1) / fth) * ((W + TS - 1) / TS);
     const char* hp = getenv("AVX_MST_FFN_HPASS");  // A/B: 128 = one 8-wave workgroup per CU, 64 (C = 32 only) = two
-    const bool small = C == 32 && !(hp && atoi(hp) == 128);
+    const bool small = C == 32 && (march || !(hp && atoi(hp) == 128));
     const int hpass = (small || C == 128) ? 64 : 128, hpitch = hpass * 2 + 16, rpitch = (HS * hpitch + 255) / 256 * 256;
     const long cap = (long)ctx->num_cus * (small ? 2 : 1);
-    const bool nw16 = C == 64 && dwpack && !(getenv("AVX_MST_FFN_NW") && atoi(getenv("AVX_MST_FFN_NW")) == 8);  // AVX_MST_FFN_NW=8: A/B, the round-2 split
-    const size_t lds = (size_t)kFfnNGRP * 32 * (C * 2 + 16) + (size_t)(kFfnTH + 2) * rpitch + (dwpack ? 0 : (size_t)9 * 4 * C * 2) + sizeof(float) * 2 * C + (nw16 ? (size_t)(C / 32) * (hpass / 16) * 1024 : 0);
+    const bool nw16 = C == 64 && dwpack && (march || !(getenv("AVX_MST_FFN_NW") && atoi(getenv("AVX_MST_FFN_NW")) == 8));  // AVX_MST_FFN_NW=8: A/B, the round-2 split
+    const size_t lds = (size_t)(march ? 8 : kFfnNGRP) * 32 * (C * 2 + 16) + (size_t)(fth + 2) * rpitch + (dwpack ? 0 : (size_t)9 * 4 * C * 2) + sizeof(float) * 2 * C +
+                       (nw16 ? (size_t)(C / 32) * (hpass / 16) * 1024 : 0) + (march ? (size_t)(4 * C / hpass) * 2 * HS * hpitch : 0);
     AVX_REQUIRE(ctx, total <= 0x7fffffffl, "avx_mst_ffn_fused: 2^31 tiles or more");
-    const dim3 grid((unsigned)(total < cap ? total : cap));
+    AVX_REQUIRE(ctx, !march || (dwpack && (C == 32 || C == 64)), "avx_mst_ffn_fused: the marching form is built for the matrix-pipe kernels at C = 32 and 64");
+    long nwg = total < cap ? total : cap;
+    if (max_workgroups > 0 && max_workgroups < nwg) nwg = max_workgroups;
+    const dim3 grid((unsigned)nwg);
     const int order = mst_tile_order();
-#define AVX_FFN1S(CV, HP, MW, DW, NWV, SP)                                                                                                       \
+#define AVX_FFN1M(CV, HP, MW, DW, NWV, SP, MR)                                                                                                   \
     {                                                                                                                                            \
-        auto k = k_mst_ffn_fused<CV, HP, MW, DW, false, NWV, SP>;                                                                                \
+        auto k = k_mst_ffn_fused<CV, HP, MW, DW, false, NWV, SP, MR>;                                                                            \
         AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
         hipLaunchKernelGGL(k, grid, dim3(64 * NWV), lds, s, (const __half*)x, gamma, beta, eps, (const uint4*)w1pack, (const __half*)taps_9xhid, \
                            (const uint4*)w2pack, (__half*)out, B, H, W, (const uint4*)dwpack, (unsigned long long*)nullptr, order);              \
     }
+#define AVX_FFN1S(CV, HP, MW, DW, NWV, SP) AVX_FFN1M(CV, HP, MW, DW, NWV, SP, false)
 #define AVX_FFN1(CV, HP, MW, DW, NWV) AVX_FFN1S(CV, HP, MW, DW, NWV, false)
 #define AVX_FFN(CV, HP, MW) { if (dwpack && sparse) AVX_FFN1S(CV, HP, MW, true, 8, true) else if (dwpack) AVX_FFN1(CV, HP, MW, true, 8) else AVX_FFN1(CV, HP, MW, false, 8) }
     if (dwpack && getenv("AVX_FFN_STAMPS") && ((C == 32 && small) || C == 64 || C == 128)) {  // diagnostic: per-segment cycles of every wave, summed and printed
@@ -1775,17 +1920,22 @@ static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, con
         const int nwv = nw16 ? 16 : 8;
         const size_t n = (size_t)grid.x * nwv * 8;
         AVX_HIP(ctx, hipMalloc((void**)&d_st, n * sizeof(unsigned long long)));
-#define AVX_FFN_ST1(CV, HP, MW, NWV, SP)                                                                                                         \
+#define AVX_FFN_ST2(CV, HP, MW, NWV, SP, MR)                                                                                                     \
     {                                                                                                                                            \
-        auto k = k_mst_ffn_fused<CV, HP, MW, true, true, NWV, SP>;                                                                               \
+        auto k = k_mst_ffn_fused<CV, HP, MW, true, true, NWV, SP, MR>;                                                                           \
         AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
         hipLaunchKernelGGL(k, grid, dim3(64 * NWV), lds, s, (const __half*)x, gamma, beta, eps, (const uint4*)w1pack, (const __half*)taps_9xhid, \
                            (const uint4*)w2pack, (__half*)out, B, H, W, (const uint4*)dwpack, d_st, order);                                      \
     }
+#define AVX_FFN_ST1(CV, HP, MW, NWV, SP) AVX_FFN_ST2(CV, HP, MW, NWV, SP, false)
 #define AVX_FFN_ST(CV, HP, MW, NWV) { if (sparse) AVX_FFN_ST1(CV, HP, MW, NWV, true) else AVX_FFN_ST1(CV, HP, MW, NWV, false) }
-        if (C == 32) AVX_FFN_ST(32, 64, 4, 8) else if (nw16) AVX_FFN_ST(64, 128, 1, 16) else if (C == 64) AVX_FFN_ST(64, 128, 2, 8) else AVX_FFN_ST(128, 64, 2, 8)
+#define AVX_FFN_STM(CV, HP, MW, NWV) { if (sparse) AVX_FFN_ST2(CV, HP, MW, NWV, true, true) else AVX_FFN_ST2(CV, HP, MW, NWV, false, true) }
+        if (march && C == 32) AVX_FFN_STM(32, 64, 4, 8) else if (march) AVX_FFN_STM(64, 128, 1, 16)  // the marching form: priming counts as ln+fetch
+        else if (C == 32) AVX_FFN_ST(32, 64, 4, 8) else if (nw16) AVX_FFN_ST(64, 128, 1, 16) else if (C == 64) AVX_FFN_ST(64, 128, 2, 8) else AVX_FFN_ST(128, 64, 2, 8)
+#undef AVX_FFN_STM
 #undef AVX_FFN_ST
 #undef AVX_FFN_ST1
+#undef AVX_FFN_ST2
         AVX_HIP(ctx, hipStreamSynchronize(s));
         unsigned long long* h_st = (unsigned long long*)malloc(n * sizeof(unsigned long long));
         AVX_HIP(ctx, hipMemcpy(h_st, d_st, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -1793,19 +1943,24 @@ static int ffn_fused_launch(avx_ctx* ctx, const void* x, const float* gamma, con
         for (size_t i = 0; i < n; ++i) { tot[i & 7] += (double)h_st[i]; if (((i >> 3) % nwv) == 0) w0[i & 7] += (double)h_st[i]; if (((i >> 3) % nwv) == (size_t)nwv - 1) w7[i & 7] += (double)h_st[i]; }
         double all = 0;
         for (int k2 = 0; k2 < 8; ++k2) all += tot[k2];
-        fprintf(stderr, "[ffn stamps C=%d] %u blocks x %d waves, mean cycles per wave %.0f; share per segment (all waves | first wave | last wave): ", C, grid.x, nwv, all / (grid.x * (double)nwv));
+        fprintf(stderr, "[ffn stamps C=%d%s] %u blocks x %d waves, mean cycles per wave %.0f; share per segment (all waves | first wave | last wave): ", C, march ? " march" : "", grid.x, nwv, all / (grid.x * (double)nwv));
         const char* nm[8] = {"bar1", "phase1", "bar2", "phase2a", "bar3", "phase2b", "epilogue", "ln+fetch"};
         for (int k2 = 0; k2 < 8; ++k2) fprintf(stderr, "%s %.1f%% | %.1f%% | %.1f%%  ", nm[k2], 100 * tot[k2] / all, 100 * w0[k2] * nwv / all, 100 * w7[k2] * nwv / all);
         fprintf(stderr, "\n");
         free(h_st);
         (void)hipFree(d_st);
-    } else if (C == 32 && small) AVX_FFN(32, 64, 4) else if (C == 32) AVX_FFN(32, 128, 2)
+    } else if (march && C == 32 && sparse) AVX_FFN1M(32, 64, 4, true, 8, true, true)
+    else if (march && C == 32) AVX_FFN1M(32, 64, 4, true, 8, false, true)
+    else if (march && sparse) AVX_FFN1M(64, 128, 1, true, 16, true, true)
+    else if (march) AVX_FFN1M(64, 128, 1, true, 16, false, true)
+    else if (C == 32 && small) AVX_FFN(32, 64, 4) else if (C == 32) AVX_FFN(32, 128, 2)
     else if (nw16 && sparse) AVX_FFN1S(64, 128, 1, true, 16, true)
     else if (nw16) AVX_FFN1(64, 128, 1, true, 16)
     else if (C == 64) AVX_FFN(64, 128, 2) else AVX_FFN(128, 64, 2)
 #undef AVX_FFN
 #undef AVX_FFN1
 #undef AVX_FFN1S
+#undef AVX_FFN1M
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
 }

@@ -89,3 +89,40 @@ struct TileWalk {
         b += db + cy;
     }
 };
+
+// COLUMN (round 10): the marching FeedForward kernel carries the two bottom halo rows of a tile on chip into the tile below, so a workgroup owns one contiguous
+// RUN of the column-major order (frame, tile column, tile row) and walks it a tile at a time.  Run r of nwg is the positions [T r / nwg, T (r + 1) / nwg): a
+// bijection for any T and nwg, balanced to one tile.  The workgroups of one class (blockIdx.x % 8, see above) own neighbouring runs -- neighbouring tile columns
+// meet in one L2 -- and nothing but speed depends on that.  A SEGMENT starts at a walk's first tile and at the top of every column: there the rows above are not
+// on chip.  The divisions run when the walk starts; a step is an increment and two carries.
+struct ColumnWalk {
+    int xi, yi, b;      // this tile's column, row and frame
+    bool live;          // false: past this workgroup's last tile (the coordinates mean nothing)
+    bool seg;           // this tile starts a segment
+    int tx, ty;         // the grid
+    unsigned pos, end;  // column-major position, this walk's last + 1
+
+    __host__ __device__ __forceinline__ void init(unsigned wg, unsigned nwg, int frames, int ty_, int tx_) {
+        tx = tx_; ty = ty_;
+        const unsigned total = (unsigned)frames * (unsigned)ty_ * (unsigned)tx_;
+        const unsigned g = wg % kTileXcds, m = wg / kTileXcds, base = nwg / kTileXcds, rem = nwg % kTileXcds;
+        const unsigned run = g * base + (g < rem ? g : rem) + m;  // the workgroups in the classes below g, then this one's place in its class
+        pos = (unsigned)AVX_TW_UNI32((unsigned long long)total * run / nwg);
+        end = (unsigned)AVX_TW_UNI32((unsigned long long)total * (run + 1) / nwg);
+        live = pos < end;
+        seg = true;
+        const unsigned col = pos / (unsigned)ty_;
+        yi = AVX_TW_UNI32(pos - col * (unsigned)ty_); xi = AVX_TW_UNI32(col % (unsigned)tx_); b = AVX_TW_UNI32(col / (unsigned)tx_);
+    }
+    __host__ __device__ __forceinline__ void advance() {
+        ++pos;  // < 2^32: pos < 2^31 while the walk is live, and a dead walk is advanced a few times at most
+        live = live && pos < end;
+        ++yi;
+        seg = yi >= ty;
+        yi = seg ? 0 : yi;
+        xi += seg ? 1 : 0;
+        const int cx = xi >= tx ? 1 : 0;
+        xi = cx ? 0 : xi;
+        b += cx;
+    }
+};

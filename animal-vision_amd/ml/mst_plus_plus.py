@@ -240,6 +240,8 @@ class _AvxOps:
         self._specfuse = os.environ.get("AVX_MST_NO_SPEC_FUSE", "") == ""  # A/B: the spectral integration as conv_out's epilogue (the cube is never written)
         self._cinfuse = os.environ.get("AVX_MST_NO_CONV_IN_FUSE", "") == ""  # A/B: conv_in recomputed from the uint8 frame in its three consumers, its output never stored (round 7)
         self.FFN_FUSED_C = tuple(int(v) for v in os.environ.get("AVX_MST_FFN_FUSED_C", "32,64,128").split(",") if v)
+        self._ffn_march = os.environ.get("AVX_MST_NO_FFN_MARCH", "") == ""  # A/B: the matrix-pipe FeedForward kernel marches down tile columns in 14-row steps (round 10)
+        self.FFN_MARCH_C = (32, 64)  # the widths the marching form is built for (C = 128 stays on the 16-row kernel)
         self._ctx = {}
 
     def ctx(self, device: torch.device):
@@ -617,10 +619,12 @@ class _AvxOps:
         return out
 
     def ffn_fused(self, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, w1p: torch.Tensor, taps: torch.Tensor, w2p: torch.Tensor,
-                  eps: float = 1e-5, dwpack: torch.Tensor = None, sparse: bool = False) -> torch.Tensor:
+                  eps: float = 1e-5, dwpack: torch.Tensor = None, sparse: bool = False, march: bool = False, max_workgroups: int = 0) -> torch.Tensor:
         """x + FeedForward(LayerNorm(x)) on (b, h, w, c) float16 in ONE kernel, the 4c hidden tile in LDS (csrc/mst_fused.hip).
         dwpack (pack_dw_mfma): the depthwise conv runs on the matrix pipe (avx_mst_ffn_fused_mx); else taps ([9][4c]) on the vector unit.
-        sparse: dwpack is pack_dw_smfmac's (avx_mst_ffn_fused_sp: one dense + one 2:4-sparse instruction per unit)."""
+        sparse: dwpack is pack_dw_smfmac's (avx_mst_ffn_fused_sp: one dense + one 2:4-sparse instruction per unit).
+        march (with dwpack, c in FFN_MARCH_C): the column-marching form (avx_mst_ffn_fused_mx_col / _sp_col), the same result to the bit;
+        max_workgroups > 0 caps its grid (tests)."""
         from .._lib import lib
 
         b, h, w, c = x.shape
@@ -628,7 +632,11 @@ class _AvxOps:
         out = torch.empty_like(x)
         ctx = self.ctx(x.device)
         st = torch.cuda.current_stream(x.device).cuda_stream
-        if dwpack is not None:
+        if dwpack is not None and march:
+            fn = lib.avx_mst_ffn_fused_sp_col if sparse else lib.avx_mst_ffn_fused_mx_col
+            ctx._check(fn(ctx._h, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, w1p.data_ptr(), dwpack.data_ptr(), w2p.data_ptr(), out.data_ptr(), b, h, w, c,
+                          max_workgroups, st))
+        elif dwpack is not None:
             fn = lib.avx_mst_ffn_fused_sp if sparse else lib.avx_mst_ffn_fused_mx
             ctx._check(fn(ctx._h, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, w1p.data_ptr(), dwpack.data_ptr(), w2p.data_ptr(), out.data_ptr(), b, h, w, c, st))
         else:
@@ -922,9 +930,10 @@ class MSTPlusPlus(torch.nn.Module):
                 gs = _AVX.gelu_prescale()  # both GELUs work on x / gs (csrc/mst_common.h): W1 / gs, the depthwise conv as it is (linear: x2 / gs again), W2 * gs
                 w1s = self._prep(p + f".w1.frag16.ln/{gs}", lambda: pack_fragments16(fold_layernorm(self._w(p + ".fn.net.0.weight", (0, 1)).reshape(4 * c, c).t(), g32, b32, gs).to(x.dtype)))
                 w2s = self._prep(p + f".w2.frag16*{gs}", lambda: pack_fragments16((w2.float() * gs).to(x.dtype).contiguous()))
+                march = _AVX._ffn_march and c in _AVX.FFN_MARCH_C
                 if _AVX._dwsp and c in _AVX.DW_SPARSE_FFN_C:
-                    return _AVX.ffn_fused(x, g32, b32, w1s, None, w2s, dwpack=self._prep(key + ".dwsp", lambda: pack_dw_smfmac(self._w(key, (0,)))), sparse=True)
-                return _AVX.ffn_fused(x, g32, b32, w1s, None, w2s, dwpack=self._prep(key + ".dwmx", lambda: pack_dw_mfma(self._w(key, (0,)))))
+                    return _AVX.ffn_fused(x, g32, b32, w1s, None, w2s, dwpack=self._prep(key + ".dwsp", lambda: pack_dw_smfmac(self._w(key, (0,)))), sparse=True, march=march)
+                return _AVX.ffn_fused(x, g32, b32, w1s, None, w2s, dwpack=self._prep(key + ".dwmx", lambda: pack_dw_mfma(self._w(key, (0,)))), march=march)
             w1q = self._prep(p + ".w1.frag16", lambda: pack_fragments16(self._w(p + ".fn.net.0.weight", (0, 1)).reshape(4 * c, c).t().contiguous()))
             w2q = self._prep(p + ".w2.frag16", lambda: pack_fragments16(w2))
             t9 = self._prep(key + ".t9h", lambda: self._w(key, (0,)).reshape(4 * c, 9).t().contiguous())  # [9][4c], tap-major, the model's own float16 values

@@ -835,6 +835,20 @@ float avx_mst_gelu_prescale(void);
  * ... of the raster, which the environment variable AVX_MST_TILE_ORDER=raster (read per call) selects in the kernels.  Results do not depend on the order. */
 int avx_mst_tile_order(int frames, int ty, int tx, int nwg, int raster, long long* visit, int steps_cap, int* steps_out);
 
+/* avx_mst_ffn_fused_mx / _sp as a march down tile columns (C = 32 or 64; same weights, same results to the bit).  Tiles are 16 x 14; a workgroup walks a
+ * contiguous run of the column-major tile order downwards and keeps the hidden map of a tile's two bottom halo rows on chip for the tile below, so a step runs
+ * LayerNorm, the first GEMM and its GELU on 18 x 14 = 252 pixels (8 groups of 32: two items per wave) where the 16 x 16 tile's 18 x 18 halo region takes 11
+ * groups (three).  At a run's first tile and at the top of a column the two rows are computed.  max_workgroups > 0 caps the grid below the launcher's own cap
+ * (0: that cap), so that a few workgroups march over a small frame. */
+int avx_mst_ffn_fused_mx_col(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* dwpack,
+                             const void* w2pack, void* out, int B, int H, int W, int C, int max_workgroups, void* stream);
+int avx_mst_ffn_fused_sp_col(avx_ctx* ctx, const void* x, const float* gamma, const float* beta, float eps, const void* w1pack, const void* dwpack,
+                             const void* w2pack, void* out, int B, int H, int W, int C, int max_workgroups, void* stream);
+/* The march's tile order, run on the host with the kernel's own walk (csrc/mst_tile_order.h, ColumnWalk), as avx_mst_tile_order: workgroup wg takes the
+ * positions [T r / nwg, T (r + 1) / nwg) of the column-major order (frame, tile column, tile row), r its run (the workgroups with the same index % 8 own
+ * neighbouring runs).  seg[wg * steps_cap + k] (may be NULL) receives 1 where the tile starts a segment -- a run's first tile, the top of a column -- else 0. */
+int avx_mst_tile_order_col(int frames, int ty, int tx, int nwg, long long* visit, unsigned char* seg, int steps_cap, int* steps_out);
+
 /* out = [add +] a @ W [+ a2 @ W2] for (rows x C) float16 tensors and C x C weights in fragment order (out may alias
  * add; a2 / W2 and add may be NULL): MS_MSA's `proj(attn @ v)` collapsed to one matrix per frame (:132-135)
  * accumulated onto pos_emb(v) + x, and the decoder's 1x1 fusion conv over [up | skip] (:257) without the concatenation. */

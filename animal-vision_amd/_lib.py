@@ -50,6 +50,22 @@ class DichromatDesc(ctypes.Structure):
     ]
 
 
+class NightDesc(ctypes.Structure):
+    """avx_night_desc (include/avx.h): rod vision and tapetum bloom of avx_dichromat_night_u8."""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("chroma_scale", ctypes.c_double),
+        ("luminance_boost", ctypes.c_double),
+        ("gamma", ctypes.c_double),
+        ("rod_ksize", ctypes.c_int32),
+        ("rod_taps_host", ctypes.POINTER(ctypes.c_double)),
+        ("bloom_strength", ctypes.c_double),
+        ("bloom_ksize", ctypes.c_int32),
+        ("bloom_taps_host", ctypes.POINTER(ctypes.c_double)),
+    ]
+
+
 class DichromatLaunchInfo(ctypes.Structure):
     """avx_dichromat_launch_info (include/avx.h): kernel family and launch geometry of the last avx_dichromat_u8 call."""
 
@@ -310,6 +326,7 @@ _SIGS = {
     "avx_timer_stop": (_i, [_vp, _vp, ctypes.POINTER(ctypes.c_float)]),
     "avx_dichromat_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(DichromatDesc), _vp]),
     "avx_dichromat_last_launch": (_i, [_vp, ctypes.POINTER(DichromatLaunchInfo)]),
+    "avx_dichromat_night_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(DichromatDesc), ctypes.POINTER(NightDesc), _vp]),
     "avx_get_table": (_i, [_i, _vp, _sz]),
     "avx_percentile": (_i, [_vp, _vp, _sz, ctypes.c_double, ctypes.POINTER(ctypes.c_double), _vp]),
     "avx_spectral_integrate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),

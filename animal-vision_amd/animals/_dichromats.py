@@ -9,7 +9,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from ..dichromat import DichromatOp, DichromatSpec
+from .. import _lib
+from ..dichromat import DichromatOp, DichromatSpec, NightSpec
 from .animal import Animal
 from .animal_utils import check_input_image
 
@@ -17,16 +18,30 @@ from .animal_utils import check_input_image
 class _Dichromat(Animal):
     SPEC: DichromatSpec = None  # type: ignore
 
-    def __init__(self):
+    def __init__(self, *, night=None):
+        """night: None (by day, the reference's active code), True (NightSpec's defaults: the values of the commented night
+        branch of animals/cat.py:50-60) or a NightSpec: rod vision in front of the colour stage, optional tapetum bloom."""
         self._op = None
+        if night is True:
+            night = NightSpec()
+        elif night is False:
+            night = None
+        if night is not None and not isinstance(night, NightSpec):
+            raise TypeError(f"night must be None, True or a NightSpec (got {type(night).__name__})")
+        self.night = night
 
     def _operator(self) -> DichromatOp:
         if self._op is None:
-            self._op = DichromatOp(self.SPEC)
+            self._op = DichromatOp(self.SPEC, night=self.night)
         return self._op
+
+    def _refuse_float_night(self, image: np.ndarray) -> None:
+        if self.night is not None and image.dtype != np.uint8:
+            raise NotImplementedError(f"{type(self).__name__}: night is implemented for uint8 frames, got {image.dtype}")
 
     def visualize(self, image: np.ndarray) -> Optional[Tuple[np.ndarray, np.ndarray]]:
         assert check_input_image(image)  # dog.py:33
+        self._refuse_float_night(image)
         if image.dtype != np.uint8:
             # The reference tolerates float / wider-int frames (animal_utils.py:45-48); its video, webcam and image
             # renderers only ever produce uint8 (video.py:95).  Float frames of the Gaussian / row-gain species run as a
@@ -128,6 +143,7 @@ class Cat(_Dichromat):
 
     def visualize(self, image: np.ndarray):
         assert isinstance(image, np.ndarray) and image.ndim == 3 and image.shape[2] == 3, "HxWx3 RGB"
+        self._refuse_float_night(image)
         if image.dtype != np.uint8:
             if np.issubdtype(image.dtype, np.floating):
                 return self._visualize_float(image)
@@ -135,7 +151,7 @@ class Cat(_Dichromat):
         # one frame through the stream operator's two launches (CatStreamOp): device tables and buffers are kept per size
         H, W = image.shape[:2]
         plans = self.__dict__.setdefault("_u8_plans", {})
-        key = (H, W, bool(self.ENABLE_FOV_WARP), self.CAMERA_HFOV_DEG, self.CAT_PER_EYE_HALF_FOV_DEG, self.CAT_OVERLAP_DEG, self.CAT_TO_HUMAN_RATIO)
+        key = (H, W, bool(self.ENABLE_FOV_WARP), self.CAMERA_HFOV_DEG, self.CAT_PER_EYE_HALF_FOV_DEG, self.CAT_OVERLAP_DEG, self.CAT_TO_HUMAN_RATIO, self.night)
         sop = plans.get(key)
         if sop is None:
             if len(plans) >= 4:
@@ -209,7 +225,10 @@ class CatStreamOp:
     the slot's stream: avx_center_zoom_u8 into the slot's baseline (visualize()'s first frame, the split frame's left half) and
     avx_cat_wide_u8 (csrc/cat_wide.hip: warp, colour tail, blur and encode fused).  With cat.ENABLE_FOV_WARP false the wide view is
     the ordinary dichromat kernel on the uint8 frames; with a zoom scale <= 1 the baseline is the input itself.  The buffers are
-    plain allocations of the op, which outlive the slot streams."""
+    plain allocations of the op, which outlive the slot streams.
+    At night (Cat(night=...)) the wide view is the chain the fused kernel is defined by, with the night entry at its
+    end: avx_binocular_warp_u8 per frame into the slot's float32 frames, then avx_dichromat_night_u8 with in_f32 = 1 on the batch;
+    with ENABLE_FOV_WARP false the night entry on the uint8 frames.  The baseline launch is the same."""
 
     def __init__(self, cat: Cat, H: int, W: int, depth: int = 3, batch: int = 1, ctx=None):
         from .. import geometry as G
@@ -218,7 +237,7 @@ class CatStreamOp:
             raise ValueError(f"batch must be at least 1 (got {batch})")
         self.cat, self.H, self.W = cat, int(H), int(W)
         self.batch = self.max_batch = int(batch)
-        self._op = cat._operator() if ctx is None else DichromatOp(cat.SPEC, ctx)
+        self._op = cat._operator() if ctx is None else DichromatOp(cat.SPEC, ctx, night=cat.night)
         self.ctx = self._op._ctx()
         self.warp = bool(cat.ENABLE_FOV_WARP)
         self.rect = self.crop_rect(cat, self.H, self.W)
@@ -227,7 +246,14 @@ class CatStreamOp:
         self._base = [self.ctx.malloc(nbytes) if self.rect is not None else None for _ in range(depth)]
         self._by_in = {d_in.ptr: k for k, (d_in, _) in enumerate(self._bufs)}
         self._tables, self._table_ptrs = None, None
-        if self.warp:
+        self.night = cat.night
+        self._warped, self._host_tables, self._op_f32 = [], None, None
+        if self.warp and self.night is not None:
+            self._host_tables = G.binocular_warp_tables(self.H, self.W, self.W, self.H, cat.CAMERA_HFOV_DEG, cat.CAT_PER_EYE_HALF_FOV_DEG, cat.CAT_OVERLAP_DEG)
+            self._warped = [self.ctx.malloc(nbytes * 4) for _ in range(depth)]  # float32 HWC frames in [0, 1]
+            self._op_f32 = DichromatOp(cat.SPEC, self.ctx, night=self.night)
+            self._op_f32.desc.in_f32 = 1
+        elif self.warp:
             tables = G.binocular_warp_tables(self.H, self.W, self.W, self.H, cat.CAMERA_HFOV_DEG, cat.CAT_PER_EYE_HALF_FOV_DEG, cat.CAT_OVERLAP_DEG)
             self._tables, self._table_ptrs = G.binocular_warp_tables_device(self.ctx, tables)
 
@@ -254,7 +280,14 @@ class CatStreamOp:
         assert 1 <= n_frames <= self.batch and (H, W) == (self.H, self.W)
         if self.rect is not None:
             G.center_zoom_device(self.ctx, d_in, self._base[self._by_in[d_in.ptr]], n_frames, H, W, self.rect, stream)
-        if self.warp:
+        if self.warp and self.night is not None:
+            d_f32 = self._warped[self._by_in[d_in.ptr]]
+            xL, xR, ymap, wL, wR = self._host_tables
+            for f in range(n_frames):
+                self.ctx._check(_lib.lib.avx_binocular_warp_u8(self.ctx._h, d_in.ptr + f * H * W * 3, H, W, xL.ctypes.data, xR.ctypes.data, ymap.ctypes.data,
+                                                               wL.ctypes.data, wR.ctypes.data, H, W, d_f32.ptr + f * H * W * 12, self.ctx._s(stream)))
+            self._op_f32.run_device(d_f32, d_out, n_frames, H, W, stream=stream)
+        elif self.warp:
             G.cat_wide_device(self.ctx, d_in, d_out, n_frames, H, W, self._op.desc, self._table_ptrs, stream)
         else:
             self._op.run_device(d_in, d_out, n_frames, H, W, stream=stream)
@@ -263,7 +296,7 @@ class CatStreamOp:
         for pair in self._bufs:
             for b in pair:
                 b.free()
-        for b in self._base + [self._tables]:
+        for b in self._base + [self._tables] + self._warped:
             if b is not None:
                 b.free()
-        self._bufs, self._base, self._tables = [], [], None
+        self._bufs, self._base, self._tables, self._warped = [], [], None, []

@@ -117,12 +117,60 @@ class DichromatSpec:
     chroma: Optional[float] = None   # apply_chroma_compression strength whose result is USED
     
 
-class DichromatOp:
-    """Configured fused kernel launch for one species; reusable across frames (stateless between them)."""
+ROD_SIGMA, BLOOM_SIGMA = 1.2, 3.0  # apply_rod_vision's and apply_tapetum_bloom's blurs (animal_utils.py:261-305, :183-204): fixed
 
-    def __init__(self, spec: DichromatSpec, ctx: Optional[Context] = None):
+
+@dataclass(frozen=True)
+class NightSpec:
+    """A dichromat at night: apply_rod_vision in front of the colour stage with the values of the reference's
+    commented call (animals/cat.py:50-60), and apply_tapetum_bloom behind the post stage when `bloom` (its strength) is above 0."""
+
+    chroma_scale: float = 0.07
+    luminance_boost: float = 1.8
+    gamma: float = 0.7
+    bloom: float = 0.0
+
+    def __post_init__(self):
+        for name in ("chroma_scale", "luminance_boost", "gamma", "bloom"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f"NightSpec.{name} must be a finite number (got {v!r})")
+        if not 0.0 <= self.chroma_scale <= 1.0:
+            raise ValueError(f"NightSpec.chroma_scale must be in [0, 1] (got {self.chroma_scale})")
+        if not self.luminance_boost > 0.0:
+            raise ValueError(f"NightSpec.luminance_boost must be positive (got {self.luminance_boost})")
+        if not self.gamma > 0.0:
+            raise ValueError(f"NightSpec.gamma must be positive (got {self.gamma})")
+        if not 0.0 <= self.bloom <= 1.0:
+            raise ValueError(f"NightSpec.bloom must be in [0, 1] (got {self.bloom})")
+
+
+def night_desc(night: NightSpec):
+    """(avx_night_desc, the tap arrays it points into) for `night`."""
+    rod = gaussian_taps(cv_auto_ksize(ROD_SIGMA), ROD_SIGMA)
+    bloom = gaussian_taps(cv_auto_ksize(BLOOM_SIGMA), BLOOM_SIGMA)
+    nd = _lib.NightDesc()
+    nd.struct_size = ctypes.sizeof(_lib.NightDesc)
+    nd.chroma_scale, nd.luminance_boost, nd.gamma = float(night.chroma_scale), float(night.luminance_boost), float(night.gamma)
+    nd.rod_ksize = rod.size
+    nd.rod_taps_host = rod.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    nd.bloom_strength = float(night.bloom)
+    nd.bloom_ksize = bloom.size
+    nd.bloom_taps_host = bloom.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    return nd, (rod, bloom)
+
+
+class DichromatOp:
+    """Configured fused kernel launch for one species; reusable across frames (stateless between them).  With `night` (a NightSpec)
+    run_device and __call__ go to avx_dichromat_night_u8 (csrc/night.hip) instead of the day kernel."""
+
+    def __init__(self, spec: DichromatSpec, ctx: Optional[Context] = None, night: Optional[NightSpec] = None):
         self.spec = spec
         self.ctx = ctx
+        if night is not None and not isinstance(night, NightSpec):
+            raise TypeError(f"night must be a NightSpec or None (got {type(night).__name__})")
+        self.night = night
+        self.night_desc, self._night_taps = night_desc(night) if night is not None else (None, None)
         d = DichromatDesc()
         d.struct_size = ctypes.sizeof(DichromatDesc)
         if spec.color == "collapse":
@@ -185,6 +233,10 @@ class DichromatOp:
             if self._streak is None or self._streak.shape[0] != H:
                 self._streak = streak_row_tables(H, *self.spec.streak)
             self.desc.streak_rows_host = self._streak.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        if self.night is not None:  # (a frame below 13 x 13 is refused by the library, by name)
+            ctx._check(lib.avx_dichromat_night_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, ctypes.byref(self.desc),
+                                                  ctypes.byref(self.night_desc), ctx._s(stream)))
+            return
         ctx._check(lib.avx_dichromat_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, ctypes.byref(self.desc), ctx._s(stream)))
 
     def last_launch(self) -> dict:

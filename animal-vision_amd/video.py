@@ -44,7 +44,12 @@ INPUT and OUTPUT are a .y4m file, "-" (stdin / stdout, Y4M), or the other forms 
 `--batch N` (1..16) puts N frames into every pipeline slot: the plane-program species then run their launch chain once per N
 frames (planevm.DeviceBackend(frames=N): the frame is a grid dimension of the kernels), the dichromats and HoneyBee hand their
 kernels n_frames = N (with --hsi-model the network still runs frame by frame on the slot's stream; Cat's zoom and wide-view
-launches take the N frames of a slot each).  The species of the per-frame loop have no batched form: for them `--batch` above 1 is an error."""
+launches take the N frames of a slot each).  The species of the per-frame loop have no batched form: for them `--batch` above 1 is an error.
+
+`--night` shows one of the 20 dichromats by night: the reference's rod vision in front of the species' colour stage, and
+with `--bloom S` (0 < S <= 1) its tapetum bloom behind the post stage.  The species streams as by day:
+
+    python -m animal_vision_amd.video in.y4m out.y4m --species Cat --night --bloom 0.12 --split-compare"""
 from __future__ import annotations
 
 import argparse
@@ -72,6 +77,10 @@ def make_animal(args):
         from .ml import MSTPlusPlusPredictor
 
         kw["hsi_model"] = MSTPlusPlusPredictor(None if args.hsi_model == "seeded" else args.hsi_model, seed=0, half=True)
+    if getattr(args, "night", False):
+        from .dichromat import NightSpec
+
+        kw["night"] = NightSpec(bloom=args.bloom if getattr(args, "bloom", None) is not None else 0.0)
     return cls(**kw)
 
 
@@ -153,6 +162,23 @@ def _hsi_scale_arg(text: str) -> float:
     return v
 
 
+def _bloom_arg(text: str) -> float:
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--bloom takes a number (got {text!r})")
+    if not 0.0 < v <= 1.0:  # (also refuses nan)
+        raise argparse.ArgumentTypeError(f"--bloom must be above 0 and at most 1 (got {text!r})")
+    return v
+
+
+def is_dichromat(species: str) -> bool:
+    """Whether the display name is one of the 20 dichromats, the species that have a night form."""
+    from .animals._dichromats import _Dichromat
+
+    return issubclass(species_class(species), _Dichromat)
+
+
 def _wxh_arg(flag: str, example: str):
     def parse(text: str):
         try:
@@ -217,6 +243,11 @@ class _VideoParser(argparse.ArgumentParser):
         for flag, v in (("--hsi-model", args.hsi_model), ("--hsi-scale", args.hsi_scale)):
             if v is not None and args.species != "HoneyBee":
                 self.error(f"{flag} configures HoneyBee's RGB-to-spectrum conversion: --species {args.species} has none")
+        night, bloom = getattr(args, "night", False), getattr(args, "bloom", None)  # (add_night_options: parse_args adds them)
+        if bloom is not None and not night:
+            self.error("--bloom needs --night: the tapetum bloom is part of the night view")
+        if night and not is_dichromat(args.species):
+            self.error(f"--night: --species {args.species} is not one of the 20 dichromats, the species that have a night view")
         if args.hsi_model not in (None, "seeded") and not os.path.isfile(args.hsi_model):
             self.error(f"--hsi-model {args.hsi_model}: no such file (a local .pth checkpoint, or 'seeded')")
         check_io_options(self, args)
@@ -277,8 +308,18 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def add_night_options(ap: argparse.ArgumentParser) -> None:
+    """--night and --bloom.  parse_args adds them to build_parser()'s parser: build_parser() itself stays the option
+    list and help text that tests/golden/video_parser.json records."""
+    ap.add_argument("--night", action="store_true",
+                    help="the dichromats only: rod vision (scotopic luminance, desaturation, boost, gamma) in front of the species' colour stage")
+    ap.add_argument("--bloom", default=None, type=_bloom_arg, metavar="S",
+                    help="with --night, 0 < S <= 1: tapetum bloom of this strength (a luminance-gated screen blend with a sigma 3 blur)")
+
+
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap = build_parser()
+    add_night_options(ap)
     args = ap.parse_args(argv)
     check_raw_options(ap, args)
     return args

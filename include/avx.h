@@ -136,6 +136,33 @@ typedef struct avx_dichromat_launch_info {
 
 int avx_dichromat_last_launch(avx_ctx* ctx, avx_dichromat_launch_info* out);
 
+/* The dichromats at night (csrc/night.hip): apply_rod_vision (animals/animal_utils.py:261-305) between the decode and
+ * the colour stage -- the commented night branch of animals/cat.py:50-60 -- and, with bloom_strength > 0, apply_tapetum_bloom
+ * (animal_utils.py:183-204, sigma 3.0) between the chroma compression and the encode.  Everything else is avx_dichromat_u8's
+ * pipeline with the same avx_dichromat_desc (in_f32 = 1: float32 HWC sRGB frames in [0, 1], Cat after avx_binocular_warp_u8; variant
+ * is ignored).  Float32 throughout, codes within +-1 of the reference's arithmetic (device powf; Cat's float64 tail is rounded to
+ * float32 planes); the encode is the float32 threshold table.
+ * Per group of frames: k_night_front -> [avx_planes_gaussian_blur_batch | avx_streak_planes_f32 per frame] -> k_night_back, all on
+ * `stream`, nothing synchronises once the stream workspace's scratch holds the planes (12 B per pixel and frame, 24 B with a Gaussian
+ * or streak post stage; a batch is walked in groups of at most 16 frames and at most 1 GiB of scratch, AVX_NIGHT_GROUP=n forces
+ * groups of n).  Every frame's bytes are the same in any batch and any grouping.
+ * AVX_ERR_INVALID (avx_last_error starts with the function's name): NULL pointers, a desc of the wrong struct_size, H or W below 13
+ * (one BORDER_REFLECT_101 reflection must cover the 12-pixel bloom radius), tap counts other than 11 and 25, parameters out of range. */
+typedef struct avx_night_desc {
+    uint32_t struct_size;          /* sizeof(avx_night_desc)                                                      */
+    double chroma_scale;           /* 0..1: x = L (1 - chroma_scale) + x chroma_scale                              */
+    double luminance_boost;        /* > 0                                                                         */
+    double gamma;                  /* > 0: clip(x boost, 0, 1) ** gamma                                           */
+    int32_t rod_ksize;             /* 11: cv2.GaussianBlur((0, 0), 1.2) of the scotopic luminance                  */
+    const double* rod_taps_host;   /* rod_ksize normalised taps in double (getGaussianKernel), like taps_host      */
+    double bloom_strength;         /* 0: no bloom; else 0 < S <= 1                                                */
+    int32_t bloom_ksize;           /* 25: cv2.GaussianBlur((0, 0), 3.0) of the mask and the frame                  */
+    const double* bloom_taps_host; /* bloom_ksize taps in double; read only when bloom_strength > 0               */
+} avx_night_desc;
+
+int avx_dichromat_night_u8(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_hwc, int n_frames, int H, int W,
+                           const avx_dichromat_desc* desc, const avx_night_desc* night, void* stream);
+
 /* ---- UV / spectral path: uv_helpers.py, uv_mappers.py, ml/classic_rgb_to_hsi, animals/honeybee.py ----
  *
  * Planes are float32, K x (H*W), struct-of-arrays.  Float contract: within 1e-4 relative of the reference

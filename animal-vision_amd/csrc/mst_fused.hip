@@ -1130,6 +1130,32 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_mst_attn_tail_mx(const __half
     }
 }
 
+// AVX_TAIL_STAMPS=1: what the stamped tail kernels (16-row and marching) wrote, [blocks][nw][8] cycles, summed and printed: the share of each segment over all waves,
+// and per wave index the mean cycles of the segments whose work is dealt unevenly (v from x, conv1).
+static int tail_stamps_report(avx_ctx* ctx, hipStream_t s, unsigned long long* d_st, unsigned blocks, int nw, long total, int C, const char* form) {
+    const size_t n = (size_t)blocks * nw * 8;
+    AVX_HIP(ctx, hipStreamSynchronize(s));
+    unsigned long long* h_st = (unsigned long long*)malloc(n * sizeof(unsigned long long));
+    AVX_HIP(ctx, hipMemcpy(h_st, d_st, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    double tot[8] = {0}, all = 0, wv0[16] = {0}, wv2[16] = {0};
+    for (size_t i = 0; i < n; ++i) {
+        tot[i & 7] += (double)h_st[i]; all += (double)h_st[i];
+        if ((i & 7) == 0) wv0[(i >> 3) % nw] += (double)h_st[i];
+        if ((i & 7) == 2) wv2[(i >> 3) % nw] += (double)h_st[i];
+    }
+    const char* nm[8] = {"v from x", "bar1", "conv1+gelu", "conv2+proj+store", "bar2", "-", "-", "-"};
+    fprintf(stderr, "[tail stamps C=%d%s] %u blocks, %ld tiles, mean cycles per wave %.0f:", C, form, blocks, total, all / (blocks * (double)nw));
+    for (int k2 = 0; k2 < 8; ++k2) fprintf(stderr, "  %s %.1f%%", nm[k2], 100 * tot[k2] / all);
+    fprintf(stderr, "\n    mean cycles per wave index, v from x:");
+    for (int w2 = 0; w2 < nw; ++w2) fprintf(stderr, " %.0f", wv0[w2] / blocks);
+    fprintf(stderr, "; conv1+gelu:");
+    for (int w2 = 0; w2 < nw; ++w2) fprintf(stderr, " %.0f", wv2[w2] / blocks);
+    fprintf(stderr, "\n");
+    free(h_st);
+    (void)hipFree(d_st);
+    return AVX_OK;
+}
+
 template <int C, int TR, int MINW, int NW = 8, bool DWS = false>
 int launch_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack, const void* mpack, const void* dw1, const void* dw2, const float* bias, void* out, int B, int H, int W,
                         hipStream_t s) {
@@ -1146,23 +1172,326 @@ int launch_attn_tail_mx(avx_ctx* ctx, const void* x, const void* wvpack, const v
         AVX_HIP(ctx, hipMalloc((void**)&d_st, n * sizeof(unsigned long long)));
         AVX_HIP(ctx, hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(ks, dim3(blocks), dim3(64 * NW), lds, s, (const __half*)x, (const uint4*)wvpack, (const uint4*)mpack, (const uint4*)dw1, (const uint4*)dw2, bias, (__half*)out, B, H, W, d_st, mst_tile_order());
-        AVX_HIP(ctx, hipStreamSynchronize(s));
-        unsigned long long* h_st = (unsigned long long*)malloc(n * sizeof(unsigned long long));
-        AVX_HIP(ctx, hipMemcpy(h_st, d_st, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        double tot[8] = {0}, all = 0;
-        for (size_t i = 0; i < n; ++i) { tot[i & 7] += (double)h_st[i]; all += (double)h_st[i]; }
-        const char* nm[8] = {"v from x", "bar1", "conv1+gelu", "conv2+proj+store", "bar2", "-", "-", "-"};
-        fprintf(stderr, "[tail stamps C=%d] %u blocks, %ld tiles, mean cycles per wave %.0f:", C, blocks, total, all / (blocks * (double)NW));
-        for (int k2 = 0; k2 < 8; ++k2) fprintf(stderr, "  %s %.1f%%", nm[k2], 100 * tot[k2] / all);
-        fprintf(stderr, "\n");
-        free(h_st);
-        (void)hipFree(d_st);
-        return AVX_OK;
+        return tail_stamps_report(ctx, s, d_st, blocks, NW, total, C, "");
     }
     auto k = k_mst_attn_tail_mx<C, TR, MINW, false, NW, DWS>;
     AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * NW), lds, s, (const __half*)x, (const uint4*)wvpack, (const uint4*)mpack, (const uint4*)dw1,
                        (const uint4*)dw2, bias, (__half*)out, B, H, W, (unsigned long long*)nullptr, mst_tile_order());
+    AVX_HIP(ctx, hipGetLastError());
+    return AVX_OK;
+}
+
+
+// ---- the matrix-pipe attention tail as a march down tile columns (round 11) -----------------------------------------------------------------
+// k_mst_attn_tail_mx forms v on TR + 4 halo rows and mid on TR + 2 for TR output rows; here a workgroup walks a run of the column-major tile order downwards
+// (ColumnSteps) and what the tile above already formed stays on chip.  Tiles are TB column blocks of 14 pixels wide and TR rows tall; with the tile's first output
+// row at y0, LDS row r of the v map (and of the stash of raw x rows) is image row y0 + r, r = 0 ... TR + 1, and mid pair j is image rows y0 + 2j - 1, y0 + 2j,
+// j = 0 ... TR/2.  Output pair k (rows y0 + 2k, + 1) takes mid pairs k, k + 1, v rows 2k, 2k + 1 (projection) and stash rows 2k, 2k + 1 (residual); mid pair j takes
+// v rows 2j - 2 ... 2j + 1.
+//   carried in:   v rows 0, 1 and stash rows 0, 1 (rows TR, TR + 1 of the tile above); mid pair 0 (pair TR/2 of the tile above)
+//   new per step: v / stash rows 2 ... TR + 1 from x rows y0 + 2 ... y0 + TR + 1 (TR x (14 TB + 4) pixels: exactly 8 groups of 32 at 28 x 8 and at 14 x 14, one per wave),
+//                 mid pairs 1 ... TR/2, output pairs 0 ... TR/2 - 1
+// The carry is lane-local: the lane of phase A that writes a v or stash pixel of rows TR, TR + 1 first moves the old content of that address up by TR rows -- behind
+// the "v free" barrier, in front of "v complete"; rows 0, 1 have no other writer.  A wave keeps its last conv1 result (its 8 bytes per lane of mid pair TR/2) in two
+// registers and stores it to pair 0 at the top of the next step: mid bytes are their wave's own.  Two barriers per step, as before; x is requested once.
+// Wave = (octet, column block): NOCT * TB = 8 waves, each with all rows of its octet and block: TR/2 conv1 units and TR/2 conv2 + projection units, none computed twice.
+// Block blk's mid columns 0 ... 15 are image columns x0 + 14 blk - 1 ..., its v columns 14 blk ... 14 blk + 17 of the 14 TB + 4 wide map (x0 - 2 ...).
+// Segment starts (ColumnSteps: a walk's first tile, the top of a column): a PRIMING step, the same step on the tile above (y0 - TR, which is -TR at the top of a
+// frame) reduced to phase A and the last conv1 unit, which reads new v rows only (TR - 2 ... TR + 1): no conv2, no stores.  Its v and stash rows TR, TR + 1 and its
+// mid pair TR/2 are what the tile below carries in -- zeros above the frame, through the clamped fetch and the mid mask.  Whatever stale content its own carry
+// moves into rows 0, 1 and pair 0 is read by nobody: the next step's carry overwrites it.
+// Bounds.  A step fetches rows y0 + 2 ... y0 + TR + 1, columns x0 - 2 ... x0 + 14 TB + 1.  The fast path (scalar origin + fixed lane offsets) is taken only when
+// 0 <= y0 + 2, y0 + TR + 1 <= H - 1, 0 <= x0 - 2 and x0 + 14 TB + 1 <= W - 1: every lane's pixel (row offset <= TR - 1, column offset <= 14 TB + 3; the lanes past
+// the last pixel of the last group repeat it) then lies in frame b.  Every other step -- priming steps above the frame among them: y0 + 2 = 2 - TR < 0 -- clamps
+// row and column into the frame and zeroes what lay outside.  Stores go to rows y0 + 2k + (0, 1) < H and columns < W of real steps (y0 >= 0) only.
+// A v pixel, a mid pixel, the projection's K order and the residual are what k_mst_attn_tail_mx computes: the results are the same to the bit.
+#ifndef AVX_TAIL_MARCH_PIPE2
+#define AVX_TAIL_MARCH_PIPE2 1  // conv2 with two units in flight (0: one, for an A/B)
+#endif
+template <int C, int TB, int TR, int MINW, bool STAMP = false, bool DWS = false>
+__global__ __launch_bounds__(512, MINW) void k_mst_attn_tail_march(const __half* __restrict__ x /*[B][H][W][C]*/, const uint4* __restrict__ wvpack /*[C/32][C/16][64], half-row K order*/,
+                                                                   const uint4* __restrict__ mpack /*[C/8][C/16][64]*/, const uint4* __restrict__ dw1 /*[C/8][3][64]*/,
+                                                                   const uint4* __restrict__ dw2 /*[C/8][3][64]*/, const float* __restrict__ bias /*[C] or NULL*/,
+                                                                   __half* __restrict__ out, int B, int H, int W, unsigned long long* __restrict__ stamps /*STAMP: [blocks][8][8]*/) {
+    constexpr int NW = 8, TW = 14, SW = TW * TB, VW = SW + 4, NR = TR + 2, NU = TR / 2, NOCT = C / 8, NK = C / 16, NT = C / 32, NS = C / 16, LNV = C / 16;
+    constexpr int PP = C * 2 + 16, RP = (VW * PP + 255) / 256 * 256, MP = TB * 16 * PP;  // pixel pitch; row pitch of v and of mid (TB blocks of 16 px): multiples of 256 bytes
+    constexpr int NTHR = 64 * NW, NPIX = TR * VW, NG = (NPIX + 31) / 32, NGW = (NG + NW - 1) / NW;  // new halo pixels per step; their 32-pixel groups; per wave
+    static_assert((C == 32 || C == 64) && NOCT * TB == NW && TR % 2 == 0 && TR >= 4, "wave = (octet, column block)");
+    static_assert(MP % 256 == 0 && RP % 256 == 0, "pitches");
+    extern __shared__ __align__(16) unsigned char smem[];
+    unsigned char* vt = smem;                                     // [NR][RP]: v (zeros outside the image)
+    unsigned char* mt = vt + (size_t)NR * RP;                     // [NR][TB][16] x PP: mid = gelu(dw1(v)); an (octet, block)'s bytes belong to its wave
+    uint4* wvl = reinterpret_cast<uint4*>(mt + (size_t)NR * MP);  // [NT * NS][64]: W_v's fragments (also absorbs the reads of the two unused columns past the last mid row)
+    unsigned char* xs = reinterpret_cast<unsigned char*>(wvl + NT * NS * 64);  // [NR][SW] x PP: the raw x rows of the tile's columns (the residual); reads of lanes 14, 15 run into the next row
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, p = lane & 31, h = lane >> 5, n16 = lane & 15, q = lane >> 4;
+    // STAMP (AVX_TAIL_STAMPS=1): the five segments of k_mst_attn_tail_mx
+    unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
+    auto stamp = [&](int kk) {
+        if constexpr (STAMP) {
+            const unsigned long long now = __builtin_readcyclecounter();
+            seg[kk] += now - tlast;
+            tlast = now;
+        }
+    };
+    if constexpr (STAMP) tlast = __builtin_readcyclecounter();
+    const int tx = (W + SW - 1) / SW, ty = (H + TR - 1) / TR;
+    for (int i = tid; i < NT * NS * 64; i += NTHR) wvl[i] = wvpack[i];
+    const int o = wave % NOCT, blk = wave / NOCT, cb = TW * blk;  // this wave's octet, column block and the block's first tile column
+    half8_t a1[3], a2[3], am[NK];
+    float bs[4];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        a1[i] = dw_frag<DWS>(dw1 + ((size_t)o * 3 + i) * 64 + lane, i);
+        a2[i] = dw_frag<DWS>(dw2 + ((size_t)o * 3 + i) * 64 + lane, i);
+    }
+#pragma unroll
+    for (int t2 = 0; t2 < NK; ++t2) am[t2] = __builtin_bit_cast(half8_t, mpack[((size_t)o * NK + t2) * 64 + lane]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bs[j] = bias ? bias[8 * o + 4 * (q & 1) + j] : 0.f;
+    // used once here, so that the wait for these loads sits in front of the step loop (see k_mst_attn_tail_mx)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) asm volatile("" ::"v"(a1[i]), "v"(a2[i]));
+#pragma unroll
+    for (int t2 = 0; t2 < NK; ++t2) asm volatile("" ::"v"(am[t2]));
+    asm volatile("" ::"v"(bs[0]), "v"(bs[1]), "v"(bs[2]), "v"(bs[3]));
+    // lane-constant LDS addresses: row pair, column shift and K step are immediates
+    const unsigned char* rbB = vt + (size_t)q * RP + (size_t)(cb + n16) * PP + 16 * o;                         // first conv's B operand: + 2 (j - 1) RP + i PP
+    unsigned char* wbB = mt + (size_t)(q >> 1) * MP + (size_t)(16 * blk + n16) * PP + 16 * o + 8 * (q & 1);     // mid: + 2 j MP
+    const unsigned char* rbC = mt + (size_t)q * MP + (size_t)(16 * blk + n16) * PP + 16 * o;                    // second conv's B operand: + 2 k MP + i PP
+    const unsigned char* rbG = vt + (size_t)(q & 1) * RP + (size_t)(cb + n16 + 2) * PP + 16 * (q >> 1);         // projection's B operand: + 2 k RP + 32 t
+    const unsigned char* rbX = xs + (size_t)((q >> 1) * SW + cb + n16) * PP + 16 * o + 8 * (q & 1);             // residual: + 2 k SW PP
+    // this wave's groups of new halo pixels: where a lane's pixel sits in the frame (relative to the step's first new pixel), in the v map and in the stash
+    unsigned f_rel[NGW];
+    int v_dst[NGW], s_dst[NGW], p_row[NGW], p_col[NGW];
+#pragma unroll
+    for (int gi = 0; gi < NGW; ++gi) {
+        const int g = wave + NW * gi, qq = 32 * g + p, qc = qq < NPIX ? qq : NPIX - 1;
+        const bool mine = g < NG && qq < NPIX;
+        p_row[gi] = qc / VW; p_col[gi] = qc % VW;
+        f_rel[gi] = (unsigned)((p_row[gi] * W + p_col[gi]) * C + h * (C / 2)) * 2u;
+        v_dst[gi] = mine ? (p_row[gi] + 2) * RP + p_col[gi] * PP + 32 * h : -1;
+        s_dst[gi] = (mine && (unsigned)(p_col[gi] - 2) < (unsigned)SW) ? ((p_row[gi] + 2) * SW + p_col[gi] - 2) * PP + h * C : -1;
+    }
+    uint4 pre[NGW][LNV];  // a lane's half row of its new halo pixels: fetched a step ahead, consumed as MFMA operands
+    auto fetch = [&](int x0, int y0, long b) {
+        if (y0 + 2 >= 0 && y0 + TR + 2 <= H && x0 >= 2 && x0 + SW + 2 <= W) {  // the new rows and their halo columns inside the frame (Bounds, above)
+            const char* origin = reinterpret_cast<const char*>(x + ((b * H + y0 + 2) * (size_t)W + x0 - 2) * C);
+#pragma unroll
+            for (int gi = 0; gi < NGW; ++gi) {
+                if (wave + NW * gi >= NG) break;
+                unsigned of = f_rel[gi];
+                asm volatile("" : "+v"(of));
+                const uint4* src = reinterpret_cast<const uint4*>(origin + of);
+#pragma unroll
+                for (int v = 0; v < LNV; ++v) pre[gi][v] = src[v];
+            }
+            return;
+        }
+#pragma unroll
+        for (int gi = 0; gi < NGW; ++gi) {
+            if (wave + NW * gi >= NG) break;
+            const int yy = y0 + 2 + p_row[gi], xx = x0 - 2 + p_col[gi];
+            const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;  // zeros outside the image: v = 0 there (to_v has no bias), the convs' padding
+            const int yc = yy < 0 ? 0 : (yy >= H ? H - 1 : yy), xc = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
+            const uint4* src = reinterpret_cast<const uint4*>(x + ((b * H + yc) * (size_t)W + xc) * C + h * (C / 2));
+#pragma unroll
+            for (int v = 0; v < LNV; ++v) {
+                uint4 r = src[v];
+                r.x = ok ? r.x : 0u; r.y = ok ? r.y : 0u; r.z = ok ? r.z : 0u; r.w = ok ? r.w : 0u;
+                pre[gi][v] = r;
+            }
+        }
+    };
+    ColumnSteps ahead;  // after next(): the step to run; the walk inside is one tile further
+    ahead.init(blockIdx.x, gridDim.x, B, ty, tx);
+    if (!ahead.next()) return;
+    int x0 = ahead.xi * SW, y0 = ahead.yi * TR;
+    long fb = ahead.b;
+    bool prime = ahead.prime;
+    fetch(x0, y0, fb);
+    uint2 cm = uint2{0, 0};  // this wave's bytes of mid pair TR/2 of the step before: the next step's pair 0
+    __syncthreads();  // W_v's fragments are in LDS
+    for (;;) {
+        *reinterpret_cast<uint2*>(wbB) = cm;
+        // ---- phase A: v = float16(x W_v^T) for this wave's new halo pixels, straight from the prefetched rows; rows TR, TR + 1 first move up ----
+#pragma unroll
+        for (int gi = 0; gi < NGW; ++gi) {
+            if (wave + NW * gi >= NG) break;  // wave-uniform
+            const bool carry = v_dst[gi] >= TR * RP;
+            if (carry) {  // this lane's 32 NT bytes of v and, inside the tile's columns, its half row of x: up by TR rows, before the new content lands
+                uint4* vd = reinterpret_cast<uint4*>(vt + v_dst[gi]);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const uint4 c0 = vd[4 * nt], c1 = vd[4 * nt + 1];
+                    vd[4 * nt - TR * RP / 16] = c0; vd[4 * nt + 1 - TR * RP / 16] = c1;
+                }
+                if (s_dst[gi] >= 0) {
+                    uint4* sd = reinterpret_cast<uint4*>(xs + s_dst[gi]);
+#pragma unroll
+                    for (int v = 0; v < LNV; ++v) { const uint4 c0 = sd[v]; sd[v - TR * SW * PP / 16] = c0; }
+                }
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                float16_t d;
+#pragma unroll
+                for (int vv = 0; vv < 16; ++vv) d[vv] = 0.f;
+#pragma unroll
+                for (int s2 = 0; s2 < NS; ++s2) d = mfma16(__builtin_bit_cast(half8_t, wvl[(nt * NS + s2) * 64 + lane]), __builtin_bit_cast(half8_t, pre[gi][s2]), d);
+                if (v_dst[gi] >= 0) {
+                    half8_t w0, w1;
+#pragma unroll
+                    for (int vv = 0; vv < 8; ++vv) { w0[vv] = (_Float16)d[vv]; w1[vv] = (_Float16)d[8 + vv]; }
+                    uint4* dst = reinterpret_cast<uint4*>(vt + v_dst[gi] + 64 * nt);
+                    dst[0] = __builtin_bit_cast(uint4, w0);
+                    dst[1] = __builtin_bit_cast(uint4, w1);
+                }
+            }
+            if (s_dst[gi] >= 0) {
+                unsigned char* dst = xs + s_dst[gi];
+#pragma unroll
+                for (int v = 0; v < LNV; ++v) *reinterpret_cast<uint4*>(dst + 16 * v) = pre[gi][v];
+            }
+        }
+        stamp(0);
+        __syncthreads();  // v complete
+        stamp(1);
+        const bool more = ahead.next();
+        if (more) fetch(ahead.xi * SW, ahead.yi * TR, ahead.b);  // the next step's new rows: in flight while this wave works through its units
+        // ---- conv1 + GELU -> mid pairs 1 ... NU of this wave's octet and block (zero outside the image: the second conv's padding applies to THIS map) ----
+        {
+            const bool mid_inside = y0 + 1 >= 0 && y0 + TR + 1 <= H && x0 + cb >= 1 && x0 + cb + 15 <= W;  // scalar: rows y0 + 1 ... y0 + TR, columns x0 + cb - 1 ... + 14
+            // software pipeline, one unit deep: unit j's MFMAs | reads of unit j + 1 | GELU + store of unit j - 1
+            uint4 bq[3];
+            auto rd = [&](int j) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) bq[i] = *reinterpret_cast<const uint4*>(rbB + (size_t)(2 * (j - 1)) * RP + i * PP);
+            };
+            auto finish = [&](int j, float4_t a) {
+                float2_t gp[2] = {float2_t{a[0], a[1]}, float2_t{a[2], a[3]}};
+                if constexpr (C >= 64) gelu_mx<2>(gp);
+                else { float2_t g0[1] = {gp[0]}, g1[1] = {gp[1]}; gelu_mx<1>(g0); gelu_mx<1>(g1); gp[0] = g0[0]; gp[1] = g1[0]; }
+                uint2 ov = uint2{pack_f16(gp[0].x, gp[0].y), pack_f16(gp[1].x, gp[1].y)};
+                if (!mid_inside) {
+                    const int yy = y0 - 1 + 2 * j + (q >> 1), xx = x0 + cb - 1 + n16;
+                    const unsigned keep = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? 0xffffffffu : 0u;
+                    ov.x &= keep; ov.y &= keep;
+                }
+                *reinterpret_cast<uint2*>(wbB + (size_t)(2 * j) * MP) = ov;
+                return ov;
+            };
+            if (prime) {  // only the pair the tile below carries in
+                rd(NU);
+                cm = finish(NU, dw_unit<DWS>(a1, bq));
+            } else {
+                rd(1);
+                float4_t prev = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 1; j <= NU; ++j) {
+                    const float4_t acc = dw_unit<DWS>(a1, bq);
+                    if (j < NU) rd(j + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (j > 1) finish(j - 1, prev);
+                    __builtin_amdgcn_sched_barrier(0);
+                    prev = acc;
+                }
+                cm = finish(NU, prev);
+            }
+        }
+        stamp(2);
+        // ---- conv2(mid) + v @ M + bias + x for output pairs 0 ... NU - 1, stored from registers (a priming step has none) ----
+        if (!prime) {
+            // where unit u's 8 bytes go: e0 + u * estep elements, when the pixel lies in the frame
+            const int yo0 = y0 + (q >> 1), xo = x0 + cb + n16;
+            const bool livex = n16 < TW && xo < W;
+            const size_t e0 = ((fb * H + (yo0 < H ? yo0 : 0)) * (size_t)W + (livex ? xo : 0)) * C + 8 * o + 4 * (q & 1), estep = (size_t)2 * W * C;
+            auto live = [&](int u) { return livex && yo0 + 2 * u < H; };
+            uint4 bq[3], bg[NK];
+            uint2 xn = uint2{0, 0};  // unit u's piece of x, read with its operands
+            auto rd = [&](int u) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) bq[i] = *reinterpret_cast<const uint4*>(rbC + (size_t)(2 * u) * MP + i * PP);
+#pragma unroll
+                for (int t2 = 0; t2 < NK; ++t2) bg[t2] = *reinterpret_cast<const uint4*>(rbG + (size_t)(2 * u) * RP + 32 * t2);
+                xn = *reinterpret_cast<const uint2*>(rbX + (size_t)(2 * u) * SW * PP);
+            };
+            auto finish = [&](int u, float4_t acc, uint2 xu) {
+                if (live(u)) {  // ((pos_emb + projection) + bias) + x: the float16 residual taken as it is (v_fma_mix_f32: x * 1.0 + sum)
+                    constexpr unsigned kOnes = 0x3c003c00u;
+                    float s0 = acc[0] + bs[0], s1 = acc[1] + bs[1], s2 = acc[2] + bs[2], s3 = acc[3] + bs[3];
+                    fma_mix_lo(s0, xu.x, kOnes); fma_mix_hi(s1, xu.x, kOnes);
+                    fma_mix_lo(s2, xu.y, kOnes); fma_mix_hi(s3, xu.y, kOnes);
+                    *reinterpret_cast<uint2*>(out + e0 + u * estep) = uint2{pack_f16(s0, s1), pack_f16(s2, s3)};
+                }
+            };
+            rd(0);
+            if constexpr (AVX_TAIL_MARCH_PIPE2) {
+                // two units in flight: unit u's 3 + NK MFMAs | the reads of unit u + 1 | sums and store of unit u - 1
+                float4_t prev = {0.f, 0.f, 0.f, 0.f};
+                uint2 xp = uint2{0, 0};
+#pragma unroll
+                for (int u = 0; u < NU; ++u) {
+                    const uint2 xu = xn;
+                    float4_t acc = dw_unit<DWS>(a2, bq);
+#pragma unroll
+                    for (int t2 = 0; t2 < NK; ++t2) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(am[t2], __builtin_bit_cast(half8_t, bg[t2]), acc, 0, 0, 0);
+                    if (u + 1 < NU) rd(u + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (u > 0) finish(u - 1, prev, xp);
+                    __builtin_amdgcn_sched_barrier(0);
+                    prev = acc; xp = xu;
+                }
+                finish(NU - 1, prev, xp);
+            } else {
+#pragma unroll
+                for (int u = 0; u < NU; ++u) {
+                    const uint2 xu = xn;
+                    float4_t acc = dw_unit<DWS>(a2, bq);
+#pragma unroll
+                    for (int t2 = 0; t2 < NK; ++t2) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(am[t2], __builtin_bit_cast(half8_t, bg[t2]), acc, 0, 0, 0);
+                    if (u + 1 < NU) rd(u + 1);
+                    finish(u, acc, xu);
+                }
+            }
+        }
+        stamp(3);
+        if (!more) break;
+        x0 = ahead.xi * SW; y0 = ahead.yi * TR; fb = ahead.b; prime = ahead.prime;
+        __syncthreads();  // every wave is done reading v and the stash: the next step's rows may be written
+        stamp(4);
+    }
+    if constexpr (STAMP) {
+        if (lane == 0 && stamps)
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk) stamps[((size_t)blockIdx.x * NW + wave) * 8 + kk] = seg[kk];
+    }
+}
+
+template <int C, int TB, int TR, int MINW, bool DWS>
+int launch_attn_tail_march(avx_ctx* ctx, const void* x, const void* wvpack, const void* mpack, const void* dw1, const void* dw2, const float* bias, void* out, int B, int H, int W,
+                           int max_workgroups, hipStream_t s) {
+    constexpr int PP = C * 2 + 16, SW = 14 * TB, RP = ((SW + 4) * PP + 255) / 256 * 256;
+    constexpr size_t lds = (size_t)(TR + 2) * RP + (size_t)(TR + 2) * TB * 16 * PP + (size_t)(C / 32) * (C / 16) * 1024 + (size_t)(TR + 2) * SW * PP;  // v, mid, W_v, stash
+    static_assert(lds * (MINW / 2) <= 160 * 1024, "LDS for MINW / 2 workgroups per CU");
+    const long total = (long)B * ((H + TR - 1) / TR) * ((W + SW - 1) / SW);
+    const long cap = (long)ctx->num_cus * (MINW / 2);
+    AVX_REQUIRE(ctx, total <= 0x7fffffffl, "avx_mst_attn_tail_mx_col: 2^31 tiles or more");
+    long nwg = total < cap ? total : cap;
+    if (max_workgroups > 0 && max_workgroups < nwg) nwg = max_workgroups;
+    const unsigned blocks = (unsigned)nwg;
+    if (getenv("AVX_TAIL_STAMPS")) {
+        auto ks = k_mst_attn_tail_march<C, TB, TR, MINW, true, DWS>;
+        unsigned long long* d_st = nullptr;
+        AVX_HIP(ctx, hipMalloc((void**)&d_st, (size_t)blocks * 8 * 8 * sizeof(unsigned long long)));
+        AVX_HIP(ctx, hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(ks, dim3(blocks), dim3(512), lds, s, (const __half*)x, (const uint4*)wvpack, (const uint4*)mpack, (const uint4*)dw1, (const uint4*)dw2, bias, (__half*)out, B, H, W, d_st);
+        return tail_stamps_report(ctx, s, d_st, blocks, 8, total, C, " march");
+    }
+    auto k = k_mst_attn_tail_march<C, TB, TR, MINW, false, DWS>;
+    AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(512), lds, s, (const __half*)x, (const uint4*)wvpack, (const uint4*)mpack, (const uint4*)dw1, (const uint4*)dw2, bias,
+                       (__half*)out, B, H, W, (unsigned long long*)nullptr);
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
 }
@@ -2023,6 +2352,58 @@ extern "C" int avx_mst_attn_tail_sp(avx_ctx* ctx, const void* x, const void* wvp
                                     const float* bias, void* out, int B, int H, int W, int C, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
     return attn_tail_mx_launch<true>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, C, stream);
+}
+
+// avx_mst_attn_tail_mx / _sp as a march down tile columns (k_mst_attn_tail_march): the same arguments, the same results to the bit.  C = 32 (28 x 8 tiles) or 64
+// (14 x 14); C = 128 stays on the 14 x 8 kernel.  max_workgroups > 0 caps the grid below the launcher's own cap.
+template <bool DWS>
+static int attn_tail_march_launch(avx_ctx* ctx, const char* fn, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack, const float* bias,
+                                  void* out, int B, int H, int W, int C, int max_workgroups, void* stream) {
+    AVX_REQUIRE(ctx, x && wvpack16 && mpack_mx && dw1pack && dw2pack && out && B > 0 && H > 0 && W > 0, "%s: NULL pointer or empty tensor", fn);
+    AVX_REQUIRE(ctx, (C == 32 || C == 64) && max_workgroups >= 0, "%s: C=%d (32 or 64), max_workgroups=%d (>= 0)", fn, C, max_workgroups);
+    AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)wvpack16 | (uintptr_t)mpack_mx | (uintptr_t)out | (uintptr_t)dw1pack | (uintptr_t)dw2pack)) & 15u) == 0,
+                "%s: pointers must be 16-byte aligned", fn);
+    AVX_REQUIRE(ctx, x != out, "%s: neighbouring tiles read each other's rows of x: the output cannot be x", fn);
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    if (C == 32) return launch_attn_tail_march<32, 2, 8, 4, DWS>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, max_workgroups, s);
+    // 14 x 16 steps (9 groups: one wave still runs two; 8 + 8 units) measured 3 % SLOWER than the 14 x 16 kernel, 14 x 14 steps 3 % faster (profiles/r11/ab_tail_march.txt)
+    return launch_attn_tail_march<64, 1, 14, 2, DWS>(ctx, x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, max_workgroups, s);
+}
+extern "C" int avx_mst_attn_tail_mx_col(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack,
+                                        const float* bias, void* out, int B, int H, int W, int C, int max_workgroups, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    return attn_tail_march_launch<false>(ctx, "avx_mst_attn_tail_mx_col", x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, C, max_workgroups, stream);
+}
+extern "C" int avx_mst_attn_tail_sp_col(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack,
+                                        const float* bias, void* out, int B, int H, int W, int C, int max_workgroups, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    return attn_tail_march_launch<true>(ctx, "avx_mst_attn_tail_sp_col", x, wvpack16, mpack_mx, dw1pack, dw2pack, bias, out, B, H, W, C, max_workgroups, stream);
+}
+
+// The steps of the marching tail (ColumnSteps), run on the host with the kernel's own walk: visit[wg * steps_cap + k] = raster index ((frame * ty + row) * tx + column)
+// of the tile workgroup wg of nwg works on at its k-th step, -1 past its last one; prime[...] = 1 where that step is a priming step: it runs on the tile ABOVE the
+// one in visit[] (which the next step then computes) and stores nothing.
+extern "C" int avx_mst_tail_march_steps(int frames, int ty, int tx, int nwg, long long* visit, unsigned char* prime, int steps_cap, int* steps_out) {
+    if (frames <= 0 || ty <= 0 || tx <= 0 || nwg <= 0 || ((visit || prime) && steps_cap <= 0) || (long long)frames * ty * tx > 0x7fffffffll) return AVX_ERR_INVALID;
+    int most = 0;
+    for (int wg = 0; wg < nwg; ++wg) {
+        ColumnSteps st;
+        st.init((unsigned)wg, (unsigned)nwg, frames, ty, tx);
+        int k = 0;
+        for (; st.next(); ++k)
+            if (k < steps_cap) {
+                if (visit) visit[(size_t)wg * steps_cap + k] = ((long long)st.b * ty + st.yi + (st.prime ? 1 : 0)) * tx + st.xi;
+                if (prime) prime[(size_t)wg * steps_cap + k] = st.prime ? 1 : 0;
+            }
+        for (int r = k; r < steps_cap; ++r) {
+            if (visit) visit[(size_t)wg * steps_cap + r] = -1;
+            if (prime) prime[(size_t)wg * steps_cap + r] = 0;
+        }
+        most = k > most ? k : most;
+    }
+    if (steps_out) *steps_out = most;
+    return AVX_OK;
 }
 
 extern "C" int avx_mst_conv3x3_lds(avx_ctx* ctx, const void* x, const void* wpack16, const void* add, void* out, int B, int H, int W, int C, void* stream) {

@@ -126,3 +126,27 @@ struct ColumnWalk {
         b += cx;
     }
 };
+
+// COLUMN STEPS (round 11): the marching attention tail carries v rows, a mid row pair and stash rows from the tile above.  At a segment start they are not on chip,
+// and the kernel gets them by running an ordinary step on the tile ABOVE (row index yi - 1, which is -1 at the top of a column) with its stores masked: a PRIMING
+// step.  This is the ColumnWalk with those steps put in: next() yields the step to run (false: the walk is over), and the walk itself stays a step ahead, so the
+// kernel can prefetch the step after the one it works on.
+struct ColumnSteps {
+    ColumnWalk wk;
+    bool primed;     // the last step yielded was the priming step of wk's tile
+    int xi, yi, b;   // the step's tile (yi = -1: the tile above the frame's first row)
+    bool prime;      // a priming step: nothing is stored
+
+    __host__ __device__ __forceinline__ void init(unsigned wg, unsigned nwg, int frames, int ty_, int tx_) {
+        wk.init(wg, nwg, frames, ty_, tx_);
+        primed = false;
+    }
+    __host__ __device__ __forceinline__ bool next() {
+        if (!wk.live) return false;
+        prime = wk.seg && !primed;
+        xi = wk.xi; b = wk.b; yi = wk.yi - (prime ? 1 : 0);
+        primed = prime;
+        if (!prime) wk.advance();
+        return true;
+    }
+};

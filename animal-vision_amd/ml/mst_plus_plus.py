@@ -242,6 +242,8 @@ class _AvxOps:
         self.FFN_FUSED_C = tuple(int(v) for v in os.environ.get("AVX_MST_FFN_FUSED_C", "32,64,128").split(",") if v)
         self._ffn_march = os.environ.get("AVX_MST_NO_FFN_MARCH", "") == ""  # A/B: the matrix-pipe FeedForward kernel marches down tile columns in 14-row steps (round 10)
         self.FFN_MARCH_C = (32, 64)  # the widths the marching form is built for (C = 128 stays on the 16-row kernel)
+        self._tail_march = os.environ.get("AVX_MST_NO_TAIL_MARCH", "") == ""  # A/B: the matrix-pipe attention tail marches down tile columns, carrying v, x and mid rows (round 11)
+        self.TAIL_MARCH_C = (32, 64)  # the widths at which the marching form measured faster, dense and sparse, kernel against kernel (profiles/r11/ab_tail_march.txt)
         self._ctx = {}
 
     def ctx(self, device: torch.device):
@@ -563,18 +565,25 @@ class _AvxOps:
         return out
 
     def attn_tail_mx(self, x: torch.Tensor, wvpack16: torch.Tensor, mpack_mx: torch.Tensor, dw1: torch.Tensor, dw2: torch.Tensor, bias: torch.Tensor,
-                     out: torch.Tensor = None, sparse: bool = False) -> torch.Tensor:
+                     out: torch.Tensor = None, sparse: bool = False, march: bool = False, max_workgroups: int = 0) -> torch.Tensor:
         """pos_emb(v) + v @ M + bias + x with v = float16(x @ W_v) formed inside the kernel and both depthwise convs on the matrix pipe, on one
-        (h, w, c) float16 frame (csrc/mst_fused.hip::k_mst_attn_tail_mx).  sparse: dw1 / dw2 are pack_dw_smfmac fragments (avx_mst_attn_tail_sp)."""
+        (h, w, c) float16 frame (csrc/mst_fused.hip::k_mst_attn_tail_mx).  sparse: dw1 / dw2 are pack_dw_smfmac fragments (avx_mst_attn_tail_sp).
+        march (c = 32 or 64): the column-marching form (avx_mst_attn_tail_mx_col / _sp_col), the same result to the bit; max_workgroups > 0 caps its grid (tests)."""
         from .._lib import lib
 
         h, w, c = x.shape
         assert x.is_contiguous()
         out = torch.empty_like(x) if out is None else out
         ctx = self.ctx(x.device)
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        if march:
+            fn = lib.avx_mst_attn_tail_sp_col if sparse else lib.avx_mst_attn_tail_mx_col
+            ctx._check(fn(ctx._h, x.data_ptr(), wvpack16.data_ptr(), mpack_mx.data_ptr(), dw1.data_ptr(), dw2.data_ptr(), bias.data_ptr(),
+                          out.data_ptr(), 1, h, w, c, max_workgroups, st))
+            return out
         fn = lib.avx_mst_attn_tail_sp if sparse else lib.avx_mst_attn_tail_mx
         ctx._check(fn(ctx._h, x.data_ptr(), wvpack16.data_ptr(), mpack_mx.data_ptr(), dw1.data_ptr(), dw2.data_ptr(), bias.data_ptr(),
-                      out.data_ptr(), 1, h, w, c, torch.cuda.current_stream(x.device).cuda_stream))
+                      out.data_ptr(), 1, h, w, c, st))
         return out
 
     def attn_tail(self, v: torch.Tensor, x: torch.Tensor, mpack16: torch.Tensor, taps1: torch.Tensor, taps2: torch.Tensor, bias: torch.Tensor,
@@ -857,8 +866,9 @@ class MSTPlusPlus(torch.nn.Module):
                     pk, tag = (pack_dw_smfmac, ".dwsp") if sp else (pack_dw_mfma, ".dwmx")
                     d1 = self._prep(k1 + f"{tag}/{gs}", lambda: pk((self._w(k1, (0,)).float() / gs).to(x.dtype)))
                     d2 = self._prep(k2 + f"{tag}*{gs}", lambda: pk((self._w(k2, (0,)).float() * gs).to(x.dtype)))
+                    march = _AVX._tail_march and c in _AVX.TAIL_MARCH_C
                     for i in range(b):
-                        _AVX.attn_tail_mx(xc[i], wv16, _AVX.attn_pack_mx(gram[i], nq[i], nk[i], resc, wpt), d1, d2, bias32, out[i], sparse=sp)
+                        _AVX.attn_tail_mx(xc[i], wv16, _AVX.attn_pack_mx(gram[i], nq[i], nk[i], resc, wpt), d1, d2, bias32, out[i], sparse=sp, march=march)
                     return out
                 if tailx:
                     wv16 = self._prep(p + ".wv.frag16", lambda: pack_fragments16(wqkv[:, 2 * c :].contiguous()))

@@ -876,6 +876,20 @@ int avx_mst_ffn_fused_sp_col(avx_ctx* ctx, const void* x, const float* gamma, co
  * neighbouring runs).  seg[wg * steps_cap + k] (may be NULL) receives 1 where the tile starts a segment -- a run's first tile, the top of a column -- else 0. */
 int avx_mst_tile_order_col(int frames, int ty, int tx, int nwg, long long* visit, unsigned char* seg, int steps_cap, int* steps_out);
 
+/* avx_mst_attn_tail_mx / _sp as a march down tile columns (round 11; C = 32 or 64, C = 128 is refused; same arguments, same results to the bit).  Tiles are
+ * 28 x 8 (C = 32: two 14-pixel column blocks) or 14 x 14 (C = 64); a workgroup walks a run of the column-major tile order downwards and keeps on chip what the
+ * tile below needs of this one: its last two rows of v and of x and its last row pair of mid = gelu(dw1(v)).  A step forms v on TR x (14 TB + 4) new pixels --
+ * exactly 8 groups of 32, one per wave -- and no mid row pair twice.  max_workgroups > 0 caps the grid below the launcher's own cap (0: that cap). */
+int avx_mst_attn_tail_mx_col(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack,
+                             const float* bias, void* out, int B, int H, int W, int C, int max_workgroups, void* stream);
+int avx_mst_attn_tail_sp_col(avx_ctx* ctx, const void* x, const void* wvpack16, const void* mpack_mx, const void* dw1pack, const void* dw2pack,
+                             const float* bias, void* out, int B, int H, int W, int C, int max_workgroups, void* stream);
+/* The steps of that march, run on the host with the kernel's own walk (csrc/mst_tile_order.h, ColumnSteps): the tiles of avx_mst_tile_order_col, with a PRIMING
+ * step in front of every tile that starts a segment -- the kernel's ordinary step on the tile above it (above the frame at the top of a column) without stores,
+ * which leaves on chip what the segment's first tile carries in.  visit[wg * steps_cap + k]: the raster index of the tile the step belongs to, -1 past the last
+ * step; prime[...] (may be NULL): 1 for a priming step (the step after it has the same visit[] entry), else 0; *steps_out: the most steps of any workgroup. */
+int avx_mst_tail_march_steps(int frames, int ty, int tx, int nwg, long long* visit, unsigned char* prime, int steps_cap, int* steps_out);
+
 /* out = [add +] a @ W [+ a2 @ W2] for (rows x C) float16 tensors and C x C weights in fragment order (out may alias
  * add; a2 / W2 and add may be NULL): MS_MSA's `proj(attn @ v)` collapsed to one matrix per frame (:132-135)
  * accumulated onto pos_emb(v) + x, and the decoder's 1x1 fusion conv over [up | skip] (:257) without the concatenation. */

@@ -66,6 +66,20 @@ class NightDesc(ctypes.Structure):
     ]
 
 
+class LumaModeRec(ctypes.Structure):
+    """avx_luma_mode_rec (include/avx.h): one frame's record of avx_luma_mode_u8."""
+
+    _fields_ = [
+        ("below", ctypes.c_uint32),
+        ("max_below", ctypes.c_float),
+        ("min_at_or_above", ctypes.c_float),
+        ("pad_", ctypes.c_uint32),
+    ]
+
+
+LUMA_MODE_REC_DTYPE = [("below", "<u4"), ("max_below", "<f4"), ("min_at_or_above", "<f4"), ("pad_", "<u4")]  # the same record for NumPy
+
+
 class DichromatLaunchInfo(ctypes.Structure):
     """avx_dichromat_launch_info (include/avx.h): kernel family and launch geometry of the last avx_dichromat_u8 call."""
 
@@ -327,6 +341,9 @@ _SIGS = {
     "avx_dichromat_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(DichromatDesc), _vp]),
     "avx_dichromat_last_launch": (_i, [_vp, ctypes.POINTER(DichromatLaunchInfo)]),
     "avx_dichromat_night_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(DichromatDesc), ctypes.POINTER(NightDesc), _vp]),
+    "avx_luma_mode_u8": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp]),
+    "avx_luma_mode_finish": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_double, _vp]),
+    "avx_dichromat_auto_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(DichromatDesc), ctypes.POINTER(NightDesc), ctypes.c_double, _vp, _vp]),
     "avx_get_table": (_i, [_i, _vp, _sz]),
     "avx_percentile": (_i, [_vp, _vp, _sz, ctypes.c_double, ctypes.POINTER(ctypes.c_double), _vp]),
     "avx_spectral_integrate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),

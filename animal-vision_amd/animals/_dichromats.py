@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from .. import _lib
-from ..dichromat import DichromatOp, DichromatSpec, NightSpec
+from ..dichromat import AutoNight, DichromatOp, DichromatSpec, NightSpec
 from .animal import Animal
 from .animal_utils import check_input_image
 
@@ -20,14 +20,15 @@ class _Dichromat(Animal):
 
     def __init__(self, *, night=None):
         """night: None (by day, the reference's active code), True (NightSpec's defaults: the values of the commented night
-        branch of animals/cat.py:50-60) or a NightSpec: rod vision in front of the colour stage, optional tapetum bloom."""
+        branch of animals/cat.py:50-60) or a NightSpec: rod vision in front of the colour stage, optional tapetum bloom; or an
+        AutoNight: every frame by day or as its NightSpec says, decided by the frame's median luma."""
         self._op = None
         if night is True:
             night = NightSpec()
         elif night is False:
             night = None
-        if night is not None and not isinstance(night, NightSpec):
-            raise TypeError(f"night must be None, True or a NightSpec (got {type(night).__name__})")
+        if night is not None and not isinstance(night, (NightSpec, AutoNight)):
+            raise TypeError(f"night must be None, True, a NightSpec or an AutoNight (got {type(night).__name__})")
         self.night = night
 
     def _operator(self) -> DichromatOp:
@@ -37,7 +38,8 @@ class _Dichromat(Animal):
 
     def _refuse_float_night(self, image: np.ndarray) -> None:
         if self.night is not None and image.dtype != np.uint8:
-            raise NotImplementedError(f"{type(self).__name__}: night is implemented for uint8 frames, got {image.dtype}")
+            what = "night=AutoNight" if isinstance(self.night, AutoNight) else "night"
+            raise NotImplementedError(f"{type(self).__name__}: {what} is implemented for uint8 frames, got {image.dtype}")
 
     def visualize(self, image: np.ndarray) -> Optional[Tuple[np.ndarray, np.ndarray]]:
         assert check_input_image(image)  # dog.py:33
@@ -228,7 +230,11 @@ class CatStreamOp:
     plain allocations of the op, which outlive the slot streams.
     At night (Cat(night=...)) the wide view is the chain the fused kernel is defined by, with the night entry at its
     end: avx_binocular_warp_u8 per frame into the slot's float32 frames, then avx_dichromat_night_u8 with in_f32 = 1 on the batch;
-    with ENABLE_FOV_WARP false the night entry on the uint8 frames.  The baseline launch is the same."""
+    with ENABLE_FOV_WARP false the night entry on the uint8 frames.  The baseline launch is the same.
+    With Cat(night=AutoNight(...)) the decision is taken on the slot's input frames -- the scene, not the warp:
+    avx_luma_mode_u8, the records into pinned memory, one synchronisation of the slot's stream -- and the batch is walked in runs
+    of equal mode: a day run is one avx_cat_wide_u8 launch, a night run the chain above; with ENABLE_FOV_WARP false the
+    switched entry avx_dichromat_auto_u8 does the same inside the library.  `last_modes` and `auto_counts` as DichromatOp's."""
 
     def __init__(self, cat: Cat, H: int, W: int, depth: int = 3, batch: int = 1, ctx=None):
         from .. import geometry as G
@@ -247,13 +253,19 @@ class CatStreamOp:
         self._by_in = {d_in.ptr: k for k, (d_in, _) in enumerate(self._bufs)}
         self._tables, self._table_ptrs = None, None
         self.night = cat.night
+        self.auto = cat.night if isinstance(cat.night, AutoNight) else None
+        self.last_modes, self.auto_counts = np.zeros(0, np.uint8), [0, 0]
         self._warped, self._host_tables, self._op_f32 = [], None, None
+        self._rec, self._rec_host = None, None
+        if self.warp and self.auto is not None:
+            self._rec = self.ctx.malloc(16 * 16)
+            self._rec_host = self.ctx.pinned((16,), _lib.LUMA_MODE_REC_DTYPE)
         if self.warp and self.night is not None:
             self._host_tables = G.binocular_warp_tables(self.H, self.W, self.W, self.H, cat.CAMERA_HFOV_DEG, cat.CAT_PER_EYE_HALF_FOV_DEG, cat.CAT_OVERLAP_DEG)
             self._warped = [self.ctx.malloc(nbytes * 4) for _ in range(depth)]  # float32 HWC frames in [0, 1]
-            self._op_f32 = DichromatOp(cat.SPEC, self.ctx, night=self.night)
+            self._op_f32 = DichromatOp(cat.SPEC, self.ctx, night=self.auto.night if self.auto is not None else self.night)
             self._op_f32.desc.in_f32 = 1
-        elif self.warp:
+        if self.warp and (self.night is None or self.auto is not None):
             tables = G.binocular_warp_tables(self.H, self.W, self.W, self.H, cat.CAMERA_HFOV_DEG, cat.CAT_PER_EYE_HALF_FOV_DEG, cat.CAT_OVERLAP_DEG)
             self._tables, self._table_ptrs = G.binocular_warp_tables_device(self.ctx, tables)
 
@@ -280,23 +292,50 @@ class CatStreamOp:
         assert 1 <= n_frames <= self.batch and (H, W) == (self.H, self.W)
         if self.rect is not None:
             G.center_zoom_device(self.ctx, d_in, self._base[self._by_in[d_in.ptr]], n_frames, H, W, self.rect, stream)
-        if self.warp and self.night is not None:
-            d_f32 = self._warped[self._by_in[d_in.ptr]]
-            xL, xR, ymap, wL, wR = self._host_tables
-            for f in range(n_frames):
-                self.ctx._check(_lib.lib.avx_binocular_warp_u8(self.ctx._h, d_in.ptr + f * H * W * 3, H, W, xL.ctypes.data, xR.ctypes.data, ymap.ctypes.data,
-                                                               wL.ctypes.data, wR.ctypes.data, H, W, d_f32.ptr + f * H * W * 12, self.ctx._s(stream)))
-            self._op_f32.run_device(d_f32, d_out, n_frames, H, W, stream=stream)
+        if self.warp and self.auto is not None:
+            from ..dichromat import finish_modes, luma_records_device
+
+            rec = luma_records_device(self.ctx, d_in.ptr, n_frames, H, W, self.auto.threshold, self._rec, out=self._rec_host.array, stream=stream)
+            modes = finish_modes(rec["below"], rec["max_below"], rec["min_at_or_above"], H * W, self.auto.threshold).astype(np.uint8)
+            fb, f0 = H * W * 3, 0
+            while f0 < n_frames:
+                f1 = f0 + 1
+                while f1 < n_frames and modes[f1] == modes[f0]:
+                    f1 += 1
+                run_in, run_out = d_in.view(f0 * fb, (f1 - f0) * fb), d_out.view(f0 * fb, (f1 - f0) * fb)
+                if modes[f0]:
+                    self._wide_night(run_in, run_out, self._warped[self._by_in[d_in.ptr]], f1 - f0, H, W, stream)
+                else:
+                    G.cat_wide_device(self.ctx, run_in, run_out, f1 - f0, H, W, self._op.desc, self._table_ptrs, stream)
+                f0 = f1
+            self._note_modes(modes)
+        elif self.warp and self.night is not None:
+            self._wide_night(d_in, d_out, self._warped[self._by_in[d_in.ptr]], n_frames, H, W, stream)
         elif self.warp:
             G.cat_wide_device(self.ctx, d_in, d_out, n_frames, H, W, self._op.desc, self._table_ptrs, stream)
         else:
             self._op.run_device(d_in, d_out, n_frames, H, W, stream=stream)
+            if self.auto is not None:
+                self._note_modes(self._op.last_modes)
+
+    def _note_modes(self, modes: np.ndarray) -> None:
+        self.last_modes = np.array(modes, np.uint8)
+        self.auto_counts[0] += int(self.last_modes.sum())
+        self.auto_counts[1] += self.last_modes.size
+
+    def _wide_night(self, d_in, d_out, d_f32, n_frames: int, H: int, W: int, stream) -> None:
+        """The night chain on n_frames frames: the binocular warp per frame into d_f32's first frames, then the night entry."""
+        xL, xR, ymap, wL, wR = self._host_tables
+        for f in range(n_frames):
+            self.ctx._check(_lib.lib.avx_binocular_warp_u8(self.ctx._h, d_in.ptr + f * H * W * 3, H, W, xL.ctypes.data, xR.ctypes.data, ymap.ctypes.data,
+                                                           wL.ctypes.data, wR.ctypes.data, H, W, d_f32.ptr + f * H * W * 12, self.ctx._s(stream)))
+        self._op_f32.run_device(d_f32, d_out, n_frames, H, W, stream=stream)
 
     def close(self):
         for pair in self._bufs:
             for b in pair:
                 b.free()
-        for b in self._base + [self._tables] + self._warped:
+        for b in self._base + [self._tables, self._rec, self._rec_host] + self._warped:
             if b is not None:
                 b.free()
-        self._bufs, self._base, self._tables, self._warped = [], [], None, []
+        self._bufs, self._base, self._tables, self._warped, self._rec, self._rec_host = [], [], None, [], None, None

@@ -42,6 +42,8 @@ static void avx_ws_release(avx_ws* w) {
     if (w->d_scan) (void)hipFree(w->d_scan);
     if (w->d_periph) (void)hipFree(w->d_periph);
     if (w->bee_small) (void)hipFree(w->bee_small);
+    if (w->d_luma_rec) (void)hipFree(w->d_luma_rec);
+    if (w->h_luma_rec) (void)hipHostFree(w->h_luma_rec);
     for (int i = 0; i < w->n_geom_tabs; ++i)
         if (((w->geom_tabs[i].key >> 54) & 0xf) < 8) (void)hipFree(w->geom_tabs[i].dev);  // component >= 8: a scalar, not a pointer
     *w = avx_ws();
@@ -366,10 +368,12 @@ int avx_timer_stop(avx_ctx* ctx, void* stream, float* out_ms) {
 int avx_get_table(int which, void* dst_host, size_t capacity) {
     const void* src = nullptr;
     size_t size = 0;
+    float luma[768];
     switch (which) {
         case 0: src = kDecodeLutBits; size = sizeof(kDecodeLutBits); break;
         case 1: src = kEncThrF32Bits; size = sizeof(kEncThrF32Bits); break;
         case 2: src = kEncThrF64Bits; size = sizeof(kEncThrF64Bits); break;
+        case 3: avx_luma_tables_host(luma); src = luma; size = sizeof(luma); break;
         default: return AVX_ERR_INVALID;
     }
     if (dst_host) memcpy(dst_host, src, capacity < size ? capacity : size);

@@ -21,9 +21,9 @@ struct avx_ws {
     // Small constant tables of a caller's pipeline (matrices, weights, coordinate rows): device copy + host mirror per slot,
     // uploaded only when the bytes change (avx_const_upload).  Slots: 0 UV matrix / weights, 1 band-major spectral weights (k_spectral_nhwc_h), 2-7 mantis tables,
     // 8-9 label stroke segments (labels.hip), 10 montage descriptors + segments + resize tables (gallery.hip),
-    // 11 the S-CIELAB filter taps (scielab.hip).
+    // 11 the S-CIELAB filter taps (scielab.hip), 12 the three luma tables (daynight.hip).
     struct const_slot { void* dev = nullptr; void* host = nullptr; size_t bytes = 0, cap = 0; };
-    static constexpr int kConstSlots = 12;
+    static constexpr int kConstSlots = 13;
     const_slot consts[kConstSlots];
     void* uv_small = nullptr;        // UV path: partial statistics, histogram, select state, percentiles
     void* d_scratch = nullptr;       // scratch arena (UV path planes)
@@ -42,6 +42,8 @@ struct avx_ws {
     uint64_t periph_key = 0;
     void* d_ew = nullptr;            // per-block partial reductions of elementwise programs (ew.hip)
     size_t ew_cap = 0;
+    void* d_luma_rec = nullptr;      // daynight.hip: the 16 records of avx_dichromat_auto_u8 and their pinned host copy
+    void* h_luma_rec = nullptr;
 };
 
 struct avx_ctx {
@@ -94,6 +96,7 @@ int avx_ensure_scratch(avx_ctx* ctx, avx_ws* ws, size_t bytes);
 // Per-row table (row gains / streak taps) -> ws->d_row_gain: grows the buffer, uploads only when the bytes differ from the last upload.
 int avx_upload_row_table(avx_ctx* ctx, avx_ws* ws, const void* host, size_t bytes, hipStream_t s);
 int avx_const_upload(avx_ctx* ctx, avx_ws* ws, int slot, const void* host, size_t bytes, hipStream_t s, void** dev_out);
+void avx_luma_tables_host(float* dst768);  // daynight.hip: the tables avx_get_table(3) hands out
 int avx_lanes(avx_ctx* ctx, int want);  // creates the frame-lane streams on first use; returns how many exist (<= want), 0 on failure
 // mst_mfma.hip: reduce the per-workgroup Gram partials ([blocks][heads][34][32]) of a Gram pass into gram / nq / nk (k_mst_qkv_final)
 int avx_mst_qkv_final_launch(avx_ctx* ctx, const float* partial, int blocks, int heads, float* gram, float* nq, float* nk, hipStream_t s);

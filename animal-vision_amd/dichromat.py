@@ -160,16 +160,104 @@ def night_desc(night: NightSpec):
     return nd, (rod, bloom)
 
 
+NIGHT_THRESHOLD = 0.12  # RatUV._choose_mode (animals/rat_uv.py:99-104): night when the median Rec.709 luma is below it
+
+
+@dataclass(frozen=True)
+class AutoNight:
+    """Day or night, decided per frame: a frame whose median Rec.709 luma is below `threshold` is shown as `night`
+    describes, every other frame by day.  Accepted wherever `night=` takes a NightSpec."""
+
+    night: NightSpec = NightSpec()
+    threshold: float = NIGHT_THRESHOLD
+
+    def __post_init__(self):
+        if not isinstance(self.night, NightSpec):
+            raise TypeError(f"AutoNight.night must be a NightSpec (got {type(self.night).__name__})")
+        check_threshold(self.threshold, "AutoNight.threshold")
+
+
+def check_threshold(v, what: str = "threshold") -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+        raise ValueError(f"{what} must be a finite number (got {v!r})")
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"{what} must be in [0, 1] (got {v})")
+    return float(v)
+
+
+LUMA_WEIGHTS = (0.2126, 0.7152, 0.0722)
+
+
+def luma_tables() -> np.ndarray:
+    """float32 [3][256]: t_c[v] = w_c * (v / 255) as NumPy forms it on a uint8 frame (oracle NumpyProbes.median_luma), so that
+    Y = (t_0[R] + t_1[G]) + t_2[B].  The library computes the same bits (avx_get_table(3))."""
+    x = np.arange(256, dtype=np.uint8).astype(np.float32) / 255.0
+    return np.stack([w * x for w in LUMA_WEIGHTS]).astype(np.float32, copy=False)
+
+
+def finish_modes(below, max_below, min_at_or_above, n: int, threshold: float) -> np.ndarray:
+    """bool[N]: whether float(np.median(Y)) < threshold, from the records of avx_luma_mode_u8 over frames of n pixels.  The count
+    decides unless it is exactly n / 2; then the two middle values are max_below and min_at_or_above, and np.median is their
+    float32 mean."""
+    below = np.atleast_1d(np.asarray(below)).astype(np.int64)
+    a = np.atleast_1d(np.asarray(max_below, np.float32))
+    b = np.atleast_1d(np.asarray(min_at_or_above, np.float32))
+    out = 2 * below > n
+    for f in np.nonzero(2 * below == n)[0]:
+        out[f] = float(np.float32(a[f] + b[f]) / np.float32(2)) < threshold
+    return out
+
+
+def luma_records_device(ctx: Context, ptr: int, n_frames: int, H: int, W: int, threshold: float, d_rec: DeviceBuffer, out: Optional[np.ndarray] = None,
+                        stream=None) -> np.ndarray:
+    """avx_luma_mode_u8 on n_frames (1..16) uint8 frames at device address `ptr`, the records through d_rec (at least 16 bytes per
+    frame) into `out` (a structured array of _lib.LUMA_MODE_REC_DTYPE; pinned memory makes the copy asynchronous until the
+    synchronisation of `stream` that ends this call)."""
+    ctx._check(lib.avx_luma_mode_u8(ctx._h, ptr, n_frames, H, W, float(threshold), d_rec.ptr, ctx._s(stream)))
+    if out is None:
+        out = np.empty(n_frames, _lib.LUMA_MODE_REC_DTYPE)
+    return ctx.download(d_rec, (n_frames,), out.dtype, out=out, stream=stream)[:n_frames]
+
+
+def luma_modes(frames: np.ndarray, threshold: float = NIGHT_THRESHOLD, ctx: Optional[Context] = None):
+    """(night bool[N], below uint32[N], max_below float32[N], min_at_or_above float32[N]) of uint8 host frames N x H x W x 3 or
+    H x W x 3: the day/night decision of AutoNight and the record it rests on (avx_luma_mode_u8; max_below is 0 where below is 0,
+    min_at_or_above +inf where every pixel is below)."""
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8:
+        raise NotImplementedError(f"luma_modes takes uint8 frames (got {frames.dtype})")
+    batch = frames[None] if frames.ndim == 3 else frames
+    if batch.ndim != 4 or batch.shape[3] != 3 or batch.shape[0] < 1:
+        raise ValueError(f"luma_modes takes N x H x W x 3 or H x W x 3 frames (got shape {frames.shape})")
+    threshold = check_threshold(threshold)
+    ctx = ctx or get_context()
+    N, H, W, _ = batch.shape
+    d_in, d_rec = ctx.upload(batch), ctx.malloc(16 * 16)
+    try:
+        recs = [luma_records_device(ctx, d_in.ptr + f0 * H * W * 3, min(16, N - f0), H, W, threshold, d_rec).copy() for f0 in range(0, N, 16)]
+    finally:
+        d_in.free()
+        d_rec.free()
+    rec = np.concatenate(recs)
+    return finish_modes(rec["below"], rec["max_below"], rec["min_at_or_above"], H * W, threshold), rec["below"], rec["max_below"], rec["min_at_or_above"]
+
+
 class DichromatOp:
     """Configured fused kernel launch for one species; reusable across frames (stateless between them).  With `night` (a NightSpec)
-    run_device and __call__ go to avx_dichromat_night_u8 (csrc/night.hip) instead of the day kernel."""
+    run_device and __call__ go to avx_dichromat_night_u8 (csrc/night.hip) instead of the day kernel; with an AutoNight to
+    avx_dichromat_auto_u8 (csrc/daynight.hip), which decides per frame: `last_modes` then holds the last call's decisions
+    (uint8, 1 = night) and `auto_counts` [night frames, frames] over the op's life."""
 
-    def __init__(self, spec: DichromatSpec, ctx: Optional[Context] = None, night: Optional[NightSpec] = None):
+    def __init__(self, spec: DichromatSpec, ctx: Optional[Context] = None, night=None):
         self.spec = spec
         self.ctx = ctx
-        if night is not None and not isinstance(night, NightSpec):
-            raise TypeError(f"night must be a NightSpec or None (got {type(night).__name__})")
+        if night is not None and not isinstance(night, (NightSpec, AutoNight)):
+            raise TypeError(f"night must be a NightSpec, an AutoNight or None (got {type(night).__name__})")
         self.night = night
+        self.auto = night if isinstance(night, AutoNight) else None
+        night = night.night if self.auto is not None else night
+        self.last_modes = np.zeros(0, np.uint8)
+        self.auto_counts = [0, 0]
         self.night_desc, self._night_taps = night_desc(night) if night is not None else (None, None)
         d = DichromatDesc()
         d.struct_size = ctypes.sizeof(DichromatDesc)
@@ -233,6 +321,14 @@ class DichromatOp:
             if self._streak is None or self._streak.shape[0] != H:
                 self._streak = streak_row_tables(H, *self.spec.streak)
             self.desc.streak_rows_host = self._streak.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        if self.auto is not None:
+            modes = np.zeros(16, np.uint8)
+            ctx._check(lib.avx_dichromat_auto_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, ctypes.byref(self.desc), ctypes.byref(self.night_desc),
+                                                 float(self.auto.threshold), modes.ctypes.data, ctx._s(stream)))
+            self.last_modes = modes[:n_frames].copy()
+            self.auto_counts[0] += int(self.last_modes.sum())
+            self.auto_counts[1] += n_frames
+            return
         if self.night is not None:  # (a frame below 13 x 13 is refused by the library, by name)
             ctx._check(lib.avx_dichromat_night_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, ctypes.byref(self.desc),
                                                   ctypes.byref(self.night_desc), ctx._s(stream)))
@@ -261,7 +357,15 @@ class DichromatOp:
         d_in = ctx.upload(batch)
         d_out = ctx.malloc(batch.nbytes)
         try:
-            self.run_device(d_in, d_out, n, H, W)
+            if self.auto is not None and n > self.max_batch:  # the switched entry takes at most max_batch frames
+                modes, fb = [], H * W * 3
+                for f0 in range(0, n, self.max_batch):
+                    m = min(self.max_batch, n - f0)
+                    self.run_device(d_in.view(f0 * fb, m * fb), d_out.view(f0 * fb, m * fb), m, H, W)
+                    modes.append(self.last_modes)
+                self.last_modes = np.concatenate(modes)
+            else:
+                self.run_device(d_in, d_out, n, H, W)
             out = ctx.download(d_out, batch.shape, np.uint8)
         finally:
             d_in.free()

@@ -180,7 +180,8 @@ def get_context(device: Optional[int] = None) -> Context:
 
 
 def get_table(which: int) -> np.ndarray:
-    """The constant tables compiled into the library (0: decode LUT, 1: f32 thresholds, 2: f64 thresholds)."""
+    """The constant tables compiled into the library (0: decode LUT, 1: f32 thresholds, 2: f64 thresholds, 3: the 3 x 256 luma
+    tables of avx_luma_mode_u8)."""
     size = lib.avx_get_table(which, None, 0)
     dt = np.float64 if which == 2 else np.float32
     out = np.empty(size // np.dtype(dt).itemsize, dt)

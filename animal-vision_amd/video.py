@@ -49,7 +49,12 @@ launches take the N frames of a slot each).  The species of the per-frame loop h
 `--night` shows one of the 20 dichromats by night: the reference's rod vision in front of the species' colour stage, and
 with `--bloom S` (0 < S <= 1) its tapetum bloom behind the post stage.  The species streams as by day:
 
-    python -m animal_vision_amd.video in.y4m out.y4m --species Cat --night --bloom 0.12 --split-compare"""
+    python -m animal_vision_amd.video in.y4m out.y4m --species Cat --night --bloom 0.12 --split-compare
+
+`--night-auto` decides day or night for every frame: a frame whose median Rec.709 luma is below `--night-threshold T`
+(default 0.12, the rule of the reference's RatUV) gets the night view, with `--bloom S` the bloom as well; every other frame the day
+view.  The rule has no memory, so a frame's output does not depend on --batch, --depth or the shard -- and a clip that hovers at
+the threshold flickers between the two views.  A line on stderr reports how many frames were night."""
 from __future__ import annotations
 
 import argparse
@@ -77,10 +82,13 @@ def make_animal(args):
         from .ml import MSTPlusPlusPredictor
 
         kw["hsi_model"] = MSTPlusPlusPredictor(None if args.hsi_model == "seeded" else args.hsi_model, seed=0, half=True)
-    if getattr(args, "night", False):
-        from .dichromat import NightSpec
+    if getattr(args, "night", False) or getattr(args, "night_auto", False):
+        from .dichromat import NIGHT_THRESHOLD, AutoNight, NightSpec
 
         kw["night"] = NightSpec(bloom=args.bloom if getattr(args, "bloom", None) is not None else 0.0)
+        if getattr(args, "night_auto", False):
+            thr = getattr(args, "night_threshold", None)
+            kw["night"] = AutoNight(kw["night"], NIGHT_THRESHOLD if thr is None else thr)
     return cls(**kw)
 
 
@@ -172,6 +180,16 @@ def _bloom_arg(text: str) -> float:
     return v
 
 
+def _night_threshold_arg(text: str) -> float:
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--night-threshold takes a number (got {text!r})")
+    if not 0.0 <= v <= 1.0:  # (also refuses nan)
+        raise argparse.ArgumentTypeError(f"--night-threshold must be at least 0 and at most 1 (got {text!r})")
+    return v
+
+
 def is_dichromat(species: str) -> bool:
     """Whether the display name is one of the 20 dichromats, the species that have a night form."""
     from .animals._dichromats import _Dichromat
@@ -244,10 +262,17 @@ class _VideoParser(argparse.ArgumentParser):
             if v is not None and args.species != "HoneyBee":
                 self.error(f"{flag} configures HoneyBee's RGB-to-spectrum conversion: --species {args.species} has none")
         night, bloom = getattr(args, "night", False), getattr(args, "bloom", None)  # (add_night_options: parse_args adds them)
-        if bloom is not None and not night:
+        auto, threshold = getattr(args, "night_auto", False), getattr(args, "night_threshold", None)
+        if night and auto:
+            self.error("--night and --night-auto exclude each other: --night is night for every frame, --night-auto decides per frame")
+        if threshold is not None and not auto:
+            self.error("--night-threshold needs --night-auto: it is the median luma below which --night-auto calls a frame night")
+        if bloom is not None and not (night or auto):
             self.error("--bloom needs --night: the tapetum bloom is part of the night view")
         if night and not is_dichromat(args.species):
             self.error(f"--night: --species {args.species} is not one of the 20 dichromats, the species that have a night view")
+        if auto and not is_dichromat(args.species):
+            self.error(f"--night-auto: --species {args.species} is not one of the 20 dichromats, the species that have a night view")
         if args.hsi_model not in (None, "seeded") and not os.path.isfile(args.hsi_model):
             self.error(f"--hsi-model {args.hsi_model}: no such file (a local .pth checkpoint, or 'seeded')")
         check_io_options(self, args)
@@ -317,9 +342,19 @@ def add_night_options(ap: argparse.ArgumentParser) -> None:
                     help="with --night, 0 < S <= 1: tapetum bloom of this strength (a luminance-gated screen blend with a sigma 3 blur)")
 
 
+def add_night_auto_options(ap: argparse.ArgumentParser) -> None:
+    """--night-auto and --night-threshold, added by parse_args like add_night_options."""
+    ap.add_argument("--night-auto", action="store_true",
+                    help="the dichromats only: decide per frame -- the night view (with --bloom S its bloom) where the frame's median Rec.709 luma "
+                         "is below the threshold, the day view elsewhere")
+    ap.add_argument("--night-threshold", default=None, type=_night_threshold_arg, metavar="T",
+                    help="with --night-auto, 0 <= T <= 1: the median luma below which a frame is night (default 0.12)")
+
+
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap = build_parser()
     add_night_options(ap)
+    add_night_auto_options(ap)
     args = ap.parse_args(argv)
     check_raw_options(ap, args)
     return args
@@ -349,6 +384,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         vr.close()
         raise SystemExit(f"video: --batch {args.batch}: {args.species} runs visualize() per frame and has no batched form")
     labels = None if args.no_labels else ("Original", "Transformed")
+    auto_counts = [0, 0]  # --night-auto: night frames, frames (the stream op counts them)
     t0 = time.perf_counter()
     try:
         hw = None if vr.y4m_header is None else (vr.y4m_header.height, vr.y4m_header.width)
@@ -375,6 +411,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 stats = run_video(op, vr, depth=args.depth, split_compare=args.split_compare, labels=labels,
                                   split_baseline=hasattr(op, "slot_baseline"), batch=args.batch)
             finally:
+                auto_counts = list(getattr(op, "auto_counts", auto_counts))
                 if hasattr(op, "close"):
                     op.close()
             frames = stats.frames
@@ -400,6 +437,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         vr.close()
     dt = time.perf_counter() - t0
     print(f"video: {args.species}: {frames} frames in {dt:.2f} s ({frames / dt if dt > 0 else 0.0:.1f} fps)", file=sys.stderr)
+    if getattr(args, "night_auto", False):
+        k, n = auto_counts
+        print(f"night-auto: {k} of {n} frames night (threshold {animal.night.threshold:g})", file=sys.stderr)
     return 0
 
 

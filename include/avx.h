@@ -163,6 +163,42 @@ typedef struct avx_night_desc {
 int avx_dichromat_night_u8(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_hwc, int n_frames, int H, int W,
                            const avx_dichromat_desc* desc, const avx_night_desc* night, void* stream);
 
+/* Day or night, per frame (csrc/daynight.hip): the one day/night rule the reference implements, RatUV._choose_mode
+ * (animals/rat_uv.py:99-104) -- a frame is night when the median Rec.709 luma of its sRGB values is below a threshold (0.12 there).
+ * For a uint8 frame Y = (t0[R] + t1[G]) + t2[B] in float32 with t_c[v] = float32(w_c * float32(v / 255)), w = (0.2126, 0.7152,
+ * 0.0722): the values NumPy forms for `0.2126 * x[..., 0] + 0.7152 * x[..., 1] + 0.0722 * x[..., 2]` on x = u8.astype(float32) / 255.
+ * The three tables are avx_get_table(3): 768 floats.
+ * One pass gives the decision exactly.  With n = H * W and T = threshold the record of a frame holds
+ *   below            #{Y < T}, compared as double
+ *   max_below        the largest Y counted in `below`      (0 when below == 0)
+ *   min_at_or_above  the smallest Y not counted            (+inf when below == n)
+ * and the frame is night iff  2 * below > n,  or  2 * below == n and float32(max_below + min_at_or_above) / 2 < T: the median of an
+ * even count is the float32 mean of its two middle values, which are then exactly these two.  avx_luma_mode_finish is that rule on
+ * the host (no device call; ctx may be NULL).
+ * avx_luma_mode_u8: asynchronous on `stream`; one launch that initialises the n_frames records and one launch of grid (chunks,
+ * frames) that reduces per wave, then per workgroup, and applies three integer atomics per workgroup (add, unsigned max and min
+ * on the bit patterns: Y >= 0), so a frame's record is the same bytes in any batch and any grid.  1 <= n_frames <= 16, H, W >= 1,
+ * H * W < 2^31, 0 <= threshold <= 1; rec_dev is device memory, 16-byte aligned. */
+typedef struct avx_luma_mode_rec {
+    uint32_t below;
+    float max_below;
+    float min_at_or_above;
+    uint32_t pad_;
+} avx_luma_mode_rec;
+
+int avx_luma_mode_u8(avx_ctx* ctx, const uint8_t* in_hwc, int n_frames, int H, int W, double threshold, avx_luma_mode_rec* rec_dev,
+                     void* stream);
+int avx_luma_mode_finish(avx_ctx* ctx, const avx_luma_mode_rec* rec_host, int n_frames, int H, int W, double threshold, uint8_t* modes_host);
+
+/* The dichromats, switched per frame: avx_luma_mode_u8 on the n_frames uint8 frames, the 16-byte records into pinned memory of the
+ * stream's workspace, hipStreamSynchronize(stream) -- that stream only; a stated cost --, the decision on the host, then
+ * avx_dichromat_u8 on every maximal run of day frames and avx_dichromat_night_u8 on every maximal run of night frames, with the
+ * pointers at the run's first frame.  A frame's bytes are what that entry writes for the frame alone.  modes_host (may be NULL)
+ * receives 1 for night, 0 for day.  1 <= n_frames <= 16.  AVX_ERR_INVALID, by name: desc->in_f32 (the decision is defined on
+ * uint8 frames), H or W below 13 (as the night entry, also when every frame is day), and whatever the two entries refuse. */
+int avx_dichromat_auto_u8(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_hwc, int n_frames, int H, int W,
+                          const avx_dichromat_desc* desc, const avx_night_desc* night, double threshold, uint8_t* modes_host, void* stream);
+
 /* ---- UV / spectral path: uv_helpers.py, uv_mappers.py, ml/classic_rgb_to_hsi, animals/honeybee.py ----
  *
  * Planes are float32, K x (H*W), struct-of-arrays.  Float contract: within 1e-4 relative of the reference
@@ -936,7 +972,8 @@ int avx_layernorm_rows_grouped(avx_ctx* ctx, const void* x, const float* gamma, 
                                int group, int real, void* stream);
 
 /* The constant tables compiled into the library (reference outputs, see csrc/srgb_tables.h):
- * which = 0: 256 x f32 decode LUT; 1: 255 x f32 encode thresholds; 2: 255 x f64 encode thresholds.
+ * which = 0: 256 x f32 decode LUT; 1: 255 x f32 encode thresholds; 2: 255 x f64 encode thresholds; 3: 3 x 256 x f32 luma tables
+ * (avx_luma_mode_u8; computed, not stored).
  * Copies min(capacity, size) bytes to dst_host and returns the table's size in bytes. */
 int avx_get_table(int which, void* dst_host, size_t capacity);
 

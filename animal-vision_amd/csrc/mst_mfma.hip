@@ -835,6 +835,193 @@ __global__ __launch_bounds__(kT) void k_mst_convt2x2(const __half* __restrict__ 
     }
 }
 
+// ---- the upsampling on v_mfma_f32_32x32x16_f16 --------------------------------------------------------------------------------------------
+// k_mst_convt2x2's walk, scattered 32-byte stores, bias add and rounding with the tap and skip products on the K = 16 form: a lane's contiguous
+// half row as loaded (one uint4 = 8 channels) IS one K = 16 operand (step q, lane half h, element j <-> input channel h C/2 + 8 q + j), the weights
+// are ml/mst_plus_plus.py::pack_fragments16(..., halfrow=True) -- the same LDS bytes as the K = 8 fragments, read 16 at a time.  Inside a wave-tile
+// the x row and ALL FOUR taps' skip rows are requested in front of the first MFMA (16 more registers at C = 64, 64 at C = 128), so the products
+// of tap 0 run under the loads of taps 1-3 instead of each tap paying its own round trip.  NW waves share one weight image.
+// GRAM: the Gram pass of the MSAB block that follows, over the pixel's CO = C / 2 rounded output channels (HD = CO / 32 heads).  A lane holds
+// channels 32 t + 16 h + v of its output pixel: at CO = 32 that is k_mst_qkv16's operand as it stands; at CO = 64 the two half-waves trade 16
+// channels each (eight v_permlane32_swap per tap) and lane (p, h) ends with channels 32 h .. 32 h + 31 -- again that operand, so q and k are the
+// bits k_mst_qkv16 forms from the stored row and wqk is pack_qkv16's (tiles [0, 2 HD)).  Partials are laid out as k_mst_qkv16 writes them.
+template <int C, int NW, bool SKIP, bool GRAM>
+__global__ __launch_bounds__(64 * NW, C == 64 ? 4 : 1) void k_mst_convt2x2_16(const __half* __restrict__ x /*[B][H][W][C]*/, const uint4* __restrict__ wpack /*[4][C/64][C/16][64]*/,
+                                                            const float* __restrict__ bias /*[C/2]*/, const __half* __restrict__ skip /*[B][2H][2W][C/2]*/,
+                                                            const uint4* __restrict__ wskip /*[C/64][C/32][64]*/, __half* __restrict__ out /*[B][2H][2W][C/2]*/, int B,
+                                                            int H, int W, const uint4* __restrict__ wqk /*[2 HD][C/32][64]*/, float* __restrict__ partial /*[blocks][HD][34][32]*/) {
+    constexpr int KS = C / 16, CO = C / 2, NT = CO / 32, KSS = CO / 16, HD = NT;
+    static_assert(!GRAM || SKIP, "the Gram epilogue belongs to the fused decoder step");
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint4* wl = reinterpret_cast<uint4*>(smem);
+    float* bl = reinterpret_cast<float*>(wl + 4 * NT * KS * 64);
+    uint4* wsl = reinterpret_cast<uint4*>(bl + CO);
+    uint4* wq = wsl + (SKIP ? NT * KSS * 64 : 0);  // GRAM only
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < 4 * NT * KS * 64; i += 64 * NW) wl[i] = wpack[i];
+    for (int i = tid; i < CO; i += 64 * NW) bl[i] = bias[i];
+    if constexpr (SKIP)
+        for (int i = tid; i < NT * KSS * 64; i += 64 * NW) wsl[i] = wskip[i];
+    float16_t G[GRAM ? HD : 1];
+    float nq[GRAM ? HD : 1], nk[GRAM ? HD : 1];
+    if constexpr (GRAM) {
+        for (int i = tid; i < 2 * HD * KSS * 64; i += 64 * NW) wq[i] = wqk[i];
+#pragma unroll
+        for (int hd = 0; hd < HD; ++hd) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) G[hd][v] = 0.f;
+            nq[hd] = 0.f;
+            nk[hd] = 0.f;
+        }
+    }
+    __syncthreads();
+    const int xt = (W + 31) / 32;
+    const long total = (long)B * H * xt;
+    const int p = lane & 31, h = lane >> 5;
+    for (long tile = (long)blockIdx.x * NW + wave; tile < total; tile += (long)gridDim.x * NW) {
+        const int x0 = (int)(tile % xt) * 32, y = (int)((tile / xt) % H);
+        const long b = tile / ((long)xt * H);
+        const int xw = x0 + p, xc = xw < W ? xw : W - 1;
+        uint4 xr[KS], sr[SKIP ? 4 : 1][KSS];
+        {
+            const uint4* src = reinterpret_cast<const uint4*>(x + (size_t)((b * H + y) * (long)W + xc) * C + h * (C / 2));
+#pragma unroll
+            for (int q = 0; q < KS; ++q) xr[q] = src[q];
+        }
+        const size_t opix0 = (size_t)(b * 2 * H + 2 * y) * (size_t)(2 * W) + (size_t)(2 * xc);  // tap (dy, dx): + dy 2W + dx
+        if constexpr (SKIP) {  // lane (p, h): channels [h CO/2, (h + 1) CO/2) of the OUTPUT pixel's skip row, all four taps in flight with x
+#pragma unroll
+            for (int tap = 0; tap < 4; ++tap) {
+                const uint4* src = reinterpret_cast<const uint4*>(skip + (opix0 + (size_t)(tap >> 1) * (size_t)(2 * W) + (tap & 1)) * CO + h * (CO / 2));
+#pragma unroll
+                for (int q = 0; q < KSS; ++q) sr[tap][q] = src[q];
+            }
+        }
+        asm volatile("" ::: "memory");  // weight fragments stay in LDS, the loads stay in front of the products
+#pragma unroll
+        for (int tap = 0; tap < 4; ++tap) {
+            const size_t opix = opix0 + (size_t)(tap >> 1) * (size_t)(2 * W) + (tap & 1);
+            uint4 og[NT][2];  // the rounded output row: channels 32 t + 16 h + 8 b + j
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                float16_t d;
+#pragma unroll
+                for (int v = 0; v < 16; ++v) d[v] = 0.f;
+#pragma unroll
+                for (int s = 0; s < KS; ++s) d = mfma16(__builtin_bit_cast(half8_t, wl[((tap * NT + t) * KS + s) * 64 + lane]), __builtin_bit_cast(half8_t, xr[s]), d);
+                if constexpr (SKIP) {
+#pragma unroll
+                    for (int s = 0; s < KSS; ++s) d = mfma16(__builtin_bit_cast(half8_t, wsl[(t * KSS + s) * 64 + lane]), __builtin_bit_cast(half8_t, sr[tap][s]), d);
+                }
+                _Float16 o[16];
+#pragma unroll
+                for (int v = 0; v < 16; ++v) o[v] = (_Float16)(d[v] + bl[32 * t + 16 * h + v]);
+                if (xw < W) store_tile16(out + opix * CO + 32 * t + 16 * h, o);
+                if constexpr (GRAM) {
+                    half8_t o0, o1;
+#pragma unroll
+                    for (int v = 0; v < 8; ++v) { o0[v] = xw < W ? o[v] : (_Float16)0.f; o1[v] = xw < W ? o[8 + v] : (_Float16)0.f; }  // columns past the edge take no part
+                    og[t][0] = __builtin_bit_cast(uint4, o0);
+                    og[t][1] = __builtin_bit_cast(uint4, o1);
+                }
+            }
+            if constexpr (GRAM) {
+                half8_t xq[KSS];  // k_mst_qkv16's operand: step s of lane (p, h) carries channels h CO/2 + 8 s + j of the pixel
+                if constexpr (NT == 1) {
+                    xq[0] = __builtin_bit_cast(half8_t, og[0][0]);
+                    xq[1] = __builtin_bit_cast(half8_t, og[0][1]);
+                } else {  // the half-waves trade: h = 0 gives its 16 channels of tile 1 for its partner's 16 of tile 0, and each ends with one whole tile of its pixel
+                    unsigned a[8] = {og[0][0].x, og[0][0].y, og[0][0].z, og[0][0].w, og[0][1].x, og[0][1].y, og[0][1].z, og[0][1].w};
+                    unsigned c[8] = {og[1][0].x, og[1][0].y, og[1][0].z, og[1][0].w, og[1][1].x, og[1][1].y, og[1][1].z, og[1][1].w};
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {  // v_permlane32_swap: lanes 32-63 of a <-> lanes 0-31 of c
+                        const auto r = __builtin_amdgcn_permlane32_swap(a[i], c[i], false, false);
+                        a[i] = r[0];
+                        c[i] = r[1];
+                    }
+                    xq[0] = __builtin_bit_cast(half8_t, uint4{a[0], a[1], a[2], a[3]});
+                    xq[1] = __builtin_bit_cast(half8_t, uint4{a[4], a[5], a[6], a[7]});
+                    xq[2] = __builtin_bit_cast(half8_t, uint4{c[0], c[1], c[2], c[3]});
+                    xq[3] = __builtin_bit_cast(half8_t, uint4{c[4], c[5], c[6], c[7]});
+                }
+#pragma unroll
+                for (int hd = 0; hd < HD; ++hd) {
+                    float16_t dq, dk;
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) { dq[v] = 0.f; dk[v] = 0.f; }
+#pragma unroll
+                    for (int s = 0; s < KSS; ++s) dq = mfma16(xq[s], __builtin_bit_cast(half8_t, wq[(hd * KSS + s) * 64 + lane]), dq);         // D[pixel][q channel]
+#pragma unroll
+                    for (int s = 0; s < KSS; ++s) dk = mfma16(xq[s], __builtin_bit_cast(half8_t, wq[((HD + hd) * KSS + s) * 64 + lane]), dk);  // D[pixel][k channel]
+                    unsigned aq[8], ak[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        aq[j] = pack_f16(dq[2 * j], dq[2 * j + 1]);
+                        ak[j] = pack_f16(dk[2 * j], dk[2 * j + 1]);
+                        fma_mix_lo(nq[hd], aq[j], aq[j]); fma_mix_hi(nq[hd], aq[j], aq[j]);
+                        fma_mix_lo(nk[hd], ak[j], ak[j]); fma_mix_hi(nk[hd], ak[j], ak[j]);
+                    }
+#pragma unroll
+                    for (int b2 = 0; b2 < 2; ++b2)
+                        G[hd] = mfma16(__builtin_bit_cast(half8_t, uint4{ak[4 * b2], ak[4 * b2 + 1], ak[4 * b2 + 2], ak[4 * b2 + 3]}),
+                                       __builtin_bit_cast(half8_t, uint4{aq[4 * b2], aq[4 * b2 + 1], aq[4 * b2 + 2], aq[4 * b2 + 3]}), G[hd]);
+                }
+            }
+        }
+    }
+    if constexpr (GRAM) {  // this workgroup's partial: [hd][34][32] = 32 Gram rows, sum q^2, sum k^2 (as k_mst_qkv16); the weights in LDS are dead
+        __syncthreads();
+        float* red = reinterpret_cast<float*>(smem);
+#pragma unroll
+        for (int hd = 0; hd < HD; ++hd) {
+            float* mine = red + ((size_t)wave * HD + hd) * 34 * 32;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) mine[(8 * (v / 4) + 4 * h + (v % 4)) * 32 + p] = G[hd][v];
+            const float sq = nq[hd] + __shfl_xor(nq[hd], 32), sk = nk[hd] + __shfl_xor(nk[hd], 32);
+            if (h == 0) { mine[32 * 32 + p] = sq; mine[33 * 32 + p] = sk; }
+        }
+        __syncthreads();
+        for (int i = tid; i < HD * 34 * 32; i += 64 * NW) {
+            float sum = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) sum += red[(size_t)w * HD * 34 * 32 + i];
+            partial[(size_t)blockIdx.x * HD * 34 * 32 + i] = sum;
+        }
+    }
+}
+
+// waves per workgroup and workgroups per CU of every instantiation (profiles/r12/resource_usage_mst_mfma.txt): C = 64 runs four workgroups of four
+// waves per CU (the kernel is held to the 128 registers of four waves per SIMD, which it meets without spilling); C = 128 shares one weight image (72 KB, 88 KB with the q / k weights) among 8 waves: with the skip rows a wave holds 188 registers (223
+// with the Gram epilogue), so one workgroup fills a CU at two waves per SIMD; at 12 and 16 waves per workgroup the compiler spills (17 .. 79 registers)
+template <int C, bool SKIP, bool GRAM> struct convt16_geom {
+    static constexpr int NW = C == 128 ? 8 : 4, PER_CU = C == 128 ? (SKIP ? 1 : 2) : 4;
+};
+
+template <int C, bool SKIP, bool GRAM>
+int launch_convt16(avx_ctx* ctx, avx_ws* ws, const void* x, const void* wpack, const float* bias, const void* skip, const void* wskip, void* out, int B, int H, int W,
+                   const void* wqk, float* gram, float* nq, float* nk, hipStream_t s) {
+    constexpr int NW = convt16_geom<C, SKIP, GRAM>::NW, KS = C / 16, CO = C / 2, NT = CO / 32, KSS = CO / 16, HD = NT;
+    size_t lds = sizeof(uint4) * ((size_t)4 * NT * KS * 64 + (SKIP ? NT * KSS * 64 : 0) + (GRAM ? 2 * HD * KSS * 64 : 0)) + sizeof(float) * CO;
+    if (GRAM && lds < sizeof(float) * NW * HD * 34 * 32) lds = sizeof(float) * NW * HD * 34 * 32;  // the waves' results land where the weights were
+    const long total = (long)B * H * ((W + 31) / 32);
+    long blocks = (total + NW - 1) / NW;
+    const long cap = (long)ctx->num_cus * convt16_geom<C, SKIP, GRAM>::PER_CU;
+    if (blocks > cap) blocks = cap;
+    float* partial = nullptr;
+    if (GRAM) {
+        int rc = avx_ensure_scratch(ctx, ws, sizeof(float) * (size_t)blocks * HD * 34 * 32);
+        if (rc) return rc;
+        partial = (float*)ws->d_scratch;
+    }
+    auto k = k_mst_convt2x2_16<C, NW, SKIP, GRAM>;
+    AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * NW), lds, s, (const __half*)x, (const uint4*)wpack, bias, (const __half*)skip, (const uint4*)wskip, (__half*)out, B,
+                       H, W, (const uint4*)wqk, partial);
+    AVX_HIP(ctx, hipGetLastError());
+    if (GRAM) return avx_mst_qkv_final_launch(ctx, partial, (int)blocks, HD, gram, nq, nk, s);
+    return AVX_OK;
+}
+
 // ---- the same pass on v_mfma_f32_32x32x16_f16 (gfx950's double-rate form) ------------------------------------------------------------------
 // k_mst_qkv above is BOUND by its K = 8 MFMAs (64 cycles each: 144 per 32 pixels at C = 128 is 70 us of matrix-core time per 4K launch at a
 // sixteenth of the pixels, 77 us at C = 64, 93 at C = 32); the K = 16 form does the same products in a quarter of the cycles and leaves
@@ -1226,6 +1413,40 @@ static int convt2x2_impl(avx_ctx* ctx, const void* x, const void* wpack, const f
     }
     AVX_HIP(ctx, hipGetLastError());
     return AVX_OK;
+}
+
+// avx_mst_convt2x2 / avx_mst_convt2x2_fuse (skip and wskip16 both NULL / both given) on K = 16 MFMAs: wpack16 / wskip16 are pack_fragments16(..., halfrow=True)
+int avx_mst_convt2x2_fuse16(avx_ctx* ctx, const void* x, const void* wpack16, const float* bias, const void* skip, const void* wskip16, void* out, int B, int H, int W,
+                            int C, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, x && wpack16 && bias && out && B > 0 && H > 0 && W > 0 && (!skip == !wskip16), "avx_mst_convt2x2_fuse16: NULL pointer or empty tensor");
+    AVX_REQUIRE(ctx, C == 64 || C == 128, "avx_mst_convt2x2_fuse16: C=%d (64 or 128 input channels)", C);
+    AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)wpack16 | (uintptr_t)out | (uintptr_t)skip | (uintptr_t)wskip16)) & 15u) == 0,
+                "avx_mst_convt2x2_fuse16: pointers must be 16-byte aligned");
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    if (C == 64) {
+        if (skip) return launch_convt16<64, true, false>(ctx, nullptr, x, wpack16, bias, skip, wskip16, out, B, H, W, nullptr, nullptr, nullptr, nullptr, s);
+        return launch_convt16<64, false, false>(ctx, nullptr, x, wpack16, bias, nullptr, nullptr, out, B, H, W, nullptr, nullptr, nullptr, nullptr, s);
+    }
+    if (skip) return launch_convt16<128, true, false>(ctx, nullptr, x, wpack16, bias, skip, wskip16, out, B, H, W, nullptr, nullptr, nullptr, nullptr, s);
+    return launch_convt16<128, false, false>(ctx, nullptr, x, wpack16, bias, nullptr, nullptr, out, B, H, W, nullptr, nullptr, nullptr, nullptr, s);
+}
+
+// avx_mst_convt2x2_fuse16 followed by avx_mst_qkv_gram16 (v_out = NULL) on its C / 2 output channels (heads = C / 64), in one pass; one frame
+int avx_mst_convt2x2_fuse16_gram(avx_ctx* ctx, const void* x, const void* wpack16, const float* bias, const void* skip, const void* wskip16, void* out, int H, int W,
+                                 int C, int heads, const void* wqk16, float* gram, float* nq, float* nk, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, x && wpack16 && bias && skip && wskip16 && out && wqk16 && gram && nq && nk && H > 0 && W > 0, "avx_mst_convt2x2_fuse16_gram: NULL pointer or empty tensor");
+    AVX_REQUIRE(ctx, (C == 64 || C == 128) && heads == C / 64, "avx_mst_convt2x2_fuse16_gram: C=%d, heads=%d (64 or 128 input channels, one head per 32 output channels)", C, heads);
+    AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)wpack16 | (uintptr_t)out | (uintptr_t)skip | (uintptr_t)wskip16 | (uintptr_t)wqk16)) & 15u) == 0,
+                "avx_mst_convt2x2_fuse16_gram: pointers must be 16-byte aligned");
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    avx_ws* ws = avx_workspace(ctx, s);
+    if (!ws) return AVX_ERR_NOMEM;
+    if (C == 64) return launch_convt16<64, true, true>(ctx, ws, x, wpack16, bias, skip, wskip16, out, 1, H, W, wqk16, gram, nq, nk, s);
+    return launch_convt16<128, true, true>(ctx, ws, x, wpack16, bias, skip, wskip16, out, 1, H, W, wqk16, gram, nq, nk, s);
 }
 
 }  // extern "C"

@@ -244,6 +244,9 @@ class _AvxOps:
         self.FFN_MARCH_C = (32, 64)  # the widths the marching form is built for (C = 128 stays on the 16-row kernel)
         self._tail_march = os.environ.get("AVX_MST_NO_TAIL_MARCH", "") == ""  # A/B: the matrix-pipe attention tail marches down tile columns, carrying v, x and mid rows (round 11)
         self.TAIL_MARCH_C = (32, 64)  # the widths at which the marching form measured faster, dense and sparse, kernel against kernel (profiles/r11/ab_tail_march.txt)
+        self._convt16 = os.environ.get("AVX_MST_NO_CONVT16", "") == ""  # A/B: the decoder upsampling on K = 16 MFMAs, the C = 64 block's Gram pass as its epilogue (round 12)
+        self.CONVT16_C = (64, 128)  # input widths at which the K = 16 kernel measured faster than the K = 8 one, kernel against kernel (profiles/r12/ab_convt16.txt)
+        self.CONVT16_GRAM_C = (128,)  # ... and at which it won with the Gram epilogue: at 64 it ties the K = 8 kernel with its epilogue (326.2 against 324.5 us), which stays
         self._ctx = {}
 
     def ctx(self, device: torch.device):
@@ -355,6 +358,41 @@ class _AvxOps:
         for i in range(b):
             ctx._check(lib.avx_mst_convt2x2_fuse_gram(ctx._h, x[i].data_ptr(), wpack.data_ptr(), bias.data_ptr(), skip[i].data_ptr(), wskip.data_ptr(), out[i].data_ptr(), h, w, c,
                                                       wqk16.data_ptr(), g[i].data_ptr(), nq[i].data_ptr(), nk[i].data_ptr(), st))
+        return out, g, nq, nk
+
+    def convt2x2_16(self, x: torch.Tensor, wpack16: torch.Tensor, bias: torch.Tensor, skip: torch.Tensor = None, wskip16: torch.Tensor = None) -> torch.Tensor:
+        """convt2x2 on K = 16 MFMAs (csrc/mst_mfma.hip::k_mst_convt2x2_16): wpack16 = the four taps' pack_fragments16(..., halfrow=True), wskip16 likewise."""
+        from .._lib import lib
+
+        b, h, w, c = x.shape
+        x = x.contiguous()
+        out = torch.empty((b, 2 * h, 2 * w, c // 2), dtype=torch.float16, device=x.device)
+        ctx = self.ctx(x.device)
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        if skip is not None:
+            assert skip.is_contiguous() and skip.shape == out.shape and wskip16 is not None
+        ctx._check(lib.avx_mst_convt2x2_fuse16(ctx._h, x.data_ptr(), wpack16.data_ptr(), bias.data_ptr(), skip.data_ptr() if skip is not None else None,
+                                               wskip16.data_ptr() if skip is not None else None, out.data_ptr(), b, h, w, c, st))
+        return out
+
+    def convt2x2_16_gram(self, x: torch.Tensor, wpack16: torch.Tensor, bias: torch.Tensor, skip: torch.Tensor, wskip16: torch.Tensor, wqk16: torch.Tensor):
+        """convt2x2_16 with skip / wskip16 and, as its epilogue, the Gram pass of the MSAB block that follows, at c = 64 (one head) or 128 (two);
+        wqk16 = pack_qkv16 of the block's qkv weight -> (out, gram (b, heads, 32, 32), nq (b, c / 2), nk (b, c / 2))."""
+        from .._lib import lib
+
+        b, h, w, c = x.shape
+        ch, heads = c // 2, c // 64
+        assert c in (64, 128) and skip.is_contiguous() and skip.shape == (b, 2 * h, 2 * w, ch)
+        x = x.contiguous()
+        out = torch.empty((b, 2 * h, 2 * w, ch), dtype=torch.float16, device=x.device)
+        g = torch.empty((b, heads, 32, 32), dtype=torch.float32, device=x.device)
+        nq = torch.empty((b, ch), dtype=torch.float32, device=x.device)
+        nk = torch.empty((b, ch), dtype=torch.float32, device=x.device)
+        ctx = self.ctx(x.device)
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        for i in range(b):
+            ctx._check(lib.avx_mst_convt2x2_fuse16_gram(ctx._h, x[i].data_ptr(), wpack16.data_ptr(), bias.data_ptr(), skip[i].data_ptr(), wskip16.data_ptr(), out[i].data_ptr(),
+                                                        h, w, c, heads, wqk16.data_ptr(), g[i].data_ptr(), nq[i].data_ptr(), nk[i].data_ptr(), st))
         return out, g, nq, nk
 
     def posemb(self, v: torch.Tensor, w1_c9: torch.Tensor, w2_c9: torch.Tensor, residual: torch.Tensor = None, bias: torch.Tensor = None) -> torch.Tensor:
@@ -1010,21 +1048,30 @@ class MSTPlusPlus(torch.nn.Module):
                 ch = fea.shape[-1] // 2
                 wfk = f"{p}.fuse{i}"
                 wf_ = self._prep(wfk, lambda: self._w(f"{p}.decoder_layers.{i}.1.weight", (0, 1)).reshape(ch, 2 * ch).t().contiguous())
-                gt = self._prep(kw + ".upfuse4", lambda: torch.stack([pack_fragments((self._w(kw, (0, 1))[:, :, t // 2, t % 2].float() @ wf_[:ch].float()).half().contiguous(), True)
-                                                                     for t in range(4)]).contiguous())
                 gb = self._prep(kw + ".upfuse.bias", lambda: (self._w(f"{p}.decoder_layers.{i}.0.bias", (0,)).float() @ wf_[:ch].float()).contiguous())
-                wbot_ = self._prep(f"{p}.fuse{i}.bot", lambda: pack_fragments(wf_[ch:].contiguous(), True))
                 heads //= 2
                 a2 = f"{p}.decoder_layers.{i}.2.blocks.0.0"
-                if ch == 32 and _AVX._convgram and _AVX._qkv16 and _AVX._tail and _AVX._tailx:  # back at full resolution: the block's Gram pass rides on this launch
+                # the block's Gram pass rides on this launch: at full resolution on either kernel, at half resolution (two heads) on the K = 16 one
+                cangram = _AVX._convgram and _AVX._qkv16 and _AVX._tail and _AVX._tailx
+                gram16 = cangram and _AVX._convt16 and 2 * ch in _AVX.CONVT16_C and 2 * ch in _AVX.CONVT16_GRAM_C
+                gram8 = cangram and ch == 32 and not gram16
+                k16 = gram16 or (_AVX._convt16 and 2 * ch in _AVX.CONVT16_C and not gram8)  # K = 16 MFMAs, all skip rows requested in front of the products
+                tap = lambda t: (self._w(kw, (0, 1))[:, :, t // 2, t % 2].float() @ wf_[:ch].float()).half().contiguous()  # noqa: E731
+                if k16:
+                    gt = self._prep(kw + ".upfuse4k16", lambda: torch.stack([pack_fragments16(tap(t), halfrow=True) for t in range(4)]).contiguous())
+                    wbot_ = self._prep(f"{p}.fuse{i}.bot16", lambda: pack_fragments16(wf_[ch:].contiguous(), halfrow=True))
+                else:
+                    gt = self._prep(kw + ".upfuse4", lambda: torch.stack([pack_fragments(tap(t), True) for t in range(4)]).contiguous())
+                    wbot_ = self._prep(f"{p}.fuse{i}.bot", lambda: pack_fragments(wf_[ch:].contiguous(), True))
+                pre2 = None
+                if gram16 or gram8:
                     wqkv2 = self._prep(a2 + ".qkv", lambda: torch.cat([self._w(a2 + ".to_q.weight", (0, 1)), self._w(a2 + ".to_k.weight", (0, 1)),
                                                                        self._w(a2 + ".to_v.weight", (0, 1))], 0).t().contiguous())
-                    wqk2 = self._prep(a2 + ".qkv.frag16", lambda: pack_qkv16(wqkv2))
-                    fea, g2, nq2, nk2 = _AVX.convt2x2_gram(fea, gt, gb, skips[1 - i].contiguous(), wbot_, wqk2)
-                    fea = self._msab(fea, f"{p}.decoder_layers.{i}.2", heads, (g2, nq2, nk2))
-                    continue
-                fea = _AVX.convt2x2(fea, gt, gb, skips[1 - i].contiguous(), wbot_)
-                fea = self._msab(fea, f"{p}.decoder_layers.{i}.2", heads)
+                    wqk2 = self._prep(a2 + ".qkv.frag16", lambda: pack_qkv16(wqkv2))  # its q and k tiles are what the epilogue reads
+                    fea, *pre2 = (_AVX.convt2x2_16_gram if gram16 else _AVX.convt2x2_gram)(fea, gt, gb, skips[1 - i].contiguous(), wbot_, wqk2)
+                else:
+                    fea = (_AVX.convt2x2_16 if k16 else _AVX.convt2x2)(fea, gt, gb, skips[1 - i].contiguous(), wbot_)
+                fea = self._msab(fea, f"{p}.decoder_layers.{i}.2", heads, tuple(pre2) if pre2 else None)
                 continue
             if _AVX.fused_ok(fea) and fea.shape[-1] in (64, 128):  # four 1x1 products on the matrix cores (kernel size == stride)
                 wt = self._prep(kw + ".frag4", lambda: torch.stack([pack_fragments(self._w(kw, (0, 1))[:, :, t // 2, t % 2].contiguous(), True) for t in range(4)]).contiguous())
@@ -1138,6 +1185,8 @@ def hbm_bytes_per_px(stage: int = 3) -> float:
     per_stage = 2 * msab(32) + 2 * msab(64) / 4 + msab(128) / 16
     if _AVX._convgram and _AVX._qkv16 and _AVX._tail and _AVX._tailx and _AVX._conv_lds and _AVX._upfuse:
         per_stage -= 2 * 64.0          # both full-resolution blocks take their Gram matrix from the conv that produces their input: no read of x for it
+        if _AVX._convt16 and 128 in _AVX.CONVT16_C and 128 in _AVX.CONVT16_GRAM_C:
+            per_stage -= 128.0 / 4     # so does the decoder's C = 64 block (the upsampling kernel's epilogue at 128 input channels)
     t32, t64, t128 = 64.0, 128.0 / 4, 256.0 / 16
     convs = (2 * t32) + (3 * t32)                # embedding; mapping + x
     convs += (t32 + t64) + (t64 + t128)          # two strided 4x4 convs

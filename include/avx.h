@@ -955,6 +955,16 @@ int avx_mst_convt2x2(avx_ctx* ctx, const void* x, const void* wpack, const float
  * `skip` half in fragment order ([C/64][C/16][64] x 4 float16, pack_fragments(..., True)): out = convT'(x) + skip @ W_skip^T. */
 int avx_mst_convt2x2_fuse(avx_ctx* ctx, const void* x, const void* wpack, const float* bias, const void* skip, const void* wskip, void* out, int B, int H,
                           int W, int C, void* stream);
+/* Both of the above on v_mfma_f32_32x32x16_f16 (skip and wskip16 both NULL: the plain transposed conv): wpack16 = 4 taps x pack_fragments16(W_tap,
+ * halfrow=True) ([C/64][C/16][64] x 8 float16 each), wskip16 = pack_fragments16(W_skip, halfrow=True).  Same walk, stores and roundings; a pixel's
+ * products may be summed in another order than the K = 8 kernels sum them. */
+int avx_mst_convt2x2_fuse16(avx_ctx* ctx, const void* x, const void* wpack16, const float* bias, const void* skip, const void* wskip16, void* out, int B, int H,
+                            int W, int C, void* stream);
+/* avx_mst_convt2x2_fuse16 with the Gram pass of the MSAB block that follows as its epilogue (one frame): C = 64 (heads = 1) or 128 (heads = 2);
+ * wqk16 = the block's avx_mst_qkv_gram16 weights (its q and k tiles are read); gram (heads, 32, 32), nq / nk (heads * 32) as avx_mst_qkv_gram16
+ * computes them from `out`. */
+int avx_mst_convt2x2_fuse16_gram(avx_ctx* ctx, const void* x, const void* wpack16, const float* bias, const void* skip, const void* wskip16, void* out, int H, int W,
+                                 int C, int heads, const void* wqk16, float* gram, float* nq, float* nk, void* stream);
 
 /* nn.Conv2d(C, C, 3, 1, 1, groups=C, bias=False) on a channels-last (B,H,W,C) tensor (pos_emb :104-106,
  * FeedForward :147), float32 accumulate; w_c9: C x 9 float32 (weight.reshape(C, 9)); gelu_out: exact-erf GELU. */

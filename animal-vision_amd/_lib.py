@@ -370,6 +370,7 @@ _SIGS = {
     "avx_resize_hwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "avx_binocular_warp_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "avx_cat_wide_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(DichromatDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avx_dichromat_wide_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(DichromatDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     "avx_center_zoom_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "avx_split_compose_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "avx_draw_label_u8": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_int), _fp, _i, ctypes.c_float, ctypes.c_float, _i, _vp]),

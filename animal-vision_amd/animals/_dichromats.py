@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from .. import _lib
-from ..dichromat import AutoNight, DichromatOp, DichromatSpec, NightSpec
+from ..dichromat import AutoNight, DichromatOp, DichromatSpec, NightSpec, as_fov
 from .animal import Animal
 from .animal_utils import check_input_image
 
@@ -18,8 +18,10 @@ from .animal_utils import check_input_image
 class _Dichromat(Animal):
     SPEC: DichromatSpec = None  # type: ignore
 
-    def __init__(self, *, night=None):
-        """night: None (by day, the reference's active code), True (NightSpec's defaults: the values of the commented night
+    def __init__(self, *, night=None, fov=None):
+        """fov: None, or a FovSpec (or its arguments as a tuple): visualize(uint8) then returns (centre-zoomed input, wide view) --
+        the reference's binocular warp in front of this species' colour stage, the pair Cat returns.
+        night: None (by day, the reference's active code), True (NightSpec's defaults: the values of the commented night
         branch of animals/cat.py:50-60) or a NightSpec: rod vision in front of the colour stage, optional tapetum bloom; or an
         AutoNight: every frame by day or as its NightSpec says, decided by the frame's median luma."""
         self._op = None
@@ -30,6 +32,7 @@ class _Dichromat(Animal):
         if night is not None and not isinstance(night, (NightSpec, AutoNight)):
             raise TypeError(f"night must be None, True, a NightSpec or an AutoNight (got {type(night).__name__})")
         self.night = night
+        self.fov = as_fov(fov)
 
     def _operator(self) -> DichromatOp:
         if self._op is None:
@@ -41,9 +44,40 @@ class _Dichromat(Animal):
             what = "night=AutoNight" if isinstance(self.night, AutoNight) else "night"
             raise NotImplementedError(f"{type(self).__name__}: {what} is implemented for uint8 frames, got {image.dtype}")
 
+    def _refuse_float_fov(self, image: np.ndarray) -> None:
+        if self.fov is not None and image.dtype != np.uint8:
+            raise NotImplementedError(f"{type(self).__name__}: fov is implemented for uint8 frames, got {image.dtype}")
+
+    def _fov_constants(self):
+        """(camera_hfov_deg, per_eye_half_fov_deg, overlap_deg, to_human_ratio) of the wide view."""
+        f = self.fov
+        return f.camera_hfov_deg, f.per_eye_half_fov_deg, f.overlap_deg, f.to_human_ratio
+
+    def _visualize_wide_u8(self, image: np.ndarray):
+        """One uint8 frame through the stream operator's launches (WideStreamOp): device tables and buffers are kept per size."""
+        H, W = image.shape[:2]
+        plans = self.__dict__.setdefault("_u8_plans", {})
+        key = (H, W, bool(getattr(self, "ENABLE_FOV_WARP", True)), *self._fov_constants(), self.night)
+        sop = plans.get(key)
+        if sop is None:
+            if len(plans) >= 4:
+                plans.pop(next(iter(plans))).close()
+            sop = plans[key] = (CatStreamOp if isinstance(self, Cat) else WideStreamOp)(self, H, W, depth=1, batch=1)
+        ctx = sop.ctx
+        d_in, d_out = sop.slot_buffers(0)
+        ctx.upload(image, d_in)
+        sop.run_device(d_in, d_out, 1, H, W)
+        wide = ctx.download(d_out, image.shape, np.uint8)
+        d_base = sop.slot_baseline(0)
+        zoomed = image if d_base is d_in else ctx.download(d_base, image.shape, np.uint8)  # center_zoom at scale <= 1: the frame itself
+        return zoomed, wide
+
     def visualize(self, image: np.ndarray) -> Optional[Tuple[np.ndarray, np.ndarray]]:
         assert check_input_image(image)  # dog.py:33
         self._refuse_float_night(image)
+        self._refuse_float_fov(image)
+        if self.fov is not None:
+            return self._visualize_wide_u8(image)
         if image.dtype != np.uint8:
             # The reference tolerates float / wider-int frames (animal_utils.py:45-48); its video, webcam and image
             # renderers only ever produce uint8 (video.py:95).  Float frames of the Gaussian / row-gain species run as a
@@ -143,6 +177,16 @@ class Cat(_Dichromat):
     CAT_TO_HUMAN_RATIO = 1.30
     ENABLE_FOV_WARP = True
 
+    def __init__(self, *, night=None, fov=None):
+        """fov: a FovSpec (or its arguments as a tuple) sets this instance's four FOV constants; every route follows them."""
+        super().__init__(night=night, fov=fov)
+        if self.fov is not None:
+            self.CAMERA_HFOV_DEG, self.CAT_PER_EYE_HALF_FOV_DEG = float(self.fov.camera_hfov_deg), float(self.fov.per_eye_half_fov_deg)
+            self.CAT_OVERLAP_DEG, self.CAT_TO_HUMAN_RATIO = float(self.fov.overlap_deg), float(self.fov.to_human_ratio)
+
+    def _fov_constants(self):
+        return self.CAMERA_HFOV_DEG, self.CAT_PER_EYE_HALF_FOV_DEG, self.CAT_OVERLAP_DEG, self.CAT_TO_HUMAN_RATIO
+
     def visualize(self, image: np.ndarray):
         assert isinstance(image, np.ndarray) and image.ndim == 3 and image.shape[2] == 3, "HxWx3 RGB"
         self._refuse_float_night(image)
@@ -150,23 +194,7 @@ class Cat(_Dichromat):
             if np.issubdtype(image.dtype, np.floating):
                 return self._visualize_float(image)
             raise NotImplementedError(f"Cat: device path implemented for uint8 and float frames, got {image.dtype}")
-        # one frame through the stream operator's two launches (CatStreamOp): device tables and buffers are kept per size
-        H, W = image.shape[:2]
-        plans = self.__dict__.setdefault("_u8_plans", {})
-        key = (H, W, bool(self.ENABLE_FOV_WARP), self.CAMERA_HFOV_DEG, self.CAT_PER_EYE_HALF_FOV_DEG, self.CAT_OVERLAP_DEG, self.CAT_TO_HUMAN_RATIO, self.night)
-        sop = plans.get(key)
-        if sop is None:
-            if len(plans) >= 4:
-                plans.pop(next(iter(plans))).close()
-            sop = plans[key] = CatStreamOp(self, H, W, depth=1, batch=1)
-        ctx = sop.ctx
-        d_in, d_out = sop.slot_buffers(0)
-        ctx.upload(image, d_in)
-        sop.run_device(d_in, d_out, 1, H, W)
-        cat_out = ctx.download(d_out, image.shape, np.uint8)
-        d_base = sop.slot_baseline(0)
-        human_zoomed = image if d_base is d_in else ctx.download(d_base, image.shape, np.uint8)  # center_zoom at scale <= 1: the frame itself
-        return human_zoomed, cat_out
+        return self._visualize_wide_u8(image)
 
     def _visualize_float(self, image: np.ndarray):
         """cat.py:73-112 for a float frame, as a plane program in float32 (the reference's float64 tail is held to the float
@@ -221,62 +249,66 @@ class Cat(_Dichromat):
         return human_zoomed.astype(image.dtype, copy=False), out.astype(image.dtype, copy=False)
 
 
-class CatStreamOp:
-    """Cat as a frame-loop operator (pipeline.FramePipeline's protocol, like SpeciesStreamOp): per slot `batch` contiguous uint8
-    frames in, out and baseline on the device; once per op the five binocular warp tables.  run_device enqueues two launches on
-    the slot's stream: avx_center_zoom_u8 into the slot's baseline (visualize()'s first frame, the split frame's left half) and
-    avx_cat_wide_u8 (csrc/cat_wide.hip: warp, colour tail, blur and encode fused).  With cat.ENABLE_FOV_WARP false the wide view is
-    the ordinary dichromat kernel on the uint8 frames; with a zoom scale <= 1 the baseline is the input itself.  The buffers are
-    plain allocations of the op, which outlive the slot streams.
-    At night (Cat(night=...)) the wide view is the chain the fused kernel is defined by, with the night entry at its
+class WideStreamOp:
+    """The wide view of a dichromat as a frame-loop operator (pipeline.FramePipeline's protocol, like SpeciesStreamOp): Cat, or any of
+    the 19 other dichromats built with fov=.  Per slot `batch` contiguous uint8 frames in, out and baseline on the
+    device; once per op the five binocular warp tables.  run_device enqueues two launches on the slot's stream: avx_center_zoom_u8
+    into the slot's baseline (visualize()'s first frame, the split frame's left half) and the fused wide view -- avx_cat_wide_u8 for
+    Cat, avx_dichromat_wide_u8 for the others (csrc/dichromat_wide.hip: warp, colour stage, post stage and encode behind
+    one entry).  With Cat's ENABLE_FOV_WARP false the wide view is the ordinary dichromat kernel on the uint8 frames; with a zoom
+    scale <= 1 the baseline is the input itself.  The buffers are plain allocations of the op, which outlive the slot streams.
+    At night (night=...) the wide view is the chain the fused kernel is defined by, with the night entry at its
     end: avx_binocular_warp_u8 per frame into the slot's float32 frames, then avx_dichromat_night_u8 with in_f32 = 1 on the batch;
     with ENABLE_FOV_WARP false the night entry on the uint8 frames.  The baseline launch is the same.
-    With Cat(night=AutoNight(...)) the decision is taken on the slot's input frames -- the scene, not the warp:
+    With night=AutoNight(...) the decision is taken on the slot's input frames -- the scene, not the warp:
     avx_luma_mode_u8, the records into pinned memory, one synchronisation of the slot's stream -- and the batch is walked in runs
-    of equal mode: a day run is one avx_cat_wide_u8 launch, a night run the chain above; with ENABLE_FOV_WARP false the
+    of equal mode: a day run is one fused launch, a night run the chain above; with ENABLE_FOV_WARP false the
     switched entry avx_dichromat_auto_u8 does the same inside the library.  `last_modes` and `auto_counts` as DichromatOp's."""
 
-    def __init__(self, cat: Cat, H: int, W: int, depth: int = 3, batch: int = 1, ctx=None):
+    def __init__(self, animal: _Dichromat, H: int, W: int, depth: int = 3, batch: int = 1, ctx=None):
         from .. import geometry as G
 
         if batch < 1:
             raise ValueError(f"batch must be at least 1 (got {batch})")
-        self.cat, self.H, self.W = cat, int(H), int(W)
+        self.animal = self.cat = animal
+        self.H, self.W = int(H), int(W)
         self.batch = self.max_batch = int(batch)
-        self._op = cat._operator() if ctx is None else DichromatOp(cat.SPEC, ctx, night=cat.night)
+        self._op = animal._operator() if ctx is None else DichromatOp(animal.SPEC, ctx, night=animal.night)
         self.ctx = self._op._ctx()
-        self.warp = bool(cat.ENABLE_FOV_WARP)
-        self.rect = self.crop_rect(cat, self.H, self.W)
+        self.warp = bool(getattr(animal, "ENABLE_FOV_WARP", True))
+        self.rect = self.crop_rect(animal, self.H, self.W)
+        camera, phi, overlap, _ = animal._fov_constants()
         nbytes = self.batch * self.H * self.W * 3
         self._bufs = [(self.ctx.malloc(nbytes), self.ctx.malloc(nbytes)) for _ in range(depth)]
         self._base = [self.ctx.malloc(nbytes) if self.rect is not None else None for _ in range(depth)]
         self._by_in = {d_in.ptr: k for k, (d_in, _) in enumerate(self._bufs)}
         self._tables, self._table_ptrs = None, None
-        self.night = cat.night
-        self.auto = cat.night if isinstance(cat.night, AutoNight) else None
+        self.night = animal.night
+        self.auto = animal.night if isinstance(animal.night, AutoNight) else None
         self.last_modes, self.auto_counts = np.zeros(0, np.uint8), [0, 0]
         self._warped, self._host_tables, self._op_f32 = [], None, None
         self._rec, self._rec_host = None, None
+        self._wide_day = G.cat_wide_device if isinstance(animal, Cat) else G.dichromat_wide_device
         if self.warp and self.auto is not None:
             self._rec = self.ctx.malloc(16 * 16)
             self._rec_host = self.ctx.pinned((16,), _lib.LUMA_MODE_REC_DTYPE)
         if self.warp and self.night is not None:
-            self._host_tables = G.binocular_warp_tables(self.H, self.W, self.W, self.H, cat.CAMERA_HFOV_DEG, cat.CAT_PER_EYE_HALF_FOV_DEG, cat.CAT_OVERLAP_DEG)
+            self._host_tables = G.binocular_warp_tables(self.H, self.W, self.W, self.H, camera, phi, overlap)
             self._warped = [self.ctx.malloc(nbytes * 4) for _ in range(depth)]  # float32 HWC frames in [0, 1]
-            self._op_f32 = DichromatOp(cat.SPEC, self.ctx, night=self.auto.night if self.auto is not None else self.night)
+            self._op_f32 = DichromatOp(animal.SPEC, self.ctx, night=self.auto.night if self.auto is not None else self.night)
             self._op_f32.desc.in_f32 = 1
         if self.warp and (self.night is None or self.auto is not None):
-            tables = G.binocular_warp_tables(self.H, self.W, self.W, self.H, cat.CAMERA_HFOV_DEG, cat.CAT_PER_EYE_HALF_FOV_DEG, cat.CAT_OVERLAP_DEG)
+            tables = G.binocular_warp_tables(self.H, self.W, self.W, self.H, camera, phi, overlap)
             self._tables, self._table_ptrs = G.binocular_warp_tables_device(self.ctx, tables)
 
     @staticmethod
-    def crop_rect(cat: Cat, H: int, W: int):
+    def crop_rect(animal, H: int, W: int):
         """The crop (x0, y0, cw, ch) of the H x W frame that the baseline enlarges (cat.py:74-79), or None at a zoom scale <= 1:
         the baseline is the input.  Host arithmetic only."""
         from .. import geometry as G
 
-        scale = G.zoom_scale_from_cat_ratio(camera_hfov_deg=cat.CAMERA_HFOV_DEG, cat_per_eye_half_fov_deg=cat.CAT_PER_EYE_HALF_FOV_DEG,
-                                            cat_to_human_ratio=cat.CAT_TO_HUMAN_RATIO)
+        camera, phi, _, ratio = animal._fov_constants()
+        scale = G.zoom_scale_from_cat_ratio(camera_hfov_deg=camera, cat_per_eye_half_fov_deg=phi, cat_to_human_ratio=ratio)
         return G.center_zoom_rect(H, W, scale)
 
     def slot_buffers(self, k: int):
@@ -290,6 +322,8 @@ class CatStreamOp:
         from .. import geometry as G
 
         assert 1 <= n_frames <= self.batch and (H, W) == (self.H, self.W)
+        if self._table_ptrs is not None:  # the day desc's per-row host tables: the species' op is shared by its operators of every size
+            self._op.prepare_tables(H)
         if self.rect is not None:
             G.center_zoom_device(self.ctx, d_in, self._base[self._by_in[d_in.ptr]], n_frames, H, W, self.rect, stream)
         if self.warp and self.auto is not None:
@@ -306,13 +340,13 @@ class CatStreamOp:
                 if modes[f0]:
                     self._wide_night(run_in, run_out, self._warped[self._by_in[d_in.ptr]], f1 - f0, H, W, stream)
                 else:
-                    G.cat_wide_device(self.ctx, run_in, run_out, f1 - f0, H, W, self._op.desc, self._table_ptrs, stream)
+                    self._wide_day(self.ctx, run_in, run_out, f1 - f0, H, W, self._op.desc, self._table_ptrs, stream)
                 f0 = f1
             self._note_modes(modes)
         elif self.warp and self.night is not None:
             self._wide_night(d_in, d_out, self._warped[self._by_in[d_in.ptr]], n_frames, H, W, stream)
         elif self.warp:
-            G.cat_wide_device(self.ctx, d_in, d_out, n_frames, H, W, self._op.desc, self._table_ptrs, stream)
+            self._wide_day(self.ctx, d_in, d_out, n_frames, H, W, self._op.desc, self._table_ptrs, stream)
         else:
             self._op.run_device(d_in, d_out, n_frames, H, W, stream=stream)
             if self.auto is not None:
@@ -339,3 +373,7 @@ class CatStreamOp:
             if b is not None:
                 b.free()
         self._bufs, self._base, self._tables, self._warped, self._rec, self._rec_host = [], [], None, [], None, None
+
+
+class CatStreamOp(WideStreamOp):
+    """WideStreamOp for Cat, whose geometry is its four FOV constants: the wide view goes through avx_cat_wide_u8."""

@@ -132,5 +132,12 @@ template <> struct Vec8<double> { using type = double; };
 // variant 2 (dichromat_march.hip): returns AVX_ERR_UNSUPPORTED when no instantiation covers (type, radius).
 int avx_launch_dichromat_march(avx_ctx* ctx, avxk::DichromatArgs& a, const avx_dichromat_desc* d, bool f64_cat, hipStream_t s);
 
+// dichromat_wide.hip: what avx_dichromat_wide_u8 and avx_cat_wide_u8 run once their own checks have passed (n_frames >= 1); `who`
+// names the entry in errors, `tile_env` the entry's tile switch (AVX_WIDE_TILE is read where that one is not set).
+int avx_wide_run(avx_ctx* ctx, const char* who, const char* tile_env, const uint8_t* in_hwc_u8, uint8_t* out_hwc_u8, int n_frames, int H, int W,
+                 const avx_dichromat_desc* d, const float* d_xL, const float* d_xR, const float* d_ymap, const float* d_wL, const float* d_wR, void* stream);
+// workgroups of 256 threads per frame for a batched one-item-per-thread-step kernel: enough for `items`, at most ~16 per CU in all
+int avx_blocks_per_frame(avx_ctx* ctx, size_t items, int n_frames);
+
 // AVX_POST_STREAK (dichromat_streak.hip): float32 colour matrix only, like every streak species.
 int avx_launch_dichromat_streak(avx_ctx* ctx, avx_ws* ws, avxk::DichromatArgs& a, const avx_dichromat_desc* d, hipStream_t s);

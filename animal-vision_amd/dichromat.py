@@ -160,6 +160,48 @@ def night_desc(night: NightSpec):
     return nd, (rod, bloom)
 
 
+@dataclass(frozen=True)
+class FovSpec:
+    """A dichromat's field of view: the binocular wide view of the reference (animal_fov_binocular_warp,
+    animals/cat_widevision_utils.py:46-99) in front of the species' colour stage, and the centre-zoomed input
+    (zoom_scale_from_cat_ratio, center_zoom) as the baseline.  Each eye sees `per_eye_half_fov_deg` (phi) to either side of its
+    axis, the two fields share `overlap_deg` (O), and the camera's frame covers `camera_hfov_deg` (2 psi) of the 4 phi - O degrees
+    shown.  The defaults of the last two are Cat's class constants.  The values are the user's: there is no per-species table."""
+
+    per_eye_half_fov_deg: float
+    overlap_deg: float
+    camera_hfov_deg: float = 100.0
+    to_human_ratio: float = 1.30
+
+    def __post_init__(self):
+        for name in ("per_eye_half_fov_deg", "overlap_deg", "camera_hfov_deg", "to_human_ratio"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f"FovSpec.{name} must be a finite number (got {v!r})")
+        if not 0.0 < self.per_eye_half_fov_deg <= 180.0:  # the model divides by phi
+            raise ValueError(f"FovSpec.per_eye_half_fov_deg must be above 0 and at most 180 (got {self.per_eye_half_fov_deg})")
+        if not 0.0 <= self.overlap_deg <= 360.0:  # alpha = max(0, phi - O / 2)
+            raise ValueError(f"FovSpec.overlap_deg must be in [0, 360] (got {self.overlap_deg})")
+        if not 0.0 < self.camera_hfov_deg < 180.0:  # the model takes tan(psi) and divides by psi
+            raise ValueError(f"FovSpec.camera_hfov_deg must be above 0 and below 180 (got {self.camera_hfov_deg})")
+        if not self.to_human_ratio >= 1.0:  # (the reference clamps at 1.01 itself)
+            raise ValueError(f"FovSpec.to_human_ratio must be at least 1 (got {self.to_human_ratio})")
+
+    @property
+    def shown_deg(self) -> float:
+        """The field the output's columns span, in degrees: 4 phi - O (2 phi + 2 alpha, alpha clamped at 0)."""
+        return 2.0 * self.per_eye_half_fov_deg + 2.0 * max(0.0, self.per_eye_half_fov_deg - 0.5 * self.overlap_deg)
+
+
+def as_fov(fov) -> Optional["FovSpec"]:
+    """None, a FovSpec, or the arguments of one as a tuple or list (phi, O[, camera[, ratio]])."""
+    if fov is None or isinstance(fov, FovSpec):
+        return fov
+    if isinstance(fov, (tuple, list)) and 2 <= len(fov) <= 4:
+        return FovSpec(*fov)
+    raise TypeError(f"fov must be None, a FovSpec or its arguments as a tuple (got {type(fov).__name__})")
+
+
 NIGHT_THRESHOLD = 0.12  # RatUV._choose_mode (animals/rat_uv.py:99-104): night when the median Rec.709 luma is below it
 
 
@@ -304,14 +346,8 @@ class DichromatOp:
             self.ctx = get_context()
         return self.ctx
 
-    max_batch = 16  # frames one run_device call takes from a pipeline slot (pipeline.FramePipeline(batch=))
-
-    def run_device(self, d_in: DeviceBuffer, d_out: DeviceBuffer, n_frames: int, H: int, W: int, stream=None):
-        """N uint8 HWC frames resident in HBM -> N uint8 HWC frames; asynchronous on `stream`."""
-        ctx = self._ctx()
-        need = n_frames * H * W * 3
-        if d_in.nbytes < need * (4 if self.desc.in_f32 else 1) or d_out.nbytes < need:
-            raise ValueError("device buffers smaller than n_frames*H*W*3")
+    def prepare_tables(self, H: int) -> None:
+        """The desc's per-row host tables (row gains, streak taps) for frames of H rows; kept until H changes."""
         if self.spec.post == "scone":
             if self._gain is None or self._gain.size != H:
                 s_top, s_bottom, power, boost = self.spec.scone
@@ -321,6 +357,16 @@ class DichromatOp:
             if self._streak is None or self._streak.shape[0] != H:
                 self._streak = streak_row_tables(H, *self.spec.streak)
             self.desc.streak_rows_host = self._streak.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+    max_batch = 16  # frames one run_device call takes from a pipeline slot (pipeline.FramePipeline(batch=))
+
+    def run_device(self, d_in: DeviceBuffer, d_out: DeviceBuffer, n_frames: int, H: int, W: int, stream=None):
+        """N uint8 HWC frames resident in HBM -> N uint8 HWC frames; asynchronous on `stream`."""
+        ctx = self._ctx()
+        need = n_frames * H * W * 3
+        if d_in.nbytes < need * (4 if self.desc.in_f32 else 1) or d_out.nbytes < need:
+            raise ValueError("device buffers smaller than n_frames*H*W*3")
+        self.prepare_tables(H)
         if self.auto is not None:
             modes = np.zeros(16, np.uint8)
             ctx._check(lib.avx_dichromat_auto_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, ctypes.byref(self.desc), ctypes.byref(self.night_desc),

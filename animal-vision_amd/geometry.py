@@ -152,6 +152,13 @@ def cat_wide_device(ctx: Context, d_in: DeviceBuffer, d_out: DeviceBuffer, n_fra
     ctx._check(lib.avx_cat_wide_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, ctypes.byref(desc), xL, xR, ymap, wL, wR, ctx._s(stream)))
 
 
+def dichromat_wide_device(ctx: Context, d_in: DeviceBuffer, d_out: DeviceBuffer, n_frames: int, H: int, W: int, desc, table_ptrs, stream=None):
+    """The wide view of any dichromat desc (avx_dichromat_wide_u8), as cat_wide_device; the desc's per-row host tables
+    (DichromatOp.prepare_tables) must be set for H."""
+    xL, xR, ymap, wL, wR = table_ptrs
+    ctx._check(lib.avx_dichromat_wide_u8(ctx._h, d_in.ptr, d_out.ptr, n_frames, H, W, ctypes.byref(desc), xL, xR, ymap, wL, wR, ctx._s(stream)))
+
+
 def animal_fov_binocular_warp_u8(image: np.ndarray, *, fov_in_deg: float, per_eye_half_fov_deg: float, overlap_deg: float,
                                  out_size=None, ctx: Optional[Context] = None) -> np.ndarray:
     """get_normalized_image + animal_fov_binocular_warp (cat.py:82-92) for a uint8 frame -> float32 HxWx3 in [0,1]."""

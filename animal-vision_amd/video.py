@@ -32,7 +32,7 @@ format keep the payload (1.5 B/px for nv12, 3 B/px for p010le) across the host a
 
 INPUT and OUTPUT are a .y4m file, "-" (stdin / stdout, Y4M), or the other forms renderers.VideoRenderer takes (synthetic:,
 .npy, an image directory).  Species are the display names of gallery.py's registry.  Routing:
-  * the dichromats (DichromatOp; Cat: CatStreamOp, the fused wide-view kernel of DESIGN §4.14), HoneyBee (HoneybeeOp; with
+  * the dichromats (DichromatOp; Cat and --fov: WideStreamOp, the fused wide-view kernels of DESIGN §4.14 and §4.24), HoneyBee (HoneybeeOp; with
     --hsi-model: ml.MstHoneybeeStreamOp) and the plane-program UV
     species with a fixed plan (SpeciesStreamOp) stream through pipeline.run_video: `--depth` frames in flight, split-compose and labels on the device
     (against each species' own baseline, as visualize() returns it: the plane-program species' is their panorama-warped
@@ -54,7 +54,15 @@ with `--bloom S` (0 < S <= 1) its tapetum bloom behind the post stage.  The spec
 `--night-auto` decides day or night for every frame: a frame whose median Rec.709 luma is below `--night-threshold T`
 (default 0.12, the rule of the reference's RatUV) gets the night view, with `--bloom S` the bloom as well; every other frame the day
 view.  The rule has no memory, so a frame's output does not depend on --batch, --depth or the shard -- and a clip that hovers at
-the threshold flickers between the two views.  A line on stderr reports how many frames were night."""
+the threshold flickers between the two views.  A line on stderr reports how many frames were night.
+
+`--fov PHI:OVERLAP` shows one of the 20 dichromats with the reference's binocular wide view in front of its colour stage (DESIGN
+§4.24): each eye sees PHI degrees to either side of its axis, the fields share OVERLAP degrees, the output spans 4 PHI - OVERLAP
+degrees of which the camera supplies `--camera-hfov` (default 100); columns no eye finds in the camera's frame are black.  The
+split frame's left half is the input zoomed to the human's share of that field (`--fov-ratio`, default 1.30).  It streams like Cat,
+with --batch, --night, --night-auto and the rest:
+
+    python -m animal_vision_amd.video in.y4m out.y4m --species Horse --fov 105:40 --split-compare"""
 from __future__ import annotations
 
 import argparse
@@ -89,13 +97,19 @@ def make_animal(args):
         if getattr(args, "night_auto", False):
             thr = getattr(args, "night_threshold", None)
             kw["night"] = AutoNight(kw["night"], NIGHT_THRESHOLD if thr is None else thr)
+    if getattr(args, "fov", None) is not None:
+        from .dichromat import FovSpec
+
+        cam, ratio = getattr(args, "camera_hfov", None), getattr(args, "fov_ratio", None)
+        kw["fov"] = FovSpec(args.fov[0], args.fov[1], 100.0 if cam is None else cam, 1.30 if ratio is None else ratio)
     return cls(**kw)
 
 
 def route(animal) -> str:
     """The kind of `animal`'s frame operator: "dichromat" / "honeybee" / "honeybee_mst" / "plane" name the ops that stream through
     run_video as they are; "frame" is every other species.  Of those Cat streams too, through an operator of its own
-    (CatStreamOp: has_stream_op, stream_op); the rest run visualize() per frame."""
+    (WideStreamOp: has_stream_op, stream_op), as does every dichromat built with fov= (its route() keeps the value it has without);
+    the rest run visualize() per frame."""
     from .animals import Cat, HoneyBee
     from .animals._dichromats import _Dichromat
     from .animals._uv_species import UVSpecies
@@ -114,23 +128,23 @@ def route(animal) -> str:
 
 def has_stream_op(animal) -> bool:
     """Whether stream_op gives `animal` an operator for run_video (and so --batch, --depth and payload I/O): every route but
-    "frame", and Cat."""
+    "frame", Cat, and any dichromat with a field of view (fov=)."""
     from .animals import Cat
 
-    return isinstance(animal, Cat) or route(animal) != "frame"
+    return isinstance(animal, Cat) or getattr(animal, "fov", None) is not None or route(animal) != "frame"
 
 
 def stream_op(animal, H: int, W: int, depth: int, batch: int = 1):
     """The op run_video streams for `animal`, or None when the species goes through the per-frame loop.  batch: frames per
     pipeline slot -- the plane-program species record their plans for that many frames; the dichromat and honeybee ops take
-    n_frames per call as they are; Cat's operator holds `batch` frames per slot; a species of the per-frame loop cannot batch
-    (ValueError)."""
+    n_frames per call as they are; the wide view's operator (Cat, or fov=) holds `batch` frames per slot; a species of the
+    per-frame loop cannot batch (ValueError)."""
     from .animals import Cat
 
-    if isinstance(animal, Cat):
-        from .animals._dichromats import CatStreamOp
+    if isinstance(animal, Cat) or getattr(animal, "fov", None) is not None:
+        from .animals._dichromats import CatStreamOp, WideStreamOp
 
-        return CatStreamOp(animal, H, W, depth=depth, batch=batch)
+        return (CatStreamOp if isinstance(animal, Cat) else WideStreamOp)(animal, H, W, depth=depth, batch=batch)
     kind = route(animal)
     if kind in ("dichromat", "honeybee"):
         return animal._operator()
@@ -187,6 +201,38 @@ def _night_threshold_arg(text: str) -> float:
         raise argparse.ArgumentTypeError(f"--night-threshold takes a number (got {text!r})")
     if not 0.0 <= v <= 1.0:  # (also refuses nan)
         raise argparse.ArgumentTypeError(f"--night-threshold must be at least 0 and at most 1 (got {text!r})")
+    return v
+
+
+def _fov_arg(text: str):
+    try:
+        phi, overlap = (float(v) for v in text.split(":"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--fov takes PHI:OVERLAP in degrees, e.g. 105:40 (got {text!r})")
+    if not 0.0 < phi <= 180.0:  # (also refuses nan)
+        raise argparse.ArgumentTypeError(f"--fov: PHI must be above 0 and at most 180 (got {text!r})")
+    if not 0.0 <= overlap <= 360.0:
+        raise argparse.ArgumentTypeError(f"--fov: OVERLAP must be at least 0 and at most 360 (got {text!r})")
+    return phi, overlap
+
+
+def _camera_hfov_arg(text: str) -> float:
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--camera-hfov takes a number (got {text!r})")
+    if not 0.0 < v < 180.0:  # (also refuses nan)
+        raise argparse.ArgumentTypeError(f"--camera-hfov must be above 0 and below 180 (got {text!r})")
+    return v
+
+
+def _fov_ratio_arg(text: str) -> float:
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--fov-ratio takes a number (got {text!r})")
+    if not (math.isfinite(v) and v >= 1.0):
+        raise argparse.ArgumentTypeError(f"--fov-ratio must be finite and at least 1 (got {text!r})")
     return v
 
 
@@ -273,6 +319,12 @@ class _VideoParser(argparse.ArgumentParser):
             self.error(f"--night: --species {args.species} is not one of the 20 dichromats, the species that have a night view")
         if auto and not is_dichromat(args.species):
             self.error(f"--night-auto: --species {args.species} is not one of the 20 dichromats, the species that have a night view")
+        fov = getattr(args, "fov", None)  # (add_fov_options: parse_args adds them)
+        for flag, v in (("--camera-hfov", getattr(args, "camera_hfov", None)), ("--fov-ratio", getattr(args, "fov_ratio", None))):
+            if v is not None and fov is None:
+                self.error(f"{flag} needs --fov: it is part of the wide view's geometry")
+        if fov is not None and not is_dichromat(args.species):
+            self.error(f"--fov: --species {args.species} is not one of the 20 dichromats, the species that have a wide view")
         if args.hsi_model not in (None, "seeded") and not os.path.isfile(args.hsi_model):
             self.error(f"--hsi-model {args.hsi_model}: no such file (a local .pth checkpoint, or 'seeded')")
         check_io_options(self, args)
@@ -351,10 +403,23 @@ def add_night_auto_options(ap: argparse.ArgumentParser) -> None:
                     help="with --night-auto, 0 <= T <= 1: the median luma below which a frame is night (default 0.12)")
 
 
+def add_fov_options(ap: argparse.ArgumentParser) -> None:
+    """--fov, --camera-hfov and --fov-ratio, added by parse_args like add_night_options."""
+    ap.add_argument("--fov", default=None, type=_fov_arg, metavar="PHI:OVERLAP",
+                    help="the dichromats only: the binocular wide view, e.g. 105:40 -- each eye sees PHI degrees to either side of its axis, "
+                         "the two fields share OVERLAP degrees; the output spans 4 PHI - OVERLAP degrees and --split-compare's left half is "
+                         "the centre-zoomed input")
+    ap.add_argument("--camera-hfov", default=None, type=_camera_hfov_arg, metavar="DEG",
+                    help="with --fov, 0 < DEG < 180: the horizontal field the camera's frame covers (default 100)")
+    ap.add_argument("--fov-ratio", default=None, type=_fov_ratio_arg, metavar="R",
+                    help="with --fov, R >= 1: how much wider the animal's field is than the human's the baseline is zoomed to (default 1.30)")
+
+
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap = build_parser()
     add_night_options(ap)
     add_night_auto_options(ap)
+    add_fov_options(ap)
     args = ap.parse_args(argv)
     check_raw_options(ap, args)
     return args

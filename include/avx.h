@@ -310,6 +310,25 @@ int avx_binocular_warp_u8(avx_ctx* ctx, const uint8_t* in_hwc, int H, int W, con
 int avx_cat_wide_u8(avx_ctx* ctx, const uint8_t* in_hwc_u8, uint8_t* out_hwc_u8, int n_frames, int H, int W, const avx_dichromat_desc* desc,
                     const float* d_xL, const float* d_xR, const float* d_ymap, const float* d_wL, const float* d_wR, void* stream);
 
+/* The wide view of any dichromat (csrc/dichromat_wide.hip): avx_cat_wide_u8's definition with any dichromat desc --
+ * AVX_COLOR_MATRIX or AVX_COLOR_CAT_MERGE; AVX_POST_NONE, _GAUSS (odd ksize <= AVX_MAX_KSIZE), _ROWGAIN or _STREAK; chroma
+ * compression on or off; in_f32 and variant are ignored.  For NONE, GAUSS and ROWGAIN every frame is byte for byte the chain
+ *     avx_binocular_warp_u8(frame, H, W, tables, Ho = H, Wo = W) -> float32 frame -> avx_dichromat_u8(desc with in_f32 = 1)
+ * on the same device.  AVX_POST_STREAK (AVX_COLOR_MATRIX only) has no such chain: warp, blend, float32 sRGB decode and the matrix
+ * -> three float32 planes, avx_streak_planes_f32 per frame, chroma compression, the float32 threshold encode; codes within +-1 of
+ * the reference's arithmetic (device powf).  Two routes compute the same bytes: one fused tile kernel, or planes in the stream
+ * workspace's scratch (12 B per pixel and frame, 24 B with a Gaussian or streak post stage; a batch is walked in groups of at most
+ * 16 frames and 1 GiB).  The entry picks by post stage and radius; AVX_WIDE_ROUTE=fused|planes, AVX_WIDE_TILE=WxH (the fused
+ * kernel's tile) and AVX_WIDE_GROUP=n (frames per group) are tuning and test switches.  STREAK always takes the planes route,
+ * AVX_COLOR_CAT_MERGE (float64) always the fused one.
+ * Tables and call discipline as avx_cat_wide_u8: device pointers the caller owns; asynchronous on `stream`, no stream
+ * synchronisation and no copy of the warp tables (the row gains and the streak row tables are host tables of the desc and are
+ * uploaded when they differ from the last call's, like avx_dichromat_u8's).  AVX_ERR_INVALID (avx_last_error starts with the
+ * function's name) for NULL or aliased frame pointers, NULL tables, n_frames < 0, H or W <= 0 and a desc of the wrong struct_size,
+ * colour mode, post mode, ksize or missing host tables; n_frames == 0 is AVX_OK without a launch. */
+int avx_dichromat_wide_u8(avx_ctx* ctx, const uint8_t* in_hwc_u8, uint8_t* out_hwc_u8, int n_frames, int H, int W, const avx_dichromat_desc* desc,
+                          const float* d_xL, const float* d_xR, const float* d_ymap, const float* d_wL, const float* d_wR, void* stream);
+
 /* center_zoom (cat_widevision_utils.py:11-29) of n_frames contiguous uint8 HWC frames in one launch: each output frame is
  * cv2.resize(frame[y0:y0+ch, x0:x0+cw], (W, H), INTER_LINEAR), byte for byte avx_resize_hwc(dtype 2, interp 1) of the contiguous crop,
  * with that call's tables (the stream workspace's cache: built and uploaded the first time a geometry is seen); the crop is read in

@@ -249,6 +249,17 @@ assert ctypes.sizeof(DeltaERecord) == 1048
 AVX_DELTA_E_MODES = {"heat": 0, "plain": 1}   # enum avx_delta_e_mode
 AVX_DELTA_E_LAYOUTS = {"map": 0, "side": 1}   # enum avx_delta_e_layout
 
+
+class ReceptorDesc(ctypes.Structure):
+    """avx_receptor_desc (include/avx.h)."""
+
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_receptors", ctypes.c_int32), ("matrix", ctypes.c_double * 12), ("weber", ctypes.c_double * 4),
+                ("floor", ctypes.c_double)]
+
+
+assert ctypes.sizeof(ReceptorDesc) == 144
+
+
 class EwInsn(ctypes.Structure):
     _fields_ = [("op", ctypes.c_uint8), ("dst", ctypes.c_uint8), ("a", ctypes.c_uint8), ("b", ctypes.c_uint8), ("imm", ctypes.c_uint32)]
 
@@ -398,6 +409,7 @@ _SIGS = {
     "avx_diff_map_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _i, _i, _vp, _vp, _vp, _vp]),
     "avx_delta_e_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp]),
     "avx_scielab_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp]),
+    "avx_receptor_delta_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

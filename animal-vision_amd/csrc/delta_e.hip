@@ -4,13 +4,14 @@
 // dE with the first pixel that attains it, and the number of pixels beyond the threshold.
 //
 // k_delta_e: grid (chunks, frames); a workgroup owns kChunk = 4096 consecutive pixels of a frame -- a function of H and W alone, so
-// that the float64 sum of a frame is formed in one order whatever the batch.  The chunk of both frames goes into LDS first (VEC: W a
-// multiple of 16 and every buffer 16-byte aligned, 16-byte loads; otherwise byte loads, any size and alignment); thread t then takes
-// pixels t, t + 256, ... of the chunk: Lab of both (a 256-entry decode table in LDS, the anchored matrix form, cbrtf), dE00 in radians
-// throughout (the four cosines of T from one sincosf by the multiple-angle formulas), and the map's bytes go back into LDS; the
-// workgroup writes the panels out in 16-byte stores (VEC: a 16-byte run never leaves its row, and the panels of the side layout start
-// at multiples of 48 bytes in rows of 9 W bytes) or bytes.  A pixel whose codes are equal is 0 by definition and skips the arithmetic;
-// the branch is taken by a wave whose 64 pixels are all equal.  The arithmetic is the vector unit's: nothing here is bound by bytes.
+// that the float64 sum of a frame is formed in one order whatever the batch.  The walk of a chunk -- both frames into LDS, thread t
+// on pixels t, t + 256, ..., the map's bytes back through LDS, the panels out in 16-byte stores or bytes -- is delta_e_walk.h's,
+// shared with receptor.hip; the value of a pixel is this file's: Lab of both (a 256-entry decode table in LDS, the anchored matrix
+// form, cbrtf) and dE00 in radians throughout (the four cosines of T from one sincosf by the multiple-angle formulas).  A pixel whose
+// codes are equal is 0 by definition and skips the arithmetic; the branch is taken by a wave whose 64 pixels are all equal.  The
+// arithmetic is the vector unit's: nothing here is bound by bytes.
+// The map's quantiser is the walk's too, float32 with one rounding per operation and nothing fused:
+// v = fminf(floorf(__fadd_rn(__fmul_rn(G, x), 0.5f)), 255.0f) with x = __fsub_rn(dE, T) in the heat mode and dE in the plain mode.
 // The record: the histogram is counted in LDS (zeros in a register) and flushed with one atomic per non-empty bin; a thread adds its
 // pixels' dE in float64 in pixel order, the workgroup sums in ssim_window.h's fixed order into partials[frame][chunk], and
 // k_delta_e_final adds a frame's partials in index order: no float atomics.  The largest dE is one 64-bit integer maximum over
@@ -19,11 +20,10 @@
 // The Lab transfer function, ciede2000, the key, the colour of a map pixel, the workgroup's share of the record and k_delta_e_final are
 // delta_e_common.h's, shared with scielab.hip.
 #include "delta_e_common.h"
+#include "delta_e_walk.h"
 
 namespace {
 
-constexpr int kPerThread = 16;
-constexpr int kChunk = kThreads * kPerThread;  // pixels of a workgroup: 12288 bytes of each frame, a multiple of 48
 // M': the sRGB -> XYZ (D65) matrix with every row divided by its own sum; columns 0 and 2, the anchored form needs no other
 constexpr float kX0 = (float)(0.4124564 / kSX), kX2 = (float)(0.1804375 / kSX);
 constexpr float kY0 = (float)(0.2126729 / kSY), kY2 = (float)(0.0721750 / kSY);
@@ -40,113 +40,19 @@ __device__ __forceinline__ void lab_of(float r, float g, float b, float& L, floa
     B = 200.0f * (fy - fz);
 }
 
-struct DeArgs {
-    const uint8_t* a;
-    const uint8_t* b;
-    uint8_t* out;      // NULL: no map
-    float* de;         // NULL: no float plane
-    double* partials;  // [frame][chunk]
-    avx_delta_e_rec* rec;
-    int H, W, mode, side;
-    float gain, threshold;
+// dE00 of two pixels whose codes differ
+struct Ciede {
+    __device__ __forceinline__ float operator()(const float* lut, int ar, int ag, int ab, int br, int bg, int bb) const {
+        float L1, a1, b1, L2, a2, b2;
+        lab_of(lut[ar], lut[ag], lut[ab], L1, a1, b1);
+        lab_of(lut[br], lut[bg], lut[bb], L2, a2, b2);
+        return ciede2000(L1, a1, b1, L2, a2, b2);
+    }
 };
 
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void k_delta_e(DeArgs p) {
-    __shared__ __attribute__((aligned(16))) uint8_t sa[kChunk * 3];
-    __shared__ __attribute__((aligned(16))) uint8_t sb[kChunk * 3];
-    __shared__ __attribute__((aligned(16))) uint8_t so[kChunk * 3];
-    __shared__ float lut[256];
-    __shared__ unsigned hist[256];
-    __shared__ double red[kThreads / 64];
-    __shared__ unsigned long long wred[kThreads / 64];
-    __shared__ unsigned bred[kThreads / 64];
-    const int tid = threadIdx.x, f = blockIdx.y;
-    const size_t npx = (size_t)p.H * p.W;  // below 2^32
-    const size_t base = (size_t)blockIdx.x * kChunk;
-    const int valid = (int)min((size_t)kChunk, npx - base);  // pixels of this chunk; VEC: a multiple of 16
-    const uint8_t* fa = p.a + ((size_t)f * npx + base) * 3;
-    const uint8_t* fb = p.b + ((size_t)f * npx + base) * 3;
-    lut[tid] = __uint_as_float(kLabDecodeBits[tid]);
-    hist[tid] = 0;
-    if (VEC) {
-        for (int j = tid; j < valid * 3 / 16; j += kThreads) {
-            reinterpret_cast<uint4*>(sa)[j] = reinterpret_cast<const uint4*>(fa)[j];
-            reinterpret_cast<uint4*>(sb)[j] = reinterpret_cast<const uint4*>(fb)[j];
-        }
-    } else {
-        for (int j = tid; j < valid * 3; j += kThreads) sa[j] = fa[j], sb[j] = fb[j];
-    }
-    __syncthreads();
-
-    const float G = p.gain, T = p.threshold;
-    double sum = 0.0;
-    unsigned long long key = 0;
-    unsigned beyond = 0, zeros = 0;
-    float* de_out = p.de ? p.de + (size_t)f * npx + base : nullptr;
-#pragma unroll 1
-    for (int i = tid; i < valid; i += kThreads) {
-        const int ar = sa[3 * i], ag = sa[3 * i + 1], ab = sa[3 * i + 2];
-        const int br = sb[3 * i], bg = sb[3 * i + 1], bb = sb[3 * i + 2];
-        float de = 0.0f;  // equal codes: 0 by definition
-        if (ar != br || ag != bg || ab != bb) {
-            float L1, a1, b1, L2, a2, b2;
-            lab_of(lut[ar], lut[ag], lut[ab], L1, a1, b1);
-            lab_of(lut[br], lut[bg], lut[bb], L2, a2, b2);
-            de = ciede2000(L1, a1, b1, L2, a2, b2);
-        }
-        const int bin = min(255, (int)(de + de));  // floor(2 dE): dE >= 0
-        if (bin == 0) ++zeros;
-        else atomicAdd(&hist[bin], 1u);
-        sum += (double)de;
-        beyond += de > T ? 1u : 0u;
-        const unsigned long long k = de_key(de, (uint32_t)(base + i));
-        key = k > key ? k : key;
-        if (de_out) de_out[i] = de;
-        if (p.out) {
-            // the quantiser: float32, one rounding per operation, multiply and add never fused
-            const float x = p.mode == AVX_DELTA_E_HEAT ? __fsub_rn(de, T) : de;
-            const float v = fminf(floorf(__fadd_rn(__fmul_rn(G, x), 0.5f)), 255.0f);
-            uint32_t r, g, b;
-            de_colour(v, de, T, p.mode, ar, ag, ab, r, g, b);
-            so[3 * i] = (uint8_t)r, so[3 * i + 1] = (uint8_t)g, so[3 * i + 2] = (uint8_t)b;
-        }
-    }
-    __syncthreads();
-
-    // ---- the panels out of LDS ----
-    if (p.out) {
-        const size_t row = (size_t)p.W * 3;  // bytes of a panel's row
-        uint8_t* fo = p.out + (size_t)f * npx * 3 * (p.side ? 3 : 1);
-        if (VEC) {
-            for (int j = tid; j < valid * 3 / 16; j += kThreads) {
-                const size_t q = base * 3 + (size_t)j * 16;  // byte of the frame: a 16-byte run lies within one row (row % 48 == 0)
-                if (p.side) {
-                    const size_t y = q / row, xb = q - y * row;
-                    uint8_t* dst = fo + y * (3 * row) + xb;
-                    *reinterpret_cast<uint4*>(dst) = reinterpret_cast<const uint4*>(sa)[j];
-                    *reinterpret_cast<uint4*>(dst + row) = reinterpret_cast<const uint4*>(sb)[j];
-                    *reinterpret_cast<uint4*>(dst + 2 * row) = reinterpret_cast<const uint4*>(so)[j];
-                } else {
-                    *reinterpret_cast<uint4*>(fo + q) = reinterpret_cast<const uint4*>(so)[j];
-                }
-            }
-        } else {
-            for (int j = tid; j < valid * 3; j += kThreads) {
-                const size_t q = base * 3 + (size_t)j;
-                if (p.side) {
-                    const size_t y = q / row, xb = q - y * row;
-                    uint8_t* dst = fo + y * (3 * row) + xb;
-                    dst[0] = sa[j], dst[row] = sb[j], dst[2 * row] = so[j];
-                } else {
-                    fo[q] = so[j];
-                }
-            }
-        }
-    }
-
-    // ---- the record ----
-    de_record_share(sum, key, beyond, zeros, hist, red, wred, bred, p.partials + ((size_t)f * gridDim.x + blockIdx.x), p.rec + f);
+    de_chunk_walk<VEC>(p, Ciede());
 }
 
 }  // namespace
@@ -154,35 +60,11 @@ __global__ __launch_bounds__(kThreads) void k_delta_e(DeArgs p) {
 extern "C" int avx_delta_e_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int mode, float gain, float threshold,
                               int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
-    AVX_REQUIRE(ctx, a_hwc && b_hwc && rec_dev, "avx_delta_e_u8: NULL buffer (a %p, b %p, rec %p)", (const void*)a_hwc, (const void*)b_hwc, (void*)rec_dev);
-    AVX_REQUIRE(ctx, n_frames >= 1 && n_frames <= 16, "avx_delta_e_u8: n_frames must be 1..16 (got %d)", n_frames);
-    AVX_REQUIRE(ctx, H >= 1 && W >= 1 && (uint64_t)H * (uint64_t)W < (1ull << 32), "avx_delta_e_u8: bad frame size %d x %d (H * W must be below 2^32)", H, W);
-    AVX_REQUIRE(ctx, mode == AVX_DELTA_E_HEAT || mode == AVX_DELTA_E_PLAIN, "avx_delta_e_u8: bad mode %d", mode);
-    AVX_REQUIRE(ctx, layout == AVX_DELTA_E_MAP || layout == AVX_DELTA_E_SIDE, "avx_delta_e_u8: bad layout %d", layout);
-    AVX_REQUIRE(ctx, std::isfinite(gain) && gain > 0.0f && gain <= 255.0f, "avx_delta_e_u8: the gain must be above 0 and at most 255 (got %g)", (double)gain);
-    AVX_REQUIRE(ctx, std::isfinite(threshold) && threshold >= 0.0f, "avx_delta_e_u8: the threshold must be finite and at least 0 (got %g)", (double)threshold);
-    AVX_REQUIRE(ctx, ((uintptr_t)rec_dev & 7) == 0, "avx_delta_e_u8: rec_dev must be 8-byte aligned");
-    AVX_REQUIRE(ctx, ((uintptr_t)de_out & 3) == 0, "avx_delta_e_u8: de_out must be 4-byte aligned");
-    const size_t npx = (size_t)H * W, in_bytes = (size_t)n_frames * npx * 3, map_bytes = in_bytes * (layout == AVX_DELTA_E_SIDE ? 3 : 1);
-    AVX_REQUIRE(ctx, !map_out || (!overlaps(map_out, map_bytes, a_hwc, in_bytes) && !overlaps(map_out, map_bytes, b_hwc, in_bytes)),
-                "avx_delta_e_u8: map_out overlaps an input (a %p, b %p, map %p)", (const void*)a_hwc, (const void*)b_hwc, (void*)map_out);
-    const size_t nchunks = (npx + kChunk - 1) / kChunk;  // below 2^20
-    AVX_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = avx_pick_stream(ctx, stream);
-    avx_ws* ws = avx_workspace(ctx, s);
-    if (!ws) return AVX_ERR_NOMEM;
-    const int rc = avx_ensure_scratch(ctx, ws, sizeof(double) * nchunks * (size_t)n_frames);
+    const int rc = de_walk_check(ctx, "avx_delta_e_u8", a_hwc, b_hwc, n_frames, H, W, mode, gain, threshold, layout, map_out, rec_dev, de_out);
     if (rc) return rc;
-    AVX_HIP(ctx, hipMemsetAsync(rec_dev, 0, sizeof(avx_delta_e_rec) * (size_t)n_frames, s));
-    DeArgs p;
-    p.a = a_hwc, p.b = b_hwc, p.out = map_out, p.de = de_out, p.partials = (double*)ws->d_scratch, p.rec = rec_dev;
-    p.H = H, p.W = W, p.mode = mode, p.side = layout == AVX_DELTA_E_SIDE, p.gain = gain, p.threshold = threshold;
-    const bool vec = W % 16 == 0 && (((uintptr_t)a_hwc | (uintptr_t)b_hwc | (uintptr_t)map_out) & 15) == 0;
-    const dim3 grid((unsigned)nchunks, n_frames);
-    if (vec) hipLaunchKernelGGL(k_delta_e<true>, grid, dim3(kThreads), 0, s, p);
-    else hipLaunchKernelGGL(k_delta_e<false>, grid, dim3(kThreads), 0, s, p);
-    AVX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_delta_e_final, dim3(n_frames), dim3(kThreads), 0, s, (const double*)ws->d_scratch, nchunks, W, rec_dev);
-    AVX_HIP(ctx, hipGetLastError());
-    return AVX_OK;
+    return de_walk_launch(ctx, a_hwc, b_hwc, n_frames, H, W, mode, gain, threshold, layout, map_out, rec_dev, de_out, stream,
+                          [](bool vec, dim3 grid, hipStream_t s, const DeArgs& p) {
+                              if (vec) hipLaunchKernelGGL(k_delta_e<true>, grid, dim3(kThreads), 0, s, p);
+                              else hipLaunchKernelGGL(k_delta_e<false>, grid, dim3(kThreads), 0, s, p);
+                          });
 }

@@ -1,7 +1,9 @@
 // csrc/delta_e_common.h -- what the colour difference kernels share (delta_e.hip: dE00 per pixel; scielab.hip: dE00 after the S-CIELAB
-// filters), in one copy so that the two cannot drift apart: the Lab transfer function, CIEDE2000, the choice between the palette and
-// the dim grey of a map pixel, the key of the largest dE, a workgroup's share of a record and the kernel that finishes the records.
-// The two roundings of the map's quantiser (__fmul_rn, __fadd_rn) are spelled out in each kernel, next to the pixel they apply to.
+// filters; receptor.hip: the receptor-noise-limited distance per pixel, which takes the record and the map's colours), in one copy so
+// that they cannot drift apart: the Lab transfer function, CIEDE2000, the choice between the palette and the dim grey of a map pixel,
+// the key of the largest dE, a workgroup's share of a record and the kernel that finishes the records.
+// The two roundings of the map's quantiser (__fmul_rn, __fadd_rn) are spelled out next to the pixel they apply to: in delta_e_walk.h
+// (the chunk walk of delta_e.hip and receptor.hip) and in scielab.hip.
 #pragma once
 #include "lab_tables.h"
 #include "map_common.h"

@@ -34,7 +34,22 @@ seen from three picture heights is about 57, and 60 is the usual round number; n
 it.  Finite, from 2 to 128.  Everything else keeps its meaning: the columns, the limits, --threshold, the modes, the layouts (the dim
 grey and the A and B panels are the unfiltered frames), all sources and sinks.  Without --ppd nothing changes.
 
-    python -m animal_vision_amd.deltae full.y4m half.y4m --ppd 60 --max-p95 2"""
+    python -m animal_vision_amd.deltae full.y4m half.y4m --ppd 60 --max-p95 2
+
+--observer NAME --weber E1,E2[,E3] [--floor EPS] asks the question of another animal: can a dog, or a bee, tell the two
+clips apart, and where in the frame.  The value of a pixel is then the receptor-noise-limited distance dS of Vorobyev & Osorio (1998)
+in place of dE00: every receptor class of the observer contributes the logarithm of the ratio of its two catches, weighted by the
+noise of the class -- its Weber fraction --, and the result is in just-noticeable differences, so --threshold 1 keeps its meaning.
+NAME is one of the 20 dichromats (two classes, in the order LM, S: the species' alpha-weighted L and M, and S) or HoneyBee (three:
+UV, Blue, Green); the UV plane-program species, Mantis Shrimp and RatUV have no such matrix on RGB and are refused.  The Weber
+fractions are yours, one per class, each from 0.01 to 1: there is no per-species table (for the honeybee 0.13,0.06,0.12 are the values
+commonly cited from Vorobyev et al. 2001).  EPS (1e-6 to 0.1, default 0.001) is added to every catch before the logarithm and bounds
+what near-black pixels can contribute.  The measure is chromatic: every receptor class is adapted to white, and two greys are 0 apart
+whatever their brightness.  It is a per-pixel measure of the frames as given: it does not combine with --ppd.  Everything else keeps
+its meaning: the columns, the limits, --threshold, the modes, the layouts, all sources and sinks.  Without --observer nothing changes.
+
+    python -m animal_vision_amd.deltae ripe.y4m unripe.y4m heat.y4m --observer Dog --weber 0.05,0.05 --layout side
+    python -m animal_vision_amd.deltae flower.y4m leaf.y4m --observer HoneyBee --weber 0.13,0.06,0.12 --csv bee.csv"""
 from __future__ import annotations
 
 import argparse
@@ -45,8 +60,9 @@ from typing import Iterator, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .metrics import (DELTA_E_DEFAULT_GAIN, DELTA_E_DEFAULT_THRESHOLD, DELTA_E_LAYOUTS, DELTA_E_MODES, DELTA_E_RECORD_BYTES, DeltaE,
-                      check_delta_e_options, check_ppd, delta_e_launch, delta_e_records_from_bytes, scielab_launch)
+from .metrics import (DELTA_E_DEFAULT_GAIN, DELTA_E_DEFAULT_THRESHOLD, DELTA_E_LAYOUTS, DELTA_E_MODES, DELTA_E_RECORD_BYTES, RECEPTOR_DEFAULT_FLOOR,
+                      DeltaE, check_delta_e_options, check_ppd, delta_e_launch, delta_e_records_from_bytes, observer_for, observer_names,
+                      receptor_delta_launch, scielab_launch)
 from .pairs import (add_inputs, check_depth, check_inputs, check_stdin, exit_status, num, open_sink, opened, sink_format,  # noqa: F401
                     stream_map_pairs)
 from .video import add_input_options, add_output_options
@@ -74,6 +90,28 @@ def violation(args, r: DeltaE) -> Optional[str]:
 
 
 class _DeltaEParser(argparse.ArgumentParser):
+    def _observer(self, args):
+        """The metrics.Observer that --observer, --weber and --floor name, or None without them."""
+        if args.observer is None:
+            for flag, v in (("--weber", args.weber), ("--floor", args.floor)):
+                if v is not None:
+                    self.error(f"{flag} belongs to --observer NAME: without an observer there are no receptor classes")
+            return None
+        if args.weber is None:
+            self.error("--observer needs --weber E1,E2[,E3]: the Weber fraction of each receptor class; there is no per-species table")
+        if args.ppd is not None:
+            self.error("--observer and --ppd do not combine: the receptor distance is taken per pixel of the frames as given")
+        try:
+            weber = [float(v) for v in args.weber.split(",")]
+        except ValueError:
+            self.error(f"--weber: comma-separated numbers, e.g. 0.05,0.05 (got {args.weber!r})")
+        if args.observer not in observer_names():
+            self.error(f"--observer: no receptor model on RGB for {args.observer!r}: the observers are {', '.join(observer_names())}")
+        try:
+            return observer_for(args.observer, weber, RECEPTOR_DEFAULT_FLOOR if args.floor is None else args.floor)
+        except ValueError as e:
+            self.error(f"--weber / --floor: {e}")
+
     def parse_args(self, args=None, namespace=None):
         args = super().parse_args(args, namespace)
         if args.out is None:
@@ -93,6 +131,7 @@ class _DeltaEParser(argparse.ArgumentParser):
                 args.ppd = check_ppd(args.ppd)
             except ValueError as e:
                 self.error(f"--ppd: {e}")
+        args.observer = self._observer(args)
         for flag, v in (("--max-mean", args.max_mean), ("--max-p95", args.max_p95), ("--max-de", args.max_de)):
             if v is not None and not (math.isfinite(v) and v >= 0.0):
                 self.error(f"{flag} must be finite and at least 0 (got {v:g})")
@@ -101,7 +140,8 @@ class _DeltaEParser(argparse.ArgumentParser):
 
 
 def build_parser() -> argparse.ArgumentParser:
-    ap = _DeltaEParser(prog="deltae", description="CIEDE2000 colour difference of two videos, per frame and as a video of maps, computed on the device.")
+    ap = _DeltaEParser(prog="deltae", description="CIEDE2000 colour difference of two videos -- or, with --observer, the distance another species' receptors see -- per frame and as a video of "
+                                         "maps, computed on the device.")
     add_inputs(ap)
     ap.add_argument("out", metavar="OUT", nargs="?", default=None,
                     help="optional: .y4m file, '-' (stdout: Y4M, or raw video with --pix-fmt / --out-pix-fmt), a raw video file, .npy or a directory "
@@ -120,6 +160,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="S-CIELAB: filter both frames by the eye's contrast sensitivity at X pixels per degree of visual angle before dE is taken "
                          "(X = pixels per unit length x viewing distance x tan 1 degree; a 1080-line picture seen from three picture heights is "
                          "about 57; take 60 when in doubt).  Finite, from 2 to 128.  Default: none, the plain per-pixel dE")
+    ap.add_argument("--observer", default=None, metavar="NAME",
+                    help="the receptor-noise-limited distance dS (Vorobyev & Osorio 1998), in just-noticeable differences, as this species' receptor "
+                         "classes see it, in place of dE: one of the 20 dichromats (two classes: LM, S) or HoneyBee (three: UV, Blue, Green).  "
+                         "Needs --weber; chromatic only: two greys are 0 apart.  Default: none, the human dE")
+    ap.add_argument("--weber", default=None, metavar="E1,E2[,E3]",
+                    help="with --observer: the Weber fraction of each receptor class, in the observer's order, each from 0.01 to 1.  They are "
+                         "yours to choose: there is no per-species table (0.13,0.06,0.12 are the values commonly cited for the honeybee from "
+                         "Vorobyev et al. 2001)")
+    ap.add_argument("--floor", type=float, default=None, metavar="EPS",
+                    help=f"with --observer: added to every catch before the logarithm, from 1e-6 to 0.1 (default {RECEPTOR_DEFAULT_FLOOR:g})")
     ap.add_argument("--layout", default=None, choices=list(DELTA_E_LAYOUTS), help="map (default): the map alone.  side: A | B | map, three times as wide")
     ap.add_argument("--csv", default=None, metavar="FILE",
                     help=f"write {CSV_HEADER} per frame here; without OUT the default is stdout, with OUT nothing is written unless this is given")
@@ -139,11 +189,13 @@ def stream_records(args, info: dict, fmt: Optional[str] = None) -> Iterator[Tupl
     """(output frame, record) of the common prefix of args.a and args.b, in frame order.  Without args.out the frame is None and no map
     is computed.  Otherwise it is RGB uint8 H x W x 3 (H x 3W x 3 with --layout side) when fmt is None, else the flat payload the
     device encoded it to ("i420", or a raw pixel format name).  info["hw"] is the output frames' (H, W) once the first item is there;
-    info["longer"] names the input ("A" / "B") that had frames left over, when one had.  The loop is pairs.stream_map_pairs; args.ppd
-    picks the launch: delta_e_launch when None, else scielab_launch."""
+    info["longer"] names the input ("A" / "B") that had frames left over, when one had.  The loop is pairs.stream_map_pairs;
+    args.observer and args.ppd pick the launch: receptor_delta_launch with an observer, scielab_launch with ppd, else delta_e_launch."""
     def launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, stream):
         kw = dict(mode=args.mode, gain=args.gain, threshold=args.threshold, layout=args.layout, stream=stream)
-        if getattr(args, "ppd", None) is None:
+        if getattr(args, "observer", None) is not None:
+            receptor_delta_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, observer=args.observer, **kw)
+        elif getattr(args, "ppd", None) is None:
             delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, **kw)
         else:
             scielab_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, ppd=args.ppd, **kw)
@@ -189,8 +241,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             csv.close()
     dt = time.perf_counter() - t0
     where = f" (frame {worst[1]}, pixel x {worst[2]} y {worst[3]})" if worst[0] else ""
-    what = "dE" if args.ppd is None else f"S-CIELAB dE (ppd {args.ppd:g})"
-    print(f"deltae: {frames} frames, mean {what} {num(sum_mean / frames) if frames else 'nan'}, largest dE {num(worst[0])}{where}, "
+    observer = getattr(args, "observer", None)
+    what = f"RNL dS ({observer.describe()})" if observer is not None else "dE" if args.ppd is None else f"S-CIELAB dE (ppd {args.ppd:g})"
+    unit = "dS" if observer is not None else "dE"
+    print(f"deltae: {frames} frames, mean {what} {num(sum_mean / frames) if frames else 'nan'}, largest {unit} {num(worst[0])}{where}, "
           f"{beyond} pixels beyond {args.threshold:g}, {frames / dt if dt > 0 else 0.0:.1f} fps", file=sys.stderr)
     return exit_status("deltae", args, info, frames, first_bad)
 

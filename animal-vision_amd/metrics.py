@@ -23,19 +23,27 @@ delta_e, delta_e_map and delta_e_values take arrays.  python -m animal_vision_am
 
 S-CIELAB (csrc/scielab.hip) is the same difference for a viewer at a stated distance: both frames are filtered by the
 eye's contrast sensitivity at `ppd` pixels per degree before dE00 is taken.  scielab_launch, scielab, scielab_map and scielab_values
-are the counterparts of the four above and return the same DeltaE records; `deltae --ppd` is the command."""
+are the counterparts of the four above and return the same DeltaE records; `deltae --ppd` is the command.
+
+Receptor-noise-limited distance (csrc/receptor.hip; Vorobyev & Osorio 1998) asks the question of another observer: can an
+animal with these receptor classes and these Weber fractions tell the two colours apart, and where.  An Observer is a K x 3 matrix on
+linear RGB with K Weber fractions (observer_for builds the one of a dichromat species or of HoneyBee); receptor_delta_launch,
+receptor_delta, receptor_delta_map and receptor_delta_values return dS in just-noticeable differences in the same DeltaE records, maps
+and value planes; `deltae --observer` is the command."""
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 import numbers
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 
 from ._lib import AVX_DELTA_E_LAYOUTS, AVX_DELTA_E_MODES, AVX_DIFF_LAYOUTS, AVX_DIFF_MODES, AVX_METRICS_MAX_FRAMES, AVX_PIX_FMTS, FrameMetricsRecord, MsSsimRecord, PlaneMetricsRecord, lib
 from ._lib import DeltaERecord as DeltaERecordStruct
 from ._lib import DiffRecord as DiffRecordStruct
+from ._lib import ReceptorDesc
 from .runtime import Context, DeviceBuffer, get_context
 
 MAX_FRAMES = AVX_METRICS_MAX_FRAMES
@@ -677,13 +685,8 @@ def check_delta_e_options(mode: str = "heat", gain=None, threshold=DELTA_E_DEFAU
     return float(gain), float(threshold)
 
 
-def delta_e_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_map: Optional[DeviceBuffer],
-                   d_rec: DeviceBuffer, *, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map",
-                   d_float: Optional[DeviceBuffer] = None, stream=None) -> None:
-    """Enqueue the colour difference of n_frames frames on `stream`: d_rec takes n_frames records of DELTA_E_RECORD_BYTES
-    (delta_e_records_from_bytes reads them); d_map, when not None, n_frames frames of H x W x 3 (layout "map") or H x 3W x 3 ("side":
-    A | B | map); d_float, when not None, the float32 dE of every pixel, n_frames x H x W.  Nothing is downloaded and nothing waits."""
-    _check_call(n_frames, H, W, d_a, d_b)
+def _check_delta_e_buffers(n_frames: int, H: int, W: int, d_map, d_rec, d_float, mode, gain, threshold, layout):
+    """check_delta_e_options, then the sizes of the buffers a colour difference launch writes; (gain, threshold) as floats."""
     g, t = check_delta_e_options(mode, gain, threshold, layout)
     if d_rec.nbytes < n_frames * DELTA_E_RECORD_BYTES:
         raise ValueError(f"{n_frames} records need {n_frames * DELTA_E_RECORD_BYTES} bytes; the buffer holds {d_rec.nbytes}")
@@ -692,6 +695,17 @@ def delta_e_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames:
         raise ValueError(f"{n_frames} {layout} frames need {need} bytes; the buffer holds {d_map.nbytes}")
     if d_float is not None and d_float.nbytes < n_frames * H * W * 4:
         raise ValueError(f"the values of {n_frames} frames need {n_frames * H * W * 4} bytes; the buffer holds {d_float.nbytes}")
+    return g, t
+
+
+def delta_e_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_map: Optional[DeviceBuffer],
+                   d_rec: DeviceBuffer, *, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map",
+                   d_float: Optional[DeviceBuffer] = None, stream=None) -> None:
+    """Enqueue the colour difference of n_frames frames on `stream`: d_rec takes n_frames records of DELTA_E_RECORD_BYTES
+    (delta_e_records_from_bytes reads them); d_map, when not None, n_frames frames of H x W x 3 (layout "map") or H x 3W x 3 ("side":
+    A | B | map); d_float, when not None, the float32 dE of every pixel, n_frames x H x W.  Nothing is downloaded and nothing waits."""
+    _check_call(n_frames, H, W, d_a, d_b)
+    g, t = _check_delta_e_buffers(n_frames, H, W, d_map, d_rec, d_float, mode, gain, threshold, layout)
     ctx._check(lib.avx_delta_e_u8(ctx._h, d_a.ptr, d_b.ptr, int(n_frames), int(H), int(W), AVX_DELTA_E_MODES[mode], g, t, AVX_DELTA_E_LAYOUTS[layout],
                                   None if d_map is None else d_map.ptr, d_rec.ptr, None if d_float is None else d_float.ptr, ctx._s(stream)))
 
@@ -702,9 +716,9 @@ def delta_e_records_from_bytes(buf: np.ndarray, n_frames: int) -> List[DeltaE]:
             for r in _records(buf, n_frames, DELTA_E_RECORD_BYTES, _DELTA_E_DTYPE)]
 
 
-def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_float, ppd=None):
-    """delta_e, delta_e_map, delta_e_values and (with ppd) their scielab counterparts: the stack in chunks of at most 16 frames ->
-    (maps or None, records, values or None)."""
+def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_float, ppd=None, observer=None):
+    """delta_e, delta_e_map, delta_e_values and their scielab (with ppd) and receptor_delta (with observer) counterparts: the stack in
+    chunks of at most 16 frames -> (maps or None, records, values or None)."""
     N, H, W = a.shape[:3]
     wide = 3 if layout == "side" else 1
     maps = np.empty((N, H, W * wide, 3), np.uint8) if with_map else None
@@ -712,7 +726,10 @@ def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_flo
     recs: List[DeltaE] = []
 
     def per_chunk(ctx, i, n, d_a, d_b, d_rec, d_map, d_val):
-        if ppd is None:
+        if observer is not None:
+            receptor_delta_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, observer=observer, mode=mode, gain=gain, threshold=threshold, layout=layout,
+                                  d_float=d_val)
+        elif ppd is None:
             delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_float=d_val)
         else:
             scielab_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, ppd=ppd, mode=mode, gain=gain, threshold=threshold, layout=layout, d_float=d_val)
@@ -770,14 +787,7 @@ def scielab_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames:
     and map.  Nothing is downloaded and nothing waits."""
     _check_call(n_frames, H, W, d_a, d_b)
     ppd = check_ppd(ppd)
-    g, t = check_delta_e_options(mode, gain, threshold, layout)
-    if d_rec.nbytes < n_frames * DELTA_E_RECORD_BYTES:
-        raise ValueError(f"{n_frames} records need {n_frames * DELTA_E_RECORD_BYTES} bytes; the buffer holds {d_rec.nbytes}")
-    need = n_frames * H * W * 3 * (3 if layout == "side" else 1)
-    if d_map is not None and d_map.nbytes < need:
-        raise ValueError(f"{n_frames} {layout} frames need {need} bytes; the buffer holds {d_map.nbytes}")
-    if d_float is not None and d_float.nbytes < n_frames * H * W * 4:
-        raise ValueError(f"the values of {n_frames} frames need {n_frames * H * W * 4} bytes; the buffer holds {d_float.nbytes}")
+    g, t = _check_delta_e_buffers(n_frames, H, W, d_map, d_rec, d_float, mode, gain, threshold, layout)
     ctx._check(lib.avx_scielab_u8(ctx._h, d_a.ptr, d_b.ptr, int(n_frames), int(H), int(W), ppd, AVX_DELTA_E_MODES[mode], g, t,
                                   AVX_DELTA_E_LAYOUTS[layout], None if d_map is None else d_map.ptr, d_rec.ptr,
                                   None if d_float is None else d_float.ptr, ctx._s(stream)))
@@ -807,4 +817,156 @@ def scielab_values(a, b, *, ppd, ctx: Optional[Context] = None) -> np.ndarray:
     a, b, batched = check_pair(a, b)
     ppd = check_ppd(ppd)
     vals = _delta_e_chunks(a, b, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True, ppd)[2]
+    return vals if batched else vals[0]
+
+
+# ------------------------------------------------------------------------------------------------ receptor-noise-limited distance
+RECEPTOR_MIN_WEBER, RECEPTOR_MAX_WEBER = 0.01, 1.0
+RECEPTOR_MIN_FLOOR, RECEPTOR_MAX_FLOOR = 1e-6, 0.1
+RECEPTOR_DEFAULT_FLOOR = 1e-3
+
+
+def _real(v) -> bool:
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+@dataclasses.dataclass(frozen=True)
+class Observer:
+    """Who looks (avx_receptor_desc, include/avx.h): K = 2, 3 or 4 receptor classes as the K x 3 `matrix` on linear RGB (entries finite
+    and not negative, no zero row; the library divides every row by its sum, so white has catch 1 in every class), the Weber fraction
+    of every class in `weber` (0.01 .. 1: the noise of the class, the caller's choice -- there is no per-species table) and the
+    `floor` (1e-6 .. 0.1) added to every catch before the logarithm.  matrix and weber are kept as tuples of floats.  ValueError
+    naming the field otherwise."""
+
+    name: str
+    matrix: Tuple[Tuple[float, float, float], ...]
+    weber: Tuple[float, ...]
+    floor: float = RECEPTOR_DEFAULT_FLOOR
+
+    def __post_init__(self):
+        try:
+            m = np.array(self.matrix, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"matrix must be K x 3 numbers (got {self.matrix!r})") from None
+        if m.ndim != 2 or m.shape[1] != 3 or not 2 <= m.shape[0] <= 4:
+            raise ValueError(f"matrix must be K x 3 with K = 2, 3 or 4 receptor classes (got shape {m.shape})")
+        if not np.isfinite(m).all() or (m < 0).any():
+            raise ValueError(f"matrix entries must be finite and not negative (got {m.tolist()})")
+        for i, row in enumerate(m):
+            if not (row.sum() > 0 and math.isfinite(row.sum())):
+                raise ValueError(f"matrix row {i} sums to {row.sum():g}: it must be above 0")
+        w = self.weber
+        if isinstance(w, (str, bytes)) or not hasattr(w, "__len__") or len(w) != m.shape[0]:
+            raise ValueError(f"weber must hold one Weber fraction per receptor class, {m.shape[0]} (got {w!r})")
+        for i, e in enumerate(w):
+            if not _real(e) or not RECEPTOR_MIN_WEBER <= e <= RECEPTOR_MAX_WEBER:
+                raise ValueError(f"weber[{i}] must be a number from {RECEPTOR_MIN_WEBER:g} to {RECEPTOR_MAX_WEBER:g} (got {e!r})")
+        if not _real(self.floor) or not RECEPTOR_MIN_FLOOR <= self.floor <= RECEPTOR_MAX_FLOOR:
+            raise ValueError(f"floor must be a number from {RECEPTOR_MIN_FLOOR:g} to {RECEPTOR_MAX_FLOOR:g} (got {self.floor!r})")
+        object.__setattr__(self, "name", str(self.name))
+        object.__setattr__(self, "matrix", tuple(tuple(float(v) for v in row) for row in m))
+        object.__setattr__(self, "weber", tuple(float(e) for e in w))
+        object.__setattr__(self, "floor", float(self.floor))
+
+    @property
+    def n_receptors(self) -> int:
+        return len(self.matrix)
+
+    def desc(self) -> ReceptorDesc:
+        """The avx_receptor_desc of this observer."""
+        d = ReceptorDesc()
+        d.struct_size, d.n_receptors, d.floor = ctypes.sizeof(ReceptorDesc), self.n_receptors, self.floor
+        for i, row in enumerate(self.matrix):
+            d.matrix[3 * i : 3 * i + 3] = row
+        d.weber[: self.n_receptors] = self.weber
+        return d
+
+    def describe(self) -> str:
+        """"Dog, weber 0.05,0.05, floor 0.001"."""
+        return f"{self.name}, weber {','.join(f'{e:g}' for e in self.weber)}, floor {self.floor:g}"
+
+
+def observer_names() -> List[str]:
+    """The display names observer_for takes: the 20 dichromats, then HoneyBee."""
+    from .gallery import NON_UV_NAMES
+
+    return list(NON_UV_NAMES) + ["HoneyBee"]
+
+
+def observer_for(species, weber, floor=RECEPTOR_DEFAULT_FLOOR) -> Observer:
+    """The Observer of a species -- a display name (observer_names()), a class or an instance -- with the caller's Weber fractions.
+    A dichromat has K = 2 classes in the order (LM, S): alpha L + (1 - alpha) M with the species' alpha, and S, of dichromat.py's
+    RGB -> LMS matrix (s_scale cancels in a ratio).  HoneyBee has K = 3 in the order (UV, Blue, Green): its operator's rgb_matrix
+    (an instance's own, with its illuminant and curves).  ValueError naming anything else: the UV plane-program species, MantisShrimp
+    and RatUV have no K x 3 matrix on RGB."""
+    from . import animals
+    from .animals._dichromats import _Dichromat
+    from .dichromat import M_RGB_TO_LMS
+    from .gallery import species_class
+
+    if isinstance(species, str):
+        if species not in observer_names():
+            raise ValueError(f"no receptor model on RGB for {species!r}: the observers are {', '.join(observer_names())}")
+        name, who = species, species_class(species)
+    else:
+        who = species
+        name = (who if isinstance(who, type) else type(who)).__name__
+    cls = who if isinstance(who, type) else type(who)
+    if issubclass(cls, _Dichromat):
+        lms = M_RGB_TO_LMS.astype(np.float64)
+        alpha = float(cls.SPEC.alpha)
+        matrix = np.stack([alpha * lms[0] + (1.0 - alpha) * lms[1], lms[2]])
+    elif issubclass(cls, animals.HoneyBee):
+        bee = who() if isinstance(who, type) else who
+        matrix = np.asarray(bee._operator().rgb_matrix, np.float64)
+    else:
+        raise ValueError(f"no receptor model on RGB for {name!r}: the observers are {', '.join(observer_names())}")
+    return Observer(name, matrix, tuple(weber) if hasattr(weber, "__iter__") and not isinstance(weber, (str, bytes)) else weber, floor)
+
+
+def _check_observer(observer) -> Observer:
+    if not isinstance(observer, Observer):
+        raise ValueError(f"observer must be an Observer, as observer_for(species, weber) builds one (got {type(observer).__name__})")
+    return observer
+
+
+def receptor_delta_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_map: Optional[DeviceBuffer],
+                          d_rec: DeviceBuffer, *, observer: Observer, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD,
+                          layout: str = "map", d_float: Optional[DeviceBuffer] = None, stream=None) -> None:
+    """delta_e_launch with the receptor-noise-limited distance dS of `observer` in place of dE00: the same buffers, records and map;
+    the threshold is in just-noticeable differences.  Nothing is downloaded and nothing waits."""
+    _check_call(n_frames, H, W, d_a, d_b)
+    desc = _check_observer(observer).desc()
+    g, t = _check_delta_e_buffers(n_frames, H, W, d_map, d_rec, d_float, mode, gain, threshold, layout)
+    ctx._check(lib.avx_receptor_delta_u8(ctx._h, d_a.ptr, d_b.ptr, int(n_frames), int(H), int(W), ctypes.byref(desc), AVX_DELTA_E_MODES[mode], g, t,
+                                         AVX_DELTA_E_LAYOUTS[layout], None if d_map is None else d_map.ptr, d_rec.ptr,
+                                         None if d_float is None else d_float.ptr, ctx._s(stream)))
+
+
+def receptor_delta(a, b, observer: Observer, threshold=DELTA_E_DEFAULT_THRESHOLD, *, ctx: Optional[Context] = None):
+    """How far apart `observer` sees a and b: uint8 sRGB H x W x 3 -> the DeltaE record of dS (just-noticeable differences), or
+    N x H x W x 3 -> a list of N; no map is computed.  The measure is chromatic: two greys are 0 apart whatever their brightness.
+    ValueError for a bad option or shape before any device work."""
+    a, b, batched = check_pair(a, b)
+    _check_observer(observer)
+    check_delta_e_options("heat", None, threshold, "map")
+    recs = _delta_e_chunks(a, b, "heat", None, threshold, "map", ctx, False, False, observer=observer)[1]
+    return recs if batched else recs[0]
+
+
+def receptor_delta_map(a, b, observer: Observer, *, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map",
+                       ctx: Optional[Context] = None):
+    """delta_e_map of dS as `observer` sees it: (the map, its DeltaE record), or (N maps, a list of N records)."""
+    a, b, batched = check_pair(a, b)
+    _check_observer(observer)
+    check_delta_e_options(mode, gain, threshold, layout)
+    maps, recs, _ = _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, True, False, observer=observer)
+    return (maps, recs) if batched else (maps[0], recs[0])
+
+
+def receptor_delta_values(a, b, observer: Observer, *, ctx: Optional[Context] = None) -> np.ndarray:
+    """delta_e_values of dS as `observer` sees it: float32 H x W or N x H x W."""
+    a, b, batched = check_pair(a, b)
+    _check_observer(observer)
+    vals = _delta_e_chunks(a, b, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True, observer=observer)[2]
     return vals if batched else vals[0]

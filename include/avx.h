@@ -642,6 +642,46 @@ int avx_delta_e_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int
 int avx_scielab_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, double ppd, int mode, float gain,
                    float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream);
 
+/* Receptor-noise-limited colour distance maps (csrc/receptor.hip; Vorobyev & Osorio 1998): avx_delta_e_u8 with the
+ * distance dS between the pixels of two batches of uint8 sRGB frames as an observer's receptor classes tell them apart, in
+ * just-noticeable differences, in place of dE00.  The measure is chromatic: it says nothing about brightness.
+ * The observer: K = n_receptors in 2..4 receptor classes; R = matrix, K rows of 3 (row-major; the rows beyond K are not read) on
+ * linear RGB, every entry finite and >= 0 and every row sum > 0; e_i = weber[i], the Weber fraction of class i, 0.01 <= e_i <= 1;
+ * eps = floor, 1e-6 <= eps <= 0.1 (1e-3 is the usual choice).
+ * Each row of R is divided by its own sum in double and then rounded to float32 once (R'), so that white has catch 1 in every class:
+ * von Kries adaptation to a white background, as avx_delta_e_u8 does with M'.
+ * The catch of a pixel: with lin the 256-entry decode table of avx_delta_e_u8 and (r, g, b) = lin of the codes,
+ * q_i = (g + R'_i0 (r - g)) + R'_i2 (b - g) in float32, one rounding per operation: the anchored form of avx_delta_e_u8, so a grey
+ * has q_i = g exactly for every i.
+ * The contrast of class i between pixel A and pixel B: df_i = logf((q_iA + eps) / (q_iB + eps)): two float32 sums, one float32
+ * division, the library logf (not the fast intrinsic).
+ * The distance:
+ *   K = 2: dS = |df_1 - df_2| / sqrt(e_1^2 + e_2^2).
+ *   K = 3: dS^2 = [e_1^2 (df_3 - df_2)^2 + e_2^2 (df_3 - df_1)^2 + e_3^2 (df_2 - df_1)^2] / [(e_1 e_2)^2 + (e_1 e_3)^2 + (e_2 e_3)^2].
+ *   K = 4: dS^2 = [(e_1 e_2)^2 (df_4 - df_3)^2 + (e_1 e_3)^2 (df_4 - df_2)^2 + (e_1 e_4)^2 (df_3 - df_2)^2 + (e_2 e_3)^2 (df_4 - df_1)^2
+ *                  + (e_2 e_4)^2 (df_3 - df_1)^2 + (e_3 e_4)^2 (df_2 - df_1)^2]
+ *                 / [(e_1 e_2 e_3)^2 + (e_1 e_2 e_4)^2 + (e_1 e_3 e_4)^2 + (e_2 e_3 e_4)^2].
+ * The weights of the numerator and the denominators are formed on the host in double; each weight is rounded to float32 once and the
+ * denominator is passed as one float32 reciprocal (K = 2: of its root): dS = |df_1 - df_2| * rcp for K = 2, and for K = 3 and 4 the
+ * numerator's terms are added in the order written, multiplied by rcp, and the root is taken (float32, one rounding each).
+ * Two pixels of equal codes are 0 by definition and skip the arithmetic; any two greys give exactly 0, because their df_i are equal.
+ * Everything downstream of the value is avx_delta_e_u8's, unchanged: the record (0.5-wide bins with the last one open, the float64
+ * sum from per-chunk partials in index order, the largest value with its first pixel, beyond), the HEAT and PLAIN maps with the
+ * unfused float32 quantiser, the dim grey of A, the MAP and SIDE layouts, the optional float32 value plane ds_out, the buffers and
+ * their alignment, and the guarantee that a frame's record, map and values are bit-identical in any batch and at any alignment.
+ * AVX_ERR_INVALID (avx_last_error starts with this function's name) for everything avx_delta_e_u8 refuses, and for a NULL obs or one
+ * of the wrong struct_size, n_receptors outside 2..4, a negative or non-finite matrix entry, a row whose sum is 0 or not finite, a
+ * Weber fraction outside [0.01, 1] and a floor outside [1e-6, 0.1]; nothing is launched or written then. */
+typedef struct avx_receptor_desc {
+    uint32_t struct_size;  /* sizeof(avx_receptor_desc) */
+    int32_t n_receptors;   /* K: 2, 3 or 4 */
+    double matrix[12];     /* R, K rows of 3 on linear RGB, row-major */
+    double weber[4];       /* e_i */
+    double floor;          /* eps */
+} avx_receptor_desc;
+int avx_receptor_delta_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, const avx_receptor_desc* obs, int mode,
+                          float gain, float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* ds_out, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

@@ -1,6 +1,6 @@
-"""Time of the colour difference kernels (DESIGN §4.20, §4.21).  Not part of bench.py.
+"""Time of the colour difference kernels (DESIGN §4.20, §4.21, §4.25).  Not part of bench.py.
 
-  python tools/deltae_bench.py kernel [--reps 7] [--ppd 60 [--ppd 30 ...]]
+  python tools/deltae_bench.py kernel [--reps 7] [--ppd 60 [--ppd 30 ...]] [--observer Dog [--observer HoneyBee ...]]
       avx_delta_e_u8 on frames resident on the device, 4K and 1080p, batches of 8: records only (no map), the heat map, the heat map
       side by side, and records only on a pair whose upper half is identical (those pixels are 0 by definition and skip the
       arithmetic), interleaved in one process with avx_frame_metrics_u8(with_ssim = 1) on the same frames -- per repetition each form
@@ -10,6 +10,9 @@
       Each --ppd X adds avx_scielab_u8 at X pixels per degree to the same interleaved repetitions, records only and with the heat map
       (the row pass, the column pass and the final launch between one pair of events); its lines also carry the ratio to the plain dE
       records and the fused multiply-adds per pixel pair of the two filter passes, 28 (2 ceil(X / 2) + 1).
+      Each --observer NAME adds avx_receptor_delta_u8 for that observer (Weber fractions 0.05 each, 0.13,0.06,0.12 for HoneyBee: they
+      are kernel arguments and do not change the work) to the same interleaved repetitions: records only, with the heat map, and side
+      by side; its lines also carry the ratio to the plain dE form of the same outputs.
   python tools/deltae_bench.py command [--frames 32] [--reps 3] [--dir DIR] [--ppd X]
       Two 4K nv12 files of `frames` frames in DIR (default: /dev/shm when there is one, so they are read from and written to memory)
       through python -m animal_vision_amd.deltae's main(), --batch 8 --depth 2: no OUT (statistics only), heat into a raw nv12 file (the
@@ -42,7 +45,8 @@ def _pair(n, H, W, seed=0):
 
 
 def kernel(args):
-    from animal_vision_amd.metrics import DELTA_E_RECORD_BYTES, RECORD_BYTES, delta_e_launch, frame_metrics_launch, scielab_launch
+    from animal_vision_amd.metrics import (DELTA_E_RECORD_BYTES, RECORD_BYTES, delta_e_launch, frame_metrics_launch, observer_for, receptor_delta_launch,
+                                           scielab_launch)
     from animal_vision_amd.runtime import get_context
 
     ctx, n = get_context(), 8
@@ -59,10 +63,17 @@ def kernel(args):
         def filtered(ppd, d_map):
             return lambda: scielab_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, ppd=ppd, mode="heat", layout="map")
 
+        def receptor(obs, d_map, layout):
+            return lambda: receptor_delta_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, observer=obs, mode="heat", layout=layout)
+
         forms = [("records", route(d_b, None, "map")), ("heat map", route(d_b, d_out, "map")), ("heat side", route(d_b, d_out, "side")),
                  ("records, upper half identical", route(d_half, None, "map"))]
         for ppd in args.ppd or []:
             forms += [(f"scielab records, ppd {ppd:g}", filtered(ppd, None)), (f"scielab heat map, ppd {ppd:g}", filtered(ppd, d_out))]
+        for who in args.observer or []:
+            obs = observer_for(who, (0.13, 0.06, 0.12) if who == "HoneyBee" else (0.05, 0.05))
+            forms += [(f"receptor {who} {what}", receptor(obs, d_map, layout))
+                      for what, d_map, layout in (("records", None, "map"), ("heat map", d_out, "map"), ("heat side", d_out, "side"))]
         forms.append(("ssim record", lambda: frame_metrics_launch(ctx, d_a, d_b, n, H, W, d_metrics, ssim=True)))
         times = [[] for _ in forms]
         for _, r in forms:  # warm-up: code objects are loaded and the workspaces are sized here
@@ -81,6 +92,9 @@ def kernel(args):
             if form.startswith("scielab"):
                 fma = 28 * (2 * math.ceil(float(form.rsplit(" ", 1)[1]) / 2) + 1)  # 7 terms x 2 sides x 2 passes, per tap
                 line.update(over_plain_records=round(med / plain, 2), filter_fma_per_px=fma, filter_tflops=round(2 * fma * H * W / med * 1e-6, 2))
+            if form.startswith("receptor"):
+                same = {"records": 0, "map": 1, "side": 2}[form.rsplit(" ", 1)[1]]  # the plain dE form with the same outputs
+                line.update(over_plain_same_outputs=round(med / float(np.median(times[same])), 2))
             print(json.dumps(line), flush=True)
         for d in (d_a, d_b, d_half, d_out, d_rec, d_metrics):
             d.free()
@@ -127,6 +141,8 @@ def main():
     k = sub.add_parser("kernel")
     k.add_argument("--reps", type=int, default=7)
     k.add_argument("--ppd", type=float, action="append", default=None, help="add avx_scielab_u8 at this many pixels per degree (repeatable)")
+    k.add_argument("--observer", action="append", default=None, metavar="NAME",
+                   help="add avx_receptor_delta_u8 for this observer, a dichromat's display name or HoneyBee (repeatable)")
     c = sub.add_parser("command")
     c.add_argument("--frames", type=int, default=32)
     c.add_argument("--reps", type=int, default=3)

@@ -410,6 +410,8 @@ _SIGS = {
     "avx_delta_e_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp]),
     "avx_scielab_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp]),
     "avx_receptor_delta_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp]),
+    "avx_receptor_acuity_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), ctypes.c_double, _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp,
+                               _vp, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

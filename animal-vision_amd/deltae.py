@@ -49,7 +49,16 @@ whatever their brightness.  It is a per-pixel measure of the frames as given: it
 its meaning: the columns, the limits, --threshold, the modes, the layouts, all sources and sinks.  Without --observer nothing changes.
 
     python -m animal_vision_amd.deltae ripe.y4m unripe.y4m heat.y4m --observer Dog --weber 0.05,0.05 --layout side
-    python -m animal_vision_amd.deltae flower.y4m leaf.y4m --observer HoneyBee --weber 0.13,0.06,0.12 --csv bee.csv"""
+    python -m animal_vision_amd.deltae flower.y4m leaf.y4m --observer HoneyBee --weber 0.13,0.06,0.12 --csv bee.csv
+
+--acuity SIGMA|species, with --observer, puts the observer's acuity in front of the distance (AcuityView, Caves & Johnsen
+2018, then the receptor distance: the first two stages of QCPA): both frames are blurred in linear light by a Gaussian of SIGMA pixels
+before the catches are taken, so that detail the animal cannot resolve -- resampling, fine texture, noise -- counts for what is left of
+it.  `species` takes the blur the species' own rendering ends with (Dog 3.5, Cat 1.0, ...: the ten dichromats with a Gaussian acuity;
+the others are refused by name, with the reason); a number is in pixels of the frames as compared, after --scale, from 0.2 to 4.
+Everything else keeps its meaning; the dim grey and the A and B panels are the unfiltered frames.  Without --acuity nothing changes.
+
+    python -m animal_vision_amd.deltae full.y4m half.y4m --observer Dog --weber 0.05,0.05 --acuity species --max-p95 1"""
 from __future__ import annotations
 
 import argparse
@@ -61,8 +70,8 @@ from typing import Iterator, Optional, Sequence, Tuple
 import numpy as np
 
 from .metrics import (DELTA_E_DEFAULT_GAIN, DELTA_E_DEFAULT_THRESHOLD, DELTA_E_LAYOUTS, DELTA_E_MODES, DELTA_E_RECORD_BYTES, RECEPTOR_DEFAULT_FLOOR,
-                      DeltaE, check_delta_e_options, check_ppd, delta_e_launch, delta_e_records_from_bytes, observer_for, observer_names,
-                      receptor_delta_launch, scielab_launch)
+                      DeltaE, check_acuity, check_delta_e_options, check_ppd, delta_e_launch, delta_e_records_from_bytes, observer_for, observer_names,
+                      receptor_delta_launch, scielab_launch, species_acuity)
 from .pairs import (add_inputs, check_depth, check_inputs, check_stdin, exit_status, num, open_sink, opened, sink_format,  # noqa: F401
                     stream_map_pairs)
 from .video import add_input_options, add_output_options
@@ -96,6 +105,8 @@ class _DeltaEParser(argparse.ArgumentParser):
             for flag, v in (("--weber", args.weber), ("--floor", args.floor)):
                 if v is not None:
                     self.error(f"{flag} belongs to --observer NAME: without an observer there are no receptor classes")
+            if args.acuity is not None:
+                self.error("--acuity belongs to --observer NAME: the acuity is an observer's; dE00 at a viewing distance is --ppd")
             return None
         if args.weber is None:
             self.error("--observer needs --weber E1,E2[,E3]: the Weber fraction of each receptor class; there is no per-species table")
@@ -108,9 +119,21 @@ class _DeltaEParser(argparse.ArgumentParser):
         if args.observer not in observer_names():
             self.error(f"--observer: no receptor model on RGB for {args.observer!r}: the observers are {', '.join(observer_names())}")
         try:
-            return observer_for(args.observer, weber, RECEPTOR_DEFAULT_FLOOR if args.floor is None else args.floor)
+            observer = observer_for(args.observer, weber, RECEPTOR_DEFAULT_FLOOR if args.floor is None else args.floor)
         except ValueError as e:
             self.error(f"--weber / --floor: {e}")
+        if args.acuity is not None:
+            try:
+                args.acuity = species_acuity(args.observer) if args.acuity == "species" else check_acuity(self._sigma(args.acuity))
+            except ValueError as e:
+                self.error(f"--acuity: {e}")
+        return observer
+
+    def _sigma(self, text: str) -> float:
+        try:
+            return float(text)
+        except ValueError:
+            self.error(f"--acuity: a number of pixels, or `species` for the observer's own (got {text!r})")
 
     def parse_args(self, args=None, namespace=None):
         args = super().parse_args(args, namespace)
@@ -170,6 +193,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "Vorobyev et al. 2001)")
     ap.add_argument("--floor", type=float, default=None, metavar="EPS",
                     help=f"with --observer: added to every catch before the logarithm, from 1e-6 to 0.1 (default {RECEPTOR_DEFAULT_FLOOR:g})")
+    ap.add_argument("--acuity", default=None, metavar="SIGMA|species",
+                    help="with --observer: blur both frames in linear light by the observer's acuity, a Gaussian of SIGMA pixels of the frames as "
+                         "compared (0.2 to 4), before the distance is taken.  `species`: the blur the species' own rendering ends with (the ten "
+                         "dichromats with a Gaussian acuity, e.g. Dog 3.5).  Default: none, the distance per pixel")
     ap.add_argument("--layout", default=None, choices=list(DELTA_E_LAYOUTS), help="map (default): the map alone.  side: A | B | map, three times as wide")
     ap.add_argument("--csv", default=None, metavar="FILE",
                     help=f"write {CSV_HEADER} per frame here; without OUT the default is stdout, with OUT nothing is written unless this is given")
@@ -190,10 +217,13 @@ def stream_records(args, info: dict, fmt: Optional[str] = None) -> Iterator[Tupl
     is computed.  Otherwise it is RGB uint8 H x W x 3 (H x 3W x 3 with --layout side) when fmt is None, else the flat payload the
     device encoded it to ("i420", or a raw pixel format name).  info["hw"] is the output frames' (H, W) once the first item is there;
     info["longer"] names the input ("A" / "B") that had frames left over, when one had.  The loop is pairs.stream_map_pairs;
-    args.observer and args.ppd pick the launch: receptor_delta_launch with an observer, scielab_launch with ppd, else delta_e_launch."""
+    args.observer and args.ppd pick the launch: receptor_delta_launch with an observer (and args.acuity, when there is one), scielab_launch
+    with ppd, else delta_e_launch."""
     def launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, stream):
         kw = dict(mode=args.mode, gain=args.gain, threshold=args.threshold, layout=args.layout, stream=stream)
         if getattr(args, "observer", None) is not None:
+            if getattr(args, "acuity", None) is not None:
+                kw["acuity"] = args.acuity
             receptor_delta_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, observer=args.observer, **kw)
         elif getattr(args, "ppd", None) is None:
             delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, **kw)
@@ -242,7 +272,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     dt = time.perf_counter() - t0
     where = f" (frame {worst[1]}, pixel x {worst[2]} y {worst[3]})" if worst[0] else ""
     observer = getattr(args, "observer", None)
-    what = f"RNL dS ({observer.describe()})" if observer is not None else "dE" if args.ppd is None else f"S-CIELAB dE (ppd {args.ppd:g})"
+    acuity = getattr(args, "acuity", None)
+    blur = "" if acuity is None else f", acuity {acuity:g} px"
+    what = f"RNL dS ({observer.describe()}{blur})" if observer is not None else "dE" if args.ppd is None else f"S-CIELAB dE (ppd {args.ppd:g})"
     unit = "dS" if observer is not None else "dE"
     print(f"deltae: {frames} frames, mean {what} {num(sum_mean / frames) if frames else 'nan'}, largest {unit} {num(worst[0])}{where}, "
           f"{beyond} pixels beyond {args.threshold:g}, {frames / dt if dt > 0 else 0.0:.1f} fps", file=sys.stderr)

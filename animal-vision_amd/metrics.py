@@ -29,7 +29,9 @@ Receptor-noise-limited distance (csrc/receptor.hip; Vorobyev & Os
 animal with these receptor classes and these Weber fractions tell the two colours apart, and where.  An Observer is a K x 3 matrix on
 linear RGB with K Weber fractions (observer_for builds the one of a dichromat species or of HoneyBee); receptor_delta_launch,
 receptor_delta, receptor_delta_map and receptor_delta_values return dS in just-noticeable differences in the same DeltaE records, maps
-and value planes; `deltae --observer` is the command."""
+and value planes; `deltae --observer` is the command.  With acuity=SIGMA (csrc/receptor_acuity.hip) both frames are first
+blurred in linear light by the observer's acuity, a Gaussian of SIGMA pixels -- species_acuity gives the one a species' own rendering
+uses --, so that what the animal cannot resolve counts for little; `deltae --acuity` is the command."""
 from __future__ import annotations
 
 import ctypes
@@ -716,7 +718,7 @@ def delta_e_records_from_bytes(buf: np.ndarray, n_frames: int) -> List[DeltaE]:
             for r in _records(buf, n_frames, DELTA_E_RECORD_BYTES, _DELTA_E_DTYPE)]
 
 
-def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_float, ppd=None, observer=None):
+def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_float, ppd=None, observer=None, acuity=None):
     """delta_e, delta_e_map, delta_e_values and their scielab (with ppd) and receptor_delta (with observer) counterparts: the stack in
     chunks of at most 16 frames -> (maps or None, records, values or None)."""
     N, H, W = a.shape[:3]
@@ -728,7 +730,7 @@ def _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, with_map, with_flo
     def per_chunk(ctx, i, n, d_a, d_b, d_rec, d_map, d_val):
         if observer is not None:
             receptor_delta_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, observer=observer, mode=mode, gain=gain, threshold=threshold, layout=layout,
-                                  d_float=d_val)
+                                  d_float=d_val, acuity=acuity)
         elif ppd is None:
             delta_e_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, mode=mode, gain=gain, threshold=threshold, layout=layout, d_float=d_val)
         else:
@@ -930,43 +932,111 @@ def _check_observer(observer) -> Observer:
     return observer
 
 
+# ------------------------------------------------------------------------------------------------ the observer's acuity
+ACUITY_MIN_SIGMA, ACUITY_MAX_SIGMA = 0.2, 4.0
+ACUITY_MAX_KSIZE = 33  # AVX_MAX_KSIZE
+
+
+def check_acuity(sigma) -> float:
+    """sigma -- the observer's acuity as the standard deviation of a Gaussian, in pixels of the frames as compared -- as the number the
+    library takes, after avx_receptor_acuity_u8's check: finite, from 0.2 to 4, which keeps the cvRound(8 sigma + 1) | 1 taps at or
+    below 33.  ValueError naming it otherwise."""
+    from .dichromat import cv_auto_ksize
+
+    if not _real(sigma) or not (math.isfinite(sigma) and ACUITY_MIN_SIGMA <= sigma <= ACUITY_MAX_SIGMA):
+        raise ValueError(f"acuity must be a finite number of pixels from {ACUITY_MIN_SIGMA:g} to {ACUITY_MAX_SIGMA:g} (got {sigma!r})")
+    k = cv_auto_ksize(float(sigma))
+    if not 3 <= k <= ACUITY_MAX_KSIZE:
+        raise ValueError(f"acuity {sigma!r} needs {k} taps: 3 to {ACUITY_MAX_KSIZE} are supported")
+    return float(sigma)
+
+
+def acuity_taps(sigma) -> np.ndarray:
+    """The taps avx_receptor_acuity_u8 forms for `sigma`: dichromat.gaussian_taps(dichromat.cv_auto_ksize(sigma), sigma) -- what the
+    species' own rendering blurs with -- formed in float64 and rounded once to float32."""
+    from .dichromat import cv_auto_ksize, gaussian_taps
+
+    sigma = check_acuity(sigma)
+    return gaussian_taps(cv_auto_ksize(sigma), sigma).astype(np.float32)
+
+
+def species_acuity(name: str) -> float:
+    """The sigma, in pixels, of the Gaussian a species' own rendering ends with (its DichromatSpec: post == "gauss"): Dog 3.5, Squirrel
+    0.7, Elephant 1.8, Lion 1.2, Tiger 1.2, Bear 1.6, Wolf 1.4, Fox 1.3, Raccoon 2.0, Cat 1.0.  ValueError, by name and with the reason,
+    for every other observer: for those the caller gives a number."""
+    from .animals._dichromats import _Dichromat
+    from .gallery import species_class
+
+    if not isinstance(name, str) or name not in observer_names():
+        raise ValueError(f"no receptor model on RGB for {name!r}: the observers are {', '.join(observer_names())}")
+    cls = species_class(name)
+    if not issubclass(cls, _Dichromat):
+        raise ValueError(f"{name} has no acuity blur: its rendering ends without one; give the acuity as a number of pixels")
+    spec = cls.SPEC
+    if spec.post == "scone":
+        raise ValueError(f"{name} has no acuity blur: its rendering ends with a gain per image row; give the acuity as a number of pixels")
+    if spec.post == "streak":
+        raise ValueError(f"{name} has no single acuity: the blur of its visual streak is anisotropic and differs per image row; give the acuity as a "
+                         "number of pixels")
+    if spec.post != "gauss":
+        raise ValueError(f"{name} has no acuity blur (post stage {spec.post!r}); give the acuity as a number of pixels")
+    return check_acuity(float(spec.sigma))
+
+
 def receptor_delta_launch(ctx: Context, d_a: DeviceBuffer, d_b: DeviceBuffer, n_frames: int, H: int, W: int, d_map: Optional[DeviceBuffer],
                           d_rec: DeviceBuffer, *, observer: Observer, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD,
-                          layout: str = "map", d_float: Optional[DeviceBuffer] = None, stream=None) -> None:
+                          layout: str = "map", d_float: Optional[DeviceBuffer] = None, stream=None, acuity=None) -> None:
     """delta_e_launch with the receptor-noise-limited distance dS of `observer` in place of dE00: the same buffers, records and map;
-    the threshold is in just-noticeable differences.  Nothing is downloaded and nothing waits."""
+    the threshold is in just-noticeable differences.  acuity: None, the distance per pixel of the frames as given; a number (0.2 .. 4),
+    the sigma in pixels of the Gaussian both frames are blurred with, in linear light, before the catches are taken
+    (avx_receptor_acuity_u8).  Nothing is downloaded and nothing waits."""
     _check_call(n_frames, H, W, d_a, d_b)
     desc = _check_observer(observer).desc()
     g, t = _check_delta_e_buffers(n_frames, H, W, d_map, d_rec, d_float, mode, gain, threshold, layout)
+    if acuity is not None:
+        sigma = check_acuity(acuity)
+        ctx._check(lib.avx_receptor_acuity_u8(ctx._h, d_a.ptr, d_b.ptr, int(n_frames), int(H), int(W), ctypes.byref(desc), sigma,
+                                              AVX_DELTA_E_MODES[mode], g, t, AVX_DELTA_E_LAYOUTS[layout], None if d_map is None else d_map.ptr, d_rec.ptr,
+                                              None if d_float is None else d_float.ptr, ctx._s(stream)))
+        return
     ctx._check(lib.avx_receptor_delta_u8(ctx._h, d_a.ptr, d_b.ptr, int(n_frames), int(H), int(W), ctypes.byref(desc), AVX_DELTA_E_MODES[mode], g, t,
                                          AVX_DELTA_E_LAYOUTS[layout], None if d_map is None else d_map.ptr, d_rec.ptr,
                                          None if d_float is None else d_float.ptr, ctx._s(stream)))
 
 
-def receptor_delta(a, b, observer: Observer, threshold=DELTA_E_DEFAULT_THRESHOLD, *, ctx: Optional[Context] = None):
+def _check_acuity_option(acuity) -> Optional[float]:
+    return None if acuity is None else check_acuity(acuity)
+
+
+def receptor_delta(a, b, observer: Observer, threshold=DELTA_E_DEFAULT_THRESHOLD, *, acuity=None, ctx: Optional[Context] = None):
     """How far apart `observer` sees a and b: uint8 sRGB H x W x 3 -> the DeltaE record of dS (just-noticeable differences), or
     N x H x W x 3 -> a list of N; no map is computed.  The measure is chromatic: two greys are 0 apart whatever their brightness.
+    acuity: None, or the sigma in pixels of the observer's acuity blur (receptor_delta_launch; species_acuity(name) for a species' own).
     ValueError for a bad option or shape before any device work."""
     a, b, batched = check_pair(a, b)
     _check_observer(observer)
+    acuity = _check_acuity_option(acuity)
     check_delta_e_options("heat", None, threshold, "map")
-    recs = _delta_e_chunks(a, b, "heat", None, threshold, "map", ctx, False, False, observer=observer)[1]
+    recs = _delta_e_chunks(a, b, "heat", None, threshold, "map", ctx, False, False, observer=observer, acuity=acuity)[1]
     return recs if batched else recs[0]
 
 
 def receptor_delta_map(a, b, observer: Observer, *, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map",
-                       ctx: Optional[Context] = None):
-    """delta_e_map of dS as `observer` sees it: (the map, its DeltaE record), or (N maps, a list of N records)."""
+                       acuity=None, ctx: Optional[Context] = None):
+    """delta_e_map of dS as `observer` sees it: (the map, its DeltaE record), or (N maps, a list of N records).  With an acuity the dim
+    grey and the A and B panels are still the unfiltered frames'."""
     a, b, batched = check_pair(a, b)
     _check_observer(observer)
+    acuity = _check_acuity_option(acuity)
     check_delta_e_options(mode, gain, threshold, layout)
-    maps, recs, _ = _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, True, False, observer=observer)
+    maps, recs, _ = _delta_e_chunks(a, b, mode, gain, threshold, layout, ctx, True, False, observer=observer, acuity=acuity)
     return (maps, recs) if batched else (maps[0], recs[0])
 
 
-def receptor_delta_values(a, b, observer: Observer, *, ctx: Optional[Context] = None) -> np.ndarray:
+def receptor_delta_values(a, b, observer: Observer, *, acuity=None, ctx: Optional[Context] = None) -> np.ndarray:
     """delta_e_values of dS as `observer` sees it: float32 H x W or N x H x W."""
     a, b, batched = check_pair(a, b)
     _check_observer(observer)
-    vals = _delta_e_chunks(a, b, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True, observer=observer)[2]
+    acuity = _check_acuity_option(acuity)
+    vals = _delta_e_chunks(a, b, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True, observer=observer, acuity=acuity)[2]
     return vals if batched else vals[0]

@@ -682,6 +682,40 @@ typedef struct avx_receptor_desc {
 int avx_receptor_delta_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, const avx_receptor_desc* obs, int mode,
                           float gain, float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* ds_out, void* stream);
 
+/* The receptor-noise-limited distance behind the observer's acuity blur (csrc/receptor_acuity.hip; AcuityView, Caves &
+ * Johnsen 2018, followed by the distance above -- the first two stages of QCPA, van den Berg et al. 2020): avx_receptor_delta_u8 with
+ * one more argument, sigma, the observer's acuity as the standard deviation of a Gaussian in pixels of the frames as given.  Both
+ * frames are blurred in linear light before the catches are taken, so that differences too fine for the observer to resolve count
+ * for little.  Buffers, n_frames (1..16), mode, gain, threshold, layout, map_out, rec_dev, ds_out, the record, the quantiser, the
+ * palette and the errors are those of avx_delta_e_u8, the observer is avx_receptor_delta_u8's; the dim grey of the heat mode and the A
+ * and B panels of the side layout are the unfiltered frames', as in avx_scielab_u8.  Per pixel:
+ *   Decode: (r, g, b) = lin[code] with avx_delta_e_u8's 256-entry float32 table, for every pixel of A and of B.
+ *   Taps: k = cvRound(8 sigma + 1) | 1 and t = cv::getGaussianKernel(k, sigma), t_i = exp(-(i - (k - 1) / 2)^2 / (2 sigma^2)) over their
+ *       sum added left to right: the taps a species' own rendering uses (AVX_POST_GAUSS).  t is formed in double and rounded once to
+ *       float32.  3 <= k <= AVX_MAX_KSIZE, which holds for 0.2 <= sigma <= 4; the radius is R = (k - 1) / 2 <= 16.
+ *   Blur: each of the three linear planes of each side is blurred separably, rows (along x) first, then columns.  A sum over the taps
+ *       is formed in index order in float32: s_0 = t_0 x_0 (one rounding), s_j = fma(t_j, x_j, s_(j-1)) -- the plain form, not OpenCV's
+ *       symmetric-pair form.
+ *   Border: BORDER_REFLECT_101, folded as often as needed, so that any frame size is legal: with p = 2 (n - 1) and
+ *       m = ((i mod p) + p) mod p the index is m where m < n, else p - m; n = 1 gives 0.  Frames smaller than the radius, 1 x 1
+ *       included, are legal.
+ *   Catches: on the blurred values (r~, g~, b~) in the anchored form of avx_receptor_delta_u8: q_i = (g~ + R'_i0 (r~ - g~)) +
+ *       R'_i2 (b~ - g~).
+ *   Distance: df_i = logf((q_iA + eps) / (q_iB + eps)), and dS follows for K = 2, 3, 4 exactly as written for avx_receptor_delta_u8,
+ *       with the same constants formed on the host in double.  There is NO "equal codes skip" rule here: the value of a pixel depends
+ *       on its neighbourhood.
+ * What follows from it: both sides run the same operations in the same order, so a pixel whose reflected (2R + 1)^2 neighbourhood is
+ * the same in A and B is exactly 0; identical frames give an all-zero record and a black PLAIN map; any two frames of greys are exactly
+ * 0 apart everywhere (the three blurred planes are equal, so every q_i = g~ and all df_i are equal).  A frame's record, map and values
+ * do not depend on its batch, its place in the batch, the alignment of the buffers or the run: counts are integers, and the float64 sum
+ * is formed from per-workgroup partials (a workgroup owns a 64 x 32 tile, a thread adds its pixels from the top down) added in an
+ * order that is a function of H and W alone, without float atomics.  The call needs no scratch planes: 8 bytes of workspace a tile.
+ * AVX_ERR_INVALID (avx_last_error starts with this function's name) for everything avx_receptor_delta_u8 refuses, and for a sigma that
+ * is not finite or outside [0.2, 4]; nothing is launched or written then. */
+int avx_receptor_acuity_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, const avx_receptor_desc* obs,
+                           double sigma, int mode, float gain, float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* ds_out,
+                           void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

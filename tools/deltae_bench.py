@@ -1,6 +1,7 @@
-"""Time of the colour difference kernels (DESIGN §4.20, §4.21, §4.25).  Not part of bench.py.
+"""Time of the colour difference kernels (DESIGN §4.20, §4.21, §4.25, §4.26).  Not part of bench.py.
 
   python tools/deltae_bench.py kernel [--reps 7] [--ppd 60 [--ppd 30 ...]] [--observer Dog [--observer HoneyBee ...]]
+                                      [--acuity species [--acuity 1.0 ...]]
       avx_delta_e_u8 on frames resident on the device, 4K and 1080p, batches of 8: records only (no map), the heat map, the heat map
       side by side, and records only on a pair whose upper half is identical (those pixels are 0 by definition and skip the
       arithmetic), interleaved in one process with avx_frame_metrics_u8(with_ssim = 1) on the same frames -- per repetition each form
@@ -13,6 +14,11 @@
       Each --observer NAME adds avx_receptor_delta_u8 for that observer (Weber fractions 0.05 each, 0.13,0.06,0.12 for HoneyBee: they
       are kernel arguments and do not change the work) to the same interleaved repetitions: records only, with the heat map, and side
       by side; its lines also carry the ratio to the plain dE form of the same outputs.
+      Each --acuity SIGMA|species adds avx_receptor_acuity_u8 at that sigma for every --observer (`species`: the observer's own,
+      skipped with a note for an observer without a Gaussian acuity) to the same interleaved repetitions, records only and with the
+      heat map; its lines also carry the ratio to the observer's per-pixel records, the taps, and the fused multiply-adds per pixel pair
+      of the two blur passes by arithmetic -- 6 planes x k taps x (1 + (32 + 2R) / 32): the column pass, and the row pass on the tile's
+      32 rows and its 2R halo rows -- with the rate they imply.
   python tools/deltae_bench.py command [--frames 32] [--reps 3] [--dir DIR] [--ppd X]
       Two 4K nv12 files of `frames` frames in DIR (default: /dev/shm when there is one, so they are read from and written to memory)
       through python -m animal_vision_amd.deltae's main(), --batch 8 --depth 2: no OUT (statistics only), heat into a raw nv12 file (the
@@ -45,8 +51,9 @@ def _pair(n, H, W, seed=0):
 
 
 def kernel(args):
-    from animal_vision_amd.metrics import (DELTA_E_RECORD_BYTES, RECORD_BYTES, delta_e_launch, frame_metrics_launch, observer_for, receptor_delta_launch,
-                                           scielab_launch)
+    from animal_vision_amd.dichromat import cv_auto_ksize
+    from animal_vision_amd.metrics import (DELTA_E_RECORD_BYTES, RECORD_BYTES, check_acuity, delta_e_launch, frame_metrics_launch, observer_for,
+                                           receptor_delta_launch, scielab_launch, species_acuity)
     from animal_vision_amd.runtime import get_context
 
     ctx, n = get_context(), 8
@@ -66,6 +73,9 @@ def kernel(args):
         def receptor(obs, d_map, layout):
             return lambda: receptor_delta_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, observer=obs, mode="heat", layout=layout)
 
+        def blurred(obs, sigma, d_map):
+            return lambda: receptor_delta_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, observer=obs, mode="heat", layout="map", acuity=sigma)
+
         forms = [("records", route(d_b, None, "map")), ("heat map", route(d_b, d_out, "map")), ("heat side", route(d_b, d_out, "side")),
                  ("records, upper half identical", route(d_half, None, "map"))]
         for ppd in args.ppd or []:
@@ -74,6 +84,13 @@ def kernel(args):
             obs = observer_for(who, (0.13, 0.06, 0.12) if who == "HoneyBee" else (0.05, 0.05))
             forms += [(f"receptor {who} {what}", receptor(obs, d_map, layout))
                       for what, d_map, layout in (("records", None, "map"), ("heat map", d_out, "map"), ("heat side", d_out, "side"))]
+            for text in args.acuity or []:
+                try:
+                    sigma = species_acuity(who) if text == "species" else check_acuity(float(text))
+                except ValueError as e:
+                    print(f"deltae_bench: --acuity {text} skipped for {who}: {e}", file=sys.stderr)
+                    continue
+                forms += [(f"acuity {who} sigma {sigma:g} records", blurred(obs, sigma, None)), (f"acuity {who} sigma {sigma:g} heat map", blurred(obs, sigma, d_out))]
         forms.append(("ssim record", lambda: frame_metrics_launch(ctx, d_a, d_b, n, H, W, d_metrics, ssim=True)))
         times = [[] for _ in forms]
         for _, r in forms:  # warm-up: code objects are loaded and the workspaces are sized here
@@ -95,6 +112,13 @@ def kernel(args):
             if form.startswith("receptor"):
                 same = {"records": 0, "map": 1, "side": 2}[form.rsplit(" ", 1)[1]]  # the plain dE form with the same outputs
                 line.update(over_plain_same_outputs=round(med / float(np.median(times[same])), 2))
+            if form.startswith("acuity"):
+                who, sigma = form.split(" ")[1], float(form.split(" ")[3])
+                k = cv_auto_ksize(sigma)
+                fma = 6 * k * (1 + (32 + (k - 1)) / 32)
+                base = [t2 for (f2, _), t2 in zip(forms, times) if f2 == f"receptor {who} records"][0]
+                line.update(over_receptor_records=round(med / float(np.median(base)), 2), taps=k, blur_fma_per_px=round(fma, 1),
+                            blur_tflops=round(2 * fma * H * W / med * 1e-6, 2))
             print(json.dumps(line), flush=True)
         for d in (d_a, d_b, d_half, d_out, d_rec, d_metrics):
             d.free()
@@ -143,6 +167,8 @@ def main():
     k.add_argument("--ppd", type=float, action="append", default=None, help="add avx_scielab_u8 at this many pixels per degree (repeatable)")
     k.add_argument("--observer", action="append", default=None, metavar="NAME",
                    help="add avx_receptor_delta_u8 for this observer, a dichromat's display name or HoneyBee (repeatable)")
+    k.add_argument("--acuity", action="append", default=None, metavar="SIGMA|species",
+                   help="add avx_receptor_acuity_u8 at this sigma in pixels, or at each observer's own, for every --observer (repeatable)")
     c = sub.add_parser("command")
     c.add_argument("--frames", type=int, default=32)
     c.add_argument("--reps", type=int, default=3)

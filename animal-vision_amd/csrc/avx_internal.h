@@ -112,6 +112,15 @@ int avx_geom_area_tables(avx_ctx* ctx, avx_ws* ws, hipStream_t s, int H, int W, 
 int avx_metrics_scale0_launch(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, double* partials,
                               avx_frame_metrics* out_dev, avx_ms_ssim_rec* ms, hipStream_t s);
 size_t avx_metrics_scale0_tiles(int H, int W);
+// uv.hip: the UV path's small per-stream scratch (ws->uv_small), zero at rest where the kernels need it so: one set of radix-select histograms
+// (kSelMax x 2048 bins), kSelMax select states, the ticket block (ticket_is_last's 1 + 32 counters; word 56: k_sel_pass_up's candidate count), 16 percentiles.
+struct Stat3;
+struct SelState;
+struct UvScratch { Stat3* partials; float4* stats; uint32_t* hist; SelState* sel; uint32_t* ticket; double* pct; float* mat; };
+int uv_small_scratch(avx_ctx* ctx, hipStream_t stream, UvScratch* s, avx_ws** out_ws = nullptr);
+// select.hip: exact np.percentile(x, q) (linear interpolation) of n device floats -> *out_dev, any count of requests, four per set of radix passes
+struct PctReq { const float* x; size_t n; double q; double* out_dev; };
+int run_percentiles(avx_ctx* ctx, const UvScratch& u, const PctReq* req, int count, hipStream_t s);
 
 #define AVX_HIP(ctx, call)                                                                         \
     do {                                                                                            \

@@ -67,14 +67,11 @@ __device__ __forceinline__ void cat_merge_stage(float c0, float c1, float c2, co
 // with it); here a workgroup arrives at counter 1 + (block % kTicketFan) and only the one that completes its group goes on to counter 0: <= nblocks / 32 + 32 arrivals
 // deep.  Called by ONE thread of each workgroup after its own stores have completed (s_waitcnt vmcnt(0)); tk: 1 + kTicketFan words, zero at rest and left zero.
 constexpr unsigned kTicketFan = 32;
-// reuse: the counters are used again INSIDE the same launch (k_sel_all): a group's reset is then waited for before its finisher moves on (between launches the kernel
-// boundary orders it).
-__device__ __forceinline__ bool ticket_is_last(uint32_t* tk, unsigned block, unsigned nblocks, bool reuse = false) {
+__device__ __forceinline__ bool ticket_is_last(uint32_t* tk, unsigned block, unsigned nblocks) {
     const unsigned fan = nblocks < kTicketFan ? nblocks : kTicketFan, grp = block % kTicketFan;
     const unsigned gsize = (nblocks - grp + kTicketFan - 1) / kTicketFan;  // blocks b < nblocks with b % kTicketFan == grp
     if (__hip_atomic_fetch_add(&tk[1 + grp], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != gsize - 1) return false;
     __hip_atomic_store(&tk[1 + grp], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (reuse) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (__hip_atomic_fetch_add(&tk[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != fan - 1) return false;
     __hip_atomic_store(&tk[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return true;

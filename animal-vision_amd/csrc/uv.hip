@@ -16,6 +16,7 @@
 #include <hip/hip_fp16.h>
 
 #include "dichromat_common.h"
+#include "radix_select.h"
 #include "stack_up.h"
 
 using namespace avxk;
@@ -23,9 +24,12 @@ using namespace avxk;
 // geom.hip: the INTER_LINEAR tables of an h x w -> H x W resize out of the stream workspace's table cache (TableCache::lin)
 int avx_geom_linear_tables(avx_ctx* ctx, avx_ws* ws, hipStream_t s, int H, int W, int Hd, int Wd, avx_lin_tab* ax, avx_lin_tab* ay);
 
+// Per-block partial {min, max, sum} of up to 16 planes -> partials[block][k][3] (sum kept in double).
+struct Stat3 { float mn, mx; double sum; };
+
 namespace {
 
-constexpr int kT = 256;
+constexpr int kT = kSelT;
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -42,9 +46,6 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
-
-// Per-block partial {min, max, sum} of up to 16 planes -> partials[block][k][3] (sum kept in double).
-struct Stat3 { float mn, mx; double sum; };
 
 template <int KMAX>
 __device__ __forceinline__ void block_stats_store(const float (&mn)[KMAX], const float (&mx)[KMAX], const double (&sm)[KMAX], int K,
@@ -534,161 +535,6 @@ static int launch_plane_blur(avx_ctx* ctx, const BlurArgs& a, hipStream_t s, int
     return AVX_OK;
 }
 
-// ---- exact order statistic: 3-pass radix select on order-preserving keys ---------------------------
-struct SelState {
-    uint32_t prefix, mask;      // key bits fixed so far
-    unsigned long long rank;    // remaining 0-based rank inside the selected prefix
-    uint32_t key_lo, key_hi;    // results: key of x[k] and of x[k+1]
-    uint32_t cnt_in_bin;        // size of the finally selected bin (duplicates of x[k])
-    uint32_t next_key;          // smallest key > key_lo
-    uint32_t next_above;        // smallest key above the selected 22-bit prefix range (last histogram pass)
-};
-
-__device__ __forceinline__ uint32_t f2key(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// One launch per radix pass.  Every workgroup histograms its share in LDS and flushes the non-empty bins with global
-// atomics; the LAST workgroup to finish (ticket counter behind an agent-scope fence) picks the bin that holds the rank,
-// narrows the prefix, re-zeroes the histogram and the ticket, and -- on the last pass -- resolves the successor key
-// and performs NumPy's float32 lerp.  Pass 0 takes its state from the arguments: no init launch, no memset.
-constexpr int kSelMax = 4;  // order statistics resolved together by one set of passes
-struct SelJob { const float* x; size_t n; unsigned long long rank0; float gamma; int has_next; double* out; };
-struct SelPass { int n_jobs, pass, shift, bits; SelState* st; uint32_t* hist; uint32_t* ticket; SelJob job[kSelMax];
-                 size_t x_frame_stride; int out_frame_stride; };  // blockIdx.y = frame: job arrays x_frame_stride floats apart, results out_frame_stride doubles apart, kSelMax states / histograms and one ticket per frame
-
-// NJ percentiles per launch: the data pass walks the NJ arrays one after the other into NJ LDS histograms, and the
-// last workgroup picks for each in turn -- the per-launch fixed costs (LDS clear / flush, ticket, tail latency)
-// are paid once, which is most of the time of a pass at 1080p.
-template <bool AG>
-__device__ void sel_pick_t(uint32_t* hist, SelState* st, int pass, int shift, int bits, unsigned long long rank0, float gamma, int has_next, double* out,
-                           uint32_t prefix0, uint32_t mask0);
-__device__ __forceinline__ void sel_pick(uint32_t* hist, SelState* st, int pass, int shift, int bits, unsigned long long rank0, float gamma, int has_next, double* out,
-                                         uint32_t prefix0 = 0u, uint32_t mask0 = 0u) {
-    sel_pick_t<false>(hist, st, pass, shift, bits, rank0, gamma, has_next, out, prefix0, mask0);
-}
-
-template <int NJ>
-__global__ __launch_bounds__(kT) void k_sel_pass(const SelPass a_in) {
-    SelPass a = a_in;
-    {   // frame of this workgroup (gridDim.y == 1: the plain single-array form)
-        const int f = blockIdx.y;
-        a.st += (size_t)f * kSelMax; a.hist += (size_t)f * kSelMax * 2048; a.ticket += f;
-        for (int j = 0; j < kSelMax; ++j) { a.job[j].x += (size_t)f * a.x_frame_stride; a.job[j].out += (size_t)f * a.out_frame_stride; }
-    }
-    __shared__ uint32_t h[NJ][2048];
-    __shared__ uint32_t wmin[kT / 64];
-    __shared__ int is_last;
-    const int nb = 1 << a.bits, t = threadIdx.x;
-    const bool last_pass = a.pass == 2;
-    // The first eight 16-byte vectors of a thread's share of job j (all of it for a 1080p plane at one workgroup per CU): fetched a
-    // job AHEAD -- job 0's while the histograms are cleared, job j + 1's before job j is visited -- so the jobs' memory round trips
-    // overlap instead of adding up (a pass over four planes was four dependent round trips).
-    const size_t stride = (size_t)gridDim.x * kT, i0 = (size_t)blockIdx.x * kT + t;
-    auto job_vec = [&](int j, const float4*& xv, size_t& nvec, size_t& head, size_t& tail0) {
-        const SelJob jb = a.job[j];
-        const size_t mis = ((16 - ((uintptr_t)jb.x & 15)) & 15) / 4;
-        head = mis < jb.n ? mis : jb.n;
-        nvec = (jb.n - head) / 4; tail0 = head + nvec * 4;
-        xv = reinterpret_cast<const float4*>(jb.x + head);
-    };
-    auto fetch8 = [&](int j, float4 (&v)[8]) {
-        const float4* xv; size_t nvec, head, tail0;
-        job_vec(j, xv, nvec, head, tail0);
-        if (nvec == 0) return;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { const size_t idx = i0 + q * stride; v[q] = xv[idx < nvec ? idx : nvec - 1]; }
-    };
-    float4 cur[8], nxt[8];
-    fetch8(0, cur);
-    for (int i = t; i < NJ * 2048; i += kT) (&h[0][0])[i] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if (j >= a.n_jobs) break;
-        if (j + 1 < NJ && j + 1 < a.n_jobs) fetch8(j + 1 < NJ ? j + 1 : j, nxt);
-        const SelJob jb = a.job[j];
-        SelState* st = a.st + j;
-        const bool find_next = last_pass && jb.has_next;
-        const uint32_t prefix = a.pass == 0 ? 0u : st->prefix, mask = a.pass == 0 ? 0u : st->mask;
-        const uint32_t above = prefix | ~mask;  // largest key with this prefix
-        uint32_t best = 0xffffffffu;
-        // Run-length combining: neighbouring samples of a frame usually share a bin (always, nearly, in the first pass, where a bin is a
-        // quarter of a binade), and 64 lanes adding 1 to the same LDS word serialise -- a thread keeps (bin, count) of its current run and
-        // issues one atomic per run instead of one per sample.
-        uint32_t run_bin = 0xffffffffu, run_cnt = 0;
-        auto visit = [&](float f) {
-            const uint32_t k = f2key(f);
-            if ((k & mask) == prefix) {
-                const uint32_t b = (k >> a.shift) & (nb - 1);
-                if (b == run_bin) { ++run_cnt; }
-                else {
-                    if (run_cnt) atomicAdd(&h[j][run_bin], run_cnt);
-                    run_bin = b; run_cnt = 1;
-                }
-            } else if (find_next && k > above && k < best) best = k;  // successor candidates outside the 22-bit prefix
-        };
-        // 16-byte loads over the aligned body; the (<= 3 + 3) head / tail elements go to the first threads of block 0
-        const float4* xv; size_t nvec, head, tail0;
-        job_vec(j, xv, nvec, head, tail0);
-        // first batch: already here (cur); further batches (frames beyond 8 vectors per thread): eight loads in flight each, the ragged
-        // end included (clamped index, masked visit)
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            if (i0 + q * stride < nvec) { visit(cur[q].x); visit(cur[q].y); visit(cur[q].z); visit(cur[q].w); }
-        for (size_t i = i0 + 8 * stride; i < nvec; i += 8 * stride) {
-            float4 v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { const size_t idx = i + q * stride; v[q] = xv[idx < nvec ? idx : nvec - 1]; }
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if (i + q * stride < nvec) { visit(v[q].x); visit(v[q].y); visit(v[q].z); visit(v[q].w); }
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) cur[q] = nxt[q];
-        if (blockIdx.x == 0) {
-            if ((size_t)t < head) visit(jb.x[t]);
-            if (tail0 + t < jb.n && t < 4) visit(jb.x[tail0 + t]);
-        }
-        if (run_cnt) atomicAdd(&h[j][run_bin], run_cnt);
-        if (find_next) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(best, o); best = v < best ? v : best; }
-            __syncthreads();
-            if ((t & 63) == 0) wmin[t >> 6] = best;
-            __syncthreads();
-            if (t == 0) {
-                for (int w = 1; w < kT / 64; ++w) best = wmin[w] < best ? wmin[w] : best;
-                if (best != 0xffffffffu) atomicMin(&st->next_above, best);
-            }
-        }
-    }
-    __syncthreads();
-    for (int j = 0; j < a.n_jobs; ++j)
-        for (int i = t; i < nb; i += kT)
-            if (h[j][i]) atomicAdd(&a.hist[j * 2048 + i], h[j][i]);
-    // ---- last workgroup: pick ------------------------------------------------------------------------------------
-    // Everything the workgroups exchange travels in agent-scope atomics (histogram, successor key, ticket) and is
-    // read back with agent-scope atomic loads, so no cache write-back / invalidate (__threadfence: a whole-L2 flush
-    // per workgroup on this multi-XCD part) is needed: only this wave's atomics must have been performed before
-    // the ticket is taken.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    // one word per frame in the batched form (blockIdx.y = frame); the single-array form owns the whole ticket block and arrives through the two-level ticket
-    if (t == 0) is_last = gridDim.y > 1 ? atomicAdd(a.ticket, 1u) == gridDim.x - 1 : avxk::ticket_is_last(a.ticket, blockIdx.x, gridDim.x);
-    __syncthreads();
-    if (!is_last) return;
-    for (int j = 0; j < a.n_jobs; ++j) {
-        const SelJob jb = a.job[j];
-        sel_pick(a.hist + j * 2048, a.st + j, a.pass, a.shift, a.bits, jb.rank0, jb.gamma, jb.has_next, jb.out, 0u, 0u);
-    }
-    if (t == 0 && gridDim.y > 1) *a.ticket = 0;
-}
-
 // ---- opponent prep / maps / encode ------------------------------------------------------------------
 __global__ __launch_bounds__(kT) void k_opponent_prep(const float* __restrict__ UBG, size_t n, float* __restrict__ radius, float* __restrict__ L) {
     for (size_t i = (size_t)blockIdx.x * kT + threadIdx.x; i < n; i += (size_t)gridDim.x * kT) {
@@ -851,7 +697,7 @@ struct BeeArgs {
     int H, W; const float* lut; const float* mat; const float4* stats; int scale_mode; float t0, t1, t2;
     int mode, n_jobs, pass, shift, bits;
     SelState* st; uint32_t* hist; uint32_t* ticket; double* pct;          // per frame: kSelMax states, kSelMax x 2048 bins, 1 ticket, 8 doubles
-    unsigned long long rank0; float gamma; int has_next;
+    SelRank r;
     float eps; float M[9]; const float* enc_thr; const uint8_t* coarse; uint32_t lo_key;
     float* sel_planes;   // STAGE 0, pass 0: the values being selected are also written out, [frame][job][H*W] (passes 1-2 then read planes)
 };
@@ -886,226 +732,6 @@ __device__ __forceinline__ void map_rgb(int mode, float U, float B, float G, con
     }
 }
 
-// the last workgroup of a radix pass: pick the bin holding the rank, narrow the prefix, on the last pass resolve x[k], x[k+1] and
-// NumPy's float32 lerp (the logic of k_sel_pass's tail, for one job)
-// prefix0 / mask0: key bits every element is known to share before the first pass (0 / 0: none)
-// AG: the state travels between workgroups INSIDE one launch (k_sel_all): every field is read and written with agent-scope atomics (the L2 slices of the XCDs are not
-// coherent with each other for plain accesses before the kernel ends), and the histogram is left as it is (k_sel_all uses one per pass and clears them at its end).
-__device__ __forceinline__ uint32_t ld_ag(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_ag(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned long long ld_ag(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_ag(unsigned long long* p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <bool AG>
-__device__ void sel_pick_t(uint32_t* hist, SelState* st, int pass, int shift, int bits, unsigned long long rank0, float gamma, int has_next, double* out,
-                           uint32_t prefix0, uint32_t mask0) {
-    __shared__ unsigned long long csum[kT];
-    __shared__ int first_after[kT / 64];
-    __shared__ int sel_chunk, sel_bin;
-    __shared__ unsigned long long sel_rank;
-    __shared__ uint32_t sel_cnt;
-    const int nb = 1 << bits, t = threadIdx.x, per = nb / kT;
-    const bool last_pass = pass == 2;
-    const uint32_t prefix = pass == 0 ? prefix0 : (AG ? ld_ag(&st->prefix) : st->prefix), mask = pass == 0 ? mask0 : (AG ? ld_ag(&st->mask) : st->mask);
-    uint32_t loc[8];
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) loc[i] = i < per ? __hip_atomic_load(&hist[t * per + (i < per ? i : 0)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sum += loc[i];
-    // inclusive scan of the 256 chunk sums: within a wave by shuffles, across the four waves through LDS (two barriers; the
-    // Hillis-Steele form in LDS took sixteen, and the pick is pure latency on the critical path of every pass)
-    unsigned long long incl = sum;
-    {
-        const int lane = t & 63, wave = t >> 6;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long v = __shfl_up(incl, o);
-            if (lane >= o) incl += v;
-        }
-        __syncthreads();  // csum is free (a previous job's readers are done)
-        if (lane == 63) csum[wave] = incl;
-        if (t == 0) sel_chunk = kT - 1;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) incl += csum[w];
-    }
-    const unsigned long long r = pass == 0 ? rank0 : (AG ? ld_ag(&st->rank) : st->rank);
-    const unsigned long long excl = incl - sum;
-    if (excl <= r && r < incl) sel_chunk = t;
-    __syncthreads();
-    if (t == sel_chunk) {
-        unsigned long long cum = excl;
-        int i = 0;
-        for (; i < per; ++i) {
-            if (cum + loc[i] > r) break;
-            cum += loc[i];
-        }
-        if (i == per) i = per - 1;
-        const int b = t * per + i;
-        if constexpr (AG) {
-            st_ag(&st->prefix, prefix | ((uint32_t)b << shift));
-            st_ag(&st->mask, mask | ((uint32_t)(nb - 1) << shift));
-            st_ag(&st->rank, r - cum);
-            if (pass == 0) st_ag(&st->next_above, 0xffffffffu);
-        } else {
-            st->prefix = prefix | ((uint32_t)b << shift);
-            st->mask = mask | ((uint32_t)(nb - 1) << shift);
-            st->rank = r - cum;
-            if (pass == 0) st->next_above = 0xffffffffu;
-        }
-        if (last_pass) { st->key_lo = prefix | (uint32_t)b; st->cnt_in_bin = loc[i]; sel_bin = b; sel_rank = r - cum; sel_cnt = loc[i]; }
-    }
-    if (last_pass) {
-        __syncthreads();
-        int f = 0x7fffffff;
-        for (int i = per - 1; i >= 0; --i)
-            if (loc[i] && t * per + i > sel_bin) f = t * per + i;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const int v = __shfl_xor(f, o); f = v < f ? v : f; }
-        if ((t & 63) == 0) first_after[t >> 6] = f;
-        __syncthreads();
-        if (t == 0) {
-            int m = first_after[0];
-            for (int w = 1; w < kT / 64; ++w) m = first_after[w] < m ? first_after[w] : m;
-            const uint32_t next_above = __hip_atomic_load(&st->next_above, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t next_key = m != 0x7fffffff ? (prefix | (uint32_t)m) : next_above;
-            const uint32_t key_lo = prefix | (uint32_t)sel_bin;
-            const float lo = key2f(key_lo);
-            float hi = lo;
-            if (has_next && sel_rank + 1 >= sel_cnt) hi = next_key == 0xffffffffu ? lo : key2f(next_key);
-            const float diff = hi - lo;
-            float res = lo + diff * gamma;
-            if (gamma >= 0.5f) res = hi - diff * (1.0f - gamma);
-            *out = (double)res;
-        }
-    }
-    if constexpr (!AG)
-        for (int i = 0; i < per; ++i) hist[t * per + i] = 0;
-    __syncthreads();
-}
-
-// One radix pass over the values of a band stack that only exists at reduced size (stack_up.h): every thread recomputes the K
-// resized + normalised values of its pixels and histograms them; flush, ticket and pick as in k_sel_pass (one job).
-// cand / cand_cnt (round 3): the SECOND pass also copies every value of the bin the first pass selected into cand[] (count in *cand_cnt) and tracks the smallest key
-// above that bin, so the THIRD pass scans those candidates (k_sel_cand) instead of recomputing the whole stack a third time.
-struct SelUpArgs { StackUp u; size_t cap_floats; uint32_t prefix0, mask0; int pass, shift, bits; SelState* st; uint32_t* hist; uint32_t* ticket; unsigned long long rank0; float gamma; int has_next; double* out;
-                   float* cand; uint32_t* cand_cnt; };
-constexpr uint32_t kSelStage = 3072;  // staged candidates per tile (12 KB of LDS); denser tiles take a second sweep
-template <int K>
-__global__ __launch_bounds__(kT) void k_sel_pass_up(const SelUpArgs a) {
-    __shared__ uint32_t h[2048];
-    __shared__ uint32_t wmin[kT / 64];
-    __shared__ int is_last;
-    __shared__ uint32_t scnt, sbase;
-    __shared__ int redo;  // collect: 1 during the second sweep of a tile whose candidates outgrew the staging area (values are then written straight to cand[])
-    const int nb = 1 << a.bits, t = threadIdx.x;
-    const bool last_pass = a.pass == 2, collect = a.pass == 1 && a.cand != nullptr;
-    const bool find_next = (last_pass || collect) && a.has_next;  // collect: the smallest key above the first pass's bin (the successor when the candidates hold none)
-    for (int i = t; i < 2048; i += kT) h[i] = 0;
-    if (t == 0) { scnt = 0; redo = 0; }
-    const uint32_t prefix = a.pass == 0 ? a.prefix0 : a.st->prefix, mask = a.pass == 0 ? a.mask0 : a.st->mask;
-    const uint32_t above = prefix | ~mask;
-    uint32_t best = 0xffffffffu;
-    __syncthreads();
-    extern __shared__ float tile_lds[];
-    float* stage = tile_lds + a.cap_floats;  // collect: this tile's candidates, up to kSelStage of them
-    stack_tiles<K, true>(a.u, tile_lds, a.cap_floats, [&](int, int, float (&v)[K]) {
-        const bool second = collect && redo;  // uniform
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const uint32_t key = f2key(v[k]);
-            if ((key & mask) == prefix) {
-                if (!second) atomicAdd(&h[(key >> a.shift) & (nb - 1)], 1u);
-                if (collect) {
-                    const uint32_t idx = atomicAdd(&scnt, 1u);
-                    if (second) a.cand[(size_t)sbase + idx] = v[k];
-                    else if (idx < kSelStage) stage[idx] = v[k];
-                }
-            } else if (find_next && key > above && key < best) best = key;
-        }
-    }, [&]() -> bool {
-        if (!collect) return false;  // uniform
-        const uint32_t m = scnt;
-        const bool was_second = redo != 0, dense = !was_second && m > kSelStage;
-        __syncthreads();  // everyone has read scnt / redo
-        if (was_second) {
-            if (t == 0) { scnt = 0; redo = 0; }
-            __syncthreads();
-            return false;
-        }
-        if (t == 0) {
-            if (m) sbase = atomicAdd(a.cand_cnt, m);  // one reservation per tile
-            scnt = 0;
-            redo = dense ? 1 : 0;
-        }
-        __syncthreads();
-        if (dense) return true;  // too many for the staging area (a flat region: every value in the bin): the tile is swept again and writes straight to cand[sbase + ...]
-        for (uint32_t i = t; i < m; i += kT) a.cand[(size_t)sbase + i] = stage[i];
-        __syncthreads();  // the staging area is free again
-        return false;
-    });
-    if (find_next) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const uint32_t w = __shfl_xor(best, o); best = w < best ? w : best; }
-        __syncthreads();
-        if ((t & 63) == 0) wmin[t >> 6] = best;
-        __syncthreads();
-        if (t == 0) {
-            for (int w = 1; w < kT / 64; ++w) best = wmin[w] < best ? wmin[w] : best;
-            if (best != 0xffffffffu) atomicMin(&a.st->next_above, best);
-        }
-    }
-    __syncthreads();
-    for (int i = t; i < nb; i += kT)
-        if (h[i]) atomicAdd(&a.hist[i], h[i]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) is_last = avxk::ticket_is_last(a.ticket, blockIdx.x, gridDim.x);  // two-level: up to 1,024 workgroups arrive here
-    __syncthreads();
-    if (!is_last) return;
-    sel_pick(a.hist, a.st, a.pass, a.shift, a.bits, a.rank0, a.gamma, a.has_next, a.out, a.prefix0, a.mask0);
-    if (a.pass == 0 && a.cand_cnt && t == 0) *a.cand_cnt = 0;  // the next launch collects from zero (the kernel boundary publishes it)
-}
-
-// The third radix pass over the candidates the second one collected (k_sel_pass_up): *cand_cnt values, all inside the first pass's bin.  Same histogram, successor
-// search, flush, ticket and pick as the full pass; the successor found among keys above that bin is already in st->next_above.
-__global__ __launch_bounds__(kT) void k_sel_cand(const SelUpArgs a) {
-    __shared__ uint32_t h[2048];
-    __shared__ uint32_t wmin[kT / 64];
-    __shared__ int is_last;
-    const int nb = 1 << a.bits, t = threadIdx.x;
-    const bool find_next = a.has_next != 0;
-    for (int i = t; i < 2048; i += kT) h[i] = 0;
-    const uint32_t prefix = a.st->prefix, mask = a.st->mask, above = prefix | ~mask;
-    const size_t n = *a.cand_cnt;
-    uint32_t best = 0xffffffffu;
-    __syncthreads();
-    for (size_t i = (size_t)blockIdx.x * kT + t; i < n; i += (size_t)gridDim.x * kT) {
-        const uint32_t key = f2key(a.cand[i]);
-        if ((key & mask) == prefix) atomicAdd(&h[(key >> a.shift) & (nb - 1)], 1u);
-        else if (find_next && key > above && key < best) best = key;
-    }
-    if (find_next) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const uint32_t w = __shfl_xor(best, o); best = w < best ? w : best; }
-        __syncthreads();
-        if ((t & 63) == 0) wmin[t >> 6] = best;
-        __syncthreads();
-        if (t == 0) {
-            for (int w = 1; w < kT / 64; ++w) best = wmin[w] < best ? wmin[w] : best;
-            if (best != 0xffffffffu) atomicMin(&a.st->next_above, best);
-        }
-    }
-    __syncthreads();
-    for (int i = t; i < nb; i += kT)
-        if (h[i]) atomicAdd(&a.hist[i], h[i]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) is_last = avxk::ticket_is_last(a.ticket, blockIdx.x, gridDim.x);
-    __syncthreads();
-    if (!is_last) return;
-    sel_pick(a.hist, a.st, 2, a.shift, a.bits, a.rank0, a.gamma, a.has_next, a.out, a.prefix0, a.mask0);
-}
-
 // SRC: 0 uint8 frames (decode table + K x 3 matrix), 1 raw catch planes.  R: blur radius 0 | 1.  STAGE: 0 one radix-select pass
 // (NJ order statistics per frame), 1 map + encode.
 template <int SRC, int R, int STAGE, int NJ>
@@ -1117,8 +743,6 @@ __global__ __launch_bounds__(kT) void k_bee_tile(const BeeArgs a) {
     __shared__ uint32_t h[STAGE == 0 ? NJ : 1][STAGE == 0 ? 2048 : 1];
     __shared__ float thr[STAGE == 1 ? 256 : 1];
     __shared__ uint8_t coarse[STAGE == 1 ? kCoarseTableBytes : 1];
-    __shared__ uint32_t wmin[kT / 64];
-    __shared__ int is_last;
     const int t = threadIdx.x, f = blockIdx.y;
     const size_t n = (size_t)a.H * a.W;
     if (SRC == 0)
@@ -1139,21 +763,15 @@ __global__ __launch_bounds__(kT) void k_bee_tile(const BeeArgs a) {
     const float* raw = a.raw + (size_t)f * n * 3;
     const double* pct = a.pct + (size_t)f * 8;
     SelState* sst = a.st + (size_t)f * kSelMax;
-    const bool last_pass = a.pass == 2, find_next = STAGE == 0 && last_pass && a.has_next;
-    uint32_t prefix[NJ], mask[NJ], above[NJ], best[NJ];
+    const bool find_next = STAGE == 0 && a.pass == 2 && a.r.has_next;
+    uint32_t prefix[NJ], mask[NJ], best[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         prefix[j] = (STAGE == 0 && a.pass != 0) ? sst[j].prefix : 0u;
         mask[j] = (STAGE == 0 && a.pass != 0) ? sst[j].mask : 0u;
-        above[j] = prefix[j] | ~mask[j];
         best[j] = 0xffffffffu;
     }
-    const int nb = 1 << a.bits;
-    auto visit = [&](int j, float v) {
-        const uint32_t k = f2key(v);
-        if ((k & mask[j]) == prefix[j]) atomicAdd(&h[STAGE == 0 ? j : 0][(k >> a.shift) & (nb - 1)], 1u);
-        else if (find_next && k > above[j] && k < best[j]) best[j] = k;
-    };
+    auto visit = [&](int j, float v) { sel_visit(SelDigit(prefix[j], mask[j], a.shift, a.bits, find_next), v, h[STAGE == 0 ? j : 0], best[j]); };
     __syncthreads();
     const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH;
     // catches of a tile and its halo, rescaled (reflect-101 at the frame border).  A thread's loads for the NEXT tile are issued
@@ -1261,35 +879,12 @@ __global__ __launch_bounds__(kT) void k_bee_tile(const BeeArgs a) {
         }
         __syncthreads();
     }
-    if (STAGE == 1) return;
-    // ---- end of a radix pass: successor candidates, histogram flush, ticket, and the last workgroup of this FRAME picks ----
-    uint32_t* hist = a.hist + (size_t)f * kSelMax * 2048;
-    if (find_next) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            uint32_t b = best[j];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(b, o); b = v < b ? v : b; }
-            __syncthreads();
-            if ((t & 63) == 0) wmin[t >> 6] = b;
-            __syncthreads();
-            if (t == 0) {
-                for (int w = 1; w < kT / 64; ++w) b = wmin[w] < b ? wmin[w] : b;
-                if (b != 0xffffffffu) atomicMin(&sst[j].next_above, b);
-            }
-        }
-    }
-    __syncthreads();
-    for (int j = 0; j < NJ; ++j)
-        for (int i = t; i < nb; i += kT)
-            if (h[STAGE == 0 ? j : 0][i]) atomicAdd(&hist[j * 2048 + i], h[STAGE == 0 ? j : 0][i]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) is_last = atomicAdd(a.ticket + f, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!is_last) return;
-    for (int j = 0; j < NJ; ++j) sel_pick(hist + j * 2048, sst + j, a.pass, a.shift, a.bits, a.rank0, a.gamma, a.has_next, a.pct + (size_t)f * 8 + j);
-    if (t == 0) a.ticket[f] = 0;
+    // ---- end of a radix pass: the last workgroup of this FRAME picks ----
+    if constexpr (STAGE == 0)
+        sel_finish_pass<NJ>(h, best, NJ, a.pass, a.shift, a.bits, a.ticket, f, kSelTicketFrame, 0u, 0u,
+                            [sst, hist = a.hist + (size_t)f * kSelMax * 2048, r = a.r, out = a.pct + (size_t)f * 8, find_next](int j) {
+                                return SelTail{sst + j, hist + j * 2048, r, out + j, find_next};
+                            });
 }
 
 int grid_for(avx_ctx* ctx, size_t items) {
@@ -1301,274 +896,25 @@ int grid_for(avx_ctx* ctx, size_t items) {
 }  // namespace
 
 // ======================================= C ABI =======================================================
-struct UvScratch {
-    Stat3* partials; float4* stats; uint32_t* hist; SelState* sel; uint32_t* ticket; double* pct; float* mat;
-};
-
-// ---- the three radix passes in ONE launch (round 3) ----------------------------------------------------------------------------------------
-// A percentile used to be three dependent launches of ~16-40 us each for a 1080p plane, almost all of it fixed cost (launch, re-reading the plane, the drain before
-// the next pass).  Here the grid stays resident: a workgroup keeps its share of every job in REGISTERS (8 x 16 bytes per thread and job: a whole 1080p plane at one
-// workgroup per CU; what does not fit is re-read), histograms pass p, flushes, takes a ticket; the LAST workgroup picks, then releases the others through a
-// generation counter they poll (agent-scope atomic loads + s_sleep).  The grid is capped at one workgroup per CU (256 threads, 32 KB of LDS at NJ = 4): every
-// workgroup of ONE such launch is resident at once; launches from several streams can starve each other (each gets part of its grid and waits for the rest), which is
-// why this form is opt-in (run_percentiles); a wait that outlasts ~0.3 s gives up (the launch then returns without a result rather than hanging the GPU).  Measured (hummingbird 1080p, phases ablated): 50 us for one plane = visits 14.5 (the run-length LDS atomics), flush 11.6, picks 5.8,
-// the bare ticket / release / poll chain 23 (~ eight dependent agent-scope round trips per pass); the three-launch form took 54.  One global histogram per pass (cleared by the last workgroup at the end: the kernel boundary publishes the zeros).
-struct SelAll { int n_jobs; SelState* st; uint32_t* hist /*[3][kSelMax][2048]*/; uint32_t* ticket; uint32_t* gen; SelJob job[kSelMax]; int shift[3], bits[3]; };
-template <int NJ>
-__global__ __launch_bounds__(kT) void k_sel_all(const SelAll a) {
-    __shared__ uint32_t h[NJ][2048];
-    __shared__ uint32_t wmin[kT / 64];
-    __shared__ int is_last, gave_up;
-    const int t = threadIdx.x;
-    const uint32_t gen0 = ld_ag(a.gen);  // read before this workgroup's first ticket: nobody can have advanced it yet
-    const size_t stride = (size_t)gridDim.x * kT, i0 = (size_t)blockIdx.x * kT + t;
-    auto job_vec = [&](int j, const float4*& xv, size_t& nvec, size_t& head, size_t& tail0) {
-        const SelJob jb = a.job[j];
-        const size_t mis = ((16 - ((uintptr_t)jb.x & 15)) & 15) / 4;
-        head = mis < jb.n ? mis : jb.n;
-        nvec = (jb.n - head) / 4; tail0 = head + nvec * 4;
-        xv = reinterpret_cast<const float4*>(jb.x + head);
-    };
-    float4 keep[NJ][8];  // this thread's first eight vectors of every job: loaded once, visited in all three passes
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if (j >= a.n_jobs) break;
-        const float4* xv; size_t nvec, head, tail0;
-        job_vec(j, xv, nvec, head, tail0);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { const size_t idx = i0 + q * stride; keep[j][q] = nvec ? xv[idx < nvec ? idx : nvec - 1] : make_float4(0.f, 0.f, 0.f, 0.f); }
-    }
-    if (t == 0) gave_up = 0;
-#pragma unroll 1
-    for (int pass = 0; pass < 3; ++pass) {
-        const int shift = a.shift[pass], nb = 1 << a.bits[pass];
-        const bool last_pass = pass == 2;
-        for (int i = t; i < NJ * 2048; i += kT) (&h[0][0])[i] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            if (j >= a.n_jobs) break;
-            const SelJob jb = a.job[j];
-            SelState* st = a.st + j;
-            const bool find_next = last_pass && jb.has_next;
-            const uint32_t prefix = pass == 0 ? 0u : ld_ag(&st->prefix), mask = pass == 0 ? 0u : ld_ag(&st->mask);
-            const uint32_t above = prefix | ~mask;
-            uint32_t best = 0xffffffffu, run_bin = 0xffffffffu, run_cnt = 0;
-            auto visit = [&](float f) {  // as k_sel_pass: run-length combined LDS atomics
-                const uint32_t k = f2key(f);
-                if ((k & mask) == prefix) {
-                    const uint32_t b = (k >> shift) & (nb - 1);
-                    if (b == run_bin) { ++run_cnt; }
-                    else {
-                        if (run_cnt) atomicAdd(&h[j][run_bin], run_cnt);
-                        run_bin = b; run_cnt = 1;
-                    }
-                } else if (find_next && k > above && k < best) best = k;
-            };
-            const float4* xv; size_t nvec, head, tail0;
-            job_vec(j, xv, nvec, head, tail0);
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if (i0 + q * stride < nvec) { visit(keep[j][q].x); visit(keep[j][q].y); visit(keep[j][q].z); visit(keep[j][q].w); }
-            for (size_t i = i0 + 8 * stride; i < nvec; i += 8 * stride) {  // planes beyond 8 vectors per thread: re-read
-                float4 v[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) { const size_t idx = i + q * stride; v[q] = xv[idx < nvec ? idx : nvec - 1]; }
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    if (i + q * stride < nvec) { visit(v[q].x); visit(v[q].y); visit(v[q].z); visit(v[q].w); }
-            }
-            if (blockIdx.x == 0) {
-                if ((size_t)t < head) visit(jb.x[t]);
-                if (tail0 + t < jb.n && t < 4) visit(jb.x[tail0 + t]);
-            }
-            if (run_cnt) atomicAdd(&h[j][run_bin], run_cnt);
-            if (find_next) {
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { const uint32_t v = __shfl_xor(best, o); best = v < best ? v : best; }
-                __syncthreads();
-                if ((t & 63) == 0) wmin[t >> 6] = best;
-                __syncthreads();
-                if (t == 0) {
-                    for (int w = 1; w < kT / 64; ++w) best = wmin[w] < best ? wmin[w] : best;
-                    if (best != 0xffffffffu) __hip_atomic_fetch_min(&st->next_above, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-        __syncthreads();
-        uint32_t* ghist = a.hist + (size_t)pass * kSelMax * 2048;
-        for (int j = 0; j < a.n_jobs; ++j)
-            for (int i = t; i < nb; i += kT)
-                if (h[j][i]) __hip_atomic_fetch_add(&ghist[j * 2048 + i], h[j][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (t == 0) is_last = avxk::ticket_is_last(a.ticket, blockIdx.x, gridDim.x, true);
-        __syncthreads();
-        if (is_last) {
-            for (int j = 0; j < a.n_jobs; ++j) {
-                const SelJob jb = a.job[j];
-                sel_pick_t<true>(ghist + j * 2048, a.st + j, pass, shift, a.bits[pass], jb.rank0, jb.gamma, jb.has_next, jb.out, 0u, 0u);
-            }
-            if (last_pass)  // leave every histogram of the launch zero for the next one (plain stores: the kernel boundary publishes them)
-                for (int i = t; i < 3 * kSelMax * 2048; i += kT) a.hist[i] = 0;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (t == 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the ticket's own resets (ticket_is_last) and the state have landed before anyone is released
-                __hip_atomic_fetch_add(a.gen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        } else if (!last_pass) {
-            if (t == 0) {
-                int spins = 0;
-                while ((int)(ld_ag(a.gen) - (gen0 + (uint32_t)pass + 1u)) < 0) {
-                    __builtin_amdgcn_s_sleep(16);
-                    if (++spins > (1 << 20)) { gave_up = 1; break; }
-                }
-            }
-            __syncthreads();
-            if (gave_up) return;
-        }
-    }
-}
-
-static int uv_small_scratch(avx_ctx* ctx, hipStream_t stream, UvScratch* s, avx_ws** out_ws = nullptr) {
+int uv_small_scratch(avx_ctx* ctx, hipStream_t stream, UvScratch* s, avx_ws** out_ws) {
     avx_ws* ws = avx_workspace(ctx, stream);
     if (!ws) return AVX_ERR_NOMEM;
     if (out_ws) *out_ws = ws;
-    const size_t need = (size_t)ctx->num_cus * 8 * 16 * sizeof(Stat3) + 16 * sizeof(float4) + 3 * kSelMax * 2048 * 4 + kSelMax * sizeof(SelState) + 64 + 16 * 8 + 16 * 129 * 4 + 4096;
+    const size_t need = (size_t)ctx->num_cus * 8 * 16 * sizeof(Stat3) + 16 * sizeof(float4) + kSelMax * 2048 * 4 + kSelMax * sizeof(SelState) + 64 + 16 * 8 + 16 * 129 * 4 + 4096;
     if (ws->uv_small == nullptr) {
         AVX_HIP(ctx, hipMalloc(&ws->uv_small, need));
-        AVX_HIP(ctx, hipMemsetAsync(ws->uv_small, 0, need, stream));  // histogram and ticket start at zero; k_sel_pass leaves them so
+        AVX_HIP(ctx, hipMemsetAsync(ws->uv_small, 0, need, stream));  // histogram and ticket start at zero; the select kernels leave them so
     }
     char* p = (char*)ws->uv_small;
     s->partials = (Stat3*)p; p += (size_t)ctx->num_cus * 8 * 16 * sizeof(Stat3);
     s->stats = (float4*)p; p += 16 * sizeof(float4);
-    s->hist = (uint32_t*)p; p += 3 * kSelMax * 2048 * 4;  // one per pass for k_sel_all; the per-pass kernels use the first
+    s->hist = (uint32_t*)p; p += kSelMax * 2048 * 4;
     s->sel = (SelState*)p; p += kSelMax * sizeof(SelState) + 8;
-    s->ticket = (uint32_t*)p; p += 256;  // ticket_is_last's 1 + 32 counters; word 48: k_sel_all's generation counter
+    s->ticket = (uint32_t*)p; p += 256;  // ticket_is_last's 1 + 32 counters; word 56: the candidate count of avx_uv_percentile_up_device
     p = (char*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
     s->pct = (double*)p; p += 16 * 8;
     s->mat = (float*)p;
     return AVX_OK;
-}
-
-// exact np.percentile(x_j, q_j) (linear interpolation) of n_j device floats -> *out_j (device doubles), up to kSelMax
-// order statistics resolved by the same three passes
-struct PctReq { const float* x; size_t n; double q; double* out_dev; };
-static int run_percentiles(avx_ctx* ctx, const UvScratch& u, const PctReq* req, int count, hipStream_t s) {
-    for (int base = 0; base < count; base += kSelMax) {
-        const int nj = count - base < kSelMax ? count - base : kSelMax;
-        SelPass a{};
-        a.n_jobs = nj; a.st = u.sel; a.hist = u.hist; a.ticket = u.ticket;
-        size_t nmax = 0;
-        for (int j = 0; j < nj; ++j) {
-            const PctReq& r = req[base + j];
-            // NumPy (2.x) evaluates the virtual index in the array's dtype: float32(n-1) * (float32(q)/float32(100)).
-            const float vi = (float)(r.n - 1) * ((float)r.q / 100.0f);
-            float lo = floorf(vi);
-            if (lo < 0) lo = 0;
-            if (lo > (float)(r.n - 1)) lo = (float)(r.n - 1);
-            a.job[j] = SelJob{r.x, r.n, (unsigned long long)lo, vi - lo, (size_t)lo + 1 < r.n ? 1 : 0, r.out_dev};
-            nmax = r.n > nmax ? r.n : nmax;
-        }
-        // few, fat workgroups: every workgroup flushes its non-empty LDS bins with global atomics
-        const size_t want = (nmax + (size_t)kT * 16 - 1) / ((size_t)kT * 16);
-        static const int wg_per_cu = [] { const char* e = getenv("AVX_SEL_WG"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
-        const size_t cap = (size_t)ctx->num_cus * wg_per_cu;  // measured again in round 2 (hummingbird 1080p: 3.24 / 3.02 / 2.49 / 2.07 GP/s at 1 / 2 / 4 / 8 per CU): every workgroup pays the histogram clear, flush and ticket
-        const int g = (int)(want < cap ? (want ? want : 1) : cap);
-        const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
-        // The one-launch form (k_sel_all) is OPT-IN (AVX_SEL_ONE=1; read per call: tests flip it).  Its inner barriers need the whole grid resident, and that holds for ONE
-        // instance only: at 128+ registers per lane a CU takes two of its workgroups, so when several streams run selects at once (the four frame lanes of bench.py's
-        // UV legs did) the dispatcher can give each launch HALF of its workgroups and all of them wait for the other halves until the time-out fires (measured: the
-        // default bench's hummingbird leg at 326 ms per step, its selects giving up).  With one stream it is 14 us per hummingbird frame faster than three launches.
-        const char* one_env = getenv("AVX_SEL_ONE");
-        if (one_env && one_env[0] == '1') {
-            SelAll b{};
-            b.n_jobs = nj; b.st = u.sel; b.hist = u.hist; b.ticket = u.ticket; b.gen = u.ticket + 48;
-            for (int j = 0; j < nj; ++j) b.job[j] = a.job[j];
-            for (int p = 0; p < 3; ++p) { b.shift[p] = shifts[p]; b.bits[p] = bits[p]; }
-            const int g1 = (int)(want < (size_t)ctx->num_cus ? (want ? want : 1) : (size_t)ctx->num_cus);
-            if (nj == 1) hipLaunchKernelGGL(k_sel_all<1>, dim3(g1), dim3(kT), 0, s, b);
-            else if (nj == 2) hipLaunchKernelGGL(k_sel_all<2>, dim3(g1), dim3(kT), 0, s, b);
-            else hipLaunchKernelGGL(k_sel_all<4>, dim3(g1), dim3(kT), 0, s, b);
-            continue;
-        }
-        for (int p = 0; p < 3; ++p) {
-            a.pass = p; a.shift = shifts[p]; a.bits = bits[p];
-            if (nj == 1) hipLaunchKernelGGL(k_sel_pass<1>, dim3(g), dim3(kT), 0, s, a);
-            else if (nj == 2) hipLaunchKernelGGL(k_sel_pass<2>, dim3(g), dim3(kT), 0, s, a);
-            else hipLaunchKernelGGL(k_sel_pass<4>, dim3(g), dim3(kT), 0, s, a);
-        }
-    }
-    AVX_HIP(ctx, hipGetLastError());
-    return AVX_OK;
-}
-static int run_percentile(avx_ctx* ctx, const UvScratch& u, const float* x, size_t n, double q, double* out_dev, hipStream_t s) {
-    const PctReq r{x, n, q, out_dev};
-    return run_percentiles(ctx, u, &r, 1, s);
-}
-
-// ---- internal entry points for other translation units of the library (mantis.hip) ---------------------
-int avx_uv_percentile_device(avx_ctx* ctx, const float* x, size_t n, double q, double* out_dev, hipStream_t s) {
-    UvScratch u;
-    int rc = uv_small_scratch(ctx, s, &u);
-    if (rc) return rc;
-    return run_percentile(ctx, u, x, n, q, out_dev, s);
-}
-
-// np.percentile(q) over the H x W x K values of a reduced-size band stack read through its resize (+ safe_norm): stack_up.h
-int avx_uv_percentile_up_device(avx_ctx* ctx, const StackUp& up, double q, double* out_dev, hipStream_t s, float* cand_buf /*H * W * K floats, or NULL: three full passes*/) {
-    UvScratch u;
-    int rc = uv_small_scratch(ctx, s, &u);
-    if (rc) return rc;
-    const size_t n = (size_t)up.H * up.W * up.K;
-    const float vi = (float)(n - 1) * ((float)q / 100.0f);  // as run_percentiles
-    float lo = floorf(vi);
-    if (lo < 0) lo = 0;
-    if (lo > (float)(n - 1)) lo = (float)(n - 1);
-    SelUpArgs a{};
-    a.u = up; a.st = u.sel; a.hist = u.hist; a.ticket = u.ticket; a.rank0 = (unsigned long long)lo; a.gamma = vi - lo; a.has_next = (size_t)lo + 1 < n ? 1 : 0; a.out = out_dev;
-    static_assert(kT == 256, "AVX_STACK_TILES assumes 256 threads");
-    const size_t tiles = (size_t)((up.W + kUpTW - 1) / kUpTW) * ((up.H + kUpTH - 1) / kUpTH), cap = (size_t)ctx->num_cus * 4;
-    const int g = (int)(tiles < cap ? (tiles ? tiles : 1) : cap);
-    a.cap_floats = stack_tile_floats(up.hs, up.ws, up.H, up.W, up.K);
-    const size_t lds_tile = a.cap_floats * sizeof(float);
-    AVX_REQUIRE(ctx, lds_tile <= 96 * 1024, "percentile through a resized stack: the tile's source rectangle does not fit LDS (%zu bytes)", lds_tile);
-    // candidates: the second pass stages a tile's matching values in LDS (kSelStage floats behind the source rectangle) and copies them out once per tile
-    const size_t lds_stage = (size_t)kSelStage * sizeof(float);
-    const char* cand_env = getenv("AVX_MANTIS_CAND");  // read per call: tests flip it (0: three full passes)
-    const bool use_cand = cand_buf && !(cand_env && cand_env[0] == '0') && lds_tile + lds_stage <= 120 * 1024;
-    const size_t lds = lds_tile + (use_cand ? lds_stage : 0);
-    AVX_REQUIRE(ctx, stack_k_tiled(up.K) && up.mm, "percentile through a resized stack: K=%d is not instantiated / no min-max table", up.K);
-    AVX_STACK_K_SWITCH(up.K, AVX_HIP(ctx, hipFuncSetAttribute((const void*)k_sel_pass_up<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)))
-    // safe_norm's values lie in [0, 1]: every key starts with the bits 10 (positive, exponent < 128), so the three digits are taken from
-    // bits 29..19, 18..8, 7..0 -- the first histogram then resolves 16 mantissa steps per binade instead of 4, and its LDS atomics
-    // collide a quarter as often (the plain 11/11/10 split put an eighth of a uniform [0, 1] sample into ONE bin)
-    a.prefix0 = 0x80000000u; a.mask0 = 0xc0000000u;
-    const int shifts[3] = {19, 8, 0}, bits[3] = {11, 11, 8};
-    if (use_cand) { a.cand = cand_buf; a.cand_cnt = u.ticket + 56; }  // word 56 of the ticket block: zero at rest (uv_small_scratch), re-zeroed by the first pass
-    for (int p = 0; p < 3; ++p) {
-        a.pass = p; a.shift = shifts[p]; a.bits = bits[p];
-        if (p == 2 && use_cand) {  // the candidates of the first pass's bin instead of the whole stack
-            const int gc = (int)((size_t)ctx->num_cus < (size_t)g ? (size_t)ctx->num_cus : (size_t)g);
-            hipLaunchKernelGGL(k_sel_cand, dim3(gc), dim3(kT), 0, s, a);
-            break;
-        }
-        const size_t lds_p = (p == 1 && use_cand) ? lds : lds_tile;  // only the collecting pass carries the staging area
-        AVX_STACK_K_SWITCH(up.K, hipLaunchKernelGGL(k_sel_pass_up<KT>, dim3(g), dim3(kT), lds_p, s, a))
-    }
-    AVX_HIP(ctx, hipGetLastError());
-    return AVX_OK;
-}
-
-int avx_uv_percentiles_device(avx_ctx* ctx, int count, const float* const* x, const size_t* n, const double* q, double* const* out_dev, hipStream_t s) {
-    UvScratch u;
-    int rc = uv_small_scratch(ctx, s, &u);
-    if (rc) return rc;
-    PctReq rq[16];
-    if (count > 16) return avx_fail(ctx, AVX_ERR_INVALID, "at most 16 percentiles per call");
-    for (int i = 0; i < count; ++i) rq[i] = PctReq{x[i], n[i], q[i], out_dev[i]};
-    return run_percentiles(ctx, u, rq, count, s);
 }
 
 int avx_uv_plane_blur_device(avx_ctx* ctx, const float* in, float* out, int K, int H, int W, int ksize, const double* taps_host, hipStream_t s) {
@@ -1643,8 +989,8 @@ static int honeybee_recompute(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_
     const int nj = mode == 2 ? 2 : (mode == 0 ? 3 : (mode == 3 ? 1 : 0));
     float *raw = nullptr, *selp = nullptr;
     {
-        // AVX_BEE_SELPLANES=0: all three radix passes recompute (no plane scratch)
-        static const bool planes_on = [] { const char* e = getenv("AVX_BEE_SELPLANES"); return !(e && e[0] == '0'); }();
+        const char* planes_env = getenv("AVX_BEE_SELPLANES");  // read per call: tests flip it (0: all three radix passes recompute, no plane scratch)
+        const bool planes_on = !(planes_env && planes_env[0] == '0');
         const int fb = n_frames < kBeeMaxFrames ? n_frames : kBeeMaxFrames;
         const size_t raw_f = d->source == 1 ? n * 3 * fb : 0, sel_f = (planes_on && nj > 0) ? n * nj * fb : 0;
         if (raw_f + sel_f) {
@@ -1654,11 +1000,7 @@ static int honeybee_recompute(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_
         }
         if (d->source == 2) raw = const_cast<float*>(d->catches);  // the catches came with their statistics (csrc/mst_fused.hip: conv_out's epilogue)
     }
-    const double q = mode == 3 ? 98.0 : 95.0;
-    const float vi = (float)(n - 1) * ((float)q / 100.0f);  // NumPy evaluates the virtual index in float32 (run_percentiles)
-    float lo = floorf(vi);
-    if (lo < 0) lo = 0;
-    if (lo > (float)(n - 1)) lo = (float)(n - 1);
+    const SelRank rk = sel_rank(n, mode == 3 ? 98.0 : 95.0);
     const long tiles = (long)((W + 31) / 32) * ((H + 31) / 32);
     for (int f0 = 0; f0 < n_frames; f0 += kBeeMaxFrames) {
         const int F = n_frames - f0 < kBeeMaxFrames ? n_frames - f0 : kBeeMaxFrames;
@@ -1688,13 +1030,12 @@ static int honeybee_recompute(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_
         a.scale_mode = d->adaptation ? 1 : 0;
         a.t0 = R ? (float)d->blur_taps_host[0] : 1.f; a.t1 = R ? (float)d->blur_taps_host[1] : 1.f; a.t2 = R ? (float)d->blur_taps_host[2] : 1.f;
         a.mode = mode; a.n_jobs = nj; a.st = sel; a.hist = hist; a.ticket = ticket; a.pct = pct;
-        a.rank0 = (unsigned long long)lo; a.gamma = vi - lo; a.has_next = (size_t)lo + 1 < n ? 1 : 0;
+        a.r = rk;
         a.eps = d->eps;
         for (int i = 0; i < 9; ++i) a.M[i] = d->custom_matrix[i];
         a.enc_thr = ctx->d_enc_thr_f32; a.coarse = ctx->d_coarse_f32; a.lo_key = ctx->coarse_lo_key[0];
         long per = ((long)ctx->num_cus * 3 + F - 1) / F;
         const int gx = (int)(tiles < per ? tiles : (per < 1 ? 1 : per));
-        const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
 #define AVX_BEE(SRCV, RV, STG, NJV) hipLaunchKernelGGL((k_bee_tile<SRCV, RV, STG, NJV>), dim3(gx, F), dim3(kT), 0, s, a)
 #define AVX_BEE_SR(STG, NJV)                                                                         \
         {                                                                                            \
@@ -1706,20 +1047,18 @@ static int honeybee_recompute(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_
         //    the plain selection kernel (all F frames per launch) instead of recomputing catches, rescale and blur twice more.
         a.sel_planes = selp;
         for (int ps = 0; ps < (selp ? 1 : 3) && nj > 0; ++ps) {
-            a.pass = ps; a.shift = shifts[ps]; a.bits = bits[ps];
+            a.pass = ps; a.shift = kSelSplit.shift[ps]; a.bits = kSelSplit.bits[ps];
             if (nj == 1) AVX_BEE_SR(0, 1) else if (nj == 2) AVX_BEE_SR(0, 2) else AVX_BEE_SR(0, 3)
         }
         if (selp && nj > 0) {
             SelPass sp{};
             sp.n_jobs = nj; sp.st = sel; sp.hist = hist; sp.ticket = ticket; sp.x_frame_stride = (size_t)nj * n; sp.out_frame_stride = 8;
-            for (int j = 0; j < nj; ++j) sp.job[j] = SelJob{selp + (size_t)j * n, n, (unsigned long long)lo, vi - lo, (size_t)lo + 1 < n ? 1 : 0, pct + j};
+            for (int j = 0; j < nj; ++j) sp.job[j] = SelJob{selp + (size_t)j * n, n, rk, pct + j};
             const size_t want = (n + (size_t)kT * 16 - 1) / ((size_t)kT * 16), capb = (size_t)ctx->num_cus;
             const int gs = (int)(want < capb ? (want ? want : 1) : capb);
             for (int ps = 1; ps < 3; ++ps) {
-                sp.pass = ps; sp.shift = shifts[ps]; sp.bits = bits[ps];
-                if (nj == 1) hipLaunchKernelGGL(k_sel_pass<1>, dim3(gs, F), dim3(kT), 0, s, sp);
-                else if (nj == 2) hipLaunchKernelGGL(k_sel_pass<2>, dim3(gs, F), dim3(kT), 0, s, sp);
-                else hipLaunchKernelGGL(k_sel_pass<4>, dim3(gs, F), dim3(kT), 0, s, sp);
+                sp.pass = ps; sp.shift = kSelSplit.shift[ps]; sp.bits = kSelSplit.bits[ps];
+                sel_launch_pass(sp, gs, F, s);
             }
         }
         // 3) map + encode
@@ -1733,21 +1072,6 @@ static int honeybee_recompute(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_
 }
 
 extern "C" {
-
-int avx_percentile(avx_ctx* ctx, const float* data, size_t n, double q, double* out_host, void* stream) {
-    if (!ctx) return AVX_ERR_INVALID;
-    AVX_REQUIRE(ctx, data && out_host && n > 0 && q >= 0.0 && q <= 100.0, "avx_percentile: bad arguments");
-    AVX_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = avx_pick_stream(ctx, stream);
-    UvScratch u;
-    int rc = uv_small_scratch(ctx, s, &u);
-    if (rc) return rc;
-    rc = run_percentile(ctx, u, data, n, q, u.pct, s);
-    if (rc) return rc;
-    AVX_HIP(ctx, hipMemcpyAsync(out_host, u.pct, sizeof(double), hipMemcpyDeviceToHost, s));
-    AVX_HIP(ctx, hipStreamSynchronize(s));
-    return AVX_OK;
-}
 
 int avx_spectral_integrate(avx_ctx* ctx, const void* hsi, int layout, int dtype, int H, int W, int B, const float* weights_host, int K,
                            float* out_planes, float* stats_host, void* stream) {
@@ -1979,11 +1303,12 @@ int avx_honeybee_u8(avx_ctx* ctx, const uint8_t* in_hwc, uint8_t* out_hwc, int n
             if (d->mapping == 4) rq[nr++] = PctReq{ubg, n, 98.0, u.pct + 3};
             if ((rc = run_percentiles(ctx, u, rq, nr, s))) return rc;
         }
-        if (d->mapping == 3) { if ((rc = run_percentile(ctx, u, ubg, n, 98.0, u.pct + 0, s))) return rc; }
+        if (d->mapping == 3) { const PctReq rq{ubg, n, 98.0, u.pct + 0}; if ((rc = run_percentiles(ctx, u, &rq, 1, s))) return rc; }
         if (d->mapping == 4) {
             m.pass = 1;
             hipLaunchKernelGGL(k_map_encode, dim3(g), dim3(kT), 0, s, m);
-            if ((rc = run_percentile(ctx, u, aux, 3 * n, 99.0, u.pct + 4, s))) return rc;
+            const PctReq rq{aux, 3 * n, 99.0, u.pct + 4};
+            if ((rc = run_percentiles(ctx, u, &rq, 1, s))) return rc;
             m.pass = 2;
         }
         hipLaunchKernelGGL(k_map_encode, dim3(g), dim3(kT), 0, s, m);

@@ -115,7 +115,7 @@ def test_mantis_fused_finishing_stages_equal_the_seven_launch_route(monkeypatch)
 
 def test_mantis_percentile_candidates_equal_three_full_passes(monkeypatch):
     """Round 3: the second radix pass of the P95 over the (virtual) band stack copies the values of the first pass's bin out, the third pass
-    scans those candidates only (csrc/uv.hip::k_sel_cand).  Exact by construction: the frames must equal the three-full-pass route
+    scans those candidates only (csrc/select.hip::k_sel_cand).  Exact by construction: the frames must equal the three-full-pass route
     (AVX_MANTIS_CAND=0), also where nearly every value shares a bin (flat frames: the candidate list is the whole stack)."""
     from animal_vision_amd.animals import MantisShrimp
     from animal_vision_amd.synthetic import noise_frame, structured_frame

@@ -37,22 +37,70 @@ def test_percentile_matches_numpy(uv, n, q):
     assert got == want, (n, q, got, want)
 
 
-def test_percentile_one_launch_equals_numpy_and_the_three_launch_form(uv, monkeypatch):
-    """Round 3: the three radix passes can run in one launch (csrc/uv.hip::k_sel_all: register-resident share of the plane, ticket + generation
-    counter between the passes; opt-in, AVX_SEL_ONE=1: several such launches on different streams can starve each other).  Planes smaller than a grid, a 1080p plane (exactly the register share), a 4K plane (the re-read loop),
-    unaligned starts; each against np.percentile and against the three-launch form (AVX_SEL_ONE=0), repeated (the histograms and the
-    ticket must be left clean)."""
+def test_percentile_below_a_grid_the_eight_vector_share_and_the_reread_loop(uv):
+    """k_sel_pass (csrc/select.hip) keeps the first eight 16-byte vectors of a thread's share in registers and re-reads the rest: planes
+    smaller than a grid, a 1080p plane (exactly the eight-vector share at one workgroup per CU), a 4K plane (the re-read loop), slices
+    starting one float into the host array; each against np.percentile, repeated (the histograms and the ticket must be left clean)."""
     rng = np.random.default_rng(77)
     for n in (5, 4099, 1920 * 1080, 3840 * 2160 + 3):
         x = (rng.random(n + 1, dtype=np.float32) ** 2) * 3.0 - 0.25
         for off in (0, 1):
             for q in (95.0, 50.0, 99.9):
                 want = float(np.percentile(x[off:off + n], q))
-                assert uv.percentile(x[off:off + n], q) == want, (n, off, q, "three launches (the default)")
-                monkeypatch.setenv("AVX_SEL_ONE", "1")
-                for rep in range(2):
+                for rep in range(3):
                     assert uv.percentile(x[off:off + n], q) == want, (n, off, q, rep)
-                monkeypatch.delenv("AVX_SEL_ONE")
+
+
+def test_percentiles_dev_on_misaligned_device_pointers():
+    """avx_percentiles_dev with job pointers 0..3 floats off a 16-byte boundary: the head / tail elements of k_sel_pass (uv.percentile
+    uploads into a fresh allocation, so its device pointer is always aligned).  Lengths from 1 to 65537 mixed within a call; 1, 2, 3, 4, 5
+    and 16 jobs per call (one and two jobs, four slots with three live, a second group of passes on the same stream -- which must find
+    histogram, state and ticket clean -- and the limit); every (offset, length, q) combination occurs; every call is issued twice.  Exact
+    equality with np.percentile; 17 jobs are refused."""
+    import ctypes
+
+    from animal_vision_amd._lib import AvxError, lib
+    from animal_vision_amd.runtime import get_context
+
+    ctx = get_context()
+    offs, lens, qs = (0, 1, 2, 3), (1, 2, 3, 7, 1027, 65537), (0.0, 50.0, 95.0, 100.0)
+    calls, k, need = [], 0, 0
+    for _ in range(4):
+        for count in (1, 2, 3, 4, 5, 16):
+            jobs, pos = [], 0
+            for _ in range(count):
+                off, n, q = offs[k % 4], lens[(k // 4) % 6], qs[(k + k // 24) % 4]
+                k += 1
+                start = (pos + 3) // 4 * 4 + off  # off floats past a 16-byte boundary of the (256-byte aligned) allocation
+                jobs.append((start, n, q))
+                pos = start + n
+            calls.append(jobs)
+            need = max(need, pos)
+    assert {(s % 4, n, q) for jobs in calls for s, n, q in jobs} == {(o, n, q) for o in offs for n in lens for q in qs}
+    x = (np.random.default_rng(5).random(need, dtype=np.float32) ** 3) * 4.0 - 0.5  # mixed signs, skewed
+    dx, dout = ctx.upload(x), ctx.malloc(16 * 8)
+
+    def run(jobs):
+        c = len(jobs)
+        a_ptr = (ctypes.c_void_p * c)(*[dx.ptr + 4 * s for s, _, _ in jobs])
+        a_n = (ctypes.c_size_t * c)(*[n for _, n, _ in jobs])
+        a_q = (ctypes.c_double * c)(*[q for _, _, q in jobs])
+        a_out = (ctypes.c_void_p * c)(*[dout.ptr + 8 * (i % 16) for i in range(c)])
+        ctx.memset(dout, 0xFF)  # NaNs: a result that is not written shows
+        ctx._check(lib.avx_percentiles_dev(ctx._h, c, a_ptr, a_n, a_q, a_out, ctx.stream))
+        return ctx.download(dout, (16,), np.float64)[:c]
+
+    try:
+        for jobs in calls:
+            want = [float(np.percentile(x[s:s + n], q)) for s, n, q in jobs]
+            for rep in range(2):
+                got = run(jobs)
+                assert got.tolist() == want, (jobs, rep, got.tolist(), want)
+        with pytest.raises(AvxError, match="avx_percentiles_dev: bad arguments"):
+            run([(0, 7, 50.0)] * 17)
+    finally:
+        dx.free()
+        dout.free()
 
 
 def test_percentile_duplicates_and_constants(uv):
@@ -264,3 +312,37 @@ def test_honeybee_recompute_form_equals_plane_form(uv, oracle, mapping, adaptati
         for k in range(3):
             _, want = oracle.honeybee_visualize(frames[k], adaptation=adaptation, mapping_mode=mapping, custom_matrix=M, blur_sigma_px=sigma)
             _u8_close(outs["1"][k], want, max_frac=5e-3)
+
+
+@pytest.mark.parametrize("mapping", ["uv_purple_yellow", "opponent", "falsecolor"])  # 1, 2 and 3 order statistics per frame
+@pytest.mark.parametrize("sigma", [0.0, 0.2])  # blur ksize 0 and 3
+def test_honeybee_recompute_all_passes_equals_selection_planes(uv, oracle, mapping, sigma, monkeypatch):
+    """The recompute form's radix passes 2 and 3 either read the planes pass 1 wrote (k_sel_pass, the default) or recompute the values in
+    k_bee_tile (AVX_BEE_SELPLANES=0, read per call): k_bee_tile then runs the narrowed-prefix passes, the successor search and the
+    last-pass pick through the shared tail.  Same values, same order statistics: the outputs agree byte for byte.  33 x 65: partial 32 x 32
+    tiles in both directions and two tile rows; three frames use the frame dimension of the grid."""
+    from animal_vision_amd.animals import HoneyBee
+    from animal_vision_amd.synthetic import structured_frame
+
+    H, W = 33, 65
+    for n_frames in (1, 3):
+        frames = np.stack([structured_frame(k, H, W) for k in range(n_frames)])
+        outs = {}
+        for planes in ("0", None):
+            if planes is None:
+                monkeypatch.delenv("AVX_BEE_SELPLANES", raising=False)
+            else:
+                monkeypatch.setenv("AVX_BEE_SELPLANES", planes)
+            op = HoneyBee(mapping_mode=mapping, blur_sigma_px=sigma)._operator()
+            assert op.desc.blur_ksize == (3 if sigma else 0)
+            ctx = op._ctx()
+            d_in, d_out = ctx.upload(frames), ctx.malloc(frames.nbytes)
+            ctx.memset(d_out, 0x5A)
+            op.run_device(d_in, d_out, n_frames, H, W)
+            outs[planes] = ctx.download(d_out, frames.shape, np.uint8)
+            d_in.free(); d_out.free()
+        assert np.array_equal(outs["0"], outs[None]), (mapping, sigma, n_frames, int(np.abs(outs["0"].astype(int) - outs[None].astype(int)).max()))
+        if mapping == "opponent" and sigma and n_frames == 3:
+            for k in range(n_frames):
+                _, want = oracle.honeybee_visualize(frames[k], mapping_mode=mapping, blur_sigma_px=sigma)
+                _u8_close(outs["0"][k], want, max_frac=5e-3)

@@ -1,7 +1,7 @@
 """GPU: the 14 plane-program UV species, MantisShrimp and HoneyBee against the oracle at video sizes (1080p, an odd 1079 x 1917, 4K).
 
 Their kernels change code path with the frame size: plane programs take 8 pixels per thread from n >= 2^20 and sweep a capped grid several
-times (csrc/ew.hip), the radix-select candidate pass sweeps dense tiles twice (csrc/uv.hip), and the blur / resize / remap / Sobel tiles run
+times (csrc/ew.hip), the radix-select candidate pass sweeps dense tiles twice (csrc/select.hip), and the blur / resize / remap / Sobel tiles run
 with many tiles per row and ragged right and bottom edges.  The other tests compare one device route with another at these sizes; here the
 device is compared with the oracle itself.
 

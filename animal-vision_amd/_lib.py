@@ -260,6 +260,17 @@ class ReceptorDesc(ctypes.Structure):
 assert ctypes.sizeof(ReceptorDesc) == 144
 
 
+class ItpSide(ctypes.Structure):
+    """avx_itp_side (include/avx.h)."""
+
+    _fields_ = [("struct_size", ctypes.c_uint32), ("kind", ctypes.c_int32), ("data", ctypes.c_void_p), ("panel", ctypes.c_void_p),
+                ("pix_fmt", ctypes.c_int32), ("full_range", ctypes.c_int32), ("transfer", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(ItpSide) == 40
+AVX_ITP_KINDS = {"sdr": 0, "hdr": 1}  # enum avx_itp_kind
+
+
 class EwInsn(ctypes.Structure):
     _fields_ = [("op", ctypes.c_uint8), ("dst", ctypes.c_uint8), ("a", ctypes.c_uint8), ("b", ctypes.c_uint8), ("imm", ctypes.c_uint32)]
 
@@ -412,6 +423,8 @@ _SIGS = {
     "avx_receptor_delta_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp]),
     "avx_receptor_acuity_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), ctypes.c_double, _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp,
                                _vp, _vp]),
+    "avx_itp_delta": (_i, [_vp, ctypes.POINTER(ItpSide), ctypes.POINTER(ItpSide), ctypes.c_double, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i, _vp,
+                           _vp, _vp, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "avx_sobel3_plane": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "avx_mst_gram": (_i, [_vp, _vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),

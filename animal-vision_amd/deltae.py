@@ -58,7 +58,20 @@ it.  `species` takes the blur the species' own rendering ends with (Dog 3.5, Cat
 the others are refused by name, with the reason); a number is in pixels of the frames as compared, after --scale, from 0.2 to 4.
 Everything else keeps its meaning; the dim grey and the A and B panels are the unfiltered frames.  Without --acuity nothing changes.
 
-    python -m animal_vision_amd.deltae full.y4m half.y4m --observer Dog --weber 0.05,0.05 --acuity species --max-p95 1"""
+    python -m animal_vision_amd.deltae full.y4m half.y4m --observer Dog --weber 0.05,0.05 --acuity species --max-p95 1
+
+--itp switches to dE_ITP of ITU-R BT.2124: 720 x the distance in ICtCp with Ct halved, about 1 per just-noticeable
+difference, and defined at HDR light levels, where dE00 is not.  An input read as raw video with a 10-bit --pix-fmt (and --size) is an
+HDR side -- --transfer pq|hlg is then required --: it crosses to the device as its payload and is compared as stored, in display
+light, with no tone map in between.  Every other input (.y4m, .npy, an image directory, synthetic:, 8-bit raw video) is an SDR side:
+8-bit sRGB, decoded as without --transfer, with code 255 shown at --sdr-white nits (default 203).  So the SDR rendering of an HDR master
+can be held against the master itself, or two tone maps, or two encodes of one HDR clip, against each other.  With OUT an HDR side is
+also decoded once with --tonemap, --peak-nits and --sdr-white: that is what the dim grey and the A and B panels show.  Everything else
+keeps its meaning: the columns, --threshold (1 is about one just-noticeable difference), the modes, the layouts, the limits, all
+sinks.  It is a per-pixel measure of the frames as stored: it does not combine with --ppd, --observer, --acuity or --scale.  Without
+--itp nothing changes.
+
+    python -m animal_vision_amd.deltae master.yuv sdr.y4m --pix-fmt p010le --size 3840x2160 --transfer pq --itp --max-p95 3"""
 from __future__ import annotations
 
 import argparse
@@ -70,10 +83,10 @@ from typing import Iterator, Optional, Sequence, Tuple
 import numpy as np
 
 from .metrics import (DELTA_E_DEFAULT_GAIN, DELTA_E_DEFAULT_THRESHOLD, DELTA_E_LAYOUTS, DELTA_E_MODES, DELTA_E_RECORD_BYTES, RECEPTOR_DEFAULT_FLOOR,
-                      DeltaE, check_acuity, check_delta_e_options, check_ppd, delta_e_launch, delta_e_records_from_bytes, observer_for, observer_names,
-                      receptor_delta_launch, scielab_launch, species_acuity)
-from .pairs import (add_inputs, check_depth, check_inputs, check_stdin, exit_status, num, open_sink, opened, sink_format,  # noqa: F401
-                    stream_map_pairs)
+                      DeltaE, ItpSide, check_acuity, check_delta_e_options, check_ppd, delta_e_launch, delta_e_records_from_bytes, itp_delta_launch,
+                      observer_for, observer_names, receptor_delta_launch, scielab_launch, species_acuity)
+from .pairs import (add_inputs, check_depth, check_inputs, check_stdin, exit_status, is_raw_input, num, open_sink, opened,  # noqa: F401
+                    sink_format, stream_map_pairs)
 from .video import add_input_options, add_output_options
 
 CSV_HEADER = "frame,de_mean,de_p50,de_p95,de_max,x,y,beyond"
@@ -98,7 +111,37 @@ def violation(args, r: DeltaE) -> Optional[str]:
     return None
 
 
+def itp_side_kind(args, path: str) -> str:
+    """What `path` is to --itp: "hdr" when it is read as raw video with a 10-bit --pix-fmt, else "sdr"."""
+    from .yuv import HDR_PIX_FMTS
+
+    return "hdr" if is_raw_input(args, path) and args.pix_fmt in HDR_PIX_FMTS else "sdr"
+
+
+def _itp_renderer(args, path: str):
+    """The renderer of one input of --itp: an HDR side with the HDR options (its decode makes the panel), every other input as
+    without --transfer, and --pix-fmt / --size only where the input is raw video."""
+    from .renderers import VideoRenderer
+
+    if itp_side_kind(args, path) == "hdr":
+        return VideoRenderer(read_path=path, write_path=None, range=args.range, pix_fmt=args.pix_fmt, size=args.size, transfer=args.transfer,
+                             tonemap=args.tonemap, peak_nits=args.peak_nits, sdr_white=args.sdr_white)
+    raw = is_raw_input(args, path)
+    return VideoRenderer(read_path=path, write_path=None, matrix=args.matrix, range=args.range, pix_fmt=args.pix_fmt if raw else None,
+                         size=args.size if raw else None)
+
+
 class _DeltaEParser(argparse.ArgumentParser):
+    def _itp(self, args):
+        """The checks of --itp that need no file; the kind of each side is left in args.itp_kinds."""
+        for flag, v in (("--ppd", args.ppd), ("--observer", args.observer), ("--acuity", args.acuity), ("--scale", args.scale)):
+            if v is not None:
+                self.error(f"--itp and {flag} do not combine: dE_ITP is taken per pixel of the frames as stored")
+        args.itp_kinds = tuple(itp_side_kind(args, p) for p in (args.a, args.b))
+        for path, kind in zip((args.a, args.b), args.itp_kinds):
+            if kind == "hdr" and args.transfer is None:
+                self.error(f"--itp: {path} is raw {args.pix_fmt} video, an HDR side: --transfer pq|hlg must name its transfer function")
+
     def _observer(self, args):
         """The metrics.Observer that --observer, --weber and --floor name, or None without them."""
         if args.observer is None:
@@ -145,6 +188,11 @@ class _DeltaEParser(argparse.ArgumentParser):
         args.depth = 2 if args.depth is None else args.depth
         check_depth(self, args)
         args.mode, args.layout = args.mode or "heat", args.layout or "map"
+        white = None
+        if args.itp:
+            self._itp(args)
+            if args.transfer is None:  # SDR sides only: --sdr-white is theirs here, and the HDR options' check must not see it
+                white, args.sdr_white = args.sdr_white, None
         try:
             args.gain, args.threshold = check_delta_e_options(args.mode, args.gain, args.threshold, args.layout)
         except ValueError as e:
@@ -159,6 +207,10 @@ class _DeltaEParser(argparse.ArgumentParser):
             if v is not None and not (math.isfinite(v) and v >= 0.0):
                 self.error(f"{flag} must be finite and at least 0 (got {v:g})")
         check_inputs(self, args)
+        if white is not None:
+            if not (math.isfinite(white) and white > 0.0):
+                self.error(f"--sdr-white must be finite and positive (got {white})")
+            args.sdr_white = white
         return args
 
 
@@ -197,6 +249,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --observer: blur both frames in linear light by the observer's acuity, a Gaussian of SIGMA pixels of the frames as "
                          "compared (0.2 to 4), before the distance is taken.  `species`: the blur the species' own rendering ends with (the ten "
                          "dichromats with a Gaussian acuity, e.g. Dog 3.5).  Default: none, the distance per pixel")
+    ap.add_argument("--itp", action="store_true",
+                    help="dE_ITP of ITU-R BT.2124 in place of dE00: defined for HDR and SDR light alike.  Raw video read with a 10-bit --pix-fmt is "
+                         "an HDR side (needs --transfer) and is compared as stored, without a tone map; every other input is an SDR side with "
+                         "code 255 at --sdr-white nits.  Does not combine with --ppd, --observer, --acuity or --scale")
     ap.add_argument("--layout", default=None, choices=list(DELTA_E_LAYOUTS), help="map (default): the map alone.  side: A | B | map, three times as wide")
     ap.add_argument("--csv", default=None, metavar="FILE",
                     help=f"write {CSV_HEADER} per frame here; without OUT the default is stdout, with OUT nothing is written unless this is given")
@@ -218,7 +274,17 @@ def stream_records(args, info: dict, fmt: Optional[str] = None) -> Iterator[Tupl
     device encoded it to ("i420", or a raw pixel format name).  info["hw"] is the output frames' (H, W) once the first item is there;
     info["longer"] names the input ("A" / "B") that had frames left over, when one had.  The loop is pairs.stream_map_pairs;
     args.observer and args.ppd pick the launch: receptor_delta_launch with an observer (and args.acuity, when there is one), scielab_launch
-    with ppd, else delta_e_launch."""
+    with ppd, else delta_e_launch.  With args.itp the launch is itp_delta_launch on the sides as they are: an HDR side's payloads as
+    stored, with its decode as the panel when there is a map."""
+    if getattr(args, "itp", False):
+        def launch_itp(ctx, sides, k, n, H, W, d_map, d_rec, stream):
+            ss = [ItpSide(s.d_in[k], s.fmt, args.transfer, s.vr.yuv_range, s.d_rgb[k] if s.d_rgb else None) if s.hdr else ItpSide(s.d_rgb[k]) for s in sides]
+            itp_delta_launch(ctx, ss[0], ss[1], n, H, W, d_map, d_rec, sdr_white=args.sdr_white, mode=args.mode, gain=args.gain,
+                             threshold=args.threshold, layout=args.layout, stream=stream)
+
+        return stream_map_pairs(args, info, "deltae", fmt, launch_itp, DELTA_E_RECORD_BYTES, delta_e_records_from_bytes, renderer=_itp_renderer,
+                                hdr=[k == "hdr" for k in args.itp_kinds], launch_sides=True)
+
     def launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, stream):
         kw = dict(mode=args.mode, gain=args.gain, threshold=args.threshold, layout=args.layout, stream=stream)
         if getattr(args, "observer", None) is not None:
@@ -275,6 +341,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     acuity = getattr(args, "acuity", None)
     blur = "" if acuity is None else f", acuity {acuity:g} px"
     what = f"RNL dS ({observer.describe()}{blur})" if observer is not None else "dE" if args.ppd is None else f"S-CIELAB dE (ppd {args.ppd:g})"
+    if getattr(args, "itp", False):
+        what = f"dE_ITP ({args.transfer + ', ' if 'hdr' in args.itp_kinds else ''}sdr white {args.sdr_white:g})"
     unit = "dS" if observer is not None else "dE"
     print(f"deltae: {frames} frames, mean {what} {num(sum_mean / frames) if frames else 'nan'}, largest {unit} {num(worst[0])}{where}, "
           f"{beyond} pixels beyond {args.threshold:g}, {frames / dt if dt > 0 else 0.0:.1f} fps", file=sys.stderr)

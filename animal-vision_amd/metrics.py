@@ -31,7 +31,12 @@ linear RGB with K Weber fractions (observer_for builds the one of a dichromat sp
 receptor_delta, receptor_delta_map and receptor_delta_values return dS in just-noticeable differences in the same DeltaE records, maps
 and value planes; `deltae --observer` is the command.  With acuity=SIGMA (csrc/receptor_acuity.hip) both frames are first
 blurred in linear light by the observer's acuity, a Gaussian of SIGMA pixels -- species_acuity gives the one a species' own rendering
-uses --, so that what the animal cannot resolve counts for little; `deltae --acuity` is the command."""
+uses --, so that what the animal cannot resolve counts for little; `deltae --acuity` is the command.
+
+dE_ITP (csrc/itp.hip; ITU-R BT.2124) is the colour difference that is defined at HDR light levels: 720 x the distance in
+ICtCp with Ct halved.  A side is an HdrFrames (10-bit PQ or HLG payloads as stored) or a uint8 sRGB array shown at sdr_white nits, in
+any mix; itp_delta_launch, itp_delta, itp_delta_map and itp_delta_values return the same DeltaE records, maps and value planes;
+`deltae --itp` is the command."""
 from __future__ import annotations
 
 import ctypes
@@ -45,6 +50,7 @@ import numpy as np
 from ._lib import AVX_DELTA_E_LAYOUTS, AVX_DELTA_E_MODES, AVX_DIFF_LAYOUTS, AVX_DIFF_MODES, AVX_METRICS_MAX_FRAMES, AVX_PIX_FMTS, FrameMetricsRecord, MsSsimRecord, PlaneMetricsRecord, lib
 from ._lib import DeltaERecord as DeltaERecordStruct
 from ._lib import DiffRecord as DiffRecordStruct
+from ._lib import ItpSide as ItpSideStruct
 from ._lib import ReceptorDesc
 from .runtime import Context, DeviceBuffer, get_context
 
@@ -1039,4 +1045,168 @@ def receptor_delta_values(a, b, observer: Observer, *, acuity=None, ctx: Optiona
     _check_observer(observer)
     acuity = _check_acuity_option(acuity)
     vals = _delta_e_chunks(a, b, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True, observer=observer, acuity=acuity)[2]
+    return vals if batched else vals[0]
+
+
+# ------------------------------------------------------------------------------------------------ dE_ITP
+ITP_DEFAULT_SDR_WHITE = 203.0
+
+
+def check_sdr_white(sdr_white) -> float:
+    """The nits of SDR code 255 as the number the library takes: finite and positive, ValueError otherwise."""
+    if isinstance(sdr_white, bool) or not isinstance(sdr_white, numbers.Real) or not (math.isfinite(sdr_white) and sdr_white > 0.0):
+        raise ValueError(f"sdr_white must be finite and positive (got {sdr_white!r})")
+    return float(sdr_white)
+
+
+class HdrFrames:
+    """An HDR side of itp_delta: `payload` holds frames of H x W in one of the four 10-bit formats as they are stored (uint8, 16-bit
+    samples as little-endian byte pairs, or uint16) -- one frame in any shape, or (N, frame bytes) --, BT.2020 Y'CbCr in `range`
+    ("limited" or "full") with `transfer` "pq" or "hlg".  ValueError for a setting the HDR decode refuses or a payload of another size."""
+
+    def __init__(self, payload, pix_fmt: str, H: int, W: int, transfer: str, range: str = "limited"):  # noqa: A002  (the decode's name for it)
+        from .yuv import frame_size, hdr_codes
+
+        hdr_codes(pix_fmt, transfer, range)
+        a = np.ascontiguousarray(payload)
+        if a.dtype == np.dtype("<u2"):
+            a = a.view(np.uint8) if a.ndim else a.reshape(1).view(np.uint8)
+        if a.dtype != np.uint8:
+            raise ValueError(f"HDR payloads are uint8 or little-endian uint16 (got {a.dtype})")
+        fsz = frame_size(pix_fmt, H, W)
+        self.batched = a.ndim == 2 and a.shape[1] == fsz
+        if not self.batched and a.size != fsz:
+            raise ValueError(f"expected {fsz} bytes per {H}x{W} {pix_fmt} frame (or an (N, {fsz}) batch), got shape {a.shape}")
+        self.payload = a if self.batched else a.reshape(1, fsz)
+        self.pix_fmt, self.H, self.W, self.transfer, self.range = pix_fmt, int(H), int(W), transfer, range
+
+    def __len__(self) -> int:
+        return len(self.payload)
+
+    def decode(self, tonemap: str = "mobius", peak_nits: float = 1000.0, sdr_white: float = ITP_DEFAULT_SDR_WHITE):
+        """The yuv.Decode that makes this side's panel frames."""
+        from .yuv import Decode
+
+        return Decode(self.pix_fmt, range=self.range, transfer=self.transfer, tonemap=tonemap, peak_nits=peak_nits, sdr_white=sdr_white)
+
+
+@dataclasses.dataclass
+class ItpSide:
+    """One side of itp_delta_launch on the device.  d_data: the frames -- uint8 sRGB H x W x 3 when pix_fmt is None, else the HDR
+    payloads as stored (pix_fmt, transfer, range as HdrFrames takes them); d_panel: for an HDR side whose launch writes a map, its
+    tone-mapped decode to uint8 RGB."""
+    d_data: DeviceBuffer
+    pix_fmt: Optional[str] = None
+    transfer: Optional[str] = None
+    range: str = "limited"
+    d_panel: Optional[DeviceBuffer] = None
+
+    @property
+    def hdr(self) -> bool:
+        return self.pix_fmt is not None
+
+    def _struct(self, n_frames: int, H: int, W: int, with_map: bool) -> ItpSideStruct:
+        from .yuv import frame_size, hdr_codes
+
+        s = ItpSideStruct(struct_size=ctypes.sizeof(ItpSideStruct), kind=1 if self.hdr else 0, data=self.d_data.ptr)
+        need = n_frames * (frame_size(self.pix_fmt, H, W) if self.hdr else H * W * 3)
+        if self.d_data.nbytes < need:
+            raise ValueError(f"{n_frames} frames of {H} x {W} need {need} bytes; the buffer holds {self.d_data.nbytes}")
+        if self.hdr:
+            s.pix_fmt, s.full_range, s.transfer = hdr_codes(self.pix_fmt, self.transfer, self.range)[:3]
+            if with_map:
+                if self.d_panel is None or self.d_panel.nbytes < n_frames * H * W * 3:
+                    raise ValueError(f"a map needs the {n_frames} decoded panel frames of an HDR side ({n_frames * H * W * 3} bytes)")
+                s.panel = self.d_panel.ptr
+        return s
+
+
+def itp_delta_launch(ctx: Context, a: ItpSide, b: ItpSide, n_frames: int, H: int, W: int, d_map: Optional[DeviceBuffer], d_rec: DeviceBuffer, *,
+                     sdr_white=ITP_DEFAULT_SDR_WHITE, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map",
+                     d_float: Optional[DeviceBuffer] = None, stream=None) -> None:
+    """delta_e_launch with dE_ITP in place of dE00 and sides of either kind: the same records, map and value plane.  sdr_white is the
+    nits of code 255 of an SDR side.  Nothing is downloaded and nothing waits."""
+    if not 1 <= n_frames <= MAX_FRAMES:
+        raise ValueError(f"n_frames must be 1..{MAX_FRAMES} (got {n_frames})")
+    if H < 1 or W < 1 or H * W >= 1 << 32:
+        raise ValueError(f"bad frame size {H} x {W}")
+    white = check_sdr_white(sdr_white)
+    g, t = _check_delta_e_buffers(n_frames, H, W, d_map, d_rec, d_float, mode, gain, threshold, layout)
+    sa, sb = a._struct(n_frames, H, W, d_map is not None), b._struct(n_frames, H, W, d_map is not None)
+    ctx._check(lib.avx_itp_delta(ctx._h, ctypes.byref(sa), ctypes.byref(sb), white, int(n_frames), int(H), int(W), AVX_DELTA_E_MODES[mode], g, t,
+                                 AVX_DELTA_E_LAYOUTS[layout], None if d_map is None else d_map.ptr, d_rec.ptr,
+                                 None if d_float is None else d_float.ptr, ctx._s(stream)))
+
+
+def _itp_sides(a, b):
+    """The two sides as (array of N rows, HdrFrames or None) each, N, H, W and whether a frame axis was given."""
+    out, shapes, batched = [], [], []
+    for name, x in (("a", a), ("b", b)):
+        if isinstance(x, HdrFrames):
+            out.append((x.payload, x))
+            shapes.append((len(x), x.H, x.W))
+            batched.append(x.batched)
+        else:
+            x = np.asarray(x)
+            if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3 or 0 in x.shape:
+                raise ValueError(f"{name}: an SDR side is uint8 H x W x 3 or N x H x W x 3; an HDR side is an HdrFrames (got {x.dtype} {x.shape})")
+            batched.append(x.ndim == 4)
+            x = np.ascontiguousarray(x if x.ndim == 4 else x[None])
+            out.append((x, None))
+            shapes.append(x.shape[:3])
+    if shapes[0] != shapes[1]:
+        raise ValueError(f"a and b differ in frames or size (a: {shapes[0][0]} of {shapes[0][1]} x {shapes[0][2]}, b: {shapes[1][0]} of {shapes[1][1]} x {shapes[1][2]})")
+    return out, shapes[0], batched[0] or batched[1]
+
+
+def _itp_chunks(a, b, sdr_white, mode, gain, threshold, layout, ctx, with_map, with_float, tonemap="mobius", peak_nits=1000.0):
+    """itp_delta, itp_delta_map and itp_delta_values: the sides in chunks of at most 16 frames -> (maps or None, records, values or
+    None, whether a frame axis was given)."""
+    white = check_sdr_white(sdr_white)
+    check_delta_e_options(mode, gain, threshold, layout)
+    sides, (N, H, W), batched = _itp_sides(a, b)
+    (xa, ha), (xb, hb) = sides
+    wide = 3 if layout == "side" else 1
+    maps = np.empty((N, H, W * wide, 3), np.uint8) if with_map else None
+    vals = np.empty((N, H, W), np.float32) if with_float else None
+    recs: List[DeltaE] = []
+    decodes = [h.decode(tonemap, peak_nits, white) if (h is not None and with_map) else None for _, h in sides]
+
+    def per_chunk(ctx, i, n, d_a, d_b, d_rec, d_map, d_val, d_pa, d_pb):
+        launch_sides = []
+        for d, h, dec, d_p in ((d_a, ha, decodes[0], d_pa), (d_b, hb, decodes[1], d_pb)):
+            if dec is not None:
+                dec.launch(ctx, d, d_p, n, H, W)
+            launch_sides.append(ItpSide(d) if h is None else ItpSide(d, h.pix_fmt, h.transfer, h.range, d_p))
+        itp_delta_launch(ctx, launch_sides[0], launch_sides[1], n, H, W, d_map, d_rec, sdr_white=white, mode=mode, gain=gain, threshold=threshold,
+                         layout=layout, d_float=d_val)
+        if with_map:
+            ctx.download(d_map, (n, H, W * wide, 3), np.uint8, out=maps[i : i + n])
+        recs.extend(delta_e_records_from_bytes(ctx.download(d_rec, (n * DELTA_E_RECORD_BYTES,), np.uint8), n))
+        if with_float:
+            ctx.download(d_val, (n, H, W), np.float32, out=vals[i : i + n])
+
+    _walk(ctx, xa, xb, per_chunk, (DELTA_E_RECORD_BYTES, H * W * 3 * wide if with_map else None, H * W * 4 if with_float else None,
+                                   H * W * 3 if decodes[0] is not None else None, H * W * 3 if decodes[1] is not None else None))
+    return maps, recs, vals, batched
+
+
+def itp_delta(a, b, sdr_white=ITP_DEFAULT_SDR_WHITE, *, threshold=DELTA_E_DEFAULT_THRESHOLD, ctx: Optional[Context] = None):
+    """dE_ITP (BT.2124) of a against b.  A side is an HdrFrames or uint8 sRGB frames (H x W x 3 or N x H x W x 3) shown with code 255
+    at sdr_white nits; any mix.  -> the DeltaE record, or a list of N when either side has a frame axis; no map is computed."""
+    recs, batched = _itp_chunks(a, b, sdr_white, "heat", None, threshold, "map", ctx, False, False)[1::2]
+    return recs if batched else recs[0]
+
+
+def itp_delta_map(a, b, *, mode: str = "heat", gain=None, threshold=DELTA_E_DEFAULT_THRESHOLD, layout: str = "map", sdr_white=ITP_DEFAULT_SDR_WHITE,
+                  tonemap: str = "mobius", peak_nits: float = 1000.0, ctx: Optional[Context] = None):
+    """delta_e_map of dE_ITP: (the map, its DeltaE record), or (N maps, a list of N records).  The dim grey and the A and B panels of
+    an HDR side are its decode with `tonemap`, `peak_nits` and `sdr_white`; an SDR side is shown as it is."""
+    maps, recs, _, batched = _itp_chunks(a, b, sdr_white, mode, gain, threshold, layout, ctx, True, False, tonemap, peak_nits)
+    return (maps, recs) if batched else (maps[0], recs[0])
+
+
+def itp_delta_values(a, b, sdr_white=ITP_DEFAULT_SDR_WHITE, *, ctx: Optional[Context] = None) -> np.ndarray:
+    """delta_e_values of dE_ITP: float32 H x W, or N x H x W when either side has a frame axis."""
+    vals, batched = _itp_chunks(a, b, sdr_white, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True)[2:]
     return vals if batched else vals[0]

@@ -15,6 +15,7 @@ from __future__ import annotations
 import argparse
 import itertools
 import math
+import os
 import sys
 from typing import Callable, Iterator, Optional, Sequence, Tuple
 
@@ -128,16 +129,24 @@ def _renderer(args, path: str):
                          transfer=args.transfer, tonemap=args.tonemap, peak_nits=args.peak_nits, sdr_white=args.sdr_white, scale=args.scale)
 
 
-def open_source(args, path: str):
-    """The opened renderer of `path` and the (H, W) of the frames it will be compared at."""
-    vr = _renderer(args, path)
+def is_raw_input(args, path: str) -> bool:
+    """Whether `path` is read as raw video with --pix-fmt and --size: every input that is not of a form that names itself -- a .y4m
+    or .npy file, synthetic:, an image directory."""
+    return args.pix_fmt is not None and not (path.lower().endswith((".y4m", ".npy")) or path.startswith("synthetic:") or os.path.isdir(path))
+
+
+def open_source(args, path: str, renderer: Optional[Callable] = None):
+    """The opened renderer of `path` and the (H, W) of the frames it will be compared at; renderer(args, path) makes it (default: the
+    input options applied to every input alike)."""
+    make = renderer or _renderer
+    vr = make(args, path)
     vr.open()
     hw = vr.out_hw
     if hw is None:  # synthetic:, .npy or an image directory: peek at the first frame, then start over
         first = vr.get_image()
         hw = None if first is None else tuple(first.shape[:2])
         vr.close()
-        vr = _renderer(args, path)
+        vr = make(args, path)
         vr.open()
     return vr, hw
 
@@ -152,19 +161,20 @@ def copy(ctx, kind: str, dst, src, nbytes: int, stream) -> None:
 class Side:
     """One input: its staging (pinned) and device buffers, one of each per buffer set.  An input that hands over payloads (.y4m or
     raw SDR video without --scale) sends those across and decodes them into d_rgb on the device; with stored=True (--planes yuv)
-    payloads are all it takes, d_in holds them as they are stored and there is no d_rgb."""
+    payloads are all it takes, d_in holds them as they are stored and there is no d_rgb.  hdr=True (`deltae --itp`) keeps both: the
+    HDR payloads as stored in d_in, which the kernel reads, and -- with panel=True, for a map -- their tone-mapped decode in d_rgb."""
 
-    def __init__(self, ctx, vr, H: int, W: int, batch: int, sets: int, name: str, stored: bool = False):
+    def __init__(self, ctx, vr, H: int, W: int, batch: int, sets: int, name: str, stored: bool = False, hdr: bool = False, panel: bool = True):
         from .yuv import frame_size
 
         if stored and vr.yuv_hw is None:
             raise SystemExit(f"{name}: {vr.read_path}: --planes yuv needs a .y4m or raw video input")
-        self.ctx, self.vr, self.H, self.W, self.name, self.stored = ctx, vr, H, W, name, stored
-        self.payload = stored or (vr.yuv_hw is not None and vr.scale is None and vr.transfer is None)
+        self.ctx, self.vr, self.H, self.W, self.name, self.stored, self.hdr = ctx, vr, H, W, name, stored, hdr
+        self.payload = stored or hdr or (vr.yuv_hw is not None and vr.scale is None and vr.transfer is None)
         self.fmt = vr.yuv_pix_fmt or "yuv420p"  # a .y4m is I420
         self.unit = frame_size(self.fmt, H, W) if self.payload else H * W * 3
         self.host = [ctx.pinned((batch, self.unit), np.uint8) for _ in range(sets)]
-        self.d_rgb = [] if stored else [ctx.malloc(batch * H * W * 3) for _ in range(sets)]
+        self.d_rgb = [] if stored or (hdr and not panel) else [ctx.malloc(batch * H * W * 3) for _ in range(sets)]
         self.d_in = [ctx.malloc(batch * self.unit) for _ in range(sets)] if self.payload else self.d_rgb
 
     def fill(self, k: int, limit: int) -> int:
@@ -184,7 +194,7 @@ class Side:
     def enqueue(self, k: int, n: int, stream) -> None:
         """Upload set k's n staged frames and, where they are payloads to decode, decode them into d_rgb[k]."""
         copy(self.ctx, "h2d", self.d_in[k], self.host[k], n * self.unit, stream)
-        if self.payload and not self.stored:
+        if self.payload and self.d_rgb:
             self.vr.decode.launch(self.ctx, self.d_in[k], self.d_rgb[k], n, self.H, self.W, stream)
 
     def free(self) -> None:
@@ -193,12 +203,16 @@ class Side:
 
 
 # ------------------------------------------------------------------------------------------------ the device loop
-def stream_pairs(args, info: dict, name: str, prepare: Callable, stored: bool = False) -> Iterator:
+def stream_pairs(args, info: dict, name: str, prepare: Callable, stored: bool = False, renderer: Optional[Callable] = None,
+                 hdr: Sequence[bool] = (False, False), panels: bool = True) -> Iterator:
     """What `harvest` makes of the common prefix of args.a and args.b, in frame order (the module's docstring has prepare and what it
-    returns).  `name` is the command's, for messages; `stored` compares payloads as stored (Side).  info["longer"] names the input
-    ("A" / "B") that had frames left over, when one had.  Buffers and streams are released however the generator ends."""
-    va, hwa = open_source(args, args.a)
-    vb, hwb = open_source(args, args.b)
+    returns).  `name` is the command's, for messages; `stored` compares payloads as stored (Side); renderer(args, path) opens an input
+    (open_source); hdr names the inputs that are HDR sides, which keep their payloads, and panels whether those are also decoded (Side).
+    info["longer"] names the input ("A" / "B") that had frames left over, when one had.  Buffers and streams are released however the
+    generator ends."""
+    how = {} if renderer is None else {"renderer": renderer}  # without one the call is open_source(args, path), as it was
+    va, hwa = open_source(args, args.a, **how)
+    vb, hwb = open_source(args, args.b, **how)
     ctx, sides, streams, bufs = None, [], [], []
     try:
         if hwa is not None and hwb is not None and tuple(hwa) != tuple(hwb):
@@ -210,8 +224,8 @@ def stream_pairs(args, info: dict, name: str, prepare: Callable, stored: bool = 
         H, W = hwa
         outputs, enqueue, harvest = prepare(H, W)
         ctx, batch, sets = get_context(), args.batch, args.depth or 2
-        for vr in (va, vb):
-            sides.append(Side(ctx, vr, H, W, batch, sets, name, stored))
+        for vr, is_hdr in zip((va, vb), hdr):
+            sides.append(Side(ctx, vr, H, W, batch, sets, name, stored, is_hdr, panels))
         d_out, h_out = [[] for _ in range(sets)], [[] for _ in range(sets)]
         for k in range(sets):
             streams.append(ctx.stream_create())
@@ -258,12 +272,15 @@ def stream_pairs(args, info: dict, name: str, prepare: Callable, stored: bool = 
 
 
 def stream_map_pairs(args, info: dict, name: str, fmt: Optional[str], launch: Callable, rec_bytes: int, records: Callable,
-                     check_size: Optional[Callable] = None) -> Iterator[Tuple[Optional[np.ndarray], object]]:
+                     check_size: Optional[Callable] = None, renderer: Optional[Callable] = None, hdr: Sequence[bool] = (False, False),
+                     launch_sides: bool = False) -> Iterator[Tuple[Optional[np.ndarray], object]]:
     """stream_pairs for a command that writes a map per pair (`diff`, `deltae`): (output frame, record) of every pair.  Without
     args.out the frame is None and there is no map.  Otherwise it is RGB uint8 H x W x 3 (H x 3W x 3 with --layout side) when fmt is
     None, else the flat payload the device encoded the map to ("i420", or a raw pixel format name).  info["hw"] is the output
     frames' (H, W) once the first item is there.  launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, stream) enqueues the command's
-    kernel (d_map: None without a map); records(bytes, n) reads n records of rec_bytes; check_size(H, W) refuses a frame size."""
+    kernel (d_map: None without a map); records(bytes, n) reads n records of rec_bytes; check_size(H, W) refuses a frame size.
+    renderer and hdr are stream_pairs'; with launch_sides the kernel reads the sides as they are (`deltae --itp`: an HDR side's payloads)
+    and launch is called as launch(ctx, sides, k, n, H, W, d_map, d_rec, stream) with the two Sides and the buffer set k."""
     from .yuv import Encode
 
     def prepare(H, W):
@@ -279,7 +296,10 @@ def stream_map_pairs(args, info: dict, name: str, fmt: Optional[str], launch: Ca
 
         def enqueue(k, n, stream, sides, outs):
             ctx = sides[0].ctx
-            launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, outs[0] if with_map else None, outs[-1], stream)
+            if launch_sides:
+                launch(ctx, sides, k, n, H, W, outs[0] if with_map else None, outs[-1], stream)
+            else:
+                launch(ctx, sides[0].d_rgb[k], sides[1].d_rgb[k], n, H, W, outs[0] if with_map else None, outs[-1], stream)
             if encode is not None:
                 encode.launch(ctx, outs[0], outs[1], n, H, Wo, stream)
 
@@ -292,4 +312,4 @@ def stream_map_pairs(args, info: dict, name: str, fmt: Optional[str], launch: Ca
 
         return outputs, enqueue, harvest
 
-    return stream_pairs(args, info, name, prepare)
+    return stream_pairs(args, info, name, prepare, renderer=renderer, hdr=hdr, panels=args.out is not None)

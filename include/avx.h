@@ -716,6 +716,64 @@ int avx_receptor_acuity_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_
                            double sigma, int mode, float gain, float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* ds_out,
                            void* stream);
 
+/* dE_ITP of ITU-R BT.2124 (csrc/itp.hip): 720 x the Euclidean distance in ICtCp (BT.2100) with Ct halved, about 1 per
+ * just-noticeable difference, defined for HDR and SDR light levels alike -- per pixel of two batches of frames, as float32 values, as
+ * a picture and as a record per frame, which are avx_delta_e_u8's in every respect but the value.  A side is one of two kinds; any
+ * mix is legal, and two HDR sides may differ in format, subsampling, range and transfer.
+ *   AVX_ITP_HDR: data = n_frames payloads of avx_yuv_frame_size(pix_fmt, H, W) bytes in one of the four 10-bit formats, BT.2020
+ *     non-constant-luminance Y'CbCr, limited (full_range 0) or full range, transfer AVX_TRANSFER_PQ or _HLG.  Samples, ranges and
+ *     chroma are read exactly as avx_yuv_hdr_to_rgb_u8 reads them: y = (float)(Y - yo) * ys, cb = (float)(U - 512) * cs, cr likewise
+ *     (yo = 64, ys = 1/876, cs = 1/896 limited; 0, 1/1023, 1/1023 full), the chroma block's samples for every pixel of the block,
+ *     E'_R = clamp01(y + rv cr), E'_G = clamp01(y + (gu cb + gv cr)), E'_B = clamp01(y + bu cb) with the BT.2020 coefficients rounded
+ *     once.  x = display light / 10000 nits per channel.  PQ: t = log2(E') * (float)(ln 2 / m2), h = 1 + t/6, then h = 1 + (t * (1/k)) h
+ *     for k = 5, 4, 3, 2, u = -(t h) (= 1 - E'^(1/m2) by the series of expm1: |t| <= 0.09 for every code above 0),
+ *     x = pw(max((1 - c1) - u, 0) * rcp((1 - c1) + c3 u), 1/m1), and 0 at E' = 0: the EOTF's p - c1 and c2 - c3 p without the
+ *     cancellation that costs the plain form 6e-5 of x near the top.
+ *     HLG: s = E'^2 / 3 where E' <= 1/2, else (exp2((E' - c) log2(e) / a) + b) / 12, and x = (0.1 pw((0.2627 s_R + 0.6780 s_G) +
+ *     0.0593 s_B, 0.2)) * s: the OOTF at 1000 nits, gamma 1.2.  There is no tone map and no division by sdr_white.
+ *   AVX_ITP_SDR: data = n_frames H x W x 3 uint8 sRGB frames with BT.709 primaries, code 255 shown at sdr_white nits: l = k lin(code)
+ *     with k = (float)(sdr_white / 10000) and lin the 256-entry decode table of avx_delta_e_u8, then BT.709 -> BT.2020 primaries
+ *     anchored on green, x_i = (l_G + N_i0 (l_R - l_G)) + N_i2 (l_B - l_G), N the inverse of the BT.2020 -> BT.709 matrix of
+ *     avx_yuv_hdr_to_rgb_u8 formed in double and rounded once: a grey stays exactly grey.
+ * pw(v, e) = exp2(e * log2(v)) on the hardware's v_exp_f32 and v_log_f32 for v > 0, and 0 otherwise; rcp is v_rcp_f32.
+ * From x (BT.2020): LMS in the same anchored form, L = (x_G + (1688/4096) (x_R - x_G)) + (262/4096) (x_B - x_G), M with 683 and 462,
+ * S with 99 and 3688 (the rows of the BT.2100 matrix sum to 4096).  L', M', S' are the PQ inverse EOTF in the form
+ *     p = pw(v, m1);  n = (1 - c1) * (1 - p);  d = 1 + c3 * p;  s = n * rcp((d + d) - n);  z = s * s;
+ *     v' = exp2(e * (s * (1 + z * (1/3 + z * (1/5 + z * (1/7 + z * (1/9))))))),  e = (float)(-2 m2 log2(e)):
+ * with q = (c1 + c2 p) / (1 + c3 p), 1 - q = n / d is formed without cancellation (c1 = c3 - c2 + 1) and ln q = -2 atanh(s); the
+ * plain exp2(m2 * log2(q)) multiplies the rounding of the logarithm by m2 = 78.84.  Then, with the factor 720 folded in,
+ *     I* = 360 (L' + M'),  T* = kT0 (L' - M') + kT2 (S' - M'),  P* = kP0 (L' - M') + kP2 (S' - M'),
+ *     kT0 = 360 * 6610/4096, kT2 = 360 * 7003/4096, kP0 = 720 * 17933/4096, kP2 = -720 * 543/4096 (each rounded once),
+ * and dE_ITP = |dI*| where dT* == 0 and dP* == 0, else sqrt((dI*^2 + dT*^2) + dP*^2) with v_sqrt_f32.  All arithmetic is float32 with
+ * one rounding per operation and nothing fused.
+ * What follows: equal L', M', S' give T* = P* = 0 exactly, so any two achromatic pixels (an SDR grey; an HDR pixel with U = V = 512)
+ * differ by exactly |I*_A - I*_B| = 720 |dI|, one float32 subtraction; a pixel whose samples are equal on two sides of one kind,
+ * range and transfer (the formats may differ) is exactly 0 and skips the arithmetic.
+ * sdr_white: finite and positive; it is read by SDR sides only.  n_frames, H, W, mode, gain, threshold, layout, map_out, rec_dev,
+ * de_out and stream are avx_delta_e_u8's, and so are the record, the quantiser, the palette, the workgroup's 4096 consecutive pixels
+ * and the order of the float64 sum: a frame's record, map and values do not depend on its batch, its place in it, or the alignment of
+ * the buffers (payloads are staged in 16-byte, 8-byte or sample-sized loads, whichever the address and the length of a run admit).
+ * The dim grey of the heat mode and the A and B panels of the side layout come from `panel`: n_frames H x W x 3 uint8 frames, for an
+ * HDR side its tone-mapped decode (avx_yuv_hdr_to_rgb_u8); an SDR side is its own panel and its `panel` is not read.  Panels are
+ * required only when map_out is given.
+ * AVX_ERR_INVALID (avx_last_error starts with this function's name) for everything avx_delta_e_u8 and avx_yuv_hdr_to_rgb_u8 refuse of
+ * these arguments (an HDR side above 32768 x 32768 or at an odd address included), and for a NULL side or one of the wrong
+ * struct_size, a bad kind, an 8-bit format or GRAY on an HDR side, an HDR side without a panel when map_out is given, map_out
+ * overlapping a side's data or panel, and a non-finite or non-positive sdr_white; nothing is launched or written then. */
+enum avx_itp_kind { AVX_ITP_SDR = 0, AVX_ITP_HDR = 1 };
+typedef struct avx_itp_side {
+    uint32_t struct_size;  /* sizeof(avx_itp_side) */
+    int32_t kind;          /* enum avx_itp_kind */
+    const uint8_t* data;   /* HDR: the payloads as stored; SDR: the frames */
+    const uint8_t* panel;  /* HDR, with map_out: the uint8 RGB frames the map shows; otherwise not read */
+    int32_t pix_fmt;       /* HDR: enum avx_pix_fmt, a 10-bit format */
+    int32_t full_range;    /* HDR: 0 limited, 1 full */
+    int32_t transfer;      /* HDR: enum avx_transfer */
+    int32_t reserved;      /* 0 */
+} avx_itp_side;
+int avx_itp_delta(avx_ctx* ctx, const avx_itp_side* a, const avx_itp_side* b, double sdr_white, int n_frames, int H, int W, int mode, float gain,
+                  float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream);
+
 /* cv2.remap(src, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, borderValue) on K float32 planes that share two
  * per-pixel float32 maps (anableps.py:217-226): coordinates quantised to 1/32 px like OpenCV. */
 int avx_remap_linear_planes(avx_ctx* ctx, const float* src_planes, int K, int H, int W, const float* mapx_dev,

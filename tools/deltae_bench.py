@@ -1,7 +1,7 @@
 """Time of the colour difference kernels.  Not part of bench.py.
 
   python tools/deltae_bench.py kernel [--reps 7] [--ppd 60 [--ppd 30 ...]] [--observer Dog [--observer HoneyBee ...]]
-                                      [--acuity species [--acuity 1.0 ...]]
+                                      [--acuity species [--acuity 1.0 ...]] [--itp]
       avx_delta_e_u8 on frames resident on the device, 4K and 1080p, batches of 8: records only (no map), the heat map, the heat map
       side by side, and records only on a pair whose upper half is identical (those pixels are 0 by definition and skip the
       arithmetic), interleaved in one process with avx_frame_metrics_u8(with_ssim = 1) on the same frames -- per repetition each form
@@ -19,6 +19,10 @@
       heat map; its lines also carry the ratio to the observer's per-pixel records, the taps, and the fused multiply-adds per pixel pair
       of the two blur passes by arithmetic -- 6 planes x k taps x (1 + (32 + 2R) / 32): the column pass, and the row pass on the tile's
       32 rows and its 2R halo rows -- with the rate they imply.
+      --itp adds avx_itp_delta to the same interleaved repetitions, records only: p010le PQ against p010le PQ, p010le
+      HLG against p010le HLG (noise payloads against the same samples +-2 codes, so every wave does the arithmetic) and the PQ payload
+      against the 8-bit frames as an SDR side at 203 nits, and the PQ pair once more with the heat map; its lines also carry the
+      ratio to the plain dE records, the bytes of the two sides per pixel and the time those bytes take at the 6.29 TB/s copy rate.
   python tools/deltae_bench.py command [--frames 32] [--reps 3] [--dir DIR] [--ppd X]
       Two 4K nv12 files of `frames` frames in DIR (default: /dev/shm when there is one, so they are read from and written to memory)
       through python -m animal_vision_amd.deltae's main(), --batch 8 --depth 2: no OUT (statistics only), heat into a raw nv12 file (the
@@ -52,8 +56,8 @@ def _pair(n, H, W, seed=0):
 
 def kernel(args):
     from animal_vision_amd.dichromat import cv_auto_ksize
-    from animal_vision_amd.metrics import (DELTA_E_RECORD_BYTES, RECORD_BYTES, check_acuity, delta_e_launch, frame_metrics_launch, observer_for,
-                                           receptor_delta_launch, scielab_launch, species_acuity)
+    from animal_vision_amd.metrics import (DELTA_E_RECORD_BYTES, RECORD_BYTES, ItpSide, check_acuity, delta_e_launch, frame_metrics_launch, itp_delta_launch,
+                                           observer_for, receptor_delta_launch, scielab_launch, species_acuity)
     from animal_vision_amd.runtime import get_context
 
     ctx, n = get_context(), 8
@@ -91,6 +95,21 @@ def kernel(args):
                     print(f"deltae_bench: --acuity {text} skipped for {who}: {e}", file=sys.stderr)
                     continue
                 forms += [(f"acuity {who} sigma {sigma:g} records", blurred(obs, sigma, None)), (f"acuity {who} sigma {sigma:g} heat map", blurred(obs, sigma, d_out))]
+        extra = []
+        if args.itp:
+            rng = np.random.default_rng(1)
+            ya = rng.integers(0, 1024, (n, H * W * 3 // 2), dtype=np.int16)  # p010le: 1.5 samples per pixel, the value in the top 10 bits
+            yb = np.clip(ya + rng.integers(-2, 3, ya.shape, dtype=np.int16), 0, 1023)
+            d_ya, d_yb, d_pan = ctx.upload((ya << 6).astype("<u2")), ctx.upload((yb << 6).astype("<u2")), ctx.upload(a)
+            extra = [d_ya, d_yb, d_pan]
+
+            def itp(sa, sb, d_map):
+                return lambda: itp_delta_launch(ctx, sa, sb, n, H, W, d_map, d_rec, mode="heat", layout="map")
+
+            for tr in ("pq", "hlg"):
+                forms.append((f"itp {tr} - {tr} records", itp(ItpSide(d_ya, "p010le", tr), ItpSide(d_yb, "p010le", tr), None)))
+            forms += [("itp pq - sdr records", itp(ItpSide(d_ya, "p010le", "pq"), ItpSide(d_b), None)),
+                      ("itp pq - pq heat map", itp(ItpSide(d_ya, "p010le", "pq", d_panel=d_pan), ItpSide(d_yb, "p010le", "pq", d_panel=d_pan), d_out))]
         forms.append(("ssim record", lambda: frame_metrics_launch(ctx, d_a, d_b, n, H, W, d_metrics, ssim=True)))
         times = [[] for _ in forms]
         for _, r in forms:  # warm-up: code objects are loaded and the workspaces are sized here
@@ -119,8 +138,11 @@ def kernel(args):
                 base = [t2 for (f2, _), t2 in zip(forms, times) if f2 == f"receptor {who} records"][0]
                 line.update(over_receptor_records=round(med / float(np.median(base)), 2), taps=k, blur_fma_per_px=round(fma, 1),
                             blur_tflops=round(2 * fma * H * W / med * 1e-6, 2))
+            if form.startswith("itp"):
+                nbytes = 6.0  # 3 B/px of p010le on either side, or 3 B/px of p010le and 3 B/px of RGB
+                line.update(over_plain_records=round(med / plain, 2), side_bytes_per_px=nbytes, us_per_frame_at_6p29_TBps=round(nbytes * H * W / 6.29e6, 1))
             print(json.dumps(line), flush=True)
-        for d in (d_a, d_b, d_half, d_out, d_rec, d_metrics):
+        for d in [d_a, d_b, d_half, d_out, d_rec, d_metrics] + extra:
             d.free()
 
 
@@ -169,6 +191,7 @@ def main():
                    help="add avx_receptor_delta_u8 for this observer, a dichromat's display name or HoneyBee (repeatable)")
     k.add_argument("--acuity", action="append", default=None, metavar="SIGMA|species",
                    help="add avx_receptor_acuity_u8 at this sigma in pixels, or at each observer's own, for every --observer (repeatable)")
+    k.add_argument("--itp", action="store_true", help="add avx_itp_delta: p010le PQ and HLG pairs, and PQ against an SDR side")
     c = sub.add_parser("command")
     c.add_argument("--frames", type=int, default=32)
     c.add_argument("--reps", type=int, default=3)

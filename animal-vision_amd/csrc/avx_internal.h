@@ -112,6 +112,9 @@ int avx_geom_area_tables(avx_ctx* ctx, avx_ws* ws, hipStream_t s, int H, int W, 
 int avx_metrics_scale0_launch(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, double* partials,
                               avx_frame_metrics* out_dev, avx_ms_ssim_rec* ms, hipStream_t s);
 size_t avx_metrics_scale0_tiles(int H, int W);
+// delta_e.hip, for the five colour difference entries (delta_e_common.h's de_finish): k_delta_e_final on n_frames records, each with
+// n_partials float64 partials in `partials`
+int avx_delta_e_final_launch(avx_ctx* ctx, const double* partials, size_t n_partials, int W, avx_delta_e_rec* rec_dev, int n_frames, hipStream_t s);
 // uv.hip: the UV path's small per-stream scratch (ws->uv_small), zero at rest where the kernels need it so: one set of radix-select histograms
 // (kSelMax x 2048 bins), kSelMax select states, the ticket block (ticket_is_last's 1 + 32 counters; word 56: k_sel_pass_up's candidate count), 16 percentiles.
 struct Stat3;

@@ -10,15 +10,16 @@
 // form, cbrtf) and dE00 in radians throughout (the four cosines of T from one sincosf by the multiple-angle formulas).  A pixel whose
 // codes are equal is 0 by definition and skips the arithmetic; the branch is taken by a wave whose 64 pixels are all equal.  The
 // arithmetic is the vector unit's: nothing here is bound by bytes.
-// The map's quantiser is the walk's too, float32 with one rounding per operation and nothing fused:
-// v = fminf(floorf(__fadd_rn(__fmul_rn(G, x), 0.5f)), 255.0f) with x = __fsub_rn(dE, T) in the heat mode and dE in the plain mode.
+// The map's quantiser is delta_e_common.h's de_map_colour, float32 with one rounding per operation and nothing fused (its __fsub_rn(),
+// __fmul_rn() and __fadd_rn() name them): v = min(floor(G x + 0.5), 255) with x = dE - T in the heat mode and dE in the plain mode.
 // The record: the histogram is counted in LDS (zeros in a register) and flushed with one atomic per non-empty bin; a thread adds its
 // pixels' dE in float64 in pixel order, the workgroup sums in ssim_window.h's fixed order into partials[frame][chunk], and
 // k_delta_e_final adds a frame's partials in index order: no float atomics.  The largest dE is one 64-bit integer maximum over
 // (float bits of dE << 32) | (0xFFFFFFFF - pixel index): dE is never negative, so its bits order as its value, and among equals the
 // earlier pixel wins; the key lies in the bytes of (max_de, max_x) until k_delta_e_final takes it apart.
-// The Lab transfer function, ciede2000, the key, the colour of a map pixel, the workgroup's share of the record and k_delta_e_final are
-// delta_e_common.h's, shared with scielab.hip.
+// The Lab transfer function, ciede2000, the key, a thread's tally, the workgroup's share of the record, the map's colour and the
+// host side's checks and launch frame are delta_e_common.h's, shared with the four other colour difference entries.  k_delta_e_final,
+// which finishes the records of all five, is defined here and nowhere else: they reach it through avx_delta_e_final_launch.
 #include "delta_e_common.h"
 #include "delta_e_walk.h"
 
@@ -55,13 +56,27 @@ __global__ __launch_bounds__(kThreads) void k_delta_e(DeArgs p) {
     de_chunk_walk<VEC>(p, Ciede());
 }
 
+// grid (frames): the body is delta_e_common.h's de_final
+__global__ __launch_bounds__(kThreads) void k_delta_e_final(const double* __restrict__ partials, size_t n_partials, int W, avx_delta_e_rec* __restrict__ rec) {
+    de_final(partials, n_partials, W, rec);
+}
+
+static_assert(sizeof(avx_delta_e_rec) == 1048 && offsetof(avx_delta_e_rec, max_de) == 1032, "avx_delta_e_rec: the key needs 8 aligned bytes at max_de");
+
 }  // namespace
+
+int avx_delta_e_final_launch(avx_ctx* ctx, const double* partials, size_t n_partials, int W, avx_delta_e_rec* rec_dev, int n_frames, hipStream_t s) {
+    hipLaunchKernelGGL(k_delta_e_final, dim3(n_frames), dim3(kThreads), 0, s, partials, n_partials, W, rec_dev);
+    AVX_HIP(ctx, hipGetLastError());
+    return AVX_OK;
+}
 
 extern "C" int avx_delta_e_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, int mode, float gain, float threshold,
                               int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream) {
+    static const char fn[] = "avx_delta_e_u8";
     if (!ctx) return AVX_ERR_INVALID;
-    const int rc = de_walk_check(ctx, "avx_delta_e_u8", a_hwc, b_hwc, n_frames, H, W, mode, gain, threshold, layout, map_out, rec_dev, de_out);
-    if (rc) return rc;
+    if (const int rc = de_check_options(ctx, fn, n_frames, H, W, mode, gain, threshold, layout, rec_dev, de_out)) return rc;
+    if (const int rc = de_check_pair(ctx, fn, a_hwc, b_hwc, n_frames, H, W, layout, map_out)) return rc;
     return de_walk_launch(ctx, a_hwc, b_hwc, n_frames, H, W, mode, gain, threshold, layout, map_out, rec_dev, de_out, stream,
                           [](bool vec, dim3 grid, hipStream_t s, const DeArgs& p) {
                               if (vec) hipLaunchKernelGGL(k_delta_e<true>, grid, dim3(kThreads), 0, s, p);

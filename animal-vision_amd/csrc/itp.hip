@@ -13,9 +13,9 @@
 // kind, the format and the transfer of a side are kernel arguments, uniform over the launch: the branches on them are scalar.
 // A pixel whose samples are equal on two sides of one kind, range and transfer is 0 by definition and skips the arithmetic; the
 // branch is taken by a wave whose 64 pixels are all equal.
-// The map's bytes go back through LDS; the A and B panels of the side layout are copied from the callers' panel frames.  The record,
-// the key of the maximum, the palette and k_delta_e_final are delta_e_common.h's; HLG's inverse OETF, pw and the constants of the curves
-// are yuv_hdr_px.h's.
+// The map's bytes go back through LDS; the A and B panels of the side layout are copied from the callers' panel frames.  A thread's
+// tally, the workgroup's share of the record, the map's quantiser and colour, the rows of the side layout and the host side's common
+// checks and launch frame are delta_e_common.h's; HLG's inverse OETF, pw and the constants of the curves are yuv_hdr_px.h's.
 #include "delta_e_common.h"
 #include "yuv_hdr_px.h"
 
@@ -43,12 +43,8 @@ struct ItpC {
 struct ItpArgs {
     ItpSide a, b;
     ItpC c;
-    uint8_t* out;      // NULL: no map
-    float* de;         // NULL: no float plane
-    double* partials;  // [frame][chunk]
-    avx_delta_e_rec* rec;
-    int H, W, mode, side, same;  // same: equal samples mean equal pixels
-    float gain, threshold;
+    int same;  // equal samples mean equal pixels
+    DeOut o;   // partials: [frame][chunk]
 };
 
 // BT.2100 LMS over 4096 in the form anchored on green (every row sums to 4096), and ICtCp scaled by 720 with Ct halved, formed
@@ -170,37 +166,33 @@ __global__ __launch_bounds__(kThreads) void k_itp(ItpArgs p) {
     __shared__ __attribute__((aligned(16))) uint8_t sb[kChunk * 3];
     __shared__ __attribute__((aligned(16))) uint8_t so[kChunk * 3];
     __shared__ float lut[256];
-    __shared__ unsigned hist[256];
-    __shared__ double red[kThreads / 64];
-    __shared__ unsigned long long wred[kThreads / 64];
-    __shared__ unsigned bred[kThreads / 64];
+    __shared__ DeRecLds lds;
+    const DeOut& o = p.o;
     const int tid = threadIdx.x, f = blockIdx.y;
-    const size_t npx = (size_t)p.H * p.W;  // below 2^32
+    const size_t npx = (size_t)o.H * o.W;  // below 2^32
     const size_t base = (size_t)blockIdx.x * kChunk;
     const int valid = (int)min((size_t)kChunk, npx - base);  // pixels of this chunk
     const uint8_t* fa = p.a.data + (size_t)f * p.a.fsz;
     const uint8_t* fb = p.b.data + (size_t)f * p.b.fsz;
     lut[tid] = __uint_as_float(kLabDecodeBits[tid]);
-    hist[tid] = 0;
+    lds.hist[tid] = 0;
     if (p.a.hdr) stage_run(sa, fa + base * 2, valid * 2, 2);
     else stage_run(sa, fa + base * 3, valid * 3, 1);
     if (p.b.hdr) stage_run(sb, fb + base * 2, valid * 2, 2);
     else stage_run(sb, fb + base * 3, valid * 3, 1);
     __syncthreads();
 
-    const float G = p.gain, T = p.threshold;
+    const float G = o.gain, T = o.threshold;
     const bool any_hdr = p.a.hdr || p.b.hdr;
-    const uint8_t* pa = p.out ? p.a.panel + ((size_t)f * npx + base) * 3 : nullptr;  // the chunk's pixels of A's panel
-    double sum = 0.0;
-    unsigned long long key = 0;
-    unsigned beyond = 0, zeros = 0;
-    float* de_out = p.de ? p.de + (size_t)f * npx + base : nullptr;
+    const uint8_t* pa = o.out ? p.a.panel + ((size_t)f * npx + base) * 3 : nullptr;  // the chunk's pixels of A's panel
+    DeTally tally;
+    float* de_out = o.de ? o.de + (size_t)f * npx + base : nullptr;
 #pragma unroll 1
     for (int i = tid; i < valid; i += kThreads) {
         int y = 0, x = 0;
         if (any_hdr) {
             const uint32_t idx = (uint32_t)(base + i);
-            y = (int)(idx / (uint32_t)p.W), x = (int)(idx - (uint32_t)y * (uint32_t)p.W);
+            y = (int)(idx / (uint32_t)o.W), x = (int)(idx - (uint32_t)y * (uint32_t)o.W);
         }
         int a0, a1, a2, b0, b1, b2;
         side_samples(p.a, sa, fa, i, y, x, a0, a1, a2);
@@ -213,56 +205,30 @@ __global__ __launch_bounds__(kThreads) void k_itp(ItpArgs p) {
             const float di = ia - ib, dt = ta - tb, dp = qa - qb;
             de = (dt == 0.0f && dp == 0.0f) ? fabsf(di) : fsqrt((di * di + dt * dt) + dp * dp);
         }
-        const int bin = min(255, (int)(de + de));  // floor(2 dE): dE >= 0
-        if (bin == 0) ++zeros;
-        else atomicAdd(&hist[bin], 1u);
-        sum += (double)de;
-        beyond += de > T ? 1u : 0u;
-        const unsigned long long k = de_key(de, (uint32_t)(base + i));
-        key = k > key ? k : key;
+        tally.add(de, (uint32_t)(base + i), T, lds.hist);
         if (de_out) de_out[i] = de;
-        if (p.out) {
-            // the quantiser: float32, one rounding per operation, multiply and add never fused
-            const float xq = p.mode == AVX_DELTA_E_HEAT ? __fsub_rn(de, T) : de;
-            const float v = fminf(floorf(__fadd_rn(__fmul_rn(G, xq), 0.5f)), 255.0f);
+        if (o.out) {
             uint32_t r, g, b;
-            de_colour(v, de, T, p.mode, pa[3 * i], pa[3 * i + 1], pa[3 * i + 2], r, g, b);
+            de_map_colour(de, G, T, o.mode, pa[3 * i], pa[3 * i + 1], pa[3 * i + 2], r, g, b);
             so[3 * i] = (uint8_t)r, so[3 * i + 1] = (uint8_t)g, so[3 * i + 2] = (uint8_t)b;
         }
     }
     __syncthreads();
 
     // ---- the panels out ----
-    if (p.out) {
-        const size_t row = (size_t)p.W * 3;  // bytes of a panel's row
-        if (!p.side) {
-            unstage_run(p.out + ((size_t)f * npx + base) * 3, so, valid * 3);
-        } else {
-            uint8_t* fo = p.out + (size_t)f * npx * 9;
-            const uint8_t* pb = p.b.panel + ((size_t)f * npx + base) * 3;
-            const bool vec = p.W % 16 == 0 && (((uintptr_t)p.out | (uintptr_t)p.a.panel | (uintptr_t)p.b.panel) & 15) == 0;
-            if (vec) {  // valid is a multiple of 16; a 16-byte run lies within one row (row % 48 == 0)
-                for (int j = tid; j < valid * 3 / 16; j += kThreads) {
-                    const size_t q = base * 3 + (size_t)j * 16;
-                    const size_t yy = q / row, xb = q - yy * row;
-                    uint8_t* dst = fo + yy * (3 * row) + xb;
-                    *reinterpret_cast<uint4*>(dst) = reinterpret_cast<const uint4*>(pa)[j];
-                    *reinterpret_cast<uint4*>(dst + row) = reinterpret_cast<const uint4*>(pb)[j];
-                    *reinterpret_cast<uint4*>(dst + 2 * row) = reinterpret_cast<const uint4*>(so)[j];
-                }
-            } else {
-                for (int j = tid; j < valid * 3; j += kThreads) {
-                    const size_t q = base * 3 + (size_t)j;
-                    const size_t yy = q / row, xb = q - yy * row;
-                    uint8_t* dst = fo + yy * (3 * row) + xb;
-                    dst[0] = pa[j], dst[row] = pb[j], dst[2 * row] = so[j];
-                }
-            }
-        }
+    if (o.out && !o.side) {
+        unstage_run(o.out + ((size_t)f * npx + base) * 3, so, valid * 3);
+    } else if (o.out) {
+        uint8_t* fo = o.out + (size_t)f * npx * 9;
+        const uint8_t* pb = p.b.panel + ((size_t)f * npx + base) * 3;
+        const size_t row = (size_t)o.W * 3;  // bytes of a panel's row
+        const bool vec = o.W % 16 == 0 && (((uintptr_t)o.out | (uintptr_t)p.a.panel | (uintptr_t)p.b.panel) & 15) == 0;
+        if (vec) de_side_rows_out<true>(fo, row, base, valid, pa, pb, so);
+        else de_side_rows_out<false>(fo, row, base, valid, pa, pb, so);
     }
 
     // ---- the record ----
-    de_record_share(sum, key, beyond, zeros, hist, red, wred, bred, p.partials + ((size_t)f * gridDim.x + blockIdx.x), p.rec + f);
+    de_record_share(tally, lds, o.partials + ((size_t)f * gridDim.x + blockIdx.x), o.rec + f);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
@@ -310,18 +276,10 @@ ItpSide side_args(const avx_itp_side* s, int H, int W) {
 extern "C" int avx_itp_delta(avx_ctx* ctx, const avx_itp_side* a, const avx_itp_side* b, double sdr_white, int n_frames, int H, int W, int mode, float gain,
                              float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream) {
     if (!ctx) return AVX_ERR_INVALID;
-    AVX_REQUIRE(ctx, rec_dev, "%s: NULL buffer (rec %p)", kFn, (const void*)rec_dev);
-    AVX_REQUIRE(ctx, n_frames >= 1 && n_frames <= 16, "%s: n_frames must be 1..16 (got %d)", kFn, n_frames);
-    AVX_REQUIRE(ctx, H >= 1 && W >= 1 && (uint64_t)H * (uint64_t)W < (1ull << 32), "%s: bad frame size %d x %d (H * W must be below 2^32)", kFn, H, W);
+    if (const int rc = de_check_options(ctx, kFn, n_frames, H, W, mode, gain, threshold, layout, rec_dev, de_out)) return rc;
     if (const int rc = side_check(ctx, "A", a, n_frames, H, W, map_out != nullptr)) return rc;
     if (const int rc = side_check(ctx, "B", b, n_frames, H, W, map_out != nullptr)) return rc;
     AVX_REQUIRE(ctx, std::isfinite(sdr_white) && sdr_white > 0.0, "%s: sdr_white %g must be finite and positive", kFn, sdr_white);
-    AVX_REQUIRE(ctx, mode == AVX_DELTA_E_HEAT || mode == AVX_DELTA_E_PLAIN, "%s: bad mode %d", kFn, mode);
-    AVX_REQUIRE(ctx, layout == AVX_DELTA_E_MAP || layout == AVX_DELTA_E_SIDE, "%s: bad layout %d", kFn, layout);
-    AVX_REQUIRE(ctx, std::isfinite(gain) && gain > 0.0f && gain <= 255.0f, "%s: the gain must be above 0 and at most 255 (got %g)", kFn, (double)gain);
-    AVX_REQUIRE(ctx, std::isfinite(threshold) && threshold >= 0.0f, "%s: the threshold must be finite and at least 0 (got %g)", kFn, (double)threshold);
-    AVX_REQUIRE(ctx, ((uintptr_t)rec_dev & 7) == 0, "%s: rec_dev must be 8-byte aligned", kFn);
-    AVX_REQUIRE(ctx, ((uintptr_t)de_out & 3) == 0, "%s: de_out must be 4-byte aligned", kFn);
 
     ItpArgs p = {};
     p.a = side_args(a, H, W), p.b = side_args(b, H, W);
@@ -340,20 +298,12 @@ extern "C" int avx_itp_delta(avx_ctx* ctx, const avx_itp_side* a, const avx_itp_
     inv3(m, mi);  // BT.709 -> BT.2020: every row sums to 1
     for (int i = 0; i < 3; ++i) p.c.g0[i] = (float)mi[i][0], p.c.g2[i] = (float)mi[i][2];
     p.same = p.a.hdr == p.b.hdr && (!p.a.hdr || (a->full_range == b->full_range && a->transfer == b->transfer));
-    p.out = map_out, p.de = de_out, p.rec = rec_dev;
-    p.H = H, p.W = W, p.mode = mode, p.side = layout == AVX_DELTA_E_SIDE, p.gain = gain, p.threshold = threshold;
 
     const size_t nchunks = (npx + kChunk - 1) / kChunk;  // below 2^20
-    AVX_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = avx_pick_stream(ctx, stream);
-    avx_ws* ws = avx_workspace(ctx, s);
-    if (!ws) return AVX_ERR_NOMEM;
-    if (const int rc = avx_ensure_scratch(ctx, ws, sizeof(double) * nchunks * (size_t)n_frames)) return rc;
-    AVX_HIP(ctx, hipMemsetAsync(rec_dev, 0, sizeof(avx_delta_e_rec) * (size_t)n_frames, s));
-    p.partials = (double*)ws->d_scratch;
+    hipStream_t s;
+    avx_ws* ws;
+    if (const int rc = de_begin(ctx, stream, sizeof(double) * nchunks * (size_t)n_frames, rec_dev, n_frames, &s, &ws)) return rc;
+    p.o = {map_out, de_out, (double*)ws->d_scratch, rec_dev, H, W, mode, layout == AVX_DELTA_E_SIDE, gain, threshold};
     hipLaunchKernelGGL(k_itp, dim3((unsigned)nchunks, n_frames), dim3(kThreads), 0, s, p);
-    AVX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_delta_e_final, dim3(n_frames), dim3(kThreads), 0, s, (const double*)ws->d_scratch, nchunks, W, rec_dev);
-    AVX_HIP(ctx, hipGetLastError());
-    return AVX_OK;
+    return de_finish(ctx, s, p.o.partials, nchunks, W, rec_dev, n_frames);
 }

@@ -3,7 +3,8 @@
 // an observer with K = 2, 3 or 4 receptor classes tells them apart -- as a float32 plane, as a picture and as a record per frame,
 // which are avx_delta_e_u8's in every respect but the value.
 //
-// k_receptor<K>: the chunk walk, the map and the record are delta_e_walk.h's one copy, shared with delta_e.hip; the value of a pixel is
+// k_receptor<K>: the chunk walk is delta_e_walk.h's one copy, shared with delta_e.hip, and the map, the record and the host side's checks
+// and launch frame are delta_e_common.h's, shared with all the colour difference entries; the value of a pixel is
 // this file's: the K catches of both pixels (the decode table in LDS, the anchored matrix form: a grey has every catch equal to g), K
 // divisions and K logf for the contrasts, and the quadratic form of their differences (receptor_common.h's Rnl<K>, shared with
 // receptor_acuity.hip).  The observer's constants -- the normalised matrix, the weights of the pairs and the reciprocal of the
@@ -31,13 +32,13 @@ void launch_receptor(bool vec, dim3 grid, hipStream_t s, const DeArgs& p, const 
 extern "C" int avx_receptor_delta_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, const avx_receptor_desc* obs,
                                      int mode, float gain, float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* ds_out,
                                      void* stream) {
+    static const char fn[] = "avx_receptor_delta_u8";
     if (!ctx) return AVX_ERR_INVALID;
-    const int rc = de_walk_check(ctx, "avx_receptor_delta_u8", a_hwc, b_hwc, n_frames, H, W, mode, gain, threshold, layout, map_out, rec_dev, ds_out);
-    if (rc) return rc;
+    if (const int rc = de_check_options(ctx, fn, n_frames, H, W, mode, gain, threshold, layout, rec_dev, ds_out)) return rc;
+    if (const int rc = de_check_pair(ctx, fn, a_hwc, b_hwc, n_frames, H, W, layout, map_out)) return rc;
     RnlArgs c;
     int K;
-    const int rc2 = rnl_constants(ctx, "avx_receptor_delta_u8", obs, c, K);
-    if (rc2) return rc2;
+    if (const int rc = rnl_constants(ctx, fn, obs, c, K)) return rc;
 
     return de_walk_launch(ctx, a_hwc, b_hwc, n_frames, H, W, mode, gain, threshold, layout, map_out, rec_dev, ds_out, stream,
                           [&](bool vec, dim3 grid, hipStream_t s, const DeArgs& p) {

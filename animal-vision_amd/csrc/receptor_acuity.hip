@@ -2,8 +2,8 @@
 // 2018, followed by the distance of Vorobyev & Osorio 1998; the definition is include/avx.h's): both frames are blurred
 // in linear light by the species' own Gaussian -- cv::getGaussianKernel(cvRound(8 sigma + 1) | 1, sigma), rows then columns,
 // BORDER_REFLECT_101 -- and the distance of receptor.hip is taken per pixel on the blurred values.  The value arithmetic is
-// receptor_common.h's Rnl<K>, the map's colours, the key, the record's share and the finishing kernel are delta_e_common.h's: one copy
-// of each.
+// receptor_common.h's Rnl<K>; the record's share, the map's quantiser and colours, a pixel's panels and the host side's checks and
+// launch frame are delta_e_common.h's: one copy of each.
 //
 // k_receptor_acuity<K>: grid (tiles, frames); a workgroup of 256 threads owns a kTileW x kTileH = 64 x 32 tile of one frame pair and
 // needs no scratch planes: plane by plane, for the three channels of A and then of B,
@@ -38,14 +38,10 @@ static_assert(4 * ((2 * kMaxRad + 3) / 4) + 6 < kTapSlots &&kTapFront + 4 * ((2 
 struct AcArgs {
     const uint8_t* a;
     const uint8_t* b;
-    uint8_t* out;      // NULL: no map
-    float* de;         // NULL: no float plane
-    double* partials;  // [frame][tile]
-    avx_delta_e_rec* rec;
-    int H, W, R, mode, side;
+    int R;
     unsigned tiles_x;
-    float gain, threshold;
     float tp[kTapSlots];  // tp[kTapFront + k] = t_k, zero elsewhere
+    DeOut o;              // partials: [frame][tile]
 };
 
 // BORDER_REFLECT_101, folded as often as needed: n = 1 gives 0
@@ -57,15 +53,13 @@ __device__ __forceinline__ long long fold101(long long i, long long n) {
     return m < n ? m : p - m;
 }
 
+// six waves a SIMD: at most 80 registers, which the small radii need (their LDS admits seven workgroups a compute unit)
 template <int K>
-__global__ __launch_bounds__(kThreads) void k_receptor_acuity(AcArgs p, RnlArgs c) {
+__global__ __launch_bounds__(kThreads, 6) void k_receptor_acuity(AcArgs p, RnlArgs c) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ float lut[256];
-    __shared__ unsigned hist[256];
-    __shared__ double red[kThreads / 64];
-    __shared__ unsigned long long wred[kThreads / 64];
-    __shared__ unsigned bred[kThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, R = p.R, H = p.H, W = p.W;
+    __shared__ DeRecLds lds;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, R = p.R, H = p.o.H, W = p.o.W;
     const unsigned tile_y = blockIdx.x / p.tiles_x, tile_x = blockIdx.x - tile_y * p.tiles_x;
     const int f = blockIdx.y;
     const long long x0 = (long long)tile_x * kTileW, y0 = (long long)tile_y * kTileH;
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void k_receptor_acuity(AcArgs p, RnlArgs 
     float* tile = dyn;                            // [rows][span]
     float* rowres = dyn + rows * span;            // [rows + kPadRows][kTileW]
     lut[tid] = __uint_as_float(kLabDecodeBits[tid]);
-    hist[tid] = 0;
+    lds.hist[tid] = 0;
     rowres[rows * kTileW + tid] = 0.0f;           // kPadRows * kTileW == kThreads
     static_assert(kPadRows * kTileW == kThreads, "one pad word a thread");
 
@@ -158,52 +152,23 @@ __global__ __launch_bounds__(kThreads) void k_receptor_acuity(AcArgs p, RnlArgs 
     const Rnl<K> rnl{c};
     const uint8_t* fa = p.a + (size_t)f * npx * 3;
     const uint8_t* fb = p.b + (size_t)f * npx * 3;
-    const float G = p.gain, T = p.threshold;
-    double sum = 0.0;
-    unsigned long long key = 0;
-    unsigned beyond = 0, zeros = 0;
-    float* de_out = p.de ? p.de + (size_t)f * npx : nullptr;
-    uint8_t* fo = p.out ? p.out + (size_t)f * npx * 3 * (p.side ? 3 : 1) : nullptr;
-    const size_t row = (size_t)W * 3;  // bytes of a panel's row
+    DeTally tally;
+    float* de_out = p.o.de ? p.o.de + (size_t)f * npx : nullptr;
+    uint8_t* fo = p.o.out ? p.o.out + (size_t)f * npx * 3 * (p.o.side ? 3 : 1) : nullptr;
     const size_t x = (size_t)x0 + col;
 #pragma unroll
     for (int o = 0; o < kPer; ++o) {
         const size_t y = (size_t)y0 + seg * kPer + o;
         if (y >= (size_t)H || x >= (size_t)W) continue;
         const float de = rnl.value(filt[0][0][o], filt[0][1][o], filt[0][2][o], filt[1][0][o], filt[1][1][o], filt[1][2][o]);
-        const int bin = min(255, (int)(de + de));  // floor(2 dS): dS >= 0
-        if (bin == 0) ++zeros;
-        else atomicAdd(&hist[bin], 1u);
-        sum += (double)de;
-        beyond += de > T ? 1u : 0u;
         const size_t at = y * W + x;
-        const unsigned long long k = de_key(de, (uint32_t)at);
-        key = k > key ? k : key;
+        tally.add(de, (uint32_t)at, p.o.threshold, lds.hist);
         if (de_out) de_out[at] = de;
-        if (fo) {
-            // the quantiser: float32, one rounding per operation, multiply and add never fused
-            const float xq = p.mode == AVX_DELTA_E_HEAT ? __fsub_rn(de, T) : de;
-            const float v = fminf(floorf(__fadd_rn(__fmul_rn(G, xq), 0.5f)), 255.0f);
-            const uint8_t* pa = fa + at * 3;  // the dim grey and the side panels are the unfiltered frames'
-            const int ar = pa[0], ag = pa[1], ab = pa[2];
-            uint32_t r, g, b;
-            de_colour(v, de, T, p.mode, ar, ag, ab, r, g, b);
-            if (p.side) {
-                const uint8_t* pb = fb + at * 3;
-                uint8_t* dst = fo + y * (3 * row) + x * 3;
-                dst[0] = (uint8_t)ar, dst[1] = (uint8_t)ag, dst[2] = (uint8_t)ab;
-                dst[row] = pb[0], dst[row + 1] = pb[1], dst[row + 2] = pb[2];
-                dst += 2 * row;
-                dst[0] = (uint8_t)r, dst[1] = (uint8_t)g, dst[2] = (uint8_t)b;
-            } else {
-                uint8_t* dst = fo + at * 3;
-                dst[0] = (uint8_t)r, dst[1] = (uint8_t)g, dst[2] = (uint8_t)b;
-            }
-        }
+        if (fo) de_px_panels(p.o, fo, fa, fb, y, x, de);  // the dim grey and the side panels are the unfiltered frames'
     }
 
     // ---- the record ----
-    de_record_share(sum, key, beyond, zeros, hist, red, wred, bred, p.partials + ((size_t)f * gridDim.x + blockIdx.x), p.rec + f);
+    de_record_share(tally, lds, p.o.partials + ((size_t)f * gridDim.x + blockIdx.x), p.o.rec + f);
 }
 
 }  // namespace
@@ -213,22 +178,11 @@ extern "C" int avx_receptor_acuity_u8(avx_ctx* ctx, const uint8_t* a_hwc, const 
                                       float* ds_out, void* stream) {
     static const char fn[] = "avx_receptor_acuity_u8";
     if (!ctx) return AVX_ERR_INVALID;
-    AVX_REQUIRE(ctx, a_hwc && b_hwc && rec_dev, "%s: NULL buffer (a %p, b %p, rec %p)", fn, (const void*)a_hwc, (const void*)b_hwc, (const void*)rec_dev);
-    AVX_REQUIRE(ctx, n_frames >= 1 && n_frames <= 16, "%s: n_frames must be 1..16 (got %d)", fn, n_frames);
-    AVX_REQUIRE(ctx, H >= 1 && W >= 1 && (uint64_t)H * (uint64_t)W < (1ull << 32), "%s: bad frame size %d x %d (H * W must be below 2^32)", fn, H, W);
-    AVX_REQUIRE(ctx, mode == AVX_DELTA_E_HEAT || mode == AVX_DELTA_E_PLAIN, "%s: bad mode %d", fn, mode);
-    AVX_REQUIRE(ctx, layout == AVX_DELTA_E_MAP || layout == AVX_DELTA_E_SIDE, "%s: bad layout %d", fn, layout);
-    AVX_REQUIRE(ctx, std::isfinite(gain) && gain > 0.0f && gain <= 255.0f, "%s: the gain must be above 0 and at most 255 (got %g)", fn, (double)gain);
-    AVX_REQUIRE(ctx, std::isfinite(threshold) && threshold >= 0.0f, "%s: the threshold must be finite and at least 0 (got %g)", fn, (double)threshold);
-    AVX_REQUIRE(ctx, ((uintptr_t)rec_dev & 7) == 0, "%s: rec_dev must be 8-byte aligned", fn);
-    AVX_REQUIRE(ctx, ((uintptr_t)ds_out & 3) == 0, "%s: ds_out must be 4-byte aligned", fn);
-    const size_t npx = (size_t)H * W, in_bytes = (size_t)n_frames * npx * 3, map_bytes = in_bytes * (layout == AVX_DELTA_E_SIDE ? 3 : 1);
-    AVX_REQUIRE(ctx, !map_out || (!overlaps(map_out, map_bytes, a_hwc, in_bytes) && !overlaps(map_out, map_bytes, b_hwc, in_bytes)),
-                "%s: map_out overlaps an input (a %p, b %p, map %p)", fn, (const void*)a_hwc, (const void*)b_hwc, (const void*)map_out);
+    if (const int rc = de_check_options(ctx, fn, n_frames, H, W, mode, gain, threshold, layout, rec_dev, ds_out)) return rc;
+    if (const int rc = de_check_pair(ctx, fn, a_hwc, b_hwc, n_frames, H, W, layout, map_out)) return rc;
     RnlArgs c;
     int K;
-    int rc = rnl_constants(ctx, fn, obs, c, K);
-    if (rc) return rc;
+    if (const int rc = rnl_constants(ctx, fn, obs, c, K)) return rc;
     AVX_REQUIRE(ctx, std::isfinite(sigma) && sigma >= 0.2 && sigma <= 4.0, "%s: sigma must be a finite number from 0.2 to 4 (got %g)", fn, sigma);
     const int ksize = (int)lrint(sigma * 8.0 + 1.0) | 1;  // cvRound: half to even
     AVX_REQUIRE(ctx, ksize >= 3 && ksize <= AVX_MAX_KSIZE, "%s: sigma %g needs %d taps, 3 .. %d are supported", fn, sigma, ksize, AVX_MAX_KSIZE);
@@ -244,23 +198,16 @@ extern "C" int avx_receptor_acuity_u8(avx_ctx* ctx, const uint8_t* a_hwc, const 
     }
     const int R = (ksize - 1) / 2;
     const size_t tiles_x = ((size_t)W + kTileW - 1) / kTileW, tiles = tiles_x * (((size_t)H + kTileH - 1) / kTileH);  // below 2^31
-    AVX_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = avx_pick_stream(ctx, stream);
-    avx_ws* ws = avx_workspace(ctx, s);
-    if (!ws) return AVX_ERR_NOMEM;
-    rc = avx_ensure_scratch(ctx, ws, sizeof(double) * tiles * (size_t)n_frames);
-    if (rc) return rc;
-    AVX_HIP(ctx, hipMemsetAsync(rec_dev, 0, sizeof(avx_delta_e_rec) * (size_t)n_frames, s));
-    p.a = a_hwc, p.b = b_hwc, p.out = map_out, p.de = ds_out, p.partials = (double*)ws->d_scratch, p.rec = rec_dev;
-    p.H = H, p.W = W, p.R = R, p.mode = mode, p.side = layout == AVX_DELTA_E_SIDE, p.tiles_x = (unsigned)tiles_x, p.gain = gain, p.threshold = threshold;
+    hipStream_t s;
+    avx_ws* ws;
+    if (const int rc = de_begin(ctx, stream, sizeof(double) * tiles * (size_t)n_frames, rec_dev, n_frames, &s, &ws)) return rc;
+    p.a = a_hwc, p.b = b_hwc, p.R = R, p.tiles_x = (unsigned)tiles_x;
+    p.o = {map_out, ds_out, (double*)ws->d_scratch, rec_dev, H, W, mode, layout == AVX_DELTA_E_SIDE, gain, threshold};
     const int rows = kTileH + 2 * R, span = (kTileW + 2 * R + 3) & ~3;
     const size_t lds = sizeof(float) * ((size_t)rows * span + (size_t)(rows + kPadRows) * kTileW);  // at most 41984 bytes
     const dim3 grid((unsigned)tiles, n_frames);
     if (K == 2) hipLaunchKernelGGL((k_receptor_acuity<2>), grid, dim3(kThreads), lds, s, p, c);
     else if (K == 3) hipLaunchKernelGGL((k_receptor_acuity<3>), grid, dim3(kThreads), lds, s, p, c);
     else hipLaunchKernelGGL((k_receptor_acuity<4>), grid, dim3(kThreads), lds, s, p, c);
-    AVX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_delta_e_final, dim3(n_frames), dim3(kThreads), 0, s, (const double*)ws->d_scratch, tiles, W, rec_dev);
-    AVX_HIP(ctx, hipGetLastError());
-    return AVX_OK;
+    return de_finish(ctx, s, p.o.partials, tiles, W, rec_dev, n_frames);
 }

@@ -1,8 +1,8 @@
 // csrc/scielab.hip -- S-CIELAB colour difference maps on the device (Zhang & Wandell 1996; the definition is
 // include/avx.h's): both frames are filtered in an opponent colour space by the eye's contrast sensitivity at `ppd` pixels per degree,
 // and the dE00 of delta_e.hip is taken per pixel on the filtered frames.  The values, the map and the record are those of
-// avx_delta_e_u8 in every other respect, and the Lab transfer function, CIEDE2000, the record and the map's colours are
-// delta_e_common.h's one copy.
+// avx_delta_e_u8 in every other respect, and the Lab transfer function, CIEDE2000, the record, the map's quantiser and colours, a
+// pixel's panels and the host side's checks and launch frame are delta_e_common.h's one copy; the 3 x 3 inverse is yuv_hdr_px.h's.
 //
 // Seven separable Gaussian terms (three of the luminance channel, two of each chroma channel) with R = ceil(ppd / 2) taps to either
 // side, borders clamped.  The taps are formed on the host in float64, each normalised over its support, rounded once to float32 and
@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "delta_e_common.h"
+#include "yuv_hdr_px.h"
 
 namespace {
 
@@ -48,23 +49,19 @@ struct SlArgs {
     const uint8_t* b;
     const float* taps;   // [2R + 1][kTapStride]
     float* planes;       // [frame of the group][side][term][H][W]
-    uint8_t* out;        // NULL: no map
-    float* de;           // NULL: no float plane
-    double* partials;    // [frame of the group][tile]
-    avx_delta_e_rec* rec;
-    int H, W, R, mode, side;
+    int R;
     unsigned tiles_x;
-    float gain, threshold;
     float q[3][3];       // P M: decoded sRGB -> opponent
     float pinv[3][3];    // opponent -> XYZ
     float white[3];      // 1 / the white point
     float weight[kTerms];
+    DeOut o;             // the group's first frame; partials: [frame of the group][tile]
 };
 
 __global__ __launch_bounds__(kThreads) void k_scielab_rows(SlArgs p) {
     __shared__ float so[kRowH][3][4 * kRowPhase];
     __shared__ float lut[256];
-    const int tid = threadIdx.x, R = p.R, H = p.H, W = p.W;
+    const int tid = threadIdx.x, R = p.R, H = p.o.H, W = p.o.W;
     const unsigned tile_y = blockIdx.x / p.tiles_x, tile_x = blockIdx.x - tile_y * p.tiles_x;
     const int f = blockIdx.y >> 1, side = blockIdx.y & 1;
     const size_t x0 = (size_t)tile_x * kRowW, y0 = (size_t)tile_y * kRowH, npx = (size_t)H * W;
@@ -131,18 +128,15 @@ __global__ __launch_bounds__(kThreads) void k_scielab_rows(SlArgs p) {
 
 __global__ __launch_bounds__(kThreads) void k_scielab_cols(SlArgs p) {
     __shared__ __attribute__((aligned(16))) float buf[kColLds];
-    __shared__ unsigned hist[256];
-    __shared__ double red[kThreads / 64];
-    __shared__ unsigned long long wred[kThreads / 64];
-    __shared__ unsigned bred[kThreads / 64];
-    const int tid = threadIdx.x, R = p.R, H = p.H, W = p.W;
+    __shared__ DeRecLds lds;
+    const int tid = threadIdx.x, R = p.R, H = p.o.H, W = p.o.W;
     const unsigned tile_y = blockIdx.x / p.tiles_x, tile_x = blockIdx.x - tile_y * p.tiles_x;
     const int f = blockIdx.y;
     const size_t x0 = (size_t)tile_x * kColW, y0 = (size_t)tile_y * kColH, npx = (size_t)H * W;
     const int col = tid & 63, seg = tid >> 6;
     const size_t xc = min(x0 + col, (size_t)W - 1);  // columns right of the frame repeat the last; they are not kept
     const float* taps = p.taps;
-    hist[tid] = 0;
+    lds.hist[tid] = 0;
 
     float filt[2][3][kColPer];
     const int rows = kColH + 2 * R;
@@ -188,13 +182,9 @@ __global__ __launch_bounds__(kThreads) void k_scielab_cols(SlArgs p) {
     // ---- the pixels of the tile: Lab of both sides, dE00, the record, the panels (a wave's 64 pixels are 192 adjacent bytes of each) ----
     const uint8_t* fa = p.a + (size_t)f * npx * 3;
     const uint8_t* fb = p.b + (size_t)f * npx * 3;
-    const float G = p.gain, T = p.threshold;
-    double sum = 0.0;
-    unsigned long long key = 0;
-    unsigned beyond = 0, zeros = 0;
-    float* de_out = p.de ? p.de + (size_t)f * npx : nullptr;
-    uint8_t* fo = p.out ? p.out + (size_t)f * npx * 3 * (p.side ? 3 : 1) : nullptr;
-    const size_t row = (size_t)W * 3;  // bytes of a panel's row
+    DeTally tally;
+    float* de_out = p.o.de ? p.o.de + (size_t)f * npx : nullptr;
+    uint8_t* fo = p.o.out ? p.o.out + (size_t)f * npx * 3 * (p.o.side ? 3 : 1) : nullptr;
 #pragma unroll 1
     for (int i = tid; i < kColPx; i += kThreads) {
         const size_t y = y0 + (i >> 6), x = x0 + (i & 63);
@@ -212,50 +202,14 @@ __global__ __launch_bounds__(kThreads) void k_scielab_cols(SlArgs p) {
             lab[side][2] = 200.0f * (fx[1] - fx[2]);
         }
         const float de = ciede2000(lab[0][0], lab[0][1], lab[0][2], lab[1][0], lab[1][1], lab[1][2]);
-        const int bin = min(255, (int)(de + de));  // floor(2 dE): dE >= 0
-        if (bin == 0) ++zeros;
-        else atomicAdd(&hist[bin], 1u);
-        sum += (double)de;
-        beyond += de > T ? 1u : 0u;
         const size_t at = y * W + x;
-        const unsigned long long k = de_key(de, (uint32_t)at);
-        key = k > key ? k : key;
+        tally.add(de, (uint32_t)at, p.o.threshold, lds.hist);
         if (de_out) de_out[at] = de;
-        if (fo) {
-            // the quantiser: float32, one rounding per operation, multiply and add never fused
-            const float xq = p.mode == AVX_DELTA_E_HEAT ? __fsub_rn(de, T) : de;
-            const float v = fminf(floorf(__fadd_rn(__fmul_rn(G, xq), 0.5f)), 255.0f);
-            const uint8_t* pa = fa + at * 3;  // the dim grey and the side panels are the unfiltered frames'
-            const int ar = pa[0], ag = pa[1], ab = pa[2];
-            uint32_t r, g, b;
-            de_colour(v, de, T, p.mode, ar, ag, ab, r, g, b);
-            if (p.side) {
-                const uint8_t* pb = fb + at * 3;
-                uint8_t* dst = fo + y * (3 * row) + x * 3;
-                dst[0] = (uint8_t)ar, dst[1] = (uint8_t)ag, dst[2] = (uint8_t)ab;
-                dst[row] = pb[0], dst[row + 1] = pb[1], dst[row + 2] = pb[2];
-                dst += 2 * row;
-                dst[0] = (uint8_t)r, dst[1] = (uint8_t)g, dst[2] = (uint8_t)b;
-            } else {
-                uint8_t* dst = fo + at * 3;
-                dst[0] = (uint8_t)r, dst[1] = (uint8_t)g, dst[2] = (uint8_t)b;
-            }
-        }
+        if (fo) de_px_panels(p.o, fo, fa, fb, y, x, de);  // the dim grey and the side panels are the unfiltered frames'
     }
 
     // ---- the record ----
-    de_record_share(sum, key, beyond, zeros, hist, red, wred, bred, p.partials + ((size_t)f * gridDim.x + blockIdx.x), p.rec + f);
-}
-
-// the inverse of a 3 x 3 matrix by cofactors
-void invert3(const double (&m)[3][3], double (&inv)[3][3]) {
-    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2], c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
-    const double det = m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02;
-    inv[0][0] = c00 / det, inv[1][0] = c01 / det, inv[2][0] = c02 / det;
-    inv[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, inv[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det;
-    inv[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det;
-    inv[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det, inv[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
-    inv[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
+    de_record_share(tally, lds, p.o.partials + ((size_t)f * gridDim.x + blockIdx.x), p.o.rec + f);
 }
 
 // Zhang & Wandell 1996: XYZ -> opponent (luminance, red-green, blue-yellow), and the (weight, spread in degrees) of the filter terms
@@ -267,20 +221,11 @@ constexpr double kTermSpread[kTerms] = {0.0283, 0.133, 4.336, 0.0392, 0.494, 0.0
 
 extern "C" int avx_scielab_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_hwc, int n_frames, int H, int W, double ppd, int mode, float gain,
                               float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* de_out, void* stream) {
+    static const char fn[] = "avx_scielab_u8";
     if (!ctx) return AVX_ERR_INVALID;
-    AVX_REQUIRE(ctx, a_hwc && b_hwc && rec_dev, "avx_scielab_u8: NULL buffer (a %p, b %p, rec %p)", (const void*)a_hwc, (const void*)b_hwc, (void*)rec_dev);
-    AVX_REQUIRE(ctx, n_frames >= 1 && n_frames <= 16, "avx_scielab_u8: n_frames must be 1..16 (got %d)", n_frames);
-    AVX_REQUIRE(ctx, H >= 1 && W >= 1 && (uint64_t)H * (uint64_t)W < (1ull << 32), "avx_scielab_u8: bad frame size %d x %d (H * W must be below 2^32)", H, W);
-    AVX_REQUIRE(ctx, std::isfinite(ppd) && ppd >= 2.0 && ppd <= 128.0, "avx_scielab_u8: ppd must be a finite number from 2 to 128 (got %g)", ppd);
-    AVX_REQUIRE(ctx, mode == AVX_DELTA_E_HEAT || mode == AVX_DELTA_E_PLAIN, "avx_scielab_u8: bad mode %d", mode);
-    AVX_REQUIRE(ctx, layout == AVX_DELTA_E_MAP || layout == AVX_DELTA_E_SIDE, "avx_scielab_u8: bad layout %d", layout);
-    AVX_REQUIRE(ctx, std::isfinite(gain) && gain > 0.0f && gain <= 255.0f, "avx_scielab_u8: the gain must be above 0 and at most 255 (got %g)", (double)gain);
-    AVX_REQUIRE(ctx, std::isfinite(threshold) && threshold >= 0.0f, "avx_scielab_u8: the threshold must be finite and at least 0 (got %g)", (double)threshold);
-    AVX_REQUIRE(ctx, ((uintptr_t)rec_dev & 7) == 0, "avx_scielab_u8: rec_dev must be 8-byte aligned");
-    AVX_REQUIRE(ctx, ((uintptr_t)de_out & 3) == 0, "avx_scielab_u8: de_out must be 4-byte aligned");
-    const size_t npx = (size_t)H * W, in_bytes = (size_t)n_frames * npx * 3, map_bytes = in_bytes * (layout == AVX_DELTA_E_SIDE ? 3 : 1);
-    AVX_REQUIRE(ctx, !map_out || (!overlaps(map_out, map_bytes, a_hwc, in_bytes) && !overlaps(map_out, map_bytes, b_hwc, in_bytes)),
-                "avx_scielab_u8: map_out overlaps an input (a %p, b %p, map %p)", (const void*)a_hwc, (const void*)b_hwc, (void*)map_out);
+    if (const int rc = de_check_options(ctx, fn, n_frames, H, W, mode, gain, threshold, layout, rec_dev, de_out)) return rc;
+    if (const int rc = de_check_pair(ctx, fn, a_hwc, b_hwc, n_frames, H, W, layout, map_out)) return rc;
+    AVX_REQUIRE(ctx, std::isfinite(ppd) && ppd >= 2.0 && ppd <= 128.0, "%s: ppd must be a finite number from 2 to 128 (got %g)", fn, ppd);
 
     // ---- the constants: float64 on the host, rounded once ----
     SlArgs p;
@@ -296,7 +241,7 @@ extern "C" int avx_scielab_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t*
         p.weight[i] = (float)(kTermWeight[i] / wsum);
     }
     double pinv[3][3];
-    invert3(kOpp, pinv);
+    inv3(kOpp, pinv);
     const double white[3] = {kSX, kSY, kSZ};
     for (int i = 0; i < 3; ++i) {
         p.white[i] = (float)(1.0 / white[i]);
@@ -307,32 +252,29 @@ extern "C" int avx_scielab_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t*
     }
 
     // ---- the scratch: the partials of all 16 frames a batch may hold, then the planes of one group ----
+    const size_t npx = (size_t)H * W;
     const size_t row_tiles_x = (W + kRowW - 1) / kRowW, row_tiles = row_tiles_x * (((size_t)H + kRowH - 1) / kRowH);
     const size_t col_tiles_x = (W + kColW - 1) / kColW, col_tiles = col_tiles_x * (((size_t)H + kColH - 1) / kColH);  // both below 2^31
     const size_t part_bytes = (sizeof(double) * col_tiles * 16 + 255) & ~(size_t)255;
     const size_t pair_bytes = npx * 2 * kTerms * sizeof(float);
     const size_t fit = kScratchCap > part_bytes ? (kScratchCap - part_bytes) / pair_bytes : 0;
     const int group = (int)(fit < 1 ? 1 : fit > 16 ? 16 : fit);  // a pair above 19 Mpixel is walked alone and takes its 56 bytes a pixel
-    AVX_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = avx_pick_stream(ctx, stream);
-    avx_ws* ws = avx_workspace(ctx, s);
-    if (!ws) return AVX_ERR_NOMEM;
-    int rc = avx_ensure_scratch(ctx, ws, part_bytes + pair_bytes * (size_t)(group < n_frames ? group : n_frames));
-    if (rc) return rc;
+    hipStream_t s;
+    avx_ws* ws;
+    if (const int rc = de_begin(ctx, stream, part_bytes + pair_bytes * (size_t)(group < n_frames ? group : n_frames), rec_dev, n_frames, &s, &ws)) return rc;
     void* d_taps = nullptr;
-    rc = avx_const_upload(ctx, ws, kConstSlot, taps, sizeof(float) * (size_t)(2 * R + 1) * kTapStride, s, &d_taps);
-    if (rc) return rc;
-    AVX_HIP(ctx, hipMemsetAsync(rec_dev, 0, sizeof(avx_delta_e_rec) * (size_t)n_frames, s));
+    if (const int rc = avx_const_upload(ctx, ws, kConstSlot, taps, sizeof(float) * (size_t)(2 * R + 1) * kTapStride, s, &d_taps)) return rc;
     p.taps = (const float*)d_taps;
     p.planes = (float*)((char*)ws->d_scratch + part_bytes);
-    p.H = H, p.W = W, p.R = R, p.mode = mode, p.side = layout == AVX_DELTA_E_SIDE, p.gain = gain, p.threshold = threshold;
+    p.R = R;
+    p.o.H = H, p.o.W = W, p.o.mode = mode, p.o.side = layout == AVX_DELTA_E_SIDE, p.o.gain = gain, p.o.threshold = threshold;
     for (int f0 = 0; f0 < n_frames; f0 += group) {
         const int n = n_frames - f0 < group ? n_frames - f0 : group;
         p.a = a_hwc + (size_t)f0 * npx * 3, p.b = b_hwc + (size_t)f0 * npx * 3;
-        p.out = map_out ? map_out + (size_t)f0 * npx * 3 * (p.side ? 3 : 1) : nullptr;
-        p.de = de_out ? de_out + (size_t)f0 * npx : nullptr;
-        p.partials = (double*)ws->d_scratch + (size_t)f0 * col_tiles;
-        p.rec = rec_dev + f0;
+        p.o.out = map_out ? map_out + (size_t)f0 * npx * 3 * (p.o.side ? 3 : 1) : nullptr;
+        p.o.de = de_out ? de_out + (size_t)f0 * npx : nullptr;
+        p.o.partials = (double*)ws->d_scratch + (size_t)f0 * col_tiles;
+        p.o.rec = rec_dev + f0;
         p.tiles_x = (unsigned)row_tiles_x;
         hipLaunchKernelGGL(k_scielab_rows, dim3((unsigned)row_tiles, 2 * n), dim3(kThreads), 0, s, p);
         AVX_HIP(ctx, hipGetLastError());
@@ -340,7 +282,5 @@ extern "C" int avx_scielab_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t*
         hipLaunchKernelGGL(k_scielab_cols, dim3((unsigned)col_tiles, n), dim3(kThreads), 0, s, p);
         AVX_HIP(ctx, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_delta_e_final, dim3(n_frames), dim3(kThreads), 0, s, (const double*)ws->d_scratch, col_tiles, W, rec_dev);
-    AVX_HIP(ctx, hipGetLastError());
-    return AVX_OK;
+    return de_finish(ctx, s, (const double*)ws->d_scratch, col_tiles, W, rec_dev, n_frames);
 }

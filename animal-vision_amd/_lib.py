@@ -260,6 +260,15 @@ class ReceptorDesc(ctypes.Structure):
 assert ctypes.sizeof(ReceptorDesc) == 144
 
 
+class LuminanceDesc(ctypes.Structure):
+    """avx_luminance_desc (include/avx.h)."""
+
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("row", ctypes.c_double * 3), ("weber", ctypes.c_double)]
+
+
+AVX_EDGES_CHANNELS = {"chromatic": 0, "achromatic": 1, "either": 2}  # enum avx_edges_channel
+
+
 class ItpSide(ctypes.Structure):
     """avx_itp_side (include/avx.h)."""
 
@@ -423,6 +432,8 @@ _SIGS = {
     "avx_receptor_delta_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp]),
     "avx_receptor_acuity_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), ctypes.c_double, _i, ctypes.c_float, ctypes.c_float, _i, _vp, _vp,
                                _vp, _vp]),
+    "avx_receptor_edges_u8": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), ctypes.POINTER(LuminanceDesc), _i, ctypes.c_double, _i, _i,
+                               ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "avx_itp_delta": (_i, [_vp, ctypes.POINTER(ItpSide), ctypes.POINTER(ItpSide), ctypes.c_double, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i, _vp,
                            _vp, _vp, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),

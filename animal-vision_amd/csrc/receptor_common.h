@@ -1,7 +1,8 @@
 // csrc/receptor_common.h -- what the receptor-noise-limited distance kernels share (receptor.hip: dS per pixel; receptor_acuity.hip: dS
-// behind the observer's acuity blur), in one copy so that they cannot drift apart: the pairs of classes, the observer's constants as
-// the kernels take them, the value of two pixels from their six linear values, and the host's checks of an avx_receptor_desc with the
-// constants it yields.  The definition is include/avx.h's, above avx_receptor_delta_u8.
+// behind the observer's acuity blur; receptor_edges.hip: dS between a pixel and its neighbours within one frame), in one copy so that
+// they cannot drift apart: the pairs of classes, the observer's constants as the kernels take them, the catch of a class, the value of
+// two pixels from their six linear values or from their K contrasts, and the host's checks of an avx_receptor_desc with the constants it
+// yields.  The definition is include/avx.h's, above avx_receptor_delta_u8.
 #pragma once
 #include <cmath>
 
@@ -27,6 +28,9 @@ struct RnlArgs {
     float rcp;                   // K = 2: 1 / sqrt(e_1^2 + e_2^2); else 1 / the denominator
 };
 
+// the catch of a class in the anchored form, from the row's columns 0 and 2 and the pixel's g, r - g and b - g: a grey gives g exactly
+__device__ __forceinline__ float rnl_catch(float r0, float r2, float g, float dr, float db) { return (g + r0 * dr) + r2 * db; }
+
 template <int K>
 struct Rnl {
     RnlArgs c;
@@ -36,10 +40,15 @@ struct Rnl {
         float df[K];
 #pragma unroll
         for (int i = 0; i < K; ++i) {
-            const float qa = (g1 + c.r0[i] * dr1) + c.r2[i] * db1;
-            const float qb = (g2 + c.r0[i] * dr2) + c.r2[i] * db2;
+            const float qa = rnl_catch(c.r0[i], c.r2[i], g1, dr1, db1);
+            const float qb = rnl_catch(c.r0[i], c.r2[i], g2, dr2, db2);
             df[i] = logf((qa + c.eps) / (qb + c.eps));
         }
+        return from_contrasts(df);
+    }
+    // dS from the K contrasts df_i of two pixels: the quadratic form, in one copy (receptor_edges.hip forms its df_i as differences of
+    // log-catches and comes here too)
+    __device__ __forceinline__ float from_contrasts(const float (&df)[K]) const {
         if (K == 2) return fabsf(df[0] - df[1]) * c.rcp;
         float num = 0.0f;
 #pragma unroll

@@ -36,7 +36,13 @@ uses --, so that what the animal cannot resolve counts for little; `deltae --acu
 dE_ITP (csrc/itp.hip; ITU-R BT.2124) is the colour difference that is defined at HDR light levels: 720 x the distance in
 ICtCp with Ct halved.  A side is an HdrFrames (10-bit PQ or HLG payloads as stored) or a uint8 sRGB array shown at sdr_white nits, in
 any mix; itp_delta_launch, itp_delta, itp_delta_map and itp_delta_values return the same DeltaE records, maps and value planes;
-`deltae --itp` is the command."""
+`deltae --itp` is the command.
+
+Receptor contrast within a frame (csrc/receptor_edges.hip; Local Edge Intensity Analysis, van den Berg et al. 2020) takes
+one input: per pixel the largest receptor-noise-limited contrast to its up to eight neighbours `step` pixels away, behind the acuity
+blur -- chromatic, achromatic (a luminance channel: achromatic=(classes, weber)) or either.  receptor_edges_launch, receptor_edges,
+receptor_edges_map and receptor_edges_values return the same DeltaE records, maps and value planes; python -m animal_vision_amd.edges
+is the command."""
 from __future__ import annotations
 
 import ctypes
@@ -51,7 +57,7 @@ from ._lib import AVX_DELTA_E_LAYOUTS, AVX_DELTA_E_MODES, AVX_DIFF_LAYOUTS, AVX_
 from ._lib import DeltaERecord as DeltaERecordStruct
 from ._lib import DiffRecord as DiffRecordStruct
 from ._lib import ItpSide as ItpSideStruct
-from ._lib import ReceptorDesc
+from ._lib import AVX_EDGES_CHANNELS, LuminanceDesc, ReceptorDesc
 from .runtime import Context, DeviceBuffer, get_context
 
 MAX_FRAMES = AVX_METRICS_MAX_FRAMES
@@ -1045,6 +1051,159 @@ def receptor_delta_values(a, b, observer: Observer, *, acuity=None, ctx: Optiona
     _check_observer(observer)
     acuity = _check_acuity_option(acuity)
     vals = _delta_e_chunks(a, b, "heat", None, DELTA_E_DEFAULT_THRESHOLD, "map", ctx, False, True, observer=observer, acuity=acuity)[2]
+    return vals if batched else vals[0]
+
+
+# ------------------------------------------------------------------------------------------------ receptor contrast within a frame
+EDGES_CHANNELS = tuple(AVX_EDGES_CHANNELS)
+EDGES_MAX_STEP = 8
+
+
+def check_achromatic(observer: Observer, achromatic) -> Optional[LuminanceDesc]:
+    """achromatic -- None, or (classes, weber): the 1-based numbers of the observer's receptor classes that feed its luminance channel
+    and that channel's Weber fraction (0.01 .. 1, the caller's: there is no per-species table) -- as the avx_luminance_desc the library
+    takes: the row is the mean of those classes' normalised rows.  ValueError naming it otherwise."""
+    if achromatic is None:
+        return None
+    try:
+        classes, weber = achromatic
+        classes = tuple(classes)
+    except (TypeError, ValueError):
+        raise ValueError(f"achromatic must be (classes, weber), e.g. ((1,), 0.1) (got {achromatic!r})") from None
+    K = observer.n_receptors
+    if not classes or len(set(classes)) != len(classes):
+        raise ValueError(f"achromatic classes must name at least one receptor class, each once (got {classes!r})")
+    for k in classes:
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= K:
+            raise ValueError(f"achromatic class {k!r} is not one of {observer.name}'s receptor classes 1..{K}")
+    if not _real(weber) or not RECEPTOR_MIN_WEBER <= weber <= RECEPTOR_MAX_WEBER:
+        raise ValueError(f"achromatic weber must be a number from {RECEPTOR_MIN_WEBER:g} to {RECEPTOR_MAX_WEBER:g} (got {weber!r})")
+    m = np.array(observer.matrix, np.float64)
+    m = m / m.sum(axis=1, keepdims=True)
+    d = LuminanceDesc()
+    d.struct_size, d.weber = ctypes.sizeof(LuminanceDesc), float(weber)
+    d.row[:] = [float(v) for v in m[[k - 1 for k in classes]].mean(axis=0)]
+    return d
+
+
+def check_edges_options(observer, achromatic=None, channel=None, acuity=None, step=1):
+    """(the luminance desc or None, the channel's name, sigma -- 0.0 without an acuity --, step) after the checks of
+    avx_receptor_edges_u8 that need no device.  channel: "chromatic", "achromatic" or "either"; None is "either" with an achromatic
+    channel, else "chromatic".  acuity: None, a number (check_acuity) or "species" (species_acuity of the observer's name).  ValueError
+    naming the option otherwise."""
+    observer = _check_observer(observer)
+    lum = check_achromatic(observer, achromatic)
+    if channel is None:
+        channel = "chromatic" if lum is None else "either"
+    if channel not in AVX_EDGES_CHANNELS:
+        raise ValueError(f"channel must be one of {', '.join(AVX_EDGES_CHANNELS)} (got {channel!r})")
+    if channel != "chromatic" and lum is None:
+        raise ValueError(f"channel {channel!r} needs achromatic=(classes, weber): without it the observer has no luminance channel")
+    if isinstance(acuity, str):
+        if acuity != "species":
+            raise ValueError(f"acuity must be None, a number of pixels or 'species' (got {acuity!r})")
+        sigma = species_acuity(observer.name)
+    else:
+        sigma = 0.0 if acuity is None else check_acuity(acuity)
+    if isinstance(step, bool) or not isinstance(step, numbers.Integral) or not 1 <= step <= EDGES_MAX_STEP:
+        raise ValueError(f"step must be a whole number of pixels from 1 to {EDGES_MAX_STEP} (got {step!r})")
+    return lum, channel, sigma, int(step)
+
+
+def receptor_edges_launch(ctx: Context, d_in: DeviceBuffer, n_frames: int, H: int, W: int, d_map: Optional[DeviceBuffer], d_rec: DeviceBuffer, *,
+                          observer: Observer, achromatic=None, channel=None, acuity=None, step: int = 1, mode: str = "heat", gain=None,
+                          threshold=DELTA_E_DEFAULT_THRESHOLD, d_float: Optional[DeviceBuffer] = None, stream=None) -> None:
+    """Enqueue avx_receptor_edges_u8 on `stream`: per pixel of n_frames uint8 sRGB frames in d_in the largest receptor-noise-limited
+    contrast, as `observer` sees it, between the pixel and its up to eight neighbours `step` pixels away -- chromatic, achromatic (the
+    luminance channel that `achromatic` names) or either -- behind the acuity blur when there is one.  d_rec takes n_frames records of
+    DELTA_E_RECORD_BYTES; d_map, when not None, n_frames maps of H x W x 3; d_float, when not None, the float32 values.  Nothing is
+    downloaded and nothing waits."""
+    _check_call(n_frames, H, W, d_in, d_in)
+    lum, channel, sigma, step = check_edges_options(observer, achromatic, channel, acuity, step)
+    desc = observer.desc()
+    g, t = _check_delta_e_buffers(n_frames, H, W, d_map, d_rec, d_float, mode, gain, threshold, "map")
+    ctx._check(lib.avx_receptor_edges_u8(ctx._h, d_in.ptr, int(n_frames), int(H), int(W), ctypes.byref(desc), None if lum is None else ctypes.byref(lum),
+                                         AVX_EDGES_CHANNELS[channel], sigma, step, AVX_DELTA_E_MODES[mode], g, t, None if d_map is None else d_map.ptr,
+                                         d_rec.ptr, None if d_float is None else d_float.ptr, ctx._s(stream)))
+
+
+def _check_frames(frames):
+    """uint8 H x W x 3 or N x H x W x 3 -> the contiguous 4-D array and whether a frame axis was given."""
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8:
+        raise ValueError(f"frames are uint8 (got {frames.dtype} {frames.shape})")
+    if frames.ndim not in (3, 4) or frames.shape[-1] != 3 or 0 in frames.shape:
+        raise ValueError(f"expected H x W x 3 or N x H x W x 3 (got {frames.shape})")
+    batched = frames.ndim == 4
+    return np.ascontiguousarray(frames if batched else frames[None]), batched
+
+
+def _edges_chunks(frames, observer, opts, mode, gain, threshold, ctx, with_map, with_float):
+    """receptor_edges, receptor_edges_map and receptor_edges_values: the stack in chunks of at most 16 frames -> (maps or None,
+    records, values or None)."""
+    N, H, W = frames.shape[:3]
+    ctx = ctx or get_context()
+    chunk = min(N, MAX_FRAMES)
+    maps = np.empty((N, H, W, 3), np.uint8) if with_map else None
+    vals = np.empty((N, H, W), np.float32) if with_float else None
+    recs: List[DeltaE] = []
+    bufs = []
+    try:
+        d_in, d_rec = ctx.malloc(chunk * H * W * 3), ctx.malloc(chunk * DELTA_E_RECORD_BYTES)
+        bufs += [d_in, d_rec]
+        d_map = ctx.malloc(chunk * H * W * 3) if with_map else None
+        d_val = ctx.malloc(chunk * H * W * 4) if with_float else None
+        bufs += [d for d in (d_map, d_val) if d is not None]
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            ctx.upload(frames[i : i + n], d_in)
+            receptor_edges_launch(ctx, d_in, n, H, W, d_map, d_rec, observer=observer, mode=mode, gain=gain, threshold=threshold, d_float=d_val, **opts)
+            if with_map:
+                ctx.download(d_map, (n, H, W, 3), np.uint8, out=maps[i : i + n])
+            recs.extend(delta_e_records_from_bytes(ctx.download(d_rec, (n * DELTA_E_RECORD_BYTES,), np.uint8), n))
+            if with_float:
+                ctx.download(d_val, (n, H, W), np.float32, out=vals[i : i + n])
+    finally:
+        for d in bufs:
+            d.free()
+    return maps, recs, vals
+
+
+def _edges_call(frames, observer, achromatic, channel, acuity, step, mode, gain, threshold):
+    """The checks that the three array entries make before any device work."""
+    frames, batched = _check_frames(frames)
+    check_edges_options(observer, achromatic, channel, acuity, step)
+    check_delta_e_options(mode, gain, threshold, "map")
+    return frames, batched, dict(achromatic=achromatic, channel=channel, acuity=acuity, step=step)
+
+
+def receptor_edges(frames, observer: Observer, *, achromatic=None, channel=None, acuity=None, step: int = 1, threshold=DELTA_E_DEFAULT_THRESHOLD,
+                   ctx: Optional[Context] = None):
+    """What stands out to `observer` within a frame: uint8 sRGB H x W x 3 -> the DeltaE record of the per-pixel edge value (the largest
+    contrast to a neighbour `step` pixels away, in just-noticeable differences), or N x H x W x 3 -> a list of N; no map is computed.
+    achromatic=(classes, weber) gives the observer a luminance channel (check_achromatic); channel picks "chromatic", "achromatic" or
+    "either" (the default with a luminance channel; without one, "chromatic"); acuity is None, a sigma in pixels or "species".
+    ValueError for a bad option or shape before any device work."""
+    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, step, "heat", None, threshold)
+    recs = _edges_chunks(frames, observer, opts, "heat", None, threshold, ctx, False, False)[1]
+    return recs if batched else recs[0]
+
+
+def receptor_edges_map(frames, observer: Observer, *, achromatic=None, channel=None, acuity=None, step: int = 1, mode: str = "heat", gain=None,
+                       threshold=DELTA_E_DEFAULT_THRESHOLD, ctx: Optional[Context] = None):
+    """receptor_edges with the picture: (the map, uint8 H x W x 3, its DeltaE record), or (N maps, a list of N records).  mode "heat":
+    the dim grey of the frame where the value is within the threshold, the palette colour of gain x (value - threshold) elsewhere;
+    "plain": the colour of gain x value everywhere."""
+    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, step, mode, gain, threshold)
+    maps, recs, _ = _edges_chunks(frames, observer, opts, mode, gain, threshold, ctx, True, False)
+    return (maps, recs) if batched else (maps[0], recs[0])
+
+
+def receptor_edges_values(frames, observer: Observer, *, achromatic=None, channel=None, acuity=None, step: int = 1,
+                          ctx: Optional[Context] = None) -> np.ndarray:
+    """The edge value of every pixel: float32 H x W or N x H x W."""
+    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, step, "heat", None, DELTA_E_DEFAULT_THRESHOLD)
+    vals = _edges_chunks(frames, observer, opts, "heat", None, DELTA_E_DEFAULT_THRESHOLD, ctx, False, True)[2]
     return vals if batched else vals[0]
 
 

@@ -716,6 +716,65 @@ int avx_receptor_acuity_u8(avx_ctx* ctx, const uint8_t* a_hwc, const uint8_t* b_
                            double sigma, int mode, float gain, float threshold, int layout, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* ds_out,
                            void* stream);
 
+/* Receptor contrast within one frame (csrc/receptor_edges.hip; Local Edge Intensity Analysis, van den Berg et al. 2020:
+ * the third stage of QCPA, behind the two above): per pixel of a batch (1..16) of uint8 sRGB H x W x 3 frames, the largest
+ * receptor-noise-limited contrast between the pixel and its up to eight neighbours at distance D -- what stands out to this observer,
+ * in just-noticeable differences -- as a float32 plane (ds_out), a picture (map_out: H x W x 3 per frame, the only layout) and an
+ * avx_delta_e_rec per frame.  hwc, n_frames, H, W, mode (AVX_DELTA_E_HEAT / _PLAIN), gain, threshold, map_out, rec_dev, ds_out and
+ * stream are avx_delta_e_u8's, with the one input in the place of A; frames of any size from 1 x 1 are legal.
+ *   obs: the observer, avx_receptor_delta_u8's, unchanged: K = 2..4, the same checks, the same constants (R', the weights, rcp, eps).
+ *   lum: the luminance channel, or NULL for none.  row: its sensitivity on linear RGB, entries finite and >= 0, sum > 0; the row is
+ *       divided by its sum in double and rounded to float32 once (L'), like R'.  weber: its Weber fraction e_L, 0.01 <= e_L <= 1;
+ *       1 / e_L is formed in double and rounded to float32 once.
+ *   channel: AVX_EDGES_CHROMATIC (the colour distance dS), AVX_EDGES_ACHROMATIC (the luminance contrast dL) or AVX_EDGES_EITHER (the
+ *       larger of the two); the last two need lum.
+ *   sigma: the observer's acuity; 0 means no blur, otherwise finite and in [0.2, 4] exactly as in avx_receptor_acuity_u8.
+ *   step: D, 1..8, the distance to the neighbours in pixels.
+ * Per pixel p:
+ *   Decode: (r, g, b) = lin[code] with avx_delta_e_u8's 256-entry float32 table.
+ *   Blur (sigma != 0): the three linear planes are blurred exactly as avx_receptor_acuity_u8 blurs a side: the same taps
+ *       (k = cvRound(8 sigma + 1) | 1, formed in double, summed left to right, rounded once), the same plain index-order sums
+ *       s_0 = t_0 x_0, s_j = fma(t_j, x_j, s_(j-1)), rows then columns, the same BORDER_REFLECT_101 folded as often as needed.
+ *   Catches: q_i = (g + R'_i0 (r - g)) + R'_i2 (b - g) for the K classes, and q_L the same form with L'.
+ *   Logarithm, once per pixel: f_i = logf(q_i + eps) and f_L = logf(q_L + eps), the library logf.
+ *   Neighbours: the offsets (+-D, 0), (0, +-D), (+-D, +-D).  A neighbour outside the frame is skipped; it is not reflected.  For a
+ *       neighbour n inside the frame, df_i = f_i(p) - f_i(n), one float32 subtraction; dS(p, n) follows from the df_i by the formulas and
+ *       constants of avx_receptor_delta_u8 (K = 2: |df_1 - df_2| rcp; K = 3, 4: the terms added in the written order, times rcp, then
+ *       the root); dL(p, n) = |f_L(p) - f_L(n)| (1 / e_L); v(p, n) = dS, dL or fmaxf(dS, dL), by channel.
+ *   Value: value(p) = the largest v(p, n) over the neighbours inside the frame; 0 where there are none (H <= D and W <= D).
+ * Everything downstream of the value is avx_delta_e_u8's: the record, the HEAT and PLAIN quantiser and palette, and the dim grey of the
+ * (unfiltered) input where value <= T.
+ * What follows from it, and holds without tolerance:
+ *   v(p, n) = v(n, p) bit for bit: every df changes sign exactly, and the forms are even in the df.
+ *   A flat frame gives an all-zero record and a black PLAIN map.
+ *   A frame of greys has a chromatic value of exactly 0 everywhere, with or without blur: the three blurred planes are equal, so every
+ *       q_i = g~, all f_i are equal and so are all df_i.
+ *   Without blur, transposing or mirroring the frame transposes or mirrors the value plane exactly: f depends on the pixel alone and
+ *       the largest of a set does not depend on its order.
+ *   AVX_EDGES_EITHER is the element-wise larger of the AVX_EDGES_CHROMATIC and AVX_EDGES_ACHROMATIC planes, bit for bit.
+ *   A frame's record, map and values do not depend on its batch, its place in it, the alignment of its buffers or the run.  Counts are
+ *       integers; there are no float atomics; the float64 sum is formed in an order that is a function of H, W and D alone: a
+ *       workgroup of 256 threads works on a block of 64 x 32 pixels and owns the (64 - 2D) x (32 - 2D) pixels of its interior; block
+ *       (i, j) starts at pixel (i (64 - 2D) - D, j (32 - 2D) - D), and there are ceil(W / (64 - 2D)) x ceil(H / (32 - 2D)) of them;
+ *       thread t (column t & 63, rows 8 (t >> 6) .. + 7 of the block) adds its owned pixels inside the frame from the top down; a wave's
+ *       64 threads are folded by halves (lane l += lane l + 32, 16, ... 1), the four waves are added in order, ((w0 + w1) + w2) + w3; the
+ *       blocks' partials, in raster order of the blocks, are added as avx_delta_e_u8's are: thread t of 256 adds partials t, t + 256,
+ *       ..., and the 256 are folded by halves.  8 bytes of workspace a block, no scratch planes.
+ * AVX_ERR_INVALID (avx_last_error starts with this function's name) for everything avx_receptor_delta_u8 refuses (there is no layout),
+ * and for a lum of the wrong struct_size, a negative or non-finite row entry, a row whose sum is 0 or not finite, an e_L outside
+ * [0.01, 1], a channel outside 0..2, AVX_EDGES_ACHROMATIC or _EITHER with a NULL lum, a sigma that is neither 0 nor a finite number in
+ * [0.2, 4], and a step outside 1..8; nothing is launched or written then. */
+enum avx_edges_channel { AVX_EDGES_CHROMATIC = 0, AVX_EDGES_ACHROMATIC = 1, AVX_EDGES_EITHER = 2 };
+typedef struct avx_luminance_desc {
+    uint32_t struct_size;  /* sizeof(avx_luminance_desc) */
+    uint32_t reserved;     /* not read */
+    double row[3];         /* the sensitivity on linear RGB */
+    double weber;          /* e_L */
+} avx_luminance_desc;
+int avx_receptor_edges_u8(avx_ctx* ctx, const uint8_t* hwc, int n_frames, int H, int W, const avx_receptor_desc* obs, const avx_luminance_desc* lum,
+                          int channel, double sigma, int step, int mode, float gain, float threshold, uint8_t* map_out, avx_delta_e_rec* rec_dev,
+                          float* ds_out, void* stream);
+
 /* dE_ITP of ITU-R BT.2124 (csrc/itp.hip): 720 x the Euclidean distance in ICtCp (BT.2100) with Ct halved, about 1 per
  * just-noticeable difference, defined for HDR and SDR light levels alike -- per pixel of two batches of frames, as float32 values, as
  * a picture and as a record per frame, which are avx_delta_e_u8's in every respect but the value.  A side is one of two kinds; any

@@ -1,7 +1,7 @@
-"""Time of the colour difference kernels (DESIGN §4.20, §4.21, §4.25, §4.26).  Not part of bench.py.
+"""Time of the colour difference kernels (DESIGN §4.20, §4.21, §4.25, §4.26, §4.28).  Not part of bench.py.
 
   python tools/deltae_bench.py kernel [--reps 7] [--ppd 60 [--ppd 30 ...]] [--observer Dog [--observer HoneyBee ...]]
-                                      [--acuity species [--acuity 1.0 ...]] [--itp]
+                                      [--acuity species [--acuity 1.0 ...]] [--edges] [--itp]
       avx_delta_e_u8 on frames resident on the device, 4K and 1080p, batches of 8: records only (no map), the heat map, the heat map
       side by side, and records only on a pair whose upper half is identical (those pixels are 0 by definition and skip the
       arithmetic), interleaved in one process with avx_frame_metrics_u8(with_ssim = 1) on the same frames -- per repetition each form
@@ -19,6 +19,11 @@
       heat map; its lines also carry the ratio to the observer's per-pixel records, the taps, and the fused multiply-adds per pixel pair
       of the two blur passes by arithmetic -- 6 planes x k taps x (1 + (32 + 2R) / 32): the column pass, and the row pass on the tile's
       32 rows and its 2R halo rows -- with the rate they imply.
+      --edges adds avx_receptor_edges_u8 on the A frames for every --observer to the same interleaved repetitions,
+      records only: at every --acuity sigma that the observer takes and without blur, at steps 1 and 8, chromatic and either (the
+      luminance channel is the observer's last class at e_L = 0.1; it is a kernel argument and does not change the work); its lines
+      also carry the ratio to avx_receptor_acuity_u8's records at the same sigma (which blurs six planes, this one three) or, without
+      blur, to avx_receptor_delta_u8's, and the blurred pixels per owned pixel by arithmetic, 2048 / ((64 - 2D) (32 - 2D)).
       --itp adds avx_itp_delta to the same interleaved repetitions, records only: p010le PQ against p010le PQ, p010le
       HLG against p010le HLG (noise payloads against the same samples +-2 codes, so every wave does the arithmetic) and the PQ payload
       against the 8-bit frames as an SDR side at 203 nits, and the PQ pair once more with the heat map; its lines also carry the
@@ -57,7 +62,7 @@ def _pair(n, H, W, seed=0):
 def kernel(args):
     from animal_vision_amd.dichromat import cv_auto_ksize
     from animal_vision_amd.metrics import (DELTA_E_RECORD_BYTES, RECORD_BYTES, ItpSide, check_acuity, delta_e_launch, frame_metrics_launch, itp_delta_launch,
-                                           observer_for, receptor_delta_launch, scielab_launch, species_acuity)
+                                           observer_for, receptor_delta_launch, receptor_edges_launch, scielab_launch, species_acuity)
     from animal_vision_amd.runtime import get_context
 
     ctx, n = get_context(), 8
@@ -80,6 +85,10 @@ def kernel(args):
         def blurred(obs, sigma, d_map):
             return lambda: receptor_delta_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, observer=obs, mode="heat", layout="map", acuity=sigma)
 
+        def edges(obs, sigma, step, channel):
+            return lambda: receptor_edges_launch(ctx, d_a, n, H, W, None, d_rec, observer=obs, achromatic=((obs.n_receptors,), 0.1), channel=channel,
+                                                 acuity=sigma or None, step=step)
+
         forms = [("records", route(d_b, None, "map")), ("heat map", route(d_b, d_out, "map")), ("heat side", route(d_b, d_out, "side")),
                  ("records, upper half identical", route(d_half, None, "map"))]
         for ppd in args.ppd or []:
@@ -88,13 +97,18 @@ def kernel(args):
             obs = observer_for(who, (0.13, 0.06, 0.12) if who == "HoneyBee" else (0.05, 0.05))
             forms += [(f"receptor {who} {what}", receptor(obs, d_map, layout))
                       for what, d_map, layout in (("records", None, "map"), ("heat map", d_out, "map"), ("heat side", d_out, "side"))]
+            sigmas = [0.0]
             for text in args.acuity or []:
                 try:
                     sigma = species_acuity(who) if text == "species" else check_acuity(float(text))
                 except ValueError as e:
                     print(f"deltae_bench: --acuity {text} skipped for {who}: {e}", file=sys.stderr)
                     continue
+                sigmas.append(sigma)
                 forms += [(f"acuity {who} sigma {sigma:g} records", blurred(obs, sigma, None)), (f"acuity {who} sigma {sigma:g} heat map", blurred(obs, sigma, d_out))]
+            if args.edges:
+                forms += [(f"edges {who} sigma {sigma:g} step {step} {channel} records", edges(obs, sigma, step, channel))
+                          for sigma in sigmas for step in (1, 8) for channel in ("chromatic", "either")]
         extra = []
         if args.itp:
             rng = np.random.default_rng(1)
@@ -138,6 +152,12 @@ def kernel(args):
                 base = [t2 for (f2, _), t2 in zip(forms, times) if f2 == f"receptor {who} records"][0]
                 line.update(over_receptor_records=round(med / float(np.median(base)), 2), taps=k, blur_fma_per_px=round(fma, 1),
                             blur_tflops=round(2 * fma * H * W / med * 1e-6, 2))
+            if form.startswith("edges"):
+                who, sigma, step = form.split(" ")[1], float(form.split(" ")[3]), int(form.split(" ")[5])
+                pair = f"acuity {who} sigma {sigma:g} records" if sigma else f"receptor {who} records"
+                base = [t2 for (f2, _), t2 in zip(forms, times) if f2 == pair][0]
+                line.update(pair_form=pair, over_pair_records=round(med / float(np.median(base)), 2),
+                            blurred_px_per_owned_px=round(2048 / ((64 - 2 * step) * (32 - 2 * step)), 2))
             if form.startswith("itp"):
                 nbytes = 6.0  # 3 B/px of p010le on either side, or 3 B/px of p010le and 3 B/px of RGB
                 line.update(over_plain_records=round(med / plain, 2), side_bytes_per_px=nbytes, us_per_frame_at_6p29_TBps=round(nbytes * H * W / 6.29e6, 1))
@@ -191,6 +211,8 @@ def main():
                    help="add avx_receptor_delta_u8 for this observer, a dichromat's display name or HoneyBee (repeatable)")
     k.add_argument("--acuity", action="append", default=None, metavar="SIGMA|species",
                    help="add avx_receptor_acuity_u8 at this sigma in pixels, or at each observer's own, for every --observer (repeatable)")
+    k.add_argument("--edges", action="store_true",
+                   help="add avx_receptor_edges_u8 for every --observer: at every --acuity sigma and without blur, steps 1 and 8, chromatic and either")
     k.add_argument("--itp", action="store_true", help="add avx_itp_delta: p010le PQ and HLG pairs, and PQ against an SDR side")
     c = sub.add_parser("command")
     c.add_argument("--frames", type=int, default=32)

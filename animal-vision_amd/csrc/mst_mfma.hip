@@ -25,6 +25,7 @@
 
 #include "avx_internal.h"
 #include "mst_common.h"
+#include "mst_convt_lines.h"
 
 namespace {
 
@@ -1022,6 +1023,282 @@ int launch_convt16(avx_ctx* ctx, avx_ws* ws, const void* x, const void* wpack, c
     return AVX_OK;
 }
 
+// ---- the fused upsampling with whole-line memory accesses ------------------------------------------------------------------------------------
+// k_mst_convt2x2_16<C, NW, true, GRAM>'s products, roundings and Gram epilogue; what changes is how a wave-tile's two skip rows come in and its two
+// output rows go out.  Above, every skip load and every store moves 16 bytes per lane out of every other pixel: 32 (C = 64) or 64 (C = 128) lines
+// addressed per instruction, each line finished by four or eight instructions of two taps.  Here an output row of a wave-tile -- 64 pixels x C bytes,
+// one run in `skip` and in `out` -- crosses in 1 KB pieces, one instruction a piece:
+//   in    LDS-direct loads (inline asm as in csrc/mst_fused.hip::k_mst_down4x4_dma: the compiler would drain vmcnt before every LDS read) into a
+//         wave-private row area; which chunk a lane fetches is permuted (csrc/mst_convt_lines.h) so that the operand reads -- one ds_read_b128 per
+//         tap and step, pixel 2 p + dx -- are conflict-free.  A partial tile clamps its offsets into the run: in-range duplicates, read by no real pixel.
+//   out   the rounded 32 bytes per (tap, t) are written to the same area (its operands are in registers by then), swizzled; the wave reads the run back
+//         with lane l holding chunk 64 i + l and stores 1 KB per instruction; lanes past the row's end repeat its last chunk (the same bytes to the same place).
+// AREAS row areas per wave: with 2 (C = 64; 16 waves, 12 with the epilogue, share one weight image) row dy of the NEXT tile is requested when row dy of
+// this one has been stored, a row's products ahead of its use; with 1 (C = 128, 8 waves, 154 KB) the next row is requested as soon as this one's run
+// has been read back, in front of its stores.  A wave waits for its own loads only: every row is NP loads and NP stores whatever the tile, and s_waitcnt vmcnt(n)
+// leaves outstanding exactly what was issued behind the request it waits for (never more than was issued: that is what makes the count safe).  x is loaded
+// into registers one tile ahead.  Tiles go wave g, g + waves, ... as above, coordinates advancing with carries.  One workgroup per CU: its Gram partial sums
+// the same per-wave sums as k_mst_convt2x2_16's workgroups do, grouped differently.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"  // "m0 is reserved": nothing of the compiler's lives in M0 across this kernel (no indirect register indexing, no LDS-load builtin)
+__device__ __forceinline__ void ln_dma16(const void* base /*the same in every lane*/, unsigned ofs, unsigned lds_base /*the same in every lane*/) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(__builtin_amdgcn_readfirstlane(lds_base)), "v"(ofs), "s"(base) : "memory", "m0");
+}
+#pragma clang diagnostic pop
+template <int C, bool GRAM> struct convt_ln_geom {  // NP = C / 16: the 16-byte chunks of a pixel and, a run being 64 pixels, the 1 KB pieces of a row (mst_convt_lines.h's cpp)
+    static constexpr int NW = C == 128 ? 8 : GRAM ? 12 : 16, AREAS = C == 128 ? 1 : 2, KS = C / 16, CO = C / 2, NT = CO / 32, KSS = CO / 16, HD = NT, NP = C / 16, ROWB = 64 * C;
+    static constexpr int WBYTES = 16 * (4 * NT * KS * 64 + NT * KSS * 64 + (GRAM ? 2 * HD * KSS * 64 : 0)) + 4 * CO;
+    static constexpr int LDS = (WBYTES + 1023) / 1024 * 1024 + 1024 /*the areas start on a 1 KB boundary of the LDS*/ + NW * AREAS * ROWB;
+    static_assert(LDS <= 160 * 1024 && (!GRAM || 4 * NW * HD * 34 * 32 <= LDS), "one workgroup per CU");
+};
+template <int C, int NW_, bool GRAM>
+__global__ __launch_bounds__(64 * NW_, 1) void k_mst_convt2x2_16_ln(const __half* __restrict__ x /*[B][H][W][C]*/, const uint4* __restrict__ wpack /*[4][C/64][C/16][64]*/,
+                                                                  const float* __restrict__ bias /*[C/2]*/, const __half* __restrict__ skip /*[B][2H][2W][C/2]*/,
+                                                                  const uint4* __restrict__ wskip /*[C/64][C/32][64]*/, __half* __restrict__ out /*[B][2H][2W][C/2]*/, int B,
+                                                                  int H, int W, const uint4* __restrict__ wqk /*[2 HD][C/32][64]*/, float* __restrict__ partial /*[blocks][HD][34][32]*/) {
+    using G_ = convt_ln_geom<C, GRAM>;
+    static_assert(NW_ == G_::NW, "the geometry is convt_ln_geom's");
+    constexpr int NW = G_::NW, AREAS = G_::AREAS, KS = G_::KS, CO = G_::CO, NT = G_::NT, KSS = G_::KSS, HD = G_::HD, NP = G_::NP, ROWB = G_::ROWB;
+    using run_t = unsigned __attribute__((ext_vector_type(4 * NP)));
+    using u4_t = unsigned __attribute__((ext_vector_type(4)));
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint4* wl = reinterpret_cast<uint4*>(smem);
+    float* bl = reinterpret_cast<float*>(wl + 4 * NT * KS * 64);
+    uint4* wsl = reinterpret_cast<uint4*>(bl + CO);
+    uint4* wq = wsl + NT * KSS * 64;  // GRAM only
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int i = tid; i < 4 * NT * KS * 64; i += 64 * NW) wl[i] = wpack[i];
+    for (int i = tid; i < CO; i += 64 * NW) bl[i] = bias[i];
+    for (int i = tid; i < NT * KSS * 64; i += 64 * NW) wsl[i] = wskip[i];
+    float16_t G[GRAM ? HD : 1];
+    float nq[GRAM ? HD : 1], nk[GRAM ? HD : 1];
+    if constexpr (GRAM) {
+        for (int i = tid; i < 2 * HD * KSS * 64; i += 64 * NW) wq[i] = wqk[i];
+#pragma unroll
+        for (int hd = 0; hd < HD; ++hd) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) G[hd][v] = 0.f;
+            nq[hd] = 0.f;
+            nk[hd] = 0.f;
+        }
+    }
+    __syncthreads();
+    const int xt = (W + 31) / 32;
+    const unsigned total = (unsigned)B * (unsigned)H * (unsigned)xt;  // < 2^31: the launcher refuses more
+    const int p = lane & 31, h = lane >> 5;
+    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
+    const unsigned a0 = __builtin_amdgcn_readfirstlane(((lds0 + (unsigned)G_::WBYTES + 1023u) & ~1023u) + (unsigned)wave * (AREAS * ROWB));  // this wave's areas, as M0 wants them
+    unsigned char* const area = smem + (a0 - lds0);
+    // this lane's places, fixed for the launch
+    int fo[NP], ob[2][KSS], wb[2][NT][2];
+    const int rb[2] = {convt_ln_out_byte(NP, lane), convt_ln_out_byte(NP, 64 + lane) - 1024};  // read-back of piece i: 1024 i + rb[i & 1] (the swizzle knows i by its parity alone)
+#pragma unroll
+    for (int i = 0; i < NP; ++i) fo[i] = 1024 * i + 16 * convt_ln_skip_chunk(NP, i, lane);
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx) {
+#pragma unroll
+        for (int s = 0; s < KSS; ++s) ob[dx][s] = convt_ln_operand_byte(NP, p, h, dx, s);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            wb[dx][t][0] = convt_ln_out_byte(NP, (2 * p + dx) * NP + 4 * t + 2 * h);
+            wb[dx][t][1] = convt_ln_out_byte(NP, (2 * p + dx) * NP + 4 * t + 2 * h + 1);
+        }
+    }
+    // the walk: tile = (row yb = b H + y of x, column xi), this wave's first one and its stride
+    const unsigned nwaves = gridDim.x * NW, first = blockIdx.x * NW + wave;
+    const int sx = (int)(nwaves % (unsigned)xt), sy = (int)(nwaves / (unsigned)xt);
+    int xi = (int)(first % (unsigned)xt), yb = (int)(first / (unsigned)xt);
+    unsigned tile = first;
+    // row dy of tile (yb, xi): the run's first byte in skip / out, and how many of its 64 C bytes are inside the row
+    auto run_ofs = [&](int yb_, int xi_, int dy) { return ((size_t)(2 * yb_ + dy) * (size_t)(2 * W) + (size_t)(64 * xi_)) * (size_t)C; };
+    auto run_len = [&](int xi_) { const int px = 2 * W - 64 * xi_; return (px < 64 ? px : 64) * C; };
+    auto request = [&](int yb_, int xi_, int dy, int a) {  // NP loads, whatever the tile: the counts of s_waitcnt rest on it
+        const char* base = reinterpret_cast<const char*>(skip) + run_ofs(yb_, xi_, dy);
+        const int last = run_len(xi_) - 16;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) ln_dma16(base, (unsigned)(fo[i] < last ? fo[i] : last), a0 + a * ROWB + i * 1024);
+    };
+    auto load_x = [&](int yb_, int xi_, u4_t (&r)[KS]) {
+        const int xw = 32 * xi_ + p;
+        const u4_t* src = reinterpret_cast<const u4_t*>(x + ((size_t)yb_ * (size_t)W + (size_t)(xw < W ? xw : W - 1)) * C + h * (C / 2));
+#pragma unroll
+        for (int q = 0; q < KS; ++q) r[q] = src[q];
+    };
+    if (tile < total) {
+        u4_t xr[KS];
+        load_x(yb, xi, xr);
+#pragma unroll
+        for (int q = 0; q < KS; ++q) asm volatile("" : "+v"(xr[q]));  // the first x has arrived HERE: left pending into the loop, the wait for it would run in front of every tile and drain the queue
+        request(yb, xi, 0, 0);
+        if constexpr (AREAS == 2) request(yb, xi, 1, 1);
+        // What the counted waits rest on:
+        //   1. every row issues exactly NP LDS-direct loads (request) and exactly NP stores, whatever the tile: partial, last of the walk, or whole;
+        //   2. behind the request a row waits for, at least AREAS * NP of those have been issued when it waits: AREAS == 2: the NP stores of the row before and the
+        //      NP loads of the next request; AREAS == 1: the NP stores of the row before (the request goes in front of them);
+        //   3. anything else in between (the x loads) only makes vmcnt(AREAS * NP) wait for more, never for less: the counter retires in issue order.
+        // The wave's first row has fewer operations behind it, so it is waited for here, outright; from then on every wait is the steady state's.
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AREAS - 1) * NP) : "memory");
+        for (;;) {
+            int nxi = xi + sx, nyb = yb + sy;
+            if (nxi >= xt) { nxi -= xt; ++nyb; }
+            const bool more = tile + nwaves < total && tile + nwaves > tile;
+            if (!more) { nxi = xi; nyb = yb; }  // the last tile requests itself again: valid addresses, the same number of loads
+            const int xw = 32 * xi + p, lastc = run_len(xi) / 16 - 1;
+            u4_t xn[KS];  // the next tile's x, requested a tile ahead: by the time it is used every wait below has long covered it
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy) {
+                unsigned char* const ar = area + (AREAS == 2 ? dy : 0) * ROWB;
+                // (2) above: this row's request has AREAS * NP counted operations behind it
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AREAS * NP) : "memory");
+                if (dy == 0) load_x(nyb, nxi, xn);
+                uint4 sr[2][KSS];
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx)
+#pragma unroll
+                    for (int s = 0; s < KSS; ++s) sr[dx][s] = *reinterpret_cast<const uint4*>(ar + ob[dx][s]);
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    const int tap = 2 * dy + dx;
+                    uint4 og[NT][2];  // the rounded output row: channels 32 t + 16 h + 8 b + j
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        float16_t d;
+#pragma unroll
+                        for (int v = 0; v < 16; ++v) d[v] = 0.f;
+#pragma unroll
+                        for (int s = 0; s < KS; ++s) d = mfma16(__builtin_bit_cast(half8_t, wl[((tap * NT + t) * KS + s) * 64 + lane]), __builtin_bit_cast(half8_t, xr[s]), d);
+#pragma unroll
+                        for (int s = 0; s < KSS; ++s) d = mfma16(__builtin_bit_cast(half8_t, wsl[(t * KSS + s) * 64 + lane]), __builtin_bit_cast(half8_t, sr[dx][s]), d);
+                        half8_t o0, o1;
+#pragma unroll
+                        for (int v = 0; v < 8; ++v) { o0[v] = (_Float16)(d[v] + bl[32 * t + 16 * h + v]); o1[v] = (_Float16)(d[8 + v] + bl[32 * t + 16 * h + 8 + v]); }
+                        *reinterpret_cast<uint4*>(ar + wb[dx][t][0]) = __builtin_bit_cast(uint4, o0);
+                        *reinterpret_cast<uint4*>(ar + wb[dx][t][1]) = __builtin_bit_cast(uint4, o1);
+                        if constexpr (GRAM) {
+#pragma unroll
+                            for (int v = 0; v < 8; ++v) { o0[v] = xw < W ? o0[v] : (_Float16)0.f; o1[v] = xw < W ? o1[v] : (_Float16)0.f; }  // columns past the edge take no part
+                            og[t][0] = __builtin_bit_cast(uint4, o0);
+                            og[t][1] = __builtin_bit_cast(uint4, o1);
+                        }
+                    }
+                    if constexpr (GRAM) {  // as in k_mst_convt2x2_16
+                        half8_t xq[KSS];
+                        if constexpr (NT == 1) {
+                            xq[0] = __builtin_bit_cast(half8_t, og[0][0]);
+                            xq[1] = __builtin_bit_cast(half8_t, og[0][1]);
+                        } else {
+                            unsigned a[8] = {og[0][0].x, og[0][0].y, og[0][0].z, og[0][0].w, og[0][1].x, og[0][1].y, og[0][1].z, og[0][1].w};
+                            unsigned c[8] = {og[1][0].x, og[1][0].y, og[1][0].z, og[1][0].w, og[1][1].x, og[1][1].y, og[1][1].z, og[1][1].w};
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) {
+                                const auto r = __builtin_amdgcn_permlane32_swap(a[i], c[i], false, false);
+                                a[i] = r[0];
+                                c[i] = r[1];
+                            }
+                            xq[0] = __builtin_bit_cast(half8_t, uint4{a[0], a[1], a[2], a[3]});
+                            xq[1] = __builtin_bit_cast(half8_t, uint4{a[4], a[5], a[6], a[7]});
+                            xq[2] = __builtin_bit_cast(half8_t, uint4{c[0], c[1], c[2], c[3]});
+                            xq[3] = __builtin_bit_cast(half8_t, uint4{c[4], c[5], c[6], c[7]});
+                        }
+#pragma unroll
+                        for (int hd = 0; hd < HD; ++hd) {
+                            float16_t dq, dk;
+#pragma unroll
+                            for (int v = 0; v < 16; ++v) { dq[v] = 0.f; dk[v] = 0.f; }
+#pragma unroll
+                            for (int s = 0; s < KSS; ++s) dq = mfma16(xq[s], __builtin_bit_cast(half8_t, wq[(hd * KSS + s) * 64 + lane]), dq);
+#pragma unroll
+                            for (int s = 0; s < KSS; ++s) dk = mfma16(xq[s], __builtin_bit_cast(half8_t, wq[((HD + hd) * KSS + s) * 64 + lane]), dk);
+                            unsigned aq[8], ak[8];
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) {
+                                aq[j] = pack_f16(dq[2 * j], dq[2 * j + 1]);
+                                ak[j] = pack_f16(dk[2 * j], dk[2 * j + 1]);
+                                fma_mix_lo(nq[hd], aq[j], aq[j]); fma_mix_hi(nq[hd], aq[j], aq[j]);
+                                fma_mix_lo(nk[hd], ak[j], ak[j]); fma_mix_hi(nk[hd], ak[j], ak[j]);
+                            }
+#pragma unroll
+                            for (int b2 = 0; b2 < 2; ++b2)
+                                G[hd] = mfma16(__builtin_bit_cast(half8_t, uint4{ak[4 * b2], ak[4 * b2 + 1], ak[4 * b2 + 2], ak[4 * b2 + 3]}),
+                                               __builtin_bit_cast(half8_t, uint4{aq[4 * b2], aq[4 * b2 + 1], aq[4 * b2 + 2], aq[4 * b2 + 3]}), G[hd]);
+                        }
+                    }
+                }
+                // the run as it goes to memory: lane l holds chunk 64 i + l; past the row's end it holds the row's last chunk once more and stores the same bytes to
+                // the same place, so every row is NP stores, taken or not, and the waits above can count them
+                run_t ov;
+                int oc[NP];
+#pragma unroll
+                for (int i = 0; i < NP; ++i) {
+                    const bool in = 64 * i + lane <= lastc;
+                    oc[i] = in ? 64 * i + lane : lastc;
+                    const uint4 v = *reinterpret_cast<const uint4*>(ar + (in ? rb[i & 1] + 1024 * i : convt_ln_out_byte(NP, lastc)));
+                    ov[4 * i] = v.x; ov[4 * i + 1] = v.y; ov[4 * i + 2] = v.z; ov[4 * i + 3] = v.w;
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the area is read out: the next request may land in it
+                unsigned char* const dst = reinterpret_cast<unsigned char*>(out) + run_ofs(yb, xi, dy);
+                // the row to request now: AREAS == 2: row dy of the next tile; AREAS == 1: the next row, in front of this row's stores
+                if constexpr (AREAS == 1) request(dy == 0 ? yb : nyb, dy == 0 ? xi : nxi, dy ^ 1, 0);
+#pragma unroll
+                for (int i = 0; i < NP; ++i)
+                    *reinterpret_cast<uint4*>(dst + 16 * oc[i]) = uint4{ov[4 * i], ov[4 * i + 1], ov[4 * i + 2], ov[4 * i + 3]};
+                if constexpr (AREAS == 2) request(nyb, nxi, dy, dy);
+            }
+#pragma unroll
+            for (int q = 0; q < KS; ++q) asm volatile("" : "+v"(xn[q]));  // taken here, last tile or not: the loads stay where they were written, in front of both rows' stores
+            if (!more) break;
+#pragma unroll
+            for (int q = 0; q < KS; ++q) xr[q] = xn[q];
+            xi = nxi;
+            yb = nyb;
+            tile += nwaves;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last requests land before the area is reused below
+    }
+    if constexpr (GRAM) {  // this workgroup's partial, as in k_mst_convt2x2_16; the weights and the areas in LDS are dead
+        __syncthreads();
+        float* red = reinterpret_cast<float*>(smem);
+#pragma unroll
+        for (int hd = 0; hd < HD; ++hd) {
+            float* mine = red + ((size_t)wave * HD + hd) * 34 * 32;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) mine[(8 * (v / 4) + 4 * h + (v % 4)) * 32 + p] = G[hd][v];
+            const float sq = nq[hd] + __shfl_xor(nq[hd], 32), sk = nk[hd] + __shfl_xor(nk[hd], 32);
+            if (h == 0) { mine[32 * 32 + p] = sq; mine[33 * 32 + p] = sk; }
+        }
+        __syncthreads();
+        for (int i = tid; i < HD * 34 * 32; i += 64 * NW) {
+            float sum = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) sum += red[(size_t)w * HD * 34 * 32 + i];
+            partial[(size_t)blockIdx.x * HD * 34 * 32 + i] = sum;
+        }
+    }
+}
+
+template <int C, bool GRAM>
+int launch_convt16_ln(avx_ctx* ctx, avx_ws* ws, const void* x, const void* wpack, const float* bias, const void* skip, const void* wskip, void* out, int B, int H, int W,
+                      const void* wqk, float* gram, float* nq, float* nk, hipStream_t s) {
+    using G_ = convt_ln_geom<C, GRAM>;
+    const long total = (long)B * H * ((W + 31) / 32);
+    AVX_REQUIRE(ctx, total < 0x7fffffffl && (long)B * H * 2 < 0x7fffffffl, "avx_mst_convt2x2_fuse16_ln: %ld wave-tiles (fewer than 2^31)", total);
+    long blocks = (total + G_::NW - 1) / G_::NW;
+    if (blocks > ctx->num_cus) blocks = ctx->num_cus;
+    float* partial = nullptr;
+    if (GRAM) {
+        int rc = avx_ensure_scratch(ctx, ws, sizeof(float) * (size_t)blocks * G_::HD * 34 * 32);
+        if (rc) return rc;
+        partial = (float*)ws->d_scratch;
+    }
+    auto k = k_mst_convt2x2_16_ln<C, G_::NW, GRAM>;
+    AVX_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G_::LDS));
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * G_::NW), G_::LDS, s, (const __half*)x, (const uint4*)wpack, bias, (const __half*)skip, (const uint4*)wskip, (__half*)out, B,
+                       H, W, (const uint4*)wqk, partial);
+    AVX_HIP(ctx, hipGetLastError());
+    if (GRAM) return avx_mst_qkv_final_launch(ctx, partial, (int)blocks, G_::HD, gram, nq, nk, s);
+    return AVX_OK;
+}
+
 // ---- the same pass on v_mfma_f32_32x32x16_f16 (gfx950's double-rate form) ------------------------------------------------------------------
 // k_mst_qkv above is BOUND by its K = 8 MFMAs (64 cycles each: 144 per 32 pixels at C = 128 is 70 us of matrix-core time per 4K launch at a
 // sixteenth of the pixels, 77 us at C = 64, 93 at C = 32); the K = 16 form does the same products in a quarter of the cycles and leaves
@@ -1447,6 +1724,60 @@ int avx_mst_convt2x2_fuse16_gram(avx_ctx* ctx, const void* x, const void* wpack1
     if (!ws) return AVX_ERR_NOMEM;
     if (C == 64) return launch_convt16<64, true, true>(ctx, ws, x, wpack16, bias, skip, wskip16, out, 1, H, W, wqk16, gram, nq, nk, s);
     return launch_convt16<128, true, true>(ctx, ws, x, wpack16, bias, skip, wskip16, out, 1, H, W, wqk16, gram, nq, nk, s);
+}
+
+// avx_mst_convt2x2_fuse16 (with skip) / avx_mst_convt2x2_fuse16_gram with whole-line memory accesses (k_mst_convt2x2_16_ln): the same arguments, the same `out` to the bit
+int avx_mst_convt2x2_fuse16_ln(avx_ctx* ctx, const void* x, const void* wpack16, const float* bias, const void* skip, const void* wskip16, void* out, int B, int H, int W,
+                               int C, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, x && wpack16 && bias && out && skip && wskip16 && B > 0 && H > 0 && W > 0, "avx_mst_convt2x2_fuse16_ln: NULL pointer or empty tensor");
+    AVX_REQUIRE(ctx, C == 64 || C == 128, "avx_mst_convt2x2_fuse16_ln: C=%d (64 or 128 input channels)", C);
+    AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)wpack16 | (uintptr_t)out | (uintptr_t)skip | (uintptr_t)wskip16)) & 15u) == 0,
+                "avx_mst_convt2x2_fuse16_ln: pointers must be 16-byte aligned");
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    if (C == 64) return launch_convt16_ln<64, false>(ctx, nullptr, x, wpack16, bias, skip, wskip16, out, B, H, W, nullptr, nullptr, nullptr, nullptr, s);
+    return launch_convt16_ln<128, false>(ctx, nullptr, x, wpack16, bias, skip, wskip16, out, B, H, W, nullptr, nullptr, nullptr, nullptr, s);
+}
+
+int avx_mst_convt2x2_fuse16_gram_ln(avx_ctx* ctx, const void* x, const void* wpack16, const float* bias, const void* skip, const void* wskip16, void* out, int H, int W,
+                                    int C, int heads, const void* wqk16, float* gram, float* nq, float* nk, void* stream) {
+    if (!ctx) return AVX_ERR_INVALID;
+    AVX_REQUIRE(ctx, x && wpack16 && bias && skip && wskip16 && out && wqk16 && gram && nq && nk && H > 0 && W > 0, "avx_mst_convt2x2_fuse16_gram_ln: NULL pointer or empty tensor");
+    AVX_REQUIRE(ctx, (C == 64 || C == 128) && heads == C / 64, "avx_mst_convt2x2_fuse16_gram_ln: C=%d, heads=%d (64 or 128 input channels, one head per 32 output channels)", C, heads);
+    AVX_REQUIRE(ctx, ((((uintptr_t)x | (uintptr_t)wpack16 | (uintptr_t)out | (uintptr_t)skip | (uintptr_t)wskip16 | (uintptr_t)wqk16)) & 15u) == 0,
+                "avx_mst_convt2x2_fuse16_gram_ln: pointers must be 16-byte aligned");
+    AVX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = avx_pick_stream(ctx, stream);
+    avx_ws* ws = avx_workspace(ctx, s);
+    if (!ws) return AVX_ERR_NOMEM;
+    if (C == 64) return launch_convt16_ln<64, true>(ctx, ws, x, wpack16, bias, skip, wskip16, out, 1, H, W, wqk16, gram, nq, nk, s);
+    return launch_convt16_ln<128, true>(ctx, ws, x, wpack16, bias, skip, wskip16, out, 1, H, W, wqk16, gram, nq, nk, s);
+}
+
+// Where k_mst_convt2x2_16_ln's bytes sit in a wave's row area (csrc/mst_convt_lines.h, the kernel's own functions run on the host); byte offsets, any array may be NULL:
+//   fetch[i * 64 + l]                          the byte of the row's run that lane l of piece i fetches; it lands at area byte 1024 i + 16 l
+//   operand[(dx * KSS + s) * 64 + lane]        the area byte lane (p, h) reads as its operand of tap dx, step s (KSS = C / 32)
+//   out_write[((dx * NT + t) * 2 + b) * 64 + lane]  the area byte lane (p, h) writes its channels 32 t + 16 h + 8 b ... + 7 of pixel 2 p + dx to (NT = C / 64)
+//   out_read[i * 64 + l]                       the area byte lane l reads back for the run's byte 1024 i + 16 l
+int avx_mst_convt_lines_map(int C, int* fetch, int* operand, int* out_write, int* out_read) {
+    if (C != 64 && C != 128) return AVX_ERR_INVALID;
+    const int np = C / 16, kss = C / 32, nt = C / 64;  // np: chunks per pixel = pieces per row
+    for (int lane = 0; lane < 64; ++lane) {
+        const int p = lane & 31, h = lane >> 5;
+        for (int i = 0; i < np; ++i) {
+            if (fetch) fetch[i * 64 + lane] = 1024 * i + 16 * convt_ln_skip_chunk(np, i, lane);
+            if (out_read) out_read[i * 64 + lane] = convt_ln_out_byte(np, 64 * i + lane);
+        }
+        for (int dx = 0; dx < 2; ++dx) {
+            for (int s = 0; s < kss; ++s)
+                if (operand) operand[(dx * kss + s) * 64 + lane] = convt_ln_operand_byte(np, p, h, dx, s);
+            for (int t = 0; t < nt; ++t)
+                for (int b = 0; b < 2; ++b)
+                    if (out_write) out_write[((dx * nt + t) * 2 + b) * 64 + lane] = convt_ln_out_byte(np, (2 * p + dx) * np + 4 * t + 2 * h + b);
+        }
+    }
+    return AVX_OK;
 }
 
 }  // extern "C"

@@ -247,6 +247,9 @@ class _AvxOps:
         self._convt16 = os.environ.get("AVX_MST_NO_CONVT16", "") == ""  # A/B: the decoder upsampling on K = 16 MFMAs, the C = 64 block's Gram pass as its epilogue (round 12)
         self.CONVT16_C = (64, 128)  # input widths at which the K = 16 kernel measured faster than the K = 8 one, kernel against kernel (profiles/r12/ab_convt16.txt)
         self.CONVT16_GRAM_C = (128,)  # ... and at which it won with the Gram epilogue: at 64 it ties the K = 8 kernel with its epilogue (326.2 against 324.5 us), which stays
+        self._convt_lines = os.environ.get("AVX_MST_NO_CONVT_LINES", "") == ""  # A/B: the fused K = 16 upsampling moves its skip and output rows as whole 1 KB runs through LDS (round 13)
+        self.CONVT_LINES_C = (64, 128)  # input widths at which the whole-line form measured faster than the form routed before it, kernel against kernel (profiles/r13/ab_convt_lines.txt)
+        self.CONVT_LINES_GRAM_C = (64,)  # ... and with the Gram epilogue: 64 moves the full-resolution step from the K = 8 kernel to the K = 16 one (279.5 against 319.8 us); at 128 the ranges overlap (155.8 against 159.7 us) and k_mst_convt2x2_16 stays
         self._ctx = {}
 
     def ctx(self, device: torch.device):
@@ -360,8 +363,10 @@ class _AvxOps:
                                                       wqk16.data_ptr(), g[i].data_ptr(), nq[i].data_ptr(), nk[i].data_ptr(), st))
         return out, g, nq, nk
 
-    def convt2x2_16(self, x: torch.Tensor, wpack16: torch.Tensor, bias: torch.Tensor, skip: torch.Tensor = None, wskip16: torch.Tensor = None) -> torch.Tensor:
-        """convt2x2 on K = 16 MFMAs (csrc/mst_mfma.hip::k_mst_convt2x2_16): wpack16 = the four taps' pack_fragments16(..., halfrow=True), wskip16 likewise."""
+    def convt2x2_16(self, x: torch.Tensor, wpack16: torch.Tensor, bias: torch.Tensor, skip: torch.Tensor = None, wskip16: torch.Tensor = None,
+                    lines: bool = False) -> torch.Tensor:
+        """convt2x2 on K = 16 MFMAs (csrc/mst_mfma.hip::k_mst_convt2x2_16): wpack16 = the four taps' pack_fragments16(..., halfrow=True), wskip16 likewise.
+        lines (with skip): the whole-line form, k_mst_convt2x2_16_ln -- the same output bits."""
         from .._lib import lib
 
         b, h, w, c = x.shape
@@ -371,11 +376,16 @@ class _AvxOps:
         st = torch.cuda.current_stream(x.device).cuda_stream
         if skip is not None:
             assert skip.is_contiguous() and skip.shape == out.shape and wskip16 is not None
+        if lines:
+            assert skip is not None, "the whole-line form is the fused step's"
+            ctx._check(lib.avx_mst_convt2x2_fuse16_ln(ctx._h, x.data_ptr(), wpack16.data_ptr(), bias.data_ptr(), skip.data_ptr(), wskip16.data_ptr(), out.data_ptr(), b, h, w, c, st))
+            return out
         ctx._check(lib.avx_mst_convt2x2_fuse16(ctx._h, x.data_ptr(), wpack16.data_ptr(), bias.data_ptr(), skip.data_ptr() if skip is not None else None,
                                                wskip16.data_ptr() if skip is not None else None, out.data_ptr(), b, h, w, c, st))
         return out
 
-    def convt2x2_16_gram(self, x: torch.Tensor, wpack16: torch.Tensor, bias: torch.Tensor, skip: torch.Tensor, wskip16: torch.Tensor, wqk16: torch.Tensor):
+    def convt2x2_16_gram(self, x: torch.Tensor, wpack16: torch.Tensor, bias: torch.Tensor, skip: torch.Tensor, wskip16: torch.Tensor, wqk16: torch.Tensor,
+                         lines: bool = False):
         """convt2x2_16 with skip / wskip16 and, as its epilogue, the Gram pass of the MSAB block that follows, at c = 64 (one head) or 128 (two);
         wqk16 = pack_qkv16 of the block's qkv weight -> (out, gram (b, heads, 32, 32), nq (b, c / 2), nk (b, c / 2))."""
         from .._lib import lib
@@ -390,9 +400,10 @@ class _AvxOps:
         nk = torch.empty((b, ch), dtype=torch.float32, device=x.device)
         ctx = self.ctx(x.device)
         st = torch.cuda.current_stream(x.device).cuda_stream
+        fn = lib.avx_mst_convt2x2_fuse16_gram_ln if lines else lib.avx_mst_convt2x2_fuse16_gram  # lines: k_mst_convt2x2_16_ln, the same output bits
         for i in range(b):
-            ctx._check(lib.avx_mst_convt2x2_fuse16_gram(ctx._h, x[i].data_ptr(), wpack16.data_ptr(), bias.data_ptr(), skip[i].data_ptr(), wskip16.data_ptr(), out[i].data_ptr(),
-                                                        h, w, c, heads, wqk16.data_ptr(), g[i].data_ptr(), nq[i].data_ptr(), nk[i].data_ptr(), st))
+            ctx._check(fn(ctx._h, x[i].data_ptr(), wpack16.data_ptr(), bias.data_ptr(), skip[i].data_ptr(), wskip16.data_ptr(), out[i].data_ptr(),
+                          h, w, c, heads, wqk16.data_ptr(), g[i].data_ptr(), nq[i].data_ptr(), nk[i].data_ptr(), st))
         return out, g, nq, nk
 
     def posemb(self, v: torch.Tensor, w1_c9: torch.Tensor, w2_c9: torch.Tensor, residual: torch.Tensor = None, bias: torch.Tensor = None) -> torch.Tensor:
@@ -1053,9 +1064,11 @@ class MSTPlusPlus(torch.nn.Module):
                 a2 = f"{p}.decoder_layers.{i}.2.blocks.0.0"
                 # the block's Gram pass rides on this launch: at full resolution on either kernel, at half resolution (two heads) on the K = 16 one
                 cangram = _AVX._convgram and _AVX._qkv16 and _AVX._tail and _AVX._tailx
-                gram16 = cangram and _AVX._convt16 and 2 * ch in _AVX.CONVT16_C and 2 * ch in _AVX.CONVT16_GRAM_C
+                ln_gram = cangram and _AVX._convt16 and _AVX._convt_lines and 2 * ch in _AVX.CONVT_LINES_GRAM_C  # the whole-line K = 16 kernel with the epilogue
+                gram16 = ln_gram or (cangram and _AVX._convt16 and 2 * ch in _AVX.CONVT16_C and 2 * ch in _AVX.CONVT16_GRAM_C)
                 gram8 = cangram and ch == 32 and not gram16
                 k16 = gram16 or (_AVX._convt16 and 2 * ch in _AVX.CONVT16_C and not gram8)  # K = 16 MFMAs, all skip rows requested in front of the products
+                lines = ln_gram or (k16 and not gram16 and _AVX._convt_lines and 2 * ch in _AVX.CONVT_LINES_C)  # ... its skip and output rows as whole 1 KB runs
                 tap = lambda t: (self._w(kw, (0, 1))[:, :, t // 2, t % 2].float() @ wf_[:ch].float()).half().contiguous()  # noqa: E731
                 if k16:
                     gt = self._prep(kw + ".upfuse4k16", lambda: torch.stack([pack_fragments16(tap(t), halfrow=True) for t in range(4)]).contiguous())
@@ -1068,9 +1081,14 @@ class MSTPlusPlus(torch.nn.Module):
                     wqkv2 = self._prep(a2 + ".qkv", lambda: torch.cat([self._w(a2 + ".to_q.weight", (0, 1)), self._w(a2 + ".to_k.weight", (0, 1)),
                                                                        self._w(a2 + ".to_v.weight", (0, 1))], 0).t().contiguous())
                     wqk2 = self._prep(a2 + ".qkv.frag16", lambda: pack_qkv16(wqkv2))  # its q and k tiles are what the epilogue reads
-                    fea, *pre2 = (_AVX.convt2x2_16_gram if gram16 else _AVX.convt2x2_gram)(fea, gt, gb, skips[1 - i].contiguous(), wbot_, wqk2)
+                    if gram16:
+                        fea, *pre2 = _AVX.convt2x2_16_gram(fea, gt, gb, skips[1 - i].contiguous(), wbot_, wqk2, lines=lines)
+                    else:
+                        fea, *pre2 = _AVX.convt2x2_gram(fea, gt, gb, skips[1 - i].contiguous(), wbot_, wqk2)
+                elif k16:
+                    fea = _AVX.convt2x2_16(fea, gt, gb, skips[1 - i].contiguous(), wbot_, lines=lines)
                 else:
-                    fea = (_AVX.convt2x2_16 if k16 else _AVX.convt2x2)(fea, gt, gb, skips[1 - i].contiguous(), wbot_)
+                    fea = _AVX.convt2x2(fea, gt, gb, skips[1 - i].contiguous(), wbot_)
                 fea = self._msab(fea, f"{p}.decoder_layers.{i}.2", heads, tuple(pre2) if pre2 else None)
                 continue
             if _AVX.fused_ok(fea) and fea.shape[-1] in (64, 128):  # four 1x1 products on the matrix cores (kernel size == stride)

@@ -1175,6 +1175,19 @@ int avx_mst_convt2x2_fuse16(avx_ctx* ctx, const void* x, const void* wpack16, co
  * computes them from `out`. */
 int avx_mst_convt2x2_fuse16_gram(avx_ctx* ctx, const void* x, const void* wpack16, const float* bias, const void* skip, const void* wskip16, void* out, int H, int W,
                                  int C, int heads, const void* wqk16, float* gram, float* nq, float* nk, void* stream);
+/* avx_mst_convt2x2_fuse16 (skip and wskip16 given) and avx_mst_convt2x2_fuse16_gram with whole-line memory accesses: a wave-tile's skip rows come in and its
+ * output rows go out as 1 KB runs through a wave-private LDS area (csrc/mst_convt_lines.h) instead of 16 bytes per lane out of every other pixel.  Same
+ * arguments and validation, the same `out` to the bit; the Gram partials are summed over other workgroups (one workgroup per CU), so gram / nq / nk agree
+ * with avx_mst_convt2x2_fuse16_gram's up to the order of the float32 sums. */
+int avx_mst_convt2x2_fuse16_ln(avx_ctx* ctx, const void* x, const void* wpack16, const float* bias, const void* skip, const void* wskip16, void* out, int B, int H,
+                               int W, int C, void* stream);
+int avx_mst_convt2x2_fuse16_gram_ln(avx_ctx* ctx, const void* x, const void* wpack16, const float* bias, const void* skip, const void* wskip16, void* out, int H,
+                                    int W, int C, int heads, const void* wqk16, float* gram, float* nq, float* nk, void* stream);
+/* Where that kernel's bytes sit in a wave's row area, from the kernel's own functions run on the host (C = 64 or 128; byte offsets; any array may be NULL):
+ * fetch[i * 64 + l]: the byte of the row's run that lane l of 1 KB piece i fetches (it lands at area byte 1024 i + 16 l); operand[(dx * C/32 + s) * 64 + lane]:
+ * the area byte lane (p, h) reads as its operand of tap dx, step s; out_write[((dx * C/64 + t) * 2 + b) * 64 + lane]: the area byte the lane writes its channels
+ * 32 t + 16 h + 8 b ... + 7 of pixel 2 p + dx to; out_read[i * 64 + l]: the area byte lane l reads back for the run's byte 1024 i + 16 l. */
+int avx_mst_convt_lines_map(int C, int* fetch, int* operand, int* out_write, int* out_read);
 
 /* nn.Conv2d(C, C, 3, 1, 1, groups=C, bias=False) on a channels-last (B,H,W,C) tensor (pos_emb :104-106,
  * FeedForward :147), float32 accumulate; w_c9: C x 9 float32 (weight.reshape(C, 9)); gelu_out: exact-erf GELU. */

@@ -1,4 +1,5 @@
-"""The decoder upsampling kernels on K = 16 MFMAs against the K = 8 ones, kernel against kernel.  Not part of bench.py.
+"""The decoder upsampling kernels on K = 16 MFMAs against the K = 8 ones, and the whole-line K = 16 form (round 13) against both, kernel against kernel
+(DESIGN §4.3).  Not part of bench.py.
 
   timeout -k 10 300 python tools/mst_convt16_ab.py --out ab.jsonl
 
@@ -20,6 +21,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=60)
     ap.add_argument("--out", default=None, help="also write the JSON lines here")
+    ap.add_argument("--forms", default=None, help="comma-separated forms to launch (default: all): a counter pass or a trace of a few kernels without the others' launches in it")
     args = ap.parse_args()
 
     import torch
@@ -55,7 +57,15 @@ def main():
             "k16_fuse": lambda: _AVX.convt2x2_16(x, p16, bias, skip, s16),
             "k8_fuse+gram": k8_gram,
             "k16_fuse_gram": lambda: _AVX.convt2x2_16_gram(x, p16, bias, skip, s16, wqk)[0],
+            "k16_fuse_ln": lambda: _AVX.convt2x2_16(x, p16, bias, skip, s16, lines=True),  # round 13: skip and output rows as whole 1 KB runs through LDS
+            "k16_fuse_gram_ln": lambda: _AVX.convt2x2_16_gram(x, p16, bias, skip, s16, wqk, lines=True)[0],
         }
+        if args.forms:
+            want = args.forms.split(",")
+            unknown = [k for k in want if k not in forms]
+            if unknown:
+                raise SystemExit(f"mst_convt16_ab: unknown form(s) {unknown}; known: {sorted(forms)}")
+            forms = {k: f for k, f in forms.items() if k in want}
         for f in forms.values():
             for _ in range(5):
                 f()

@@ -269,6 +269,16 @@ class LuminanceDesc(ctypes.Structure):
 AVX_EDGES_CHANNELS = {"chromatic": 0, "achromatic": 1, "either": 2}  # enum avx_edges_channel
 
 
+class SmoothDesc(ctypes.Structure):
+    """avx_smooth_desc (include/avx.h)."""
+
+    _fields_ = [("struct_size", ctypes.c_uint32), ("radius", ctypes.c_int32), ("keep", ctypes.c_double), ("iterations", ctypes.c_int32),
+                ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(SmoothDesc) == 24
+
+
 class ItpSide(ctypes.Structure):
     """avx_itp_side (include/avx.h)."""
 
@@ -434,6 +444,8 @@ _SIGS = {
                                _vp, _vp]),
     "avx_receptor_edges_u8": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), ctypes.POINTER(LuminanceDesc), _i, ctypes.c_double, _i, _i,
                                ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "avx_receptor_edges_smooth_u8": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(ReceptorDesc), ctypes.POINTER(LuminanceDesc), _i, ctypes.c_double, _i,
+                                      ctypes.POINTER(SmoothDesc), _i, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
     "avx_itp_delta": (_i, [_vp, ctypes.POINTER(ItpSide), ctypes.POINTER(ItpSide), ctypes.c_double, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i, _vp,
                            _vp, _vp, _vp]),
     "avx_remap_linear_planes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp]),

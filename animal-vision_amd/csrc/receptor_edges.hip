@@ -3,8 +3,10 @@
 // pixel and its up to eight neighbours at distance D, chromatic (receptor.hip's dS), achromatic (the Weber contrast of a luminance
 // channel) or the larger of the two, behind the observer's acuity blur (receptor_acuity.hip's).  The quadratic form and the catch are
 // receptor_common.h's; the record's share, the map's quantiser and colours and the host side's checks and launch frame are
-// delta_e_common.h's: one copy of each.  The blur passes are a second copy of receptor_acuity.hip's, statement for statement: moved to
-// a shared header they compile k_receptor_acuity to other instructions (registers and schedule), and that kernel is pinned.
+// delta_e_common.h's; the block geometry, the reflection and the host's checks of the channel, sigma and step are
+// receptor_edges_common.h's, shared with receptor_smooth.hip: one copy of each.  The blur passes are a second copy of
+// receptor_acuity.hip's, statement for statement: moved to a shared header they compile k_receptor_acuity to other instructions
+// (registers and schedule), and that kernel is pinned.
 //
 // k_receptor_edges<K, CHROMA, LUMA>: grid (blocks, frames); a workgroup of 256 threads blurs a kBlockW x kBlockH = 64 x 32 block of
 // one frame and owns the block's interior, (64 - 2D) x (32 - 2D) pixels: blocks are pitched by the owned size, block (i, j) starts at
@@ -27,25 +29,9 @@
 
 #include "delta_e_common.h"
 #include "receptor_common.h"
+#include "receptor_edges_common.h"
 
 namespace {
-
-constexpr int kBlockW = 64, kBlockH = 32, kPer = 8;  // a thread: column tid & 63, rows (tid >> 6) * 8 ...
-constexpr int kMaxRad = (AVX_MAX_KSIZE - 1) / 2;     // 16
-constexpr int kTapFront = 3;                         // zero taps in front of t_0
-constexpr int kTapSlots = 40;                        // 3 + 33 taps, and the zeros the last group of four reads
-constexpr int kPadRows = 4;                          // zero rows below the row-pass result, for the last group of the column pass
-constexpr int kMaxStep = 8;
-constexpr int kPlane = kBlockW * kBlockH;            // floats of a plane of log-catches
-static_assert(kBlockW * kBlockH == kThreads * kPer && kBlockW == 64 && kThreads == 256, "block geometry");
-static_assert(4 * ((2 * kMaxRad + 3) / 4) + 6 < kTapSlots && kTapFront + 4 * ((2 * kMaxRad + 4) / 4) - 1 < kTapSlots, "tap slots");
-static_assert(kPadRows * kBlockW == kThreads, "one pad word a thread");
-static_assert(2 * kMaxStep < kBlockH, "a block owns pixels at every step");
-
-// the luminance channel as the kernel takes it: columns 0 and 2 of the normalised row, and 1 / e_L
-struct LumArgs {
-    float r0, r2, rcp;
-};
 
 struct EdArgs {
     const uint8_t* in;
@@ -55,18 +41,6 @@ struct EdArgs {
     LumArgs l;
     DeOut o;              // partials: [frame][block]
 };
-
-// BORDER_REFLECT_101, folded as often as needed: n = 1 gives 0
-__device__ __forceinline__ long long fold101(long long i, long long n) {
-    if (n == 1) return 0;
-    const long long p = 2 * (n - 1);
-    long long m = i % p;
-    m = m < 0 ? m + p : m;
-    return m < n ? m : p - m;
-}
-
-// the blur's dynamic LDS in floats: the tile [rows][span], then the row-pass result [rows + kPadRows][64]
-constexpr size_t blur_floats(int R) { return (size_t)(kBlockH + 2 * R) * ((kBlockW + 2 * R + 3) & ~3) + (size_t)(kBlockH + 2 * R + kPadRows) * kBlockW; }
 
 // six waves a SIMD: at most 80 registers (the kernels take 63), so that the small radii run as many workgroups as their LDS admits
 template <int K, bool CHROMA, bool LUMA>
@@ -243,36 +217,10 @@ extern "C" int avx_receptor_edges_u8(avx_ctx* ctx, const uint8_t* hwc, int n_fra
     RnlArgs c;
     int K;
     if (const int rc = rnl_constants(ctx, fn, obs, c, K)) return rc;
-    AVX_REQUIRE(ctx, channel == AVX_EDGES_CHROMATIC || channel == AVX_EDGES_ACHROMATIC || channel == AVX_EDGES_EITHER, "%s: bad channel %d", fn, channel);
-    AVX_REQUIRE(ctx, lum || channel == AVX_EDGES_CHROMATIC, "%s: channel %d needs the luminance channel (lum is NULL)", fn, channel);
     EdArgs p = {};
-    if (lum) {
-        AVX_REQUIRE(ctx, lum->struct_size == sizeof(avx_luminance_desc), "%s: lum struct_size mismatch (ABI %d)", fn, AVX_ABI_VERSION);
-        const double* row = lum->row;
-        AVX_REQUIRE(ctx, std::isfinite(row[0]) && std::isfinite(row[1]) && std::isfinite(row[2]) && row[0] >= 0.0 && row[1] >= 0.0 && row[2] >= 0.0,
-                    "%s: the luminance row must be finite and not negative (got %g %g %g)", fn, row[0], row[1], row[2]);
-        const double sum = row[0] + row[1] + row[2];
-        AVX_REQUIRE(ctx, sum > 0.0 && std::isfinite(sum), "%s: the luminance row sums to %g, it must be above 0 and finite", fn, sum);
-        AVX_REQUIRE(ctx, lum->weber >= 0.01 && lum->weber <= 1.0, "%s: the luminance Weber fraction must be from 0.01 to 1 (got %g)", fn, lum->weber);
-        p.l = {(float)(row[0] / sum), (float)(row[2] / sum), (float)(1.0 / lum->weber)};
-    }
-    AVX_REQUIRE(ctx, sigma == 0.0 || (std::isfinite(sigma) && sigma >= 0.2 && sigma <= 4.0),
-                "%s: sigma must be 0 (no blur) or a finite number from 0.2 to 4 (got %g)", fn, sigma);
-    AVX_REQUIRE(ctx, step >= 1 && step <= kMaxStep, "%s: step must be 1..%d (got %d)", fn, kMaxStep, step);
-    const int ksize = sigma == 0.0 ? 1 : (int)lrint(sigma * 8.0 + 1.0) | 1;  // cvRound: half to even
-    AVX_REQUIRE(ctx, ksize >= 1 && ksize <= AVX_MAX_KSIZE, "%s: sigma %g needs %d taps, 3 .. %d are supported", fn, sigma, ksize, AVX_MAX_KSIZE);
-
-    // ---- the taps: cv::getGaussianKernel(ksize, sigma) in double, summed left to right, rounded once; no blur is the one tap 1 ----
-    if (ksize == 1) {
-        p.tp[kTapFront] = 1.0f;
-    } else {
-        const double scale2x = -0.5 / (sigma * sigma), mid = (ksize - 1) * 0.5;
-        double t[AVX_MAX_KSIZE], sum = 0.0;
-        for (int i = 0; i < ksize; ++i) sum += t[i] = exp(scale2x * (i - mid) * (i - mid));
-        const double scale = 1.0 / sum;
-        for (int i = 0; i < ksize; ++i) p.tp[kTapFront + i] = (float)(t[i] * scale);
-    }
-    const int R = (ksize - 1) / 2, D = step;
+    int R;
+    if (const int rc = edges_check(ctx, fn, lum, channel, sigma, step, p.l, p.tp, R)) return rc;
+    const int D = step;
     const size_t own_w = kBlockW - 2 * D, own_h = kBlockH - 2 * D;
     const size_t blocks_x = ((size_t)W + own_w - 1) / own_w, blocks = blocks_x * (((size_t)H + own_h - 1) / own_h);  // below 2^31
     hipStream_t s;

@@ -24,6 +24,14 @@ the Weber fractions: there is no per-species table (`--observer Dog --achromatic
 --achromatic 3:0.12` the Green receptor).  --channel chromatic|achromatic|either picks dS, the achromatic contrast or the larger of
 the two; the default is either with --achromatic, else chromatic.  The pixel's value is the largest over its neighbours.
 
+--smooth RADIUS:KEEP[:ITERATIONS] puts an edge-preserving smoothing in receptor space in front of the edges, so that
+sensor and compression noise, which is exactly a contrast to a neighbour, does not light the map up everywhere: every pixel's
+log-catches are averaged with those pixels of the (2 RADIUS + 1)^2 window (RADIUS 1..5) that look alike to the observer -- the
+bandwidth is twice the distance to the pixel that ranks at the share KEEP (above 0, at most 1) of the window, and the weights taper to
+zero there -- ITERATIONS times (1..8, default 1).  It stands where QCPA has its RNL ranked filter; the definition is this project's own
+(micaToolbox's weights could not be pinned), and there is no default for RADIUS or KEEP.  The smoothing uses the channel of the edges,
+so with it `either` is no longer the larger of the two single-channel results.
+
 Without OUT no map is computed: one CSV line per frame goes to stdout, or to --csv FILE.  With OUT -- any sink form of `video` -- one
 map is written per frame, encoded on the device for .y4m and raw sinks, and the CSV goes only to --csv.  --mode, --gain and --threshold
 are `deltae`'s: heat (the default) shows the dim grey of the frame where the value is within T (default 1, one just-noticeable
@@ -41,8 +49,8 @@ import numpy as np
 
 from .deltae import CSV_HEADER, format_row
 from .metrics import (DELTA_E_DEFAULT_GAIN, DELTA_E_DEFAULT_THRESHOLD, DELTA_E_MODES, DELTA_E_RECORD_BYTES, EDGES_CHANNELS, EDGES_MAX_STEP,
-                      RECEPTOR_DEFAULT_FLOOR, DeltaE, check_delta_e_options, check_edges_options, delta_e_records_from_bytes, observer_for,
-                      observer_names, receptor_edges_launch)
+                      RECEPTOR_DEFAULT_FLOOR, SMOOTH_MAX_ITERATIONS, SMOOTH_MAX_RADIUS, DeltaE, check_delta_e_options, check_edges_options,
+                      delta_e_records_from_bytes, observer_for, observer_names, receptor_edges_launch)
 from .pairs import Side, check_depth, copy, named_size, num, open_sink, open_source, opened, out_matrix, sink_format
 from .runtime import get_context
 from .video import add_input_options, add_output_options, check_io_options, check_raw_options
@@ -64,6 +72,26 @@ class _EdgesParser(argparse.ArgumentParser):
             if not 1 <= k <= K:
                 self.error(f"--achromatic: class {k} is not one of {args.observer}'s receptor classes 1..{K}")
         return classes, weber
+
+    def _smooth(self, args):
+        """(radius, keep, iterations) of --smooth RADIUS:KEEP[:ITERATIONS], or None without it."""
+        if args.smooth is None:
+            return None
+        try:
+            parts = args.smooth.split(":")
+            if len(parts) not in (2, 3):
+                raise ValueError
+            radius, keep, iterations = int(parts[0]), float(parts[1]), int(parts[2]) if len(parts) == 3 else 1
+        except ValueError:
+            self.error(f"--smooth: RADIUS:KEEP[:ITERATIONS] with RADIUS and ITERATIONS whole numbers and KEEP a share of the window, e.g. 3:0.5:2 "
+                       f"(got {args.smooth!r})")
+        if not 1 <= radius <= SMOOTH_MAX_RADIUS:
+            self.error(f"--smooth: RADIUS must be 1..{SMOOTH_MAX_RADIUS} pixels (got {radius})")
+        if not 0.0 < keep <= 1.0:  # a nan is neither
+            self.error(f"--smooth: KEEP must be above 0 and at most 1 (got {keep:g})")
+        if not 1 <= iterations <= SMOOTH_MAX_ITERATIONS:
+            self.error(f"--smooth: ITERATIONS must be 1..{SMOOTH_MAX_ITERATIONS} (got {iterations})")
+        return radius, keep, iterations
 
     def parse_args(self, args=None, namespace=None):
         args = super().parse_args(args, namespace)
@@ -109,6 +137,10 @@ class _EdgesParser(argparse.ArgumentParser):
         except ValueError as e:
             self.error(f"--achromatic / --acuity: {e}")
         args.observer, args.achromatic, args.acuity = observer, achromatic, (None if acuity is None else sigma)
+        if args.smooth is None:
+            del args.smooth  # without --smooth the namespace is what it was
+        else:
+            args.smooth = self._smooth(args)
         check_io_options(self, args)
         check_raw_options(self, args)
         src = named_size(args, args.input)
@@ -143,6 +175,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="blur the frame in linear light by the observer's acuity, a Gaussian of SIGMA pixels (0.2 to 4), before the contrasts are "
                          "taken.  `species`: the blur the species' own rendering ends with.  Default: none")
     ap.add_argument("--step", type=int, default=1, metavar="D", help=f"the distance to the eight neighbours in pixels, 1..{EDGES_MAX_STEP} (default 1)")
+    ap.add_argument("--smooth", default=None, metavar="RADIUS:KEEP[:ITERATIONS]",
+                    help=f"smooth the log-catches in front of the edges, keeping the edges: average every pixel with the share KEEP (above 0, at most "
+                         f"1) of its (2 RADIUS + 1)^2 window (RADIUS 1..{SMOOTH_MAX_RADIUS}) that looks most like it to the observer, ITERATIONS times "
+                         f"(1..{SMOOTH_MAX_ITERATIONS}, default 1).  The project's stand-in for QCPA's RNL ranked filter.  Default: none")
     ap.add_argument("--mode", default=None, choices=list(DELTA_E_MODES),
                     help="heat (default): a dim grey of the frame where the value is within --threshold, a black-red-yellow-white colour of "
                          "G (value - T) where it is not.  plain: the colour of G value everywhere")
@@ -169,6 +205,9 @@ def describe(args) -> str:
         parts.append(f"channel {args.channel}")
     if args.acuity is not None:
         parts.append(f"acuity {args.acuity:g} px")
+    smooth = getattr(args, "smooth", None)
+    if smooth is not None:
+        parts.append(f"smooth {smooth[0]}:{smooth[1]:g}x{smooth[2]}")
     parts.append(f"step {args.step}")
     return ", ".join(parts)
 
@@ -225,7 +264,7 @@ def stream_records(args, info: dict, fmt: Optional[str] = None) -> Iterator[Tupl
                 side.enqueue(k, n, streams[k])
                 receptor_edges_launch(ctx, side.d_rgb[k], n, H, W, d_out[k][0] if with_map else None, d_out[k][-1], observer=args.observer,
                                       achromatic=args.achromatic, channel=args.channel, acuity=args.acuity, step=args.step, mode=args.mode,
-                                      gain=args.gain, threshold=args.threshold, stream=streams[k])
+                                      gain=args.gain, threshold=args.threshold, stream=streams[k], smooth=getattr(args, "smooth", None))
                 if encode is not None:
                     encode.launch(ctx, d_out[k][0], d_out[k][1], n, H, W, streams[k])
                 for (nbytes, _), d, h in zip(outputs, d_out[k], h_out[k]):

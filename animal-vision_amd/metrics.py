@@ -41,8 +41,9 @@ any mix; itp_delta_launch, itp_delta, itp_delta_map and itp_delta_values return 
 Receptor contrast within a frame (csrc/receptor_edges.hip; Local Edge Intensity Analysis, van den Berg et al. 2020) takes
 one input: per pixel the largest receptor-noise-limited contrast to its up to eight neighbours `step` pixels away, behind the acuity
 blur -- chromatic, achromatic (a luminance channel: achromatic=(classes, weber)) or either.  receptor_edges_launch, receptor_edges,
-receptor_edges_map and receptor_edges_values return the same DeltaE records, maps and value planes; python -m animal_vision_amd.edges
-is the command."""
+receptor_edges_map and receptor_edges_values return the same DeltaE records, maps and value planes; smooth=(radius, keep[, iterations])
+puts the edge-preserving smoothing of csrc/receptor_smooth.hip in front of the edges and receptor_smooth_planes returns the
+smoothed planes; python -m animal_vision_amd.edges is the command."""
 from __future__ import annotations
 
 import ctypes
@@ -57,7 +58,7 @@ from ._lib import AVX_DELTA_E_LAYOUTS, AVX_DELTA_E_MODES, AVX_DIFF_LAYOUTS, AVX_
 from ._lib import DeltaERecord as DeltaERecordStruct
 from ._lib import DiffRecord as DiffRecordStruct
 from ._lib import ItpSide as ItpSideStruct
-from ._lib import AVX_EDGES_CHANNELS, LuminanceDesc, ReceptorDesc
+from ._lib import AVX_EDGES_CHANNELS, LuminanceDesc, ReceptorDesc, SmoothDesc
 from .runtime import Context, DeviceBuffer, get_context
 
 MAX_FRAMES = AVX_METRICS_MAX_FRAMES
@@ -1086,11 +1087,37 @@ def check_achromatic(observer: Observer, achromatic) -> Optional[LuminanceDesc]:
     return d
 
 
-def check_edges_options(observer, achromatic=None, channel=None, acuity=None, step=1):
+SMOOTH_MAX_RADIUS, SMOOTH_MAX_ITERATIONS = 5, 8
+
+
+def check_smooth(smooth) -> Optional[SmoothDesc]:
+    """smooth -- None, or (radius, keep[, iterations = 1]): the edge-preserving smoothing in receptor space in front of the edges
+    (avx_receptor_edges_smooth_u8): the window reaches `radius` pixels (1..5) each way, a pixel is averaged with about the
+    share `keep` (above 0, at most 1) of its window that looks most like it, `iterations` times (0..8; 0 takes the planes route and
+    smooths nothing) -- as the avx_smooth_desc the library takes.  ValueError naming it otherwise."""
+    if smooth is None:
+        return None
+    try:
+        radius, keep, *rest = smooth
+        (iterations,) = rest or (1,)
+    except (TypeError, ValueError):
+        raise ValueError(f"smooth must be (radius, keep) or (radius, keep, iterations), e.g. (3, 0.5, 2) (got {smooth!r})") from None
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Integral) or not 1 <= radius <= SMOOTH_MAX_RADIUS:
+        raise ValueError(f"smooth radius must be a whole number of pixels from 1 to {SMOOTH_MAX_RADIUS} (got {radius!r})")
+    if not _real(keep) or not (math.isfinite(keep) and 0.0 < keep <= 1.0):
+        raise ValueError(f"smooth keep must be a number above 0 and at most 1 (got {keep!r})")
+    if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral) or not 0 <= iterations <= SMOOTH_MAX_ITERATIONS:
+        raise ValueError(f"smooth iterations must be a whole number from 0 to {SMOOTH_MAX_ITERATIONS} (got {iterations!r})")
+    d = SmoothDesc()
+    d.struct_size, d.radius, d.keep, d.iterations = ctypes.sizeof(SmoothDesc), int(radius), float(keep), int(iterations)
+    return d
+
+
+def check_edges_options(observer, achromatic=None, channel=None, acuity=None, step=1, smooth=None):
     """(the luminance desc or None, the channel's name, sigma -- 0.0 without an acuity --, step) after the checks of
     avx_receptor_edges_u8 that need no device.  channel: "chromatic", "achromatic" or "either"; None is "either" with an achromatic
-    channel, else "chromatic".  acuity: None, a number (check_acuity) or "species" (species_acuity of the observer's name).  ValueError
-    naming the option otherwise."""
+    channel, else "chromatic".  acuity: None, a number (check_acuity) or "species" (species_acuity of the observer's name).  smooth: None
+    or what check_smooth takes; it is checked and not returned.  ValueError naming the option otherwise."""
     observer = _check_observer(observer)
     lum = check_achromatic(observer, achromatic)
     if channel is None:
@@ -1107,21 +1134,43 @@ def check_edges_options(observer, achromatic=None, channel=None, acuity=None, st
         sigma = 0.0 if acuity is None else check_acuity(acuity)
     if isinstance(step, bool) or not isinstance(step, numbers.Integral) or not 1 <= step <= EDGES_MAX_STEP:
         raise ValueError(f"step must be a whole number of pixels from 1 to {EDGES_MAX_STEP} (got {step!r})")
+    check_smooth(smooth)
     return lum, channel, sigma, int(step)
+
+
+def edges_planes(observer: Observer, channel: str) -> int:
+    """P, the planes of log-catches a channel works on: the K receptor planes for "chromatic", the luminance plane for "achromatic",
+    K + 1 for "either"."""
+    return (0 if channel == "achromatic" else observer.n_receptors) + (0 if channel == "chromatic" else 1)
 
 
 def receptor_edges_launch(ctx: Context, d_in: DeviceBuffer, n_frames: int, H: int, W: int, d_map: Optional[DeviceBuffer], d_rec: DeviceBuffer, *,
                           observer: Observer, achromatic=None, channel=None, acuity=None, step: int = 1, mode: str = "heat", gain=None,
-                          threshold=DELTA_E_DEFAULT_THRESHOLD, d_float: Optional[DeviceBuffer] = None, stream=None) -> None:
+                          threshold=DELTA_E_DEFAULT_THRESHOLD, d_float: Optional[DeviceBuffer] = None, stream=None, smooth=None,
+                          d_planes: Optional[DeviceBuffer] = None) -> None:
     """Enqueue avx_receptor_edges_u8 on `stream`: per pixel of n_frames uint8 sRGB frames in d_in the largest receptor-noise-limited
     contrast, as `observer` sees it, between the pixel and its up to eight neighbours `step` pixels away -- chromatic, achromatic (the
     luminance channel that `achromatic` names) or either -- behind the acuity blur when there is one.  d_rec takes n_frames records of
-    DELTA_E_RECORD_BYTES; d_map, when not None, n_frames maps of H x W x 3; d_float, when not None, the float32 values.  Nothing is
-    downloaded and nothing waits."""
+    DELTA_E_RECORD_BYTES; d_map, when not None, n_frames maps of H x W x 3; d_float, when not None, the float32 values.  smooth: None,
+    or (radius, keep[, iterations]) -- check_smooth -- for avx_receptor_edges_smooth_u8: the edge-preserving smoothing in receptor space
+    in front of the edges; d_planes, which needs it, takes the smoothed planes, n_frames x P x H x W float32 (edges_planes(observer,
+    channel) says P).  Nothing is downloaded and nothing waits."""
     _check_call(n_frames, H, W, d_in, d_in)
     lum, channel, sigma, step = check_edges_options(observer, achromatic, channel, acuity, step)
+    sm = check_smooth(smooth)
     desc = observer.desc()
     g, t = _check_delta_e_buffers(n_frames, H, W, d_map, d_rec, d_float, mode, gain, threshold, "map")
+    if sm is None and d_planes is not None:
+        raise ValueError("d_planes takes the smoothed planes: it needs smooth=(radius, keep[, iterations])")
+    if sm is not None:
+        need = n_frames * edges_planes(observer, channel) * H * W * 4
+        if d_planes is not None and d_planes.nbytes < need:
+            raise ValueError(f"d_planes holds {d_planes.nbytes} bytes, the planes need {need}")
+        ctx._check(lib.avx_receptor_edges_smooth_u8(ctx._h, d_in.ptr, int(n_frames), int(H), int(W), ctypes.byref(desc), None if lum is None else ctypes.byref(lum),
+                                                    AVX_EDGES_CHANNELS[channel], sigma, step, ctypes.byref(sm), AVX_DELTA_E_MODES[mode], g, t,
+                                                    None if d_map is None else d_map.ptr, d_rec.ptr, None if d_float is None else d_float.ptr,
+                                                    None if d_planes is None else d_planes.ptr, ctx._s(stream)))
+        return
     ctx._check(lib.avx_receptor_edges_u8(ctx._h, d_in.ptr, int(n_frames), int(H), int(W), ctypes.byref(desc), None if lum is None else ctypes.byref(lum),
                                          AVX_EDGES_CHANNELS[channel], sigma, step, AVX_DELTA_E_MODES[mode], g, t, None if d_map is None else d_map.ptr,
                                          d_rec.ptr, None if d_float is None else d_float.ptr, ctx._s(stream)))
@@ -1138,14 +1187,16 @@ def _check_frames(frames):
     return np.ascontiguousarray(frames if batched else frames[None]), batched
 
 
-def _edges_chunks(frames, observer, opts, mode, gain, threshold, ctx, with_map, with_float):
-    """receptor_edges, receptor_edges_map and receptor_edges_values: the stack in chunks of at most 16 frames -> (maps or None,
-    records, values or None)."""
+def _edges_chunks(frames, observer, opts, mode, gain, threshold, ctx, with_map, with_float, with_planes=False):
+    """receptor_edges, receptor_edges_map, receptor_edges_values and receptor_smooth_planes: the stack in chunks of at most 16 frames ->
+    (maps or None, records, values or None, planes or None)."""
     N, H, W = frames.shape[:3]
     ctx = ctx or get_context()
     chunk = min(N, MAX_FRAMES)
     maps = np.empty((N, H, W, 3), np.uint8) if with_map else None
     vals = np.empty((N, H, W), np.float32) if with_float else None
+    P = edges_planes(observer, check_edges_options(observer, opts["achromatic"], opts["channel"])[1]) if with_planes else 0
+    planes = np.empty((N, P, H, W), np.float32) if with_planes else None
     recs: List[DeltaE] = []
     bufs = []
     try:
@@ -1153,58 +1204,75 @@ def _edges_chunks(frames, observer, opts, mode, gain, threshold, ctx, with_map, 
         bufs += [d_in, d_rec]
         d_map = ctx.malloc(chunk * H * W * 3) if with_map else None
         d_val = ctx.malloc(chunk * H * W * 4) if with_float else None
-        bufs += [d for d in (d_map, d_val) if d is not None]
+        d_pl = ctx.malloc(chunk * P * H * W * 4) if with_planes else None
+        bufs += [d for d in (d_map, d_val, d_pl) if d is not None]
         for i in range(0, N, chunk):
             n = min(chunk, N - i)
             ctx.upload(frames[i : i + n], d_in)
-            receptor_edges_launch(ctx, d_in, n, H, W, d_map, d_rec, observer=observer, mode=mode, gain=gain, threshold=threshold, d_float=d_val, **opts)
+            receptor_edges_launch(ctx, d_in, n, H, W, d_map, d_rec, observer=observer, mode=mode, gain=gain, threshold=threshold, d_float=d_val,
+                                  d_planes=d_pl, **opts)
             if with_map:
                 ctx.download(d_map, (n, H, W, 3), np.uint8, out=maps[i : i + n])
             recs.extend(delta_e_records_from_bytes(ctx.download(d_rec, (n * DELTA_E_RECORD_BYTES,), np.uint8), n))
             if with_float:
                 ctx.download(d_val, (n, H, W), np.float32, out=vals[i : i + n])
+            if with_planes:
+                ctx.download(d_pl, (n, P, H, W), np.float32, out=planes[i : i + n])
     finally:
         for d in bufs:
             d.free()
-    return maps, recs, vals
+    return maps, recs, vals, planes
 
 
-def _edges_call(frames, observer, achromatic, channel, acuity, step, mode, gain, threshold):
+def _edges_call(frames, observer, achromatic, channel, acuity, step, mode, gain, threshold, smooth=None):
     """The checks that the three array entries make before any device work."""
     frames, batched = _check_frames(frames)
-    check_edges_options(observer, achromatic, channel, acuity, step)
+    check_edges_options(observer, achromatic, channel, acuity, step, smooth)
     check_delta_e_options(mode, gain, threshold, "map")
-    return frames, batched, dict(achromatic=achromatic, channel=channel, acuity=acuity, step=step)
+    return frames, batched, dict(achromatic=achromatic, channel=channel, acuity=acuity, step=step, smooth=smooth)
 
 
 def receptor_edges(frames, observer: Observer, *, achromatic=None, channel=None, acuity=None, step: int = 1, threshold=DELTA_E_DEFAULT_THRESHOLD,
-                   ctx: Optional[Context] = None):
+                   smooth=None, ctx: Optional[Context] = None):
     """What stands out to `observer` within a frame: uint8 sRGB H x W x 3 -> the DeltaE record of the per-pixel edge value (the largest
     contrast to a neighbour `step` pixels away, in just-noticeable differences), or N x H x W x 3 -> a list of N; no map is computed.
     achromatic=(classes, weber) gives the observer a luminance channel (check_achromatic); channel picks "chromatic", "achromatic" or
     "either" (the default with a luminance channel; without one, "chromatic"); acuity is None, a sigma in pixels or "species".
-    ValueError for a bad option or shape before any device work."""
-    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, step, "heat", None, threshold)
+    smooth=(radius, keep[, iterations]) puts the edge-preserving smoothing of DESIGN §4.29 in front of the edges (check_smooth): the
+    project's stand-in for QCPA's RNL ranked filter; it smooths in the channel of the edges, so "either" is then no longer the larger of
+    the two single-channel results.  ValueError for a bad option or shape before any device work."""
+    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, step, "heat", None, threshold, smooth)
     recs = _edges_chunks(frames, observer, opts, "heat", None, threshold, ctx, False, False)[1]
     return recs if batched else recs[0]
 
 
 def receptor_edges_map(frames, observer: Observer, *, achromatic=None, channel=None, acuity=None, step: int = 1, mode: str = "heat", gain=None,
-                       threshold=DELTA_E_DEFAULT_THRESHOLD, ctx: Optional[Context] = None):
+                       threshold=DELTA_E_DEFAULT_THRESHOLD, smooth=None, ctx: Optional[Context] = None):
     """receptor_edges with the picture: (the map, uint8 H x W x 3, its DeltaE record), or (N maps, a list of N records).  mode "heat":
     the dim grey of the frame where the value is within the threshold, the palette colour of gain x (value - threshold) elsewhere;
-    "plain": the colour of gain x value everywhere."""
-    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, step, mode, gain, threshold)
-    maps, recs, _ = _edges_chunks(frames, observer, opts, mode, gain, threshold, ctx, True, False)
+    "plain": the colour of gain x value everywhere.  With smooth the dim grey is still the unfiltered frame's."""
+    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, step, mode, gain, threshold, smooth)
+    maps, recs = _edges_chunks(frames, observer, opts, mode, gain, threshold, ctx, True, False)[:2]
     return (maps, recs) if batched else (maps[0], recs[0])
 
 
-def receptor_edges_values(frames, observer: Observer, *, achromatic=None, channel=None, acuity=None, step: int = 1,
+def receptor_edges_values(frames, observer: Observer, *, achromatic=None, channel=None, acuity=None, step: int = 1, smooth=None,
                           ctx: Optional[Context] = None) -> np.ndarray:
     """The edge value of every pixel: float32 H x W or N x H x W."""
-    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, step, "heat", None, DELTA_E_DEFAULT_THRESHOLD)
+    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, step, "heat", None, DELTA_E_DEFAULT_THRESHOLD, smooth)
     vals = _edges_chunks(frames, observer, opts, "heat", None, DELTA_E_DEFAULT_THRESHOLD, ctx, False, True)[2]
     return vals if batched else vals[0]
+
+
+def receptor_smooth_planes(frames, observer: Observer, *, achromatic=None, channel=None, acuity=None, smooth, ctx: Optional[Context] = None) -> np.ndarray:
+    """The planes of log-catches the edges are taken on, after the smoothing (iterations 0: before it): float32 P x H x W, or
+    N x P x H x W -- the K receptor planes for "chromatic", the luminance plane for "achromatic", the K and then the luminance plane for
+    "either".  smooth is required: (radius, keep[, iterations])."""
+    if smooth is None:
+        raise ValueError("smooth must be (radius, keep) or (radius, keep, iterations): receptor_smooth_planes returns the smoothed planes")
+    frames, batched, opts = _edges_call(frames, observer, achromatic, channel, acuity, 1, "heat", None, DELTA_E_DEFAULT_THRESHOLD, smooth)
+    planes = _edges_chunks(frames, observer, opts, "heat", None, DELTA_E_DEFAULT_THRESHOLD, ctx, False, False, with_planes=True)[3]
+    return planes if batched else planes[0]
 
 
 # ------------------------------------------------------------------------------------------------ dE_ITP (DESIGN §4.27)

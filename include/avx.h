@@ -775,6 +775,58 @@ int avx_receptor_edges_u8(avx_ctx* ctx, const uint8_t* hwc, int n_frames, int H,
                           int channel, double sigma, int step, int mode, float gain, float threshold, uint8_t* map_out, avx_delta_e_rec* rec_dev,
                           float* ds_out, void* stream);
 
+/* avx_receptor_edges_u8 with an edge-preserving smoothing in receptor space in front of the neighbour contrasts (csrc/receptor_smooth.hip,
+ * DESIGN §4.29): every pixel is averaged with the pixels of a window that look alike to the observer, `iterations` times, and the
+ * edges are taken on the result.  It stands where QCPA (van den Berg et al. 2020) has its RNL ranked filter, in front of Local Edge
+ * Intensity Analysis; the definition below is this project's own -- micaToolbox's weights are not restated here -- and differs from a
+ * plain rank cut-off on purpose: the rank sets the bandwidth and the weights taper to zero at it, so the output is a continuous
+ * function of the frame and a float32 device can be held to a float64 statement of it with no pixel exempted.
+ *   Every argument of avx_receptor_edges_u8 means what it means there.
+ *   smooth: radius R, 1..5; keep KEEP, finite, 0 < KEEP <= 1; iterations ITER, 0..8.  ITER = 0 launches no smoothing: the values, the map
+ *       and the record are avx_receptor_edges_u8's byte for byte (the float64 sum included: the block pitch is the same).
+ *   planes_out: NULL, or n_frames x P x H x W float32 ([frame][plane][H][W]) that take the smoothed planes.
+ * The planes: f = the P planes of log-catches avx_receptor_edges_u8 forms per pixel (decode, blur, catches, logf(q + eps), once per
+ * pixel, to the bit): the K receptor planes for AVX_EDGES_CHROMATIC, the one luminance plane for AVX_EDGES_ACHROMATIC, the K and then
+ * the luminance plane for AVX_EDGES_EITHER.  v(p, n) is the pair value of the channel exactly as above.  One iteration replaces every
+ * pixel p of every plane at once, reading only the planes of the iteration before:
+ *   Window: W(p) = the pixels n inside the frame with |dx| <= R and |dy| <= R, p included; N = |W(p)|.  A pixel outside the frame is
+ *       skipped, not reflected.
+ *   Rank: m = ceil(KEEP N), formed on the host in double for every N = 1 .. 121 and passed to the kernel as a table; the device takes
+ *       no ceil of its own.
+ *   Bandwidth: t = the m-th smallest of { v(p, n) : n in W(p) }; the pixel's own 0 is the first.  t is exactly one of the values.
+ *   Weights: h = t + t.  h = 0: w_n = 1 where v(p, n) = 0, else 0.  Otherwise rh = 1 / h (one division per pixel), u = v(p, n) rh,
+ *       a = 1 - u u and w_n = a a where u < 1, else 0.  w_p = 1 always, so the sum of the weights is at least 1.
+ *   Update: f'(p) = f(p) + (sum of w_n (f(n) - f(p))) / (sum of w_n), per plane: both sums start at 0 and run over the window in raster
+ *       order (dy outer, dx inner), s = s + w_n (f(n) - f(p)); float32 throughout, no fused multiply-add, one division per plane and
+ *       pixel.
+ * After ITER iterations value(p) is the largest v(p, n) over the eight neighbours at distance D, on the smoothed planes, and the record
+ * and the map follow as above.  The smoothing uses the channel of the edges, so with ITER > 0 AVX_EDGES_EITHER is no longer the
+ * element-wise larger of the two single-channel results.
+ * What follows from it, and holds without tolerance:
+ *   Identical values are a fixed point: a flat frame keeps its planes bit for bit, its record is all zero and its PLAIN map black.
+ *   A frame of greys keeps K bit-equal receptor planes through every iteration: its chromatic value stays exactly 0.
+ *   Where at least m pixels of every window share the pixel's own log-catches (KEEP <= 0.5 and two flat colours with a straight seam at
+ *       least R pixels from the frame's sides), t = 0, only those pixels weigh, every difference is 0 and the planes do not change.
+ *   A frame's record, map, values and planes do not depend on its batch, its place in it, the alignment of its buffers or the run.
+ * Launches and scratch: a batch is walked in groups of frames; a group's planes lie in the workspace twice (8 P bytes a pixel, at most
+ * 40) behind the 8 bytes a block of the record's partials, and a group is as many frames as keep that at or below 1 GiB, at least one.
+ * Per group: one launch forms the planes, one launch per iteration smooths them from one set into the other, one launch takes the
+ * neighbour contrasts with avx_receptor_edges_u8's blocks and order of partials.
+ * AVX_ERR_INVALID (avx_last_error starts with this function's name) for everything avx_receptor_edges_u8 refuses, a smooth that is NULL
+ * or of the wrong struct_size, a radius outside 1..5, a keep that is not finite or not in (0, 1], iterations outside 0..8, and a
+ * planes_out that is not 4-byte aligned or overlaps the input; nothing is launched or written then. */
+typedef struct avx_smooth_desc {
+    uint32_t struct_size;  /* sizeof(avx_smooth_desc) */
+    int32_t radius;        /* R */
+    double keep;           /* KEEP */
+    int32_t iterations;    /* ITER */
+    uint32_t reserved;     /* not read */
+} avx_smooth_desc;
+int avx_receptor_edges_smooth_u8(avx_ctx* ctx, const uint8_t* hwc, int n_frames, int H, int W, const avx_receptor_desc* obs,
+                                 const avx_luminance_desc* lum, int channel, double sigma, int step, const avx_smooth_desc* smooth, int mode,
+                                 float gain, float threshold, uint8_t* map_out, avx_delta_e_rec* rec_dev, float* ds_out, float* planes_out,
+                                 void* stream);
+
 /* dE_ITP of ITU-R BT.2124 (csrc/itp.hip): 720 x the Euclidean distance in ICtCp (BT.2100) with Ct halved, about 1 per
  * just-noticeable difference, defined for HDR and SDR light levels alike -- per pixel of two batches of frames, as float32 values, as
  * a picture and as a record per frame, which are avx_delta_e_u8's in every respect but the value.  A side is one of two kinds; any

@@ -1,7 +1,7 @@
-"""Time of the colour difference kernels (DESIGN §4.20, §4.21, §4.25, §4.26, §4.28).  Not part of bench.py.
+"""Time of the colour difference kernels (DESIGN §4.20, §4.21, §4.25, §4.26, §4.28, §4.29).  Not part of bench.py.
 
   python tools/deltae_bench.py kernel [--reps 7] [--ppd 60 [--ppd 30 ...]] [--observer Dog [--observer HoneyBee ...]]
-                                      [--acuity species [--acuity 1.0 ...]] [--edges] [--itp]
+                                      [--acuity species [--acuity 1.0 ...]] [--edges [--smooth R:KEEP:ITER ...]] [--itp]
       avx_delta_e_u8 on frames resident on the device, 4K and 1080p, batches of 8: records only (no map), the heat map, the heat map
       side by side, and records only on a pair whose upper half is identical (those pixels are 0 by definition and skip the
       arithmetic), interleaved in one process with avx_frame_metrics_u8(with_ssim = 1) on the same frames -- per repetition each form
@@ -24,6 +24,11 @@
       luminance channel is the observer's last class at e_L = 0.1; it is a kernel argument and does not change the work); its lines
       also carry the ratio to avx_receptor_acuity_u8's records at the same sigma (which blurs six planes, this one three) or, without
       blur, to avx_receptor_delta_u8's, and the blurred pixels per owned pixel by arithmetic, 2048 / ((64 - 2D) (32 - 2D)).
+      Each --smooth R:KEEP:ITER (with --edges) adds avx_receptor_edges_smooth_u8 beside every step-1 edges form, on
+      the same frames in the same repetitions, and once per such form the same entry with ITER = 0 (the planes route without a
+      smoothing launch: the front and the back kernel); its lines also carry the ratio to the fused edges form, and the time of one
+      smoothing launch as (this form - the ITER = 0 form) / ITER.  The frames are noise: no window holds m exact zeros, so every pixel
+      runs the whole selection.
       --itp adds avx_itp_delta to the same interleaved repetitions, records only: p010le PQ against p010le PQ, p010le
       HLG against p010le HLG (noise payloads against the same samples +-2 codes, so every wave does the arithmetic) and the PQ payload
       against the 8-bit frames as an SDR side at 203 nits, and the PQ pair once more with the heat map; its lines also carry the
@@ -59,6 +64,11 @@ def _pair(n, H, W, seed=0):
     return a, b
 
 
+def _smooth(text):
+    r, keep, it = text.split(":")
+    return int(r), float(keep), int(it)
+
+
 def kernel(args):
     from animal_vision_amd.dichromat import cv_auto_ksize
     from animal_vision_amd.metrics import (DELTA_E_RECORD_BYTES, RECORD_BYTES, ItpSide, check_acuity, delta_e_launch, frame_metrics_launch, itp_delta_launch,
@@ -85,9 +95,9 @@ def kernel(args):
         def blurred(obs, sigma, d_map):
             return lambda: receptor_delta_launch(ctx, d_a, d_b, n, H, W, d_map, d_rec, observer=obs, mode="heat", layout="map", acuity=sigma)
 
-        def edges(obs, sigma, step, channel):
+        def edges(obs, sigma, step, channel, smooth=None):
             return lambda: receptor_edges_launch(ctx, d_a, n, H, W, None, d_rec, observer=obs, achromatic=((obs.n_receptors,), 0.1), channel=channel,
-                                                 acuity=sigma or None, step=step)
+                                                 acuity=sigma or None, step=step, smooth=smooth)
 
         forms = [("records", route(d_b, None, "map")), ("heat map", route(d_b, d_out, "map")), ("heat side", route(d_b, d_out, "side")),
                  ("records, upper half identical", route(d_half, None, "map"))]
@@ -109,6 +119,11 @@ def kernel(args):
             if args.edges:
                 forms += [(f"edges {who} sigma {sigma:g} step {step} {channel} records", edges(obs, sigma, step, channel))
                           for sigma in sigmas for step in (1, 8) for channel in ("chromatic", "either")]
+                for sigma in sigmas if args.smooth else []:
+                    for channel in ("chromatic", "either"):
+                        forms.append((f"smooth {who} sigma {sigma:g} step 1 {channel} 1:1:0 records", edges(obs, sigma, 1, channel, (1, 1.0, 0))))
+                        forms += [(f"smooth {who} sigma {sigma:g} step 1 {channel} {sm[0]}:{sm[1]:g}:{sm[2]} records", edges(obs, sigma, 1, channel, sm))
+                                  for sm in args.smooth]
         extra = []
         if args.itp:
             rng = np.random.default_rng(1)
@@ -158,6 +173,15 @@ def kernel(args):
                 base = [t2 for (f2, _), t2 in zip(forms, times) if f2 == pair][0]
                 line.update(pair_form=pair, over_pair_records=round(med / float(np.median(base)), 2),
                             blurred_px_per_owned_px=round(2048 / ((64 - 2 * step) * (32 - 2 * step)), 2))
+            if form.startswith("smooth"):
+                head, setting = form.rsplit(" ", 2)[0], form.split(" ")[-2]
+                fused = [t2 for (f2, _), t2 in zip(forms, times) if f2 == "edges" + head[len("smooth"):] + " records"][0]
+                line.update(over_fused_edges=round(med / float(np.median(fused)), 2))
+                iterations = int(setting.rsplit(":", 1)[1])
+                if iterations:
+                    bare = [t2 for (f2, _), t2 in zip(forms, times) if f2 == f"{head} 1:1:0 records"][0]
+                    line.update(front_and_back_us_per_frame=round(float(np.median(bare)), 1),
+                                smooth_us_per_frame_and_iteration=round((med - float(np.median(bare))) / iterations, 1))
             if form.startswith("itp"):
                 nbytes = 6.0  # 3 B/px of p010le on either side, or 3 B/px of p010le and 3 B/px of RGB
                 line.update(over_plain_records=round(med / plain, 2), side_bytes_per_px=nbytes, us_per_frame_at_6p29_TBps=round(nbytes * H * W / 6.29e6, 1))
@@ -213,6 +237,8 @@ def main():
                    help="add avx_receptor_acuity_u8 at this sigma in pixels, or at each observer's own, for every --observer (repeatable)")
     k.add_argument("--edges", action="store_true",
                    help="add avx_receptor_edges_u8 for every --observer: at every --acuity sigma and without blur, steps 1 and 8, chromatic and either")
+    k.add_argument("--smooth", action="append", default=None, metavar="R:KEEP:ITER", type=_smooth,
+                   help="with --edges: add avx_receptor_edges_smooth_u8 at this setting beside every step-1 edges form (repeatable)")
     k.add_argument("--itp", action="store_true", help="add avx_itp_delta: p010le PQ and HLG pairs, and PQ against an SDR side")
     c = sub.add_parser("command")
     c.add_argument("--frames", type=int, default=32)
